@@ -277,6 +277,28 @@ def build_roofline(args, sc, work, stats, level0_rays, kern, alone, ms_per_step,
     return roof
 
 
+DUMP_BUDGET_BYTES = 60_000_000          # the frame's arrays; with the ray counts and the .npy headers the dump stays under 64 MB
+
+
+def dump_outputs(directory, fb_rgb, fb_packed, stats, H, W):
+    """--dump-outputs: what a caller of the timed path receives from its last step (Renderer.render's rgb, packed and ray counts) as
+    DIR/<name>.npy in float32 / float64, so that two builds can be compared output for output.  packed holds 0x00RRGGBB words, exact in
+    float64.  A frame over the budget (1920x1080: 41 MB, whole) is cut to a fixed, seeded sample of pixels, the same for every run at the
+    same --width / --height (pixel_index.npy: their raster indices).  Returns {name: shape} of what was written."""
+    rgb = fb_rgb.cpu().numpy().reshape(H * W, 3)
+    packed = fb_packed.cpu().numpy().view(np.uint32).astype(np.float64)
+    arrays = {"ray_counts": np.array([stats[k] for k in ("primary", "shadow", "reflection", "refraction")], np.float64)}
+    if H * W * (rgb.itemsize * 3 + packed.itemsize) > DUMP_BUDGET_BYTES:
+        n = DUMP_BUDGET_BYTES // (rgb.itemsize * 3 + packed.itemsize + 8)
+        idx = np.sort(np.random.default_rng(0x5EED0003).choice(H * W, n, replace=False))
+        arrays.update(pixel_index=idx.astype(np.float64), rgb=rgb[idx], packed=packed[idx])
+    else:
+        arrays.update(rgb=rgb.reshape(H, W, 3), packed=packed.reshape(H, W))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
 
 def launch_plan(n_gpus, argv, master_port=None, env=None):
     """`python bench.py --gpus N` without a launcher around it: the ranks this process will start, one fresh process per GPU (what
@@ -350,7 +372,10 @@ def main():
     ap.add_argument("--overlap", action="store_true", help="force the two-stream intra-frame overlap even with several frames in flight")
     ap.add_argument("--no-kernel-timing", action="store_true", help="A/B: no HIP events around the launches of the timed region (roofline fields become null)")
     ap.add_argument("--cull", action="store_true", help="time with RTX_RENDER_CULL_DEAD_SHADOW_RAYS as the main figure (default: reported as an extra)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the frame and ray counts of the last timed step as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1")
 
     # `python bench.py --gpus N` on its own brings up its N ranks itself; under torch.distributed.run (WORLD_SIZE set) it IS one of the ranks
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -482,6 +507,11 @@ def main():
         ktimes += sl.r.kernel_times()
         sl.r.enable_timing(False)
     frames_with_events = sum(1 for f in range(first_timed_frame, first_timed_frame + args.steps) if f % nfl == 0)
+    # the last timed step's outputs, read before the extras below render into the framebuffers again
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        last = slots[(frame_no[0] - 1) % nfl]
+        dumped = dump_outputs(args.dump_outputs, last.fb_rgb, last.fb_packed, last.r.stats()[0], H, W)
     # extras (not the headline): (a) the same pipeline with dead shadow rays counted but not traversed; (b) one frame at a time
     t_cull = t_single = None
     if world == 1 and not args.cull and not args.simple_trace and gather is None and not args.no_extras:
@@ -548,6 +578,8 @@ def main():
             "extra_cull_dead_shadow_rays": None if t_cull is None else {"ms_per_step": round(t_cull, 4), "note": "RTX_RENDER_CULL_DEAD_SHADOW_RAYS: identical frame and ray counts; shadow rays with an exactly-zero light contribution are counted but not traversed"},
             "roofline": roof,
         }
+        if dumped:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         # ---- CPU baseline: the oracle (port of the reference's lane-1 path) on this box's host cores ------
         if world == 1 and args.cpu_seconds > 0:
             sys.path.insert(0, os.path.join(REPO, "oracle"))

@@ -80,3 +80,36 @@ def test_roofline_arithmetic_on_known_inputs(monkeypatch):
     assert abs(pk["k_trace_closest"]["frac"] - units_c / 0.8e-3 * 1e-9 / 2000.0) < 1e-3
     assert abs(pk["k_trace_any"]["frac"] - units_a / 0.5e-3 * 1e-9 / 2000.0) < 1e-3            # packet launch + item launch, alone
     assert pk["k_shade"]["bound"] == "hbm" and abs(pk["k_shade"]["frac"] - bench.shade_bytes(work, stats, 3) / 0.25e-3 / 8e12) < 1e-4
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs on host tensors: a frame within the budget is written whole; a larger one as a seeded pixel sample that is the
+    same from call to call, with the raster index of every sampled pixel."""
+    sys.path.insert(0, REPO)
+    import numpy as np
+    import torch
+    import bench
+    H, W = 6, 10
+    rng = np.random.default_rng(1)
+    rgb = torch.from_numpy(rng.random(H * W * 3, dtype=np.float32))
+    packed = torch.from_numpy(rng.integers(0, 2**32, H * W, dtype=np.uint32).view(np.int32))
+    stats = {"primary": 60, "shadow": 7, "reflection": 3, "refraction": 1}
+
+    def load(d, shapes):
+        return {n: np.load(tmp_path / d / f"{n}.npy") for n in shapes}
+
+    shapes = bench.dump_outputs(str(tmp_path / "whole"), rgb, packed, stats, H, W)
+    assert shapes == {"ray_counts": [4], "rgb": [H, W, 3], "packed": [H, W]}
+    a = load("whole", shapes)
+    assert a["rgb"].dtype == np.float32 and np.array_equal(a["rgb"].ravel(), rgb.numpy())
+    assert a["packed"].dtype == np.float64 and np.array_equal(a["packed"].astype(np.uint32).ravel(), packed.numpy().view(np.uint32))
+    assert a["ray_counts"].dtype == np.float64 and a["ray_counts"].tolist() == [60, 7, 3, 1]
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 20 * (12 + 8 + 8))             # room for 20 of the 60 pixels (rgb, packed, index)
+    b, c = (load(d, bench.dump_outputs(str(tmp_path / d), rgb, packed, stats, H, W)) for d in ("sample_1", "sample_2"))
+    assert set(b) == {"ray_counts", "rgb", "packed", "pixel_index"} and b["rgb"].shape == (20, 3) and b["packed"].shape == (20,)
+    assert all(np.array_equal(b[n], c[n]) for n in b)
+    assert sum(x.nbytes for n, x in b.items() if n != "ray_counts") <= bench.DUMP_BUDGET_BYTES
+    idx = b["pixel_index"].astype(np.int64)
+    assert len(set(idx.tolist())) == 20 and np.array_equal(b["rgb"], rgb.numpy().reshape(-1, 3)[idx])
+    assert np.array_equal(b["packed"], packed.numpy().view(np.uint32)[idx].astype(np.float64))

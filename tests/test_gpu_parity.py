@@ -175,6 +175,23 @@ def test_bench_gather_path_on_one_gpu():
     assert j["rays_per_frame"]["total"] == 57600 + 191709 + 52955 + 12692
 
 
+def test_bench_dump_outputs_is_the_reference_frame(tmp_path):
+    """bench.py --dump-outputs: the last timed step's frame (three frames in flight, so not the first context's) and ray counts, as float
+    arrays, equal the reference's golden of the same scene (identical, as in test_frame_matches_reference_golden)."""
+    import json, os, subprocess, sys
+    out = subprocess.run([sys.executable, os.path.join(util.REPO, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1", "--workload", "materials",
+                          "--cpu-seconds", "0", "--no-extras", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    j = json.loads(out.stdout.strip().splitlines()[-1])
+    assert j["steps"] == 5 and j["ms_per_step"] > 0 and set(j["dumped_outputs"]["arrays"]) == {"rgb", "packed", "ray_counts"}
+    rgb, packed, counts = (np.load(tmp_path / f"{n}.npy") for n in ("rgb", "packed", "ray_counts"))
+    assert rgb.dtype == np.float32 and packed.dtype == np.float64 and counts.dtype == np.float64
+    _, g = util.load_golden("materials_aniso")
+    dumped = {"rgb": rgb, "packed": packed.astype(np.uint32), "stats": dict(zip(("primary", "shadow", "reflection", "refraction"), counts.astype(np.int64)))}
+    c = util.compare_to_golden(dumped, g)
+    assert c["stats_equal"] and c["nan_mismatch"] == 0 and c["max_abs"] == 0.0 and c["n_diff_pixels"] == 0 and c["packed_mismatch"] == 0, c
+
+
 @pytest.mark.parametrize("name", ["monkey_small_heat", "materials_heat"])
 def test_heatmap_mode_is_bit_exact(api, name):
     """BVH_VISUALIZE_HEATMAP: integer step counts times powers of two, so the frame must equal the reference's bit for bit;
