@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 #include <algorithm>
+#include <type_traits>
 
 #include "../../include/rtx.h"
 #include "rtx_device.h"
@@ -91,6 +92,14 @@ struct rtx_ctx {
     int stage_next = 0;
     DevScene scene;
     bool frame_set = false;
+    // rtx_set_views: the cameras of a batch of views (device array, grown only, filled by a stream-ordered copy from a ring of pinned
+    // staging buffers like the frame block) and the view framebuffer (view_fb_cap views, allocated on first use, grown only) or the
+    // caller's buffers of ext_vcap views (rtx_bind_view_framebuffer)
+    DevBuf d_views, d_vfb_rgb, d_vfb_packed;
+    FrameStage vstage[3];
+    int vstage_next = 0;
+    int32_t view_count = 0, vfb_cap = 0, ext_vcap = 0;
+    void * ext_vrgb = nullptr, * ext_vpacked = nullptr;
 
     DevQueues q;
     DevBuf qb[20];
@@ -108,7 +117,7 @@ struct rtx_ctx {
     // RTX_GRAPH=1: the launches of a rtx_render_tiles call are captured once into a hipGraph and replayed while nothing they depend on changes
     hipGraphExec_t graph_exec = nullptr; std::vector<unsigned char> graph_key, graph_warm;
     // RTX_PK_LPT: level-0 closest-hit packets longest first, by their cost in the previous call with the same tiles (k_packet_order on a side stream)
-    DevBuf d_pk_cost, d_pk_order; hipStream_t order_stream = nullptr; hipEvent_t ev_cost = nullptr, ev_order = nullptr; int32_t lpt_key[4] = { -1, -1, -1, -1 }; bool lpt_valid = false;
+    DevBuf d_pk_cost, d_pk_order; hipStream_t order_stream = nullptr; hipEvent_t ev_cost = nullptr, ev_order = nullptr; int32_t lpt_key[5] = { -1, -1, -1, -1, -1 }; bool lpt_valid = false;
     std::vector<KernelTime> times;
     std::vector<hipEvent_t> event_pool;
     size_t event_next = 0;
@@ -400,12 +409,13 @@ extern "C" int rtx_destroy(rtx_ctx * c) {
     if (c->stream) hipStreamSynchronize(c->stream);
     for (auto & v : c->blas_allocs) for (void * p : v) hipFree(p);
     for (void * p : c->tex_allocs) if (p) hipFree(p);
-    DevBuf * bufs[] = { &c->d_blas, &c->d_materials, &c->d_textures, &c->d_sky, &c->d_ewa, &c->d_frame, &c->d_counters, &c->d_spill, &c->d_fb_rgb, &c->d_fb_packed, &c->d_display, &c->d_gamma, &c->d_pk_heads, &c->d_pk_fifo, &c->d_pk_items, &c->d_pk_item_count, &c->d_stats_partial, &c->d_dbg_s0, &c->d_dbg_s1, &c->d_pk_cost, &c->d_pk_order };
+    DevBuf * bufs[] = { &c->d_blas, &c->d_materials, &c->d_textures, &c->d_sky, &c->d_ewa, &c->d_frame, &c->d_counters, &c->d_spill, &c->d_fb_rgb, &c->d_fb_packed, &c->d_display, &c->d_gamma, &c->d_pk_heads, &c->d_pk_fifo, &c->d_pk_items, &c->d_pk_item_count, &c->d_stats_partial, &c->d_dbg_s0, &c->d_dbg_s1, &c->d_pk_cost, &c->d_pk_order, &c->d_views, &c->d_vfb_rgb, &c->d_vfb_packed };
     for (DevBuf * b : bufs) if (b->p) hipFree(b->p);
     for (DevBuf & b : c->qb) if (b.p) hipFree(b.p);
     for (hipEvent_t e : c->event_pool) hipEventDestroy(e);
     for (DevCounters * h : c->pending_host) hipHostFree(h);
     for (auto & st : c->stage) { if (st.host) hipHostFree(st.host); if (st.done) hipEventDestroy(st.done); }
+    for (auto & st : c->vstage) { if (st.host) hipHostFree(st.host); if (st.done) hipEventDestroy(st.done); }
     if (c->graph_exec) { hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
     if (c->order_stream) { hipStreamSynchronize(c->order_stream); hipStreamDestroy(c->order_stream); hipEventDestroy(c->ev_cost); hipEventDestroy(c->ev_order); }
     if (c->any_stream) { hipStreamSynchronize(c->any_stream); hipStreamDestroy(c->any_stream); }
@@ -694,7 +704,7 @@ static int alloc_queues(rtx_ctx * c, int batch_tiles) {
                      (void **)&c->q.sp, (void **)&c->q.sn };
     for (void ** p : f4) { if (!rc) rc = ensure(c, c->qb[k], slots * 16); *p = c->qb[k].p; k++; }
     if (!rc) rc = ensure(c, c->qb[k], slots * 4); c->q.h1 = (int32_t *)c->qb[k].p; k++;
-    c->q.n3 = nullptr; c->q.s0 = c->q.s1 = nullptr; c->q.shadow_explicit = 0; c->q.cull = 0;      // explicit shadow rays: rtx_debug_occluded allocates them (debug_explicit_rays)
+    c->q.views = nullptr; c->q.s0 = c->q.s1 = nullptr; c->q.shadow_explicit = 0; c->q.cull = 0;      // explicit shadow rays: rtx_debug_occluded allocates them (debug_explicit_rays)
     if (!rc) rc = ensure(c, c->qb[k], sslots * 4); c->q.socc = (uint32_t *)c->qb[k].p; k++;
     c->q.spill = (int32_t *)c->d_spill.p;
     c->q.counters = (DevCounters *)c->d_counters.p;
@@ -753,20 +763,24 @@ static void launch_timed(rtx_ctx * c, const char * name, hipStream_t stream, F &
     } else launch();
 }
 
-static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_stride, int32_t tile_count, uint32_t flags, uint32_t * tile_major);
+static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_stride, int32_t tile_count, uint32_t flags, uint32_t * tile_major, bool views = false);
 
 extern "C" int rtx_render_tiles(rtx_ctx * c, int32_t first_tile, int32_t tile_stride, int32_t tile_count, uint32_t flags) {
     return render_tiles_impl(c, first_tile, tile_stride, tile_count, flags, nullptr);
 }
 
-// tile_major != nullptr: the packed level-0 pixels of the i-th rendered tile go to tile_major[i * 1024 ...] (slot order) instead of the framebuffer
-static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_stride, int32_t tile_count, uint32_t flags, uint32_t * tile_major) {
+// tile_major != nullptr: the packed level-0 pixels of the i-th rendered tile go to tile_major[i * 1024 ...] (slot order) instead of the framebuffer.
+// views (rtx_render_views): the tiles are virtual tiles over views x tiles of the set views (range checked by the caller), the kernels are the
+// VIEWS instantiations and level 0 writes the view framebuffer
+static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_stride, int32_t tile_count, uint32_t flags, uint32_t * tile_major, bool views) {
     if (!c || first_tile < 0 || tile_stride < 1 || tile_count < 0) return RTX_ERR_INVALID_ARG;
     if (!c->frame_set) { c->err = "rtx_render_tiles before rtx_set_frame"; return RTX_ERR_STATE; }
     if (int bad = validate_references(c)) return bad;
     const int tcx = (c->cfg.width + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE, tcy = (c->cfg.height + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE;
-    if (tile_count > 0 && first_tile + (int64_t)(tile_count - 1) * tile_stride >= (int64_t)tcx * tcy) return RTX_ERR_INVALID_ARG;
+    if (!views && tile_count > 0 && first_tile + (int64_t)(tile_count - 1) * tile_stride >= (int64_t)tcx * tcy) return RTX_ERR_INVALID_ARG;
     hipSetDevice(c->cfg.device);
+    // the launches below that generate primary rays or read the camera take the VIEWS instantiation of their kernel in a view call
+    auto with_views = [views](auto && launch) { if (views) launch(std::true_type()); else launch(std::false_type()); };
     const bool count_work = (flags & RTX_RENDER_COUNT_WORK) != 0;
     const bool simple = (flags & RTX_RENDER_SIMPLE_TRACE) != 0;
     const bool cull = (flags & RTX_RENDER_CULL_DEAD_SHADOW_RAYS) != 0 && !simple && !count_work;
@@ -801,6 +815,11 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
     plan_batch(c, tile_count, batch_tiles);
     int rc = alloc_queues(c, batch_tiles);
     if (rc) return rc;
+    if (views) {
+        c->q.views = (const rtx_camera *)c->d_views.p;
+        c->q.fb_rgb = (float *)(c->ext_vrgb ? c->ext_vrgb : c->d_vfb_rgb.p);
+        c->q.fb_packed = (uint32_t *)(c->ext_vpacked ? c->ext_vpacked : c->d_vfb_packed.p);
+    }
     // Levels that can hold rays: a hit spawns a reflection / refraction ray only where its material's Ks / Kt is not all zero (Raytracer.cpp:204-213,
     // rtx_shade.h reflection_mask / refraction_mask).  With no such material uploaded the levels >= 1 are provably empty, and their
     // launches — three per level, each a floor of 7-9 us — are not queued (BASELINE configs[1]: diffuse Monkey.obj with NUMBER_OF_BOUNCES 3).
@@ -861,7 +880,7 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
         int lrc = ensure(c, c->d_pk_cost, (size_t)lpt_n * 4); if (!lrc) lrc = ensure(c, c->d_pk_order, (size_t)lpt_n * 4);
         if (lrc) return lrc;
         if (!c->order_stream) { HIP_OK(c, hipStreamCreateWithFlags(&c->order_stream, hipStreamNonBlocking)); hipEventCreateWithFlags(&c->ev_cost, hipEventDisableTiming); hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming); }
-        const int32_t key[4] = { first_tile, tile_stride, tile_count, levels };
+        const int32_t key[5] = { first_tile, tile_stride, tile_count, levels, views ? 1 : 0 };      // a view call has its own key space: packets over views x tiles
         const bool use_order = c->lpt_valid && memcmp(key, c->lpt_key, sizeof(key)) == 0;
         memcpy(c->lpt_key, key, sizeof(key));
         c->q.pk_cost = (uint32_t *)c->d_pk_cost.p;
@@ -870,10 +889,12 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
     } else c->lpt_valid = false;
     bool capturing = false;
     if (c->knobs.graph && !c->timing && tile_count <= batch_tiles) {
-        std::vector<unsigned char> key(sizeof(DevScene) + sizeof(DevQueues) + 5 * sizeof(int32_t) + sizeof(void *));
+        // a view call differs from a tiles call by the cameras and framebuffer pointers of the queues and the views flag; its view range is the
+        // tile range (first_tile = first_view * tiles per view); the cameras themselves are read from device memory at replay
+        std::vector<unsigned char> key(sizeof(DevScene) + sizeof(DevQueues) + 6 * sizeof(int32_t) + sizeof(void *));
         unsigned char * kp = key.data();
         memcpy(kp, &c->scene, sizeof(DevScene)); kp += sizeof(DevScene); memcpy(kp, &c->q, sizeof(DevQueues)); kp += sizeof(DevQueues);
-        const int32_t kv[5] = { first_tile, tile_stride, tile_count, (int32_t)flags, levels }; memcpy(kp, kv, sizeof(kv)); kp += sizeof(kv);
+        const int32_t kv[6] = { first_tile, tile_stride, tile_count, (int32_t)flags, levels, views ? 1 : 0 }; memcpy(kp, kv, sizeof(kv)); kp += sizeof(kv);
         memcpy(kp, &tile_major, sizeof(void *));
         if (c->graph_exec && key == c->graph_key) {
             HIP_OK(c, hipGraphLaunch(c->graph_exec, c->stream));
@@ -911,10 +932,10 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
         if (sc.heatmap) {
             // BVH_VISUALIZE_HEATMAP: bounce() returns right after the primary ray's trace (Raytracer.cpp:97-102), so a frame is one
             // closest-hit pass in reference pop order (the plain kernel counts the steps) and one colouring pass
-            launch_timed(c, "k_trace_closest", c->stream, [&] {
-                if (count_work) hipLaunchKernelGGL((k_trace<false, true>),  dim3(c->trace_blocks_count), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, 0);
-                else            hipLaunchKernelGGL((k_trace<false, false>), dim3(c->trace_blocks_count), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, 0); });
-            launch_timed(c, "k_heatmap", c->stream, [&] { hipLaunchKernelGGL(k_heatmap, dim3(stream_blocks), dim3(256), 0, c->stream, sc, q); });
+            launch_timed(c, "k_trace_closest", c->stream, [&] { with_views([&](auto V) { constexpr bool VW = decltype(V)::value;
+                if (count_work) hipLaunchKernelGGL((k_trace<false, true, VW>),  dim3(c->trace_blocks_count), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, 0);
+                else            hipLaunchKernelGGL((k_trace<false, false, VW>), dim3(c->trace_blocks_count), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, 0); }); });
+            launch_timed(c, "k_heatmap", c->stream, [&] { with_views([&](auto V) { hipLaunchKernelGGL((k_heatmap<decltype(V)::value>), dim3(stream_blocks), dim3(256), 0, c->stream, sc, q); }); });
             continue;
         }
         // traversal kernels: packet walk (production), per-lane pair fetch (RTX_RENDER_LANE_TRACE), plain pop-and-test (SIMPLE / COUNT_WORK)
@@ -941,15 +962,15 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
         auto level_blocks = [&](int level, int full) { const long long want = (((long long)q.primary_slots >> level) + 255) / 256; return (int)std::max(64ll, std::min((long long)full, want)); };
         for (int level = 0; level < levels; level++) q.stats_n[level] = level_is_fused(level) ? pk_waves_closest : level_blocks(level, shade_blocks);
         auto launch_closest = [&](int level) {
-            launch_timed(c, level_is_fused(level) ? "k_trace_closest_shade" : "k_trace_closest", c->stream, [&] {
-                if (count_work)     hipLaunchKernelGGL((k_trace<false, true>),   dim3(c->trace_blocks_count), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, level);
-                else if (simple)    hipLaunchKernelGGL((k_trace<false, false>),  dim3(c->trace_blocks_count), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, level);
-                else if (lane || (!pstat && level >= lane_from_closest)) hipLaunchKernelGGL((k_trace_fast<false>),    dim3(c->trace_blocks_closest), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, level, level);
-                else if (pstat)     hipLaunchKernelGGL((k_packet<false, true>),  dim3(c->pk_blocks_closest), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, level, level);
-                else if (level_is_fused(level) && cull) hipLaunchKernelGGL((k_packet<false, false, false, true, true>),  dim3(c->pk_blocks_closest), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, level, level);
-                else if (level_is_fused(level))         hipLaunchKernelGGL((k_packet<false, false, false, true, false>), dim3(c->pk_blocks_closest), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, level, level);
-                else                hipLaunchKernelGGL((k_packet<false, false>), dim3(c->pk_blocks_closest), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, level, level);
-            });
+            launch_timed(c, level_is_fused(level) ? "k_trace_closest_shade" : "k_trace_closest", c->stream, [&] { with_views([&](auto V) { constexpr bool VW = decltype(V)::value;
+                if (count_work)     hipLaunchKernelGGL((k_trace<false, true, VW>),   dim3(c->trace_blocks_count), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, level);
+                else if (simple)    hipLaunchKernelGGL((k_trace<false, false, VW>),  dim3(c->trace_blocks_count), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, level);
+                else if (lane || (!pstat && level >= lane_from_closest)) hipLaunchKernelGGL((k_trace_fast<false, VW>),    dim3(c->trace_blocks_closest), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, level, level);
+                else if (pstat)     hipLaunchKernelGGL((k_packet<false, true, false, false, false, VW>),  dim3(c->pk_blocks_closest), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, level, level);
+                else if (level_is_fused(level) && cull) hipLaunchKernelGGL((k_packet<false, false, false, true, true, VW>),  dim3(c->pk_blocks_closest), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, level, level);
+                else if (level_is_fused(level))         hipLaunchKernelGGL((k_packet<false, false, false, true, false, VW>), dim3(c->pk_blocks_closest), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, level, level);
+                else                hipLaunchKernelGGL((k_packet<false, false, false, false, false, VW>), dim3(c->pk_blocks_closest), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, level, level);
+            }); });
         };
         // split shadow-ray walk (RTX_PK_SPLIT): q.pk_items / q.pk_item_cap were sized for this call's largest batch before the loop
         const bool split = q.pk_items != nullptr;
@@ -983,12 +1004,12 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
                 hipEventRecord(c->ev_order, c->order_stream);
                 c->lpt_valid = true;
             }
-            if (!level_is_fused(level)) launch_timed(c, "k_shade", c->stream, [&] {
+            if (!level_is_fused(level)) launch_timed(c, "k_shade", c->stream, [&] { with_views([&](auto V) { constexpr bool VW = decltype(V)::value;
                 const int g = level_blocks(level, shade_blocks);
-                if (count_work) hipLaunchKernelGGL((k_shade<true, false>),  dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level);
-                else if (cull)  hipLaunchKernelGGL((k_shade<false, true>),  dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level);
-                else            hipLaunchKernelGGL((k_shade<false, false>), dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level);
-            });
+                if (count_work) hipLaunchKernelGGL((k_shade<true, false, VW>),  dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level);
+                else if (cull)  hipLaunchKernelGGL((k_shade<false, true, VW>),  dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level);
+                else            hipLaunchKernelGGL((k_shade<false, false, VW>), dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level);
+            }); });
             if (sc.light_count == 0) continue;
             if (overlap) {
                 if (level == 0) {
@@ -1008,7 +1029,8 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
         }
         if (overlap) { hipEventRecord(c->ev_any_done, c->any_stream); hipStreamWaitEvent(c->stream, c->ev_any_done, 0); }
         for (int level = levels - 1; level >= 0; level--)
-            launch_timed(c, "k_resolve", c->stream, [&] { hipLaunchKernelGGL(k_resolve, dim3(level_blocks(level, stream_blocks) * (256 / c->knobs.resolve_block)), dim3(c->knobs.resolve_block), 0, c->stream, sc, q, level); });
+            launch_timed(c, "k_resolve", c->stream, [&] { with_views([&](auto V) {
+                hipLaunchKernelGGL((k_resolve<decltype(V)::value>), dim3(level_blocks(level, stream_blocks) * (256 / c->knobs.resolve_block)), dim3(c->knobs.resolve_block), 0, c->stream, sc, q, level); }); });
     }
     if (capturing) {
         hipGraph_t g = nullptr;
@@ -1109,6 +1131,87 @@ extern "C" int rtx_set_stream(rtx_ctx * c, void * hip_stream) {
     hipSetDevice(c->cfg.device);
     HIP_OK(c, hipStreamSynchronize(c->stream));
     c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
+    return RTX_OK;
+}
+
+// ---- batches of views (include/rtx.h rtx_set_views ...) ------------------------------------------------------------------------------
+// A view call is a render call over virtual tiles: view v's tile t is tile v * T + t, T = tiles per view (rtx_trace.h primary_pixel_v).
+static int64_t view_pixel_count(const rtx_ctx * c, int64_t views) { return views * (int64_t)c->cfg.width * c->cfg.height; }
+
+extern "C" int rtx_set_views(rtx_ctx * c, const rtx_camera * cameras, int32_t view_count) {
+    if (!c || !cameras || view_count < 1 || view_count > RTX_MAX_VIEWS) return RTX_ERR_INVALID_ARG;
+    if (view_pixel_count(c, view_count) >= (1ll << 31)) { c->err = "view_count * width * height must stay below 2^31 (pixel index of a ray record)"; return RTX_ERR_INVALID_ARG; }
+    hipSetDevice(c->cfg.device);
+    const size_t bytes = (size_t)view_count * sizeof(rtx_camera);
+    if (bytes > c->d_views.cap) {                          // growth: queued work still reads the old array
+        HIP_OK(c, hipStreamSynchronize(c->stream));
+        if (int rc = ensure(c, c->d_views, bytes)) return rc;
+    }
+    rtx_ctx::FrameStage & st = c->vstage[c->vstage_next]; c->vstage_next = (c->vstage_next + 1) % 3;
+    if (st.pending) { HIP_OK(c, hipEventSynchronize(st.done)); st.pending = false; }
+    if (bytes > st.cap) {
+        if (st.host) hipHostFree(st.host);
+        st.host = nullptr; st.cap = 0;
+        HIP_OK(c, hipHostMalloc(&st.host, bytes, hipHostMallocDefault)); st.cap = bytes;
+    }
+    if (!st.done) HIP_OK(c, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
+    memcpy(st.host, cameras, bytes);
+    HIP_OK(c, hipMemcpyAsync(c->d_views.p, st.host, bytes, hipMemcpyHostToDevice, c->stream));      // after the work already queued, before the next call
+    HIP_OK(c, hipEventRecord(st.done, c->stream)); st.pending = true;
+    c->view_count = view_count;
+    return RTX_OK;
+}
+
+// the context's own view framebuffer: allocated on first use, grown only (the views already there are kept, new ones start at zero)
+static int ensure_view_fb(rtx_ctx * c, int32_t views) {
+    if (views <= c->vfb_cap) return RTX_OK;
+    const size_t px = (size_t)c->cfg.width * c->cfg.height, old = (size_t)c->vfb_cap * px;
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    DevBuf rgb, packed;
+    int rc = ensure(c, rgb, (size_t)views * px * 12);
+    if (!rc) rc = ensure(c, packed, (size_t)views * px * 4);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemset(rgb.p, 0, rgb.cap);
+    if (!rc && e == hipSuccess) e = hipMemset(packed.p, 0, packed.cap);
+    if (!rc && e == hipSuccess && old) e = hipMemcpy(rgb.p, c->d_vfb_rgb.p, old * 12, hipMemcpyDeviceToDevice);
+    if (!rc && e == hipSuccess && old) e = hipMemcpy(packed.p, c->d_vfb_packed.p, old * 4, hipMemcpyDeviceToDevice);
+    if (!rc && e != hipSuccess) { c->err = std::string("view framebuffer growth: ") + hipGetErrorString(e); rc = RTX_ERR_HIP; }
+    if (rc) { if (rgb.p) hipFree(rgb.p); if (packed.p) hipFree(packed.p); return rc; }      // the old buffers stay in place
+    if (old) { hipFree(c->d_vfb_rgb.p); hipFree(c->d_vfb_packed.p); }
+    c->d_vfb_rgb = rgb; c->d_vfb_packed = packed; c->vfb_cap = views;
+    return RTX_OK;
+}
+
+extern "C" int rtx_render_views(rtx_ctx * c, int32_t first_view, int32_t view_count, uint32_t flags) {
+    if (!c || first_view < 0 || view_count < 1 || view_count > RTX_MAX_VIEWS) return RTX_ERR_INVALID_ARG;
+    if (view_pixel_count(c, view_count) >= (1ll << 31)) return RTX_ERR_INVALID_ARG;
+    if (!c->frame_set) { c->err = "rtx_render_views before rtx_set_frame"; return RTX_ERR_STATE; }
+    if (c->view_count == 0) { c->err = "rtx_render_views before rtx_set_views"; return RTX_ERR_STATE; }
+    if ((int64_t)first_view + view_count > c->view_count) { c->err = "view range outside the views set by rtx_set_views"; return RTX_ERR_INVALID_ARG; }
+    if (c->ext_vrgb) { if (first_view + view_count > c->ext_vcap) { c->err = "view range outside the bound view framebuffer"; return RTX_ERR_INVALID_ARG; } }
+    else if (int rc = ensure_view_fb(c, c->view_count)) return rc;
+    const int32_t tiles = ((c->cfg.width + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE) * ((c->cfg.height + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE);
+    return render_tiles_impl(c, first_view * tiles, 1, view_count * tiles, flags, nullptr, true);
+}
+
+extern "C" int rtx_read_views(rtx_ctx * c, int32_t first_view, int32_t view_count, float * rgb_f32, uint32_t * packed_u32) {
+    if (!c || first_view < 0 || view_count < 1 || view_count > RTX_MAX_VIEWS) return RTX_ERR_INVALID_ARG;
+    if ((int64_t)first_view + view_count > c->view_count) { c->err = "view range outside the views set by rtx_set_views"; return RTX_ERR_INVALID_ARG; }
+    if (c->ext_vrgb && first_view + view_count > c->ext_vcap) { c->err = "view range outside the bound view framebuffer"; return RTX_ERR_INVALID_ARG; }
+    hipSetDevice(c->cfg.device);
+    if (!c->ext_vrgb) if (int rc = ensure_view_fb(c, c->view_count)) return rc;
+    const size_t px = (size_t)c->cfg.width * c->cfg.height, first = (size_t)first_view * px, n = (size_t)view_count * px;
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    if (rgb_f32)    HIP_OK(c, hipMemcpy(rgb_f32, (const float *)(c->ext_vrgb ? c->ext_vrgb : c->d_vfb_rgb.p) + 3 * first, n * 12, hipMemcpyDeviceToHost));
+    if (packed_u32) HIP_OK(c, hipMemcpy(packed_u32, (const uint32_t *)(c->ext_vpacked ? c->ext_vpacked : c->d_vfb_packed.p) + first, n * 4, hipMemcpyDeviceToHost));
+    return RTX_OK;
+}
+
+extern "C" int rtx_bind_view_framebuffer(rtx_ctx * c, void * rgb_f32_dev, void * packed_u32_dev, int32_t view_capacity) {
+    if (!c || ((rgb_f32_dev == nullptr) != (packed_u32_dev == nullptr))) return RTX_ERR_INVALID_ARG;
+    if (rgb_f32_dev && view_capacity < 1) return RTX_ERR_INVALID_ARG;
+    // no synchronisation: work already queued keeps writing the buffers it was queued with (the pointers travel with each launch)
+    c->ext_vrgb = rgb_f32_dev; c->ext_vpacked = packed_u32_dev; c->ext_vcap = rgb_f32_dev ? view_capacity : 0;
     return RTX_OK;
 }
 

@@ -1774,7 +1774,7 @@ RTX_D bool pk_walk(const DevScene & sc, PkWalk & W, const int lane, const bool o
 // persistent traversal grids — 0.07 ms of work took 0.29 ms per launch, a third of a frame's time on its stream — while a wave that
 // already owns its slot simply carries on; the hit records' round trip through HBM (20 B per ray each way) and four launches per frame go
 // away too.  Child-ray slots: one atomic per packet that spawns any (wave_alloc2).
-template <bool ANY, bool PSTAT, bool SPLIT = false, bool FUSE = false, bool CULL = false>
+template <bool ANY, bool PSTAT, bool SPLIT = false, bool FUSE = false, bool CULL = false, bool VIEWS = false>
 __global__ __launch_bounds__(RTX_PK_BLOCK, ANY ? (SPLIT ? RTX_PK_WAVES_SPLIT : RTX_PK_WAVES_ANY) : (FUSE ? RTX_PK_WAVES_FUSED : RTX_PK_WAVES_CLOSEST))
 void k_packet(const DevScene sc, const DevQueues q, const int level, const int level_hi) {
     // hybrid any-hit walk: the lanes' private stacks, striped through LDS ([entry][lane]: conflict-free)
@@ -1907,8 +1907,8 @@ void k_packet(const DevScene sc, const DevQueues q, const int level, const int l
             if (W.valid) {
                 out_slot = (uint32_t)q.level_base[level] + pix_idx;
                 if (level == 0) {
-                    int px, py;
-                    if (primary_pixel(sc, q, pix_idx, px, py)) { RayFull r; primary_ray(sc, px, py, r, false); wo = r.o; wd = r.d; }
+                    int px, py, view;
+                    if (primary_pixel_v<VIEWS, true>(sc, q, pix_idx, px, py, view)) { RayFull r; primary_ray_v<VIEWS>(sc, q, view, px, py, r, false); wo = r.o; wd = r.d; }
                     else { clipped = true; W.valid = false; }
                 } else {
                     const float4 r0 = q.r0[out_slot], r1 = q.r1[out_slot];
@@ -1923,7 +1923,7 @@ void k_packet(const DevScene sc, const DevQueues q, const int level, const int l
             o = V3(0.0f, 0.0f, 0.0f); d = V3(1.0f, 1.0f, 1.0f);
             if (!W.valid) return;
             if (ANY) { float tm; load_shadow_ray(sc, q, any_level, any_light, any_rank, out_slot, o, d, tm); }
-            else if (level == 0) { int px, py; primary_pixel(sc, q, pix_idx, px, py); RayFull r; primary_ray(sc, px, py, r, false); o = r.o; d = r.d; }
+            else if (level == 0) { int px, py, view; primary_pixel_v<VIEWS, true>(sc, q, pix_idx, px, py, view); RayFull r; primary_ray_v<VIEWS>(sc, q, view, px, py, r, false); o = r.o; d = r.d; }
             else { const float4 r0 = q.r0[out_slot], r1 = q.r1[out_slot]; o = V3(r0.x, r0.y, r0.z); d = V3(r0.w, r1.x, r1.y); }
         };
         // Scene::trace_primitives / intersect_primitives: spheres, then planes, then the TLAS (Scene.cpp:173-190)
@@ -1978,7 +1978,7 @@ void k_packet(const DevScene sc, const DevQueues q, const int level, const int l
 #ifdef RTX_LANE_PROF
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long sp_t0 = __builtin_amdgcn_s_memtime();
 #endif
-            shade_ray<false, CULL>(sc, q, level, pix_idx, in_range, W.valid, make_float4(W.ray.tcur, W.best_u, W.best_v, as_f(W.best_prim)),
+            shade_ray<false, CULL, VIEWS>(sc, q, level, pix_idx, in_range, W.valid, make_float4(W.ray.tcur, W.best_u, W.best_v, as_f(W.best_prim)),
                                    clipped ? -1 : W.best_tri, wave_alloc2, tally);
 #ifdef RTX_LANE_PROF
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");

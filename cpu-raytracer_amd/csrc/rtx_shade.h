@@ -200,7 +200,7 @@ struct ShadeTally { uint32_t n_shadow, n_refl, n_refr, n_primary, n_shaded, n_sk
 // packet kernel right after a packet's walk (rtx_packet.h: no h0 / h1 round trip through HBM, no launch of its own to find room for
 // beside other frames' persistent grids).  `valid` = the slot holds a ray; `in_range` = the slot exists (idx < rays of the level).
 // alloc2(want_a, want_b, counter, slot_a, slot_b) hands out the child-ray slots; every lane of the wave must call it.
-template <bool COUNT, bool CULL, typename Alloc2>
+template <bool COUNT, bool CULL, bool VIEWS, typename Alloc2>
 RTX_D void shade_ray(const DevScene & sc, const DevQueues & q, const int level, const uint32_t idx, const bool in_range, bool valid,
                      const float4 h0, const int tri, Alloc2 && alloc2, ShadeTally & T) {
     DevCounters * const ctr = q.counters;
@@ -209,14 +209,15 @@ RTX_D void shade_ray(const DevScene & sc, const DevQueues & q, const int level, 
     const int lit_cap = q.level_cap[level];
     const uint32_t slot = (uint32_t)q.level_base[level] + (in_range ? idx : 0u);
     RayFull ray;
-    int pixel = 0, parent = -1;
+    int pixel = 0, parent = -1, view = 0;      // VIEWS: pixel = view * width * height + y * width + x (rtx_render_views), at every level
     if (valid && tri == -1) valid = false;                        // a slot without a ray: clipped pixel of an edge tile (level 0), unused tail of a wave's slot chunk (deeper levels)
     if (valid) {
         if (level == 0) {
             int px, py;
-            primary_pixel(sc, q, idx, px, py);
-            primary_ray(sc, px, py, ray, true);
+            primary_pixel_v<VIEWS, true>(sc, q, idx, px, py, view);
+            primary_ray_v<VIEWS>(sc, q, view, px, py, ray, true);
             pixel = py * sc.width + px;
+            if (VIEWS) pixel += view * view_pixels(sc);
         } else {
             const float4 r0 = q.r0[slot], r1 = q.r1[slot], r2 = q.r2[slot], r3 = q.r3[slot], r4 = q.r4[slot];
             ray.o = V3(r0.x, r0.y, r0.z); ray.d = V3(r0.w, r1.x, r1.y);
@@ -276,7 +277,8 @@ RTX_D void shade_ray(const DevScene & sc, const DevQueues & q, const int level, 
         q.sp[slot] = make_float4(h.point.x, h.point.y, h.point.z, 0.0f);
         q.sn[slot] = make_float4(h.normal.x, h.normal.y, h.normal.z, 0.0f);
         if (CULL) {
-            const v3 to_camera = vnormalize(vsub(v3p(sc.cam_pos), h.point));     // Raytracer.cpp:152 (camera, not ray origin)
+            if (VIEWS && level > 0) view = pixel / view_pixels(sc);                // the view's camera at every depth
+            const v3 to_camera = vnormalize(vsub(camera_position<VIEWS>(sc, q, view), h.point));     // Raytracer.cpp:152 (camera, not ray origin)
             for (int L = 0; L < nL; L++) {
                 const v3 c = light_contribution(sc, L, h.point, h.normal, to_camera);
                 const uint32_t s = (uint32_t)q.shadow_base[level] + (uint32_t)L * (uint32_t)lit_cap + (uint32_t)lit_rank;
@@ -373,7 +375,7 @@ RTX_D void shade_ray(const DevScene & sc, const DevQueues & q, const int level, 
     }
 }
 
-template <bool COUNT, bool CULL>
+template <bool COUNT, bool CULL, bool VIEWS = false>
 __global__ __launch_bounds__(RTX_SHADE_BLOCK, RTX_WAVES_SHADE)
 void k_shade(const DevScene sc, const DevQueues q, const int level) {
     DevCounters * const ctr = q.counters;
@@ -408,7 +410,7 @@ void k_shade(const DevScene sc, const DevQueues q, const int level) {
         const bool valid = idx < count;
         float4 h0 = make_float4(0, 0, 0, 0); int tri = 0;
         if (valid) { const uint32_t slot = (uint32_t)q.level_base[level] + idx; h0 = q.h0[slot]; tri = q.h1[slot]; }
-        shade_ray<COUNT, CULL>(sc, q, level, idx, valid, valid, h0, tri, block_alloc2, T);
+        shade_ray<COUNT, CULL, VIEWS>(sc, q, level, idx, valid, valid, h0, tri, block_alloc2, T);
     }
     // statistics: the tallies are per-wave sums; the block adds them up in LDS and ONE thread hands them on.  (One atomic per wave and
     // counter was 20 000 atomics on one cache line at the end of every level-0 launch: at the ~90 atomics/us that line sustains, two
@@ -451,15 +453,16 @@ RTX_D uint32_t plot_pack(v3 c) {
 
 // BVH_VISUALIZE_HEATMAP (Raytracer.cpp:97-102): the pixel is the primary ray's BLAS step count scaled per channel; no shading,
 // no secondary rays.  k_trace<false, *> left the count in h1 (-1 = pixel clipped off the frame).
+template <bool VIEWS = false>
 __global__ __launch_bounds__(256)
 void k_heatmap(const DevScene sc, const DevQueues q) {
     uint32_t n_primary = 0;
     for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < (uint32_t)q.primary_slots; slot += gridDim.x * blockDim.x) {
-        int px, py;
-        if (!primary_pixel(sc, q, slot, px, py)) continue;
+        int px, py, view;
+        if (!primary_pixel_v<VIEWS, true>(sc, q, slot, px, py, view)) continue;
         const float steps = (float)q.h1[(uint32_t)q.level_base[0] + slot];
         const v3 colour = V3(steps * (1.0f / 32.0f), steps * (1.0f / 256.0f), steps * (1.0f / 512.0f));
-        const size_t pixel = (size_t)py * sc.width + px;
+        const size_t pixel = (size_t)py * sc.width + px + (VIEWS ? (size_t)view * view_pixels(sc) : 0);
         q.fb_rgb[3 * pixel + 0] = colour.x; q.fb_rgb[3 * pixel + 1] = colour.y; q.fb_rgb[3 * pixel + 2] = colour.z;
         q.fb_packed[pixel] = plot_pack(colour);
         n_primary++;
@@ -468,6 +471,7 @@ void k_heatmap(const DevScene sc, const DevQueues q) {
     if ((threadIdx.x & 63) == 0 && n_primary) atomicAdd(&q.counters->stats[0], (unsigned long long)n_primary);
 }
 
+template <bool VIEWS = false>
 __global__ __launch_bounds__(256)
 void k_resolve(const DevScene sc, const DevQueues q, const int level) {
     DevCounters * const ctr = q.counters;
@@ -508,7 +512,9 @@ void k_resolve(const DevScene sc, const DevQueues q, const int level) {
                 const uint32_t rank = idx;                          // a hit's shadow rays sit in the hit's own slot of every light's segment
                 const float4 pp = q.sp[slot], nn = q.sn[slot];
                 const v3 point = V3(pp.x, pp.y, pp.z), normal = V3(nn.x, nn.y, nn.z);
-                const v3 to_camera = vnormalize(vsub(v3p(sc.cam_pos), point));     // Raytracer.cpp:152
+                int view = 0;                                                 // VIEWS: the camera of the pixel's view, at every depth
+                if (VIEWS) { int px, py; if (level == 0) primary_pixel_v<true, true>(sc, q, idx, px, py, view); else view = as_i(q.r1[slot].z) / view_pixels(sc); }
+                const v3 to_camera = vnormalize(vsub(camera_position<VIEWS>(sc, q, view), point));     // Raytracer.cpp:152
                 v3 diffuse = v3p(sc.ambient);
                 for (int L = 0; L < nL; L++) {
                     const uint32_t s = (uint32_t)q.shadow_base[level] + (uint32_t)L * (uint32_t)lit_cap + rank;
@@ -549,8 +555,8 @@ void k_resolve(const DevScene sc, const DevQueues q, const int level) {
         if (level == 0 && q.tm_packed) {
             q.tm_packed[(uint32_t)q.tm_base + idx] = plot_pack(colour);        // tile-major: slot order, one coalesced store per wave
         } else if (level == 0) {
-            int px, py; primary_pixel(sc, q, idx, px, py);
-            const int pixel = py * sc.width + px;
+            int px, py, view; primary_pixel_v<VIEWS, true>(sc, q, idx, px, py, view);
+            const int pixel = py * sc.width + px + (VIEWS ? view * view_pixels(sc) : 0);
             q.fb_rgb[3 * (size_t)pixel + 0] = colour.x;
             q.fb_rgb[3 * (size_t)pixel + 1] = colour.y;
             q.fb_rgb[3 * (size_t)pixel + 2] = colour.z;

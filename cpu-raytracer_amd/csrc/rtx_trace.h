@@ -72,14 +72,13 @@ struct RayFull {
     v3 o, d, dO_dx, dO_dy, dD_dx, dD_dy;
 };
 
-// Raytracer::render_tile, Raytracer.cpp:30-59 (lane 1)
-RTX_D void primary_ray(const DevScene & sc, int px, int py, RayFull & r, bool with_differentials) {
-    v3 ax = v3p(sc.cam_x), ay = v3p(sc.cam_y), tl = v3p(sc.cam_tl);
+// Raytracer::render_tile, Raytracer.cpp:30-59 (lane 1), for the camera (pos, tl, ax, ay)
+RTX_D void primary_ray_cam(const v3 pos, const v3 tl, const v3 ax, const v3 ay, int px, int py, RayFull & r, bool with_differentials) {
     float is = (float)px, js = (float)py;
     v3 d = vmadd_s(ax, is, vmadd_s(ay, js, tl));
     float dd  = vdot(d, d);
     float inv = 1.0f / sqrtf(dd);
-    r.o = v3p(sc.cam_pos);
+    r.o = pos;
     r.d = vmuls(d, inv);
     if (with_differentials) {
         float denom = inv / dd;
@@ -88,6 +87,45 @@ RTX_D void primary_ray(const DevScene & sc, int px, int py, RayFull & r, bool wi
         r.dD_dx = vmuls(vsub(vmuls(ax, dd), vmuls(d, vdot(d, ax))), denom);
         r.dD_dy = vmuls(vsub(vmuls(ay, dd), vmuls(d, vdot(d, ay))), denom);
     }
+}
+RTX_D void primary_ray(const DevScene & sc, int px, int py, RayFull & r, bool with_differentials) {
+    primary_ray_cam(v3p(sc.cam_pos), v3p(sc.cam_tl), v3p(sc.cam_x), v3p(sc.cam_y), px, py, r, with_differentials);
+}
+
+// ---- batches of views (rtx_render_views) -------------------------------------------------------------------------------------------
+// A view call renders VIRTUAL tiles over views x tiles: tile t is tile t % T of view t / T (T = tiles per frame), whose camera is
+// q.views[view] and whose pixels are [view * W * H, (view + 1) * W * H) of the view framebuffer.  Every kernel that
+// generates primary rays or needs the camera position has a VIEWS instantiation; VIEWS = false is exactly the single-camera code.
+// UNIFORM: the caller's wave covers 64 consecutive slots (one 8x8 block of one tile), so the tile, the view and the camera are
+// wave-uniform: computed once per wave in SGPRs, the camera by scalar loads.  The per-lane kernels (lane refill) compute them per lane.
+typedef const __attribute__((address_space(4))) rtx_f4v * rtx_cam_cptr;
+RTX_D int view_tiles(const DevScene & sc) { return sc.tile_count_x * ((sc.height + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE); }      // Window.cpp:11-12
+RTX_D int view_pixels(const DevScene & sc) { return sc.width * sc.height; }
+template <bool VIEWS, bool UNIFORM>
+RTX_D bool primary_pixel_v(const DevScene & sc, const DevQueues & q, uint32_t slot, int & px, int & py, int & view) {
+    view = 0;
+    if (!VIEWS) return primary_pixel(sc, q, slot, px, py);
+    int t = q.first_tile + (int)(slot >> 10) * q.tile_stride;
+    if (UNIFORM) t = __builtin_amdgcn_readfirstlane(t);
+    const int tiles = view_tiles(sc);
+    view = t / tiles;
+    tile_slot_pixel(t - view * tiles, (int)(slot & 1023u), sc.tile_count_x, px, py);
+    return px < sc.width && py < sc.height;
+}
+// the camera of `view` as 3 float4: (pos, tl.x) (tl.y, tl.z, x.x, x.y) (x.z, y.x, y.y, y.z)   (rtx_camera, 48 B)
+RTX_D v3 view_camera_position(const DevQueues & q, int view) {
+    const rtx_cam_cptr p = (rtx_cam_cptr)(const void *)(q.views + view);
+    const rtx_f4v a = p[0];
+    return V3(a.x, a.y, a.z);
+}
+template <bool VIEWS>
+RTX_D v3 camera_position(const DevScene & sc, const DevQueues & q, int view) { return VIEWS ? view_camera_position(q, view) : v3p(sc.cam_pos); }
+template <bool VIEWS>
+RTX_D void primary_ray_v(const DevScene & sc, const DevQueues & q, int view, int px, int py, RayFull & r, bool with_differentials) {
+    if (!VIEWS) { primary_ray(sc, px, py, r, with_differentials); return; }
+    const rtx_cam_cptr p = (rtx_cam_cptr)(const void *)(q.views + view);
+    const rtx_f4v a = p[0], b = p[1], c = p[2];
+    primary_ray_cam(V3(a.x, a.y, a.z), V3(a.w, b.x, b.y), V3(b.z, b.w, c.x), V3(c.y, c.z, c.w), px, py, r, with_differentials);
 }
 
 // AABB::intersect, AABB.cpp:38-52
@@ -241,7 +279,7 @@ RTX_D bool shadow_slot_is_lit(const DevQueues & q, int level, uint32_t rank) {
     return (as_i(q.n0[(uint32_t)q.level_base[level] + rank].w) & NF_LIT) != 0;
 }
 
-template <bool ANY, bool COUNT>
+template <bool ANY, bool COUNT, bool VIEWS = false>
 __global__ __launch_bounds__(RTX_TRACE_BLOCK)
 void k_trace(const DevScene sc, const DevQueues q, const int level) {
     __shared__ int lds_stack[RTX_TRACE_BLOCK / RTX_WAVE][RTX_LDS_STACK][RTX_WAVE];
@@ -314,10 +352,10 @@ void k_trace(const DevScene sc, const DevQueues q, const int level) {
                 } else {
                     out_slot = (uint32_t)q.level_base[level] + idx;
                     if (level == 0) {
-                        int px, py;
-                        live = primary_pixel(sc, q, idx, px, py);
+                        int px, py, view;
+                        live = primary_pixel_v<VIEWS, false>(sc, q, idx, px, py, view);
                         RayFull r;
-                        if (live) { primary_ray(sc, px, py, r, false); wo = r.o; wd = r.d; }
+                        if (live) { primary_ray_v<VIEWS>(sc, q, view, px, py, r, false); wo = r.o; wd = r.d; }
                     } else {
                         const float4 r0 = q.r0[out_slot], r1 = q.r1[out_slot];
                         wo = V3(r0.x, r0.y, r0.z); wd = V3(r0.w, r1.x, r1.y);
@@ -468,7 +506,7 @@ void k_trace(const DevScene sc, const DevQueues q, const int level) {
 //    reference's pop-time test.  For shadow rays D never changes, so the re-test is skipped.
 //
 // Work counters are produced by k_trace<ANY, true> (reference-order accounting); this kernel has none.
-template <bool ANY>
+template <bool ANY, bool VIEWS = false>
 __global__ __launch_bounds__(RTX_TRACE_BLOCK, ANY ? RTX_WAVES_ANY : RTX_WAVES_CLOSEST)
 void k_trace_fast(const DevScene sc, const DevQueues q, const int level, const int level_hi) {
     __shared__ int lds_stack[RTX_TRACE_BLOCK / RTX_WAVE][RTX_LDS_STACK][RTX_WAVE];
@@ -557,10 +595,10 @@ void k_trace_fast(const DevScene sc, const DevQueues q, const int level, const i
                 } else {
                     out_slot = (uint32_t)q.level_base[level] + idx;
                     if (level == 0) {
-                        int px, py;
-                        live = primary_pixel(sc, q, idx, px, py);
+                        int px, py, view;
+                        live = primary_pixel_v<VIEWS, false>(sc, q, idx, px, py, view);
                         RayFull r;
-                        if (live) { primary_ray(sc, px, py, r, false); wo = r.o; wd = r.d; }
+                        if (live) { primary_ray_v<VIEWS>(sc, q, view, px, py, r, false); wo = r.o; wd = r.d; }
                     } else {
                         const float4 r0 = q.r0[out_slot], r1 = q.r1[out_slot];
                         wo = V3(r0.x, r0.y, r0.z); wd = V3(r0.w, r1.x, r1.y);

@@ -22,7 +22,11 @@ EXPORTS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error", "rt
            "rtx_read_framebuffer", "rtx_framebuffer_device_ptrs", "rtx_last_kernel_times", "rtx_enable_kernel_timing",
            "rtx_bind_framebuffer", "rtx_set_stream", "rtx_present", "rtx_debug_libm", "rtx_debug_texture_sample", "rtx_debug_sky_sample", "rtx_debug_blas_wide", "rtx_debug_blas_wide_closest",
            "rtx_group_unique_id", "rtx_group_create", "rtx_group_render", "rtx_group_destroy", "rtx_group_attach", "rtx_group_create_local", "rtx_group_render_local",
-           "rtx_group_layout", "rtx_group_slot_pixels", "rtx_debug_group_loopback", "rtx_debug_trace_rays", "rtx_debug_occluded", "rtx_debug_light_plot"]
+           "rtx_group_layout", "rtx_group_slot_pixels", "rtx_debug_group_loopback", "rtx_debug_trace_rays", "rtx_debug_occluded", "rtx_debug_light_plot",
+           "rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer"]
+# newer than the A/B variants tools/ab.py may load (RTX_HIP_LIB = a library built from an older commit): bound when the library has them,
+# otherwise a call raises AttributeError (undefined symbol)
+VIEW_EXPORTS = ("rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer")
 
 RTX_RENDER_COUNT_WORK = 1
 RTX_RENDER_SIMPLE_TRACE = 2
@@ -31,6 +35,7 @@ RTX_RENDER_SERIAL = 8
 RTX_RENDER_LANE_TRACE = 16
 RTX_RENDER_PACKET_STATS = 32
 RTX_RENDER_PACKET_CLOSEST = 64
+RTX_MAX_VIEWS = 4096
 ERRORS = {1: "RTX_ERR_INVALID_ARG", 2: "RTX_ERR_NO_DEVICE", 3: "RTX_ERR_HIP", 4: "RTX_ERR_LIMIT", 5: "RTX_ERR_STATE", 6: "RTX_ERR_OOM"}
 
 _lib = None
@@ -89,12 +94,48 @@ def load_library(path: Optional[str] = None):
     lib.rtx_debug_trace_rays.argtypes = [vp, vp, i32, vp, u32]
     lib.rtx_debug_occluded.argtypes = [vp, vp, i32, vp, u32]
     lib.rtx_debug_light_plot.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, i32]
+    if hasattr(lib, "rtx_set_views"):
+        lib.rtx_set_views.argtypes = [vp, vp, i32]
+        lib.rtx_render_views.argtypes = [vp, i32, i32, u32]
+        lib.rtx_read_views.argtypes = [vp, i32, i32, vp, vp]
+        lib.rtx_bind_view_framebuffer.argtypes = [vp, vp, vp, i32]
     for name in EXPORTS:
+        if name in VIEW_EXPORTS and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         if name not in ("rtx_last_error",):
             fn.restype = C.c_int
     _lib = lib
     return lib
+
+
+def render_flags(count_work: bool = False, simple_trace: bool = False, cull_dead_shadow_rays: bool = False, serial: bool = False,
+                 lane_trace: bool = False, packet_stats: bool = False, packet_closest: bool = False) -> int:
+    """The RTX_RENDER_* bits of the keyword flags Renderer.render / render_views take."""
+    return ((RTX_RENDER_COUNT_WORK if count_work else 0) | (RTX_RENDER_SIMPLE_TRACE if simple_trace else 0)
+            | (RTX_RENDER_CULL_DEAD_SHADOW_RAYS if cull_dead_shadow_rays else 0) | (RTX_RENDER_SERIAL if serial else 0)
+            | (RTX_RENDER_LANE_TRACE if lane_trace else 0) | (RTX_RENDER_PACKET_STATS if packet_stats else 0)
+            | (RTX_RENDER_PACKET_CLOSEST if packet_closest else 0))
+
+
+def views_array(cameras) -> np.ndarray:
+    """Cameras for rtx_set_views as a contiguous scene_io.CAMERA array of shape (V,): accepts that, or float32 (V, 12) rows of
+    (position, rotated_top_left_corner, rotated_x_axis, rotated_y_axis).  Raises before anything reaches the library."""
+    if not isinstance(cameras, np.ndarray):
+        raise TypeError(f"cameras must be a numpy array (scene_io.CAMERA (V,) or float32 (V, 12)), not {type(cameras).__name__}")
+    if cameras.dtype == sio.CAMERA:
+        if cameras.ndim != 1:
+            raise ValueError(f"a scene_io.CAMERA array of views must have shape (V,), not {cameras.shape}")
+        cams = np.ascontiguousarray(cameras)
+    elif cameras.dtype == np.float32:
+        if cameras.ndim != 2 or cameras.shape[1] != 12:
+            raise ValueError(f"float32 cameras must have shape (V, 12), not {cameras.shape}")
+        cams = np.ascontiguousarray(cameras).view(sio.CAMERA).reshape(-1)
+    else:
+        raise TypeError(f"cameras must be scene_io.CAMERA or float32, not {cameras.dtype}")
+    if not 1 <= cams.shape[0] <= RTX_MAX_VIEWS:
+        raise ValueError(f"1 .. {RTX_MAX_VIEWS} views, not {cams.shape[0]}")
+    return cams
 
 
 def group_layout(width: int, height: int, world: int, rank: int):
@@ -128,6 +169,7 @@ class Renderer:
         cfg = RtxConfig()
         C.memmove(C.byref(cfg), scene.config.ctypes.data, C.sizeof(RtxConfig))
         cfg.device = device
+        self.device = device
         self.ctx = C.c_void_p()
         rc = self.lib.rtx_create(C.byref(cfg), C.byref(self.ctx))
         if rc:
@@ -181,10 +223,7 @@ class Renderer:
                      packet_stats: bool = False, packet_closest: bool = False):
         if tile_count is None:
             tile_count = (self.scene.tile_count - first_tile + tile_stride - 1) // tile_stride
-        flags = ((RTX_RENDER_COUNT_WORK if count_work else 0) | (RTX_RENDER_SIMPLE_TRACE if simple_trace else 0)
-                 | (RTX_RENDER_CULL_DEAD_SHADOW_RAYS if cull_dead_shadow_rays else 0) | (RTX_RENDER_SERIAL if serial else 0)
-                 | (RTX_RENDER_LANE_TRACE if lane_trace else 0) | (RTX_RENDER_PACKET_STATS if packet_stats else 0)
-                 | (RTX_RENDER_PACKET_CLOSEST if packet_closest else 0))
+        flags = render_flags(count_work, simple_trace, cull_dead_shadow_rays, serial, lane_trace, packet_stats, packet_closest)
         self._chk(self.lib.rtx_render_tiles(self.ctx, first_tile, tile_stride, tile_count, flags), "rtx_render_tiles")
 
     def synchronize(self):
@@ -226,6 +265,91 @@ class Renderer:
 
     def set_stream(self, stream_handle: Optional[int]):
         self._chk(self.lib.rtx_set_stream(self.ctx, stream_handle), "rtx_set_stream")
+        self._stream = stream_handle
+
+    # ---- batches of views (include/rtx.h: rtx_set_views ...) ----------------------------------------------------------------------
+    def set_views(self, cameras):
+        """The cameras of a batch of views of the current frame: scene_io.CAMERA (V,) or float32 (V, 12)."""
+        cams = views_array(cameras)
+        self._chk(self.lib.rtx_set_views(self.ctx, cams.ctypes.data, cams.shape[0]), "rtx_set_views")
+        self.view_count = int(cams.shape[0])
+
+    def _view_range(self, first_view: int, view_count: Optional[int]):
+        if view_count is None:
+            view_count = getattr(self, "view_count", 0) - first_view
+        return int(first_view), int(view_count)
+
+    def render_views_async(self, first_view: int = 0, view_count: Optional[int] = None, **flags):
+        first_view, view_count = self._view_range(first_view, view_count)
+        self._chk(self.lib.rtx_render_views(self.ctx, first_view, view_count, render_flags(**flags)), "rtx_render_views")
+
+    def read_views(self, first_view: int = 0, view_count: Optional[int] = None):
+        first_view, view_count = self._view_range(first_view, view_count)
+        sc = self.scene
+        rgb = np.zeros((max(view_count, 0), sc.height, sc.width, 3), np.float32)
+        packed = np.zeros((max(view_count, 0), sc.height, sc.width), np.uint32)
+        self._chk(self.lib.rtx_read_views(self.ctx, first_view, view_count, rgb.ctypes.data, packed.ctypes.data), "rtx_read_views")
+        return rgb, packed
+
+    def bind_view_framebuffer(self, rgb_ptr: Optional[int], packed_ptr: Optional[int], view_capacity: int = 0):
+        self._chk(self.lib.rtx_bind_view_framebuffer(self.ctx, rgb_ptr, packed_ptr, view_capacity), "rtx_bind_view_framebuffer")
+        self._view_fb = (rgb_ptr, packed_ptr, view_capacity) if rgb_ptr else None
+
+    def render_views(self, first_view: int = 0, view_count: Optional[int] = None, **flags) -> Dict:
+        """Views [first_view, first_view + view_count) of the cameras set by set_views in one rtx_render_views call (flags as render);
+        rgb (V, H, W, 3) float32, packed (V, H, W) uint32, stats / work summed over the views.  Uses the context's own view framebuffer."""
+        if getattr(self, "_view_fb", None):
+            self.bind_view_framebuffer(None, None)
+        self.render_views_async(first_view, view_count, **flags)
+        stats, work = self.stats()
+        rgb, packed = self.read_views(first_view, view_count)
+        return {"rgb": rgb, "packed": packed, "stats": stats, "work": work}
+
+    def render_views_into(self, rgb, packed, first_view: int = 0, view_count: Optional[int] = None, **flags):
+        """Render views into caller-owned device tensors: rgb float32 (C, H, W, 3) and packed int32 (C, H, W) of C >= first_view + view_count
+        views, contiguous, on this context's GPU; view v lands in rgb[v] / packed[v].  The work is queued on torch's current stream of that
+        device (rtx_set_stream: the context stays on it), so torch work queued after this call sees the images.  On torch's default stream (handle 0,
+        which the C ABI reads as "the context's own stream") the work goes to a side stream that waits for the current stream and that the
+        current stream then waits for: the same ordering.  Returns at once."""
+        import torch
+        sc, dev = self.scene, self.device
+        want = (("rgb", rgb, torch.float32, (sc.height, sc.width, 3)), ("packed", packed, torch.int32, (sc.height, sc.width)))
+        for name, t, dt, _ in want:
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name} must be a torch.Tensor, not {type(t).__name__}")
+            if t.dtype != dt:
+                raise TypeError(f"{name} must be {dt}, not {t.dtype}")
+        for name, t, _, shape in want:
+            if t.dim() != len(shape) + 1 or tuple(t.shape[1:]) != shape:
+                raise ValueError(f"{name} must have shape (views, {', '.join(map(str, shape))}), not {tuple(t.shape)}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+            if t.device.type != "cuda" or t.device.index != dev:
+                raise ValueError(f"{name} must be on cuda:{dev} (this context's GPU), not {t.device}")
+        if rgb.shape[0] != packed.shape[0]:
+            raise ValueError(f"rgb and packed hold different numbers of views ({rgb.shape[0]} vs {packed.shape[0]})")
+        first_view, view_count = self._view_range(first_view, view_count)
+        if view_count < 1 or first_view < 0 or first_view + view_count > rgb.shape[0]:
+            raise ValueError(f"views [{first_view}, {first_view + view_count}) do not fit tensors of {rgb.shape[0]} views")
+        cur = torch.cuda.current_stream(dev)
+        # torch's default stream has the handle 0, which rtx_set_stream reads as "the context's own stream" — a non-blocking stream that does
+        # not synchronise with it.  Then the work goes to a side stream of this renderer, joined to the current stream on both sides by events.
+        side = None
+        if cur.cuda_stream == 0:
+            side = getattr(self, "_side_stream", None)
+            if side is None:
+                side = self._side_stream = torch.cuda.Stream(device=dev)
+            side.wait_stream(cur)
+        stream = (side or cur).cuda_stream
+        if getattr(self, "_stream", None) != stream:
+            self.set_stream(stream)
+        fb = (rgb.data_ptr(), packed.data_ptr(), int(rgb.shape[0]))
+        if getattr(self, "_view_fb", None) != fb:
+            self.bind_view_framebuffer(*fb)
+        self.render_views_async(first_view, view_count, **flags)
+        if side is not None:
+            cur.wait_stream(side)
+            rgb.record_stream(side); packed.record_stream(side)      # the caching allocator must not hand the memory out before the render is done
 
     def enable_timing(self, on: bool = True):
         self._chk(self.lib.rtx_enable_kernel_timing(self.ctx, 1 if on else 0), "rtx_enable_kernel_timing")

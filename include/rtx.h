@@ -309,6 +309,31 @@ int rtx_bind_framebuffer(rtx_ctx * ctx, void * rgb_f32_dev, void * packed_u32_de
  * kernels / collectives without host synchronisation.                                              */
 int rtx_set_stream(rtx_ctx * ctx, void * hip_stream);
 
+/* ---- several camera views of one frame ------------------------------------------------------------------------------------------
+ * N views of the same scene state (stereo pairs, cube maps, a camera path, multi-view image sets) in ONE render call: the tiles of
+ * all views are one batch of work, so a small frame fills the GPU and the launch floors of a call are shared by its views.  The
+ * view framebuffer is separate from the context's framebuffer: rtx_render_tiles, rtx_read_framebuffer, rtx_present and the
+ * rtx_group_* path behave as before and use the rtx_set_frame camera, whatever views are set.  Per-view scene state, resolution
+ * or stats are not supported.                                                                                                     */
+#define RTX_MAX_VIEWS 4096
+/* Cameras of a batch of views of the current frame.  Everything else (TLAS, instances, primitives, lights, ambient) comes from the
+ * last rtx_set_frame.  The cameras are copied before return, stream-ordered like rtx_set_frame: work already queued keeps the old ones.
+ * RTX_ERR_INVALID_ARG: view_count < 1, > RTX_MAX_VIEWS, or view_count * width * height >= 2^31.                                    */
+int rtx_set_views(rtx_ctx * ctx, const rtx_camera * cameras, int32_t view_count);
+/* Render every tile of views [first_view, first_view + view_count).  Each view comes out exactly as rtx_render_tiles(ctx, 0, 1, all,
+ * flags) would after rtx_set_frame with that view's camera.  View v goes to the view framebuffer at rgb[v*W*H*3 ...] and
+ * packed[v*W*H ...].  rtx_get_stats afterwards = totals over the rendered views.  Every RTX_RENDER_* flag and the heat-map config
+ * are honoured.  RTX_ERR_STATE before rtx_set_frame or rtx_set_views; RTX_ERR_INVALID_ARG for a range outside the views set or
+ * outside a bound view framebuffer.  Queued like rtx_render_tiles.                                                                 */
+int rtx_render_views(rtx_ctx * ctx, int32_t first_view, int32_t view_count, uint32_t flags);
+/* views [first_view, first_view + view_count) of the view framebuffer (waits for the context's stream); either pointer may be NULL.
+ * Pixels of views that were never rendered are zero.                                                                              */
+int rtx_read_views(rtx_ctx * ctx, int32_t first_view, int32_t view_count, float * rgb_f32, uint32_t * packed_u32);
+/* Render views into caller-owned device buffers of view_capacity views (e.g. torch tensors [V,H,W,3] f32 / [V,H,W] i32) instead of
+ * the context's own view framebuffer (allocated on first use, grown only); both NULL restores the own one.  Does not wait: work
+ * already queued keeps writing the buffers it was queued with.                                                                     */
+int rtx_bind_view_framebuffer(rtx_ctx * ctx, void * rgb_f32_dev, void * packed_u32_dev, int32_t view_capacity);
+
 /* Timing of every kernel launched since rtx_enable_kernel_timing(ctx, 1),
  * measured with HIP events on the stream the kernels are launched on.
  * names/ms hold up to `capacity` entries; *count receives the number of
