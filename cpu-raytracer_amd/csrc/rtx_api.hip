@@ -100,6 +100,10 @@ struct rtx_ctx {
     int vstage_next = 0;
     int32_t view_count = 0, vfb_cap = 0, ext_vcap = 0;
     void * ext_vrgb = nullptr, * ext_vpacked = nullptr;
+    // rtx_bind_aovs: the bound channels (RTX_AOV_* bits) and where they go: the caller's device buffers of aov_ext_cap pixels (aov_ext), or
+    // the context's own buffers d_aov[k] of aov_own_cap[k] pixels (allocated by the first call that writes the channel, grown only)
+    uint32_t aov_channels = 0; bool aov_ext = false; int64_t aov_ext_cap = 0; DevAov aov_ext_ptrs = {};
+    DevBuf d_aov[8]; int64_t aov_own_cap[8] = {};
 
     DevQueues q;
     DevBuf qb[20];
@@ -411,6 +415,7 @@ extern "C" int rtx_destroy(rtx_ctx * c) {
     for (void * p : c->tex_allocs) if (p) hipFree(p);
     DevBuf * bufs[] = { &c->d_blas, &c->d_materials, &c->d_textures, &c->d_sky, &c->d_ewa, &c->d_frame, &c->d_counters, &c->d_spill, &c->d_fb_rgb, &c->d_fb_packed, &c->d_display, &c->d_gamma, &c->d_pk_heads, &c->d_pk_fifo, &c->d_pk_items, &c->d_pk_item_count, &c->d_stats_partial, &c->d_dbg_s0, &c->d_dbg_s1, &c->d_pk_cost, &c->d_pk_order, &c->d_views, &c->d_vfb_rgb, &c->d_vfb_packed };
     for (DevBuf * b : bufs) if (b->p) hipFree(b->p);
+    for (DevBuf & b : c->d_aov) if (b.p) hipFree(b.p);
     for (DevBuf & b : c->qb) if (b.p) hipFree(b.p);
     for (hipEvent_t e : c->event_pool) hipEventDestroy(e);
     for (DevCounters * h : c->pending_host) hipHostFree(h);
@@ -764,6 +769,7 @@ static void launch_timed(rtx_ctx * c, const char * name, hipStream_t stream, F &
 }
 
 static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_stride, int32_t tile_count, uint32_t flags, uint32_t * tile_major, bool views = false);
+static int aov_targets_of_call(rtx_ctx * c, int64_t pixels, DevAov & out);
 
 extern "C" int rtx_render_tiles(rtx_ctx * c, int32_t first_tile, int32_t tile_stride, int32_t tile_count, uint32_t flags) {
     return render_tiles_impl(c, first_tile, tile_stride, tile_count, flags, nullptr);
@@ -806,6 +812,17 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
         if (2 * dt + 1 + blas_shared > RTX_PK_STACK) pk_closest = false;
     }
     const bool pstat = (flags & RTX_RENDER_PACKET_STATS) != 0 && !simple && !count_work && !lane;
+    // RTX_RENDER_AOV: level 0 takes k_shade<.., AOV = true> with the bound channels' targets; the call's pixel range is the frame, or its views
+    const bool aov = (flags & RTX_RENDER_AOV) != 0;
+    DevAov aov_t = {};
+    if (aov) {
+        if (tile_major) { c->err = "RTX_RENDER_AOV is not supported on the rtx_group_* path"; return RTX_ERR_INVALID_ARG; }
+        if (c->scene.heatmap) { c->err = "RTX_RENDER_AOV in heat-map mode (a heat-map frame has no shading)"; return RTX_ERR_STATE; }
+        if (!c->aov_channels) { c->err = "RTX_RENDER_AOV without channels bound by rtx_bind_aovs"; return RTX_ERR_STATE; }
+        const int64_t frame_px = (int64_t)c->cfg.width * c->cfg.height;
+        const int64_t pixels = views ? ((int64_t)first_tile + tile_count) / ((int64_t)tcx * tcy) * frame_px : frame_px;
+        if (int arc = aov_targets_of_call(c, pixels, aov_t)) return arc;
+    }
     c->serial = (flags & RTX_RENDER_SERIAL) != 0;
 
     // stats of this call are reset by the first k_begin_batch (WorkerThread.cpp:120 zeroes them per frame)
@@ -891,11 +908,14 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
     if (c->knobs.graph && !c->timing && tile_count <= batch_tiles) {
         // a view call differs from a tiles call by the cameras and framebuffer pointers of the queues and the views flag; its view range is the
         // tile range (first_tile = first_view * tiles per view); the cameras themselves are read from device memory at replay
-        std::vector<unsigned char> key(sizeof(DevScene) + sizeof(DevQueues) + 6 * sizeof(int32_t) + sizeof(void *));
+        std::vector<unsigned char> key(sizeof(DevScene) + sizeof(DevQueues) + 6 * sizeof(int32_t) + sizeof(void *) + sizeof(uint32_t) + sizeof(DevAov));
         unsigned char * kp = key.data();
         memcpy(kp, &c->scene, sizeof(DevScene)); kp += sizeof(DevScene); memcpy(kp, &c->q, sizeof(DevQueues)); kp += sizeof(DevQueues);
         const int32_t kv[6] = { first_tile, tile_stride, tile_count, (int32_t)flags, levels, views ? 1 : 0 }; memcpy(kp, kv, sizeof(kv)); kp += sizeof(kv);
-        memcpy(kp, &tile_major, sizeof(void *));
+        memcpy(kp, &tile_major, sizeof(void *)); kp += sizeof(void *);
+        // an AOV call also depends on the bound channels and their targets (zero for a call without RTX_RENDER_AOV): a rebind is a new key
+        const uint32_t aov_mask = aov ? c->aov_channels : 0u; memcpy(kp, &aov_mask, sizeof(aov_mask)); kp += sizeof(aov_mask);
+        memcpy(kp, &aov_t, sizeof(DevAov));
         if (c->graph_exec && key == c->graph_key) {
             HIP_OK(c, hipGraphLaunch(c->graph_exec, c->stream));
             c->stats_pending = true;
@@ -955,7 +975,8 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
         // Which levels shade their own hits inside the closest-hit packet kernel (k_packet<.., FUSE>, rtx_packet.h) and which get a k_shade
         // launch (every other closest-hit kernel: per-lane, plain, instrumented).  Decided before anything is launched: k_resolve is told
         // how many partial tallies each level's shading pass leaves (q.stats_n).
-        auto level_is_fused = [&](int level) { return c->knobs.fuse_shade && !count_work && !simple && !pstat && !lane && level < lane_from_closest; };
+        // Level 0 of an AOV call always has its k_shade launch: the fused packet kernel has no AOV variant (its VGPR budget is tight).
+        auto level_is_fused = [&](int level) { return c->knobs.fuse_shade && !count_work && !simple && !pstat && !lane && level < lane_from_closest && !(aov && level == 0); };
         // Grids of the streaming kernels (k_shade, k_resolve: grid-stride loops, any grid is correct) follow the batch: level d of a batch of P
         // primary slots is given room for P / 2^d rays — the dispatcher spends ~16 ns per workgroup, which is most of a small launch's
         // time (a 1/8 tile shard's k_shade launches of levels 1-3: 18 us each with 1 024 workgroups for 74 k / 6 k / 1 k rays).
@@ -1006,7 +1027,12 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
             }
             if (!level_is_fused(level)) launch_timed(c, "k_shade", c->stream, [&] { with_views([&](auto V) { constexpr bool VW = decltype(V)::value;
                 const int g = level_blocks(level, shade_blocks);
-                if (count_work) hipLaunchKernelGGL((k_shade<true, false, VW>),  dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level);
+                if (aov && level == 0) {
+                    if (count_work) hipLaunchKernelGGL((k_shade<true, false, VW, true, DevAov>),  dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level, aov_t);
+                    else if (cull)  hipLaunchKernelGGL((k_shade<false, true, VW, true, DevAov>),  dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level, aov_t);
+                    else            hipLaunchKernelGGL((k_shade<false, false, VW, true, DevAov>), dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level, aov_t);
+                }
+                else if (count_work) hipLaunchKernelGGL((k_shade<true, false, VW>),  dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level);
                 else if (cull)  hipLaunchKernelGGL((k_shade<false, true, VW>),  dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level);
                 else            hipLaunchKernelGGL((k_shade<false, false, VW>), dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level);
             }); });
@@ -1212,6 +1238,68 @@ extern "C" int rtx_bind_view_framebuffer(rtx_ctx * c, void * rgb_f32_dev, void *
     if (rgb_f32_dev && view_capacity < 1) return RTX_ERR_INVALID_ARG;
     // no synchronisation: work already queued keeps writing the buffers it was queued with (the pointers travel with each launch)
     c->ext_vrgb = rgb_f32_dev; c->ext_vpacked = packed_u32_dev; c->ext_vcap = rgb_f32_dev ? view_capacity : 0;
+    return RTX_OK;
+}
+
+// ---- per-pixel primary-hit AOVs (include/rtx.h rtx_bind_aovs ...) ------------------------------------------------------------------------
+static const size_t kAovBytes[8] = { 4, 12, 12, 12, 8, 4, 4, 4 };        // bytes per pixel of channel k = bit 1 << k, in rtx_aov_buffers order
+template <typename T> static void ** aov_slot(T & a, int k) {             // DevAov and rtx_aov_buffers: eight pointers in channel-bit order
+    static_assert(sizeof(T) == 8 * sizeof(void *), "eight channel pointers");
+    return reinterpret_cast<void **>(&a) + k;
+}
+
+extern "C" int rtx_bind_aovs(rtx_ctx * c, uint32_t channels, const rtx_aov_buffers * device, int64_t pixel_capacity) {
+    if (!c || (channels & ~(uint32_t)RTX_AOV_ALL)) return RTX_ERR_INVALID_ARG;
+    if (device && channels && pixel_capacity < 1) return RTX_ERR_INVALID_ARG;
+    // no synchronisation: work already queued keeps writing the buffers it was queued with (the targets travel with each k_shade launch)
+    c->aov_channels = channels;
+    c->aov_ext = device != nullptr && channels != 0;
+    c->aov_ext_cap = c->aov_ext ? pixel_capacity : 0;
+    c->aov_ext_ptrs = DevAov{};
+    if (c->aov_ext) {
+        rtx_aov_buffers d = *device;
+        for (int k = 0; k < 8; k++) if (channels & (1u << k)) *aov_slot(c->aov_ext_ptrs, k) = *aov_slot(d, k);
+    }
+    return RTX_OK;
+}
+
+// The targets of a RTX_RENDER_AOV call that writes pixels [0, pixels): the caller's buffers (capacity checked) or the context's own, grown to
+// `pixels` where needed (growth waits for queued work, which may still write the old buffers; the pixels already there are kept).
+static int aov_targets_of_call(rtx_ctx * c, int64_t pixels, DevAov & out) {
+    out = DevAov{};
+    if (c->aov_ext) {
+        if (pixels > c->aov_ext_cap) { c->err = "the call's pixel range exceeds the pixel_capacity of the bound AOV buffers"; return RTX_ERR_INVALID_ARG; }
+        out = c->aov_ext_ptrs;
+        return RTX_OK;
+    }
+    for (int k = 0; k < 8; k++) {
+        if (!(c->aov_channels & (1u << k))) continue;
+        if (pixels > c->aov_own_cap[k]) {
+            HIP_OK(c, hipStreamSynchronize(c->stream));
+            DevBuf nb;
+            if (int rc = ensure(c, nb, (size_t)pixels * kAovBytes[k])) return rc;
+            hipError_t e = hipMemset(nb.p, 0, nb.cap);
+            if (e == hipSuccess && c->aov_own_cap[k]) e = hipMemcpy(nb.p, c->d_aov[k].p, (size_t)c->aov_own_cap[k] * kAovBytes[k], hipMemcpyDeviceToDevice);
+            if (e != hipSuccess) { hipFree(nb.p); c->err = std::string("AOV buffer growth: ") + hipGetErrorString(e); return RTX_ERR_HIP; }
+            if (c->d_aov[k].p) hipFree(c->d_aov[k].p);
+            c->d_aov[k] = nb; c->aov_own_cap[k] = pixels;
+        }
+        *aov_slot(out, k) = c->d_aov[k].p;
+    }
+    return RTX_OK;
+}
+
+extern "C" int rtx_read_aovs(rtx_ctx * c, int32_t first_view, int32_t view_count, const rtx_aov_buffers * host) {
+    if (!c || !host || first_view < 0 || view_count < 1) return RTX_ERR_INVALID_ARG;
+    if (c->aov_ext) { c->err = "rtx_read_aovs while caller AOV buffers are bound"; return RTX_ERR_STATE; }
+    const int64_t px = (int64_t)c->cfg.width * c->cfg.height, first = first_view * px, n = view_count * px;
+    rtx_aov_buffers h = *host;
+    for (int k = 0; k < 8; k++)
+        if (*aov_slot(h, k) && first + n > c->aov_own_cap[k]) { c->err = "rtx_read_aovs: a requested channel's own buffer does not hold the range"; return RTX_ERR_INVALID_ARG; }
+    hipSetDevice(c->cfg.device);
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 8; k++)
+        if (void * dst = *aov_slot(h, k)) HIP_OK(c, hipMemcpy(dst, (const char *)c->d_aov[k].p + (size_t)first * kAovBytes[k], (size_t)n * kAovBytes[k], hipMemcpyDeviceToHost));
     return RTX_OK;
 }
 
@@ -1526,12 +1614,12 @@ static int group_render_one(rtx_group * g, uint32_t flags, bool render, bool gat
 // packed tiles to rank 0 and, there, writes the frame into the context's packed framebuffer.  Everything is queued on the context's
 // stream; nothing synchronises with the host.
 extern "C" int rtx_group_render(rtx_group * g, uint32_t flags) {
-    if (!g || !g->ctx) return RTX_ERR_INVALID_ARG;
+    if (!g || !g->ctx || (flags & RTX_RENDER_AOV)) return RTX_ERR_INVALID_ARG;      // AOVs are not supported on the group path
     return group_render_one(g, flags, true, true, true);
 }
 
 extern "C" int rtx_group_render_local(rtx_group ** groups, int32_t n, uint32_t flags) {
-    if (!groups || n < 1) return RTX_ERR_INVALID_ARG;
+    if (!groups || n < 1 || (flags & RTX_RENDER_AOV)) return RTX_ERR_INVALID_ARG;
     RcclApi * r = rccl();
     if (!r) return RTX_ERR_STATE;
     for (int i = 0; i < n; i++) { if (!groups[i]) return RTX_ERR_INVALID_ARG; const int rc = group_render_one(groups[i], flags, true, false, false); if (rc) return rc; }
@@ -1562,7 +1650,7 @@ extern "C" int rtx_group_destroy(rtx_group * g) {
 // its slice of rank 0's receive buffer, then the same k_unswizzle.  Covers the partition, the tile-major writes and the frame assembly
 // for any world size; the ncclGather itself is exercised by rtx_group_render.
 extern "C" int rtx_debug_group_loopback(rtx_ctx * c, int32_t world, uint32_t flags) {
-    if (!c || world < 1) return RTX_ERR_INVALID_ARG;
+    if (!c || world < 1 || (flags & RTX_RENDER_AOV)) return RTX_ERR_INVALID_ARG;
     rtx_group g; g.ctx = c; g.rank = 0; g.world = world;
     int rc = group_setup(&g);
     for (int r = 0; r < world && !rc; r++) {

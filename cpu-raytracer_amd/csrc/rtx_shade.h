@@ -6,6 +6,7 @@
 //                     contribution per light, and the reflected / refracted child rays with their
 //                     ray differentials.  Queue appends are wave-compacted: ballot, popcount prefix,
 //                     one atomicAdd per wave.
+//   k_shade<.., AOV>  the same pass for level 0 of a RTX_RENDER_AOV call: also stores the primary hit's AOV channels (DevAov)
 //   k_resolve(level)  folds a level bottom-up in EXACTLY the reference's evaluation order
 //                     (result = diffuse*albedo; += Ks*C_refl; TIR / Beer / Schlick blend), so the
 //                     colours are bit-identical to the recursion, then hands the colour to the
@@ -191,6 +192,13 @@ RTX_D v3 light_contribution(const DevScene & sc, const int L, const v3 point, co
 // ray is still COUNTED (the reference counts before testing, Raytracer.cpp:163,180,192) but marked so that k_trace<any>
 // retires it without traversal.  Off by default; bench.py reports it as a separate figure.
 
+// Targets of the per-pixel AOV channels of a RTX_RENDER_AOV call (include/rtx.h rtx_aov_buffers): null = channel not written.  An extra kernel
+// argument of k_shade<.., AOV = true> only: DevScene / DevQueues, and with them every other kernel's arguments, keep their layout.
+struct DevAov {
+    float * depth; float * position; float * normal; float * albedo; float * uv;
+    int32_t * material_id; int32_t * object_id; int32_t * triangle_id;
+};
+
 // wave-uniform tallies of a shading pass (SGPRs): ballot popcounts instead of one VGPR counter per statistic; n_texels is per lane (COUNT builds)
 struct ShadeTally { uint32_t n_shadow, n_refl, n_refr, n_primary, n_shaded, n_sky, n_trihit, n_texels; };
 
@@ -200,9 +208,10 @@ struct ShadeTally { uint32_t n_shadow, n_refl, n_refr, n_primary, n_shaded, n_sk
 // packet kernel right after a packet's walk (rtx_packet.h: no h0 / h1 round trip through HBM, no launch of its own to find room for
 // beside other frames' persistent grids).  `valid` = the slot holds a ray; `in_range` = the slot exists (idx < rays of the level).
 // alloc2(want_a, want_b, counter, slot_a, slot_b) hands out the child-ray slots; every lane of the wave must call it.
-template <bool COUNT, bool CULL, bool VIEWS, typename Alloc2>
+// AOV (level 0 of a RTX_RENDER_AOV call): the primary hit's channels go to `aov` at the pixel the colour goes to.
+template <bool COUNT, bool CULL, bool VIEWS, bool AOV = false, typename Alloc2>
 RTX_D void shade_ray(const DevScene & sc, const DevQueues & q, const int level, const uint32_t idx, const bool in_range, bool valid,
-                     const float4 h0, const int tri, Alloc2 && alloc2, ShadeTally & T) {
+                     const float4 h0, const int tri, Alloc2 && alloc2, ShadeTally & T, const DevAov * aov_targets = nullptr) {
     DevCounters * const ctr = q.counters;
     const int bounces_left = sc.bounces - level;
     const int nL = sc.light_count;
@@ -259,6 +268,23 @@ RTX_D void shade_ray(const DevScene & sc, const DevQueues & q, const int level, 
         }
         Ks = v3p(m.reflection); Kt = v3p(m.transmittance); ior = m.index_of_refraction;
         if (vdot(albedo, albedo) > 0.0f) flags |= NF_LIT;         // Raytracer.cpp:143-145
+    }
+    if constexpr (AOV) if (level == 0 && valid) {
+        const DevAov & aov = *aov_targets;
+        // the primary ray's RayHit (RayHit.h:4-36) as bounce() has it (Raytracer.cpp:87-145): distance (:113), point, normal, uv, material,
+        // albedo (the sky colour on a miss, :105-111) and which primitive; miss / no such field: INFINITY, 0, -1.  One lane = one pixel: a wave
+        // of an 8x8 block stores eight row segments per channel, like k_resolve's framebuffer writes.
+        const size_t p = (size_t)(uint32_t)pixel;
+        const int kind = PRIM_KIND(prim), pi = PRIM_INDEX(prim);
+        if (aov.depth) aov.depth[p] = is_hit ? t : INFINITY;
+        if (aov.position) { aov.position[3 * p + 0] = h.point.x; aov.position[3 * p + 1] = h.point.y; aov.position[3 * p + 2] = h.point.z; }
+        if (aov.normal) { aov.normal[3 * p + 0] = h.normal.x; aov.normal[3 * p + 1] = h.normal.y; aov.normal[3 * p + 2] = h.normal.z; }
+        if (aov.albedo) { aov.albedo[3 * p + 0] = albedo.x; aov.albedo[3 * p + 1] = albedo.y; aov.albedo[3 * p + 2] = albedo.z; }
+        if (aov.uv) { aov.uv[2 * p + 0] = h.u; aov.uv[2 * p + 1] = h.v; }
+        if (aov.material_id) aov.material_id[p] = is_hit ? h.material_id : -1;
+        if (aov.object_id)                                        // instances, then spheres, then planes (rtx_frame order)
+            aov.object_id[p] = !is_hit ? -1 : kind == PRIM_TRI ? pi : kind == PRIM_SPHERE ? sc.instance_count + pi : sc.instance_count + sc.sphere_count + pi;
+        if (aov.triangle_id) aov.triangle_id[p] = (is_hit && kind == PRIM_TRI) ? tri : -1;
     }
 
     if (COUNT) {
@@ -375,9 +401,11 @@ RTX_D void shade_ray(const DevScene & sc, const DevQueues & q, const int level, 
     }
 }
 
-template <bool COUNT, bool CULL, bool VIEWS = false>
+// AOV = true: launched for level 0 of a RTX_RENDER_AOV call with one more argument, the DevAov targets (Targets = DevAov); otherwise none
+template <bool COUNT, bool CULL, bool VIEWS = false, bool AOV = false, typename... Targets>
 __global__ __launch_bounds__(RTX_SHADE_BLOCK, RTX_WAVES_SHADE)
-void k_shade(const DevScene sc, const DevQueues q, const int level) {
+void k_shade(const DevScene sc, const DevQueues q, const int level, const Targets... targets) {
+    static_assert(sizeof...(Targets) == (AOV ? 1 : 0), "k_shade<.., AOV = true, DevAov> takes the AOV targets, every other instantiation nothing more");
     DevCounters * const ctr = q.counters;
     const uint32_t count = ctr->ray_count[level];
     const int lane = threadIdx.x & 63;
@@ -410,7 +438,8 @@ void k_shade(const DevScene sc, const DevQueues q, const int level) {
         const bool valid = idx < count;
         float4 h0 = make_float4(0, 0, 0, 0); int tri = 0;
         if (valid) { const uint32_t slot = (uint32_t)q.level_base[level] + idx; h0 = q.h0[slot]; tri = q.h1[slot]; }
-        shade_ray<COUNT, CULL, VIEWS>(sc, q, level, idx, valid, valid, h0, tri, block_alloc2, T);
+        if constexpr (AOV) { const DevAov aov[] = { targets... }; shade_ray<COUNT, CULL, VIEWS, true>(sc, q, level, idx, valid, valid, h0, tri, block_alloc2, T, &aov[0]); }
+        else shade_ray<COUNT, CULL, VIEWS>(sc, q, level, idx, valid, valid, h0, tri, block_alloc2, T);
     }
     // statistics: the tallies are per-wave sums; the block adds them up in LDS and ONE thread hands them on.  (One atomic per wave and
     // counter was 20 000 atomics on one cache line at the end of every level-0 launch: at the ~90 atomics/us that line sustains, two

@@ -12,7 +12,7 @@ from typing import Dict, List, Optional
 import numpy as np
 
 from . import scene_io as sio
-from .ctypes_structs import RtxConfig, RtxFrame, RtxStats, RtxWork, RtxTextureDesc, fill_frame
+from .ctypes_structs import RtxConfig, RtxFrame, RtxStats, RtxWork, RtxTextureDesc, RtxAovBuffers, AOV_CHANNELS, RTX_AOV_ALL, fill_frame
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "..", "csrc", "librtx_hip.so")
@@ -23,10 +23,11 @@ EXPORTS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error", "rt
            "rtx_bind_framebuffer", "rtx_set_stream", "rtx_present", "rtx_debug_libm", "rtx_debug_texture_sample", "rtx_debug_sky_sample", "rtx_debug_blas_wide", "rtx_debug_blas_wide_closest",
            "rtx_group_unique_id", "rtx_group_create", "rtx_group_render", "rtx_group_destroy", "rtx_group_attach", "rtx_group_create_local", "rtx_group_render_local",
            "rtx_group_layout", "rtx_group_slot_pixels", "rtx_debug_group_loopback", "rtx_debug_trace_rays", "rtx_debug_occluded", "rtx_debug_light_plot",
-           "rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer"]
+           "rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer", "rtx_bind_aovs", "rtx_read_aovs"]
 # newer than the A/B variants tools/ab.py may load (RTX_HIP_LIB = a library built from an older commit): bound when the library has them,
 # otherwise a call raises AttributeError (undefined symbol)
 VIEW_EXPORTS = ("rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer")
+AOV_EXPORTS = ("rtx_bind_aovs", "rtx_read_aovs")
 
 RTX_RENDER_COUNT_WORK = 1
 RTX_RENDER_SIMPLE_TRACE = 2
@@ -35,6 +36,7 @@ RTX_RENDER_SERIAL = 8
 RTX_RENDER_LANE_TRACE = 16
 RTX_RENDER_PACKET_STATS = 32
 RTX_RENDER_PACKET_CLOSEST = 64
+RTX_RENDER_AOV = 128
 RTX_MAX_VIEWS = 4096
 ERRORS = {1: "RTX_ERR_INVALID_ARG", 2: "RTX_ERR_NO_DEVICE", 3: "RTX_ERR_HIP", 4: "RTX_ERR_LIMIT", 5: "RTX_ERR_STATE", 6: "RTX_ERR_OOM"}
 
@@ -99,8 +101,11 @@ def load_library(path: Optional[str] = None):
         lib.rtx_render_views.argtypes = [vp, i32, i32, u32]
         lib.rtx_read_views.argtypes = [vp, i32, i32, vp, vp]
         lib.rtx_bind_view_framebuffer.argtypes = [vp, vp, vp, i32]
+    if hasattr(lib, "rtx_bind_aovs"):
+        lib.rtx_bind_aovs.argtypes = [vp, u32, C.POINTER(RtxAovBuffers), C.c_int64]
+        lib.rtx_read_aovs.argtypes = [vp, i32, i32, C.POINTER(RtxAovBuffers)]
     for name in EXPORTS:
-        if name in VIEW_EXPORTS and not hasattr(lib, name):
+        if name in VIEW_EXPORTS + AOV_EXPORTS and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         if name not in ("rtx_last_error",):
@@ -110,12 +115,42 @@ def load_library(path: Optional[str] = None):
 
 
 def render_flags(count_work: bool = False, simple_trace: bool = False, cull_dead_shadow_rays: bool = False, serial: bool = False,
-                 lane_trace: bool = False, packet_stats: bool = False, packet_closest: bool = False) -> int:
+                 lane_trace: bool = False, packet_stats: bool = False, packet_closest: bool = False, aov: bool = False) -> int:
     """The RTX_RENDER_* bits of the keyword flags Renderer.render / render_views take."""
     return ((RTX_RENDER_COUNT_WORK if count_work else 0) | (RTX_RENDER_SIMPLE_TRACE if simple_trace else 0)
             | (RTX_RENDER_CULL_DEAD_SHADOW_RAYS if cull_dead_shadow_rays else 0) | (RTX_RENDER_SERIAL if serial else 0)
             | (RTX_RENDER_LANE_TRACE if lane_trace else 0) | (RTX_RENDER_PACKET_STATS if packet_stats else 0)
-            | (RTX_RENDER_PACKET_CLOSEST if packet_closest else 0))
+            | (RTX_RENDER_PACKET_CLOSEST if packet_closest else 0) | (RTX_RENDER_AOV if aov else 0))
+
+
+def aov_names(channels) -> tuple:
+    """AOV channel names (keys of ctypes_structs.AOV_CHANNELS, in that order) of a RTX_AOV_* mask, one name or an iterable of names.
+    Raises before anything reaches the library."""
+    if isinstance(channels, (int, np.integer)) and not isinstance(channels, bool):
+        if not 0 <= int(channels) <= RTX_AOV_ALL:
+            raise ValueError(f"AOV channel mask {channels} has bits outside RTX_AOV_ALL")
+        return tuple(n for n, (bit, _, _) in AOV_CHANNELS.items() if int(channels) & bit)
+    if isinstance(channels, str):
+        channels = (channels,)
+    names = set()
+    for n in channels:
+        if not isinstance(n, str):
+            raise TypeError(f"AOV channels are names ({', '.join(AOV_CHANNELS)}), not {type(n).__name__}")
+        if n not in AOV_CHANNELS:
+            raise ValueError(f"unknown AOV channel {n!r} (known: {', '.join(AOV_CHANNELS)})")
+        names.add(n)
+    return tuple(n for n in AOV_CHANNELS if n in names)
+
+
+def aov_mask(channels) -> int:
+    """RTX_AOV_* bits of a mask, one channel name or an iterable of names."""
+    return sum(AOV_CHANNELS[n][0] for n in aov_names(channels))
+
+
+def aov_shape(name: str, views: Optional[int], height: int, width: int) -> tuple:
+    """Shape of channel `name` for `views` views ((H, W[, k]) when views is None)."""
+    k = AOV_CHANNELS[name][2]
+    return ((views,) if views is not None else ()) + (height, width) + ((k,) if k > 1 else ())
 
 
 def views_array(cameras) -> np.ndarray:
@@ -220,10 +255,10 @@ class Renderer:
 
     def render_async(self, first_tile: int = 0, tile_stride: int = 1, tile_count: Optional[int] = None, count_work: bool = False,
                      simple_trace: bool = False, cull_dead_shadow_rays: bool = False, serial: bool = False, lane_trace: bool = False,
-                     packet_stats: bool = False, packet_closest: bool = False):
+                     packet_stats: bool = False, packet_closest: bool = False, aov: bool = False):
         if tile_count is None:
             tile_count = (self.scene.tile_count - first_tile + tile_stride - 1) // tile_stride
-        flags = render_flags(count_work, simple_trace, cull_dead_shadow_rays, serial, lane_trace, packet_stats, packet_closest)
+        flags = render_flags(count_work, simple_trace, cull_dead_shadow_rays, serial, lane_trace, packet_stats, packet_closest, aov)
         self._chk(self.lib.rtx_render_tiles(self.ctx, first_tile, tile_stride, tile_count, flags), "rtx_render_tiles")
 
     def synchronize(self):
@@ -295,25 +330,81 @@ class Renderer:
         self._chk(self.lib.rtx_bind_view_framebuffer(self.ctx, rgb_ptr, packed_ptr, view_capacity), "rtx_bind_view_framebuffer")
         self._view_fb = (rgb_ptr, packed_ptr, view_capacity) if rgb_ptr else None
 
-    def render_views(self, first_view: int = 0, view_count: Optional[int] = None, **flags) -> Dict:
+    def render_views(self, first_view: int = 0, view_count: Optional[int] = None, aovs=(), **flags) -> Dict:
         """Views [first_view, first_view + view_count) of the cameras set by set_views in one rtx_render_views call (flags as render);
-        rgb (V, H, W, 3) float32, packed (V, H, W) uint32, stats / work summed over the views.  Uses the context's own view framebuffer."""
+        rgb (V, H, W, 3) float32, packed (V, H, W) uint32, stats / work summed over the views.  Uses the context's own view framebuffer.
+        aovs: AOV channel names (see bind_aovs) also returned, each (V, H, W[, k]), from the context's own AOV buffers."""
         if getattr(self, "_view_fb", None):
             self.bind_view_framebuffer(None, None)
+        names = aov_names(aovs)
+        if names:
+            self.bind_aovs(names)
+            flags = dict(flags, aov=True)
         self.render_views_async(first_view, view_count, **flags)
         stats, work = self.stats()
         rgb, packed = self.read_views(first_view, view_count)
-        return {"rgb": rgb, "packed": packed, "stats": stats, "work": work}
+        out = {"rgb": rgb, "packed": packed, "stats": stats, "work": work}
+        if names:
+            out.update(self.read_aovs(names, *self._view_range(first_view, view_count)))
+        return out
 
-    def render_views_into(self, rgb, packed, first_view: int = 0, view_count: Optional[int] = None, **flags):
+    # ---- per-pixel primary-hit AOVs (include/rtx.h: rtx_bind_aovs / rtx_read_aovs) ------------------------------------------------
+    def bind_aovs(self, channels, buffers: Optional[Dict] = None, pixel_capacity: int = 0):
+        """Channels (RTX_AOV_* mask, a name or names: depth, position, normal, albedo, uv, material_id, object_id, triangle_id) that render
+        calls with aov=True write.  buffers=None: the context's own buffers (read_aovs); else {name: device pointer} of pixel_capacity pixels
+        each — a bound channel without a pointer is not written.  Empty channels unbind."""
+        mask = aov_mask(channels)
+        dev = None
+        if buffers is not None:
+            aov_names(list(buffers))
+            dev = RtxAovBuffers()
+            for name, ptr in buffers.items():
+                setattr(dev, name, int(ptr) if ptr else None)
+        self._chk(self.lib.rtx_bind_aovs(self.ctx, mask, C.byref(dev) if dev is not None else None, int(pixel_capacity)), "rtx_bind_aovs")
+
+    def read_aovs(self, channels, first_view: int = 0, view_count: int = 1) -> Dict:
+        """Pixels of views [first_view, first_view + view_count) of the context's own AOV buffers ((0, 1) = the frame of a tiles call),
+        as {name: numpy array (view_count, H, W[, k])}."""
+        sc = self.scene
+        host = RtxAovBuffers()
+        out = {}
+        for name in aov_names(channels):
+            a = np.zeros(aov_shape(name, view_count, sc.height, sc.width), AOV_CHANNELS[name][1])
+            out[name] = a
+            setattr(host, name, a.ctypes.data)
+        self._chk(self.lib.rtx_read_aovs(self.ctx, first_view, view_count, C.byref(host)), "rtx_read_aovs")
+        return out
+
+    def render_aovs(self, channels=tuple(AOV_CHANNELS), **flags) -> Dict:
+        """The whole frame (rtx_render_tiles with RTX_RENDER_AOV, flags as render) with the context's own AOV buffers: rgb, packed, stats,
+        work and every requested channel as numpy, (H, W), (H, W, 3) or (H, W, 2)."""
+        names = aov_names(channels)
+        if not names:
+            raise ValueError("render_aovs needs at least one AOV channel")
+        self.bind_aovs(names)
+        self.render_async(aov=True, **flags)
+        stats, work = self.stats()
+        rgb, packed = self.framebuffer()
+        out = {"rgb": rgb, "packed": packed, "stats": stats, "work": work}
+        out.update({name: a[0] for name, a in self.read_aovs(names, 0, 1).items()})
+        return out
+
+    def render_views_into(self, rgb, packed, first_view: int = 0, view_count: Optional[int] = None, aovs: Optional[Dict] = None, **flags):
         """Render views into caller-owned device tensors: rgb float32 (C, H, W, 3) and packed int32 (C, H, W) of C >= first_view + view_count
         views, contiguous, on this context's GPU; view v lands in rgb[v] / packed[v].  The work is queued on torch's current stream of that
         device (rtx_set_stream: the context stays on it), so torch work queued after this call sees the images.  On torch's default stream (handle 0,
         which the C ABI reads as "the context's own stream") the work goes to a side stream that waits for the current stream and that the
-        current stream then waits for: the same ordering.  Returns at once."""
+        current stream then waits for: the same ordering.  aovs = {channel name: tensor} also writes those per-pixel AOV channels of the
+        views (see bind_aovs): float32 / int32 tensors of shape (C, H, W) or (C, H, W, k) like rgb's, checked like rgb / packed.  Returns at once."""
         import torch
         sc, dev = self.scene, self.device
         want = (("rgb", rgb, torch.float32, (sc.height, sc.width, 3)), ("packed", packed, torch.int32, (sc.height, sc.width)))
+        if aovs:
+            if not isinstance(aovs, dict):
+                raise TypeError(f"aovs must be a dict {{channel name: tensor}}, not {type(aovs).__name__}")
+            aov_names(list(aovs))
+            want += tuple((name, t, torch.float32 if AOV_CHANNELS[name][1] == np.float32 else torch.int32, aov_shape(name, None, sc.height, sc.width))
+                          for name, t in aovs.items())
         for name, t, dt, _ in want:
             if not isinstance(t, torch.Tensor):
                 raise TypeError(f"{name} must be a torch.Tensor, not {type(t).__name__}")
@@ -322,12 +413,14 @@ class Renderer:
         for name, t, _, shape in want:
             if t.dim() != len(shape) + 1 or tuple(t.shape[1:]) != shape:
                 raise ValueError(f"{name} must have shape (views, {', '.join(map(str, shape))}), not {tuple(t.shape)}")
+            if t.shape[0] != rgb.shape[0]:
+                raise ValueError(f"rgb and {name} hold different numbers of views ({rgb.shape[0]} vs {t.shape[0]})")
+        for name, t, _, _ in want:
             if not t.is_contiguous():
                 raise ValueError(f"{name} must be contiguous")
+        for name, t, _, _ in want:
             if t.device.type != "cuda" or t.device.index != dev:
                 raise ValueError(f"{name} must be on cuda:{dev} (this context's GPU), not {t.device}")
-        if rgb.shape[0] != packed.shape[0]:
-            raise ValueError(f"rgb and packed hold different numbers of views ({rgb.shape[0]} vs {packed.shape[0]})")
         first_view, view_count = self._view_range(first_view, view_count)
         if view_count < 1 or first_view < 0 or first_view + view_count > rgb.shape[0]:
             raise ValueError(f"views [{first_view}, {first_view + view_count}) do not fit tensors of {rgb.shape[0]} views")
@@ -346,10 +439,14 @@ class Renderer:
         fb = (rgb.data_ptr(), packed.data_ptr(), int(rgb.shape[0]))
         if getattr(self, "_view_fb", None) != fb:
             self.bind_view_framebuffer(*fb)
+        if aovs:
+            self.bind_aovs(list(aovs), {name: t.data_ptr() for name, t in aovs.items()}, int(rgb.shape[0]) * sc.height * sc.width)
+            flags = dict(flags, aov=True)
         self.render_views_async(first_view, view_count, **flags)
         if side is not None:
             cur.wait_stream(side)
-            rgb.record_stream(side); packed.record_stream(side)      # the caching allocator must not hand the memory out before the render is done
+            for _, t, _, _ in want:
+                t.record_stream(side)      # the caching allocator must not hand the memory out before the render is done
 
     def enable_timing(self, on: bool = True):
         self._chk(self.lib.rtx_enable_kernel_timing(self.ctx, 1 if on else 0), "rtx_enable_kernel_timing")

@@ -63,6 +63,27 @@ class RtxWork(C.Structure):
         return d
 
 
+# per-pixel primary-hit AOV channels (include/rtx.h RTX_AOV_*): name -> (bit, numpy dtype, components per pixel), in rtx_aov_buffers order
+RTX_AOV_DEPTH = 1
+RTX_AOV_POSITION = 2
+RTX_AOV_NORMAL = 4
+RTX_AOV_ALBEDO = 8
+RTX_AOV_UV = 16
+RTX_AOV_MATERIAL_ID = 32
+RTX_AOV_OBJECT_ID = 64
+RTX_AOV_TRIANGLE_ID = 128
+RTX_AOV_ALL = 255
+AOV_CHANNELS = {"depth": (RTX_AOV_DEPTH, np.float32, 1), "position": (RTX_AOV_POSITION, np.float32, 3),
+                "normal": (RTX_AOV_NORMAL, np.float32, 3), "albedo": (RTX_AOV_ALBEDO, np.float32, 3), "uv": (RTX_AOV_UV, np.float32, 2),
+                "material_id": (RTX_AOV_MATERIAL_ID, np.int32, 1), "object_id": (RTX_AOV_OBJECT_ID, np.int32, 1),
+                "triangle_id": (RTX_AOV_TRIANGLE_ID, np.int32, 1)}
+
+
+class RtxAovBuffers(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in AOV_CHANNELS]
+
+
+assert C.sizeof(RtxAovBuffers) == 64
 assert C.sizeof(RtxConfig) == 64 and C.sizeof(RtxTextureDesc) == 80 and C.sizeof(RtxCamera) == 48
 assert C.sizeof(RtxWork) == 160
 

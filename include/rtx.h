@@ -266,9 +266,11 @@ enum {
                                           by default every lane of a closest-hit packet walks its own ray from the BLAS root (private stacks in
                                           LDS), which is faster until the shared part of that walk is hand-scheduled like the shadow-ray
                                           kernel's.  Frames are bit-identical either way.                                                   */
-    RTX_RENDER_CULL_DEAD_SHADOW_RAYS = 4 /* count, but do not traverse, shadow rays whose unshadowed light contribution is exactly 0
+    RTX_RENDER_CULL_DEAD_SHADOW_RAYS = 4, /* count, but do not traverse, shadow rays whose unshadowed light contribution is exactly 0
                                           (N.L <= 0 or outside a spot cone): the pixel cannot depend on them.  Frames and
                                           rtx_stats are bit-identical with and without this flag.                                   */
+    RTX_RENDER_AOV = 128               /* also write the channels bound by rtx_bind_aovs for every primary ray of the call (see below).
+                                          Frames and rtx_stats are bit-identical with and without this flag.                        */
 };
 
 /* Renders tiles first_tile + i*tile_stride, i in [0, tile_count), numbered as
@@ -333,6 +335,53 @@ int rtx_read_views(rtx_ctx * ctx, int32_t first_view, int32_t view_count, float 
  * the context's own view framebuffer (allocated on first use, grown only); both NULL restores the own one.  Does not wait: work
  * already queued keeps writing the buffers it was queued with.                                                                     */
 int rtx_bind_view_framebuffer(rtx_ctx * ctx, void * rgb_f32_dev, void * packed_u32_dev, int32_t view_capacity);
+
+/* ---- per-pixel primary-hit AOVs (G-buffer channels) ---------------------------------------------------------------------------------
+ * What Raytracer::bounce (Raytracer.cpp:87-145) knows about the PRIMARY ray of each pixel, written next to the colour by a render call
+ * with RTX_RENDER_AOV.  The values are the frame's own: stored by the shading pass where it has them, not evaluated a second time.
+ * Channel (bit)          per pixel    hit                                                        miss
+ *   DEPTH                f32          RayHit::distance (RayHit.h:6), bounce's `distance` (:113)  +INFINITY (:107)
+ *   POSITION             3 x f32      RayHit::point, world space (RayHit.h:8)                     0
+ *   NORMAL               3 x f32      RayHit::normal, as shading uses it (RayHit.h:9)             0
+ *   ALBEDO               3 x f32      Material::get_albedo: diffuse x Texture::sample with the    Sky::sample of the ray direction (:106)
+ *                                     shading's LOD inputs (Material.h:16-22)
+ *   UV                   2 x f32      RayHit::u, v (RayHit.h:12)                                  0
+ *   MATERIAL_ID          i32          RayHit::material_id, global (RayHit.h:11)                   -1
+ *   OBJECT_ID            i32          mesh instance i -> i (rtx_frame.instances); sphere s ->     -1
+ *                                     instance_count + s; plane p -> instance_count + sphere_count + p
+ *   TRIANGLE_ID          i32          index into the triangle arrays given to rtx_upload_blas     -1 (also for spheres and planes)
+ *                                     for the instance's BLAS (flattened order, BottomLevelBVH.cpp:196-212)
+ * Pixel index: y * width + x of a rtx_render_tiles call, view * width * height + y * width + x of a rtx_render_views call; only the
+ * rendered pixels are written (clipped slots of edge tiles and tiles outside the call are left as they are).  Not available in
+ * heat-map mode, nor on the rtx_group_* path.                                                                                        */
+enum {
+    RTX_AOV_DEPTH = 1, RTX_AOV_POSITION = 2, RTX_AOV_NORMAL = 4, RTX_AOV_ALBEDO = 8, RTX_AOV_UV = 16,
+    RTX_AOV_MATERIAL_ID = 32, RTX_AOV_OBJECT_ID = 64, RTX_AOV_TRIANGLE_ID = 128,
+    RTX_AOV_ALL = 255
+};
+typedef struct rtx_aov_buffers {       /* one pointer per channel, NULL = not written / not read */
+    float   * depth;                   /* [pixels]     */
+    float   * position;                /* [pixels][3]  */
+    float   * normal;                  /* [pixels][3]  */
+    float   * albedo;                  /* [pixels][3]  */
+    float   * uv;                      /* [pixels][2]  */
+    int32_t * material_id;             /* [pixels]     */
+    int32_t * object_id;               /* [pixels]     */
+    int32_t * triangle_id;             /* [pixels]     */
+} rtx_aov_buffers;
+/* Bind the channels in `channels` (RTX_AOV_* bits) for render calls with RTX_RENDER_AOV.  device != NULL: caller-owned device buffers of
+ * pixel_capacity pixels each; a channel is written only if its bit is set and its pointer is not NULL.  device == NULL: the context's own
+ * buffers (allocated on first use, grown only, like the view framebuffer; read with rtx_read_aovs).  channels == 0 unbinds.  Does not
+ * wait: work already queued keeps writing the buffers it was queued with.  RTX_ERR_INVALID_ARG: unknown bits, or device != NULL with
+ * pixel_capacity < 1.
+ * A render call with RTX_RENDER_AOV returns RTX_ERR_STATE when nothing is bound or the context is in heat-map mode (no shading), and
+ * RTX_ERR_INVALID_ARG when its pixel range — [0, width*height) for rtx_render_tiles, [0, (first_view + view_count)*width*height) for
+ * rtx_render_views — exceeds pixel_capacity.  rtx_group_render* with it returns RTX_ERR_INVALID_ARG.                                 */
+int rtx_bind_aovs(rtx_ctx * ctx, uint32_t channels, const rtx_aov_buffers * device, int64_t pixel_capacity);
+/* pixels [first_view*W*H, (first_view + view_count)*W*H) of the context's own AOV buffers to host (waits for the context's stream); a
+ * tiles call is (0, 1).  NULL host pointers are skipped.  RTX_ERR_STATE while caller buffers are bound; RTX_ERR_INVALID_ARG for a channel
+ * whose own buffer does not hold the range (never bound, or bound for fewer pixels than rendered).                                  */
+int rtx_read_aovs(rtx_ctx * ctx, int32_t first_view, int32_t view_count, const rtx_aov_buffers * host);
 
 /* Timing of every kernel launched since rtx_enable_kernel_timing(ctx, 1),
  * measured with HIP events on the stream the kernels are launched on.
