@@ -68,6 +68,12 @@ def lib():
         _lib.orc_trace_closest.argtypes = [C.POINTER(OrcScene), C.c_void_p, C.c_void_p]
         _lib.orc_trace_any.restype = C.c_int
         _lib.orc_trace_any.argtypes = [C.POINTER(OrcScene), C.c_void_p, C.c_void_p, C.c_float]
+        _lib.orc_trace_closest_ids.restype = None
+        _lib.orc_trace_closest_ids.argtypes = [C.POINTER(OrcScene), C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.orc_trace_closest_n.restype = C.c_int
+        _lib.orc_trace_closest_n.argtypes = [C.POINTER(OrcScene), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+        _lib.orc_trace_any_n.restype = C.c_int
+        _lib.orc_trace_any_n.argtypes = [C.POINTER(OrcScene), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
         _lib.orc_calc_lighting.restype = None
         _lib.orc_calc_lighting.argtypes = [C.c_void_p] * 6 + [C.c_float, C.c_void_p]
         _lib.orc_ewa_table.restype = None
@@ -131,6 +137,30 @@ class OracleScene:
         if want_dist:
             out["dist"] = dist
         return out
+
+    def trace_closest(self, rays18: np.ndarray, threads: int = 8) -> Tuple[np.ndarray, np.ndarray]:
+        """Scene::trace_primitives of n rays: (hits (n, 27) float32 in orc_trace_closest's layout, ids (n, 3) int32: material, object,
+        triangle id as the RTX_AOV_*_ID channels number them, -1 where there is none)."""
+        r = np.ascontiguousarray(rays18, np.float32).reshape(-1, 18)
+        out = np.zeros((len(r), 27), np.float32)
+        ids = np.zeros((len(r), 3), np.int32)
+        rc = lib().orc_trace_closest_n(C.byref(self.struct), len(r), r.ctypes.data, out.ctypes.data, ids.ctypes.data, threads)
+        if rc != 0:
+            raise RuntimeError(f"orc_trace_closest_n failed: {rc}")
+        return out, ids
+
+    def trace_any(self, rays18: np.ndarray, max_distance: np.ndarray, threads: int = 8) -> np.ndarray:
+        """Scene::intersect_primitives of n rays (origin and direction: columns 0..5) at k max distances each (max_distance (n, k) or
+        (n,)): bool array of max_distance's shape."""
+        r = np.ascontiguousarray(rays18, np.float32).reshape(-1, 18)
+        md = np.asarray(max_distance, np.float32)
+        shape = md.shape
+        md = np.ascontiguousarray(md.reshape(len(r), -1))
+        occ = np.zeros(md.shape, np.int32)
+        rc = lib().orc_trace_any_n(C.byref(self.struct), len(r), r.ctypes.data, md.shape[1], md.ctypes.data, occ.ctypes.data, threads)
+        if rc != 0:
+            raise RuntimeError(f"orc_trace_any_n failed: {rc}")
+        return (occ != 0).reshape(shape)
 
 
 def gamma_lut() -> np.ndarray:

@@ -57,6 +57,23 @@ def stage():
     synthetic_sky().tofile(os.path.join(data, "Sky_Probes", "rnl_probe.float"))
 
 
+def stage_fixture_meshes(scene_dir):
+    """Copy the repo's own mesh fixtures (tests/golden/<scene_dir>/*.obj, *.mtl) into the staged Data/.  The reference caches a mesh's BVH
+    next to it (<mesh>.bvh, BottomLevelBVH.cpp:26); a cache older than a changed mesh is dropped."""
+    data = os.path.join(WORK, "Data")
+    for f in sorted(os.listdir(os.path.join(OUT, scene_dir))):
+        if f.split(".")[-1] not in ("obj", "mtl"):
+            continue
+        src, dst = os.path.join(OUT, scene_dir, f), os.path.join(data, f)
+        new = open(src, "rb").read()
+        if os.path.exists(dst) and open(dst, "rb").read() == new:
+            continue
+        with open(dst, "wb") as g:
+            g.write(new)
+        if os.path.exists(dst + ".bvh"):
+            os.remove(dst + ".bvh")
+
+
 def run_ref(variant, script_path, name):
     exe = os.path.join(REPO, "oracle", "_ref", "refdump_" + variant)
     if not os.path.exists(exe):
@@ -139,6 +156,17 @@ def main():
     if "--knobs-only" in sys.argv:
         knob_goldens()
         return
+
+    def coincident_golden():
+        # coincident geometry (scenes/coincident.txt): two Cube.obj instances at bit-identical transforms, a mesh whose front face is
+        # Cube.obj's in a TLAS leaf of its own, a mesh with every face doubled in another material, a plane in the plane of the bottom
+        # faces, a camera on box planes.  Tied primitives differ in material, so the frame shows which one the BLAS and TLAS walks
+        # tested first.  The meshes are this repo's fixtures (tests/golden/coincident).
+        stage_fixture_meshes("coincident")
+        golden("coincident", "coincident", "s0_m1_b3_t2")
+    if "--coincident-only" in sys.argv:
+        coincident_golden()
+        return
     # BVH_VISUALIZE_HEATMAP builds (Config.h:23, Raytracer.cpp:97-102): same scenes, pixels = BLAS traversal steps
     golden("monkey_small", "monkey_small", "s0_m1_b3_t2_heat", keep_scene=False, tag="heat")
     golden("materials", "materials", "s0_m1_b3_t2_heat", extra=mat_extra[:2], keep_scene=False, tag="heat")
@@ -169,6 +197,7 @@ def main():
     golden("dynamic", "dynamic", "s1_m2_b3_t2", extra=["size 320 180"])
     golden("tori16", "tori16", "s1_m2_b3_t2", extra=["size 320 180"])
     golden("tori16_f1", "tori16", "s1_m2_b3_t2", extra=["size 320 180", "frames 1 0.0166666667"])
+    coincident_golden()
 
     total = 0
     for root, _, files in os.walk(OUT):

@@ -122,6 +122,7 @@ int main(int argc, char ** argv) {
 
 	int W = 256, H = 256, bounces = NUMBER_OF_BOUNCES, frames = 1; float delta = 0.0f;
 	int unit_n = 0; unsigned unit_seed = 1;
+	std::string rayprobe_path; int rayprobe_n = 0;
 	bool keep_base = false, drop_base_meshes = false, have_camera = false, have_ambient = false;
 	Vector3 cam_pos; Quaternion cam_rot; Vector3 ambient;
 	std::vector<MeshSpec> meshes;
@@ -173,6 +174,7 @@ int main(int argc, char ** argv) {
 			else if (w[0] == "matset")  { MatEdit e; e.target = w[1]; e.field = w[2]; e.args.assign(w.begin() + 3, w.end()); edits.push_back(e); }
 			else if (w[0] == "texprobe") { probes.push_back({ w[1], atoi(w[2].c_str()), (unsigned)strtoul(w[3].c_str(), nullptr, 0) }); }
 			else if (w[0] == "unitprobe") { unit_n = atoi(w[1].c_str()); unit_seed = (unsigned)strtoul(w[2].c_str(), nullptr, 0); }
+			else if (w[0] == "rayprobe")  { rayprobe_path = w[1]; rayprobe_n = atoi(w[2].c_str()); }
 			else { fprintf(stderr, "unknown script command '%s'\n", w[0].c_str()); return 2; }
 		}
 	}
@@ -655,6 +657,42 @@ int main(int argc, char ** argv) {
 			memcpy(&r[3], &px, 4);
 		}
 		dump("unit_plot.f32", pq.data(), pq.size() * 4);
+	}
+
+	// ---- ray probes: caller-supplied rays (tests/rayset.py) through Scene::trace_primitives and Scene::intersect_primitives ---------
+	// in:  <file> n records of RAYPROBE_IN floats: origin, direction, dO_dx, dO_dy, dD_dx, dD_dy (18), max distances (RAYPROBE_DIST)
+	// out: rayprobe.f32 n records: the RayHit fields as unit_rays.f32 has them (27), then intersect_primitives at each max distance (RAYPROBE_DIST)
+	if (rayprobe_n > 0) {
+		enum { RAYPROBE_DIST = 7, RAYPROBE_IN = 18 + RAYPROBE_DIST, RAYPROBE_OUT = 27 + RAYPROBE_DIST };
+		std::vector<float> in((size_t)rayprobe_n * RAYPROBE_IN), io((size_t)rayprobe_n * RAYPROBE_OUT);
+		FILE * f = fopen(rayprobe_path.c_str(), "rb");
+		if (!f || fread(in.data(), 4, in.size(), f) != in.size()) { fprintf(stderr, "cannot read %d rays from %s\n", rayprobe_n, rayprobe_path.c_str()); return 2; }
+		fclose(f);
+		for (int i = 0; i < rayprobe_n; i++) {
+			const float * r = &in[(size_t)RAYPROBE_IN * i];
+			float * q = &io[(size_t)RAYPROBE_OUT * i];
+			const Vector3 o(r[0], r[1], r[2]), d(r[3], r[4], r[5]);
+			Ray ray;
+			ray.origin = SIMD_Vector3(o); ray.direction = SIMD_Vector3(d);
+#if RAY_DIFFERENTIALS_ENABLED
+			ray.dO_dx = SIMD_Vector3(Vector3(r[6], r[7], r[8]));    ray.dO_dy = SIMD_Vector3(Vector3(r[9], r[10], r[11]));
+			ray.dD_dx = SIMD_Vector3(Vector3(r[12], r[13], r[14])); ray.dD_dy = SIMD_Vector3(Vector3(r[15], r[16], r[17]));
+#endif
+			RayHit h;
+			memset(&h, 0, sizeof(h)); h.hit = SIMD_float(0.0f); h.distance = SIMD_float(INFINITY);
+			scene.trace_primitives(ray, h);
+			q[0] = SIMD_float::all_false(h.hit) ? 0.0f : 1.0f; q[1] = h.distance[0];
+			q[2] = h.point.x[0]; q[3] = h.point.y[0]; q[4] = h.point.z[0]; q[5] = h.normal.x[0]; q[6] = h.normal.y[0]; q[7] = h.normal.z[0];
+			q[8] = (float)h.material_id[0]; q[9] = h.u[0]; q[10] = h.v[0];
+#if RAY_DIFFERENTIALS_ENABLED
+			q[11] = h.ds_dx[0]; q[12] = h.ds_dy[0]; q[13] = h.dt_dx[0]; q[14] = h.dt_dy[0];
+			q[15] = h.dO_dx.x[0]; q[16] = h.dO_dx.y[0]; q[17] = h.dO_dx.z[0]; q[18] = h.dO_dy.x[0]; q[19] = h.dO_dy.y[0]; q[20] = h.dO_dy.z[0];
+			q[21] = h.dN_dx.x[0]; q[22] = h.dN_dx.y[0]; q[23] = h.dN_dx.z[0]; q[24] = h.dN_dy.x[0]; q[25] = h.dN_dy.y[0]; q[26] = h.dN_dy.z[0];
+#endif
+			for (int k = 0; k < RAYPROBE_DIST; k++)
+				q[27 + k] = SIMD_float::all_false(scene.intersect_primitives(ray, SIMD_float(r[18 + k]))) ? 0.0f : 1.0f;
+		}
+		dump("rayprobe.f32", io.data(), io.size() * 4);
 	}
 
 	{

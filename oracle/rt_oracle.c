@@ -79,6 +79,9 @@ typedef struct {          /* RayHit.h:4-36 */
     float ds_dx, ds_dy, dt_dx, dt_dy;
     v3    dO_dx, dO_dy, dN_dx, dN_dy;
     int   bvh_steps;      /* RayHit.h:24-26 (BVH_VISUALIZE_HEATMAP) */
+    /* not in RayHit: which primitive won, numbered as rtx.h documents RTX_AOV_OBJECT_ID / RTX_AOV_TRIANGLE_ID (-1: none).
+     * cur_object is the object whose primitives are being tested; the accept branches copy it. */
+    int   object_id, triangle_id, cur_object;
 } hit_t;
 
 typedef struct {
@@ -139,6 +142,7 @@ static void triangle_trace(const orc_blas * b, int index, const ray_t * ray, hit
     const rtx_triangle_cold * tc = &b->tri_cold[index];
     h->hit      = 1;
     h->distance = t;
+    h->object_id = h->cur_object; h->triangle_id = index;
 
     v3 n_edge_1 = v3p(tc->normal_edge_1);
     v3 n_edge_2 = v3p(tc->normal_edge_2);
@@ -292,8 +296,10 @@ static void tlas_trace(const orc_scene * sc, const ray_t * ray, hit_t * h, count
         c->work.tlas_nodes_closest++;
         if (!aabb_intersect(node, ray->origin, inv_dir, h->distance)) continue;
         if (((uint32_t)node->count & ~AXIS_MASK) > 0) {
-            for (int i = node->left_or_first; i < node->left_or_first + node->count; i++)
+            for (int i = node->left_or_first; i < node->left_or_first + node->count; i++) {
+                h->cur_object = fr->tlas_indices[i];
                 mesh_trace(sc, &fr->instances[fr->tlas_indices[i]], ray, h, c);
+            }
         } else {
             if (visit_left_first(node, ray->direction, sc->config.traversal_strategy)) {
                 stack[stack_size++] = node->left_or_first + 1;
@@ -356,6 +362,7 @@ static void sphere_trace(const rtx_sphere * sp, const ray_t * ray, hit_t * h) {
     const float one_over_r = sp->radius_inv;
     h->hit = 1;
     h->distance = t;
+    h->object_id = h->cur_object; h->triangle_id = -1;
     h->point  = vadd(ray->origin, vmuls(ray->direction, t));
     h->normal = vmuls(vsub(h->point, center), one_over_r);
     h->material_id = sp->material_id;
@@ -402,6 +409,7 @@ static void plane_trace(const rtx_plane * pl, const ray_t * ray, hit_t * h) {
     if (!((t > RAY_EPSILON) & (t < h->distance))) return;
     h->hit = 1;
     h->distance = t;
+    h->object_id = h->cur_object; h->triangle_id = -1;
     h->point  = vadd(ray->origin, vmuls(ray->direction, t));
     h->normal = normal;
     h->material_id = pl->material_id;
@@ -437,8 +445,8 @@ static int plane_intersect(const rtx_plane * pl, v3 origin, v3 direction, float 
 static void scene_trace(const orc_scene * sc, const ray_t * ray, hit_t * h, counters_t * c) {
     const rtx_frame * fr = &sc->frame;
     c->work.closest_rays++;
-    for (int i = 0; i < fr->sphere_count; i++) sphere_trace(&fr->spheres[i], ray, h);
-    for (int i = 0; i < fr->plane_count;  i++) plane_trace (&fr->planes[i],  ray, h);
+    for (int i = 0; i < fr->sphere_count; i++) { h->cur_object = fr->instance_count + i;                   sphere_trace(&fr->spheres[i], ray, h); }
+    for (int i = 0; i < fr->plane_count;  i++) { h->cur_object = fr->instance_count + fr->sphere_count + i; plane_trace (&fr->planes[i],  ray, h); }
     tlas_trace(sc, ray, h, c);
 }
 
@@ -929,8 +937,13 @@ int orc_render_tiles(const orc_scene * scene, int32_t first_tile, int32_t tile_s
     for (int i = 0; i < threads; i++) { wa[i].job = &job; wa[i].tid = i; }
     if (threads == 1) worker(&wa[0]);
     else {
-        for (int i = 0; i < threads; i++) pthread_create(&th[i], NULL, worker, &wa[i]);
-        for (int i = 0; i < threads; i++) pthread_join(th[i], NULL);
+        /* a worker that cannot be started runs here instead, with its own counters: it drains the same tile counter */
+        int * started = (int *)calloc((size_t)threads, sizeof(int));
+        if (!started) { free(job.per_thread); free(th); free(wa); return RTX_ERR_OOM; }
+        for (int i = 0; i < threads; i++) started[i] = pthread_create(&th[i], NULL, worker, &wa[i]) == 0;
+        for (int i = 0; i < threads; i++) if (!started[i]) worker(&wa[i]);
+        for (int i = 0; i < threads; i++) if (started[i]) pthread_join(th[i], NULL);
+        free(started);
     }
     counters_t total; memset(&total, 0, sizeof(total));
     for (int i = 0; i < threads; i++) {
@@ -945,11 +958,11 @@ int orc_render_tiles(const orc_scene * scene, int32_t first_tile, int32_t tile_s
     return RTX_OK;
 }
 
-void orc_trace_closest(const orc_scene * scene, const float r[18], float out[27]) {
+static void trace_closest_one(const orc_scene * scene, const float r[18], float out[27], int32_t * ids3) {
     ray_t ray;
     ray.origin = v3p(r); ray.direction = v3p(r + 3);
     ray.dO_dx = v3p(r + 6); ray.dO_dy = v3p(r + 9); ray.dD_dx = v3p(r + 12); ray.dD_dy = v3p(r + 15);
-    hit_t h; memset(&h, 0, sizeof(h)); h.distance = INFINITY;
+    hit_t h; memset(&h, 0, sizeof(h)); h.distance = INFINITY; h.object_id = h.triangle_id = -1;
     counters_t c; memset(&c, 0, sizeof(c));
     scene_trace(scene, &ray, &h, &c);
     out[0] = (float)h.hit; out[1] = h.distance;
@@ -961,6 +974,75 @@ void orc_trace_closest(const orc_scene * scene, const float r[18], float out[27]
     out[18] = h.dO_dy.x; out[19] = h.dO_dy.y; out[20] = h.dO_dy.z;
     out[21] = h.dN_dx.x; out[22] = h.dN_dx.y; out[23] = h.dN_dx.z;
     out[24] = h.dN_dy.x; out[25] = h.dN_dy.y; out[26] = h.dN_dy.z;
+    if (ids3) {
+        ids3[0] = h.hit ? h.material_id : -1;
+        ids3[1] = h.hit ? h.object_id : -1;
+        ids3[2] = h.hit ? h.triangle_id : -1;
+    }
+}
+
+void orc_trace_closest(const orc_scene * scene, const float r[18], float out[27]) {
+    trace_closest_one(scene, r, out, NULL);
+}
+
+void orc_trace_closest_ids(const orc_scene * scene, const float r[18], float out[27], int32_t ids3[3]) {
+    trace_closest_one(scene, r, out, ids3);
+}
+
+/* Batch forms: rays split into `threads` contiguous ranges, one pthread each (the results do not depend on the split). */
+typedef struct {
+    const orc_scene * sc; const float * rays; const float * maxd; float * out; int32_t * ids; int32_t * occ;
+    int32_t k, lo, hi;
+} batch_t;
+
+static void * closest_worker(void * p) {
+    const batch_t * b = (const batch_t *)p;
+    for (int32_t i = b->lo; i < b->hi; i++)
+        trace_closest_one(b->sc, b->rays + 18 * (size_t)i, b->out + 27 * (size_t)i, b->ids ? b->ids + 3 * (size_t)i : NULL);
+    return NULL;
+}
+
+static void * any_worker(void * p) {
+    const batch_t * b = (const batch_t *)p;
+    counters_t c; memset(&c, 0, sizeof(c));
+    for (int32_t i = b->lo; i < b->hi; i++) {
+        const float * r = b->rays + 18 * (size_t)i;
+        for (int32_t j = 0; j < b->k; j++)
+            b->occ[(size_t)i * b->k + j] = scene_intersect(b->sc, v3p(r), v3p(r + 3), b->maxd[(size_t)i * b->k + j], &c);
+    }
+    return NULL;
+}
+
+static int run_batch(batch_t * proto, int32_t n, int32_t threads, void * (*fn)(void *)) {
+    if (threads < 1) threads = 1;
+    if (threads > 256) threads = 256;
+    if (threads > n) threads = n > 0 ? n : 1;
+    batch_t jobs[256]; pthread_t th[256];
+    for (int t = 0; t < threads; t++) {
+        jobs[t] = *proto;
+        jobs[t].lo = (int32_t)((int64_t)n * t / threads); jobs[t].hi = (int32_t)((int64_t)n * (t + 1) / threads);
+    }
+    int started[256];
+    for (int t = 0; t < threads; t++) {
+        started[t] = threads > 1 && pthread_create(&th[t], NULL, fn, &jobs[t]) == 0;
+        if (!started[t]) fn(&jobs[t]);                      /* no thread (or one asked for): the range runs here */
+    }
+    for (int t = 0; t < threads; t++) if (started[t]) pthread_join(th[t], NULL);
+    return RTX_OK;
+}
+
+int orc_trace_closest_n(const orc_scene * scene, int32_t n, const float * rays18, float * out27, int32_t * ids3, int32_t threads) {
+    if (!scene || n < 0 || (n > 0 && (!rays18 || !out27))) return RTX_ERR_INVALID_ARG;
+    batch_t b; memset(&b, 0, sizeof(b));
+    b.sc = scene; b.rays = rays18; b.out = out27; b.ids = ids3;
+    return run_batch(&b, n, threads, closest_worker);
+}
+
+int orc_trace_any_n(const orc_scene * scene, int32_t n, const float * rays18, int32_t k, const float * max_distance, int32_t * occluded, int32_t threads) {
+    if (!scene || n < 0 || k < 0 || (n > 0 && k > 0 && (!rays18 || !max_distance || !occluded))) return RTX_ERR_INVALID_ARG;
+    batch_t b; memset(&b, 0, sizeof(b));
+    b.sc = scene; b.rays = rays18; b.k = k; b.maxd = max_distance; b.occ = occluded;
+    return run_batch(&b, n, threads, any_worker);
 }
 
 /* PointLight / SpotLight / DirectionalLight::calc_lighting at one set of inputs (PointLight.h:9-11, SpotLight.h:17-33, DirectionalLight.h:9-11) */

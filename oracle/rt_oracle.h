@@ -73,6 +73,16 @@ void     orc_ewa_table(float out[RTX_EWA_LUT_SIZE]);
 void orc_trace_closest(const orc_scene * scene, const float ray[18], float hit_out[27]);
 int  orc_trace_any(const orc_scene * scene, const float origin[3], const float direction[3], float max_distance);
 
+/* orc_trace_closest plus the winner's ids (not RayHit fields): ids3 = material id, object id, triangle id, numbered as
+ * RTX_AOV_MATERIAL_ID / RTX_AOV_OBJECT_ID / RTX_AOV_TRIANGLE_ID (rtx.h), -1 where the channel has no value (miss; triangle id of
+ * a sphere or plane).                                                                                                              */
+void orc_trace_closest_ids(const orc_scene * scene, const float ray[18], float hit_out[27], int32_t ids3[3]);
+
+/* Batch forms over n rays of 18 floats, on `threads` threads.  orc_trace_closest_n: out27 per ray, ids3 per ray (may be NULL).
+ * orc_trace_any_n: k max distances per ray (n*k, row-major), occluded[i*k+j] = orc_trace_any(ray i, max_distance[i*k+j]).   */
+int  orc_trace_closest_n(const orc_scene * scene, int32_t n, const float * rays18, float * out27, int32_t * ids3, int32_t threads);
+int  orc_trace_any_n(const orc_scene * scene, int32_t n, const float * rays18, int32_t k, const float * max_distance, int32_t * occluded, int32_t threads);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 
 Every channel is what Raytracer::bounce has for the pixel's primary ray: depth must equal the oracle's `dist` output bit for bit, the
 hit fields must equal orc_trace_closest on the primary ray rebuilt with the oracle's render_tile arithmetic, the albedo Material::diffuse x
-Texture::sample of the oracle (or its Sky::sample on a miss), and the ids must name a primitive the ray hits at that depth.  The colour,
+Texture::sample of the oracle (or its Sky::sample on a miss), and the ids must be the oracle's winner (orc_trace_closest_ids) and name a
+primitive the ray hits at that depth.  The colour,
 packed pixels and ray counts of an AOV call must equal the call without it in every launch shape.
 """
 import ctypes as C
@@ -19,7 +20,7 @@ pytestmark = pytest.mark.gpu
 f32 = np.float32
 ALL = ("depth", "position", "normal", "albedo", "uv", "material_id", "object_id", "triangle_id")
 IDS = ("material_id", "object_id", "triangle_id")
-SCENES = ["cube", "materials_aniso", "materials_ewa", "materials_bilinear", "monkey_small", "tori16", "dynamic", "ragged"]
+SCENES = ["cube", "materials_aniso", "materials_ewa", "materials_bilinear", "monkey_small", "tori16", "dynamic", "ragged", "coincident"]
 
 
 @pytest.fixture(scope="module")
@@ -73,14 +74,15 @@ _ORACLE = {}
 
 
 def oracle(name, sc):
-    """dist of orc render (want_dist) and, per pixel, orc_trace_closest of the primary ray, the oracle's albedo and sky colour."""
+    """dist of orc render (want_dist) and, per pixel, orc_trace_closest_ids of the primary ray (hit fields and the winner's material,
+    object and triangle ids), the oracle's albedo and sky colour."""
     if name in _ORACLE:
         return _ORACLE[name]
     import orc
     o = orc.OracleScene(sc); L = orc.lib()
     dist = o.render(threads=8, want_dist=True)["dist"].reshape(-1)
     rays = primary_rays(sc)
-    hits = np.zeros((len(rays), 27), f32)
+    hits, ids = o.trace_closest(rays)
     albedo = np.zeros((len(rays), 3), f32)
     cfg = sc.config
     mode, filt, aniso = int(cfg["texture_mode"][0]), int(cfg["mip_filter"][0]), float(cfg["max_anisotropy"][0])
@@ -88,7 +90,6 @@ def oracle(name, sc):
     tex = np.zeros(3, f32)
     for p in range(len(rays)):
         r = rays[p]
-        L.orc_trace_closest(C.byref(o.struct), r.ctypes.data, hits[p].ctypes.data)
         h = hits[p]
         if h[0] > 0:
             m = sc.materials[int(h[8])]
@@ -101,7 +102,7 @@ def oracle(name, sc):
         else:
             d = np.ascontiguousarray(r[3:6])
             L.orc_sky_sample(o._sky.ctypes.data, o.struct.sky_size, d.ctypes.data, albedo[p].ctypes.data)
-    _ORACLE[name] = (dist, rays, hits, albedo)
+    _ORACLE[name] = (dist, rays, hits, albedo, ids)
     return _ORACLE[name]
 
 
@@ -119,7 +120,7 @@ def test_channels_match_the_oracle(api, name):
     for ch, shape in (("depth", (H, W)), ("position", (H, W, 3)), ("normal", (H, W, 3)), ("albedo", (H, W, 3)), ("uv", (H, W, 2)),
                       ("material_id", (H, W)), ("object_id", (H, W)), ("triangle_id", (H, W))):
         assert out[ch].shape == shape, ch
-    dist, rays, hits, albedo = oracle(name, sc)
+    dist, rays, hits, albedo, ids = oracle(name, sc)
     # the rebuilt primary rays are the oracle's: orc_trace_closest finds the distance its own render reports, +inf on a miss
     assert_same(hits[:, 1], dist, "orc_trace_closest distance vs oracle render dist")
     assert_same(flat(out, "depth"), dist, "depth")
@@ -135,6 +136,9 @@ def test_channels_match_the_oracle(api, name):
         assert not flat(out, ch)[~hit].any(), ch
     for ch in IDS:
         assert (flat(out, ch)[~hit] == -1).all(), ch
+    # the winner itself, not merely a primitive at that depth: a coplanar neighbour or a coincident instance is a different id
+    for k, ch in enumerate(IDS):
+        assert_same(flat(out, ch), ids[:, k], ch)
     check_ids(sc, out, rays)
 
 

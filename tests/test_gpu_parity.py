@@ -336,7 +336,7 @@ def test_shadow_walk_uses_wide_records_for_reference_trees_and_binary_walk_other
 
 
 @pytest.mark.parametrize("lane_from", ["99", "1", "3"])
-@pytest.mark.parametrize("name", ["dynamic", "tori16", "materials_aniso"])
+@pytest.mark.parametrize("name", ["dynamic", "tori16", "materials_aniso", "coincident"])
 def test_per_level_kernel_selection_changes_nothing(api, name, lane_from, monkeypatch):
     """Multi-instance scenes trace levels >= 2 with the per-lane kernels by default (csrc/rtx_api.hip, `lane_from`); whatever the split —
     packets at every level (99), per-lane from level 1 or 3 — the frame is the reference's, in both launch shapes."""
@@ -362,13 +362,33 @@ def test_split_shadow_walk_changes_nothing(api, name, split, monkeypatch):
         assert cmp["stats_equal"] and cmp["max_abs"] == 0.0 and cmp["n_diff_pixels"] == 0 and cmp["packed_mismatch"] == 0, (mode, cmp)
 
 
+@pytest.mark.parametrize("knobs", [{"RTX_PK_WIDE": "0"}, {"RTX_PK4_ORDER": "0"}, {"RTX_PK_ORDER": "0"}, {"RTX_PK_DEFER": "0"}, {"RTX_PK_DEFER": "64"},
+                                   {"RTX_PK_DEFER_LEAF": "0"}, {"RTX_PK_DEFER_LEAF": "64"}, {"RTX_PK_GROW": "0"}, {"RTX_PK_GROW": "31"},
+                                   {"RTX_SERIAL_MERGE_ANY": "0"}],
+                         ids=["binary_walk", "pk4_stack_order", "no_pk_order", "defer_0", "defer_64", "defer_leaf_0", "defer_leaf_64", "grow_0",
+                              "grow_31", "serial_per_level_any"])
+@pytest.mark.parametrize("name", ["monkey_small", "materials_aniso", "dynamic", "tori16", "coincident"])
+def test_shadow_walk_knobs_change_nothing(api, name, knobs, monkeypatch):
+    """The shadow-ray walk's schedule knobs (read in rtx_create): the binary walk instead of the 4-wide records (RTX_PK_WIDE=0), the records'
+    slot order (RTX_PK4_ORDER), the packet's child order (RTX_PK_ORDER), the hand-over thresholds of the shared walk (RTX_PK_DEFER,
+    RTX_PK_DEFER_LEAF, RTX_PK_GROW) at their extremes, and one shadow-ray launch per level in the one-stream shape (RTX_SERIAL_MERGE_ANY=0):
+    always the reference's frame and ray counts, in both launch shapes."""
+    for k, v in knobs.items():
+        monkeypatch.setenv(k, v)
+    sc, g = util.load_golden(name)
+    r = api.Renderer(sc)
+    for mode in ({}, {"serial": True}, {"serial": True, "cull_dead_shadow_rays": True}):
+        cmp = util.compare_to_golden(r.render(**mode), g)
+        assert cmp["stats_equal"] and cmp["max_abs"] == 0.0 and cmp["n_diff_pixels"] == 0 and cmp["packed_mismatch"] == 0, (knobs, mode, cmp)
+
+
 @pytest.mark.parametrize("knobs", [{"RTX_FUSE_SHADE": "1"}, {"RTX_PK_CLOSEST_ASM": "0", "RTX_PK_DEFER_PRIMARY": "8"}, {"RTX_PK_DEFER_PRIMARY": "64"},
                                    {"RTX_PK_DEFER_PRIMARY": "1", "RTX_PK_DEFER_CLOSEST": "2"}, {"RTX_PK_DEFER_PRIMARY": "16", "RTX_PK_DEFER_CLOSEST": "16", "RTX_LANE_FROM_LEVEL": "99"},
                                    {"RTX_PK_WIDE_CLOSEST": "0"}, {"RTX_PK_WIDE_CLOSEST": "0", "RTX_PK_DEFER_PRIMARY": "64", "RTX_LANE_FROM_LEVEL": "99"},
                                    {"RTX_PK_CLOSEST_ASM": "0", "RTX_PK_DEFER_PRIMARY": "8", "RTX_PK_WIDE_CLOSEST": "0"}],
                          ids=["fused_shade", "compiled_shared_walk", "all_private", "share_everything", "share_all_levels_packets_everywhere",
                               "binary_private_walk", "binary_private_walk_all_private_packets_everywhere", "compiled_shared_walk_binary_private_walk"])
-@pytest.mark.parametrize("name", ["materials_aniso", "dynamic", "tori16", "materials_b5", "materials_naive"])
+@pytest.mark.parametrize("name", ["materials_aniso", "dynamic", "tori16", "materials_b5", "materials_naive", "coincident"])
 def test_closest_hit_walk_variants_change_nothing(api, name, knobs, monkeypatch):
     """Round 3's closest-hit choices are scheduling decisions: the hand-scheduled shared walk (pk_blas_closest_asm) with any hand-over
     threshold, for primary packets only or for every level, the compiled shared walk it replaced (RTX_PK_CLOSEST_ASM=0), every lane private,

@@ -32,6 +32,8 @@ GOLDENS = {
     "dynamic": ("dynamic", None, {}),
     "tori16": ("tori16", None, {}),
     "tori16_f1": ("tori16_f1", None, {}),
+    # exact ties: two instances at bit-identical transforms, a plane in their bottom faces' plane, a camera on box planes (make_goldens.py)
+    "coincident": ("coincident", None, {}),
 }
 
 
@@ -91,3 +93,21 @@ def compare_to_fullsize_golden(out, g):
             "packed_equal": bool(np.array_equal(out["packed"][g["ys"], g["xs"]], g["packed"])),
             "stats_equal": [int(out["stats"][k]) for k in ("primary", "shadow", "reflection", "refraction")] == g["stats"].tolist(),
             "channel_sums_equal": bool(np.array_equal(sums, g["channel_sums"]))}
+
+
+# reference-pinned ray probes (tests/golden/unit/rayprobe_<name>.npz, oracle/ref_harness/make_ray_goldens.py): name -> golden scene
+RAY_PROBES = {"materials": "materials_aniso", "coincident": "coincident"}
+
+
+def load_ray_probe(name):
+    """rays (n, 18), dist (n, 7), label (n,) index into classes, classes, ref (n, 34): 27 RayHit fields + occlusion at each distance."""
+    return dict(np.load(os.path.join(GOLDEN, "unit", f"rayprobe_{name}.npz")))
+
+
+def check_hits(got, want, label=None, classes=None):
+    """All 27 RayHit fields bit for bit (NaN == NaN); names the classes of the rays that differ."""
+    bad = ~((got.view(np.uint32) == want.view(np.uint32)) | (np.isnan(got) & np.isnan(want))).all(axis=1)
+    if bad.any() and label is not None:
+        where = {str(classes[k]): int((label[bad] == k).sum()) for k in np.unique(label[bad])}
+        raise AssertionError(f"{int(bad.sum())} of {len(got)} rays differ, by class {where}; first {np.flatnonzero(bad)[:8].tolist()}")
+    assert not bad.any(), int(bad.sum())
