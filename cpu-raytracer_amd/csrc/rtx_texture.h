@@ -153,7 +153,10 @@ RTX_D v3 tex_ewa(TexCtx & tc, const float * lut, float max_ratio, float s, float
     const float lod = std_max(0.0f, (float)d.mip_levels - 1.0f + rtx_log2f(blen));
     const int level = f2i_rn_x86(lod);
     if (level >= d.mip_levels - 1) return tex_coarsest(tc);
-    const TexLevel L = tex_level(tc, level);
+    // An infinite minor axis (inf / 1e38 derivatives beside a NaN one) makes lod inf and the level the integer indefinite, 0x80000000.  The
+    // reference shifts the extents by it (x86 takes the count modulo 32: level 0's extents) and never looks the level up, because no texel
+    // of an all-NaN ellipse is inside; here the level's record is read up front, so that level must not index mip_offsets.
+    const TexLevel L = tex_level(tc, level < 0 ? 0 : level);
     const float cs = s * L.wf - 0.5f, ct = t * L.hf - 0.5f;                 // ellipse centre in texels
     const float Ax = ax * L.wf, Ay = ay * L.hf, Bx = bx * L.wf, By = by * L.hf;
     float qa =  1.0f + (Ay * Ay + By * By);                                  // implicit ellipse qa*u^2 + qb*u*v + qc*v^2 < 1

@@ -237,7 +237,14 @@ int rtx_upload_blas(rtx_ctx * ctx, int32_t blas_id,
 int rtx_upload_materials(rtx_ctx * ctx, const rtx_material * materials, int32_t count);
 
 /* One Texture (Texture.h:8-19): linear-space float3 texels, mip chain
- * appended as Texture::load builds it (Texture.cpp:58-117).                  */
+ * appended as Texture::load builds it (Texture.cpp:58-117).  Accepted: any
+ * width, height >= 1 (sides that are no power of two wrap by modulo); 1 ..
+ * RTX_MAX_MIP_LEVELS levels where level l is (width >> l) x (height >> l)
+ * texels at mip_offsets[l], every level non-empty and inside texel_count
+ * (so at most 1 + log2(min(width, height)) levels; non-square chains, one-
+ * level "chains" and chains on a base that is no power of two included).
+ * Anything else: RTX_ERR_INVALID_ARG, and the id keeps what it held.  An id
+ * may be uploaded again with another shape.                                  */
 int rtx_upload_texture(rtx_ctx * ctx, int32_t texture_id, const rtx_texture_desc * desc,
                        const float * texels_rgb, int64_t texel_count);
 

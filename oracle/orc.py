@@ -62,6 +62,10 @@ def lib():
         _lib.orc_float_to_int.argtypes = [C.c_float]
         _lib.orc_sky_sample.restype = None
         _lib.orc_sky_sample.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        _lib.orc_texture_sample_n.restype = C.c_int
+        _lib.orc_texture_sample_n.argtypes = [C.POINTER(OrcTexture), C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+        _lib.orc_sky_sample_n.restype = C.c_int
+        _lib.orc_sky_sample_n.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
         _lib.orc_aabb_intersect.restype = C.c_int
         _lib.orc_aabb_intersect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]
         _lib.orc_trace_closest.restype = None
@@ -161,6 +165,37 @@ class OracleScene:
         if rc != 0:
             raise RuntimeError(f"orc_trace_any_n failed: {rc}")
         return (occ != 0).reshape(shape)
+
+
+def texture_sample(tex: sio.Texture, in6: np.ndarray, texture_mode: int = 2, mip_filter: int = 1, max_anisotropy: float = 8.0,
+                   threads: int = 8) -> Tuple[np.ndarray, np.ndarray]:
+    """Texture::sample of n (s, t, ds_dx, ds_dy, dt_dx, dt_dy) rows on one scene_io.Texture: (colours (n, 3) float32, texel fetches (n,)
+    int32; an EWA footprint box of more than 2^20 texels is not walked: count INT32_MAX, colour NaN)."""
+    t = OrcTexture()
+    C.memmove(C.byref(t.desc), tex.desc.ctypes.data, C.sizeof(RtxTextureDesc))
+    texels = np.ascontiguousarray(tex.texels, np.float32)
+    t.texels = texels.ctypes.data
+    x = np.ascontiguousarray(in6, np.float32).reshape(-1, 6)
+    out = np.zeros((len(x), 3), np.float32)
+    fetches = np.zeros(len(x), np.int32)
+    rc = lib().orc_texture_sample_n(C.byref(t), texture_mode, mip_filter, float(max_anisotropy), len(x), x.ctypes.data, out.ctypes.data,
+                                    fetches.ctypes.data, threads)
+    if rc != 0:
+        raise RuntimeError(f"orc_texture_sample_n failed: {rc}")
+    return out, fetches
+
+
+def sky_sample(sky: np.ndarray, directions: np.ndarray, threads: int = 8) -> np.ndarray:
+    """Sky::sample of n directions on a (size, size, 3) probe (padded here by the texel its inclusive index clamp can reach)."""
+    size = sky.shape[0]
+    padded = np.zeros((size * size + 1, 3), np.float32)
+    padded[:size * size] = np.asarray(sky, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+    out = np.zeros_like(d)
+    rc = lib().orc_sky_sample_n(padded.ctypes.data, size, len(d), d.ctypes.data, out.ctypes.data, threads)
+    if rc != 0:
+        raise RuntimeError(f"orc_sky_sample_n failed: {rc}")
+    return out
 
 
 def gamma_lut() -> np.ndarray:

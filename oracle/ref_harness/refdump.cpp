@@ -134,6 +134,7 @@ int main(int argc, char ** argv) {
 	bool lights_given = false;
 	std::vector<MatEdit> edits;
 	struct TexProbe { std::string path; int n; unsigned seed; }; std::vector<TexProbe> probes;
+	struct TexProbeFile { std::string path, inputs; }; std::vector<TexProbeFile> file_probes;
 	int render_reps = 1;
 
 	{
@@ -173,6 +174,7 @@ int main(int argc, char ** argv) {
 			else if (w[0] == "nolights") { lights_given = true; }
 			else if (w[0] == "matset")  { MatEdit e; e.target = w[1]; e.field = w[2]; e.args.assign(w.begin() + 3, w.end()); edits.push_back(e); }
 			else if (w[0] == "texprobe") { probes.push_back({ w[1], atoi(w[2].c_str()), (unsigned)strtoul(w[3].c_str(), nullptr, 0) }); }
+			else if (w[0] == "texprobe_file") { file_probes.push_back({ w[1], w[2] }); }
 			else if (w[0] == "unitprobe") { unit_n = atoi(w[1].c_str()); unit_seed = (unsigned)strtoul(w[2].c_str(), nullptr, 0); }
 			else if (w[0] == "rayprobe")  { rayprobe_path = w[1]; rayprobe_n = atoi(w[2].c_str()); }
 			else { fprintf(stderr, "unknown script command '%s'\n", w[0].c_str()); return 2; }
@@ -558,6 +560,27 @@ int main(int argc, char ** argv) {
 			r[6] = c.x; r[7] = c.y; r[8] = c.z;
 		}
 		char name[64]; snprintf(name, sizeof(name), "texprobe%zu.f32", k);
+		dump(name, io.data(), io.size() * 4);
+	}
+
+	// ---- texture probes at caller-supplied inputs (tests/texset.py): `texprobe_file <image> <inputs.f32>`, n x 6 floats in (s, t, ds_dx, ds_dy,
+	// dt_dx, dt_dy), texprobe_file<k>.f32 out: n x 9 (the inputs, then Texture::sample's colour) --------------------------------------------
+	for (size_t k = 0; k < file_probes.size(); k++) {
+		const Texture * tx = Texture::load(file_probes[k].path.c_str());
+		FILE * f = fopen(file_probes[k].inputs.c_str(), "rb");
+		if (!f) { fprintf(stderr, "cannot read %s\n", file_probes[k].inputs.c_str()); return 2; }
+		fseek(f, 0, SEEK_END); const long bytes = ftell(f); fseek(f, 0, SEEK_SET);
+		const size_t n = (size_t)bytes / 24;
+		std::vector<float> in(n * 6), io(n * 9);
+		if (bytes % 24 != 0 || fread(in.data(), 4, in.size(), f) != in.size()) { fprintf(stderr, "%s: not n x 6 floats\n", file_probes[k].inputs.c_str()); return 2; }
+		fclose(f);
+		for (size_t i = 0; i < n; i++) {
+			float * r = &io[9 * i];
+			memcpy(r, &in[6 * i], 24);
+			Vector3 c = tx->sample(r[0], r[1], r[2], r[3], r[4], r[5]);
+			r[6] = c.x; r[7] = c.y; r[8] = c.z;
+		}
+		char name[64]; snprintf(name, sizeof(name), "texprobe_file%zu.f32", k);
 		dump(name, io.data(), io.size() * 4);
 	}
 

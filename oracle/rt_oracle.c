@@ -481,7 +481,7 @@ static inline int mod_pos(int value, int modulus) {   /* Math::mod, Math.h:54-61
     return r;
 }
 
-typedef struct { const orc_texture * t; counters_t * c; } texctx_t;
+typedef struct { const orc_texture * t; counters_t * c; int64_t box_cap; } texctx_t;   /* box_cap > 0: see orc_texture_sample_n */
 
 static v3 fetch_texel(const texctx_t * tc, int x, int y, int level) {   /* Texture.cpp:131-147 */
     const rtx_texture_desc * d = &tc->t->desc;
@@ -603,6 +603,10 @@ static v3 sample_ewa(const texctx_t * tc, float max_aniso, float s, float t, flo
     int t1 = orc_float_to_int(t + tv - 0.5f);
     v3 sum = V3(0.0f, 0.0f, 0.0f);
     float sum_weights = 0.0f;
+    if (tc->box_cap > 0 && s1 >= s0 && t1 >= t0 && ((int64_t)s1 - s0 + 1) * ((int64_t)t1 - t0 + 1) > tc->box_cap) {
+        if (tc->c) tc->c->work.texel_fetches = UINT64_MAX;     /* a footprint box nobody should walk: reported, not evaluated */
+        return V3(NAN, NAN, NAN);
+    }
     float t0f = (float)t0, s0f = (float)s0;
     float tf = t0f;
     pthread_once(&ewa_once, ewa_init);
@@ -1043,6 +1047,58 @@ int orc_trace_any_n(const orc_scene * scene, int32_t n, const float * rays18, in
     batch_t b; memset(&b, 0, sizeof(b));
     b.sc = scene; b.rays = rays18; b.k = k; b.maxd = max_distance; b.occ = occluded;
     return run_batch(&b, n, threads, any_worker);
+}
+
+/* Texture::sample of n inputs (s, t, ds_dx, ds_dy, dt_dx, dt_dy) on one texture, and how many texels each sample fetched (what one lane of
+ * the device's debug kernel will have to walk: the callers bound it before a sample reaches a GPU).  An EWA footprint whose bounding box
+ * holds more than ORC_EWA_BOX_CAP texels is not walked: its count is INT32_MAX and its colour NaN.  Sky::sample of n directions. */
+#define ORC_EWA_BOX_CAP (1 << 20)
+typedef struct { const orc_texture * tex; rtx_config cf; const float * sky; int32_t sky_size; } sampler_t;
+
+static void * texture_worker(void * p) {
+    const batch_t * b = (const batch_t *)p;
+    const sampler_t * sm = (const sampler_t *)b->sc;
+    for (int32_t i = b->lo; i < b->hi; i++) {
+        counters_t c; memset(&c, 0, sizeof(c));
+        texctx_t tc = { sm->tex, &c, ORC_EWA_BOX_CAP };
+        const float * in = b->rays + 6 * (size_t)i;
+        const v3 r = texture_sample(&tc, &sm->cf, in[0], in[1], in[2], in[3], in[4], in[5]);
+        float * o = b->out + 3 * (size_t)i;
+        o[0] = r.x; o[1] = r.y; o[2] = r.z;
+        if (b->ids) b->ids[i] = c.work.texel_fetches > 0x7fffffff ? 0x7fffffff : (int32_t)c.work.texel_fetches;
+    }
+    return NULL;
+}
+
+static void * sky_worker(void * p) {
+    const batch_t * b = (const batch_t *)p;
+    const sampler_t * sm = (const sampler_t *)b->sc;
+    for (int32_t i = b->lo; i < b->hi; i++) {
+        const v3 r = sky_sample(sm->sky, sm->sky_size, v3p(b->rays + 3 * (size_t)i));
+        float * o = b->out + 3 * (size_t)i;
+        o[0] = r.x; o[1] = r.y; o[2] = r.z;
+    }
+    return NULL;
+}
+
+int orc_texture_sample_n(const orc_texture * tex, int32_t texture_mode, int32_t mip_filter, float max_anisotropy,
+                         int32_t n, const float * in6, float * out_rgb, int32_t * fetches, int32_t threads) {
+    if (!tex || !tex->texels || n < 0 || (n > 0 && (!in6 || !out_rgb))) return RTX_ERR_INVALID_ARG;
+    sampler_t sm; memset(&sm, 0, sizeof(sm));
+    sm.tex = tex; sm.cf.texture_mode = texture_mode; sm.cf.mip_filter = mip_filter; sm.cf.max_anisotropy = max_anisotropy;
+    pthread_once(&ewa_once, ewa_init);
+    batch_t b; memset(&b, 0, sizeof(b));
+    b.sc = (const orc_scene *)&sm; b.rays = in6; b.out = out_rgb; b.ids = fetches;
+    return run_batch(&b, n, threads, texture_worker);
+}
+
+int orc_sky_sample_n(const float * sky, int32_t size, int32_t n, const float * directions, float * out_rgb, int32_t threads) {
+    if (!sky || size <= 0 || n < 0 || (n > 0 && (!directions || !out_rgb))) return RTX_ERR_INVALID_ARG;
+    sampler_t sm; memset(&sm, 0, sizeof(sm));
+    sm.sky = sky; sm.sky_size = size;
+    batch_t b; memset(&b, 0, sizeof(b));
+    b.sc = (const orc_scene *)&sm; b.rays = directions; b.out = out_rgb;
+    return run_batch(&b, n, threads, sky_worker);
 }
 
 /* PointLight / SpotLight / DirectionalLight::calc_lighting at one set of inputs (PointLight.h:9-11, SpotLight.h:17-33, DirectionalLight.h:9-11) */

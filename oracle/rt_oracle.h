@@ -60,6 +60,10 @@ int      orc_aabb_intersect(const rtx_bvh_node * node, const float origin[3], co
 void     orc_texture_sample(const orc_texture * tex, int32_t texture_mode, int32_t mip_filter, float max_anisotropy,
                             float s, float t, float ds_dx, float ds_dy, float dt_dx, float dt_dy, float out_rgb[3]);
 void     orc_sky_sample(const float * sky, int32_t size, const float direction[3], float out_rgb[3]);
+/* batch forms (threads as orc_trace_closest_n): n x 6 inputs -> n x 3 colours and, where asked for, the texel fetches of each sample */
+int      orc_texture_sample_n(const orc_texture * tex, int32_t texture_mode, int32_t mip_filter, float max_anisotropy,
+                              int32_t n, const float * in6, float * out_rgb, int32_t * fetches, int32_t threads);
+int      orc_sky_sample_n(const float * sky, int32_t size, int32_t n, const float * directions, float * out_rgb, int32_t threads);
 uint32_t orc_plot(const float rgb[3]);
 void     orc_calc_lighting(const rtx_point_light * pl, const rtx_spot_light * sl, const rtx_directional_light * dl,
                            const float normal[3], const float to_light[3], const float to_camera[3], float distance_squared, float out9[9]);

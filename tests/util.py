@@ -111,3 +111,26 @@ def check_hits(got, want, label=None, classes=None):
         where = {str(classes[k]): int((label[bad] == k).sum()) for k in np.unique(label[bad])}
         raise AssertionError(f"{int(bad.sum())} of {len(got)} rays differ, by class {where}; first {np.flatnonzero(bad)[:8].tolist()}")
     assert not bad.any(), int(bad.sum())
+
+
+# reference-pinned texture probes (tests/golden/unit/texprobe_<build>.npz, oracle/ref_harness/make_tex_goldens.py):
+# build of the reference -> (texture_mode, mip_filter, max_anisotropy)
+TEX_PROBES = {"nearest": (0, 1, 8.0), "bilinear": (1, 1, 8.0), "trilinear": (2, 0, 8.0), "aniso": (2, 1, 8.0), "aniso2": (2, 1, 2.0),
+              "ewa": (2, 2, 8.0)}
+
+
+def load_tex_probe(build):
+    """names; classes; per texture <name>: tile_<name> (texset.pixels8 expands it), in_<name> (n, 6), label_<name> (n,), ref_<name> (n, 3)."""
+    return dict(np.load(os.path.join(GOLDEN, "unit", f"texprobe_{build}.npz")))
+
+
+def check_colours(got, want, label=None, classes=None, what=""):
+    """Sampled colours bit for bit (NaN == NaN); names the classes of the samples that differ."""
+    got = np.ascontiguousarray(got, np.float32); want = np.ascontiguousarray(want, np.float32)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    bad = ~((got.view(np.uint32) == want.view(np.uint32)) | (np.isnan(got) & np.isnan(want))).all(axis=1)
+    if bad.any():
+        where = {} if label is None else {str(classes[k]): int((label[bad] == k).sum()) for k in np.unique(label[bad])}
+        first = np.flatnonzero(bad)[:4]
+        raise AssertionError(f"{what}: {int(bad.sum())} of {len(got)} samples differ, by class {where}; first rows {first.tolist()}: "
+                             f"got {got[first].tolist()} want {want[first].tolist()}")
