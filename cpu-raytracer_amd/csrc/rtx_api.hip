@@ -100,6 +100,13 @@ struct rtx_ctx {
     int vstage_next = 0;
     int32_t view_count = 0, vfb_cap = 0, ext_vcap = 0;
     void * ext_vrgb = nullptr, * ext_vpacked = nullptr;
+    // ray views (rtx_set_rays / rtx_bind_rays): the context's own ray buffer of ray_count views (grown only, filled through a ring of pinned
+    // staging buffers like the cameras) or the caller's device buffer of ext_ray_count views; independent of the rtx_set_views state
+    DevBuf d_rays;
+    FrameStage rstage[3];
+    int rstage_next = 0;
+    int32_t ray_count = 0, ext_ray_count = 0;
+    const void * ext_rays = nullptr;
     // rtx_bind_aovs: the bound channels (RTX_AOV_* bits) and where they go: the caller's device buffers of aov_ext_cap pixels (aov_ext), or
     // the context's own buffers d_aov[k] of aov_own_cap[k] pixels (allocated by the first call that writes the channel, grown only)
     uint32_t aov_channels = 0; bool aov_ext = false; int64_t aov_ext_cap = 0; DevAov aov_ext_ptrs = {};
@@ -413,7 +420,7 @@ extern "C" int rtx_destroy(rtx_ctx * c) {
     if (c->stream) hipStreamSynchronize(c->stream);
     for (auto & v : c->blas_allocs) for (void * p : v) hipFree(p);
     for (void * p : c->tex_allocs) if (p) hipFree(p);
-    DevBuf * bufs[] = { &c->d_blas, &c->d_materials, &c->d_textures, &c->d_sky, &c->d_ewa, &c->d_frame, &c->d_counters, &c->d_spill, &c->d_fb_rgb, &c->d_fb_packed, &c->d_display, &c->d_gamma, &c->d_pk_heads, &c->d_pk_fifo, &c->d_pk_items, &c->d_pk_item_count, &c->d_stats_partial, &c->d_dbg_s0, &c->d_dbg_s1, &c->d_pk_cost, &c->d_pk_order, &c->d_views, &c->d_vfb_rgb, &c->d_vfb_packed };
+    DevBuf * bufs[] = { &c->d_blas, &c->d_materials, &c->d_textures, &c->d_sky, &c->d_ewa, &c->d_frame, &c->d_counters, &c->d_spill, &c->d_fb_rgb, &c->d_fb_packed, &c->d_display, &c->d_gamma, &c->d_pk_heads, &c->d_pk_fifo, &c->d_pk_items, &c->d_pk_item_count, &c->d_stats_partial, &c->d_dbg_s0, &c->d_dbg_s1, &c->d_pk_cost, &c->d_pk_order, &c->d_views, &c->d_vfb_rgb, &c->d_vfb_packed, &c->d_rays };
     for (DevBuf * b : bufs) if (b->p) hipFree(b->p);
     for (DevBuf & b : c->d_aov) if (b.p) hipFree(b.p);
     for (DevBuf & b : c->qb) if (b.p) hipFree(b.p);
@@ -421,6 +428,7 @@ extern "C" int rtx_destroy(rtx_ctx * c) {
     for (DevCounters * h : c->pending_host) hipHostFree(h);
     for (auto & st : c->stage) { if (st.host) hipHostFree(st.host); if (st.done) hipEventDestroy(st.done); }
     for (auto & st : c->vstage) { if (st.host) hipHostFree(st.host); if (st.done) hipEventDestroy(st.done); }
+    for (auto & st : c->rstage) { if (st.host) hipHostFree(st.host); if (st.done) hipEventDestroy(st.done); }
     if (c->graph_exec) { hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
     if (c->order_stream) { hipStreamSynchronize(c->order_stream); hipStreamDestroy(c->order_stream); hipEventDestroy(c->ev_cost); hipEventDestroy(c->ev_order); }
     if (c->any_stream) { hipStreamSynchronize(c->any_stream); hipStreamDestroy(c->any_stream); }
@@ -768,7 +776,7 @@ static void launch_timed(rtx_ctx * c, const char * name, hipStream_t stream, F &
     } else launch();
 }
 
-static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_stride, int32_t tile_count, uint32_t flags, uint32_t * tile_major, bool views = false);
+static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_stride, int32_t tile_count, uint32_t flags, uint32_t * tile_major, int views = RTX_CAM_TILES);
 static int aov_targets_of_call(rtx_ctx * c, int64_t pixels, DevAov & out);
 
 extern "C" int rtx_render_tiles(rtx_ctx * c, int32_t first_tile, int32_t tile_stride, int32_t tile_count, uint32_t flags) {
@@ -777,8 +785,9 @@ extern "C" int rtx_render_tiles(rtx_ctx * c, int32_t first_tile, int32_t tile_st
 
 // tile_major != nullptr: the packed level-0 pixels of the i-th rendered tile go to tile_major[i * 1024 ...] (slot order) instead of the framebuffer.
 // views (rtx_render_views): the tiles are virtual tiles over views x tiles of the set views (range checked by the caller), the kernels are the
-// VIEWS instantiations and level 0 writes the view framebuffer
-static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_stride, int32_t tile_count, uint32_t flags, uint32_t * tile_major, bool views) {
+// VIEWS instantiations and level 0 writes the view framebuffer.  RTX_CAM_RAYS (rtx_render_rays): the same over the ray views, with the rays
+// instantiations, which read their primary rays from the current ray buffer
+static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_stride, int32_t tile_count, uint32_t flags, uint32_t * tile_major, int views) {
     if (!c || first_tile < 0 || tile_stride < 1 || tile_count < 0) return RTX_ERR_INVALID_ARG;
     if (!c->frame_set) { c->err = "rtx_render_tiles before rtx_set_frame"; return RTX_ERR_STATE; }
     if (int bad = validate_references(c)) return bad;
@@ -786,7 +795,9 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
     if (!views && tile_count > 0 && first_tile + (int64_t)(tile_count - 1) * tile_stride >= (int64_t)tcx * tcy) return RTX_ERR_INVALID_ARG;
     hipSetDevice(c->cfg.device);
     // the launches below that generate primary rays or read the camera take the VIEWS instantiation of their kernel in a view call
-    auto with_views = [views](auto && launch) { if (views) launch(std::true_type()); else launch(std::false_type()); };
+    auto with_views = [views](auto && launch) {
+        if (views == RTX_CAM_RAYS) launch(std::integral_constant<int, RTX_CAM_RAYS>()); else if (views) launch(std::integral_constant<int, RTX_CAM_VIEWS>()); else launch(std::integral_constant<int, RTX_CAM_TILES>());
+    };
     const bool count_work = (flags & RTX_RENDER_COUNT_WORK) != 0;
     const bool simple = (flags & RTX_RENDER_SIMPLE_TRACE) != 0;
     const bool cull = (flags & RTX_RENDER_CULL_DEAD_SHADOW_RAYS) != 0 && !simple && !count_work;
@@ -833,7 +844,8 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
     int rc = alloc_queues(c, batch_tiles);
     if (rc) return rc;
     if (views) {
-        c->q.views = (const rtx_camera *)c->d_views.p;
+        // one field for both: the cameras of a view call, or (cast) the rtx_ray records of a ray call, read by the instantiation that knows which
+        c->q.views = views == RTX_CAM_RAYS ? (const rtx_camera *)(c->ext_rays ? c->ext_rays : c->d_rays.p) : (const rtx_camera *)c->d_views.p;
         c->q.fb_rgb = (float *)(c->ext_vrgb ? c->ext_vrgb : c->d_vfb_rgb.p);
         c->q.fb_packed = (uint32_t *)(c->ext_vpacked ? c->ext_vpacked : c->d_vfb_packed.p);
     }
@@ -897,7 +909,7 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
         int lrc = ensure(c, c->d_pk_cost, (size_t)lpt_n * 4); if (!lrc) lrc = ensure(c, c->d_pk_order, (size_t)lpt_n * 4);
         if (lrc) return lrc;
         if (!c->order_stream) { HIP_OK(c, hipStreamCreateWithFlags(&c->order_stream, hipStreamNonBlocking)); hipEventCreateWithFlags(&c->ev_cost, hipEventDisableTiming); hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming); }
-        const int32_t key[5] = { first_tile, tile_stride, tile_count, levels, views ? 1 : 0 };      // a view call has its own key space: packets over views x tiles
+        const int32_t key[5] = { first_tile, tile_stride, tile_count, levels, views };      // view calls and ray calls have key spaces of their own: packets over views x tiles
         const bool use_order = c->lpt_valid && memcmp(key, c->lpt_key, sizeof(key)) == 0;
         memcpy(c->lpt_key, key, sizeof(key));
         c->q.pk_cost = (uint32_t *)c->d_pk_cost.p;
@@ -907,11 +919,12 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
     bool capturing = false;
     if (c->knobs.graph && !c->timing && tile_count <= batch_tiles) {
         // a view call differs from a tiles call by the cameras and framebuffer pointers of the queues and the views flag; its view range is the
-        // tile range (first_tile = first_view * tiles per view); the cameras themselves are read from device memory at replay
+        // tile range (first_tile = first_view * tiles per view); the cameras themselves are read from device memory at replay.  A ray call
+        // carries the address of its rays in the same field and its own value of the flag: a rebind is a new key, new values in the same buffer are read at replay
         std::vector<unsigned char> key(sizeof(DevScene) + sizeof(DevQueues) + 6 * sizeof(int32_t) + sizeof(void *) + sizeof(uint32_t) + sizeof(DevAov));
         unsigned char * kp = key.data();
         memcpy(kp, &c->scene, sizeof(DevScene)); kp += sizeof(DevScene); memcpy(kp, &c->q, sizeof(DevQueues)); kp += sizeof(DevQueues);
-        const int32_t kv[6] = { first_tile, tile_stride, tile_count, (int32_t)flags, levels, views ? 1 : 0 }; memcpy(kp, kv, sizeof(kv)); kp += sizeof(kv);
+        const int32_t kv[6] = { first_tile, tile_stride, tile_count, (int32_t)flags, levels, views }; memcpy(kp, kv, sizeof(kv)); kp += sizeof(kv);
         memcpy(kp, &tile_major, sizeof(void *)); kp += sizeof(void *);
         // an AOV call also depends on the bound channels and their targets (zero for a call without RTX_RENDER_AOV): a rebind is a new key
         const uint32_t aov_mask = aov ? c->aov_channels : 0u; memcpy(kp, &aov_mask, sizeof(aov_mask)); kp += sizeof(aov_mask);
@@ -952,10 +965,10 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
         if (sc.heatmap) {
             // BVH_VISUALIZE_HEATMAP: bounce() returns right after the primary ray's trace (Raytracer.cpp:97-102), so a frame is one
             // closest-hit pass in reference pop order (the plain kernel counts the steps) and one colouring pass
-            launch_timed(c, "k_trace_closest", c->stream, [&] { with_views([&](auto V) { constexpr bool VW = decltype(V)::value;
+            launch_timed(c, "k_trace_closest", c->stream, [&] { with_views([&](auto V) { constexpr int VW = decltype(V)::value;
                 if (count_work) hipLaunchKernelGGL((k_trace<false, true, VW>),  dim3(c->trace_blocks_count), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, 0);
                 else            hipLaunchKernelGGL((k_trace<false, false, VW>), dim3(c->trace_blocks_count), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, 0); }); });
-            launch_timed(c, "k_heatmap", c->stream, [&] { with_views([&](auto V) { hipLaunchKernelGGL((k_heatmap<decltype(V)::value>), dim3(stream_blocks), dim3(256), 0, c->stream, sc, q); }); });
+            launch_timed(c, "k_heatmap", c->stream, [&] { with_views([&](auto V) { if constexpr (decltype(V)::value != RTX_CAM_RAYS) hipLaunchKernelGGL((k_heatmap<decltype(V)::value>), dim3(stream_blocks), dim3(256), 0, c->stream, sc, q); }); });
             continue;
         }
         // traversal kernels: packet walk (production), per-lane pair fetch (RTX_RENDER_LANE_TRACE), plain pop-and-test (SIMPLE / COUNT_WORK)
@@ -983,7 +996,7 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
         auto level_blocks = [&](int level, int full) { const long long want = (((long long)q.primary_slots >> level) + 255) / 256; return (int)std::max(64ll, std::min((long long)full, want)); };
         for (int level = 0; level < levels; level++) q.stats_n[level] = level_is_fused(level) ? pk_waves_closest : level_blocks(level, shade_blocks);
         auto launch_closest = [&](int level) {
-            launch_timed(c, level_is_fused(level) ? "k_trace_closest_shade" : "k_trace_closest", c->stream, [&] { with_views([&](auto V) { constexpr bool VW = decltype(V)::value;
+            launch_timed(c, level_is_fused(level) ? "k_trace_closest_shade" : "k_trace_closest", c->stream, [&] { with_views([&](auto V) { constexpr int VW = decltype(V)::value;
                 if (count_work)     hipLaunchKernelGGL((k_trace<false, true, VW>),   dim3(c->trace_blocks_count), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, level);
                 else if (simple)    hipLaunchKernelGGL((k_trace<false, false, VW>),  dim3(c->trace_blocks_count), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, level);
                 else if (lane || (!pstat && level >= lane_from_closest)) hipLaunchKernelGGL((k_trace_fast<false, VW>),    dim3(c->trace_blocks_closest), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, level, level);
@@ -1025,7 +1038,7 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
                 hipEventRecord(c->ev_order, c->order_stream);
                 c->lpt_valid = true;
             }
-            if (!level_is_fused(level)) launch_timed(c, "k_shade", c->stream, [&] { with_views([&](auto V) { constexpr bool VW = decltype(V)::value;
+            if (!level_is_fused(level)) launch_timed(c, "k_shade", c->stream, [&] { with_views([&](auto V) { constexpr int VW = decltype(V)::value;
                 const int g = level_blocks(level, shade_blocks);
                 if (aov && level == 0) {
                     if (count_work) hipLaunchKernelGGL((k_shade<true, false, VW, true, DevAov>),  dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level, aov_t);
@@ -1163,6 +1176,7 @@ extern "C" int rtx_set_stream(rtx_ctx * c, void * hip_stream) {
 // ---- batches of views (include/rtx.h rtx_set_views ...) ------------------------------------------------------------------------------
 // A view call is a render call over virtual tiles: view v's tile t is tile v * T + t, T = tiles per view (rtx_trace.h primary_pixel_v).
 static int64_t view_pixel_count(const rtx_ctx * c, int64_t views) { return views * (int64_t)c->cfg.width * c->cfg.height; }
+static int32_t current_ray_views(const rtx_ctx * c) { return c->ext_rays ? c->ext_ray_count : c->ray_count; }      // ray views of the bound buffer, else of the rays set
 
 extern "C" int rtx_set_views(rtx_ctx * c, const rtx_camera * cameras, int32_t view_count) {
     if (!c || !cameras || view_count < 1 || view_count > RTX_MAX_VIEWS) return RTX_ERR_INVALID_ARG;
@@ -1217,20 +1231,81 @@ extern "C" int rtx_render_views(rtx_ctx * c, int32_t first_view, int32_t view_co
     if (c->ext_vrgb) { if (first_view + view_count > c->ext_vcap) { c->err = "view range outside the bound view framebuffer"; return RTX_ERR_INVALID_ARG; } }
     else if (int rc = ensure_view_fb(c, c->view_count)) return rc;
     const int32_t tiles = ((c->cfg.width + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE) * ((c->cfg.height + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE);
-    return render_tiles_impl(c, first_view * tiles, 1, view_count * tiles, flags, nullptr, true);
+    return render_tiles_impl(c, first_view * tiles, 1, view_count * tiles, flags, nullptr, RTX_CAM_VIEWS);
 }
 
 extern "C" int rtx_read_views(rtx_ctx * c, int32_t first_view, int32_t view_count, float * rgb_f32, uint32_t * packed_u32) {
     if (!c || first_view < 0 || view_count < 1 || view_count > RTX_MAX_VIEWS) return RTX_ERR_INVALID_ARG;
-    if ((int64_t)first_view + view_count > c->view_count) { c->err = "view range outside the views set by rtx_set_views"; return RTX_ERR_INVALID_ARG; }
+    const int32_t known_views = std::max(c->view_count, current_ray_views(c));      // the view framebuffer holds camera views and ray views alike
+    if ((int64_t)first_view + view_count > known_views) { c->err = "view range outside the views set by rtx_set_views and the ray views set by rtx_set_rays / rtx_bind_rays"; return RTX_ERR_INVALID_ARG; }
     if (c->ext_vrgb && first_view + view_count > c->ext_vcap) { c->err = "view range outside the bound view framebuffer"; return RTX_ERR_INVALID_ARG; }
     hipSetDevice(c->cfg.device);
-    if (!c->ext_vrgb) if (int rc = ensure_view_fb(c, c->view_count)) return rc;
+    if (!c->ext_vrgb) if (int rc = ensure_view_fb(c, known_views)) return rc;
     const size_t px = (size_t)c->cfg.width * c->cfg.height, first = (size_t)first_view * px, n = (size_t)view_count * px;
     HIP_OK(c, hipStreamSynchronize(c->stream));
     if (rgb_f32)    HIP_OK(c, hipMemcpy(rgb_f32, (const float *)(c->ext_vrgb ? c->ext_vrgb : c->d_vfb_rgb.p) + 3 * first, n * 12, hipMemcpyDeviceToHost));
     if (packed_u32) HIP_OK(c, hipMemcpy(packed_u32, (const uint32_t *)(c->ext_vpacked ? c->ext_vpacked : c->d_vfb_packed.p) + first, n * 4, hipMemcpyDeviceToHost));
     return RTX_OK;
+}
+
+// ---- ray views (include/rtx.h rtx_set_rays ...) -----------------------------------------------------------------------------------------
+// A ray call is a view call whose kernels read their primary rays from a buffer of rtx_ray records instead of deriving them from a camera.
+static const size_t kRayStageMax = (size_t)32 << 20;      // larger ray sets are copied synchronously instead of through the pinned ring (3 x 149 MB for one 1080p view)
+
+extern "C" int rtx_set_rays(rtx_ctx * c, const rtx_ray * host_rays, int32_t view_count) {
+    static_assert(sizeof(rtx_ray) == 72, "rtx_ray is the 18 floats of rtx_debug_trace_rays");
+    if (!c || !host_rays || view_count < 1 || view_count > RTX_MAX_VIEWS) return RTX_ERR_INVALID_ARG;
+    if (view_pixel_count(c, view_count) >= (1ll << 31)) { c->err = "view_count * width * height must stay below 2^31 (pixel index of a ray record)"; return RTX_ERR_INVALID_ARG; }
+    hipSetDevice(c->cfg.device);
+    const size_t bytes = (size_t)view_pixel_count(c, view_count) * sizeof(rtx_ray);
+    if (bytes > c->d_rays.cap) {                           // growth: queued work still reads the old buffer
+        HIP_OK(c, hipStreamSynchronize(c->stream));
+        if (int rc = ensure(c, c->d_rays, bytes)) return rc;
+    }
+    if (bytes > kRayStageMax) {                            // after the work already queued (waited for), before the next call
+        HIP_OK(c, hipStreamSynchronize(c->stream));
+        HIP_OK(c, hipMemcpy(c->d_rays.p, host_rays, bytes, hipMemcpyHostToDevice));
+        c->ray_count = view_count;
+        return RTX_OK;
+    }
+    rtx_ctx::FrameStage & st = c->rstage[c->rstage_next]; c->rstage_next = (c->rstage_next + 1) % 3;
+    if (st.pending) { HIP_OK(c, hipEventSynchronize(st.done)); st.pending = false; }
+    if (bytes > st.cap) {
+        if (st.host) hipHostFree(st.host);
+        st.host = nullptr; st.cap = 0;
+        HIP_OK(c, hipHostMalloc(&st.host, bytes, hipHostMallocDefault)); st.cap = bytes;
+    }
+    if (!st.done) HIP_OK(c, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
+    memcpy(st.host, host_rays, bytes);
+    HIP_OK(c, hipMemcpyAsync(c->d_rays.p, st.host, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(c, hipEventRecord(st.done, c->stream)); st.pending = true;
+    c->ray_count = view_count;
+    return RTX_OK;
+}
+
+extern "C" int rtx_bind_rays(rtx_ctx * c, const void * rays_dev, int32_t view_count) {
+    if (!c) return RTX_ERR_INVALID_ARG;
+    if (!rays_dev) { c->ext_rays = nullptr; c->ext_ray_count = 0; return RTX_OK; }
+    if (view_count < 1 || view_count > RTX_MAX_VIEWS) return RTX_ERR_INVALID_ARG;
+    if (view_pixel_count(c, view_count) >= (1ll << 31)) { c->err = "view_count * width * height must stay below 2^31 (pixel index of a ray record)"; return RTX_ERR_INVALID_ARG; }
+    if ((uintptr_t)rays_dev & 7u) { c->err = "the rays must be 8-byte aligned"; return RTX_ERR_INVALID_ARG; }
+    // no synchronisation: work already queued keeps reading the buffer it was queued with (the pointer travels with each launch)
+    c->ext_rays = rays_dev; c->ext_ray_count = view_count;
+    return RTX_OK;
+}
+
+extern "C" int rtx_render_rays(rtx_ctx * c, int32_t first_view, int32_t view_count, uint32_t flags) {
+    if (!c || first_view < 0 || view_count < 1 || view_count > RTX_MAX_VIEWS) return RTX_ERR_INVALID_ARG;
+    if (view_pixel_count(c, view_count) >= (1ll << 31)) return RTX_ERR_INVALID_ARG;
+    if (!c->frame_set) { c->err = "rtx_render_rays before rtx_set_frame"; return RTX_ERR_STATE; }
+    if (c->scene.heatmap) { c->err = "rtx_render_rays in heat-map mode"; return RTX_ERR_STATE; }
+    const int32_t have = current_ray_views(c);
+    if (have == 0) { c->err = "rtx_render_rays before rtx_set_rays / rtx_bind_rays"; return RTX_ERR_STATE; }
+    if ((int64_t)first_view + view_count > have) { c->err = "view range outside the rays set by rtx_set_rays / rtx_bind_rays"; return RTX_ERR_INVALID_ARG; }
+    if (c->ext_vrgb) { if (first_view + view_count > c->ext_vcap) { c->err = "view range outside the bound view framebuffer"; return RTX_ERR_INVALID_ARG; } }
+    else if (int rc = ensure_view_fb(c, std::max(have, c->view_count))) return rc;
+    const int32_t tiles = ((c->cfg.width + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE) * ((c->cfg.height + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE);
+    return render_tiles_impl(c, first_view * tiles, 1, view_count * tiles, flags, nullptr, RTX_CAM_RAYS);
 }
 
 extern "C" int rtx_bind_view_framebuffer(rtx_ctx * c, void * rgb_f32_dev, void * packed_u32_dev, int32_t view_capacity) {

@@ -131,7 +131,8 @@ struct DevQueues {
     float4 * n0;   // albedo.xyz (or sky colour on a miss), bits(flags)
     float4 * n1;   // Ks.xyz, F_r
     float4 * n2;   // (Kt - 1).xyz, hit distance
-    const rtx_camera * views;   // rtx_render_views: the cameras of the call's views (read by the VIEWS kernels only, rtx_trace.h), else null.  Takes the
+    const rtx_camera * views;   // rtx_render_views: the cameras of the call's views (read by the VIEWS kernels only, rtx_trace.h), else null; rtx_render_rays:
+                                // the address of the call's rtx_ray records instead (read by the RTX_CAM_RAYS instantiations only, ray_record).  Takes the
                                 // place of the node record n3 (unused since round 3): the kernel arguments of every existing kernel keep their layout
     float4 * c0;   // reflection child's returned colour (written by the child's k_resolve)
     float4 * c1;   // refraction child's returned colour, refraction child's hit distance

@@ -1774,7 +1774,7 @@ RTX_D bool pk_walk(const DevScene & sc, PkWalk & W, const int lane, const bool o
 // persistent traversal grids — 0.07 ms of work took 0.29 ms per launch, a third of a frame's time on its stream — while a wave that
 // already owns its slot simply carries on; the hit records' round trip through HBM (20 B per ray each way) and four launches per frame go
 // away too.  Child-ray slots: one atomic per packet that spawns any (wave_alloc2).
-template <bool ANY, bool PSTAT, bool SPLIT = false, bool FUSE = false, bool CULL = false, bool VIEWS = false>
+template <bool ANY, bool PSTAT, bool SPLIT = false, bool FUSE = false, bool CULL = false, int VIEWS = 0>
 __global__ __launch_bounds__(RTX_PK_BLOCK, ANY ? (SPLIT ? RTX_PK_WAVES_SPLIT : RTX_PK_WAVES_ANY) : (FUSE ? RTX_PK_WAVES_FUSED : RTX_PK_WAVES_CLOSEST))
 void k_packet(const DevScene sc, const DevQueues q, const int level, const int level_hi) {
     // hybrid any-hit walk: the lanes' private stacks, striped through LDS ([entry][lane]: conflict-free)
@@ -1908,7 +1908,11 @@ void k_packet(const DevScene sc, const DevQueues q, const int level, const int l
                 out_slot = (uint32_t)q.level_base[level] + pix_idx;
                 if (level == 0) {
                     int px, py, view;
-                    if (primary_pixel_v<VIEWS, true>(sc, q, pix_idx, px, py, view)) { RayFull r; primary_ray_v<VIEWS>(sc, q, view, px, py, r, false); wo = r.o; wd = r.d; }
+                    if (primary_pixel_v<VIEWS, true>(sc, q, pix_idx, px, py, view)) {
+                        RayFull r; primary_ray_v<VIEWS>(sc, q, view, px, py, r, false); wo = r.o; wd = r.d;
+                        // ray views: a ray with a non-finite component is a miss without a walk (ray_is_finite, rtx_trace.h): the lane stays valid and out of W.alive
+                        if (VIEWS == RTX_CAM_RAYS && !ray_is_finite(wo, wd)) W.occluded = true;
+                    }
                     else { clipped = true; W.valid = false; }
                 } else {
                     const float4 r0 = q.r0[out_slot], r1 = q.r1[out_slot];

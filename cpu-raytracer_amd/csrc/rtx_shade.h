@@ -209,7 +209,7 @@ struct ShadeTally { uint32_t n_shadow, n_refl, n_refr, n_primary, n_shaded, n_sk
 // beside other frames' persistent grids).  `valid` = the slot holds a ray; `in_range` = the slot exists (idx < rays of the level).
 // alloc2(want_a, want_b, counter, slot_a, slot_b) hands out the child-ray slots; every lane of the wave must call it.
 // AOV (level 0 of a RTX_RENDER_AOV call): the primary hit's channels go to `aov` at the pixel the colour goes to.
-template <bool COUNT, bool CULL, bool VIEWS, bool AOV = false, typename Alloc2>
+template <bool COUNT, bool CULL, int VIEWS, bool AOV = false, typename Alloc2>
 RTX_D void shade_ray(const DevScene & sc, const DevQueues & q, const int level, const uint32_t idx, const bool in_range, bool valid,
                      const float4 h0, const int tri, Alloc2 && alloc2, ShadeTally & T, const DevAov * aov_targets = nullptr) {
     DevCounters * const ctr = q.counters;
@@ -303,8 +303,8 @@ RTX_D void shade_ray(const DevScene & sc, const DevQueues & q, const int level, 
         q.sp[slot] = make_float4(h.point.x, h.point.y, h.point.z, 0.0f);
         q.sn[slot] = make_float4(h.normal.x, h.normal.y, h.normal.z, 0.0f);
         if (CULL) {
-            if (VIEWS && level > 0) view = pixel / view_pixels(sc);                // the view's camera at every depth
-            const v3 to_camera = vnormalize(vsub(camera_position<VIEWS>(sc, q, view), h.point));     // Raytracer.cpp:152 (camera, not ray origin)
+            if (VIEWS == RTX_CAM_VIEWS && level > 0) view = pixel / view_pixels(sc);                // the view's camera at every depth
+            const v3 to_camera = vnormalize(vsub(camera_position<VIEWS>(sc, q, view, pixel), h.point));     // Raytracer.cpp:152 (camera, not ray origin; ray views: the pixel's primary origin)
             for (int L = 0; L < nL; L++) {
                 const v3 c = light_contribution(sc, L, h.point, h.normal, to_camera);
                 const uint32_t s = (uint32_t)q.shadow_base[level] + (uint32_t)L * (uint32_t)lit_cap + (uint32_t)lit_rank;
@@ -402,7 +402,7 @@ RTX_D void shade_ray(const DevScene & sc, const DevQueues & q, const int level, 
 }
 
 // AOV = true: launched for level 0 of a RTX_RENDER_AOV call with one more argument, the DevAov targets (Targets = DevAov); otherwise none
-template <bool COUNT, bool CULL, bool VIEWS = false, bool AOV = false, typename... Targets>
+template <bool COUNT, bool CULL, int VIEWS = 0, bool AOV = false, typename... Targets>
 __global__ __launch_bounds__(RTX_SHADE_BLOCK, RTX_WAVES_SHADE)
 void k_shade(const DevScene sc, const DevQueues q, const int level, const Targets... targets) {
     static_assert(sizeof...(Targets) == (AOV ? 1 : 0), "k_shade<.., AOV = true, DevAov> takes the AOV targets, every other instantiation nothing more");
@@ -482,7 +482,7 @@ RTX_D uint32_t plot_pack(v3 c) {
 
 // BVH_VISUALIZE_HEATMAP (Raytracer.cpp:97-102): the pixel is the primary ray's BLAS step count scaled per channel; no shading,
 // no secondary rays.  k_trace<false, *> left the count in h1 (-1 = pixel clipped off the frame).
-template <bool VIEWS = false>
+template <int VIEWS = 0>
 __global__ __launch_bounds__(256)
 void k_heatmap(const DevScene sc, const DevQueues q) {
     uint32_t n_primary = 0;
@@ -500,7 +500,7 @@ void k_heatmap(const DevScene sc, const DevQueues q) {
     if ((threadIdx.x & 63) == 0 && n_primary) atomicAdd(&q.counters->stats[0], (unsigned long long)n_primary);
 }
 
-template <bool VIEWS = false>
+template <int VIEWS = 0>
 __global__ __launch_bounds__(256)
 void k_resolve(const DevScene sc, const DevQueues q, const int level) {
     DevCounters * const ctr = q.counters;
@@ -541,9 +541,11 @@ void k_resolve(const DevScene sc, const DevQueues q, const int level) {
                 const uint32_t rank = idx;                          // a hit's shadow rays sit in the hit's own slot of every light's segment
                 const float4 pp = q.sp[slot], nn = q.sn[slot];
                 const v3 point = V3(pp.x, pp.y, pp.z), normal = V3(nn.x, nn.y, nn.z);
-                int view = 0;                                                 // VIEWS: the camera of the pixel's view, at every depth
-                if (VIEWS) { int px, py; if (level == 0) primary_pixel_v<true, true>(sc, q, idx, px, py, view); else view = as_i(q.r1[slot].z) / view_pixels(sc); }
-                const v3 to_camera = vnormalize(vsub(camera_position<VIEWS>(sc, q, view), point));     // Raytracer.cpp:152
+                int view = 0, cam_pixel = 0;                                  // VIEWS: the camera of the pixel's view, at every depth; ray views: the origin of the pixel's primary ray
+                if (VIEWS == RTX_CAM_VIEWS) { int px, py; if (level == 0) primary_pixel_v<RTX_CAM_VIEWS, true>(sc, q, idx, px, py, view); else view = as_i(q.r1[slot].z) / view_pixels(sc); }
+                // ray views: only the pixel index is wanted here, so the slot is mapped by the camera-view form, which does not load the record to test it
+                if (VIEWS == RTX_CAM_RAYS) { int px, py; if (level == 0) { primary_pixel_v<RTX_CAM_VIEWS, true>(sc, q, idx, px, py, view); cam_pixel = view * view_pixels(sc) + py * sc.width + px; } else cam_pixel = as_i(q.r1[slot].z); }
+                const v3 to_camera = vnormalize(vsub(camera_position<VIEWS>(sc, q, view, cam_pixel), point));     // Raytracer.cpp:152
                 v3 diffuse = v3p(sc.ambient);
                 for (int L = 0; L < nL; L++) {
                     const uint32_t s = (uint32_t)q.shadow_base[level] + (uint32_t)L * (uint32_t)lit_cap + rank;

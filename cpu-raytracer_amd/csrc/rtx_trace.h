@@ -95,13 +95,51 @@ RTX_D void primary_ray(const DevScene & sc, int px, int py, RayFull & r, bool wi
 // ---- batches of views (rtx_render_views) -------------------------------------------------------------------------------------------
 // A view call renders VIRTUAL tiles over views x tiles: tile t is tile t % T of view t / T (T = tiles per frame), whose camera is
 // q.views[view] and whose pixels are [view * W * H, (view + 1) * W * H) of the view framebuffer.  Every kernel that
-// generates primary rays or needs the camera position has a VIEWS instantiation; VIEWS = false is exactly the single-camera code.
+// generates primary rays or needs the camera position has a VIEWS instantiation; VIEWS = 0 is exactly the single-camera code.
 // UNIFORM: the caller's wave covers 64 consecutive slots (one 8x8 block of one tile), so the tile, the view and the camera are
 // wave-uniform: computed once per wave in SGPRs, the camera by scalar loads.  The per-lane kernels (lane refill) compute them per lane.
 typedef const __attribute__((address_space(4))) rtx_f4v * rtx_cam_cptr;
 RTX_D int view_tiles(const DevScene & sc) { return sc.tile_count_x * ((sc.height + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE); }      // Window.cpp:11-12
 RTX_D int view_pixels(const DevScene & sc) { return sc.width * sc.height; }
-template <bool VIEWS, bool UNIFORM>
+
+// ---- ray views (rtx_render_rays) ------------------------------------------------------------------------------------------------------
+// The third value of the kernels' VIEWS parameter: virtual tiles over views x tiles like a view call, but the primary ray of pixel p
+// (p = view * W * H + y * W + x, the index of the view framebuffer) is the caller's record p of q.views — the device address of the
+// rays travels where the cameras' does, so DevScene, DevQueues and every kernel's argument layout stay as they are.  A record is a
+// rtx_ray: 18 floats (origin, direction, dO_dx, dO_dy, dD_dx, dD_dy), 72 bytes, so only 8-byte aligned: it is read as 16-byte vectors
+// of that alignment (global_load_dwordx4, legal at any dword address) plus one 8-byte vector.  The lanes of a wave that covers an 8x8
+// block read eight contiguous 576-byte row segments.  A record whose direction is (+-0, +-0, +-0) is no ray: its slot is a clipped slot.
+enum { RTX_CAM_TILES = 0, RTX_CAM_VIEWS = 1, RTX_CAM_RAYS = 2 };
+typedef float rtx_f4v8 __attribute__((ext_vector_type(4), aligned(8)));
+typedef float rtx_f3v8 __attribute__((ext_vector_type(3), aligned(8)));
+typedef float rtx_f2v8 __attribute__((ext_vector_type(2), aligned(8)));
+typedef const __attribute__((address_space(1))) float * rtx_ray_gptr;
+RTX_D rtx_ray_gptr ray_record(const DevQueues & q, int pixel) { return (rtx_ray_gptr)(const void *)q.views + (size_t)(uint32_t)pixel * 18u; }
+RTX_D rtx_f4v8 ray_ld4(rtx_ray_gptr p, int float_offset) { return *(const __attribute__((address_space(1))) rtx_f4v8 *)(p + float_offset); }
+RTX_D rtx_f2v8 ray_ld2(rtx_ray_gptr p, int float_offset) { return *(const __attribute__((address_space(1))) rtx_f2v8 *)(p + float_offset); }
+// origin and direction of record `pixel`: two loads per lane
+RTX_D void ray_record_od(const DevQueues & q, int pixel, v3 & o, v3 & d) {
+    const rtx_ray_gptr p = ray_record(q, pixel);
+    const rtx_f4v8 a = ray_ld4(p, 0); const rtx_f2v8 b = ray_ld2(p, 4);
+    o = V3(a.x, a.y, a.z); d = V3(a.w, b.x, b.y);
+}
+// A caller's ray with a NaN or infinite origin or direction component hits nothing: every hit test ends in a comparison with a NaN, or with
+// a zero or infinite distance (triangle: u = f * dot(s, h) is NaN or 0; sphere: the discriminant is NaN or the roots are; plane: t is +-0, +-inf
+// or NaN), exactly as in the reference's arithmetic — its frame value is Sky::sample of its direction.  The packet kernel does not walk it:
+// the NaN-free slab test is chosen by the INVERSE DIRECTION alone (pk_nan_possible), so a NaN origin with a finite direction (or an infinite
+// one through an instance transform: inf * 0) would pass every box through the hardware min / max, the zero padding slots of the 4-wide
+// records among them, whose child index 0 leads back to the root record: a walk that never ends.  Rays of deeper levels start at hit points
+// and camera rays at the camera, so only a ray call can bring such an origin.
+RTX_D bool ray_is_finite(const v3 o, const v3 d) {
+    return (__builtin_fabsf(o.x) < INFINITY) & (__builtin_fabsf(o.y) < INFINITY) & (__builtin_fabsf(o.z) < INFINITY) &
+           (__builtin_fabsf(d.x) < INFINITY) & (__builtin_fabsf(d.y) < INFINITY) & (__builtin_fabsf(d.z) < INFINITY);
+}
+RTX_D v3 ray_record_origin(const DevQueues & q, int pixel) {
+    const rtx_f3v8 a = *(const __attribute__((address_space(1))) rtx_f3v8 *)ray_record(q, pixel);
+    return V3(a.x, a.y, a.z);
+}
+
+template <int VIEWS, bool UNIFORM>
 RTX_D bool primary_pixel_v(const DevScene & sc, const DevQueues & q, uint32_t slot, int & px, int & py, int & view) {
     view = 0;
     if (!VIEWS) return primary_pixel(sc, q, slot, px, py);
@@ -110,6 +148,11 @@ RTX_D bool primary_pixel_v(const DevScene & sc, const DevQueues & q, uint32_t sl
     const int tiles = view_tiles(sc);
     view = t / tiles;
     tile_slot_pixel(t - view * tiles, (int)(slot & 1023u), sc.tile_count_x, px, py);
+    if (VIEWS == RTX_CAM_RAYS) {
+        if (!(px < sc.width && py < sc.height)) return false;
+        v3 o, d; ray_record_od(q, view * view_pixels(sc) + py * sc.width + px, o, d);
+        return !((d.x == 0.0f) & (d.y == 0.0f) & (d.z == 0.0f));          // an inactive record: no ray (NaN components compare unequal: a ray)
+    }
     return px < sc.width && py < sc.height;
 }
 // the camera of `view` as 3 float4: (pos, tl.x) (tl.y, tl.z, x.x, x.y) (x.z, y.x, y.y, y.z)   (rtx_camera, 48 B)
@@ -118,11 +161,26 @@ RTX_D v3 view_camera_position(const DevQueues & q, int view) {
     const rtx_f4v a = p[0];
     return V3(a.x, a.y, a.z);
 }
-template <bool VIEWS>
-RTX_D v3 camera_position(const DevScene & sc, const DevQueues & q, int view) { return VIEWS ? view_camera_position(q, view) : v3p(sc.cam_pos); }
-template <bool VIEWS>
+// what Raytracer.cpp:152 calls the camera: the tiles call's camera, the view's camera, or (ray views) the origin of the primary ray of `pixel`
+template <int VIEWS>
+RTX_D v3 camera_position(const DevScene & sc, const DevQueues & q, int view, int pixel) {
+    if (VIEWS == RTX_CAM_RAYS) return ray_record_origin(q, pixel);
+    return VIEWS ? view_camera_position(q, view) : v3p(sc.cam_pos);
+}
+template <int VIEWS>
 RTX_D void primary_ray_v(const DevScene & sc, const DevQueues & q, int view, int px, int py, RayFull & r, bool with_differentials) {
     if (!VIEWS) { primary_ray(sc, px, py, r, with_differentials); return; }
+    if (VIEWS == RTX_CAM_RAYS) {
+        const int pixel = view * view_pixels(sc) + py * sc.width + px;
+        ray_record_od(q, pixel, r.o, r.d);
+        if (with_differentials) {
+            const rtx_ray_gptr p = ray_record(q, pixel);
+            const rtx_f2v8 a = ray_ld2(p, 6); const rtx_f4v8 b = ray_ld4(p, 8), c = ray_ld4(p, 12); const rtx_f2v8 e = ray_ld2(p, 16);
+            r.dO_dx = V3(a.x, a.y, b.x); r.dO_dy = V3(b.y, b.z, b.w);
+            r.dD_dx = V3(c.x, c.y, c.z); r.dD_dy = V3(c.w, e.x, e.y);
+        }
+        return;
+    }
     const rtx_cam_cptr p = (rtx_cam_cptr)(const void *)(q.views + view);
     const rtx_f4v a = p[0], b = p[1], c = p[2];
     primary_ray_cam(V3(a.x, a.y, a.z), V3(a.w, b.x, b.y), V3(b.z, b.w, c.x), V3(c.y, c.z, c.w), px, py, r, with_differentials);
@@ -279,7 +337,7 @@ RTX_D bool shadow_slot_is_lit(const DevQueues & q, int level, uint32_t rank) {
     return (as_i(q.n0[(uint32_t)q.level_base[level] + rank].w) & NF_LIT) != 0;
 }
 
-template <bool ANY, bool COUNT, bool VIEWS = false>
+template <bool ANY, bool COUNT, int VIEWS = 0>
 __global__ __launch_bounds__(RTX_TRACE_BLOCK)
 void k_trace(const DevScene sc, const DevQueues q, const int level) {
     __shared__ int lds_stack[RTX_TRACE_BLOCK / RTX_WAVE][RTX_LDS_STACK][RTX_WAVE];
@@ -506,7 +564,7 @@ void k_trace(const DevScene sc, const DevQueues q, const int level) {
 //    reference's pop-time test.  For shadow rays D never changes, so the re-test is skipped.
 //
 // Work counters are produced by k_trace<ANY, true> (reference-order accounting); this kernel has none.
-template <bool ANY, bool VIEWS = false>
+template <bool ANY, int VIEWS = 0>
 __global__ __launch_bounds__(RTX_TRACE_BLOCK, ANY ? RTX_WAVES_ANY : RTX_WAVES_CLOSEST)
 void k_trace_fast(const DevScene sc, const DevQueues q, const int level, const int level_hi) {
     __shared__ int lds_stack[RTX_TRACE_BLOCK / RTX_WAVE][RTX_LDS_STACK][RTX_WAVE];

@@ -12,7 +12,7 @@ from typing import Dict, List, Optional
 import numpy as np
 
 from . import scene_io as sio
-from .ctypes_structs import RtxConfig, RtxFrame, RtxStats, RtxWork, RtxTextureDesc, RtxAovBuffers, AOV_CHANNELS, RTX_AOV_ALL, fill_frame
+from .ctypes_structs import RtxConfig, RtxFrame, RtxStats, RtxWork, RtxTextureDesc, RtxAovBuffers, RtxRay, AOV_CHANNELS, RTX_AOV_ALL, fill_frame
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "..", "csrc", "librtx_hip.so")
@@ -23,11 +23,13 @@ EXPORTS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error", "rt
            "rtx_bind_framebuffer", "rtx_set_stream", "rtx_present", "rtx_debug_libm", "rtx_debug_texture_sample", "rtx_debug_sky_sample", "rtx_debug_blas_wide", "rtx_debug_blas_wide_closest",
            "rtx_group_unique_id", "rtx_group_create", "rtx_group_render", "rtx_group_destroy", "rtx_group_attach", "rtx_group_create_local", "rtx_group_render_local",
            "rtx_group_layout", "rtx_group_slot_pixels", "rtx_debug_group_loopback", "rtx_debug_trace_rays", "rtx_debug_occluded", "rtx_debug_light_plot",
-           "rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer", "rtx_bind_aovs", "rtx_read_aovs"]
+           "rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer", "rtx_bind_aovs", "rtx_read_aovs",
+           "rtx_set_rays", "rtx_bind_rays", "rtx_render_rays"]
 # newer than the A/B variants tools/ab.py may load (RTX_HIP_LIB = a library built from an older commit): bound when the library has them,
 # otherwise a call raises AttributeError (undefined symbol)
 VIEW_EXPORTS = ("rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer")
 AOV_EXPORTS = ("rtx_bind_aovs", "rtx_read_aovs")
+RAY_EXPORTS = ("rtx_set_rays", "rtx_bind_rays", "rtx_render_rays")
 
 RTX_RENDER_COUNT_WORK = 1
 RTX_RENDER_SIMPLE_TRACE = 2
@@ -104,8 +106,12 @@ def load_library(path: Optional[str] = None):
     if hasattr(lib, "rtx_bind_aovs"):
         lib.rtx_bind_aovs.argtypes = [vp, u32, C.POINTER(RtxAovBuffers), C.c_int64]
         lib.rtx_read_aovs.argtypes = [vp, i32, i32, C.POINTER(RtxAovBuffers)]
+    if hasattr(lib, "rtx_set_rays"):
+        lib.rtx_set_rays.argtypes = [vp, vp, i32]
+        lib.rtx_bind_rays.argtypes = [vp, vp, i32]
+        lib.rtx_render_rays.argtypes = [vp, i32, i32, u32]
     for name in EXPORTS:
-        if name in VIEW_EXPORTS + AOV_EXPORTS and not hasattr(lib, name):
+        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         if name not in ("rtx_last_error",):
@@ -173,6 +179,81 @@ def views_array(cameras) -> np.ndarray:
     return cams
 
 
+RAY_FLOATS = C.sizeof(RtxRay) // 4          # 18: origin, direction, dO_dx, dO_dy, dD_dx, dD_dy
+
+
+def rays_array(rays, width: int, height: int) -> np.ndarray:
+    """Rays for rtx_set_rays as a contiguous float32 (V, H, W, 18) array: accepts that or (H, W, 18).  Raises before anything reaches
+    the library."""
+    if not isinstance(rays, np.ndarray):
+        raise TypeError(f"rays must be a numpy float32 array (V, H, W, {RAY_FLOATS}) or (H, W, {RAY_FLOATS}), not {type(rays).__name__}")
+    if rays.dtype != np.float32:
+        raise TypeError(f"rays must be float32, not {rays.dtype}")
+    if rays.ndim == 3:
+        rays = rays[None]
+    if rays.ndim != 4:
+        raise ValueError(f"rays must have shape (V, H, W, {RAY_FLOATS}) or (H, W, {RAY_FLOATS}), not {rays.shape}")
+    if rays.shape[3] != RAY_FLOATS:
+        raise ValueError(f"a ray is {RAY_FLOATS} floats (origin, direction, dO_dx, dO_dy, dD_dx, dD_dy), not {rays.shape[3]}")
+    if rays.shape[1] != height or rays.shape[2] != width:
+        raise ValueError(f"rays must be (V, {height}, {width}, {RAY_FLOATS}) for this context, not {rays.shape}")
+    if not 1 <= rays.shape[0] <= RTX_MAX_VIEWS:
+        raise ValueError(f"1 .. {RTX_MAX_VIEWS} ray views, not {rays.shape[0]}")
+    return np.ascontiguousarray(rays)
+
+
+def pinhole_rays(camera, width: int, height: int) -> np.ndarray:
+    """(H, W, 18) float32: the primary rays of Raytracer::render_tile (Raytracer.cpp:30-59) for `camera` (one scene_io.CAMERA record, or 12
+    floats: position, rotated_top_left_corner, rotated_x_axis, rotated_y_axis) in the oracle's and the kernels' operation order: unfused
+    multiply and add, correctly rounded sqrt and divide, dot products as x*x + (y*y + z*z), zero origin differentials.  Rendering them with
+    render_rays gives the bits of the camera's own frame."""
+    f32 = np.float32
+    cam = np.asarray(camera)
+    if cam.dtype == sio.CAMERA:
+        cam = np.ascontiguousarray(cam).reshape(-1)[:1].view(f32)
+    cam = np.ascontiguousarray(cam, f32).reshape(-1)
+    if cam.shape[0] != 12:
+        raise ValueError(f"a camera is 12 floats (position, top-left corner, x axis, y axis), not {cam.shape[0]}")
+    pos, tl, ax, ay = cam[0:3], cam[3:6], cam[6:9], cam[9:12]
+    j, i = np.meshgrid(np.arange(height, dtype=f32), np.arange(width, dtype=f32), indexing="ij")
+    i = i.reshape(-1, 1); j = j.reshape(-1, 1)
+    d = ax * i + (ay * j + tl)                                               # vmadd_s(ax, is, vmadd_s(ay, js, tl))
+
+    def dot(a, b):
+        return a[:, 0] * b[:, 0] + (a[:, 1] * b[:, 1] + a[:, 2] * b[:, 2])
+    dd = dot(d, d)
+    inv = f32(1.0) / np.sqrt(dd)
+    denom = inv / dd
+    axb = np.broadcast_to(ax, d.shape); ayb = np.broadcast_to(ay, d.shape)
+    rays = np.zeros((d.shape[0], RAY_FLOATS), f32)
+    rays[:, 0:3] = pos
+    rays[:, 3:6] = d * inv[:, None]
+    rays[:, 12:15] = (ax * dd[:, None] - d * dot(d, axb)[:, None]) * denom[:, None]
+    rays[:, 15:18] = (ay * dd[:, None] - d * dot(d, ayb)[:, None]) * denom[:, None]
+    return rays.reshape(height, width, RAY_FLOATS)
+
+
+def rays_from_directions(origins, directions) -> np.ndarray:
+    """(H, W, 18) float32 rays of per-pixel origins and directions, both (H, W, 3): the differentials are forward differences between
+    neighbouring pixels (d/dx: column x + 1 minus column x, d/dy: row y + 1 minus row y); the last column / row uses the backward
+    difference, a single column / row gets zero.  A convenience for camera models without analytic differentials (they only steer the
+    texture level of detail); it is not parity with anything."""
+    o = np.asarray(origins, np.float32); d = np.asarray(directions, np.float32)
+    if o.ndim != 3 or o.shape[2] != 3 or o.shape != d.shape:
+        raise ValueError(f"origins and directions must both be (H, W, 3), not {o.shape} and {d.shape}")
+
+    def diff(a, axis):
+        out = np.zeros_like(a)
+        if a.shape[axis] > 1:
+            f = np.diff(a, axis=axis)
+            if axis == 1:
+                out[:, :-1] = f; out[:, -1] = f[:, -1]
+            else:
+                out[:-1] = f; out[-1] = f[-1]
+        return out
+    return np.ascontiguousarray(np.concatenate([o, d, diff(o, 1), diff(o, 0), diff(d, 1), diff(d, 0)], axis=2), np.float32)
+
+
 def group_layout(width: int, height: int, world: int, rank: int):
     """(tiles_total, tiles_per_rank, own_tiles) of rank `rank` of `world` (rtx_group_layout: host function, no GPU needed).  The rank
     renders rtx_render_tiles(first_tile=rank, tile_stride=world, tile_count=own_tiles)."""
@@ -211,6 +292,8 @@ class Renderer:
             self.ctx = None
             raise RtxError(rc, "rtx_create")
         self._keep: List[np.ndarray] = []
+        self.ray_view_count = 0          # ray views in the context's own buffer (set_rays)
+        self._rays_bound = None          # (device pointer, views) bound with bind_rays
         if upload:
             self.upload_scene(scene)
             self.set_frame(scene)
@@ -396,6 +479,12 @@ class Renderer:
         which the C ABI reads as "the context's own stream") the work goes to a side stream that waits for the current stream and that the
         current stream then waits for: the same ordering.  aovs = {channel name: tensor} also writes those per-pixel AOV channels of the
         views (see bind_aovs): float32 / int32 tensors of shape (C, H, W) or (C, H, W, k) like rgb's, checked like rgb / packed.  Returns at once."""
+        first_view, view_count = self._view_range(first_view, view_count)
+        self._render_into(rgb, packed, first_view, view_count, aovs, flags, lambda fl: self.render_views_async(first_view, view_count, **fl))
+
+    def _render_into(self, rgb, packed, first_view: int, view_count: int, aovs, flags, launch, also=()):
+        """render_views_into / render_rays_into: checks the output tensors, moves the context to torch's current stream, binds the tensors and
+        calls launch(flags); `also` = further tensors the queued work reads."""
         import torch
         sc, dev = self.scene, self.device
         want = (("rgb", rgb, torch.float32, (sc.height, sc.width, 3)), ("packed", packed, torch.int32, (sc.height, sc.width)))
@@ -421,7 +510,6 @@ class Renderer:
         for name, t, _, _ in want:
             if t.device.type != "cuda" or t.device.index != dev:
                 raise ValueError(f"{name} must be on cuda:{dev} (this context's GPU), not {t.device}")
-        first_view, view_count = self._view_range(first_view, view_count)
         if view_count < 1 or first_view < 0 or first_view + view_count > rgb.shape[0]:
             raise ValueError(f"views [{first_view}, {first_view + view_count}) do not fit tensors of {rgb.shape[0]} views")
         cur = torch.cuda.current_stream(dev)
@@ -442,11 +530,85 @@ class Renderer:
         if aovs:
             self.bind_aovs(list(aovs), {name: t.data_ptr() for name, t in aovs.items()}, int(rgb.shape[0]) * sc.height * sc.width)
             flags = dict(flags, aov=True)
-        self.render_views_async(first_view, view_count, **flags)
+        launch(flags)
         if side is not None:
             cur.wait_stream(side)
-            for _, t, _, _ in want:
+            for t in tuple(w[1] for w in want) + tuple(also):
                 t.record_stream(side)      # the caching allocator must not hand the memory out before the render is done
+
+    # ---- ray views: caller-supplied primary rays (include/rtx.h: rtx_set_rays / rtx_bind_rays / rtx_render_rays) -------------------
+    def set_rays(self, rays):
+        """The primary rays of V ray views: numpy float32 (V, H, W, 18) or (H, W, 18), row = origin, direction, dO_dx, dO_dy, dD_dx, dD_dy;
+        a zero direction = no ray at that pixel.  Copied into the context's own ray buffer; a buffer bound with bind_rays is unbound."""
+        r = rays_array(rays, self.scene.width, self.scene.height)
+        if getattr(self, "_rays_bound", None):
+            self.bind_rays(None, 0)
+        self._chk(self.lib.rtx_set_rays(self.ctx, r.ctypes.data, r.shape[0]), "rtx_set_rays")
+        self.ray_view_count = int(r.shape[0])
+
+    def bind_rays(self, tensor_or_ptr, view_count: int = 0):
+        """Rays in device memory: a device pointer (or an object with data_ptr(), e.g. a torch tensor) to view_count x H x W x 18 float32;
+        None unbinds.  The memory stays the caller's and must outlive the work that reads it."""
+        ptr = tensor_or_ptr.data_ptr() if hasattr(tensor_or_ptr, "data_ptr") else tensor_or_ptr
+        self._chk(self.lib.rtx_bind_rays(self.ctx, int(ptr) if ptr else None, int(view_count)), "rtx_bind_rays")
+        self._rays_bound = (int(ptr), int(view_count)) if ptr else None
+
+    def _ray_range(self, first_view: int, view_count: Optional[int]):
+        if view_count is None:
+            bound = getattr(self, "_rays_bound", None)
+            view_count = (bound[1] if bound else getattr(self, "ray_view_count", 0)) - first_view
+        return int(first_view), int(view_count)
+
+    def render_rays_async(self, first_view: int = 0, view_count: Optional[int] = None, **flags):
+        first_view, view_count = self._ray_range(first_view, view_count)
+        self._chk(self.lib.rtx_render_rays(self.ctx, first_view, view_count, render_flags(**flags)), "rtx_render_rays")
+
+    def render_rays(self, first_view: int = 0, view_count: Optional[int] = None, aovs=(), **flags) -> Dict:
+        """Ray views [first_view, first_view + view_count) of the rays set by set_rays (or bound by bind_rays) in one rtx_render_rays call
+        (flags as render): rgb (V, H, W, 3) float32, packed (V, H, W) uint32, stats / work summed over the ray views, and the AOV channels
+        named in aovs, each (V, H, W[, k]).  Uses the context's own view framebuffer and AOV buffers.  Pixels without a ray keep what the
+        buffers held."""
+        if getattr(self, "_view_fb", None):
+            self.bind_view_framebuffer(None, None)
+        names = aov_names(aovs)
+        if names:
+            self.bind_aovs(names)
+            flags = dict(flags, aov=True)
+        first_view, view_count = self._ray_range(first_view, view_count)
+        self.render_rays_async(first_view, view_count, **flags)
+        stats, work = self.stats()
+        sc = self.scene
+        rgb = np.zeros((max(view_count, 0), sc.height, sc.width, 3), np.float32)
+        packed = np.zeros((max(view_count, 0), sc.height, sc.width), np.uint32)
+        self._chk(self.lib.rtx_read_views(self.ctx, first_view, view_count, rgb.ctypes.data, packed.ctypes.data), "rtx_read_views")
+        out = {"rgb": rgb, "packed": packed, "stats": stats, "work": work}
+        if names:
+            out.update(self.read_aovs(names, first_view, view_count))
+        return out
+
+    def render_rays_into(self, rgb, packed, rays, aovs: Optional[Dict] = None, **flags):
+        """Render the ray views of `rays`, a float32 device tensor (V, H, W, 18), into caller-owned device tensors: rgb float32 (C, H, W, 3)
+        and packed int32 (C, H, W) of C >= V views (ray view v lands in rgb[v] / packed[v]) and, with aovs = {channel name: tensor}, those AOV
+        channels, shaped like render_views_into's.  Everything is checked (dtype, shape, contiguity, device) before the library is reached.
+        Queued on torch's current stream like render_views_into; `rays` is read when the work runs and must stay alive until then.  The
+        tensor is unbound again before this returns (queued work keeps the address it was launched with): a later render_rays uses the rays
+        of set_rays, not memory torch may have reused.  Returns at once."""
+        import torch
+        sc, dev = self.scene, self.device
+        if not isinstance(rays, torch.Tensor):
+            raise TypeError(f"rays must be a torch.Tensor, not {type(rays).__name__}")
+        if rays.dtype != torch.float32:
+            raise TypeError(f"rays must be torch.float32, not {rays.dtype}")
+        if rays.dim() != 4 or tuple(rays.shape[1:]) != (sc.height, sc.width, RAY_FLOATS):
+            raise ValueError(f"rays must have shape (views, {sc.height}, {sc.width}, {RAY_FLOATS}), not {tuple(rays.shape)}")
+        if not 1 <= rays.shape[0] <= RTX_MAX_VIEWS:
+            raise ValueError(f"1 .. {RTX_MAX_VIEWS} ray views, not {rays.shape[0]}")
+        if not rays.is_contiguous():
+            raise ValueError("rays must be contiguous")
+        if rays.device.type != "cuda" or rays.device.index != dev:
+            raise ValueError(f"rays must be on cuda:{dev} (this context's GPU), not {rays.device}")
+        count = int(rays.shape[0])
+        self._render_into(rgb, packed, 0, count, aovs, flags, lambda fl: (self.bind_rays(rays.data_ptr(), count), self.render_rays_async(0, count, **fl), self.bind_rays(None)), (rays,))
 
     def enable_timing(self, on: bool = True):
         self._chk(self.lib.rtx_enable_kernel_timing(self.ctx, 1 if on else 0), "rtx_enable_kernel_timing")

@@ -26,6 +26,12 @@ class RtxCamera(C.Structure):
                 ("rotated_x_axis", C.c_float * 3), ("rotated_y_axis", C.c_float * 3)]
 
 
+class RtxRay(C.Structure):
+    """rtx_ray: one caller-supplied primary ray, the 18 floats of a row of Renderer.set_rays / debug_trace_rays."""
+    _fields_ = [("origin", C.c_float * 3), ("direction", C.c_float * 3), ("dO_dx", C.c_float * 3), ("dO_dy", C.c_float * 3),
+                ("dD_dx", C.c_float * 3), ("dD_dy", C.c_float * 3)]
+
+
 class RtxFrame(C.Structure):
     _fields_ = [("camera", RtxCamera), ("ambient", C.c_float * 3), ("pad0", C.c_int32),
                 ("tlas_nodes", C.c_void_p), ("tlas_node_count", C.c_int32),
@@ -86,6 +92,7 @@ class RtxAovBuffers(C.Structure):
 assert C.sizeof(RtxAovBuffers) == 64
 assert C.sizeof(RtxConfig) == 64 and C.sizeof(RtxTextureDesc) == 80 and C.sizeof(RtxCamera) == 48
 assert C.sizeof(RtxWork) == 160
+assert C.sizeof(RtxRay) == 72
 
 
 def fill_frame(fr: RtxFrame, sc: "sio.Scene", keep: list) -> None:

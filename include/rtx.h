@@ -336,12 +336,49 @@ int rtx_set_views(rtx_ctx * ctx, const rtx_camera * cameras, int32_t view_count)
  * outside a bound view framebuffer.  Queued like rtx_render_tiles.                                                                 */
 int rtx_render_views(rtx_ctx * ctx, int32_t first_view, int32_t view_count, uint32_t flags);
 /* views [first_view, first_view + view_count) of the view framebuffer (waits for the context's stream); either pointer may be NULL.
+ * The range may reach as far as the views set or the ray views set or bound (rtx_set_rays / rtx_bind_rays), whichever are more.
  * Pixels of views that were never rendered are zero.                                                                              */
 int rtx_read_views(rtx_ctx * ctx, int32_t first_view, int32_t view_count, float * rgb_f32, uint32_t * packed_u32);
 /* Render views into caller-owned device buffers of view_capacity views (e.g. torch tensors [V,H,W,3] f32 / [V,H,W] i32) instead of
  * the context's own view framebuffer (allocated on first use, grown only); both NULL restores the own one.  Does not wait: work
  * already queued keeps writing the buffers it was queued with.                                                                     */
 int rtx_bind_view_framebuffer(rtx_ctx * ctx, void * rgb_f32_dev, void * packed_u32_dev, int32_t view_capacity);
+
+/* ---- ray views: caller-supplied primary rays ------------------------------------------------------------------------------------
+ * V images of width x height primary rays that are not a rtx_camera's: fisheye, equirectangular or orthographic cameras, a lidar scan
+ * pattern (64 x 1024 beams = a 1024 x 64 context), lens distortion, rolling shutter, a re-render of some pixels.  The layout is raster:
+ * ray view*W*H + y*W + x belongs to the pixel with that index, the pixel index of the view framebuffer and of the AOVs.  Output goes
+ * where rtx_render_views puts it: the view framebuffer (own, or rtx_bind_view_framebuffer; rtx_read_views) and, with RTX_RENDER_AOV,
+ * the bound AOV channels at the view pixel index.
+ * Pixel p gets exactly Raytracer::bounce(ray_p, NUMBER_OF_BOUNCES) with one defined change: `to_camera` (Raytracer.cpp:152) is at every
+ * depth normalize(origin_p - hit.point), origin_p = the origin of the pixel's own primary ray (for the rays of a pinhole camera that is
+ * the camera position: nothing changes).  Directions are used as given — the caller normalises them; distances are in units of
+ * |direction|.  The differentials feed the texture LOD exactly like a camera ray's.
+ * A ray whose direction is exactly (+-0, +-0, +-0) is no ray: its slot is treated like a clipped slot of an edge tile — nothing is
+ * written to colour or AOVs, it is not counted in rtx_stats, it spawns nothing.  Any other float values, NaN and inf included, are legal
+ * input.  A ray with a NaN or infinite origin or direction component hits nothing in the reference's arithmetic (every hit test ends in a
+ * comparison with a NaN, a zero or an infinite distance): it is counted, and its pixel is Sky::sample of its direction.
+ * A packet is still 64 consecutive slots = one 8x8 pixel block: incoherent rays are legal but cost what incoherent packets cost
+ * (lay rays that travel together out in 8x8 blocks where the camera model allows it).
+ * Out of scope: heat-map mode (RTX_ERR_STATE), the rtx_group_* path, per-view resolution.  rtx_set_views state and ray state are
+ * independent of each other.                                                                                                          */
+typedef struct rtx_ray {            /* 72 B = the 18 floats of rtx_debug_trace_rays */
+    float origin[3], direction[3], dO_dx[3], dO_dy[3], dD_dx[3], dD_dy[3];
+} rtx_ray;
+/* view_count x height x width rays from host memory into the context's own ray buffer (grown only, freed by rtx_destroy).  Copied
+ * before return and ordered on the context's stream like rtx_set_views: work already queued keeps the rays it was queued with.
+ * RTX_ERR_INVALID_ARG: view_count < 1, > RTX_MAX_VIEWS, or view_count * width * height >= 2^31.                                       */
+int rtx_set_rays(rtx_ctx * ctx, const rtx_ray * host_rays, int32_t view_count);
+/* Rays in caller-owned device memory (e.g. a torch tensor [V,H,W,18] f32, 8-byte aligned) take the place of the own buffer; NULL
+ * unbinds (the rays of rtx_set_rays, if any, are current again).  Does not wait: work already queued keeps the buffer it was queued
+ * with, which must stay valid until that work is done.  The buffer is read when the work runs: values written into it (in stream
+ * order) before a render call are the ones rendered.  Same RTX_ERR_INVALID_ARG cases as rtx_set_rays, and an address that is not 8-byte aligned.                                 */
+int rtx_bind_rays(rtx_ctx * ctx, const void * rays_dev, int32_t view_count);
+/* Render ray views [first_view, first_view + view_count) of the bound rays, else of the rays set.  Every RTX_RENDER_* flag is honoured.
+ * rtx_get_stats afterwards = totals over the rendered ray views, num_primary_rays = the live rays.  RTX_ERR_STATE before rtx_set_frame,
+ * before any rays are set or bound, or in heat-map mode; RTX_ERR_INVALID_ARG for view_count < 1 or > RTX_MAX_VIEWS, a range outside
+ * the rays, outside a bound view framebuffer or (RTX_RENDER_AOV) outside the AOV capacity.  Queued like rtx_render_tiles.              */
+int rtx_render_rays(rtx_ctx * ctx, int32_t first_view, int32_t view_count, uint32_t flags);
 
 /* ---- per-pixel primary-hit AOVs (G-buffer channels) ---------------------------------------------------------------------------------
  * What Raytracer::bounce (Raytracer.cpp:87-145) knows about the PRIMARY ray of each pixel, written next to the colour by a render call
