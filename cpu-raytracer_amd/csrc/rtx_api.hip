@@ -28,6 +28,8 @@
 #include "rtx_shade.h"
 #include "rtx_packet.h"
 #include "rtx_present.h"
+#include "rtx_update.h"
+#include <rocprim/device/device_radix_sort.hpp>      // rtx_update_instances, scenes beyond one workgroup: header-only, part of ROCm
 
 #define SLOT_BUDGET (48ll * 1000 * 1000)      // ray slots per batch of tiles (see plan_batch)
 
@@ -62,6 +64,7 @@ struct Knobs {
     int pk4_order;               // RTX_PK4_ORDER          slot order of the 4-wide records (0: smallest stack need first)
     bool merge_any, no_wide, no_wide_closest, fail_item_alloc, graph; int lpt;
     bool fuse_shade;             // RTX_FUSE_SHADE         the closest-hit packet kernel shades its own hits (0: a k_shade launch per level)
+    int update_small_max;        // RTX_UPDATE_SMALL_MAX   rtx_update_instances: scenes up to this many instances take the one-workgroup kernel (0: always the multi-launch path)
 };
 
 struct KernelTime { const char * name; hipEvent_t a, b; };
@@ -92,6 +95,10 @@ struct rtx_ctx {
     int stage_next = 0;
     DevScene scene;
     bool frame_set = false;
+    // rtx_update_instances: a device block of its own for the updated instances / TLAS (both node layouts) / indices and the builder's scratch
+    // (AABBs, bounds, keys), grown only; the DevScene pointers are switched to it, the rest of the frame stays in d_frame.  d_upd_sort = rocPRIM's
+    // temporary storage and the unsorted keys (multi-launch path), grown only
+    DevBuf d_upd, d_upd_sort; int upd_cap = 0;
     // rtx_set_views: the cameras of a batch of views (device array, grown only, filled by a stream-ordered copy from a ring of pinned
     // staging buffers like the frame block) and the view framebuffer (view_fb_cap views, allocated on first use, grown only) or the
     // caller's buffers of ext_vcap views (rtx_bind_view_framebuffer)
@@ -365,6 +372,7 @@ extern "C" int rtx_create(const rtx_config * config, rtx_ctx ** out_ctx) {
     K.graph = knob_int("RTX_GRAPH", 0, 0, 1) != 0;                      // 1: identical rtx_render_tiles calls replay a captured hipGraph
     K.no_wide_closest = knob_int("RTX_PK_WIDE_CLOSEST", 1, 0, 1) == 0;  // 0: binary per-lane phase of the closest-hit walk for every mesh
     K.fuse_shade = knob_int("RTX_FUSE_SHADE", 0, 0, 1) != 0;      // measured: 1.51 vs 1.28 ms per cfg3 frame with three frames in flight: off
+    K.update_small_max = (int)knob_int("RTX_UPDATE_SMALL_MAX", RTX_UPDATE_SMALL_MAX, 0, RTX_UPDATE_SMALL_MAX);
     K.fail_item_alloc = knob_int("RTX_DEBUG_FAIL_ITEM_ALLOC", 0, 0, 1) != 0;      // tests: the item buffer's allocation fails (a size no device has), the fallback kernel must take over
     int bpc = 0;
     hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k_trace_fast<false>, RTX_TRACE_BLOCK, 0);
@@ -420,7 +428,7 @@ extern "C" int rtx_destroy(rtx_ctx * c) {
     if (c->stream) hipStreamSynchronize(c->stream);
     for (auto & v : c->blas_allocs) for (void * p : v) hipFree(p);
     for (void * p : c->tex_allocs) if (p) hipFree(p);
-    DevBuf * bufs[] = { &c->d_blas, &c->d_materials, &c->d_textures, &c->d_sky, &c->d_ewa, &c->d_frame, &c->d_counters, &c->d_spill, &c->d_fb_rgb, &c->d_fb_packed, &c->d_display, &c->d_gamma, &c->d_pk_heads, &c->d_pk_fifo, &c->d_pk_items, &c->d_pk_item_count, &c->d_stats_partial, &c->d_dbg_s0, &c->d_dbg_s1, &c->d_pk_cost, &c->d_pk_order, &c->d_views, &c->d_vfb_rgb, &c->d_vfb_packed, &c->d_rays };
+    DevBuf * bufs[] = { &c->d_blas, &c->d_materials, &c->d_textures, &c->d_sky, &c->d_ewa, &c->d_frame, &c->d_counters, &c->d_spill, &c->d_fb_rgb, &c->d_fb_packed, &c->d_display, &c->d_gamma, &c->d_pk_heads, &c->d_pk_fifo, &c->d_pk_items, &c->d_pk_item_count, &c->d_stats_partial, &c->d_dbg_s0, &c->d_dbg_s1, &c->d_pk_cost, &c->d_pk_order, &c->d_views, &c->d_vfb_rgb, &c->d_vfb_packed, &c->d_rays, &c->d_upd, &c->d_upd_sort };
     for (DevBuf * b : bufs) if (b->p) hipFree(b->p);
     for (DevBuf & b : c->d_aov) if (b.p) hipFree(b.p);
     for (DevBuf & b : c->qb) if (b.p) hipFree(b.p);
@@ -774,6 +782,104 @@ static void launch_timed(rtx_ctx * c, const char * name, hipStream_t stream, F &
         hipEventRecord(kt.b, stream);
         c->times.push_back(kt);
     } else launch();
+}
+
+// ---- device-side scene update (include/rtx.h: rtx_update_instances / rtx_read_frame_state; kernels in rtx_update.h) -------------------
+// The instance records, the TLAS in both node layouts and its indices are rebuilt from poses in device memory into a block of their own
+// (d_upd), and the DevScene pointers are switched to it; spheres, planes, lights and the camera stay where rtx_set_frame put them.  Everything
+// is queued on the context's stream: work queued before keeps the state it was queued with (DevScene travels by value; a render call ends
+// with the shadow-ray stream joined back into the context's stream, so the kernels here run after every reader of the block's previous
+// contents), the next render call reads the new state.  The shape of the tree is a function of the instance count, so the depth the
+// stack rules need (validate_references, render_tiles_impl) is known here without a read-back.  Nothing waits for the device except
+// growth of the block (the first call, or more instances than ever before) — the case rtx_set_frame waits in too.
+extern "C" int rtx_update_instances(rtx_ctx * c, const void * positions_dev, const void * rotations_dev, int32_t instance_count) {
+    if (!c) return RTX_ERR_INVALID_ARG;
+    if (!positions_dev || !rotations_dev || ((uintptr_t)positions_dev & 3) || ((uintptr_t)rotations_dev & 3) || instance_count < 1) {
+        c->err = "rtx_update_instances: null or misaligned pose pointer, or no instances"; return RTX_ERR_INVALID_ARG; }
+    if (instance_count > RTX_UPDATE_MAX_INSTANCES) { c->err = "rtx_update_instances supports up to 65 536 instances"; return RTX_ERR_LIMIT; }
+    if (!c->frame_set) { c->err = "rtx_update_instances before rtx_set_frame"; return RTX_ERR_STATE; }
+    if (instance_count != c->scene.instance_count) { c->err = "rtx_update_instances: instance_count differs from the frame's"; return RTX_ERR_INVALID_ARG; }
+    // the tree's depth is a function of the count: a tree the configured stack cannot hold (validate_references' rule) is refused here, before
+    // anything is queued or switched, and the frame state stays what it was
+    if (rtxu::tree_inner_depth(instance_count) + 2 > c->cfg.stack_size) {
+        c->err = "rtx_update_instances: the balanced TLAS of " + std::to_string(instance_count) + " instances needs " + std::to_string(rtxu::tree_inner_depth(instance_count) + 2) +
+                 " stack entries, rtx_config.stack_size allows fewer (BVH_TRAVERSAL_STACK_SIZE, Config.h:25)";
+        return RTX_ERR_LIMIT;
+    }
+    hipSetDevice(c->cfg.device);
+    const int n = instance_count, levels = rtxu::tree_levels(n), slots = rtxu::tree_node_count(n);
+    const bool small = n <= c->knobs.update_small_max;
+    // [nodes, lane layout][nodes, packet layout][indices][instances][AABBs][sorted keys][bounds], every part 256-byte aligned
+    const size_t len[7] = { (size_t)slots * 32, (size_t)slots * 32, (size_t)n * 4, (size_t)n * sizeof(rtx_instance), (size_t)n * 24, (size_t)n * 8, 24 };
+    size_t off[7], total = 0;
+    for (int k = 0; k < 7; k++) { off[k] = total; total += (len[k] + 255) & ~(size_t)255; }
+    if (n > c->upd_cap || total > c->d_upd.cap) {           // growth: never while the scene points into the block (the count is the frame's, the block holds it)
+        HIP_OK(c, hipStreamSynchronize(c->stream));
+        if (int rc = ensure(c, c->d_upd, total)) return rc;
+        c->upd_cap = n;
+    }
+    size_t sort_bytes = 0;
+    if (!small) {                                           // rocPRIM's temporary storage, sized for this n by a host-side query; grown only
+        if (rocprim::radix_sort_keys(nullptr, sort_bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr, (unsigned int)n, 0u, (unsigned int)RTXU_KEY_BITS, c->stream) != hipSuccess) {
+            hipGetLastError(); c->err = "rocprim::radix_sort_keys size query failed"; return RTX_ERR_HIP; }
+        const size_t keys_in = ((size_t)n * 8 + 255) & ~(size_t)255;
+        if (keys_in + sort_bytes > c->d_upd_sort.cap) {
+            HIP_OK(c, hipStreamSynchronize(c->stream));
+            if (int rc = ensure(c, c->d_upd_sort, keys_in + sort_bytes)) return rc;
+        }
+    }
+    char * const ub = (char *)c->d_upd.p;
+    DevUpdate u;
+    u.positions = (const float *)positions_dev; u.rotations = (const float *)rotations_dev;
+    u.src_instances = c->scene.instances; u.blas = c->scene.blas;
+    u.nodes = (float4 *)(ub + off[0]); u.pk_nodes = (float4 *)(ub + off[1]); u.indices = (int32_t *)(ub + off[2]);
+    u.instances = (rtx_instance *)(ub + off[3]); u.aabbs = (float *)(ub + off[4]); u.keys = (uint64_t *)(ub + off[5]); u.bounds = (uint32_t *)(ub + off[6]);
+    u.n = n; u.levels = levels;
+    if (small) {
+        launch_timed(c, "k_update_small", c->stream, [&] { hipLaunchKernelGGL(k_update_small, dim3(1), dim3(RTX_UPDATE_BLOCK), 0, c->stream, u); });
+    } else {
+        uint64_t * const keys_in = (uint64_t *)c->d_upd_sort.p;
+        void * const sort_tmp = (char *)c->d_upd_sort.p + (((size_t)n * 8 + 255) & ~(size_t)255);
+        const int blocks = (n + 255) / 256;
+        HIP_OK(c, hipMemsetAsync(u.bounds, 0xff, 24, c->stream));
+        launch_timed(c, "k_update_instances", c->stream, [&] { hipLaunchKernelGGL(k_update_instances, dim3(blocks), dim3(256), 0, c->stream, u); });
+        launch_timed(c, "k_update_keys", c->stream, [&] { hipLaunchKernelGGL(k_update_keys, dim3(blocks), dim3(256), 0, c->stream, u, keys_in); });
+        hipError_t se = hipSuccess;
+        launch_timed(c, "update_radix_sort", c->stream, [&] { se = rocprim::radix_sort_keys(sort_tmp, sort_bytes, (const uint64_t *)keys_in, u.keys, (unsigned int)n, 0u, (unsigned int)RTXU_KEY_BITS, c->stream); });
+        if (se != hipSuccess) { hipGetLastError(); c->err = std::string("rocprim::radix_sort_keys: ") + hipGetErrorString(se); return RTX_ERR_HIP; }
+        for (int d = levels; d > RTX_UPDATE_TOP_LEVELS; d--)
+            launch_timed(c, "k_update_level", c->stream, [&] { hipLaunchKernelGGL(k_update_level, dim3(((1 << d) + 255) / 256), dim3(256), 0, c->stream, u, d); });
+        launch_timed(c, "k_update_top", c->stream, [&] { hipLaunchKernelGGL(k_update_top, dim3(1), dim3(RTX_UPDATE_BLOCK), 0, c->stream, u); });
+    }
+    HIP_OK(c, hipGetLastError());
+    DevScene & s = c->scene;
+    s.tlas_nodes = u.nodes; s.pk_tlas_nodes = u.pk_nodes; s.tlas_node_count = slots;
+    s.tlas_indices = u.indices; s.tlas_index_count = n; s.instances = u.instances;
+    c->tlas_inner_depth = rtxu::tree_inner_depth(n);
+    c->refs_dirty = true;
+    return RTX_OK;
+}
+
+extern "C" int rtx_read_frame_state(rtx_ctx * c, rtx_instance * instances, rtx_bvh_node * tlas_nodes, int32_t * tlas_node_count, int32_t * tlas_indices) {
+    if (!c) return RTX_ERR_INVALID_ARG;
+    if (!c->frame_set) { c->err = "rtx_read_frame_state before rtx_set_frame"; return RTX_ERR_STATE; }
+    hipSetDevice(c->cfg.device);
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    const DevScene & s = c->scene;
+    if (tlas_node_count) *tlas_node_count = s.tlas_node_count;
+    if (instances && s.instance_count) HIP_OK(c, hipMemcpy(instances, s.instances, (size_t)s.instance_count * sizeof(rtx_instance), hipMemcpyDeviceToHost));
+    if (tlas_indices && s.tlas_index_count) HIP_OK(c, hipMemcpy(tlas_indices, s.tlas_indices, (size_t)s.tlas_index_count * 4, hipMemcpyDeviceToHost));
+    if (tlas_nodes && s.tlas_node_count) {                  // the lane layout back into the reference's (convert_nodes inverted)
+        std::vector<float4> nd((size_t)2 * s.tlas_node_count);
+        HIP_OK(c, hipMemcpy(nd.data(), s.tlas_nodes, nd.size() * 16, hipMemcpyDeviceToHost));
+        for (int i = 0; i < s.tlas_node_count; i++) {
+            const float4 a = nd[2 * (size_t)i], b = nd[2 * (size_t)i + 1];
+            tlas_nodes[i].aabb_min[0] = a.x; tlas_nodes[i].aabb_min[1] = a.y; tlas_nodes[i].aabb_min[2] = a.z;
+            tlas_nodes[i].aabb_max[0] = b.x; tlas_nodes[i].aabb_max[1] = b.y; tlas_nodes[i].aabb_max[2] = b.z;
+            memcpy(&tlas_nodes[i].left_or_first, &a.w, 4); memcpy(&tlas_nodes[i].count, &b.w, 4);
+        }
+    }
+    return RTX_OK;
 }
 
 static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_stride, int32_t tile_count, uint32_t flags, uint32_t * tile_major, int views = RTX_CAM_TILES);

@@ -5,6 +5,7 @@
 // matrices and TLAS nodes dumped from the real reference), and those classes evaluate
 // left-to-right with plain mul/add (Vector3.h:33-43, Matrix4.h:31-68, Quaternion.h:128-133).
 #include "../../include/rtx_host.h"
+#include "../csrc/rtx_update_math.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -349,6 +350,78 @@ extern "C" int rtxh_tlas_build(rtxh_tlas * t, const float * positions, const flo
     memcpy(indices_out, t->idx[0].data(), sizeof(int) * n);
     *node_count_out = b.node_index;
     return b.degenerate ? RTX_ERR_STATE : RTX_OK;
+}
+
+// ---- the balanced TLAS of rtx_update_instances: csrc/rtx_update_math.h, the code the kernels run, driven sequentially ----------------------
+extern "C" int32_t rtxh_tlas_balanced_node_count(int32_t n) { return n < 1 || n > RTX_UPDATE_MAX_INSTANCES ? 0 : rtxu::tree_node_count(n); }
+extern "C" int32_t rtxh_tlas_balanced_inner_depth(int32_t n) { return rtxu::tree_inner_depth(n); }
+
+extern "C" int rtxh_tlas_build_balanced(int32_t n, const float * positions, const float * aabbs,
+                                        rtx_bvh_node * nodes_out, int32_t * indices_out, int32_t * node_count_out) {
+    if (n < 1 || !positions || !aabbs || !nodes_out || !indices_out || !node_count_out) return RTX_ERR_INVALID_ARG;
+    if (n > RTX_UPDATE_MAX_INSTANCES) return RTX_ERR_LIMIT;
+    uint32_t bounds[6] = { RTXU_KEY_LO_INIT, RTXU_KEY_LO_INIT, RTXU_KEY_LO_INIT, RTXU_KEY_HI_INIT, RTXU_KEY_HI_INIT, RTXU_KEY_HI_INIT };
+    for (int i = 0; i < n; i++)
+        for (int a = 0; a < 3; a++) {
+            const float p = positions[3 * i + a];
+            if (!rtxu::is_finite(p)) continue;
+            const uint32_t k = rtxu::ordered_key(p);
+            if (k < bounds[a]) bounds[a] = k;
+            if (k > bounds[3 + a]) bounds[3 + a] = k;
+        }
+    std::vector<uint64_t> keys((size_t)n);
+    for (int i = 0; i < n; i++) {
+        rtxu::Box b; memcpy(b.mn, aabbs + 6 * (size_t)i, 12); memcpy(b.mx, aabbs + 6 * (size_t)i + 3, 12);
+        keys[i] = rtxu::sort_key(positions + 3 * i, bounds, (uint32_t)i, rtxu::box_is_finite(b));
+    }
+    std::sort(keys.begin(), keys.end());                                // the keys are distinct (the index is part of them): one result
+    const int levels = rtxu::tree_levels(n), slots = rtxu::tree_node_count(n);
+    memset(nodes_out, 0, sizeof(rtx_bvh_node) * (size_t)slots);
+    auto load = [&](int slot) { rtxu::Box b; memcpy(b.mn, nodes_out[slot].aabb_min, 12); memcpy(b.mx, nodes_out[slot].aabb_max, 12); return b; };
+    auto store = [&](int slot, const rtxu::Box & b, int32_t left_or_first, int32_t count) {
+        memcpy(nodes_out[slot].aabb_min, b.mn, 12); memcpy(nodes_out[slot].aabb_max, b.mx, 12);
+        nodes_out[slot].left_or_first = left_or_first; nodes_out[slot].count = count;
+    };
+    for (int d = levels; d >= 0; d--)
+        for (int j = 0; j < (1 << d); j++) {
+            int first;
+            const int cnt = rtxu::node_range(n, d, j, &first), slot = rtxu::node_slot(d, j);
+            if (cnt == 0) continue;
+            rtxu::Box b;
+            if (cnt == 1) {
+                const int inst = (int)(keys[first] & 0xffffu);
+                indices_out[first] = inst;
+                memcpy(b.mn, aabbs + 6 * (size_t)inst, 12); memcpy(b.mx, aabbs + 6 * (size_t)inst + 3, 12);
+                rtxu::fix_if_needed(b);
+                store(slot, b, first, 1);
+            } else {
+                const int left = (2 << d) | (2 * j);
+                int axis;
+                b = rtxu::join_boxes(load(left), load(left + 1), &axis);
+                store(slot, b, left, (int32_t)((uint32_t)axis << 30));
+            }
+        }
+    *node_count_out = slots;
+    return RTX_OK;
+}
+
+extern "C" int rtxh_scene_update_balanced(int32_t n, const float * positions, const float * rotations, const int32_t * blas_ids,
+                                          const float * blas_root_aabbs, rtx_instance * instances_out, rtx_bvh_node * tlas_nodes_out,
+                                          int32_t * tlas_indices_out, int32_t * tlas_node_count_out) {
+    if (n < 1 || !positions || !rotations || !blas_ids || !blas_root_aabbs || !instances_out || !tlas_nodes_out || !tlas_indices_out || !tlas_node_count_out)
+        return RTX_ERR_INVALID_ARG;
+    if (n > RTX_UPDATE_MAX_INSTANCES) return RTX_ERR_LIMIT;
+    std::vector<float> aabbs(6 * (size_t)n);
+    for (int i = 0; i < n; i++) {
+        memset(&instances_out[i], 0, sizeof(rtx_instance));
+        instances_out[i].blas_id = blas_ids[i];
+        const float * box = blas_root_aabbs + 6 * (size_t)blas_ids[i];
+        rtxu::world_matrix(positions + 3 * i, rotations + 4 * i, instances_out[i].world);
+        rtxu::invert(instances_out[i].world, instances_out[i].world_inv);
+        const rtxu::Box b = rtxu::transform_box(instances_out[i].world, box, box + 3);
+        memcpy(&aabbs[6 * (size_t)i], b.mn, 12); memcpy(&aabbs[6 * (size_t)i + 3], b.mx, 12);
+    }
+    return rtxh_tlas_build_balanced(n, positions, aabbs.data(), tlas_nodes_out, tlas_indices_out, tlas_node_count_out);
 }
 
 // The reference's non-spatial BLAS build (BottomLevelBVH::build_bvh, BottomLevelBVH.cpp:72-106): the same generic builder

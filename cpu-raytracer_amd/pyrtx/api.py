@@ -24,12 +24,14 @@ EXPORTS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error", "rt
            "rtx_group_unique_id", "rtx_group_create", "rtx_group_render", "rtx_group_destroy", "rtx_group_attach", "rtx_group_create_local", "rtx_group_render_local",
            "rtx_group_layout", "rtx_group_slot_pixels", "rtx_debug_group_loopback", "rtx_debug_trace_rays", "rtx_debug_occluded", "rtx_debug_light_plot",
            "rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer", "rtx_bind_aovs", "rtx_read_aovs",
-           "rtx_set_rays", "rtx_bind_rays", "rtx_render_rays"]
+           "rtx_set_rays", "rtx_bind_rays", "rtx_render_rays", "rtx_update_instances", "rtx_read_frame_state"]
 # newer than the A/B variants tools/ab.py may load (RTX_HIP_LIB = a library built from an older commit): bound when the library has them,
 # otherwise a call raises AttributeError (undefined symbol)
 VIEW_EXPORTS = ("rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer")
 AOV_EXPORTS = ("rtx_bind_aovs", "rtx_read_aovs")
 RAY_EXPORTS = ("rtx_set_rays", "rtx_bind_rays", "rtx_render_rays")
+UPDATE_EXPORTS = ("rtx_update_instances", "rtx_read_frame_state")
+RTX_UPDATE_MAX_INSTANCES = 65536
 
 RTX_RENDER_COUNT_WORK = 1
 RTX_RENDER_SIMPLE_TRACE = 2
@@ -110,8 +112,11 @@ def load_library(path: Optional[str] = None):
         lib.rtx_set_rays.argtypes = [vp, vp, i32]
         lib.rtx_bind_rays.argtypes = [vp, vp, i32]
         lib.rtx_render_rays.argtypes = [vp, i32, i32, u32]
+    if hasattr(lib, "rtx_update_instances"):
+        lib.rtx_update_instances.argtypes = [vp, vp, vp, i32]
+        lib.rtx_read_frame_state.argtypes = [vp, vp, vp, C.POINTER(i32), vp]
     for name in EXPORTS:
-        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS and not hasattr(lib, name):
+        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         if name not in ("rtx_last_error",):
@@ -293,6 +298,7 @@ class Renderer:
             raise RtxError(rc, "rtx_create")
         self._keep: List[np.ndarray] = []
         self.ray_view_count = 0          # ray views in the context's own buffer (set_rays)
+        self.frame_instance_count = 0    # instances of the frame last set (set_frame)
         self._rays_bound = None          # (device pointer, views) bound with bind_rays
         if upload:
             self.upload_scene(scene)
@@ -335,6 +341,7 @@ class Renderer:
         keep: List[np.ndarray] = []
         fill_frame(fr, sc, keep)
         self._chk(self.lib.rtx_set_frame(self.ctx, C.byref(fr)), "rtx_set_frame")
+        self.frame_instance_count = len(sc.instances)      # what the context now holds (read_frame_state sizes its arrays by it)
 
     def render_async(self, first_tile: int = 0, tile_stride: int = 1, tile_count: Optional[int] = None, count_work: bool = False,
                      simple_trace: bool = False, cull_dead_shadow_rays: bool = False, serial: bool = False, lane_trace: bool = False,
@@ -609,6 +616,45 @@ class Renderer:
             raise ValueError(f"rays must be on cuda:{dev} (this context's GPU), not {rays.device}")
         count = int(rays.shape[0])
         self._render_into(rgb, packed, 0, count, aovs, flags, lambda fl: (self.bind_rays(rays.data_ptr(), count), self.render_rays_async(0, count, **fl), self.bind_rays(None)), (rays,))
+
+    # ---- device-side scene update (include/rtx.h: rtx_update_instances / rtx_read_frame_state) ------------------------------------
+    def update_instances(self, positions, rotations, instance_count: Optional[int] = None):
+        """New poses of the frame's instances from DEVICE memory: positions (n, 3) and rotations (n, 4; quaternion x, y, z, w) as float32
+        torch tensors on this context's GPU, or raw device pointers with instance_count.  The instance records and a balanced TLAS are
+        rebuilt on the device, ordered on the context's stream (set_stream: torch's stream, if the tensors are written there); nothing is
+        read back.  The tensors are read when the work runs and must stay alive until then.  Returns at once."""
+        if hasattr(positions, "data_ptr") or hasattr(rotations, "data_ptr"):
+            import torch
+            for name, t, k in (("positions", positions, 3), ("rotations", rotations, 4)):
+                if not isinstance(t, torch.Tensor):
+                    raise TypeError(f"{name} must be a torch.Tensor (or both raw device pointers), not {type(t).__name__}")
+                if t.dtype != torch.float32:
+                    raise TypeError(f"{name} must be torch.float32, not {t.dtype}")
+                if t.dim() != 2 or t.shape[1] != k:
+                    raise ValueError(f"{name} must have shape (n, {k}), not {tuple(t.shape)}")
+                if not t.is_contiguous():
+                    raise ValueError(f"{name} must be contiguous")
+                if t.device.type != "cuda" or t.device.index != self.device:
+                    raise ValueError(f"{name} must be on cuda:{self.device} (this context's GPU), not {t.device}")
+            if positions.shape[0] != rotations.shape[0]:
+                raise ValueError(f"positions and rotations hold different numbers of instances ({positions.shape[0]} vs {rotations.shape[0]})")
+            if instance_count is None:
+                instance_count = int(positions.shape[0])
+            positions, rotations = positions.data_ptr(), rotations.data_ptr()
+        if instance_count is None:
+            raise ValueError("instance_count is needed with raw device pointers")
+        self._chk(self.lib.rtx_update_instances(self.ctx, int(positions) if positions else None, int(rotations) if rotations else None, int(instance_count)),
+                  "rtx_update_instances")
+
+    def read_frame_state(self):
+        """The frame state the kernels currently read (waits for the stream): (instances scene_io.INSTANCE (n,), tlas_nodes scene_io.BVH_NODE
+        in the reference layout, tlas_indices int32 (n,)) — after set_frame what was set, after update_instances what the device built."""
+        nc = C.c_int32()
+        self._chk(self.lib.rtx_read_frame_state(self.ctx, None, None, C.byref(nc), None), "rtx_read_frame_state")
+        n = self.frame_instance_count                      # the count of the frame that was set, whichever scene object it came from
+        inst = np.zeros(n, sio.INSTANCE); nodes = np.zeros(nc.value, sio.BVH_NODE); idx = np.zeros(n, np.int32)
+        self._chk(self.lib.rtx_read_frame_state(self.ctx, inst.ctypes.data, nodes.ctypes.data, C.byref(nc), idx.ctypes.data), "rtx_read_frame_state")
+        return inst, nodes, idx
 
     def enable_timing(self, on: bool = True):
         self._chk(self.lib.rtx_enable_kernel_timing(self.ctx, 1 if on else 0), "rtx_enable_kernel_timing")

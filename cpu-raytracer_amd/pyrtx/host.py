@@ -20,7 +20,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "..", "host", "librtx_host.so")
 EXPORTS = ["rtxh_camera_basis", "rtxh_camera_update", "rtxh_quaternion_axis_angle", "rtxh_scene_dynamic_animate", "rtxh_scene_update", "rtxh_instance_update", "rtxh_plane_update", "rtxh_tlas_create", "rtxh_tlas_destroy",
            "rtxh_tlas_build", "rtxh_blas_build", "rtxh_blas_build_reference_bvh", "rtxh_blas_build_reference_sbvh", "rtxh_texture_mips", "rtxh_texture_load", "rtxh_texture_free", "rtxh_sky_load", "rtxh_image_load", "rtxh_image_free", "rtxh_image_save_png", "rtxh_atrium_generate", "rtxh_mesh_free",
-           "rtxh_obj_load", "rtxh_obj_free", "rtxh_mtl_load", "rtxh_bvh_cache_load", "rtxh_bvh_cache_save", "rtxh_bvh_cache_free"]
+           "rtxh_obj_load", "rtxh_obj_free", "rtxh_mtl_load", "rtxh_bvh_cache_load", "rtxh_bvh_cache_save", "rtxh_bvh_cache_free",
+           "rtxh_tlas_build_balanced", "rtxh_scene_update_balanced", "rtxh_tlas_balanced_node_count", "rtxh_tlas_balanced_inner_depth"]
 
 PI = np.float32(3.14159265359)          # Util.h:8
 
@@ -79,6 +80,10 @@ def lib():
         l.rtxh_texture_mips.argtypes = [vp, i32, i32, C.POINTER(RtxTextureDesc), C.POINTER(C.c_int64)]
         l.rtxh_atrium_generate.argtypes = [C.c_uint32, i32, C.POINTER(RtxhMesh)]
         l.rtxh_mesh_free.argtypes = [C.POINTER(RtxhMesh)]
+        l.rtxh_tlas_build_balanced.argtypes = [i32, vp, vp, vp, vp, C.POINTER(i32)]
+        l.rtxh_scene_update_balanced.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32)]
+        l.rtxh_tlas_balanced_node_count.argtypes = [i32]
+        l.rtxh_tlas_balanced_inner_depth.argtypes = [i32]
         for n in EXPORTS:
             getattr(l, n).restype = C.c_int
         _lib = l
@@ -158,6 +163,52 @@ class Tlas:
             lib().rtxh_tlas_destroy(self.h)
         except Exception:
             pass
+
+
+def tlas_balanced_node_count(n: int) -> int:
+    """Node slots of the balanced TLAS of n instances (2 << ceil(log2 n), holes and index 1 included); 0 outside 1 .. 65 536."""
+    return int(lib().rtxh_tlas_balanced_node_count(n))
+
+
+def tlas_balanced_inner_depth(n: int) -> int:
+    """Depth of the deepest inner node of the balanced TLAS of n instances: ceil(log2 n) - 1, -1 for one instance."""
+    return int(lib().rtxh_tlas_balanced_inner_depth(n))
+
+
+def tlas_build_balanced(positions: np.ndarray, aabbs: np.ndarray):
+    """rtxh_tlas_build_balanced: the TLAS rtx_update_instances builds on the device, from the same code.  positions (n, 3), aabbs (n, 6)
+    -> (BVH_NODE array of tlas_balanced_node_count(n) slots, int32 indices (n,))."""
+    p = _f32(positions).reshape(-1, 3)
+    n = p.shape[0]
+    a = _f32(aabbs).reshape(n, 6)
+    slots = tlas_balanced_node_count(n)
+    if slots == 0:
+        raise ValueError(f"1 .. 65536 instances, not {n}")
+    nodes = np.zeros(slots, sio.BVH_NODE)
+    idx = np.zeros(n, np.int32)
+    nc = C.c_int32()
+    rc = lib().rtxh_tlas_build_balanced(n, p.ctypes.data, a.ctypes.data, nodes.ctypes.data, idx.ctypes.data, C.byref(nc))
+    if rc:
+        raise ValueError(f"rtxh_tlas_build_balanced failed with status {rc}")
+    return nodes[:nc.value], idx
+
+
+def scene_update_balanced(scene: sio.Scene, positions, rotations):
+    """rtxh_scene_update_balanced: what Renderer.update_instances(positions, rotations) leaves on the device for `scene` (its BLAS set and the
+    blas_id of its instances) -> (instances, tlas_nodes, tlas_indices)."""
+    n = len(scene.instances)
+    p, r = _f32(positions).reshape(n, 3), _f32(rotations).reshape(n, 4)
+    blas_ids = np.ascontiguousarray(scene.instances["blas_id"], np.int32)
+    roots = np.concatenate([np.concatenate([b.nodes[0]["aabb_min"], b.nodes[0]["aabb_max"]]) for b in scene.blas]).astype(np.float32)
+    inst = np.zeros(n, sio.INSTANCE)
+    nodes = np.zeros(tlas_balanced_node_count(n), sio.BVH_NODE)
+    idx = np.zeros(n, np.int32)
+    nc = C.c_int32()
+    rc = lib().rtxh_scene_update_balanced(n, p.ctypes.data, r.ctypes.data, blas_ids.ctypes.data, roots.ctypes.data, inst.ctypes.data,
+                                          nodes.ctypes.data, idx.ctypes.data, C.byref(nc))
+    if rc:
+        raise ValueError(f"rtxh_scene_update_balanced failed with status {rc}")
+    return inst, nodes[:nc.value], idx
 
 
 class DynamicScene:

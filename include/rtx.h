@@ -427,6 +427,32 @@ int rtx_bind_aovs(rtx_ctx * ctx, uint32_t channels, const rtx_aov_buffers * devi
  * whose own buffer does not hold the range (never bound, or bound for fewer pixels than rendered).                                  */
 int rtx_read_aovs(rtx_ctx * ctx, int32_t first_view, int32_t view_count, const rtx_aov_buffers * host);
 
+/* ---- device-side scene update -----------------------------------------------------------------------------------------------------------
+ * The tail of Scene::update (Scene.cpp:166-170: Mesh::update for every instance, then the TLAS rebuild) on the device, for callers whose
+ * object poses already live there (a simulation step, a learning loop): no copy to the host, no wait.
+ * Poses of the instances of the current frame, from DEVICE memory: positions n x 3 f32, rotations n x 4 f32 (quaternion x, y, z, w —
+ * Transform::position / rotation; any 4-byte aligned address).  Recomputes every rtx_instance (Mesh::update, Mesh.cpp:9-15: bit-identical to
+ * rtxh_instance_update's records), the instances' world AABBs (AABB::transform, AABB.cpp:55-73) and a TLAS over them, on the context's
+ * stream (rtx_set_stream: the caller's).  The TLAS is this project's own balanced tree, not the reference's SAH tree: rtxh_tlas_build_balanced
+ * (include/rtx_host.h) documents it and builds the same bytes on the host.  blas_id of each instance, camera, ambient, spheres, planes and
+ * lights stay as the last rtx_set_frame left them.  Does not wait for the device and reads nothing back: work already queued keeps the
+ * state it was queued with, the next render call (any entry point, any flag) renders the updated scene; a later rtx_set_frame replaces the
+ * state again.  The pose buffers are read when the work runs and must stay valid until then.
+ * Any float values are legal poses, NaN and infinities included: such an instance may become invisible, the tree stays valid.
+ * Checked in this order, the first that applies is returned and nothing changes: RTX_ERR_INVALID_ARG for a null or misaligned pointer or
+ * instance_count < 1; RTX_ERR_LIMIT above RTX_UPDATE_MAX_INSTANCES; RTX_ERR_STATE before rtx_set_frame; RTX_ERR_INVALID_ARG for an
+ * instance_count that is not the frame's; RTX_ERR_LIMIT when the tree of that many instances (deepest inner node at depth
+ * ceil(log2 n) - 1) needs more than rtx_config.stack_size entries — the rule rtx_render_tiles applies to every BVH.  Heat-map contexts are supported.  Out of scope: the rtx_group_* path (every rank would
+ * have to make the same call), world matrices or scale as input, spheres / planes / lights from device memory, BLAS refit.              */
+#define RTX_UPDATE_MAX_INSTANCES 65536
+int rtx_update_instances(rtx_ctx * ctx, const void * positions_dev, const void * rotations_dev, int32_t instance_count);
+/* The frame state the kernels currently read, to host (waits for the stream): rtx_instance records (instance_count of the frame), TLAS
+ * nodes in the reference layout (rtx_bvh_node, root 0, index 1 unused; *tlas_node_count entries — call once with NULL arrays to learn the
+ * count), TLAS indices (instance_count entries).  Any pointer may be NULL.  Handing the three arrays to rtx_set_frame of another context
+ * gives that context the same frame.  RTX_ERR_STATE before rtx_set_frame.                                                                 */
+int rtx_read_frame_state(rtx_ctx * ctx, rtx_instance * instances, rtx_bvh_node * tlas_nodes, int32_t * tlas_node_count,
+                         int32_t * tlas_indices);
+
 /* Timing of every kernel launched since rtx_enable_kernel_timing(ctx, 1),
  * measured with HIP events on the stream the kernels are launched on.
  * names/ms hold up to `capacity` entries; *count receives the number of

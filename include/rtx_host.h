@@ -17,6 +17,8 @@
  *   rtxh_tlas_*              TopLevelBVH::init / build_bvh                TopLevelBVH.cpp:5-45
  *                            (BVHBuilders::build_bvh<Mesh> BVHBuilders.h:8-46,
  *                             BVHPartitions::{calculate_bounds,partition_sah,split_indices})
+ *   rtxh_tlas_build_balanced this repo's OWN TLAS builder: the tree rtx_update_instances builds on the device, from the same
+ *                            code (csrc/rtx_update_math.h); rtxh_scene_update_balanced = rtx_update_instances on the host
  *   rtxh_blas_build          a BottomLevelBVH for a triangle soup: this repo's OWN binned-SAH
  *                            builder (not the reference's SBVH), output in the
  *                            reference's node convention + flattened leaf order
@@ -63,6 +65,26 @@ int rtxh_tlas_destroy(rtxh_tlas * t);
  * 2*n entries, indices_out n entries; *node_count_out receives TopLevelBVH::node_count.          */
 int rtxh_tlas_build(rtxh_tlas * t, const float * positions, const float * aabbs,
                     rtx_bvh_node * nodes_out, int32_t * indices_out, int32_t * node_count_out);
+
+/* The balanced TLAS of rtx_update_instances (include/rtx.h), built on the host by the code the kernels run (csrc/rtx_update_math.h): the
+ * instances sorted by (box finite?, 30-bit Morton code of their position over the bounds of all finite positions, instance index) — an
+ * instance whose box has a NaN or infinite component sorts first, so that a NaN inner box never covers a finite instance —, an implicit heap over
+ * the sorted range — node (d, j) covers sorted slots [j*n >> d, (j+1)*n >> d), is a leaf when that is one slot and is stored at index
+ * 2^d + j (root at 0, index 1 unused, children adjacent) — and boxes bottom-up: a leaf's box is its instance's after AABB::fix_if_needed
+ * (AABB.h:26-32), an inner node's the union of its children's STORED boxes, then fix_if_needed.  `count` of an inner node carries the axis
+ * (1..3, bits 30-31) on which the right child's box centre lies furthest beyond the left child's.  Shape, node count and depth depend on n
+ * alone; slots that are no node are zero.  Defined for every float input: the indices are always a permutation, every range lies inside the
+ * arrays.  O(n log n).  positions n*3, aabbs n*6 (min, max); nodes_out holds rtxh_tlas_balanced_node_count(n) entries, indices_out n.
+ * 1 <= n <= 65 536 (RTX_ERR_LIMIT above).                                                                                                  */
+int32_t rtxh_tlas_balanced_node_count(int32_t instance_count);     /* 2 << ceil(log2 n); 0 for n outside the supported range */
+int32_t rtxh_tlas_balanced_inner_depth(int32_t instance_count);    /* depth of the deepest inner node (-1 for one instance): ceil(log2 n) - 1 */
+int rtxh_tlas_build_balanced(int32_t instance_count, const float * positions, const float * aabbs,
+                             rtx_bvh_node * nodes_out, int32_t * indices_out, int32_t * node_count_out);
+/* rtxh_scene_update with that builder and the kernels' restatement of Mesh::update: what rtx_update_instances leaves on the device.  The
+ * instance records equal rtxh_scene_update's bit for bit.                                                                                  */
+int rtxh_scene_update_balanced(int32_t instance_count, const float * positions, const float * rotations, const int32_t * blas_ids,
+                               const float * blas_root_aabbs, rtx_instance * instances_out, rtx_bvh_node * tlas_nodes_out,
+                               int32_t * tlas_indices_out, int32_t * tlas_node_count_out);
 
 /* Triangle soup -> flattened BLAS.  positions: n*9 floats (p0,p1,p2).  nodes_out must hold 2*n
  * entries, order_out n entries: order_out[k] = source triangle stored at flattened slot k.       */
