@@ -29,6 +29,7 @@
 #include "rtx_packet.h"
 #include "rtx_present.h"
 #include "rtx_update.h"
+#include "rtx_refit.h"
 #include <rocprim/device/device_radix_sort.hpp>      // rtx_update_instances, scenes beyond one workgroup: header-only, part of ROCm
 
 #define SLOT_BUDGET (48ll * 1000 * 1000)      // ray slots per batch of tiles (see plan_batch)
@@ -99,6 +100,11 @@ struct rtx_ctx {
     // (AABBs, bounds, keys), grown only; the DevScene pointers are switched to it, the rest of the frame stays in d_frame.  d_upd_sort = rocPRIM's
     // temporary storage and the unsorted keys (multi-launch path), grown only
     DevBuf d_upd, d_upd_sort; int upd_cap = 0;
+    // rtx_bind_blas_vertices / rtx_refit_blas, per BLAS id: the record-slot -> node maps of the 4-wide layouts as rtx_upload_blas laid them out
+    // (empty: binary walk), and once bound the kernel arguments of a refit — the plan's device block belongs to blas_allocs[id], so uploading
+    // the id again releases it with the arrays
+    struct BlasRefit { std::vector<int32_t> map4, map4c; bool bound = false; int32_t vertex_count = 0; DevRefit dev; float * planes[3] = { nullptr, nullptr, nullptr }; void * sort_tmp = nullptr; size_t sort_bytes = 0; };
+    std::vector<BlasRefit> refit;
     // rtx_set_views: the cameras of a batch of views (device array, grown only, filled by a stream-ordered copy from a ring of pinned
     // staging buffers like the frame block) and the view framebuffer (view_fb_cap views, allocated on first use, grown only) or the
     // caller's buffers of ext_vcap views (rtx_bind_view_framebuffer)
@@ -193,7 +199,8 @@ static void convert_nodes_pk(const rtx_bvh_node * nodes, int n, std::vector<floa
 // at this node — then smallest stack need first, which bounds the occupancy by the tree's Strahler-like number.  *stack_need = the bound.
 //   record (128 B, at byte offset 64 * left-child index of j): 4 x { min.x, min.y, max.x, max.y, min.z, max.z, first, leaf count };
 //   first = left-child index of the slot node (inner, count 0) or first triangle (leaf); unused slots hold a point box, which never passes.
-static bool build_nodes_pk4(const rtx_bvh_node * nodes, int n, int tri_count, std::vector<float4> & out, int * stack_need, int order_mode) {
+// slot_map (may be null): for every record slot (index 2 * left + s of 2n + 4) the node whose box it carries, -1 for an unused slot (rtx_refit.h)
+static bool build_nodes_pk4(const rtx_bvh_node * nodes, int n, int tri_count, std::vector<float4> & out, int * stack_need, int order_mode, std::vector<int32_t> * slot_map = nullptr) {
     if (n >= (1 << 24) || tri_count >= (1 << 24)) return false;
     auto inside = [&](int c, int p) {
         for (int a = 0; a < 3; a++) if (!(nodes[c].aabb_min[a] >= nodes[p].aabb_min[a] && nodes[c].aabb_max[a] <= nodes[p].aabb_max[a])) return false;
@@ -211,6 +218,7 @@ static bool build_nodes_pk4(const rtx_bvh_node * nodes, int n, int tri_count, st
         order.push_back(i); stack.push_back(f); stack.push_back(f + 1);
     }
     out.assign((size_t)4 * (n > 0 ? n : 1) + 8, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    if (slot_map) slot_map->assign((size_t)2 * (n > 0 ? n : 1) + 4, -1);
     std::vector<int> need((size_t)n, 0);                            // packet-stack entries the walk of a subtree can have pending
     // visiting order = slot order.  For a shadow ray any hit ends the walk, so the likeliest occluder should come first: largest box first
     // (merged launch 0.652 -> 0.627 ms; by triangle count, density or an RTSAH-style area^2 / cost key: 0.635-0.70).  Where that order would
@@ -236,6 +244,7 @@ static bool build_nodes_pk4(const rtx_bvh_node * nodes, int n, int tri_count, st
             memcpy(&f, &c.left_or_first, 4); memcpy(&cn, &cnt, 4);
             rec[2 * s]     = make_float4(c.aabb_min[0], c.aabb_min[1], c.aabb_max[0], c.aabb_max[1]);
             rec[2 * s + 1] = make_float4(c.aabb_min[2], c.aabb_max[2], f, cn);
+            if (slot_map) (*slot_map)[(size_t)2 * l + s] = slot[s];
         }
     }
     *stack_need = need[0];
@@ -254,7 +263,7 @@ static bool build_nodes_pk4(const rtx_bvh_node * nodes, int n, int tri_count, st
 //   record (128 B, at byte offset 64 * left-child index of j): 4 x { (min.x, min.y, max.x, max.y) (min.z, max.z, first, meta) },
 //   meta = leaf count (< 16) | axis of the slot's PARENT (slots 0 and 2; 0: the parent is a leaf, i.e. the slot itself) << 26 | axis of the slot node << 30;
 //   unused slots hold a point box, which never passes.  *stack_need = pending entries a lane's walk can have (bound over all visiting orders).
-static bool build_nodes_pk4c(const rtx_bvh_node * nodes, int n, int tri_count, std::vector<float4> & out, int * stack_need) {
+static bool build_nodes_pk4c(const rtx_bvh_node * nodes, int n, int tri_count, std::vector<float4> & out, int * stack_need, std::vector<int32_t> * slot_map = nullptr) {
     if (n >= (1 << 24) || tri_count >= (1 << 24)) return false;
     auto inside = [&](int c, int p) {
         for (int a = 0; a < 3; a++) if (!(nodes[c].aabb_min[a] >= nodes[p].aabb_min[a] && nodes[c].aabb_max[a] <= nodes[p].aabb_max[a])) return false;
@@ -270,6 +279,7 @@ static bool build_nodes_pk4c(const rtx_bvh_node * nodes, int n, int tri_count, s
         order.push_back(i); stack.push_back(f); stack.push_back(f + 1);
     }
     out.assign((size_t)4 * (n > 0 ? n : 1) + 8, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    if (slot_map) slot_map->assign((size_t)2 * (n > 0 ? n : 1) + 4, -1);
     std::vector<int> need((size_t)n, 0);
     for (size_t k = order.size(); k-- > 0; ) {                      // children before parents
         const int j = order[k], l = nodes[j].left_or_first;
@@ -286,6 +296,7 @@ static bool build_nodes_pk4c(const rtx_bvh_node * nodes, int n, int tri_count, s
                 float f, m; memcpy(&f, &sn.left_or_first, 4); memcpy(&m, &meta, 4);
                 rec[2 * (2 * g + t)]     = make_float4(sn.aabb_min[0], sn.aabb_min[1], sn.aabb_max[0], sn.aabb_max[1]);      // the packet kernels' slot layout: the slab test runs in packed fp32
                 rec[2 * (2 * g + t) + 1] = make_float4(sn.aabb_min[2], sn.aabb_max[2], f, m);
+                if (slot_map) (*slot_map)[(size_t)2 * l + 2 * g + t] = si;
                 nd = std::max(nd, need[si]); ns++;
             }
         }
@@ -491,10 +502,13 @@ extern "C" int rtx_upload_blas(rtx_ctx * c, int32_t blas_id, const rtx_bvh_node 
         th[RTX_TRI_STRIDE * (size_t)i + 2] = make_float4(tri_hot[i].position_edge_2[0], tri_hot[i].position_edge_2[1], tri_hot[i].position_edge_2[2], 0.0f);
     }
     std::vector<float4> ndp; convert_nodes_pk(nodes, node_count, ndp);
+    if (c->refit.size() <= (size_t)blas_id) c->refit.resize(blas_id + 1);
+    c->refit[blas_id] = rtx_ctx::BlasRefit();                      // uploading an id drops its vertex binding (the plan's block was freed above)
     std::vector<float4> nd4; int need4 = 0;
-    const bool wide = !c->knobs.no_wide && build_nodes_pk4(nodes, node_count, triangle_count, nd4, &need4, c->knobs.pk4_order) && need4 <= RTX_PK4_MAX_NEED;
+    std::vector<int32_t> map4, map4c;
+    const bool wide = !c->knobs.no_wide && build_nodes_pk4(nodes, node_count, triangle_count, nd4, &need4, c->knobs.pk4_order, &map4) && need4 <= RTX_PK4_MAX_NEED;
     std::vector<float4> nd4c; int need4c = 0;
-    const bool wide_closest = !c->knobs.no_wide_closest && build_nodes_pk4c(nodes, node_count, triangle_count, nd4c, &need4c) && need4c <= RTX_MAX_STACK - 2;
+    const bool wide_closest = !c->knobs.no_wide_closest && build_nodes_pk4c(nodes, node_count, triangle_count, nd4c, &need4c, &map4c) && need4c <= RTX_MAX_STACK - 2;
     // the distinct box-plane coordinates per axis, ascending: a ray with a zero direction component can only produce a NaN in a slab test
     // (0 * inf) if its origin lies exactly on one of them (pk_nan_possible, rtx_packet.h)
     std::vector<float> planes[3];
@@ -531,6 +545,8 @@ extern "C" int rtx_upload_blas(rtx_ctx * c, int32_t blas_id, const rtx_bvh_node 
     B.pk4_nodes = (const float4 *)dn4; B.pk4c_nodes = (const float4 *)dn4c;
     for (int a = 0; a < 3; a++) { B.planes[a] = (const float *)dpl[a]; B.plane_count[a] = (int32_t)planes[a].size(); }
     B.node_count = node_count; B.tri_count = triangle_count; B.material_offset = material_offset; B.pk4_need = wide ? need4 : -1; B.pk4c_need = wide_closest ? need4c : -1;
+    if (wide) c->refit[blas_id].map4.swap(map4);
+    if (wide_closest) c->refit[blas_id].map4c.swap(map4c);
     return upload(c, c->d_blas, c->h_blas.data(), c->h_blas.size() * sizeof(DevBlas));
 }
 
@@ -879,6 +895,137 @@ extern "C" int rtx_read_frame_state(rtx_ctx * c, rtx_instance * instances, rtx_b
             memcpy(&tlas_nodes[i].left_or_first, &a.w, 4); memcpy(&tlas_nodes[i].count, &b.w, 4);
         }
     }
+    return RTX_OK;
+}
+
+// ---- device-side mesh refit (include/rtx.h: rtx_bind_blas_vertices / rtx_refit_blas / rtx_read_blas; kernels in rtx_refit.h) -----------
+// Everything the host decides from a BLAS before a launch (blas_inner_depth, blas_packet_ok, pk4_need / pk4c_need, the packet-stack rule,
+// the kernel choice per level) depends on its topology, which a refit keeps: so a refit is queued on the context's stream like
+// rtx_update_instances and nothing is read back.  The arrays are written in place and the DevBlas table is not touched after the bind, so
+// work queued before reads the old mesh, the next render call the new one, and a captured graph stays valid.
+static int refit_launch_finish(rtx_ctx * c, rtx_ctx::BlasRefit & R) {
+    const DevRefit & r = R.dev;
+    const int n = r.node_count;
+    launch_timed(c, "k_refit_finish", c->stream, [&] { hipLaunchKernelGGL(k_refit_finish, dim3((2 * n + 4 + RTX_REFIT_BLOCK - 1) / RTX_REFIT_BLOCK), dim3(RTX_REFIT_BLOCK), 0, c->stream, r); });
+    hipError_t se = hipSuccess;
+    launch_timed(c, "refit_plane_sort", c->stream, [&] {
+        for (int a = 0; a < 3 && se == hipSuccess; a++) {
+            size_t bytes = R.sort_bytes;
+            se = rocprim::radix_sort_keys(R.sort_tmp, bytes, (const float *)r.plane_keys[a], R.planes[a], (unsigned int)(2 * n), 0u, 32u, c->stream);
+        }
+    });
+    if (se != hipSuccess) { hipGetLastError(); c->err = std::string("rocprim::radix_sort_keys: ") + hipGetErrorString(se); return RTX_ERR_HIP; }
+    HIP_OK(c, hipGetLastError());
+    return RTX_OK;
+}
+
+extern "C" int rtx_bind_blas_vertices(rtx_ctx * c, int32_t blas_id, const int32_t * slot_vertices, int32_t vertex_count) {
+    if (!c) return RTX_ERR_INVALID_ARG;
+    if (!slot_vertices || blas_id < 0 || blas_id >= (1 << 20) || vertex_count < 1) { c->err = "rtx_bind_blas_vertices: null index table, bad id or no vertices"; return RTX_ERR_INVALID_ARG; }
+    if ((size_t)blas_id >= c->h_blas.size() || !c->h_blas[blas_id].nodes) { c->err = "rtx_bind_blas_vertices: no BLAS uploaded under that id"; return RTX_ERR_STATE; }
+    DevBlas & B = c->h_blas[blas_id];
+    const int n = B.node_count, T = B.tri_count;
+    for (int64_t k = 0; k < 3 * (int64_t)T; k++) if (slot_vertices[k] < 0 || slot_vertices[k] >= vertex_count) {
+        c->err = "rtx_bind_blas_vertices: vertex index outside [0, vertex_count)"; return RTX_ERR_INVALID_ARG; }
+    hipSetDevice(c->cfg.device);
+    HIP_OK(c, hipStreamSynchronize(c->stream));                    // frames in flight read the tables this call replaces
+    rtx_ctx::BlasRefit & R = c->refit[blas_id];
+    if (R.bound) {                                                  // same arrays, same topology: only the index table changes
+        if (T) HIP_OK(c, hipMemcpy((void *)R.dev.slot_vertices, slot_vertices, (size_t)T * 12, hipMemcpyHostToDevice));
+        R.vertex_count = vertex_count;
+        return RTX_OK;
+    }
+    // the topology as uploaded: the lane layout's words (a refit never writes them)
+    std::vector<float4> nd((size_t)2 * n);
+    HIP_OK(c, hipMemcpy(nd.data(), B.nodes, nd.size() * 16, hipMemcpyDeviceToHost));
+    std::vector<int32_t> parent((size_t)n, RTX_REFIT_UNREACHABLE), stack(1, 0);
+    parent[0] = -1;
+    while (!stack.empty()) {                                        // rtx_upload_blas validated the tree: in range, no node reachable twice
+        const int i = stack.back(); stack.pop_back();
+        int32_t f, cw; memcpy(&f, &nd[2 * (size_t)i].w, 4); memcpy(&cw, &nd[2 * (size_t)i + 1].w, 4);
+        if ((cw & 0x3fffffff) > 0) continue;
+        parent[f] = i; parent[f + 1] = i; stack.push_back(f); stack.push_back(f + 1);
+    }
+    size_t sort_bytes = 0;
+    if (rocprim::radix_sort_keys(nullptr, sort_bytes, (const float *)nullptr, (float *)nullptr, (unsigned int)(2 * n), 0u, 32u, c->stream) != hipSuccess) {
+        hipGetLastError(); c->err = "rocprim::radix_sort_keys size query failed"; return RTX_ERR_HIP; }
+    // [slot vertices][parents][arrival counters][pk4 slot map][pk4c slot map][3 x plane keys][3 x planes][sort storage], every part 256-byte aligned
+    const size_t slots = (size_t)2 * n + 4, pl = (size_t)2 * n * 4;
+    const size_t len[12] = { (size_t)(T > 0 ? T : 1) * 12, (size_t)n * 4, (size_t)n * 4, R.map4.empty() ? 0 : slots * 4, R.map4c.empty() ? 0 : slots * 4, pl, pl, pl, pl, pl, pl, sort_bytes };
+    size_t off[12], total = 0;
+    for (int k = 0; k < 12; k++) { off[k] = total; total += (len[k] + 255) & ~(size_t)255; }
+    void * block = nullptr;
+    { hipError_t e = hipMalloc(&block, total); if (e != hipSuccess) { c->err = std::string("hipMalloc: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP; } }
+    c->blas_allocs[blas_id].push_back(block);
+    char * const bb = (char *)block;
+    if (T) HIP_OK(c, hipMemcpy(bb + off[0], slot_vertices, (size_t)T * 12, hipMemcpyHostToDevice));
+    HIP_OK(c, hipMemcpy(bb + off[1], parent.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    HIP_OK(c, hipMemset(bb + off[2], 0, (size_t)n * 4));
+    if (!R.map4.empty()) HIP_OK(c, hipMemcpy(bb + off[3], R.map4.data(), slots * 4, hipMemcpyHostToDevice));
+    if (!R.map4c.empty()) HIP_OK(c, hipMemcpy(bb + off[4], R.map4c.data(), slots * 4, hipMemcpyHostToDevice));
+    DevRefit & r = R.dev;
+    memset(&r, 0, sizeof(r));
+    r.slot_vertices = (const int32_t *)(bb + off[0]); r.parent = (const int32_t *)(bb + off[1]); r.arrivals = (uint32_t *)(bb + off[2]);
+    r.map4 = R.map4.empty() ? nullptr : (const int32_t *)(bb + off[3]); r.map4c = R.map4c.empty() ? nullptr : (const int32_t *)(bb + off[4]);
+    for (int a = 0; a < 3; a++) r.plane_keys[a] = (float *)(bb + off[5 + a]);
+    r.nodes = (float4 *)B.nodes; r.pk_nodes = (float4 *)B.pk_nodes; r.pk4_nodes = (float4 *)B.pk4_nodes; r.pk4c_nodes = (float4 *)B.pk4c_nodes;
+    r.tri_hot = (float4 *)B.tri_hot; r.tri_cold = (float4 *)B.tri_cold;
+    r.node_count = n; r.tri_count = T;
+    R.sort_tmp = bb + off[11]; R.sort_bytes = sort_bytes;
+    // the plane lists move into buffers of a fixed 2 * node_count floats, filled from the boxes the arrays hold now by the pass a refit ends with
+    // (which also rewrites the packet and wide boxes with the values they already have): duplicates and the planes of unreachable slots only
+    // send a ray to the reference-form walker (plane_member is a lower-bound search)
+    for (int a = 0; a < 3; a++) { R.planes[a] = (float *)(bb + off[8 + a]); B.planes[a] = R.planes[a]; B.plane_count[a] = 2 * n; }
+    if (int rc = refit_launch_finish(c, R)) return rc;
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    R.bound = true; R.vertex_count = vertex_count;
+    return upload(c, c->d_blas, c->h_blas.data(), c->h_blas.size() * sizeof(DevBlas));
+}
+
+extern "C" int rtx_refit_blas(rtx_ctx * c, int32_t blas_id, const void * positions_dev, const void * normals_dev, int32_t vertex_count) {
+    if (!c) return RTX_ERR_INVALID_ARG;
+    if (!positions_dev || ((uintptr_t)positions_dev & 3) || ((uintptr_t)normals_dev & 3)) { c->err = "rtx_refit_blas: null or misaligned vertex pointer"; return RTX_ERR_INVALID_ARG; }
+    if (blas_id < 0 || (size_t)blas_id >= c->h_blas.size() || !c->h_blas[blas_id].nodes || !c->refit[blas_id].bound) {
+        c->err = "rtx_refit_blas: no BLAS uploaded under that id, or no vertices bound to it (rtx_bind_blas_vertices)"; return RTX_ERR_STATE; }
+    rtx_ctx::BlasRefit & R = c->refit[blas_id];
+    if (vertex_count != R.vertex_count) { c->err = "rtx_refit_blas: vertex_count differs from the bound one"; return RTX_ERR_INVALID_ARG; }
+    hipSetDevice(c->cfg.device);
+    DevRefit & r = R.dev;
+    r.positions = (const float *)positions_dev; r.normals = (const float *)normals_dev;
+    const int n = r.node_count, T = r.tri_count;
+    if (T) launch_timed(c, "k_refit_triangles", c->stream, [&] { hipLaunchKernelGGL(k_refit_triangles, dim3((T + RTX_REFIT_BLOCK - 1) / RTX_REFIT_BLOCK), dim3(RTX_REFIT_BLOCK), 0, c->stream, r); });
+    launch_timed(c, "k_refit_climb", c->stream, [&] { hipLaunchKernelGGL(k_refit_climb, dim3((n + RTX_REFIT_BLOCK - 1) / RTX_REFIT_BLOCK), dim3(RTX_REFIT_BLOCK), 0, c->stream, r); });
+    return refit_launch_finish(c, R);
+}
+
+extern "C" int rtx_read_blas(rtx_ctx * c, int32_t blas_id, rtx_bvh_node * nodes, rtx_triangle_hot * hot, rtx_triangle_cold * cold) {
+    if (!c) return RTX_ERR_INVALID_ARG;
+    if (blas_id < 0 || blas_id >= (1 << 20)) { c->err = "rtx_read_blas: bad id"; return RTX_ERR_INVALID_ARG; }
+    if ((size_t)blas_id >= c->h_blas.size() || !c->h_blas[blas_id].nodes) { c->err = "rtx_read_blas: no BLAS uploaded under that id"; return RTX_ERR_STATE; }
+    hipSetDevice(c->cfg.device);
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    const DevBlas & B = c->h_blas[blas_id];
+    if (nodes) {                                                    // the lane layout back into the reference's (convert_nodes inverted)
+        std::vector<float4> nd((size_t)2 * B.node_count);
+        HIP_OK(c, hipMemcpy(nd.data(), B.nodes, nd.size() * 16, hipMemcpyDeviceToHost));
+        for (int i = 0; i < B.node_count; i++) {
+            const float4 a = nd[2 * (size_t)i], b = nd[2 * (size_t)i + 1];
+            nodes[i].aabb_min[0] = a.x; nodes[i].aabb_min[1] = a.y; nodes[i].aabb_min[2] = a.z;
+            nodes[i].aabb_max[0] = b.x; nodes[i].aabb_max[1] = b.y; nodes[i].aabb_max[2] = b.z;
+            memcpy(&nodes[i].left_or_first, &a.w, 4); memcpy(&nodes[i].count, &b.w, 4);
+        }
+    }
+    if (hot && B.tri_count) {
+        std::vector<float4> th((size_t)RTX_TRI_STRIDE * B.tri_count);
+        HIP_OK(c, hipMemcpy(th.data(), B.tri_hot, th.size() * 16, hipMemcpyDeviceToHost));
+        for (int i = 0; i < B.tri_count; i++) {
+            const float4 * t = &th[(size_t)RTX_TRI_STRIDE * i];
+            hot[i].position_0[0] = t[0].x; hot[i].position_0[1] = t[0].y; hot[i].position_0[2] = t[0].z;
+            hot[i].position_edge_1[0] = t[1].x; hot[i].position_edge_1[1] = t[1].y; hot[i].position_edge_1[2] = t[1].z;
+            hot[i].position_edge_2[0] = t[2].x; hot[i].position_edge_2[1] = t[2].y; hot[i].position_edge_2[2] = t[2].z;
+        }
+    }
+    if (cold && B.tri_count) HIP_OK(c, hipMemcpy(cold, B.tri_cold, (size_t)B.tri_count * sizeof(rtx_triangle_cold), hipMemcpyDeviceToHost));
     return RTX_OK;
 }
 

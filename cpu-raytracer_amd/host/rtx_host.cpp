@@ -6,6 +6,7 @@
 // left-to-right with plain mul/add (Vector3.h:33-43, Matrix4.h:31-68, Quaternion.h:128-133).
 #include "../../include/rtx_host.h"
 #include "../csrc/rtx_update_math.h"
+#include "../csrc/rtx_refit_math.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -812,5 +813,48 @@ extern "C" int rtxh_bvh_cache_free(rtxh_bvh_cache * c) {
     if (!c) return RTX_ERR_INVALID_ARG;
     free(c->hot); free(c->cold); free(c->nodes); free(c->indices);
     memset(c, 0, sizeof(*c));
+    return RTX_OK;
+}
+
+// ---- rtx_refit_blas on the host: csrc/rtx_refit_math.h, the code the kernels run, driven sequentially -----------------------------------
+extern "C" int rtxh_blas_refit(rtx_bvh_node * nodes, int32_t node_count, const int32_t * slot_vertices, int32_t triangle_count,
+                               const float * positions, const float * normals, int32_t vertex_count,
+                               rtx_triangle_hot * hot_out, rtx_triangle_cold * cold) {
+    if (!nodes || node_count < 1 || triangle_count < 0 || vertex_count < 0 || (triangle_count > 0 && (!slot_vertices || !positions || !hot_out))) return RTX_ERR_INVALID_ARG;
+    if (normals && triangle_count > 0 && !cold) return RTX_ERR_INVALID_ARG;
+    for (int64_t k = 0; k < 3 * (int64_t)triangle_count; k++) if (slot_vertices[k] < 0 || slot_vertices[k] >= vertex_count) return RTX_ERR_INVALID_ARG;
+    // the reachable nodes in pre-order; every leaf range inside the slots, every child pair inside the nodes, no node reachable twice
+    std::vector<int> order, stack(1, 0);
+    std::vector<unsigned char> seen((size_t)node_count, 0);
+    while (!stack.empty()) {
+        const int i = stack.back(); stack.pop_back();
+        if (seen[i]) return RTX_ERR_INVALID_ARG;
+        seen[i] = 1; order.push_back(i);
+        const int cnt = nodes[i].count & 0x3fffffff, f = nodes[i].left_or_first;
+        if (cnt > 0) { if (f < 0 || (int64_t)f + cnt > triangle_count) return RTX_ERR_INVALID_ARG; }
+        else { if (f < 0 || f + 1 >= node_count) return RTX_ERR_INVALID_ARG; stack.push_back(f); stack.push_back(f + 1); }
+    }
+    for (int k = 0; k < triangle_count; k++) {
+        const float * v0 = positions + 3 * (size_t)slot_vertices[3 * k], * v1 = positions + 3 * (size_t)slot_vertices[3 * k + 1], * v2 = positions + 3 * (size_t)slot_vertices[3 * k + 2];
+        memcpy(hot_out[k].position_0, v0, 12);
+        rtxr::edges(v0, v1, v2, hot_out[k].position_edge_1, hot_out[k].position_edge_2);
+        if (normals) {
+            const float * n0 = normals + 3 * (size_t)slot_vertices[3 * k], * n1 = normals + 3 * (size_t)slot_vertices[3 * k + 1], * n2 = normals + 3 * (size_t)slot_vertices[3 * k + 2];
+            memcpy(cold[k].normal_0, n0, 12);
+            rtxr::edges(n0, n1, n2, cold[k].normal_edge_1, cold[k].normal_edge_2);
+        }
+    }
+    auto load = [&](int i) { rtxu::Box b; memcpy(b.mn, nodes[i].aabb_min, 12); memcpy(b.mx, nodes[i].aabb_max, 12); return b; };
+    for (size_t o = order.size(); o-- > 0; ) {                      // children before parents
+        const int i = order[o], cnt = nodes[i].count & 0x3fffffff, f = nodes[i].left_or_first;
+        rtxu::Box b;
+        if (cnt > 0) {
+            b = rtxr::empty_box();
+            for (int k = f; k < f + cnt; k++)
+                rtxr::expand_box(b, rtxr::triangle_box(positions + 3 * (size_t)slot_vertices[3 * k], positions + 3 * (size_t)slot_vertices[3 * k + 1], positions + 3 * (size_t)slot_vertices[3 * k + 2]));
+            rtxr::finish_leaf(b);
+        } else b = rtxr::join_children(load(f), load(f + 1));
+        memcpy(nodes[i].aabb_min, b.mn, 12); memcpy(nodes[i].aabb_max, b.mx, 12);
+    }
     return RTX_OK;
 }

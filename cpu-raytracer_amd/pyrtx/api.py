@@ -24,13 +24,15 @@ EXPORTS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error", "rt
            "rtx_group_unique_id", "rtx_group_create", "rtx_group_render", "rtx_group_destroy", "rtx_group_attach", "rtx_group_create_local", "rtx_group_render_local",
            "rtx_group_layout", "rtx_group_slot_pixels", "rtx_debug_group_loopback", "rtx_debug_trace_rays", "rtx_debug_occluded", "rtx_debug_light_plot",
            "rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer", "rtx_bind_aovs", "rtx_read_aovs",
-           "rtx_set_rays", "rtx_bind_rays", "rtx_render_rays", "rtx_update_instances", "rtx_read_frame_state"]
+           "rtx_set_rays", "rtx_bind_rays", "rtx_render_rays", "rtx_update_instances", "rtx_read_frame_state",
+           "rtx_bind_blas_vertices", "rtx_refit_blas", "rtx_read_blas"]
 # newer than the A/B variants tools/ab.py may load (RTX_HIP_LIB = a library built from an older commit): bound when the library has them,
 # otherwise a call raises AttributeError (undefined symbol)
 VIEW_EXPORTS = ("rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer")
 AOV_EXPORTS = ("rtx_bind_aovs", "rtx_read_aovs")
 RAY_EXPORTS = ("rtx_set_rays", "rtx_bind_rays", "rtx_render_rays")
 UPDATE_EXPORTS = ("rtx_update_instances", "rtx_read_frame_state")
+REFIT_EXPORTS = ("rtx_bind_blas_vertices", "rtx_refit_blas", "rtx_read_blas")
 RTX_UPDATE_MAX_INSTANCES = 65536
 
 RTX_RENDER_COUNT_WORK = 1
@@ -115,8 +117,12 @@ def load_library(path: Optional[str] = None):
     if hasattr(lib, "rtx_update_instances"):
         lib.rtx_update_instances.argtypes = [vp, vp, vp, i32]
         lib.rtx_read_frame_state.argtypes = [vp, vp, vp, C.POINTER(i32), vp]
+    if hasattr(lib, "rtx_refit_blas"):
+        lib.rtx_bind_blas_vertices.argtypes = [vp, i32, vp, i32]
+        lib.rtx_refit_blas.argtypes = [vp, i32, vp, vp, i32]
+        lib.rtx_read_blas.argtypes = [vp, i32, vp, vp, vp]
     for name in EXPORTS:
-        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS and not hasattr(lib, name):
+        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         if name not in ("rtx_last_error",):
@@ -300,6 +306,7 @@ class Renderer:
         self.ray_view_count = 0          # ray views in the context's own buffer (set_rays)
         self.frame_instance_count = 0    # instances of the frame last set (set_frame)
         self._rays_bound = None          # (device pointer, views) bound with bind_rays
+        self._blas_shapes: List[Optional[tuple]] = []      # per uploaded BLAS id: (nodes, slots, material offset, source triangles) — read_blas sizes its arrays by it
         if upload:
             self.upload_scene(scene)
             self.set_frame(scene)
@@ -326,6 +333,8 @@ class Renderer:
             nodes = np.ascontiguousarray(b.nodes); hot = np.ascontiguousarray(b.tri_hot); cold = np.ascontiguousarray(b.tri_cold)
             self._chk(self.lib.rtx_upload_blas(self.ctx, i, nodes.ctypes.data, len(nodes), hot.ctypes.data, cold.ctypes.data,
                                                len(hot), b.material_offset), "rtx_upload_blas")
+            self._blas_shapes += [None] * (i + 1 - len(self._blas_shapes))
+            self._blas_shapes[i] = (len(nodes), len(hot), b.material_offset, b.source_triangle_count)
         mats = np.ascontiguousarray(sc.materials)
         self._chk(self.lib.rtx_upload_materials(self.ctx, mats.ctypes.data, len(mats)), "rtx_upload_materials")
         for i, t in enumerate(sc.textures):
@@ -655,6 +664,58 @@ class Renderer:
         inst = np.zeros(n, sio.INSTANCE); nodes = np.zeros(nc.value, sio.BVH_NODE); idx = np.zeros(n, np.int32)
         self._chk(self.lib.rtx_read_frame_state(self.ctx, inst.ctypes.data, nodes.ctypes.data, C.byref(nc), idx.ctypes.data), "rtx_read_frame_state")
         return inst, nodes, idx
+
+    # ---- device-side mesh refit (include/rtx.h: rtx_bind_blas_vertices / rtx_refit_blas / rtx_read_blas) ----------------------------
+    def bind_blas_vertices(self, blas_id: int, slot_vertices, vertex_count: int):
+        """Once per mesh: slot_vertices (m, 3) int32 host array, the vertex indices of every flattened slot of the uploaded BLAS
+        (host.slot_vertices), each in [0, vertex_count).  May allocate and wait."""
+        sv = np.ascontiguousarray(slot_vertices, np.int32)
+        if sv.ndim != 2 or sv.shape[1] != 3:
+            raise ValueError(f"slot_vertices must have shape (slots, 3), not {tuple(sv.shape)}")
+        if 0 <= blas_id < len(self._blas_shapes) and self._blas_shapes[blas_id] and sv.shape[0] != self._blas_shapes[blas_id][1]:
+            raise ValueError(f"slot_vertices holds {sv.shape[0]} slots, BLAS {blas_id} {self._blas_shapes[blas_id][1]}")
+        self._chk(self.lib.rtx_bind_blas_vertices(self.ctx, int(blas_id), sv.ctypes.data, int(vertex_count)), "rtx_bind_blas_vertices")
+
+    def refit_blas(self, blas_id: int, positions, normals=None, vertex_count: Optional[int] = None):
+        """New vertex positions (V, 3) — and normals (V, 3), or None: the normals stay — of a bound mesh from DEVICE memory: float32 torch
+        tensors on this context's GPU, or raw device pointers with vertex_count.  Triangles, boxes and plane lists of the BLAS are rewritten in
+        place, ordered on the context's stream; nothing is read back.  The tensors are read when the work runs and must stay alive until
+        then.  Returns at once.  The TLAS is not touched: follow with update_instances when the mesh's root box moves."""
+        if hasattr(positions, "data_ptr") or hasattr(normals, "data_ptr"):
+            import torch
+            for name, t in (("positions", positions), ("normals", normals)):
+                if t is None and name == "normals":
+                    continue
+                if not isinstance(t, torch.Tensor):
+                    raise TypeError(f"{name} must be a torch.Tensor (or raw device pointers), not {type(t).__name__}")
+                if t.dtype != torch.float32:
+                    raise TypeError(f"{name} must be torch.float32, not {t.dtype}")
+                if t.dim() != 2 or t.shape[1] != 3:
+                    raise ValueError(f"{name} must have shape (V, 3), not {tuple(t.shape)}")
+                if not t.is_contiguous():
+                    raise ValueError(f"{name} must be contiguous")
+                if t.device.type != "cuda" or t.device.index != self.device:
+                    raise ValueError(f"{name} must be on cuda:{self.device} (this context's GPU), not {t.device}")
+            if normals is not None and normals.shape[0] != positions.shape[0]:
+                raise ValueError(f"positions and normals hold different numbers of vertices ({positions.shape[0]} vs {normals.shape[0]})")
+            if vertex_count is None:
+                vertex_count = int(positions.shape[0])
+            positions, normals = positions.data_ptr(), (None if normals is None else normals.data_ptr())
+        if vertex_count is None:
+            raise ValueError("vertex_count is needed with raw device pointers")
+        self._chk(self.lib.rtx_refit_blas(self.ctx, int(blas_id), int(positions) if positions else None, int(normals) if normals else None, int(vertex_count)),
+                  "rtx_refit_blas")
+
+    def read_blas(self, blas_id: int) -> sio.Blas:
+        """The BLAS arrays the kernels currently read (waits for the stream): after upload what was uploaded, after refit_blas what the device
+        wrote."""
+        if not (0 <= blas_id < len(self._blas_shapes)) or not self._blas_shapes[blas_id]:
+            self._chk(self.lib.rtx_read_blas(self.ctx, int(blas_id), None, None, None), "rtx_read_blas")
+            raise ValueError(f"BLAS {blas_id} was not uploaded through this Renderer")
+        n, m, off, src = self._blas_shapes[blas_id]
+        nodes = np.zeros(n, sio.BVH_NODE); hot = np.zeros(m, sio.TRI_HOT); cold = np.zeros(m, sio.TRI_COLD)
+        self._chk(self.lib.rtx_read_blas(self.ctx, int(blas_id), nodes.ctypes.data, hot.ctypes.data, cold.ctypes.data), "rtx_read_blas")
+        return sio.Blas(nodes, hot, cold, off, src)
 
     def enable_timing(self, on: bool = True):
         self._chk(self.lib.rtx_enable_kernel_timing(self.ctx, 1 if on else 0), "rtx_enable_kernel_timing")

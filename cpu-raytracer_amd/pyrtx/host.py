@@ -21,7 +21,7 @@ LIB_PATH = os.path.join(_HERE, "..", "host", "librtx_host.so")
 EXPORTS = ["rtxh_camera_basis", "rtxh_camera_update", "rtxh_quaternion_axis_angle", "rtxh_scene_dynamic_animate", "rtxh_scene_update", "rtxh_instance_update", "rtxh_plane_update", "rtxh_tlas_create", "rtxh_tlas_destroy",
            "rtxh_tlas_build", "rtxh_blas_build", "rtxh_blas_build_reference_bvh", "rtxh_blas_build_reference_sbvh", "rtxh_texture_mips", "rtxh_texture_load", "rtxh_texture_free", "rtxh_sky_load", "rtxh_image_load", "rtxh_image_free", "rtxh_image_save_png", "rtxh_atrium_generate", "rtxh_mesh_free",
            "rtxh_obj_load", "rtxh_obj_free", "rtxh_mtl_load", "rtxh_bvh_cache_load", "rtxh_bvh_cache_save", "rtxh_bvh_cache_free",
-           "rtxh_tlas_build_balanced", "rtxh_scene_update_balanced", "rtxh_tlas_balanced_node_count", "rtxh_tlas_balanced_inner_depth"]
+           "rtxh_tlas_build_balanced", "rtxh_scene_update_balanced", "rtxh_tlas_balanced_node_count", "rtxh_tlas_balanced_inner_depth", "rtxh_blas_refit"]
 
 PI = np.float32(3.14159265359)          # Util.h:8
 
@@ -84,6 +84,7 @@ def lib():
         l.rtxh_scene_update_balanced.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32)]
         l.rtxh_tlas_balanced_node_count.argtypes = [i32]
         l.rtxh_tlas_balanced_inner_depth.argtypes = [i32]
+        l.rtxh_blas_refit.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, vp]
         for n in EXPORTS:
             getattr(l, n).restype = C.c_int
         _lib = l
@@ -296,7 +297,38 @@ def build_blas(positions: np.ndarray, normals: np.ndarray, texcoords: np.ndarray
     cold["tex_coord_0"] = uv[:, 0]; cold["tex_coord_edge_1"] = uv[:, 1] - uv[:, 0]; cold["tex_coord_edge_2"] = uv[:, 2] - uv[:, 0]
     cold["normal_0"] = nr[:, 0]; cold["normal_edge_1"] = nr[:, 1] - nr[:, 0]; cold["normal_edge_2"] = nr[:, 2] - nr[:, 0]
     cold["material_id"] = np.asarray(material_ids, np.int32)[order]
-    return sio.Blas(nodes[:nc.value].copy(), hot, cold, material_offset, n)
+    return sio.Blas(nodes[:nc.value].copy(), hot, cold, material_offset, n, np.ascontiguousarray(order, np.int32).copy())
+
+
+def slot_vertices(blas: sio.Blas, faces: Optional[np.ndarray] = None) -> np.ndarray:
+    """Vertex indices of every flattened slot of a BLAS built by build_blas, int32 (m, 3): for a triangle soup (faces None) vertex c of source
+    triangle t is row 3 t + c of the soup's (3 n, 3) positions; for an indexed mesh, faces (n, 3) holds the indices."""
+    if blas.order is None:
+        raise ValueError("this Blas has no slot order (it was not built by host.build_blas)")
+    order = np.asarray(blas.order, np.int64)
+    if faces is None:
+        return (3 * order[:, None] + np.arange(3)[None, :]).astype(np.int32)
+    return np.ascontiguousarray(np.asarray(faces).reshape(-1, 3)[order], np.int32)
+
+
+def blas_refit(blas: sio.Blas, slot_vertices: np.ndarray, positions: np.ndarray, normals: Optional[np.ndarray] = None) -> sio.Blas:
+    """rtxh_blas_refit: the BLAS that Renderer.refit_blas leaves on the device — same topology, hot triangles (and, with normals, the cold
+    normals) and every reachable node box recomputed from positions (V, 3) [normals (V, 3)] through slot_vertices (m, 3)."""
+    sv = np.ascontiguousarray(slot_vertices, np.int32).reshape(-1, 3)
+    pos = _f32(positions).reshape(-1, 3)
+    nrm = None if normals is None else _f32(normals).reshape(-1, 3)
+    if len(sv) != len(blas.tri_hot):
+        raise ValueError(f"slot_vertices holds {len(sv)} slots, the BLAS {len(blas.tri_hot)}")
+    if nrm is not None and len(nrm) != len(pos):
+        raise ValueError("positions and normals hold different numbers of vertices")
+    nodes = np.ascontiguousarray(blas.nodes).copy()
+    hot = np.zeros(len(sv), sio.TRI_HOT)
+    cold = np.ascontiguousarray(blas.tri_cold).copy()
+    rc = lib().rtxh_blas_refit(nodes.ctypes.data, len(nodes), sv.ctypes.data, len(sv), pos.ctypes.data, None if nrm is None else nrm.ctypes.data,
+                               len(pos), hot.ctypes.data, cold.ctypes.data)
+    if rc:
+        raise ValueError(f"rtxh_blas_refit failed with status {rc}")
+    return sio.Blas(nodes, hot, cold, blas.material_offset, blas.source_triangle_count, blas.order)
 
 
 def load_bvh_cache(path: str, material_offset: int = 0) -> sio.Blas:

@@ -58,6 +58,7 @@ class Blas:
     tri_cold: np.ndarray     # TRI_COLD[m]
     material_offset: int = 0
     source_triangle_count: int = 0
+    order: Optional[np.ndarray] = None   # int32[m]: flattened slot -> source triangle (host.build_blas fills it; not stored in scene files)
 
 
 @dataclass

@@ -443,7 +443,7 @@ int rtx_read_aovs(rtx_ctx * ctx, int32_t first_view, int32_t view_count, const r
  * instance_count < 1; RTX_ERR_LIMIT above RTX_UPDATE_MAX_INSTANCES; RTX_ERR_STATE before rtx_set_frame; RTX_ERR_INVALID_ARG for an
  * instance_count that is not the frame's; RTX_ERR_LIMIT when the tree of that many instances (deepest inner node at depth
  * ceil(log2 n) - 1) needs more than rtx_config.stack_size entries — the rule rtx_render_tiles applies to every BVH.  Heat-map contexts are supported.  Out of scope: the rtx_group_* path (every rank would
- * have to make the same call), world matrices or scale as input, spheres / planes / lights from device memory, BLAS refit.              */
+ * have to make the same call), world matrices or scale as input, spheres / planes / lights from device memory.  Vertices that move: rtx_refit_blas below. */
 #define RTX_UPDATE_MAX_INSTANCES 65536
 int rtx_update_instances(rtx_ctx * ctx, const void * positions_dev, const void * rotations_dev, int32_t instance_count);
 /* The frame state the kernels currently read, to host (waits for the stream): rtx_instance records (instance_count of the frame), TLAS
@@ -452,6 +452,43 @@ int rtx_update_instances(rtx_ctx * ctx, const void * positions_dev, const void *
  * gives that context the same frame.  RTX_ERR_STATE before rtx_set_frame.                                                                 */
 int rtx_read_frame_state(rtx_ctx * ctx, rtx_instance * instances, rtx_bvh_node * tlas_nodes, int32_t * tlas_node_count,
                          int32_t * tlas_indices);
+
+/* ---- device-side mesh refit ---------------------------------------------------------------------------------------------------------------
+ * A mesh whose vertices move (cloth, a soft body, a skinned character, a learned deformation) with the positions in DEVICE memory: the BLAS
+ * keeps its topology, its triangles and boxes are rewritten in place on the context's stream.  refit -> rtx_update_instances (which takes each
+ * instance's root box from the device) -> render is a complete device-only frame update; the host copies nothing and waits for nothing.
+ *
+ * rtx_bind_blas_vertices, once per mesh, from HOST memory: slot_vertices[3k + c] = index of vertex c of the triangle in flattened slot k of the
+ * arrays given to rtx_upload_blas (slot k = order_out[k] of any rtxh_blas_build*; the duplicated references of an SBVH repeat indices), every
+ * index in [0, vertex_count).  May allocate and wait.  Uploads the table and a refit plan made from the uploaded topology (parents and arrival
+ * counters for the bottom-up pass; for every slot of the 4-wide records the node whose box it carries, in the slot order chosen at upload),
+ * and moves the mesh's box-plane lists into buffers of a fixed 2 * node_count floats per axis (duplicates allowed, padded with +inf: the
+ * search only decides which walker a ray takes, never a result).  A mesh that kept the binary walk at upload keeps it.  Binding again replaces
+ * the table; uploading the id again drops the binding.  RTX_ERR_INVALID_ARG: null pointer, bad id, vertex_count < 1, an index outside the
+ * range; RTX_ERR_STATE: no BLAS uploaded under that id.
+ *
+ * rtx_refit_blas, per step, from DEVICE memory: positions vertex_count x 3 f32, normals vertex_count x 3 f32 or NULL (any 4-byte aligned
+ * address).  Queued on the context's stream (rtx_set_stream: the caller's); never waits, allocates or reads back.  The buffers are read when
+ * the work runs.  Rewrites every hot triangle (p0, p1 - p0, p2 - p0 in fp32); with normals the three normal fields of every cold triangle
+ * (texture coordinates and material ids stay; NULL: the normals stay); the box of every node reachable from the root in all four device
+ * layouts; the three sorted plane lists.  left_or_first, count, axis bits, the meta words of the wide records and unreachable node slots are
+ * not touched, and whether the mesh takes the 4-wide walks is not decided again.  Boxes: a triangle's is AABB::from_points over its vertices,
+ * then fix_if_needed (Triangle.h:17-22, AABB.h:26-32); a leaf's the union of its triangles' boxes in slot order, then fix_if_needed; an inner
+ * node's the union of its children's STORED boxes, left first, then fix_if_needed (BVHPartitions.h:11-23).  rtxh_blas_refit (rtx_host.h)
+ * builds the same bytes on the host from the same code.  Any float is a legal coordinate: a NaN or infinite component takes no part in a
+ * box, so every reachable box stays finite with min <= max and nested in its parent; a triangle with such a vertex may become invisible, a
+ * neighbour never.  A frame queued before the call renders the old mesh, the next render call (any entry point, any flag) the new one;
+ * RTX_GRAPH=1 graphs stay valid (no pointer changes after the bind).  The instances' world boxes and the TLAS are NOT updated by this call:
+ * follow with rtx_update_instances or rtx_set_frame when the root box moved.  Checked in this order, nothing changes on an error:
+ * RTX_ERR_INVALID_ARG for a null or misaligned positions_dev or a misaligned normals_dev; RTX_ERR_STATE for an id that is not uploaded or
+ * not bound; RTX_ERR_INVALID_ARG for a vertex_count that is not the bound one.  Out of scope: a new topology (rebuild on the device),
+ * normals recomputed from positions, the rtx_group_* path (every rank would have to make the same call).
+ *
+ * rtx_read_blas: what the kernels read now, to host (waits for the stream): node_count nodes in the reference layout, triangle_count hot and
+ * cold records as given to rtx_upload_blas.  Any pointer may be NULL.  RTX_ERR_STATE: no BLAS uploaded under that id.                       */
+int rtx_bind_blas_vertices(rtx_ctx * ctx, int32_t blas_id, const int32_t * slot_vertices, int32_t vertex_count);
+int rtx_refit_blas(rtx_ctx * ctx, int32_t blas_id, const void * positions_dev, const void * normals_dev, int32_t vertex_count);
+int rtx_read_blas(rtx_ctx * ctx, int32_t blas_id, rtx_bvh_node * nodes, rtx_triangle_hot * tri_hot, rtx_triangle_cold * tri_cold);
 
 /* Timing of every kernel launched since rtx_enable_kernel_timing(ctx, 1),
  * measured with HIP events on the stream the kernels are launched on.

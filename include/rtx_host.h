@@ -19,6 +19,8 @@
  *                             BVHPartitions::{calculate_bounds,partition_sah,split_indices})
  *   rtxh_tlas_build_balanced this repo's OWN TLAS builder: the tree rtx_update_instances builds on the device, from the same
  *                            code (csrc/rtx_update_math.h); rtxh_scene_update_balanced = rtx_update_instances on the host
+ *   rtxh_blas_refit          this repo's OWN refit of a flattened BLAS to moved vertices: what rtx_refit_blas leaves on the device,
+ *                            from the same code (csrc/rtx_refit_math.h)
  *   rtxh_blas_build          a BottomLevelBVH for a triangle soup: this repo's OWN binned-SAH
  *                            builder (not the reference's SBVH), output in the
  *                            reference's node convention + flattened leaf order
@@ -107,6 +109,23 @@ int rtxh_blas_build_reference_bvh(const float * positions, int32_t triangle_coun
 int rtxh_blas_build_reference_sbvh(const float * positions, int32_t triangle_count,
                                    rtx_bvh_node * nodes_out, int32_t node_capacity, int32_t * node_count_out,
                                    int32_t * order_out, int32_t order_capacity, int32_t * order_count_out);
+
+/* rtx_refit_blas (include/rtx.h) on the host, by the code the kernels run (csrc/rtx_refit_math.h): keeps the topology of a flattened BLAS
+ * (left_or_first, count and every unreachable node slot are not touched) and rewrites, for vertices that moved,
+ *   hot_out[k]   position_0, position_edge_1 = p1 - p0, position_edge_2 = p2 - p0 of slot k, p_c = positions[slot_vertices[3k + c]];
+ *   cold[k]      with normals != NULL the three normal fields the same way (texture coordinates and material ids stay); NULL: untouched;
+ *   nodes[i]     the box of every node reachable from the root, bottom-up: a triangle's box is AABB::from_points over its vertices, then
+ *                AABB::fix_if_needed (Triangle.h:17-22); a leaf's the union of its triangles' boxes in slot order, then fix_if_needed; an
+ *                inner node's the union of its children's STORED boxes, left first, then fix_if_needed (BVHPartitions.h:11-23).
+ * Any float is a legal coordinate: a NaN or infinite component takes no part in a box, an axis on which a leaf has no finite component takes
+ * [+0, +0] before the fix.  So every reachable box is finite, min <= max, and children are nested in their parents, whatever the input; a
+ * triangle with a non-finite vertex may become invisible.  slot_vertices: 3 vertex indices per flattened slot (slot k = order_out[k] of the
+ * builders: 3 * order_out[k] + c for a soup; duplicated SBVH references repeat indices).  The output handed to rtx_upload_blas is by
+ * definition what rtx_refit_blas leaves on the device.  RTX_ERR_INVALID_ARG: null pointer, an index outside [0, vertex_count), a tree whose
+ * reachable part leaves the arrays or is no tree.                                                                                        */
+int rtxh_blas_refit(rtx_bvh_node * nodes, int32_t node_count, const int32_t * slot_vertices, int32_t triangle_count,
+                    const float * positions, const float * normals_or_null, int32_t vertex_count,
+                    rtx_triangle_hot * hot_out, rtx_triangle_cold * cold);
 
 /* Camera::update's input handling (Camera.cpp:18-39): keys = OR of RTXH_KEY_* held during this frame; position / rotation are
  * updated in place (follow with rtxh_camera_basis for the view pyramid, Camera.cpp:44-47).                                      */
