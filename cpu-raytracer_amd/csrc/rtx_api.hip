@@ -31,6 +31,7 @@
 #include "rtx_update.h"
 #include "rtx_refit.h"
 #include "rtx_build.h"
+#include "rtx_query.h"
 #include <rocprim/device/device_radix_sort.hpp>      // rtx_update_instances, scenes beyond one workgroup: header-only, part of ROCm
 
 #define SLOT_BUDGET (48ll * 1000 * 1000)      // ray slots per batch of tiles (see plan_batch)
@@ -131,6 +132,9 @@ struct rtx_ctx {
 
     DevQueues q;
     DevBuf qb[20];
+    // rtx_query_closest / rtx_query_occluded: a queue set of their own (query_queues), one chunk of query_cap slots, grown only; counters and
+    // packet-queue heads of their own too, so a query never resets what rtx_get_stats has yet to read of a render call
+    DevBuf d_query[4], d_query_counters, d_query_heads; int32_t query_cap = 0;
     size_t slots_alloc = 0, shadow_alloc = 0;
     DevBuf d_dbg_s0, d_dbg_s1, d_stats_partial, d_pk_fifo, d_counters, d_spill, d_fb_rgb, d_fb_packed, d_display, d_gamma, d_pk_heads;
     int trace_blocks_closest = 0, trace_blocks_any = 0, trace_blocks_count = 0;
@@ -447,6 +451,7 @@ extern "C" int rtx_destroy(rtx_ctx * c) {
     for (DevBuf * b : bufs) if (b->p) hipFree(b->p);
     for (DevBuf & b : c->d_aov) if (b.p) hipFree(b.p);
     for (DevBuf & b : c->qb) if (b.p) hipFree(b.p);
+    for (DevBuf * b : { &c->d_query[0], &c->d_query[1], &c->d_query[2], &c->d_query[3], &c->d_query_counters, &c->d_query_heads }) if (b->p) hipFree(b->p);
     for (hipEvent_t e : c->event_pool) hipEventDestroy(e);
     for (DevCounters * h : c->pending_host) hipHostFree(h);
     for (auto & st : c->stage) { if (st.host) hipHostFree(st.host); if (st.done) hipEventDestroy(st.done); }
@@ -1152,6 +1157,29 @@ extern "C" int rtx_read_blas(rtx_ctx * c, int32_t blas_id, rtx_bvh_node * nodes,
     return RTX_OK;
 }
 
+// What the uploaded trees allow the packet kernels (render_tiles_impl, the ray queries): lane = the call takes the per-lane kernels,
+// pk_closest = closest-hit packets may walk shared subtrees together.  Only ever turns lane on and pk_closest off.
+static void packet_kernel_limits(const rtx_ctx * c, bool & lane, bool & pk_closest) {
+    for (size_t b = 0; b < c->blas_packet_ok.size(); b++) if (c->h_blas[b].nodes && !c->blas_packet_ok[b]) lane = true;      // limits of the packet kernels' packed entries
+    // The packet kernels keep ONE 64-entry stack per wave (RTX_PK_STACK) for the TLAS part and the BLAS part of a walk together, where the
+    // reference has a stack per BVH (BVH_TRAVERSAL_STACK_SIZE each).  Both depths are known here, so the choice is made on the host
+    // and pk_push's overflow path is never taken:  TLAS part = one pending far sibling per level + the iterator entry of the leaf being
+    // visited (closest-hit rays: + one parked sign-split entry per level); BLAS part = the 4-wide records' bound (pk4_need), or one far
+    // sibling per level of the binary walk; the shared closest-hit walk parks sign-split entries there too.  Scenes beyond the bound
+    // (e.g. a chain-shaped TLAS of 60 instances) are traced by the per-lane kernels, whose stacks are per BVH like the reference's.
+    const int dt = c->tlas_inner_depth < 0 ? 0 : c->tlas_inner_depth + 1;
+    int blas_any = 0, blas_shared = 0;
+    for (size_t b = 0; b < c->h_blas.size(); b++) {
+        if (!c->h_blas[b].nodes) continue;
+        const int depth = b < c->blas_inner_depth.size() ? c->blas_inner_depth[b] + 2 : 2;
+        const int any = c->h_blas[b].pk4_nodes ? c->h_blas[b].pk4_need : depth;
+        if (any > blas_any) blas_any = any;
+        if (2 * depth > blas_shared) blas_shared = 2 * depth;
+    }
+    if (dt + 1 + blas_any > RTX_PK_STACK || 2 * dt + 1 > RTX_PK_STACK) lane = true;
+    if (2 * dt + 1 + blas_shared > RTX_PK_STACK) pk_closest = false;
+}
+
 static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_stride, int32_t tile_count, uint32_t flags, uint32_t * tile_major, int views = RTX_CAM_TILES);
 static int aov_targets_of_call(rtx_ctx * c, int64_t pixels, DevAov & out);
 
@@ -1178,26 +1206,8 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
     const bool simple = (flags & RTX_RENDER_SIMPLE_TRACE) != 0;
     const bool cull = (flags & RTX_RENDER_CULL_DEAD_SHADOW_RAYS) != 0 && !simple && !count_work;
     bool lane = (flags & RTX_RENDER_LANE_TRACE) != 0;
-    for (size_t b = 0; b < c->blas_packet_ok.size(); b++) if (c->h_blas[b].nodes && !c->blas_packet_ok[b]) lane = true;      // limits of the packet kernels' packed entries
     bool pk_closest = (flags & RTX_RENDER_PACKET_CLOSEST) != 0;            // closest-hit packets walk shared subtrees together (default: lanes turn private at once)
-    {   // The packet kernels keep ONE 64-entry stack per wave (RTX_PK_STACK) for the TLAS part and the BLAS part of a walk together, where the
-        // reference has a stack per BVH (BVH_TRAVERSAL_STACK_SIZE each).  Both depths are known here, so the choice is made on the host
-        // and pk_push's overflow path is never taken:  TLAS part = one pending far sibling per level + the iterator entry of the leaf being
-        // visited (closest-hit rays: + one parked sign-split entry per level); BLAS part = the 4-wide records' bound (pk4_need), or one far
-        // sibling per level of the binary walk; the shared closest-hit walk parks sign-split entries there too.  Scenes beyond the bound
-        // (e.g. a chain-shaped TLAS of 60 instances) are traced by the per-lane kernels, whose stacks are per BVH like the reference's.
-        const int dt = c->tlas_inner_depth < 0 ? 0 : c->tlas_inner_depth + 1;
-        int blas_any = 0, blas_shared = 0;
-        for (size_t b = 0; b < c->h_blas.size(); b++) {
-            if (!c->h_blas[b].nodes) continue;
-            const int depth = b < c->blas_inner_depth.size() ? c->blas_inner_depth[b] + 2 : 2;
-            const int any = c->h_blas[b].pk4_nodes ? c->h_blas[b].pk4_need : depth;
-            if (any > blas_any) blas_any = any;
-            if (2 * depth > blas_shared) blas_shared = 2 * depth;
-        }
-        if (dt + 1 + blas_any > RTX_PK_STACK || 2 * dt + 1 > RTX_PK_STACK) lane = true;
-        if (2 * dt + 1 + blas_shared > RTX_PK_STACK) pk_closest = false;
-    }
+    packet_kernel_limits(c, lane, pk_closest);
     const bool pstat = (flags & RTX_RENDER_PACKET_STATS) != 0 && !simple && !count_work && !lane;
     // RTX_RENDER_AOV: level 0 takes k_shade<.., AOV = true> with the bound channels' targets; the call's pixel range is the frame, or its views
     const bool aov = (flags & RTX_RENDER_AOV) != 0;
@@ -2117,6 +2127,119 @@ extern "C" int rtx_debug_group_loopback(rtx_ctx * c, int32_t world, uint32_t fla
     if (g.send.p) hipFree(g.send.p);
     if (g.recv.p) hipFree(g.recv.p);
     return rc;
+}
+
+// ---- ray queries (include/rtx.h: rtx_query_closest / rtx_query_occluded; kernels in rtx_query.h) -------------------------------------
+// N rays or segments in device memory against the frame the context holds, answers into device memory: per chunk of at most
+// RTX_QUERY_CHUNK_RAYS rows  k_begin_batch -> fill -> the production traversal kernel -> resolve / store, all on the context's stream.
+// Nothing here waits, copies or allocates once the scratch holds a chunk of the call's size.
+//
+// The queue set is the queries' own.  The debug hooks below borrow the frame's: level 1 of the ray queue (which a context with
+// bounces == 0 does not have) and light 0's shadow segment (which a frame without lights does not have), sized and re-sized by
+// alloc_queues.  Here: level 1 for rays and hits, level 0 for the node flags of the one explicit shadow segment, both at base 0 — a
+// closest-hit query touches r0 / r1 / h0 / h1, an occlusion query s0 / s1 / n0 / socc, and the two are stream-ordered, so they share four
+// buffers: 52 bytes per slot, 52 MiB for a full chunk.  DevScene and DevQueues travel by value: a frame queued before or after is untouched.
+static int query_queues(rtx_ctx * c, int64_t n, DevQueues & q) {
+    const int64_t rows = n < (int64_t)RTX_QUERY_CHUNK_RAYS ? n : (int64_t)RTX_QUERY_CHUNK_RAYS;
+    const int32_t cap = (int32_t)((rows + RTX_WAVE - 1) & ~(int64_t)(RTX_WAVE - 1));      // whole packets: the fill marks the tail of the last one
+    if (cap > c->query_cap) {                              // growth: queued queries still use the old buffers
+        HIP_OK(c, hipStreamSynchronize(c->stream));
+        int rc = ensure(c, c->d_query_counters, sizeof(DevCounters));
+        if (!rc) rc = ensure(c, c->d_query_heads, (size_t)2 * (RTX_MAX_LEVELS + 1) * RTX_PK_CLASSES * 32 * sizeof(uint32_t));
+        for (int k = 0; k < 4 && !rc; k++) rc = ensure(c, c->d_query[k], (size_t)cap * (k < 3 ? 16 : 4));
+        if (rc) { c->query_cap = 0; return rc; }
+        c->query_cap = cap;
+    }
+    q = c->q;                                              // the walkers' knobs (thresholds, spill_threads) as rtx_create read them
+    for (int d = 0; d <= RTX_MAX_LEVELS; d++) { q.level_base[d] = 0; q.level_cap[d] = d < 2 ? c->query_cap : 0; q.shadow_base[d] = 0; q.stats_n[d] = 0; }
+    q.first_tile = 0; q.tile_stride = 1; q.tile_count = 0; q.primary_slots = 0;
+    q.r0 = q.s0 = (float4 *)c->d_query[0].p; q.r1 = q.s1 = (float4 *)c->d_query[1].p; q.h0 = q.n0 = (float4 *)c->d_query[2].p;
+    q.h1 = (int32_t *)c->d_query[3].p; q.socc = (uint32_t *)c->d_query[3].p;
+    q.r2 = q.r3 = q.r4 = q.n1 = q.n2 = q.c0 = q.c1 = q.sp = q.sn = nullptr; q.views = nullptr;
+    q.shadow_explicit = 0; q.cull = 0;
+    q.spill = (int32_t *)c->d_spill.p; q.pk_fifo = (int32_t *)c->d_pk_fifo.p;
+    q.pk_items = nullptr; q.pk_item_count = nullptr; q.pk_item_cap = 0;
+    q.counters = (DevCounters *)c->d_query_counters.p; q.pk_heads = (uint32_t *)c->d_query_heads.p;
+    q.stats_partial = nullptr; q.stats_stride = 0; q.pk_cost = nullptr; q.pk_lpt_order = nullptr;
+    q.tm_packed = nullptr; q.tm_base = 0; q.fb_rgb = nullptr; q.fb_packed = nullptr;
+    return RTX_OK;
+}
+
+// the checks both calls share, in the order the header lists them; nothing is queued on an error
+static int query_checks(rtx_ctx * c, const void * in, int64_t n, const void * out, uint32_t flags, const char * what) {
+    if (!c) return RTX_ERR_INVALID_ARG;
+    if (!in || !out || n < 1) { c->err = std::string(what) + ": null pointer or n < 1"; return RTX_ERR_INVALID_ARG; }
+    if (flags & ~(uint32_t)(RTX_RENDER_LANE_TRACE | RTX_RENDER_PACKET_CLOSEST)) { c->err = std::string(what) + ": flags other than RTX_RENDER_LANE_TRACE / RTX_RENDER_PACKET_CLOSEST"; return RTX_ERR_INVALID_ARG; }
+    if (!c->frame_set) { c->err = std::string(what) + " before rtx_set_frame"; return RTX_ERR_STATE; }
+    if (c->scene.heatmap) { c->err = std::string(what) + " in heat-map mode"; return RTX_ERR_STATE; }
+    return validate_references(c);
+}
+
+static void query_begin_chunk(rtx_ctx * c, const DevQueues & q) {
+    hipLaunchKernelGGL(k_begin_batch, dim3(1), dim3(64), 0, c->stream, q.counters, q.pk_heads, 0u,
+                       (uint32_t)(c->trace_blocks_closest * RTX_TRACE_BLOCK), (uint32_t)(c->trace_blocks_any * RTX_TRACE_BLOCK),
+                       (uint32_t)(c->pk_blocks_closest * (RTX_PK_BLOCK / RTX_WAVE)), (uint32_t)(c->pk_blocks_any * (RTX_PK_BLOCK / RTX_WAVE)), 1);
+}
+
+extern "C" int rtx_query_closest(rtx_ctx * c, const void * rays_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags) {
+    if (c && (channels == 0 || (channels & ~(uint32_t)RTX_QUERY_ALL))) { c->err = "rtx_query_closest: channels must be a non-empty subset of RTX_QUERY_ALL"; return RTX_ERR_INVALID_ARG; }
+    if (int bad = query_checks(c, rays_dev, n, out, flags, "rtx_query_closest")) return bad;
+    hipSetDevice(c->cfg.device);
+    DevQueues q;
+    if (int rc = query_queues(c, n, q)) return rc;
+    bool lane = (flags & RTX_RENDER_LANE_TRACE) != 0, pk_closest = (flags & RTX_RENDER_PACKET_CLOSEST) != 0;
+    packet_kernel_limits(c, lane, pk_closest);
+    if (pk_closest) q.pk_defer_t0_closest = q.pk_defer_t0_primary = q.pk_defer_t0;
+    const DevScene sc = c->scene;
+    DevScene sc_resolve = sc; sc_resolve.diff_enabled = 0;          // the differentials are zero and no channel reports a RayHit differential
+    for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
+        const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
+        const int blocks = (((m + RTX_WAVE - 1) & ~(RTX_WAVE - 1)) + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK;
+        q.tile_count = (m + 1023) / 1024;
+        DevQuery t;
+        auto on = [&](uint32_t bit) { return (channels & bit) != 0; };
+        t.distance = on(RTX_QUERY_DISTANCE) && out->distance ? out->distance + first : nullptr;
+        t.position = on(RTX_QUERY_POSITION) && out->position ? out->position + 3 * first : nullptr;
+        t.normal = on(RTX_QUERY_NORMAL) && out->normal ? out->normal + 3 * first : nullptr;
+        t.uv = on(RTX_QUERY_UV) && out->uv ? out->uv + 2 * first : nullptr;
+        t.material_id = on(RTX_QUERY_MATERIAL_ID) && out->material_id ? out->material_id + first : nullptr;
+        t.object_id = on(RTX_QUERY_OBJECT_ID) && out->object_id ? out->object_id + first : nullptr;
+        t.triangle_id = on(RTX_QUERY_TRIANGLE_ID) && out->triangle_id ? out->triangle_id + first : nullptr;
+        query_begin_chunk(c, q);
+        launch_timed(c, "k_query_fill", c->stream, [&] { hipLaunchKernelGGL(k_query_fill, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, q, (const float *)rays_dev + 6 * first, m); });
+        launch_timed(c, "k_trace_closest", c->stream, [&] {
+            if (lane) hipLaunchKernelGGL((k_trace_fast<false>), dim3(c->trace_blocks_closest), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, 1, 1);
+            else      hipLaunchKernelGGL((k_packet<false, false>), dim3(c->pk_blocks_closest), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, 1, 1);
+        });
+        launch_timed(c, "k_query_resolve", c->stream, [&] { hipLaunchKernelGGL(k_query_resolve, dim3((m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc_resolve, q, m, t); });
+    }
+    HIP_OK(c, hipGetLastError());
+    return RTX_OK;
+}
+
+extern "C" int rtx_query_occluded(rtx_ctx * c, const void * segments_dev, int64_t n, int32_t * occluded_dev, uint32_t flags) {
+    if (int bad = query_checks(c, segments_dev, n, occluded_dev, flags, "rtx_query_occluded")) return bad;
+    hipSetDevice(c->cfg.device);
+    DevQueues q;
+    if (int rc = query_queues(c, n, q)) return rc;
+    q.shadow_explicit = 1;
+    bool lane = (flags & RTX_RENDER_LANE_TRACE) != 0, pk_closest = false;
+    packet_kernel_limits(c, lane, pk_closest);
+    DevScene sc = c->scene; sc.light_count = 1;                     // one explicit segment (k_query_fill_segments), whatever lights the frame has: none are read
+    for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
+        const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
+        const int blocks = (((m + RTX_WAVE - 1) & ~(RTX_WAVE - 1)) + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK;
+        q.tile_count = (m + 1023) / 1024;
+        query_begin_chunk(c, q);
+        launch_timed(c, "k_query_fill_segments", c->stream, [&] { hipLaunchKernelGGL(k_query_fill_segments, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, q, (const float *)segments_dev + 7 * first, m); });
+        launch_timed(c, "k_trace_any", c->stream, [&] {
+            if (lane) hipLaunchKernelGGL((k_trace_fast<true>), dim3(c->trace_blocks_any), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, 0, 0);
+            else      hipLaunchKernelGGL((k_packet<true, false>), dim3(c->pk_blocks_any), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, 0, 0);
+        });
+        launch_timed(c, "k_query_store_occluded", c->stream, [&] { hipLaunchKernelGGL(k_query_store_occluded, dim3((m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK), dim3(RTX_QUERY_BLOCK), 0, c->stream, q, m, occluded_dev + first); });
+    }
+    HIP_OK(c, hipGetLastError());
+    return RTX_OK;
 }
 
 // ---- unit-level entry points, second set: the traversal / hit / light / plot functions at caller-supplied inputs -------------------

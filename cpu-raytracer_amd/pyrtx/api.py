@@ -25,7 +25,8 @@ EXPORTS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error", "rt
            "rtx_group_layout", "rtx_group_slot_pixels", "rtx_debug_group_loopback", "rtx_debug_trace_rays", "rtx_debug_occluded", "rtx_debug_light_plot",
            "rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer", "rtx_bind_aovs", "rtx_read_aovs",
            "rtx_set_rays", "rtx_bind_rays", "rtx_render_rays", "rtx_update_instances", "rtx_read_frame_state",
-           "rtx_bind_blas_vertices", "rtx_refit_blas", "rtx_read_blas", "rtx_alloc_blas", "rtx_build_blas"]
+           "rtx_bind_blas_vertices", "rtx_refit_blas", "rtx_read_blas", "rtx_alloc_blas", "rtx_build_blas",
+           "rtx_query_closest", "rtx_query_occluded"]
 # newer than the A/B variants tools/ab.py may load (RTX_HIP_LIB = a library built from an older commit): bound when the library has them,
 # otherwise a call raises AttributeError (undefined symbol)
 VIEW_EXPORTS = ("rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer")
@@ -34,6 +35,7 @@ RAY_EXPORTS = ("rtx_set_rays", "rtx_bind_rays", "rtx_render_rays")
 UPDATE_EXPORTS = ("rtx_update_instances", "rtx_read_frame_state")
 REFIT_EXPORTS = ("rtx_bind_blas_vertices", "rtx_refit_blas", "rtx_read_blas")
 BUILD_EXPORTS = ("rtx_alloc_blas", "rtx_build_blas")
+QUERY_EXPORTS = ("rtx_query_closest", "rtx_query_occluded")
 RTX_UPDATE_MAX_INSTANCES = 65536
 
 RTX_RENDER_COUNT_WORK = 1
@@ -45,6 +47,28 @@ RTX_RENDER_PACKET_STATS = 32
 RTX_RENDER_PACKET_CLOSEST = 64
 RTX_RENDER_AOV = 128
 RTX_MAX_VIEWS = 4096
+# ray queries (include/rtx.h RTX_QUERY_*): the RTX_AOV_* bits of the same meaning, no albedo
+RTX_QUERY_DISTANCE = 1
+RTX_QUERY_POSITION = 2
+RTX_QUERY_NORMAL = 4
+RTX_QUERY_UV = 16
+RTX_QUERY_MATERIAL_ID = 32
+RTX_QUERY_OBJECT_ID = 64
+RTX_QUERY_TRIANGLE_ID = 128
+RTX_QUERY_ALL = 247
+RTX_QUERY_CHUNK_RAYS = 1 << 20
+# name -> (bit, numpy dtype, components per ray), in rtx_query_buffers order
+QUERY_CHANNELS = {"distance": (RTX_QUERY_DISTANCE, np.float32, 1), "position": (RTX_QUERY_POSITION, np.float32, 3),
+                  "normal": (RTX_QUERY_NORMAL, np.float32, 3), "uv": (RTX_QUERY_UV, np.float32, 2),
+                  "material_id": (RTX_QUERY_MATERIAL_ID, np.int32, 1), "object_id": (RTX_QUERY_OBJECT_ID, np.int32, 1),
+                  "triangle_id": (RTX_QUERY_TRIANGLE_ID, np.int32, 1)}
+
+
+class RtxQueryBuffers(C.Structure):
+    """rtx_query_buffers: one device pointer per channel, None = not written."""
+    _fields_ = [(name, C.c_void_p) for name in QUERY_CHANNELS]
+
+
 ERRORS = {1: "RTX_ERR_INVALID_ARG", 2: "RTX_ERR_NO_DEVICE", 3: "RTX_ERR_HIP", 4: "RTX_ERR_LIMIT", 5: "RTX_ERR_STATE", 6: "RTX_ERR_OOM"}
 
 _lib = None
@@ -125,8 +149,11 @@ def load_library(path: Optional[str] = None):
     if hasattr(lib, "rtx_build_blas"):
         lib.rtx_alloc_blas.argtypes = [vp, i32, i32, i32, vp, i32]
         lib.rtx_build_blas.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    if hasattr(lib, "rtx_query_closest"):
+        lib.rtx_query_closest.argtypes = [vp, vp, C.c_int64, u32, C.POINTER(RtxQueryBuffers), u32]
+        lib.rtx_query_occluded.argtypes = [vp, vp, C.c_int64, vp, u32]
     for name in EXPORTS:
-        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS and not hasattr(lib, name):
+        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         if name not in ("rtx_last_error",):
@@ -172,6 +199,29 @@ def aov_shape(name: str, views: Optional[int], height: int, width: int) -> tuple
     """Shape of channel `name` for `views` views ((H, W[, k]) when views is None)."""
     k = AOV_CHANNELS[name][2]
     return ((views,) if views is not None else ()) + (height, width) + ((k,) if k > 1 else ())
+
+
+def query_names(channels) -> tuple:
+    """Ray-query channel names (keys of QUERY_CHANNELS, in that order) of a RTX_QUERY_* mask, one name or an iterable of names; at least
+    one.  Raises before anything reaches the library."""
+    if isinstance(channels, (int, np.integer)) and not isinstance(channels, bool):
+        if int(channels) & ~RTX_QUERY_ALL or int(channels) < 0:
+            raise ValueError(f"query channel mask {channels} has bits outside RTX_QUERY_ALL")
+        names = tuple(n for n, (bit, _, _) in QUERY_CHANNELS.items() if int(channels) & bit)
+    else:
+        if isinstance(channels, str):
+            channels = (channels,)
+        want = set()
+        for n in channels:
+            if not isinstance(n, str):
+                raise TypeError(f"query channels are names ({', '.join(QUERY_CHANNELS)}), not {type(n).__name__}")
+            if n not in QUERY_CHANNELS:
+                raise ValueError(f"unknown query channel {n!r} (known: {', '.join(QUERY_CHANNELS)})")
+            want.add(n)
+        names = tuple(n for n in QUERY_CHANNELS if n in want)
+    if not names:
+        raise ValueError("a query needs at least one channel")
+    return names
 
 
 def views_array(cameras) -> np.ndarray:
@@ -532,6 +582,23 @@ class Renderer:
                 raise ValueError(f"{name} must be on cuda:{dev} (this context's GPU), not {t.device}")
         if view_count < 1 or first_view < 0 or first_view + view_count > rgb.shape[0]:
             raise ValueError(f"views [{first_view}, {first_view + view_count}) do not fit tensors of {rgb.shape[0]} views")
+        fb = (rgb.data_ptr(), packed.data_ptr(), int(rgb.shape[0]))
+
+        def bind_and_launch():
+            if getattr(self, "_view_fb", None) != fb:
+                self.bind_view_framebuffer(*fb)
+            fl = flags
+            if aovs:
+                self.bind_aovs(list(aovs), {name: t.data_ptr() for name, t in aovs.items()}, int(rgb.shape[0]) * sc.height * sc.width)
+                fl = dict(flags, aov=True)
+            launch(fl)
+        self._on_torch_stream(bind_and_launch, tuple(w[1] for w in want) + tuple(also))
+
+    def _on_torch_stream(self, launch, tensors):
+        """Moves the context to torch's current stream of its device (rtx_set_stream: it stays there), calls launch(), and keeps `tensors`
+        — everything the queued work reads or writes — from being handed out again before that work is done."""
+        import torch
+        dev = self.device
         cur = torch.cuda.current_stream(dev)
         # torch's default stream has the handle 0, which rtx_set_stream reads as "the context's own stream" — a non-blocking stream that does
         # not synchronise with it.  Then the work goes to a side stream of this renderer, joined to the current stream on both sides by events.
@@ -544,17 +611,11 @@ class Renderer:
         stream = (side or cur).cuda_stream
         if getattr(self, "_stream", None) != stream:
             self.set_stream(stream)
-        fb = (rgb.data_ptr(), packed.data_ptr(), int(rgb.shape[0]))
-        if getattr(self, "_view_fb", None) != fb:
-            self.bind_view_framebuffer(*fb)
-        if aovs:
-            self.bind_aovs(list(aovs), {name: t.data_ptr() for name, t in aovs.items()}, int(rgb.shape[0]) * sc.height * sc.width)
-            flags = dict(flags, aov=True)
-        launch(flags)
+        launch()
         if side is not None:
             cur.wait_stream(side)
-            for t in tuple(w[1] for w in want) + tuple(also):
-                t.record_stream(side)      # the caching allocator must not hand the memory out before the render is done
+            for t in tensors:
+                t.record_stream(side)      # the caching allocator must not hand the memory out before the work is done
 
     # ---- ray views: caller-supplied primary rays (include/rtx.h: rtx_set_rays / rtx_bind_rays / rtx_render_rays) -------------------
     def set_rays(self, rays):
@@ -772,6 +833,128 @@ class Renderer:
         nodes = np.zeros(n, sio.BVH_NODE); hot = np.zeros(m, sio.TRI_HOT); cold = np.zeros(m, sio.TRI_COLD)
         self._chk(self.lib.rtx_read_blas(self.ctx, int(blas_id), nodes.ctypes.data, hot.ctypes.data, cold.ctypes.data), "rtx_read_blas")
         return sio.Blas(nodes, hot, cold, off, src)
+
+    # ---- ray queries (include/rtx.h: rtx_query_closest / rtx_query_occluded) ---------------------------------------------------------
+    def _query_rows(self, name: str, rows, width: int, n: Optional[int]):
+        """(device pointer, n, tensor or None) of a query's input: a float32 torch tensor (n, width), or a raw device pointer with n.
+        Raises before anything reaches the library; _query_on_device checks where the tensor lives."""
+        if isinstance(rows, (int, np.integer)) and not isinstance(rows, bool):
+            if n is None:
+                raise ValueError(f"n is needed when {name} is a raw device pointer")
+            if int(n) < 1 or not rows:
+                raise ValueError(f"{name}: a non-null device pointer and n >= 1 are needed, not {rows} and {n}")
+            return int(rows), int(n), None
+        import torch
+        if not isinstance(rows, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor (or a raw device pointer with n), not {type(rows).__name__}")
+        if rows.dtype != torch.float32:
+            raise TypeError(f"{name} must be torch.float32, not {rows.dtype}")
+        if rows.dim() != 2 or rows.shape[1] != width:
+            raise ValueError(f"{name} must have shape (n, {width}), not {tuple(rows.shape)}")
+        if not rows.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if n is None:
+            n = int(rows.shape[0])
+        if not 1 <= int(n) <= rows.shape[0]:
+            raise ValueError(f"n must be in [1, {rows.shape[0]}] for {name} of shape {tuple(rows.shape)}, not {n}")
+        return rows.data_ptr(), int(n), rows
+
+    def _query_out(self, name: str, t, dtype, n: int, k: int, raw: bool):
+        """Device pointer of an output: a caller tensor of n rows (checked), or with raw inputs a raw device pointer."""
+        if raw and isinstance(t, (int, np.integer)) and not isinstance(t, bool):
+            if not t:
+                raise ValueError(f"out[{name!r}] is a null device pointer")
+            return int(t)
+        import torch
+        want_dt = torch.float32 if dtype == np.float32 else torch.int32
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"out[{name!r}] must be a torch.Tensor, not {type(t).__name__}")
+        if t.dtype != want_dt:
+            raise TypeError(f"out[{name!r}] must be {want_dt}, not {t.dtype}")
+        shape = (n, k) if k > 1 else (n,)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"out[{name!r}] must have shape {shape}, not {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"out[{name!r}] must be contiguous")
+        return t.data_ptr()
+
+    def _query_on_device(self, tensors: Dict):
+        """The last check of a query, after every type, dtype and shape: each tensor lives on this context's GPU."""
+        for name, t in tensors.items():
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError(f"{name} must be on cuda:{self.device} (this context's GPU), not {t.device}")
+
+    def query_closest(self, rays, channels=("distance",), out: Optional[Dict] = None, n: Optional[int] = None, **flags) -> Dict:
+        """The closest hit of n arbitrary rays against the frame the context holds (rtx_query_closest): rays = float32 torch tensor (n, 6)
+        of (origin, direction) on this context's GPU; channels = names out of distance, position, normal, uv, material_id, object_id,
+        triangle_id (or a RTX_QUERY_* mask).  Returns {name: tensor}: float32 / int32, (n,), (n, 3) or (n, 2), allocated on the device unless
+        out = {name: tensor} supplies them.  A miss: distance inf, ids -1, the rest 0; a zero direction is no ray and a miss.  Queued on
+        torch's current stream like render_views_into: torch work queued after the call sees the answers, nothing is read back.  flags:
+        lane_trace / packet_closest.  Raw device pointers: rays = address, n = rays, out = {name: address} for every channel wanted (then the
+        work goes to the stream set with set_stream).  Everything is checked before the library is reached.  Returns at once."""
+        names = query_names(channels)
+        ptr, n, rays_t = self._query_rows("rays", rays, 6, n)
+        if out is not None and not isinstance(out, dict):
+            raise TypeError(f"out must be a dict {{channel name: tensor}}, not {type(out).__name__}")
+        out = dict(out or {})
+        query_names(list(out) or names)
+        extra = [k for k in out if k not in names]
+        if extra:
+            raise ValueError(f"out holds channels that were not requested: {', '.join(extra)}")
+        raw = rays_t is None
+        if raw and len(out) != len(names):
+            raise ValueError("with raw device pointers out must hold an address for every requested channel")
+        fl = render_flags(**flags)
+        if fl & ~(RTX_RENDER_LANE_TRACE | RTX_RENDER_PACKET_CLOSEST):
+            raise ValueError("a query takes the flags lane_trace and packet_closest only")
+        buf = RtxQueryBuffers()
+        for name in out:
+            _, dt, k = QUERY_CHANNELS[name]
+            setattr(buf, name, self._query_out(name, out[name], dt, n, k, raw))
+        self._query_on_device({k: t for k, t in [("rays", rays_t)] + [(f"out[{k!r}]", t) for k, t in out.items()] if hasattr(t, "device")})
+        for name in names:
+            if name not in out:
+                import torch
+                _, dt, k = QUERY_CHANNELS[name]
+                out[name] = torch.empty((n, k) if k > 1 else (n,), dtype=torch.float32 if dt == np.float32 else torch.int32, device=rays_t.device)
+                setattr(buf, name, out[name].data_ptr())
+        mask = sum(QUERY_CHANNELS[name][0] for name in names)
+
+        def launch():
+            self._chk(self.lib.rtx_query_closest(self.ctx, ptr, n, mask, C.byref(buf), fl), "rtx_query_closest")
+        tensors = [t for t in [rays_t] + list(out.values()) if hasattr(t, "record_stream")]
+        if tensors:
+            self._on_torch_stream(launch, tensors)
+        else:
+            launch()
+        return {name: out[name] for name in names}
+
+    def query_occluded(self, segments, out=None, n: Optional[int] = None, **flags):
+        """Whether each of n segments is blocked (rtx_query_occluded): segments = float32 torch tensor (n, 7) of (origin, direction, max
+        distance) on this context's GPU; returns the int32 tensor (n,) of 1 / 0 (out, or a new one): 1 = something is hit at a distance
+        strictly below the maximum.  Queued, checked and flagged like query_closest; raw device pointers: segments = address, n, out = address."""
+        ptr, n, seg_t = self._query_rows("segments", segments, 7, n)
+        raw = seg_t is None
+        fl = render_flags(**flags)
+        if fl & ~(RTX_RENDER_LANE_TRACE | RTX_RENDER_PACKET_CLOSEST):
+            raise ValueError("a query takes the flags lane_trace and packet_closest only")
+        if out is None and raw:
+            raise ValueError("with raw device pointers out must be the address of the result")
+        optr = None if out is None else self._query_out("occluded", out, np.int32, n, 1, raw)
+        self._query_on_device({k: t for k, t in (("segments", seg_t), ("out", out)) if hasattr(t, "device")})
+        if out is None:
+            import torch
+            out = torch.empty((n,), dtype=torch.int32, device=seg_t.device)
+            optr = out.data_ptr()
+
+        def launch():
+            self._chk(self.lib.rtx_query_occluded(self.ctx, ptr, n, optr, fl), "rtx_query_occluded")
+        tensors = [t for t in (seg_t, out) if hasattr(t, "record_stream")]
+        if tensors:
+            self._on_torch_stream(launch, tensors)
+        else:
+            launch()
+        return out
 
     def enable_timing(self, on: bool = True):
         self._chk(self.lib.rtx_enable_kernel_timing(self.ctx, 1 if on else 0), "rtx_enable_kernel_timing")

@@ -528,6 +528,68 @@ int rtx_alloc_blas(rtx_ctx * ctx, int32_t blas_id, int32_t triangle_count, int32
 int rtx_build_blas(rtx_ctx * ctx, int32_t blas_id, const void * positions_dev, const void * indices_dev, const void * normals_dev,
                    const void * texcoords_dev, void * order_out_dev);
 
+/* ---- ray queries -----------------------------------------------------------------------------------------------------------------------
+ * Questions to the scene without rendering a frame: n arbitrary rays -> the closest hit of each, n segments -> whether each is blocked.
+ * For sensors with non-rectangular patterns (lidar, depth), line of sight between point pairs, contact and collision probes, points sampled
+ * on surfaces.  Rays, segments and answers live in DEVICE memory; both calls are queued on the context's stream (rtx_set_stream: the
+ * caller's) and return at once: nothing is read back, nothing waits, the inputs are read when the work runs and must stay valid until then.
+ * The scene is the frame the context holds when the call is made: what rtx_set_frame set, or what rtx_update_instances / rtx_refit_blas /
+ * rtx_build_blas last wrote into it.  They work with bounces == 0 and with a frame without lights, and they use a queue set of their own:
+ * a query between two render calls changes neither frame, nor what rtx_get_stats reports for them.
+ *
+ * rtx_query_closest: ray i = rays_dev[6i .. 6i+5] (origin, direction; any 4-byte aligned address) through Scene::trace_primitives
+ * (Scene.cpp:173-180: spheres, planes, then the TLAS) by the production closest-hit kernel, its RayHit rebuilt by the functions the shading
+ * pass uses (the accept branches of BottomLevelBVH::triangle_trace, Sphere::trace, Plane::trace), with zero ray differentials.  Directions
+ * are used as given, distances are in units of |direction|; there is no per-ray tmin / tmax (the reference has none).
+ * Channel (bit)          per ray      hit                                                        miss
+ *   DISTANCE             f32          RayHit::distance (RayHit.h:6)                              +INFINITY
+ *   POSITION             3 x f32      RayHit::point, world space (RayHit.h:8)                     0
+ *   NORMAL               3 x f32      RayHit::normal (RayHit.h:9)                                 0
+ *   UV                   2 x f32      RayHit::u, v (RayHit.h:12)                                  0
+ *   MATERIAL_ID          i32          RayHit::material_id, global (RayHit.h:11)                   -1
+ *   OBJECT_ID            i32          the numbering of RTX_AOV_OBJECT_ID                          -1
+ *   TRIANGLE_ID          i32          the numbering of RTX_AOV_TRIANGLE_ID                        -1 (also for spheres and planes)
+ * The bits are the RTX_AOV_* bits of the same meaning; there is no albedo (no texture is sampled).  A channel is written only if its bit
+ * is set and its pointer is not NULL; element i of every written channel belongs to ray i; nothing beyond element n - 1 is touched.
+ * Distance and ids come straight from the hit record; position, normal and uv cost the rebuild (two more record reads and, for a
+ * triangle, its cold record), which runs only when one of the three is requested.
+ * A ray whose direction is exactly (+-0, +-0, +-0) is no ray, as for ray views (rtx_ray above): it is not traced and gets the miss values.
+ * Any other floats are legal.  A ray with a NaN or infinite origin or direction component hits nothing in the reference's arithmetic
+ * (every hit test ends in a comparison with a NaN, a zero or an infinite distance): it gets the miss values too.
+ *
+ * rtx_query_occluded: segment i = segments_dev[7i .. 7i+6] (origin, direction, max distance) through Scene::intersect_primitives
+ * (Scene.cpp:182-190) by the production shadow-ray kernel: occluded_dev[i] = 1 when something is hit at RAY_EPSILON < t < max distance
+ * (strictly, as the reference's shadow rays), else 0.  A zero-direction segment is not occluded; nor is one with a NaN or infinite
+ * component, or a maximum distance that is NaN or not above 0.  +INFINITY is a legal maximum distance (a directional light's).
+ *
+ * Any n >= 1: rays are traced in rounds of at most RTX_QUERY_CHUNK_RAYS, queued back to back, so the scratch (52 bytes per ray of a round:
+ * ray, hit and segment records; allocated by the first call, grown only, freed by rtx_destroy) is bounded whatever n is.  A call with the
+ * same or a smaller n than an earlier one allocates and frees nothing; one that grows the scratch waits for the stream first.
+ * flags: RTX_RENDER_LANE_TRACE / RTX_RENDER_PACKET_CLOSEST choose the kernel as for a render call (the answers are bit-identical);
+ * scenes whose trees exceed the packet kernels' limits take the per-lane kernels as in a render call.  A packet is 64 consecutive rays:
+ * rays that travel together are cheapest next to each other.
+ * RTX_ERR_INVALID_ARG: n < 1, NULL rays_dev / segments_dev / out / occluded_dev, channels == 0 or with bits outside RTX_QUERY_ALL, any
+ * other flag.  RTX_ERR_STATE: before rtx_set_frame, in heat-map mode, or for a scene a render call refuses (an id outside its table);
+ * RTX_ERR_LIMIT: a BVH deeper than rtx_config.stack_size allows — the checks of rtx_render_tiles.  An error queues nothing.
+ * Out of scope: sorting rays for coherence, barycentrics, albedo, the rtx_group_* path.                                                  */
+enum { RTX_QUERY_DISTANCE = 1, RTX_QUERY_POSITION = 2, RTX_QUERY_NORMAL = 4, RTX_QUERY_UV = 16,
+       RTX_QUERY_MATERIAL_ID = 32, RTX_QUERY_OBJECT_ID = 64, RTX_QUERY_TRIANGLE_ID = 128,
+       RTX_QUERY_ALL = 247 };            /* the RTX_AOV_* bits of the same meaning; there is no albedo */
+enum { RTX_QUERY_CHUNK_RAYS = 1 << 20 }; /* rays traced per internal round */
+typedef struct rtx_query_buffers {       /* device pointers, one per channel, NULL = not written */
+    float   * distance;                  /* [n]     RayHit::distance, +INFINITY on a miss */
+    float   * position;                  /* [n][3]  RayHit::point,  0 on a miss            */
+    float   * normal;                    /* [n][3]  RayHit::normal, 0 on a miss            */
+    float   * uv;                        /* [n][2]  RayHit::u, v,   0 on a miss            */
+    int32_t * material_id;               /* [n]     global id, -1 on a miss                */
+    int32_t * object_id;                 /* [n]     numbering of RTX_AOV_OBJECT_ID, -1     */
+    int32_t * triangle_id;               /* [n]     numbering of RTX_AOV_TRIANGLE_ID, -1   */
+} rtx_query_buffers;
+int rtx_query_closest (rtx_ctx * ctx, const void * rays_dev /* [n][6] f32: origin, direction */, int64_t n,
+                       uint32_t channels, const rtx_query_buffers * out, uint32_t flags);
+int rtx_query_occluded(rtx_ctx * ctx, const void * segments_dev /* [n][7] f32: origin, direction, max distance */, int64_t n,
+                       int32_t * occluded_dev /* [n]: 1 or 0 */, uint32_t flags);
+
 /* Timing of every kernel launched since rtx_enable_kernel_timing(ctx, 1),
  * measured with HIP events on the stream the kernels are launched on.
  * names/ms hold up to `capacity` entries; *count receives the number of
