@@ -33,12 +33,9 @@
 #include "rtx_build.h"
 #include "rtx_query.h"
 #include <rocprim/device/device_radix_sort.hpp>      // rtx_update_instances, scenes beyond one workgroup: header-only, part of ROCm
+#include "rtx_hostmem.h"                             // DevBuf, StageRing, grow_keep: every device and pinned allocation has one owner
 
 #define SLOT_BUDGET (48ll * 1000 * 1000)      // ray slots per batch of tiles (see plan_batch)
-
-struct DevBuf {
-    void * p = nullptr; size_t cap = 0;
-};
 
 // Tuning knobs (environment, A/B runs and tests): read ONCE per context in rtx_create, validated and clamped there; a value that does not
 // parse or lies outside its range leaves the default in place.  Nothing on the render path calls getenv.
@@ -82,47 +79,46 @@ struct rtx_ctx {
     std::string err;
     int n_cu = 0;
 
+    // Every device and pinned allocation below belongs to a DevBuf or a StageRing member (rtx_hostmem.h) and dies with the context: there is no
+    // list of buffers to keep anywhere.  Per BLAS id: h_blas[id] is the id's entry of the contiguous table the kernels read (uploaded to d_blas),
+    // blas[id] the host's record of it; both vectors are resized together (commit_blas).
+    // rtx_bind_blas_vertices / rtx_refit_blas: the record-slot -> node maps of the 4-wide layouts as the upload laid them out (empty: binary
+    // walk), and once bound the plan's device block and the kernel arguments of a refit, which point into it
+    struct BlasRefit { std::vector<int32_t> map4, map4c; bool bound = false; int32_t vertex_count = 0; DevBuf block; DevRefit dev; float * planes[3] = { nullptr, nullptr, nullptr }; void * sort_tmp = nullptr; size_t sort_bytes = 0; };
+    // rtx_alloc_blas / rtx_build_blas: the scratch block and the kernel arguments of a build
+    struct BlasBuild { bool allocated = false; DevBuf block; DevBuild dev; void * sort_tmp = nullptr; size_t sort_bytes = 0; int levels = 0; };
+    // max_local_material, inner_depth: for validate_references(), which checks every id a kernel will follow on the host before anything is
+    // launched; packet_ok: the tree fits the packet kernels' packed entries (packet_kernel_limits)
+    struct BlasHost { std::vector<DevBuf> arrays; int max_local_material = -1, inner_depth = -1; bool packet_ok = true; BlasRefit refit; BlasBuild build; };
     std::vector<DevBlas> h_blas;
-    std::vector<std::vector<void *>> blas_allocs;
+    std::vector<BlasHost> blas;
     DevBuf d_blas, d_materials, d_textures, d_sky, d_ewa;
     std::vector<DevTexture> h_tex;
-    std::vector<void *> tex_allocs;
+    std::vector<DevBuf> tex_texels;             // per texture id, beside h_tex
     int material_count = 0, sky_size = 0;
-    // host copies for validate_references(): every id a kernel will follow is checked on the host before anything is launched
-    std::vector<rtx_material> h_materials; std::vector<int> blas_max_local_material, blas_inner_depth, blas_packet_ok; int tlas_inner_depth = -1; std::vector<int> frame_primitive_materials; bool refs_dirty = true; Knobs knobs; int item_blocks = 0, item_cap_alloc = 0; DevBuf d_pk_items, d_pk_item_count;
+    std::vector<rtx_material> h_materials; int tlas_inner_depth = -1; std::vector<int> frame_primitive_materials; bool refs_dirty = true; Knobs knobs; int item_blocks = 0, item_cap_alloc = 0; DevBuf d_pk_items, d_pk_item_count;
 
     // per-frame state (rtx_set_frame): ONE device block, filled by one asynchronous copy on the context's stream from a ring of pinned
-    // staging buffers — the host never waits for the GPU between frames (cfg5: Scene::update + TLAS rebuild every frame)
+    // staging buffers (stage_copy) — the host never waits for the GPU between frames (cfg5: Scene::update + TLAS rebuild every frame)
     DevBuf d_frame;
-    struct FrameStage { void * host = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool pending = false; } stage[3];
-    int stage_next = 0;
+    StageRing frame_ring;
     DevScene scene;
     bool frame_set = false;
     // rtx_update_instances: a device block of its own for the updated instances / TLAS (both node layouts) / indices and the builder's scratch
     // (AABBs, bounds, keys), grown only; the DevScene pointers are switched to it, the rest of the frame stays in d_frame.  d_upd_sort = rocPRIM's
     // temporary storage and the unsorted keys (multi-launch path), grown only
     DevBuf d_upd, d_upd_sort; int upd_cap = 0;
-    // rtx_bind_blas_vertices / rtx_refit_blas, per BLAS id: the record-slot -> node maps of the 4-wide layouts as rtx_upload_blas laid them out
-    // (empty: binary walk), and once bound the kernel arguments of a refit — the plan's device block belongs to blas_allocs[id], so uploading
-    // the id again releases it with the arrays
-    struct BlasRefit { std::vector<int32_t> map4, map4c; bool bound = false; int32_t vertex_count = 0; DevRefit dev; float * planes[3] = { nullptr, nullptr, nullptr }; void * sort_tmp = nullptr; size_t sort_bytes = 0; };
-    std::vector<BlasRefit> refit;
-    // rtx_alloc_blas / rtx_build_blas, per BLAS id: the kernel arguments of a build (scratch in a block of blas_allocs[id], like the refit plan)
-    struct BlasBuild { bool allocated = false; DevBuild dev; void * sort_tmp = nullptr; size_t sort_bytes = 0; int levels = 0; };
-    std::vector<BlasBuild> build;
-    // rtx_set_views: the cameras of a batch of views (device array, grown only, filled by a stream-ordered copy from a ring of pinned
-    // staging buffers like the frame block) and the view framebuffer (view_fb_cap views, allocated on first use, grown only) or the
-    // caller's buffers of ext_vcap views (rtx_bind_view_framebuffer)
+    // rtx_set_views: the cameras of a batch of views (device array, grown only, filled through a staging ring of its own like the frame block)
+    // and the view framebuffer (vfb_cap views, allocated on first use, grown only) or the caller's buffers of ext_vcap views
+    // (rtx_bind_view_framebuffer)
     DevBuf d_views, d_vfb_rgb, d_vfb_packed;
-    FrameStage vstage[3];
-    int vstage_next = 0;
+    StageRing view_ring;
     int32_t view_count = 0, vfb_cap = 0, ext_vcap = 0;
     void * ext_vrgb = nullptr, * ext_vpacked = nullptr;
-    // ray views (rtx_set_rays / rtx_bind_rays): the context's own ray buffer of ray_count views (grown only, filled through a ring of pinned
-    // staging buffers like the cameras) or the caller's device buffer of ext_ray_count views; independent of the rtx_set_views state
+    // ray views (rtx_set_rays / rtx_bind_rays): the context's own ray buffer of ray_count views (grown only, filled through a staging ring of
+    // its own like the cameras) or the caller's device buffer of ext_ray_count views; independent of the rtx_set_views state
     DevBuf d_rays;
-    FrameStage rstage[3];
-    int rstage_next = 0;
+    StageRing ray_ring;
     int32_t ray_count = 0, ext_ray_count = 0;
     const void * ext_rays = nullptr;
     // rtx_bind_aovs: the bound channels (RTX_AOV_* bits) and where they go: the caller's device buffers of aov_ext_cap pixels (aov_ext), or
@@ -142,7 +138,6 @@ struct rtx_ctx {
 
     rtx_stats stats_acc; rtx_work_counters work_acc; uint32_t err_flags_acc = 0;
     bool stats_pending = false;
-    std::vector<DevCounters *> pending_host;   // pinned copies, one per batch
 
     bool timing = false;
     bool serial = false;                 // RTX_RENDER_SERIAL: keep every kernel on one stream (per-kernel timings without overlap)
@@ -154,25 +149,6 @@ struct rtx_ctx {
     std::vector<hipEvent_t> event_pool;
     size_t event_next = 0;
 };
-
-#define HIP_OK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); return RTX_ERR_HIP; } } while (0)
-
-static int ensure(rtx_ctx * c, DevBuf & b, size_t bytes) {
-    if (bytes <= b.cap && b.p) return RTX_OK;
-    if (b.p) { hipFree(b.p); b.p = nullptr; b.cap = 0; }
-    if (bytes == 0) bytes = 16;
-    hipError_t e = hipMalloc(&b.p, bytes);
-    if (e != hipSuccess) { c->err = std::string("hipMalloc: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP; }
-    b.cap = bytes;
-    return RTX_OK;
-}
-
-static int upload(rtx_ctx * c, DevBuf & b, const void * src, size_t bytes) {
-    int rc = ensure(c, b, bytes);
-    if (rc) return rc;
-    if (bytes) HIP_OK(c, hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
-    return RTX_OK;
-}
 
 static void convert_nodes(const rtx_bvh_node * nodes, int n, std::vector<float4> & out) {
     out.resize((size_t)2 * (n > 0 ? n : 1));
@@ -445,18 +421,7 @@ extern "C" int rtx_destroy(rtx_ctx * c) {
     if (!c) return RTX_ERR_INVALID_ARG;
     hipSetDevice(c->cfg.device);
     if (c->stream) hipStreamSynchronize(c->stream);
-    for (auto & v : c->blas_allocs) for (void * p : v) hipFree(p);
-    for (void * p : c->tex_allocs) if (p) hipFree(p);
-    DevBuf * bufs[] = { &c->d_blas, &c->d_materials, &c->d_textures, &c->d_sky, &c->d_ewa, &c->d_frame, &c->d_counters, &c->d_spill, &c->d_fb_rgb, &c->d_fb_packed, &c->d_display, &c->d_gamma, &c->d_pk_heads, &c->d_pk_fifo, &c->d_pk_items, &c->d_pk_item_count, &c->d_stats_partial, &c->d_dbg_s0, &c->d_dbg_s1, &c->d_pk_cost, &c->d_pk_order, &c->d_views, &c->d_vfb_rgb, &c->d_vfb_packed, &c->d_rays, &c->d_upd, &c->d_upd_sort };
-    for (DevBuf * b : bufs) if (b->p) hipFree(b->p);
-    for (DevBuf & b : c->d_aov) if (b.p) hipFree(b.p);
-    for (DevBuf & b : c->qb) if (b.p) hipFree(b.p);
-    for (DevBuf * b : { &c->d_query[0], &c->d_query[1], &c->d_query[2], &c->d_query[3], &c->d_query_counters, &c->d_query_heads }) if (b->p) hipFree(b->p);
     for (hipEvent_t e : c->event_pool) hipEventDestroy(e);
-    for (DevCounters * h : c->pending_host) hipHostFree(h);
-    for (auto & st : c->stage) { if (st.host) hipHostFree(st.host); if (st.done) hipEventDestroy(st.done); }
-    for (auto & st : c->vstage) { if (st.host) hipHostFree(st.host); if (st.done) hipEventDestroy(st.done); }
-    for (auto & st : c->rstage) { if (st.host) hipHostFree(st.host); if (st.done) hipEventDestroy(st.done); }
     if (c->graph_exec) { hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
     if (c->order_stream) { hipStreamSynchronize(c->order_stream); hipStreamDestroy(c->order_stream); hipEventDestroy(c->ev_cost); hipEventDestroy(c->ev_order); }
     if (c->any_stream) { hipStreamSynchronize(c->any_stream); hipStreamDestroy(c->any_stream); }
@@ -464,7 +429,7 @@ extern "C" int rtx_destroy(rtx_ctx * c) {
     if (c->ev_shade_last) hipEventDestroy(c->ev_shade_last);
     if (c->ev_any_done) hipEventDestroy(c->ev_any_done);
     if (c->own_stream) hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;                            // the device is current: every DevBuf and StageRing of the context releases its memory here
     return RTX_OK;
 }
 
@@ -490,19 +455,58 @@ static bool validate_tree(const rtx_bvh_node * nodes, int node_count, int64_t pr
 }
 
 
+// ---- BLAS upload: stage, then commit -----------------------------------------------------------------------------------------------
+// Everything an id will hold is built into a BlasStaged first, which owns its allocations; commit_blas swaps it in.  A call that is refused
+// or fails on the way therefore leaves the id as it was (or empty), and what it had allocated dies with the staged record.
+struct BlasStaged { DevBlas B; rtx_ctx::BlasHost H; };
+
+// one more device array of a staged mesh: `bytes` allocated, the first `copy` filled from src
+template <typename T> static int stage_array(rtx_ctx * c, std::vector<DevBuf> & arrays, const void * src, size_t copy, size_t bytes, const T ** out) {
+    DevBuf b;
+    if (int rc = ensure(c, b, bytes)) return rc;
+    if (copy) HIP_OK(c, hipMemcpy(b.p, src, copy, hipMemcpyHostToDevice));
+    *out = (const T *)b.p;
+    arrays.push_back(std::move(b));
+    return RTX_OK;
+}
+
+// the device table follows h_blas.  A table that has to grow is built beside the old one, which a failure leaves in place.
+static int upload_blas_table(rtx_ctx * c) {
+    const size_t bytes = c->h_blas.size() * sizeof(DevBlas);
+    if (bytes <= c->d_blas.cap && c->d_blas.p) return upload(c, c->d_blas, c->h_blas.data(), bytes);
+    DevBuf nb;
+    if (int rc = upload(c, nb, c->h_blas.data(), bytes)) return rc;
+    c->d_blas = std::move(nb);
+    return RTX_OK;
+}
+
+// The one place an id's state changes hands.  Queued work may still read the old arrays and the table: it is waited for explicitly, then the
+// table is uploaded with the new entry, and only then does the old record — arrays, refit plan, build scratch — go.
+static int commit_blas(rtx_ctx * c, int32_t blas_id, BlasStaged & S) {
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    const size_t had = c->h_blas.size();
+    if ((size_t)blas_id >= had) { DevBlas none; memset(&none, 0, sizeof(none)); c->h_blas.resize(blas_id + 1, none); c->blas.resize(blas_id + 1); }
+    const DevBlas old = c->h_blas[blas_id];
+    c->h_blas[blas_id] = S.B;
+    if (int rc = upload_blas_table(c)) { c->h_blas[blas_id] = old; c->h_blas.resize(had); c->blas.resize(had); return rc; }
+    c->blas[blas_id] = std::move(S.H);
+    c->refs_dirty = true;
+    return RTX_OK;
+}
+
+// All checks, then all allocations and copies, into S; the context is only read.
 // pk4_order: the slot order of the 4-wide shadow-ray records (build_nodes_pk4): the context's knob for rtx_upload_blas, 0 for rtx_alloc_blas
-static int upload_blas_impl(rtx_ctx * c, int32_t blas_id, const rtx_bvh_node * nodes, int32_t node_count,
-                            const rtx_triangle_hot * tri_hot, const rtx_triangle_cold * tri_cold,
-                            int32_t triangle_count, int32_t material_offset, int pk4_order) {
+static int stage_blas(rtx_ctx * c, int32_t blas_id, const rtx_bvh_node * nodes, int32_t node_count,
+                      const rtx_triangle_hot * tri_hot, const rtx_triangle_cold * tri_cold,
+                      int32_t triangle_count, int32_t material_offset, int pk4_order, BlasStaged & S) {
     if (!c || blas_id < 0 || blas_id >= (1 << 20) || !nodes || node_count <= 0 || triangle_count < 0 || (triangle_count > 0 && (!tri_hot || !tri_cold)))
         return RTX_ERR_INVALID_ARG;
-    hipSetDevice(c->cfg.device);
     // every leaf must address triangles inside the arrays, every inner node children inside the node array
     int inner_depth = -1, leaf_max = 0;
     if (!validate_tree(nodes, node_count, triangle_count, &inner_depth, &leaf_max)) return RTX_ERR_INVALID_ARG;
-    if ((size_t)blas_id >= c->h_blas.size()) { c->h_blas.resize(blas_id + 1); c->blas_allocs.resize(blas_id + 1); for (auto & b : c->h_blas) if (!b.nodes) memset(&b, 0, sizeof(b)); }
-    for (void * p : c->blas_allocs[blas_id]) hipFree(p);
-    c->blas_allocs[blas_id].clear();
+    int max_local = -1;
+    for (int i = 0; i < triangle_count; i++) { if (tri_cold[i].material_id < 0) return RTX_ERR_INVALID_ARG; if (tri_cold[i].material_id > max_local) max_local = tri_cold[i].material_id; }
+    hipSetDevice(c->cfg.device);
 
     std::vector<float4> nd; convert_nodes(nodes, node_count, nd);
     std::vector<float4> th((size_t)RTX_TRI_STRIDE * (triangle_count > 0 ? triangle_count : 1), make_float4(0.0f, 0.0f, 0.0f, 0.0f));
@@ -512,15 +516,13 @@ static int upload_blas_impl(rtx_ctx * c, int32_t blas_id, const rtx_bvh_node * n
         th[RTX_TRI_STRIDE * (size_t)i + 2] = make_float4(tri_hot[i].position_edge_2[0], tri_hot[i].position_edge_2[1], tri_hot[i].position_edge_2[2], 0.0f);
     }
     std::vector<float4> ndp; convert_nodes_pk(nodes, node_count, ndp);
-    if (c->refit.size() <= (size_t)blas_id) c->refit.resize(blas_id + 1);
-    c->refit[blas_id] = rtx_ctx::BlasRefit();                      // uploading an id drops its vertex binding (the plan's block was freed above)
-    if (c->build.size() <= (size_t)blas_id) c->build.resize(blas_id + 1);
-    c->build[blas_id] = rtx_ctx::BlasBuild();                      // and what rtx_alloc_blas made of it
+    rtx_ctx::BlasHost & H = S.H;
     std::vector<float4> nd4; int need4 = 0;
-    std::vector<int32_t> map4, map4c;
-    const bool wide = !c->knobs.no_wide && build_nodes_pk4(nodes, node_count, triangle_count, nd4, &need4, pk4_order, &map4) && need4 <= RTX_PK4_MAX_NEED;
+    const bool wide = !c->knobs.no_wide && build_nodes_pk4(nodes, node_count, triangle_count, nd4, &need4, pk4_order, &H.refit.map4) && need4 <= RTX_PK4_MAX_NEED;
     std::vector<float4> nd4c; int need4c = 0;
-    const bool wide_closest = !c->knobs.no_wide_closest && build_nodes_pk4c(nodes, node_count, triangle_count, nd4c, &need4c, &map4c) && need4c <= RTX_MAX_STACK - 2;
+    const bool wide_closest = !c->knobs.no_wide_closest && build_nodes_pk4c(nodes, node_count, triangle_count, nd4c, &need4c, &H.refit.map4c) && need4c <= RTX_MAX_STACK - 2;
+    if (!wide) H.refit.map4.clear();
+    if (!wide_closest) H.refit.map4c.clear();
     // the distinct box-plane coordinates per axis, ascending: a ray with a zero direction component can only produce a NaN in a slab test
     // (0 * inf) if its origin lies exactly on one of them (pk_nan_possible, rtx_packet.h)
     std::vector<float> planes[3];
@@ -532,40 +534,31 @@ static int upload_blas_impl(rtx_ctx * c, int32_t blas_id, const rtx_bvh_node * n
         planes[a].erase(std::unique(planes[a].begin(), planes[a].end()), planes[a].end());      // +0 and -0 compare equal: one entry
         if (planes[a].empty()) planes[a].push_back(INFINITY);
     }
-    void * dn = nullptr, * dt = nullptr, * dc = nullptr, * dnp = nullptr, * dn4 = nullptr, * dn4c = nullptr, * dpl[3] = { nullptr, nullptr, nullptr };
-    for (int a = 0; a < 3; a++) { HIP_OK(c, hipMalloc(&dpl[a], planes[a].size() * 4)); c->blas_allocs[blas_id].push_back(dpl[a]); HIP_OK(c, hipMemcpy(dpl[a], planes[a].data(), planes[a].size() * 4, hipMemcpyHostToDevice)); }
-    if (wide_closest) { HIP_OK(c, hipMalloc(&dn4c, nd4c.size() * 16)); c->blas_allocs[blas_id].push_back(dn4c); HIP_OK(c, hipMemcpy(dn4c, nd4c.data(), nd4c.size() * 16, hipMemcpyHostToDevice)); }
-    if (wide) { HIP_OK(c, hipMalloc(&dn4, nd4.size() * 16)); c->blas_allocs[blas_id].push_back(dn4); HIP_OK(c, hipMemcpy(dn4, nd4.data(), nd4.size() * 16, hipMemcpyHostToDevice)); }
-    HIP_OK(c, hipMalloc(&dn, nd.size() * 16)); c->blas_allocs[blas_id].push_back(dn);
-    HIP_OK(c, hipMalloc(&dnp, ndp.size() * 16)); c->blas_allocs[blas_id].push_back(dnp);
-    HIP_OK(c, hipMemcpy(dnp, ndp.data(), ndp.size() * 16, hipMemcpyHostToDevice));
-    HIP_OK(c, hipMalloc(&dt, th.size() * 16)); c->blas_allocs[blas_id].push_back(dt);
-    HIP_OK(c, hipMalloc(&dc, (size_t)(triangle_count > 0 ? triangle_count : 1) * sizeof(rtx_triangle_cold))); c->blas_allocs[blas_id].push_back(dc);
-    HIP_OK(c, hipMemcpy(dn, nd.data(), nd.size() * 16, hipMemcpyHostToDevice));
-    HIP_OK(c, hipMemcpy(dt, th.data(), th.size() * 16, hipMemcpyHostToDevice));
-    if (triangle_count) HIP_OK(c, hipMemcpy(dc, tri_cold, (size_t)triangle_count * sizeof(rtx_triangle_cold), hipMemcpyHostToDevice));
-    if (c->blas_max_local_material.size() <= (size_t)blas_id) c->blas_max_local_material.resize(blas_id + 1, -1);
-    int max_local = -1;
-    for (int i = 0; i < triangle_count; i++) { if (tri_cold[i].material_id < 0) return RTX_ERR_INVALID_ARG; if (tri_cold[i].material_id > max_local) max_local = tri_cold[i].material_id; }
-    c->blas_max_local_material[blas_id] = max_local; c->refs_dirty = true;
-    if (c->blas_inner_depth.size() <= (size_t)blas_id) { c->blas_inner_depth.resize(blas_id + 1, -1); c->blas_packet_ok.resize(blas_id + 1, 1); }
-    c->blas_inner_depth[blas_id] = inner_depth;
-    // the packet kernels pack stack entries and address nodes / triangles with 32-bit byte offsets (rtx_packet.h)
-    c->blas_packet_ok[blas_id] = (leaf_max < 65536 && node_count < (1 << 26) && triangle_count < (1 << 25)) ? 1 : 0;
-    DevBlas & B = c->h_blas[blas_id];
-    B.nodes = (const float4 *)dn; B.pk_nodes = (const float4 *)dnp; B.tri_hot = (const float4 *)dt; B.tri_cold = (const rtx_triangle_cold *)dc;
-    B.pk4_nodes = (const float4 *)dn4; B.pk4c_nodes = (const float4 *)dn4c;
-    for (int a = 0; a < 3; a++) { B.planes[a] = (const float *)dpl[a]; B.plane_count[a] = (int32_t)planes[a].size(); }
+    DevBlas & B = S.B;
+    memset(&B, 0, sizeof(B));
+    int rc = RTX_OK;
+    for (int a = 0; a < 3 && !rc; a++) { rc = stage_array(c, H.arrays, planes[a].data(), planes[a].size() * 4, planes[a].size() * 4, &B.planes[a]); B.plane_count[a] = (int32_t)planes[a].size(); }
+    if (!rc && wide_closest) rc = stage_array(c, H.arrays, nd4c.data(), nd4c.size() * 16, nd4c.size() * 16, &B.pk4c_nodes);
+    if (!rc && wide) rc = stage_array(c, H.arrays, nd4.data(), nd4.size() * 16, nd4.size() * 16, &B.pk4_nodes);
+    if (!rc) rc = stage_array(c, H.arrays, nd.data(), nd.size() * 16, nd.size() * 16, &B.nodes);
+    if (!rc) rc = stage_array(c, H.arrays, ndp.data(), ndp.size() * 16, ndp.size() * 16, &B.pk_nodes);
+    if (!rc) rc = stage_array(c, H.arrays, th.data(), th.size() * 16, th.size() * 16, &B.tri_hot);
+    if (!rc) rc = stage_array(c, H.arrays, tri_cold, (size_t)triangle_count * sizeof(rtx_triangle_cold), (size_t)(triangle_count > 0 ? triangle_count : 1) * sizeof(rtx_triangle_cold), &B.tri_cold);
+    if (rc) return rc;
     B.node_count = node_count; B.tri_count = triangle_count; B.material_offset = material_offset; B.pk4_need = wide ? need4 : -1; B.pk4c_need = wide_closest ? need4c : -1;
-    if (wide) c->refit[blas_id].map4.swap(map4);
-    if (wide_closest) c->refit[blas_id].map4c.swap(map4c);
-    return upload(c, c->d_blas, c->h_blas.data(), c->h_blas.size() * sizeof(DevBlas));
+    H.max_local_material = max_local;
+    H.inner_depth = inner_depth;
+    // the packet kernels pack stack entries and address nodes / triangles with 32-bit byte offsets (rtx_packet.h)
+    H.packet_ok = leaf_max < 65536 && node_count < (1 << 26) && triangle_count < (1 << 25);
+    return RTX_OK;
 }
 
 extern "C" int rtx_upload_blas(rtx_ctx * c, int32_t blas_id, const rtx_bvh_node * nodes, int32_t node_count,
                                const rtx_triangle_hot * tri_hot, const rtx_triangle_cold * tri_cold,
                                int32_t triangle_count, int32_t material_offset) {
-    return upload_blas_impl(c, blas_id, nodes, node_count, tri_hot, tri_cold, triangle_count, material_offset, c ? c->knobs.pk4_order : 0);
+    BlasStaged S;      // uploading an id drops its vertex binding and what rtx_alloc_blas made of it: the staged record has neither
+    if (int rc = stage_blas(c, blas_id, nodes, node_count, tri_hot, tri_cold, triangle_count, material_offset, c ? c->knobs.pk4_order : 0, S)) return rc;
+    return commit_blas(c, blas_id, S);
 }
 
 extern "C" int rtx_upload_materials(rtx_ctx * c, const rtx_material * materials, int32_t count) {
@@ -585,21 +578,17 @@ extern "C" int rtx_upload_texture(rtx_ctx * c, int32_t texture_id, const rtx_tex
         if (lw < 1 || lh < 1 || desc->mip_offsets[l] < 0 || desc->mip_offsets[l] + lw * lh > texel_count) return RTX_ERR_INVALID_ARG;
     }
     hipSetDevice(c->cfg.device);
-    if ((size_t)texture_id >= c->h_tex.size()) { size_t old = c->h_tex.size(); c->h_tex.resize(texture_id + 1); for (size_t i = old; i < c->h_tex.size(); i++) memset(&c->h_tex[i], 0, sizeof(DevTexture)); }
-    void * d = nullptr;
-    HIP_OK(c, hipMalloc(&d, (size_t)texel_count * 16));
-    if (c->h_tex[texture_id].texels) {            // re-upload of an id: the old texel array is released (after the frames that may still read it)
-        HIP_OK(c, hipStreamSynchronize(c->stream));
-        for (void *& p : c->tex_allocs) if (p == (void *)c->h_tex[texture_id].texels) { hipFree(p); p = nullptr; }
-    }
-    c->tex_allocs.push_back(d);
+    if ((size_t)texture_id >= c->h_tex.size()) { size_t old = c->h_tex.size(); c->h_tex.resize(texture_id + 1); c->tex_texels.resize(texture_id + 1); for (size_t i = old; i < c->h_tex.size(); i++) memset(&c->h_tex[i], 0, sizeof(DevTexture)); }
+    DevBuf d;
     {   // float3 texels of the ABI -> one float4 per texel on the device
         std::vector<float4> padded((size_t)texel_count);
         for (int64_t i = 0; i < texel_count; i++) padded[(size_t)i] = make_float4(texels_rgb[3 * i], texels_rgb[3 * i + 1], texels_rgb[3 * i + 2], 0.0f);
-        HIP_OK(c, hipMemcpy(d, padded.data(), (size_t)texel_count * 16, hipMemcpyHostToDevice));
+        if (int rc = upload(c, d, padded.data(), (size_t)texel_count * 16)) return rc;
     }
+    if (c->h_tex[texture_id].texels) HIP_OK(c, hipStreamSynchronize(c->stream));      // re-upload of an id: the old texel array is released after the frames that may still read it
     c->h_tex[texture_id].desc = *desc;
-    c->h_tex[texture_id].texels = (const float4 *)d;
+    c->h_tex[texture_id].texels = (const float4 *)d.p;
+    c->tex_texels[texture_id] = std::move(d);
     c->refs_dirty = true;
     return upload(c, c->d_textures, c->h_tex.data(), c->h_tex.size() * sizeof(DevTexture));
 }
@@ -647,19 +636,9 @@ extern "C" int rtx_set_frame(rtx_ctx * c, const rtx_frame * f) {
         rc = ensure(c, c->d_frame, total + total / 2);
         if (rc) return rc;
     }
-    rtx_ctx::FrameStage & st = c->stage[c->stage_next]; c->stage_next = (c->stage_next + 1) % 3;
-    if (st.pending) { HIP_OK(c, hipEventSynchronize(st.done)); st.pending = false; }      // two frames back: long finished in steady state
-    if (total > st.cap) {
-        if (st.host) hipHostFree(st.host);
-        st.host = nullptr; st.cap = 0;
-        HIP_OK(c, hipHostMalloc(&st.host, total + total / 2, hipHostMallocDefault)); st.cap = total + total / 2;
-    }
-    if (!st.done) HIP_OK(c, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
-    for (int k = 0; k < 9; k++) if (len[k]) memcpy((char *)st.host + off[k], src[k], len[k]);
-    HIP_OK(c, hipMemcpyAsync(c->d_frame.p, st.host, total, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(c, hipEventRecord(st.done, c->stream)); st.pending = true;
-    char * const fb = (char *)c->d_frame.p;
+    rc = stage_copy(c, c->frame_ring, c->d_frame.p, total, total + total / 2, [&](void * host) { for (int k = 0; k < 9; k++) if (len[k]) memcpy((char *)host + off[k], src[k], len[k]); });
     if (rc) return rc;
+    char * const fb = (char *)c->d_frame.p;
 
     DevScene & s = c->scene;
     s.width = c->cfg.width; s.height = c->cfg.height; s.bounces = c->cfg.bounces; s.stack_size = c->cfg.stack_size;
@@ -701,7 +680,7 @@ static int validate_references(rtx_ctx * c) {
     for (int id : c->frame_primitive_materials) if (id < 0 || id >= nm) { c->err = "sphere / plane material id outside the uploaded material table"; return RTX_ERR_STATE; }
     for (size_t b = 0; b < c->h_blas.size(); b++) {
         if (!c->h_blas[b].nodes) continue;
-        const int hi = b < c->blas_max_local_material.size() ? c->blas_max_local_material[b] : -1;
+        const int hi = c->blas[b].max_local_material;
         if (c->h_blas[b].material_offset < 0 || (hi >= 0 && (long long)c->h_blas[b].material_offset + hi >= nm)) { c->err = "BLAS material_offset + triangle material id outside the uploaded material table"; return RTX_ERR_STATE; }
     }
     // BVH_TRAVERSAL_STACK_SIZE (Config.h:25).  The reference's per-BVH stack holds one pending sibling per ancestor entered through its near
@@ -710,8 +689,8 @@ static int validate_references(rtx_ctx * c) {
     // for every ray alike.  The per-lane kernels' stacks (64 entries per BVH) can then never overflow; the packet kernels share one 64-entry
     // stack between TLAS and BLAS, and render_tiles_impl hands scenes that could exceed it to the per-lane kernels.
     for (size_t b = 0; b < c->h_blas.size(); b++)
-        if (c->h_blas[b].nodes && b < c->blas_inner_depth.size() && c->blas_inner_depth[b] + 2 > c->cfg.stack_size) {
-            c->err = "BVH deeper than rtx_config.stack_size allows (BVH_TRAVERSAL_STACK_SIZE, Config.h:25): an inner node at depth " + std::to_string(c->blas_inner_depth[b]) + " needs " + std::to_string(c->blas_inner_depth[b] + 2) + " stack entries";
+        if (c->h_blas[b].nodes && c->blas[b].inner_depth + 2 > c->cfg.stack_size) {
+            c->err = "BVH deeper than rtx_config.stack_size allows (BVH_TRAVERSAL_STACK_SIZE, Config.h:25): an inner node at depth " + std::to_string(c->blas[b].inner_depth) + " needs " + std::to_string(c->blas[b].inner_depth + 2) + " stack entries";
             return RTX_ERR_LIMIT;
         }
     if (c->tlas_inner_depth + 2 > c->cfg.stack_size) { c->err = "TLAS deeper than rtx_config.stack_size allows (BVH_TRAVERSAL_STACK_SIZE, Config.h:25)"; return RTX_ERR_LIMIT; }
@@ -818,6 +797,31 @@ static void launch_timed(rtx_ctx * c, const char * name, hipStream_t stream, F &
     } else launch();
 }
 
+// k_begin_batch with the context's grid sizes: plain = the batch is traced by the plain kernels (one grid for both ray kinds)
+static void begin_batch(rtx_ctx * c, DevCounters * counters, uint32_t * pk_heads, uint32_t primary_slots, bool plain, bool first_batch) {
+    hipLaunchKernelGGL(k_begin_batch, dim3(1), dim3(64), 0, c->stream, counters, pk_heads, primary_slots,
+                       (uint32_t)((plain ? c->trace_blocks_count : c->trace_blocks_closest) * RTX_TRACE_BLOCK),
+                       (uint32_t)((plain ? c->trace_blocks_count : c->trace_blocks_any) * RTX_TRACE_BLOCK),
+                       (uint32_t)(c->pk_blocks_closest * (RTX_PK_BLOCK / RTX_WAVE)), (uint32_t)(c->pk_blocks_any * (RTX_PK_BLOCK / RTX_WAVE)), first_batch ? 1 : 0);
+}
+
+// the two launches a ray query and its debug hook share: the level-1 closest-hit walk and the level-0 shadow-ray walk, per lane or by packets
+static void launch_closest_level1(rtx_ctx * c, const DevScene & sc, const DevQueues & q, bool lane) {
+    if (lane) hipLaunchKernelGGL((k_trace_fast<false>), dim3(c->trace_blocks_closest), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, 1, 1);
+    else      hipLaunchKernelGGL((k_packet<false, false>), dim3(c->pk_blocks_closest), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, 1, 1);
+}
+static void launch_any_level0(rtx_ctx * c, const DevScene & sc, const DevQueues & q, bool lane) {
+    if (lane) hipLaunchKernelGGL((k_trace_fast<true>), dim3(c->trace_blocks_any), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, 0, 0);
+    else      hipLaunchKernelGGL((k_packet<true, false>), dim3(c->pk_blocks_any), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, 0, 0);
+}
+
+// tiles of one frame (Window.cpp:11), and whether every uploaded mesh has 4-wide shadow-ray records (the split walk needs them)
+static int32_t frame_tiles(const rtx_ctx * c) { return ((c->cfg.width + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE) * ((c->cfg.height + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE); }
+static bool all_meshes_wide(const rtx_ctx * c) {
+    for (const DevBlas & b : c->h_blas) if (b.nodes && !b.pk4_nodes) return false;
+    return true;
+}
+
 // ---- device-side scene update (include/rtx.h: rtx_update_instances / rtx_read_frame_state; kernels in rtx_update.h) -------------------
 // The instance records, the TLAS in both node layouts and its indices are rebuilt from poses in device memory into a block of their own
 // (d_upd), and the DevScene pointers are switched to it; spheres, planes, lights and the camera stay where rtx_set_frame put them.  Everything
@@ -917,7 +921,7 @@ extern "C" int rtx_read_frame_state(rtx_ctx * c, rtx_instance * instances, rtx_b
 }
 
 // ---- device-side mesh refit (include/rtx.h: rtx_bind_blas_vertices / rtx_refit_blas / rtx_read_blas; kernels in rtx_refit.h) -----------
-// Everything the host decides from a BLAS before a launch (blas_inner_depth, blas_packet_ok, pk4_need / pk4c_need, the packet-stack rule,
+// Everything the host decides from a BLAS before a launch (inner_depth, packet_ok, pk4_need / pk4c_need, the packet-stack rule,
 // the kernel choice per level) depends on its topology, which a refit keeps: so a refit is queued on the context's stream like
 // rtx_update_instances and nothing is read back.  The arrays are written in place and the DevBlas table is not touched after the bind, so
 // work queued before reads the old mesh, the next render call the new one, and a captured graph stays valid.
@@ -939,36 +943,18 @@ static int refit_launch_finish(rtx_ctx * c, rtx_ctx::BlasRefit & R, bool build =
     return RTX_OK;
 }
 
-// the table as given: rtx_bind_blas_vertices has validated it, rtx_alloc_blas hands in -1 everywhere (every triangle invalid until a build)
-static int bind_blas_impl(rtx_ctx * c, int32_t blas_id, const int32_t * slot_vertices, int32_t vertex_count);
-
-extern "C" int rtx_bind_blas_vertices(rtx_ctx * c, int32_t blas_id, const int32_t * slot_vertices, int32_t vertex_count) {
-    if (!c) return RTX_ERR_INVALID_ARG;
-    if (!slot_vertices || blas_id < 0 || blas_id >= (1 << 20) || vertex_count < 1) { c->err = "rtx_bind_blas_vertices: null index table, bad id or no vertices"; return RTX_ERR_INVALID_ARG; }
-    if ((size_t)blas_id >= c->h_blas.size() || !c->h_blas[blas_id].nodes) { c->err = "rtx_bind_blas_vertices: no BLAS uploaded under that id"; return RTX_ERR_STATE; }
-    const int64_t T3 = 3 * (int64_t)c->h_blas[blas_id].tri_count;
-    for (int64_t k = 0; k < T3; k++) if (slot_vertices[k] < 0 || slot_vertices[k] >= vertex_count) {
-        c->err = "rtx_bind_blas_vertices: vertex index outside [0, vertex_count)"; return RTX_ERR_INVALID_ARG; }
-    return bind_blas_impl(c, blas_id, slot_vertices, vertex_count);
-}
-
-static int bind_blas_impl(rtx_ctx * c, int32_t blas_id, const int32_t * slot_vertices, int32_t vertex_count) {
-    DevBlas & B = c->h_blas[blas_id];
+// The refit plan of a mesh: one device block, the kernel arguments that point into it, and the mesh's plane lists moved into it.  B and R are the
+// caller's staged copies (R carries the slot maps of the upload); nothing of the context is written, so a failure changes nothing and the
+// block dies with R.  The index table as given: rtx_bind_blas_vertices has validated it, rtx_alloc_blas hands in -1 everywhere (every
+// triangle invalid until a build).
+static int plan_refit(rtx_ctx * c, DevBlas & B, rtx_ctx::BlasRefit & R, const int32_t * slot_vertices, int32_t vertex_count) {
     const int n = B.node_count, T = B.tri_count;
-    hipSetDevice(c->cfg.device);
-    HIP_OK(c, hipStreamSynchronize(c->stream));                    // frames in flight read the tables this call replaces
-    rtx_ctx::BlasRefit & R = c->refit[blas_id];
-    if (R.bound) {                                                  // same arrays, same topology: only the index table changes
-        if (T) HIP_OK(c, hipMemcpy((void *)R.dev.slot_vertices, slot_vertices, (size_t)T * 12, hipMemcpyHostToDevice));
-        R.vertex_count = vertex_count;
-        return RTX_OK;
-    }
     // the topology as uploaded: the lane layout's words (a refit never writes them)
     std::vector<float4> nd((size_t)2 * n);
     HIP_OK(c, hipMemcpy(nd.data(), B.nodes, nd.size() * 16, hipMemcpyDeviceToHost));
     std::vector<int32_t> parent((size_t)n, RTX_REFIT_UNREACHABLE), stack(1, 0);
     parent[0] = -1;
-    while (!stack.empty()) {                                        // rtx_upload_blas validated the tree: in range, no node reachable twice
+    while (!stack.empty()) {                                        // the upload validated the tree: in range, no node reachable twice
         const int i = stack.back(); stack.pop_back();
         int32_t f, cw; memcpy(&f, &nd[2 * (size_t)i].w, 4); memcpy(&cw, &nd[2 * (size_t)i + 1].w, 4);
         if ((cw & 0x3fffffff) > 0) continue;
@@ -982,10 +968,8 @@ static int bind_blas_impl(rtx_ctx * c, int32_t blas_id, const int32_t * slot_ver
     const size_t len[12] = { (size_t)(T > 0 ? T : 1) * 12, (size_t)n * 4, (size_t)n * 4, R.map4.empty() ? 0 : slots * 4, R.map4c.empty() ? 0 : slots * 4, pl, pl, pl, pl, pl, pl, sort_bytes };
     size_t off[12], total = 0;
     for (int k = 0; k < 12; k++) { off[k] = total; total += (len[k] + 255) & ~(size_t)255; }
-    void * block = nullptr;
-    { hipError_t e = hipMalloc(&block, total); if (e != hipSuccess) { c->err = std::string("hipMalloc: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP; } }
-    c->blas_allocs[blas_id].push_back(block);
-    char * const bb = (char *)block;
+    if (int rc = ensure(c, R.block, total)) return rc;
+    char * const bb = (char *)R.block.p;
     if (T) HIP_OK(c, hipMemcpy(bb + off[0], slot_vertices, (size_t)T * 12, hipMemcpyHostToDevice));
     HIP_OK(c, hipMemcpy(bb + off[1], parent.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     HIP_OK(c, hipMemset(bb + off[2], 0, (size_t)n * 4));
@@ -1004,18 +988,46 @@ static int bind_blas_impl(rtx_ctx * c, int32_t blas_id, const int32_t * slot_ver
     // (which also rewrites the packet and wide boxes with the values they already have): duplicates and the planes of unreachable slots only
     // send a ray to the reference-form walker (plane_member is a lower-bound search)
     for (int a = 0; a < 3; a++) { R.planes[a] = (float *)(bb + off[8 + a]); B.planes[a] = R.planes[a]; B.plane_count[a] = 2 * n; }
-    if (int rc = refit_launch_finish(c, R)) return rc;
-    HIP_OK(c, hipStreamSynchronize(c->stream));
+    const int rc = refit_launch_finish(c, R);
+    const hipError_t waited = hipStreamSynchronize(c->stream);      // on failure too: what was queued writes the block the caller is about to drop
+    if (rc) return rc;
+    if (waited != hipSuccess) { c->err = std::string("hipStreamSynchronize: ") + hipGetErrorString(waited); return RTX_ERR_HIP; }
     R.bound = true; R.vertex_count = vertex_count;
-    return upload(c, c->d_blas, c->h_blas.data(), c->h_blas.size() * sizeof(DevBlas));
+    return RTX_OK;
+}
+
+extern "C" int rtx_bind_blas_vertices(rtx_ctx * c, int32_t blas_id, const int32_t * slot_vertices, int32_t vertex_count) {
+    if (!c) return RTX_ERR_INVALID_ARG;
+    if (!slot_vertices || blas_id < 0 || blas_id >= (1 << 20) || vertex_count < 1) { c->err = "rtx_bind_blas_vertices: null index table, bad id or no vertices"; return RTX_ERR_INVALID_ARG; }
+    if ((size_t)blas_id >= c->h_blas.size() || !c->h_blas[blas_id].nodes) { c->err = "rtx_bind_blas_vertices: no BLAS uploaded under that id"; return RTX_ERR_STATE; }
+    const int64_t T3 = 3 * (int64_t)c->h_blas[blas_id].tri_count;
+    for (int64_t k = 0; k < T3; k++) if (slot_vertices[k] < 0 || slot_vertices[k] >= vertex_count) {
+        c->err = "rtx_bind_blas_vertices: vertex index outside [0, vertex_count)"; return RTX_ERR_INVALID_ARG; }
+    hipSetDevice(c->cfg.device);
+    HIP_OK(c, hipStreamSynchronize(c->stream));                    // frames in flight read the tables this call replaces
+    rtx_ctx::BlasRefit & R = c->blas[blas_id].refit;
+    if (R.bound) {                                                  // same arrays, same topology: only the index table changes
+        if (T3) HIP_OK(c, hipMemcpy((void *)R.dev.slot_vertices, slot_vertices, (size_t)T3 * 4, hipMemcpyHostToDevice));
+        R.vertex_count = vertex_count;
+        return RTX_OK;
+    }
+    // the plan is made on copies and swapped in with the table: a failure leaves the id unbound, with the plane lists of its upload
+    DevBlas B = c->h_blas[blas_id];
+    rtx_ctx::BlasRefit N; N.map4 = R.map4; N.map4c = R.map4c;
+    if (int rc = plan_refit(c, B, N, slot_vertices, vertex_count)) return rc;
+    const DevBlas old = c->h_blas[blas_id];
+    c->h_blas[blas_id] = B;
+    if (int rc = upload_blas_table(c)) { c->h_blas[blas_id] = old; return rc; }
+    R = std::move(N);
+    return RTX_OK;
 }
 
 extern "C" int rtx_refit_blas(rtx_ctx * c, int32_t blas_id, const void * positions_dev, const void * normals_dev, int32_t vertex_count) {
     if (!c) return RTX_ERR_INVALID_ARG;
     if (!positions_dev || ((uintptr_t)positions_dev & 3) || ((uintptr_t)normals_dev & 3)) { c->err = "rtx_refit_blas: null or misaligned vertex pointer"; return RTX_ERR_INVALID_ARG; }
-    if (blas_id < 0 || (size_t)blas_id >= c->h_blas.size() || !c->h_blas[blas_id].nodes || !c->refit[blas_id].bound) {
+    if (blas_id < 0 || (size_t)blas_id >= c->h_blas.size() || !c->h_blas[blas_id].nodes || !c->blas[blas_id].refit.bound) {
         c->err = "rtx_refit_blas: no BLAS uploaded under that id, or no vertices bound to it (rtx_bind_blas_vertices)"; return RTX_ERR_STATE; }
-    rtx_ctx::BlasRefit & R = c->refit[blas_id];
+    rtx_ctx::BlasRefit & R = c->blas[blas_id].refit;
     if (vertex_count != R.vertex_count) { c->err = "rtx_refit_blas: vertex_count differs from the bound one"; return RTX_ERR_INVALID_ARG; }
     hipSetDevice(c->cfg.device);
     DevRefit & r = R.dev;
@@ -1028,7 +1040,7 @@ extern "C" int rtx_refit_blas(rtx_ctx * c, int32_t blas_id, const void * positio
 
 // ---- device-side mesh build (include/rtx.h: rtx_alloc_blas / rtx_build_blas; kernels in rtx_build.h) -----------------------------------
 // The balanced tree's topology is a function of the triangle count (rtx_build_math.h), so rtx_alloc_blas can do everything the host decides
-// from a BLAS before a launch — blas_inner_depth, blas_packet_ok, pk4_need / pk4c_need, the 4-wide slot orders and maps, the refit plan — once,
+// from a BLAS before a launch — inner_depth, packet_ok, pk4_need / pk4c_need, the 4-wide slot orders and maps, the refit plan — once,
 // by handing the topology with all-zero boxes (nested, min <= max) to the code rtx_upload_blas and rtx_bind_blas_vertices run.  A build is then
 // queued like a refit: it writes the arrays in place, touches no pointer and reads nothing back.
 static void balanced_topology(int T, std::vector<rtx_bvh_node> & nodes) {
@@ -1064,15 +1076,17 @@ extern "C" int rtx_alloc_blas(rtx_ctx * c, int32_t blas_id, int32_t triangle_cou
     const int T = triangle_count;
     std::vector<rtx_bvh_node> nodes;
     balanced_topology(T, nodes);
+    BlasStaged S;                                                   // mesh, refit plan and build scratch are staged together and committed as one
     {   // zeroed triangle arrays: a zero triangle is hit by no ray, so the mesh is empty and legal to render until the first build
         std::vector<rtx_triangle_hot> hot((size_t)T); std::vector<rtx_triangle_cold> cold((size_t)T);
         memset(hot.data(), 0, hot.size() * sizeof(rtx_triangle_hot)); memset(cold.data(), 0, cold.size() * sizeof(rtx_triangle_cold));
-        if (int rc = upload_blas_impl(c, blas_id, nodes.data(), (int32_t)nodes.size(), hot.data(), cold.data(), T, material_offset, 0)) return rc;
+        if (int rc = stage_blas(c, blas_id, nodes.data(), (int32_t)nodes.size(), hot.data(), cold.data(), T, material_offset, 0, S)) return rc;
     }
-    c->blas_max_local_material[blas_id] = max_local; c->refs_dirty = true;      // the ids a build will scatter into the cold records
+    S.H.max_local_material = max_local;                             // the ids a build will scatter into the cold records
+    HIP_OK(c, hipStreamSynchronize(c->stream));
     {
         std::vector<int32_t> sv((size_t)3 * T, -1);
-        if (int rc = bind_blas_impl(c, blas_id, sv.data(), vertex_count)) return rc;
+        if (int rc = plan_refit(c, S.B, S.H.refit, sv.data(), vertex_count)) return rc;
     }
     size_t sort_bytes = 0;
     if (rocprim::radix_sort_keys(nullptr, sort_bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr, (unsigned int)T, 0u, (unsigned int)RTXB_KEY_BITS, c->stream) != hipSuccess) {
@@ -1081,21 +1095,19 @@ extern "C" int rtx_alloc_blas(rtx_ctx * c, int32_t blas_id, int32_t triangle_cou
     const size_t len[5] = { (size_t)T * 4, 24, (size_t)T * 8, (size_t)T * 8, sort_bytes };
     size_t off[5], total = 0;
     for (int k = 0; k < 5; k++) { off[k] = total; total += (len[k] + 255) & ~(size_t)255; }
-    void * block = nullptr;
-    { hipError_t e = hipMalloc(&block, total); if (e != hipSuccess) { c->err = std::string("hipMalloc: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP; } }
-    c->blas_allocs[blas_id].push_back(block);
-    char * const bb = (char *)block;
+    rtx_ctx::BlasBuild & U = S.H.build;
+    if (int rc = ensure(c, U.block, total)) return rc;
+    char * const bb = (char *)U.block.p;
     if (material_ids) HIP_OK(c, hipMemcpy(bb + off[0], material_ids, (size_t)T * 4, hipMemcpyHostToDevice));
     else HIP_OK(c, hipMemset(bb + off[0], 0, (size_t)T * 4));
-    rtx_ctx::BlasBuild & U = c->build[blas_id];
     memset(&U.dev, 0, sizeof(U.dev));
     U.dev.material_ids = (const int32_t *)(bb + off[0]); U.dev.bounds = (uint32_t *)(bb + off[1]);
     U.dev.keys_in = (uint64_t *)(bb + off[2]); U.dev.keys = (uint64_t *)(bb + off[3]);
-    U.dev.slot_vertices = (int32_t *)c->refit[blas_id].dev.slot_vertices;
+    U.dev.slot_vertices = (int32_t *)S.H.refit.dev.slot_vertices;
     U.dev.tri_count = T; U.dev.vertex_count = vertex_count;
     U.sort_tmp = bb + off[4]; U.sort_bytes = sort_bytes; U.levels = rtxb::tree_levels(T);
     U.allocated = true;
-    return RTX_OK;
+    return commit_blas(c, blas_id, S);
 }
 
 extern "C" int rtx_build_blas(rtx_ctx * c, int32_t blas_id, const void * positions_dev, const void * indices_dev, const void * normals_dev,
@@ -1103,10 +1115,10 @@ extern "C" int rtx_build_blas(rtx_ctx * c, int32_t blas_id, const void * positio
     if (!c) return RTX_ERR_INVALID_ARG;
     if (!positions_dev || !indices_dev || !normals_dev || (((uintptr_t)positions_dev | (uintptr_t)indices_dev | (uintptr_t)normals_dev | (uintptr_t)texcoords_dev | (uintptr_t)order_out_dev) & 3)) {
         c->err = "rtx_build_blas: null or misaligned pointer"; return RTX_ERR_INVALID_ARG; }
-    if (blas_id < 0 || (size_t)blas_id >= c->build.size() || !c->build[blas_id].allocated) { c->err = "rtx_build_blas: the id was not created by rtx_alloc_blas"; return RTX_ERR_STATE; }
+    if (blas_id < 0 || (size_t)blas_id >= c->blas.size() || !c->blas[blas_id].build.allocated) { c->err = "rtx_build_blas: the id was not created by rtx_alloc_blas"; return RTX_ERR_STATE; }
     hipSetDevice(c->cfg.device);
-    rtx_ctx::BlasBuild & U = c->build[blas_id];
-    rtx_ctx::BlasRefit & R = c->refit[blas_id];
+    rtx_ctx::BlasBuild & U = c->blas[blas_id].build;
+    rtx_ctx::BlasRefit & R = c->blas[blas_id].refit;
     DevBuild & b = U.dev; DevRefit & r = R.dev;
     b.positions = (const float *)positions_dev; b.indices = (const int32_t *)indices_dev; b.normals = (const float *)normals_dev;
     b.texcoords = (const float *)texcoords_dev; b.order_out = (int32_t *)order_out_dev;
@@ -1160,7 +1172,7 @@ extern "C" int rtx_read_blas(rtx_ctx * c, int32_t blas_id, rtx_bvh_node * nodes,
 // What the uploaded trees allow the packet kernels (render_tiles_impl, the ray queries): lane = the call takes the per-lane kernels,
 // pk_closest = closest-hit packets may walk shared subtrees together.  Only ever turns lane on and pk_closest off.
 static void packet_kernel_limits(const rtx_ctx * c, bool & lane, bool & pk_closest) {
-    for (size_t b = 0; b < c->blas_packet_ok.size(); b++) if (c->h_blas[b].nodes && !c->blas_packet_ok[b]) lane = true;      // limits of the packet kernels' packed entries
+    for (size_t b = 0; b < c->h_blas.size(); b++) if (c->h_blas[b].nodes && !c->blas[b].packet_ok) lane = true;      // limits of the packet kernels' packed entries
     // The packet kernels keep ONE 64-entry stack per wave (RTX_PK_STACK) for the TLAS part and the BLAS part of a walk together, where the
     // reference has a stack per BVH (BVH_TRAVERSAL_STACK_SIZE each).  Both depths are known here, so the choice is made on the host
     // and pk_push's overflow path is never taken:  TLAS part = one pending far sibling per level + the iterator entry of the leaf being
@@ -1171,7 +1183,7 @@ static void packet_kernel_limits(const rtx_ctx * c, bool & lane, bool & pk_close
     int blas_any = 0, blas_shared = 0;
     for (size_t b = 0; b < c->h_blas.size(); b++) {
         if (!c->h_blas[b].nodes) continue;
-        const int depth = b < c->blas_inner_depth.size() ? c->blas_inner_depth[b] + 2 : 2;
+        const int depth = c->blas[b].inner_depth + 2;
         const int any = c->h_blas[b].pk4_nodes ? c->h_blas[b].pk4_need : depth;
         if (any > blas_any) blas_any = any;
         if (2 * depth > blas_shared) blas_shared = 2 * depth;
@@ -1195,8 +1207,7 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
     if (!c || first_tile < 0 || tile_stride < 1 || tile_count < 0) return RTX_ERR_INVALID_ARG;
     if (!c->frame_set) { c->err = "rtx_render_tiles before rtx_set_frame"; return RTX_ERR_STATE; }
     if (int bad = validate_references(c)) return bad;
-    const int tcx = (c->cfg.width + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE, tcy = (c->cfg.height + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE;
-    if (!views && tile_count > 0 && first_tile + (int64_t)(tile_count - 1) * tile_stride >= (int64_t)tcx * tcy) return RTX_ERR_INVALID_ARG;
+    if (!views && tile_count > 0 && first_tile + (int64_t)(tile_count - 1) * tile_stride >= (int64_t)frame_tiles(c)) return RTX_ERR_INVALID_ARG;
     hipSetDevice(c->cfg.device);
     // the launches below that generate primary rays or read the camera take the VIEWS instantiation of their kernel in a view call
     auto with_views = [views](auto && launch) {
@@ -1217,13 +1228,13 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
         if (c->scene.heatmap) { c->err = "RTX_RENDER_AOV in heat-map mode (a heat-map frame has no shading)"; return RTX_ERR_STATE; }
         if (!c->aov_channels) { c->err = "RTX_RENDER_AOV without channels bound by rtx_bind_aovs"; return RTX_ERR_STATE; }
         const int64_t frame_px = (int64_t)c->cfg.width * c->cfg.height;
-        const int64_t pixels = views ? ((int64_t)first_tile + tile_count) / ((int64_t)tcx * tcy) * frame_px : frame_px;
+        const int64_t pixels = views ? ((int64_t)first_tile + tile_count) / (int64_t)frame_tiles(c) * frame_px : frame_px;
         if (int arc = aov_targets_of_call(c, pixels, aov_t)) return arc;
     }
     c->serial = (flags & RTX_RENDER_SERIAL) != 0;
 
     // stats of this call are reset by the first k_begin_batch (WorkerThread.cpp:120 zeroes them per frame)
-    if (tile_count == 0) { hipLaunchKernelGGL(k_begin_batch, dim3(1), dim3(64), 0, c->stream, (DevCounters *)c->d_counters.p, (uint32_t *)c->d_pk_heads.p, 0u, 0u, 0u, 8u, 8u, 1); c->stats_pending = true; return RTX_OK; }
+    if (tile_count == 0) { begin_batch(c, (DevCounters *)c->d_counters.p, (uint32_t *)c->d_pk_heads.p, 0u, false, true); c->stats_pending = true; return RTX_OK; }
 
     int batch_tiles = 0;
     plan_batch(c, tile_count, batch_tiles);
@@ -1256,9 +1267,8 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
     // fails the pending HIP error is cleared and the call continues with the non-split kernel: a correctly queued frame must not
     // report RTX_ERR_HIP.  The split walk needs 4-wide records for every mesh.
     c->q.pk_items = nullptr; c->q.pk_item_count = nullptr; c->q.pk_item_cap = 0;
+    const bool all_wide = all_meshes_wide(c);
     if (c->knobs.split_items > 0 && c->scene.light_count > 0) {
-        bool all_wide = true;
-        for (size_t b = 0; b < c->h_blas.size(); b++) if (c->h_blas[b].nodes && !c->h_blas[b].pk4_nodes) all_wide = false;
         if (all_wide) {
             const size_t chunks = (size_t)c->pk_blocks_any * (RTX_PK_BLOCK / RTX_WAVE);
             const double expect = 0.45 * 1024.0 * (double)batch_tiles * c->scene.light_count / (double)chunks;
@@ -1337,10 +1347,7 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
         for (int d = 0; d <= RTX_MAX_LEVELS; d++) q.stats_n[d] = 0;
         const DevScene sc = c->scene;
         const bool plain = count_work || simple || sc.heatmap;
-        hipLaunchKernelGGL(k_begin_batch, dim3(1), dim3(64), 0, c->stream, q.counters, q.pk_heads, (uint32_t)q.primary_slots,
-                           (uint32_t)((plain ? c->trace_blocks_count : c->trace_blocks_closest) * RTX_TRACE_BLOCK),
-                           (uint32_t)((plain ? c->trace_blocks_count : c->trace_blocks_any) * RTX_TRACE_BLOCK),
-                           (uint32_t)(c->pk_blocks_closest * (RTX_PK_BLOCK / RTX_WAVE)), (uint32_t)(c->pk_blocks_any * (RTX_PK_BLOCK / RTX_WAVE)), done == 0 ? 1 : 0);
+        begin_batch(c, q.counters, q.pk_heads, (uint32_t)q.primary_slots, plain, done == 0);
         // Main stream: closest(d) -> shade(d) for d = 0..D.  Shadow rays depend only on shade, so in the default (fast)
         // configuration they run on a second stream: any(level 0) starts after shade(0) and overlaps the deeper levels'
         // closest/shade kernels; the shadow rays of levels 1..D are traced by ONE more launch after shade(D).  This removes
@@ -1369,7 +1376,7 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
         // With the split walk a shadow-ray packet that enters an instance with few lanes hands the whole visit over as items, and ONE packet
         // launch for all levels beats a packet launch + a per-lane launch at every instance count measured (tools/any_rule.sh: 16 / 144 / 576
         // instances 1.54 / 2.24 / 3.01 vs 1.66 / 2.41 / 3.05 ms per frame, cfg5 2.32 vs 2.42): shadow rays then stay with the packets
-        if (c->knobs.lane_from_level < 0 && c->knobs.split_items > 0 && sc.light_count > 0) { bool all_wide = true; for (size_t b = 0; b < c->h_blas.size(); b++) if (c->h_blas[b].nodes && !c->h_blas[b].pk4_nodes) all_wide = false; if (all_wide) lane_from = RTX_MAX_LEVELS + 1; }
+        if (c->knobs.lane_from_level < 0 && c->knobs.split_items > 0 && sc.light_count > 0 && all_wide) lane_from = RTX_MAX_LEVELS + 1;
         if (c->knobs.lane_from_level_any >= 0) lane_from = c->knobs.lane_from_level_any;      // shadow rays only (A/B runs)
         // Which levels shade their own hits inside the closest-hit packet kernel (k_packet<.., FUSE>, rtx_packet.h) and which get a k_shade
         // launch (every other closest-hit kernel: per-lane, plain, instrumented).  Decided before anything is launched: k_resolve is told
@@ -1573,17 +1580,7 @@ extern "C" int rtx_set_views(rtx_ctx * c, const rtx_camera * cameras, int32_t vi
         HIP_OK(c, hipStreamSynchronize(c->stream));
         if (int rc = ensure(c, c->d_views, bytes)) return rc;
     }
-    rtx_ctx::FrameStage & st = c->vstage[c->vstage_next]; c->vstage_next = (c->vstage_next + 1) % 3;
-    if (st.pending) { HIP_OK(c, hipEventSynchronize(st.done)); st.pending = false; }
-    if (bytes > st.cap) {
-        if (st.host) hipHostFree(st.host);
-        st.host = nullptr; st.cap = 0;
-        HIP_OK(c, hipHostMalloc(&st.host, bytes, hipHostMallocDefault)); st.cap = bytes;
-    }
-    if (!st.done) HIP_OK(c, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
-    memcpy(st.host, cameras, bytes);
-    HIP_OK(c, hipMemcpyAsync(c->d_views.p, st.host, bytes, hipMemcpyHostToDevice, c->stream));      // after the work already queued, before the next call
-    HIP_OK(c, hipEventRecord(st.done, c->stream)); st.pending = true;
+    if (int rc = stage_copy(c, c->view_ring, c->d_views.p, cameras, bytes)) return rc;
     c->view_count = view_count;
     return RTX_OK;
 }
@@ -1593,18 +1590,10 @@ static int ensure_view_fb(rtx_ctx * c, int32_t views) {
     if (views <= c->vfb_cap) return RTX_OK;
     const size_t px = (size_t)c->cfg.width * c->cfg.height, old = (size_t)c->vfb_cap * px;
     HIP_OK(c, hipStreamSynchronize(c->stream));
-    DevBuf rgb, packed;
-    int rc = ensure(c, rgb, (size_t)views * px * 12);
-    if (!rc) rc = ensure(c, packed, (size_t)views * px * 4);
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipMemset(rgb.p, 0, rgb.cap);
-    if (!rc && e == hipSuccess) e = hipMemset(packed.p, 0, packed.cap);
-    if (!rc && e == hipSuccess && old) e = hipMemcpy(rgb.p, c->d_vfb_rgb.p, old * 12, hipMemcpyDeviceToDevice);
-    if (!rc && e == hipSuccess && old) e = hipMemcpy(packed.p, c->d_vfb_packed.p, old * 4, hipMemcpyDeviceToDevice);
-    if (!rc && e != hipSuccess) { c->err = std::string("view framebuffer growth: ") + hipGetErrorString(e); rc = RTX_ERR_HIP; }
-    if (rc) { if (rgb.p) hipFree(rgb.p); if (packed.p) hipFree(packed.p); return rc; }      // the old buffers stay in place
-    if (old) { hipFree(c->d_vfb_rgb.p); hipFree(c->d_vfb_packed.p); }
-    c->d_vfb_rgb = rgb; c->d_vfb_packed = packed; c->vfb_cap = views;
+    DevBuf rgb, packed;                                             // both grown, or the old buffers stay in place
+    if (int rc = grown_copy(c, c->d_vfb_rgb, old * 12, (size_t)views * px * 12, "view framebuffer", rgb)) return rc;
+    if (int rc = grown_copy(c, c->d_vfb_packed, old * 4, (size_t)views * px * 4, "view framebuffer", packed)) return rc;
+    c->d_vfb_rgb = std::move(rgb); c->d_vfb_packed = std::move(packed); c->vfb_cap = views;
     return RTX_OK;
 }
 
@@ -1616,7 +1605,7 @@ extern "C" int rtx_render_views(rtx_ctx * c, int32_t first_view, int32_t view_co
     if ((int64_t)first_view + view_count > c->view_count) { c->err = "view range outside the views set by rtx_set_views"; return RTX_ERR_INVALID_ARG; }
     if (c->ext_vrgb) { if (first_view + view_count > c->ext_vcap) { c->err = "view range outside the bound view framebuffer"; return RTX_ERR_INVALID_ARG; } }
     else if (int rc = ensure_view_fb(c, c->view_count)) return rc;
-    const int32_t tiles = ((c->cfg.width + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE) * ((c->cfg.height + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE);
+    const int32_t tiles = frame_tiles(c);
     return render_tiles_impl(c, first_view * tiles, 1, view_count * tiles, flags, nullptr, RTX_CAM_VIEWS);
 }
 
@@ -1654,17 +1643,7 @@ extern "C" int rtx_set_rays(rtx_ctx * c, const rtx_ray * host_rays, int32_t view
         c->ray_count = view_count;
         return RTX_OK;
     }
-    rtx_ctx::FrameStage & st = c->rstage[c->rstage_next]; c->rstage_next = (c->rstage_next + 1) % 3;
-    if (st.pending) { HIP_OK(c, hipEventSynchronize(st.done)); st.pending = false; }
-    if (bytes > st.cap) {
-        if (st.host) hipHostFree(st.host);
-        st.host = nullptr; st.cap = 0;
-        HIP_OK(c, hipHostMalloc(&st.host, bytes, hipHostMallocDefault)); st.cap = bytes;
-    }
-    if (!st.done) HIP_OK(c, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
-    memcpy(st.host, host_rays, bytes);
-    HIP_OK(c, hipMemcpyAsync(c->d_rays.p, st.host, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(c, hipEventRecord(st.done, c->stream)); st.pending = true;
+    if (int rc = stage_copy(c, c->ray_ring, c->d_rays.p, host_rays, bytes)) return rc;
     c->ray_count = view_count;
     return RTX_OK;
 }
@@ -1690,7 +1669,7 @@ extern "C" int rtx_render_rays(rtx_ctx * c, int32_t first_view, int32_t view_cou
     if ((int64_t)first_view + view_count > have) { c->err = "view range outside the rays set by rtx_set_rays / rtx_bind_rays"; return RTX_ERR_INVALID_ARG; }
     if (c->ext_vrgb) { if (first_view + view_count > c->ext_vcap) { c->err = "view range outside the bound view framebuffer"; return RTX_ERR_INVALID_ARG; } }
     else if (int rc = ensure_view_fb(c, std::max(have, c->view_count))) return rc;
-    const int32_t tiles = ((c->cfg.width + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE) * ((c->cfg.height + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE);
+    const int32_t tiles = frame_tiles(c);
     return render_tiles_impl(c, first_view * tiles, 1, view_count * tiles, flags, nullptr, RTX_CAM_RAYS);
 }
 
@@ -1737,13 +1716,8 @@ static int aov_targets_of_call(rtx_ctx * c, int64_t pixels, DevAov & out) {
         if (!(c->aov_channels & (1u << k))) continue;
         if (pixels > c->aov_own_cap[k]) {
             HIP_OK(c, hipStreamSynchronize(c->stream));
-            DevBuf nb;
-            if (int rc = ensure(c, nb, (size_t)pixels * kAovBytes[k])) return rc;
-            hipError_t e = hipMemset(nb.p, 0, nb.cap);
-            if (e == hipSuccess && c->aov_own_cap[k]) e = hipMemcpy(nb.p, c->d_aov[k].p, (size_t)c->aov_own_cap[k] * kAovBytes[k], hipMemcpyDeviceToDevice);
-            if (e != hipSuccess) { hipFree(nb.p); c->err = std::string("AOV buffer growth: ") + hipGetErrorString(e); return RTX_ERR_HIP; }
-            if (c->d_aov[k].p) hipFree(c->d_aov[k].p);
-            c->d_aov[k] = nb; c->aov_own_cap[k] = pixels;
+            if (int rc = grow_keep(c, c->d_aov[k], (size_t)c->aov_own_cap[k] * kAovBytes[k], (size_t)pixels * kAovBytes[k], "AOV buffer")) return rc;
+            c->aov_own_cap[k] = pixels;
         }
         *aov_slot(out, k) = c->d_aov[k].p;
     }
@@ -1805,14 +1779,14 @@ __global__ void k_debug_libm(int fn, const float * a, const float * b, float * o
 extern "C" int rtx_debug_libm(rtx_ctx * c, int32_t fn, const float * a, const float * b, float * out, int32_t n) {
     if (!c || !a || !out || n <= 0) return RTX_ERR_INVALID_ARG;
     hipSetDevice(c->cfg.device);
-    float * da = nullptr, * db = nullptr, * dout = nullptr;
-    HIP_OK(c, hipMalloc(&da, (size_t)n * 4)); HIP_OK(c, hipMalloc(&db, (size_t)n * 4)); HIP_OK(c, hipMalloc(&dout, (size_t)n * 4));
-    HIP_OK(c, hipMemcpy(da, a, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIP_OK(c, hipMemcpy(db, b ? b : a, (size_t)n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_debug_libm, dim3((n + 255) / 256), dim3(256), 0, c->stream, fn, da, db, dout, n);
+    DevBuf da, db, dout;                 // scratch of this call: released on every way out
+    int rc = upload(c, da, a, (size_t)n * 4);
+    if (!rc) rc = upload(c, db, b ? b : a, (size_t)n * 4);
+    if (!rc) rc = ensure(c, dout, (size_t)n * 4);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_debug_libm, dim3((n + 255) / 256), dim3(256), 0, c->stream, fn, (const float *)da.p, (const float *)db.p, (float *)dout.p, n);
     HIP_OK(c, hipStreamSynchronize(c->stream));
-    HIP_OK(c, hipMemcpy(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost));
-    hipFree(da); hipFree(db); hipFree(dout);
+    HIP_OK(c, hipMemcpy(out, dout.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return RTX_OK;
 }
 
@@ -1832,13 +1806,13 @@ extern "C" int rtx_debug_texture_sample(rtx_ctx * c, int32_t texture_id, const f
     DevScene sc = c->scene;
     sc.texture_mode = c->cfg.texture_mode; sc.mip_filter = c->cfg.mip_filter; sc.max_anisotropy = c->cfg.max_anisotropy;
     sc.textures = (const DevTexture *)c->d_textures.p; sc.ewa_table = (const float *)c->d_ewa.p;
-    float * din = nullptr, * dout = nullptr;
-    HIP_OK(c, hipMalloc(&din, (size_t)n * 24)); HIP_OK(c, hipMalloc(&dout, (size_t)n * 12));
-    HIP_OK(c, hipMemcpy(din, in6, (size_t)n * 24, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_debug_texture, dim3((n + 255) / 256), dim3(256), 0, c->stream, sc, texture_id, din, dout, n);
+    DevBuf din, dout;
+    int rc = upload(c, din, in6, (size_t)n * 24);
+    if (!rc) rc = ensure(c, dout, (size_t)n * 12);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_debug_texture, dim3((n + 255) / 256), dim3(256), 0, c->stream, sc, texture_id, (const float *)din.p, (float *)dout.p, n);
     HIP_OK(c, hipStreamSynchronize(c->stream));
-    HIP_OK(c, hipMemcpy(out3, dout, (size_t)n * 12, hipMemcpyDeviceToHost));
-    hipFree(din); hipFree(dout);
+    HIP_OK(c, hipMemcpy(out3, dout.p, (size_t)n * 12, hipMemcpyDeviceToHost));
     return RTX_OK;
 }
 
@@ -1867,13 +1841,13 @@ extern "C" int rtx_debug_blas_wide_closest(rtx_ctx * c, int32_t blas_id, int32_t
 extern "C" int rtx_debug_sky_sample(rtx_ctx * c, const float * dirs3, float * out3, int32_t n) {
     if (!c || !dirs3 || !out3 || n <= 0) return RTX_ERR_INVALID_ARG;
     hipSetDevice(c->cfg.device);
-    float * din = nullptr, * dout = nullptr;
-    HIP_OK(c, hipMalloc(&din, (size_t)n * 12)); HIP_OK(c, hipMalloc(&dout, (size_t)n * 12));
-    HIP_OK(c, hipMemcpy(din, dirs3, (size_t)n * 12, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_debug_sky, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const float *)c->d_sky.p, c->sky_size, din, dout, n);
+    DevBuf din, dout;
+    int rc = upload(c, din, dirs3, (size_t)n * 12);
+    if (!rc) rc = ensure(c, dout, (size_t)n * 12);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_debug_sky, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const float *)c->d_sky.p, c->sky_size, (const float *)din.p, (float *)dout.p, n);
     HIP_OK(c, hipStreamSynchronize(c->stream));
-    HIP_OK(c, hipMemcpy(out3, dout, (size_t)n * 12, hipMemcpyDeviceToHost));
-    hipFree(din); hipFree(dout);
+    HIP_OK(c, hipMemcpy(out3, dout.p, (size_t)n * 12, hipMemcpyDeviceToHost));
     return RTX_OK;
 }
 
@@ -1930,8 +1904,7 @@ struct rtx_group {
 
 static int group_setup(rtx_group * g) {
     rtx_ctx * c = g->ctx;
-    const int tcx = (c->cfg.width + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE, tcy = (c->cfg.height + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE;
-    g->tiles_total = tcx * tcy;
+    g->tiles_total = frame_tiles(c);
     g->tiles_per_rank = group_tiles_per_rank(g->tiles_total, g->world);      // padded: every rank sends the same count
     g->own_tiles = group_own_tiles(g->tiles_total, g->world, g->rank);
     hipSetDevice(c->cfg.device);
@@ -2101,9 +2074,7 @@ extern "C" int rtx_group_destroy(rtx_group * g) {
     }
     if (g->ev_rendered) hipEventDestroy(g->ev_rendered);
     if (g->ev_gathered) hipEventDestroy(g->ev_gathered);
-    if (g->send.p) hipFree(g->send.p);
-    if (g->recv.p) hipFree(g->recv.p);
-    delete g;
+    delete g;                            // with its send / recv buffers
     return RTX_OK;
 }
 
@@ -2122,10 +2093,8 @@ extern "C" int rtx_debug_group_loopback(rtx_ctx * c, int32_t world, uint32_t fla
         const int tcx = (c->cfg.width + RTX_TILE_SIZE - 1) / RTX_TILE_SIZE;
         hipLaunchKernelGGL(k_unswizzle, dim3(c->n_cu * 4), dim3(256), 0, c->stream, (const uint32_t *)g.recv.p,
                            (uint32_t *)(c->ext_packed ? c->ext_packed : c->d_fb_packed.p), world, g.tiles_per_rank, g.tiles_total, tcx, c->cfg.width, c->cfg.height);
-        hipStreamSynchronize(c->stream);
     }
-    if (g.send.p) hipFree(g.send.p);
-    if (g.recv.p) hipFree(g.recv.p);
+    hipStreamSynchronize(c->stream);     // before g's buffers go: what was queued writes them
     return rc;
 }
 
@@ -2175,12 +2144,6 @@ static int query_checks(rtx_ctx * c, const void * in, int64_t n, const void * ou
     return validate_references(c);
 }
 
-static void query_begin_chunk(rtx_ctx * c, const DevQueues & q) {
-    hipLaunchKernelGGL(k_begin_batch, dim3(1), dim3(64), 0, c->stream, q.counters, q.pk_heads, 0u,
-                       (uint32_t)(c->trace_blocks_closest * RTX_TRACE_BLOCK), (uint32_t)(c->trace_blocks_any * RTX_TRACE_BLOCK),
-                       (uint32_t)(c->pk_blocks_closest * (RTX_PK_BLOCK / RTX_WAVE)), (uint32_t)(c->pk_blocks_any * (RTX_PK_BLOCK / RTX_WAVE)), 1);
-}
-
 extern "C" int rtx_query_closest(rtx_ctx * c, const void * rays_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags) {
     if (c && (channels == 0 || (channels & ~(uint32_t)RTX_QUERY_ALL))) { c->err = "rtx_query_closest: channels must be a non-empty subset of RTX_QUERY_ALL"; return RTX_ERR_INVALID_ARG; }
     if (int bad = query_checks(c, rays_dev, n, out, flags, "rtx_query_closest")) return bad;
@@ -2205,12 +2168,9 @@ extern "C" int rtx_query_closest(rtx_ctx * c, const void * rays_dev, int64_t n, 
         t.material_id = on(RTX_QUERY_MATERIAL_ID) && out->material_id ? out->material_id + first : nullptr;
         t.object_id = on(RTX_QUERY_OBJECT_ID) && out->object_id ? out->object_id + first : nullptr;
         t.triangle_id = on(RTX_QUERY_TRIANGLE_ID) && out->triangle_id ? out->triangle_id + first : nullptr;
-        query_begin_chunk(c, q);
+        begin_batch(c, q.counters, q.pk_heads, 0u, false, true);
         launch_timed(c, "k_query_fill", c->stream, [&] { hipLaunchKernelGGL(k_query_fill, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, q, (const float *)rays_dev + 6 * first, m); });
-        launch_timed(c, "k_trace_closest", c->stream, [&] {
-            if (lane) hipLaunchKernelGGL((k_trace_fast<false>), dim3(c->trace_blocks_closest), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, 1, 1);
-            else      hipLaunchKernelGGL((k_packet<false, false>), dim3(c->pk_blocks_closest), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, 1, 1);
-        });
+        launch_timed(c, "k_trace_closest", c->stream, [&] { launch_closest_level1(c, sc, q, lane); });
         launch_timed(c, "k_query_resolve", c->stream, [&] { hipLaunchKernelGGL(k_query_resolve, dim3((m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc_resolve, q, m, t); });
     }
     HIP_OK(c, hipGetLastError());
@@ -2230,12 +2190,9 @@ extern "C" int rtx_query_occluded(rtx_ctx * c, const void * segments_dev, int64_
         const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
         const int blocks = (((m + RTX_WAVE - 1) & ~(RTX_WAVE - 1)) + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK;
         q.tile_count = (m + 1023) / 1024;
-        query_begin_chunk(c, q);
+        begin_batch(c, q.counters, q.pk_heads, 0u, false, true);
         launch_timed(c, "k_query_fill_segments", c->stream, [&] { hipLaunchKernelGGL(k_query_fill_segments, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, q, (const float *)segments_dev + 7 * first, m); });
-        launch_timed(c, "k_trace_any", c->stream, [&] {
-            if (lane) hipLaunchKernelGGL((k_trace_fast<true>), dim3(c->trace_blocks_any), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, 0, 0);
-            else      hipLaunchKernelGGL((k_packet<true, false>), dim3(c->pk_blocks_any), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, 0, 0);
-        });
+        launch_timed(c, "k_trace_any", c->stream, [&] { launch_any_level0(c, sc, q, lane); });
         launch_timed(c, "k_query_store_occluded", c->stream, [&] { hipLaunchKernelGGL(k_query_store_occluded, dim3((m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK), dim3(RTX_QUERY_BLOCK), 0, c->stream, q, m, occluded_dev + first); });
     }
     HIP_OK(c, hipGetLastError());
@@ -2301,9 +2258,7 @@ static int debug_queues(rtx_ctx * c, int n) {
     if (tiles > 4096) return RTX_ERR_LIMIT;
     int rc = alloc_queues(c, tiles < 1 ? 1 : tiles);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_begin_batch, dim3(1), dim3(64), 0, c->stream, (DevCounters *)c->d_counters.p, (uint32_t *)c->d_pk_heads.p, 0u,
-                       (uint32_t)(c->trace_blocks_closest * RTX_TRACE_BLOCK), (uint32_t)(c->trace_blocks_any * RTX_TRACE_BLOCK),
-                       (uint32_t)(c->pk_blocks_closest * (RTX_PK_BLOCK / RTX_WAVE)), (uint32_t)(c->pk_blocks_any * (RTX_PK_BLOCK / RTX_WAVE)), 1);
+    begin_batch(c, (DevCounters *)c->d_counters.p, (uint32_t *)c->d_pk_heads.p, 0u, false, true);
     return RTX_OK;
 }
 
@@ -2312,21 +2267,19 @@ extern "C" int rtx_debug_trace_rays(rtx_ctx * c, const float * rays18, int32_t n
     hipSetDevice(c->cfg.device);
     int rc = debug_queues(c, n);
     if (rc) return rc;
-    float * din = nullptr, * dout = nullptr;
-    HIP_OK(c, hipMalloc(&din, (size_t)n * 72)); HIP_OK(c, hipMalloc(&dout, (size_t)n * 108));
-    HIP_OK(c, hipMemcpy(din, rays18, (size_t)n * 72, hipMemcpyHostToDevice));
+    DevBuf din, dout;
+    rc = upload(c, din, rays18, (size_t)n * 72);
+    if (!rc) rc = ensure(c, dout, (size_t)n * 108);
+    if (rc) return rc;
     DevQueues q = c->q; q.first_tile = 0; q.tile_stride = 1; q.tile_count = (n + 1023) / 1024; q.primary_slots = 0; q.tm_packed = nullptr;
     const DevScene sc = c->scene;
-    hipLaunchKernelGGL(k_debug_fill_rays, dim3((n + 255) / 256), dim3(256), 0, c->stream, q, din, n);
-    if (flags & RTX_RENDER_LANE_TRACE) hipLaunchKernelGGL((k_trace_fast<false>), dim3(c->trace_blocks_closest), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, 1, 1);
-    else {
-        if (flags & RTX_RENDER_PACKET_CLOSEST) q.pk_defer_t0_closest = q.pk_defer_t0_primary = q.pk_defer_t0;
-        hipLaunchKernelGGL((k_packet<false, false>), dim3(c->pk_blocks_closest), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, 1, 1);
-    }
-    hipLaunchKernelGGL(k_debug_rebuild, dim3((n + 255) / 256), dim3(256), 0, c->stream, sc, q, din, dout, n);
+    const bool lane = (flags & RTX_RENDER_LANE_TRACE) != 0;
+    if (!lane && (flags & RTX_RENDER_PACKET_CLOSEST)) q.pk_defer_t0_closest = q.pk_defer_t0_primary = q.pk_defer_t0;
+    hipLaunchKernelGGL(k_debug_fill_rays, dim3((n + 255) / 256), dim3(256), 0, c->stream, q, (const float *)din.p, n);
+    launch_closest_level1(c, sc, q, lane);
+    hipLaunchKernelGGL(k_debug_rebuild, dim3((n + 255) / 256), dim3(256), 0, c->stream, sc, q, (const float *)din.p, (float *)dout.p, n);
     HIP_OK(c, hipStreamSynchronize(c->stream));
-    HIP_OK(c, hipMemcpy(hits27, dout, (size_t)n * 108, hipMemcpyDeviceToHost));
-    hipFree(din); hipFree(dout);
+    HIP_OK(c, hipMemcpy(hits27, dout.p, (size_t)n * 108, hipMemcpyDeviceToHost));
     return RTX_OK;
 }
 
@@ -2335,23 +2288,20 @@ extern "C" int rtx_debug_occluded(rtx_ctx * c, const float * origin_direction_ma
     hipSetDevice(c->cfg.device);
     int rc = debug_queues(c, n);
     if (rc) return rc;
-    float * din = nullptr;
-    HIP_OK(c, hipMalloc(&din, (size_t)n * 28));
-    HIP_OK(c, hipMemcpy(din, origin_direction_maxdist7, (size_t)n * 28, hipMemcpyHostToDevice));
+    DevBuf din;
+    if ((rc = upload(c, din, origin_direction_maxdist7, (size_t)n * 28))) return rc;
     DevQueues q = c->q; q.first_tile = 0; q.tile_stride = 1; q.tile_count = (n + 1023) / 1024; q.primary_slots = n; q.tm_packed = nullptr;
     {   // explicit shadow rays (the frame kernels derive theirs from the hit's point and the light): origin + distance, direction per shadow slot of level 0
         const size_t sslots = (size_t)q.level_cap[0] * (size_t)(c->scene.light_count > 0 ? c->scene.light_count : 1);
         rc = ensure(c, c->d_dbg_s0, sslots * 16); if (!rc) rc = ensure(c, c->d_dbg_s1, sslots * 16);
-        if (rc) { hipFree(din); return rc; }
+        if (rc) return rc;
         q.s0 = (float4 *)c->d_dbg_s0.p; q.s1 = (float4 *)c->d_dbg_s1.p; q.shadow_explicit = 1;
     }
     const DevScene sc = c->scene;
-    hipLaunchKernelGGL(k_debug_fill_shadow, dim3((n + 255) / 256), dim3(256), 0, c->stream, q, sc.light_count, din, n);
-    if (flags & RTX_RENDER_LANE_TRACE) hipLaunchKernelGGL((k_trace_fast<true>), dim3(c->trace_blocks_any), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, 0, 0);
-    else hipLaunchKernelGGL((k_packet<true, false>), dim3(c->pk_blocks_any), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, 0, 0);
+    hipLaunchKernelGGL(k_debug_fill_shadow, dim3((n + 255) / 256), dim3(256), 0, c->stream, q, sc.light_count, (const float *)din.p, n);
+    launch_any_level0(c, sc, q, (flags & RTX_RENDER_LANE_TRACE) != 0);
     HIP_OK(c, hipStreamSynchronize(c->stream));
     HIP_OK(c, hipMemcpy(occluded, q.socc + q.shadow_base[0], (size_t)n * 4, hipMemcpyDeviceToHost));
-    hipFree(din);
     return RTX_OK;
 }
 
@@ -2376,16 +2326,16 @@ extern "C" int rtx_debug_light_plot(rtx_ctx * c, const rtx_point_light * pl, con
                                     const float * in10, float * out9, int32_t n_light, const float * rgb, uint32_t * packed, int32_t n_plot) {
     if (!c || !pl || !sl || !dl || n_light < 0 || n_plot < 0 || (n_light && (!in10 || !out9)) || (n_plot && (!rgb || !packed))) return RTX_ERR_INVALID_ARG;
     hipSetDevice(c->cfg.device);
-    float * din = nullptr, * dout = nullptr, * drgb = nullptr; uint32_t * dpk = nullptr;
-    HIP_OK(c, hipMalloc(&din, (size_t)(n_light + 1) * 40)); HIP_OK(c, hipMalloc(&dout, (size_t)(n_light + 1) * 36));
-    HIP_OK(c, hipMalloc(&drgb, (size_t)(n_plot + 1) * 12)); HIP_OK(c, hipMalloc(&dpk, (size_t)(n_plot + 1) * 4));
-    if (n_light) HIP_OK(c, hipMemcpy(din, in10, (size_t)n_light * 40, hipMemcpyHostToDevice));
-    if (n_plot) HIP_OK(c, hipMemcpy(drgb, rgb, (size_t)n_plot * 12, hipMemcpyHostToDevice));
+    DevBuf din, dout, drgb, dpk;
+    int rc = upload(c, din, in10, (size_t)n_light * 40);      // an empty input still gets a (16-byte) buffer: the kernel is handed valid pointers
+    if (!rc) rc = ensure(c, dout, (size_t)n_light * 36);
+    if (!rc) rc = upload(c, drgb, rgb, (size_t)n_plot * 12);
+    if (!rc) rc = ensure(c, dpk, (size_t)n_plot * 4);
+    if (rc) return rc;
     const int n = n_light > n_plot ? n_light : n_plot;
-    hipLaunchKernelGGL(k_debug_light_plot, dim3((n + 255) / 256), dim3(256), 0, c->stream, *pl, *sl, *dl, din, dout, drgb, dpk, n_light, n_plot);
+    hipLaunchKernelGGL(k_debug_light_plot, dim3((n + 255) / 256), dim3(256), 0, c->stream, *pl, *sl, *dl, (const float *)din.p, (float *)dout.p, (const float *)drgb.p, (uint32_t *)dpk.p, n_light, n_plot);
     HIP_OK(c, hipStreamSynchronize(c->stream));
-    if (n_light) HIP_OK(c, hipMemcpy(out9, dout, (size_t)n_light * 36, hipMemcpyDeviceToHost));
-    if (n_plot) HIP_OK(c, hipMemcpy(packed, dpk, (size_t)n_plot * 4, hipMemcpyDeviceToHost));
-    hipFree(din); hipFree(dout); hipFree(drgb); hipFree(dpk);
+    if (n_light) HIP_OK(c, hipMemcpy(out9, dout.p, (size_t)n_light * 36, hipMemcpyDeviceToHost));
+    if (n_plot) HIP_OK(c, hipMemcpy(packed, dpk.p, (size_t)n_plot * 4, hipMemcpyDeviceToHost));
     return RTX_OK;
 }
