@@ -54,6 +54,8 @@ def lib():
         _lib.orc_render_tiles.restype = C.c_int
         _lib.orc_render_tiles.argtypes = [C.POINTER(OrcScene), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.POINTER(RtxStats), C.POINTER(RtxWork), C.c_int32]
+        _lib.orc_shade_rays.restype = C.c_int
+        _lib.orc_shade_rays.argtypes = [C.POINTER(OrcScene), C.c_int32] + [C.c_void_p] * 6 + [C.POINTER(RtxStats), C.POINTER(RtxWork), C.c_int32]
         _lib.orc_texture_sample.restype = None
         _lib.orc_texture_sample.argtypes = [C.POINTER(OrcTexture), C.c_int32, C.c_int32, C.c_float] + [C.c_float] * 6 + [C.c_void_p]
         _lib.orc_plot.restype = C.c_uint32
@@ -141,6 +143,27 @@ class OracleScene:
         if want_dist:
             out["dist"] = dist
         return out
+
+    def shade_rays(self, rays18: np.ndarray, camera: Optional[np.ndarray] = None, threads: int = 8):
+        """Raytracer::bounce of caller-supplied primary rays (orc_shade_rays): rays18 (..., 18); camera None (every ray's own origin is its
+        camera, as in rtx_render_rays) or (..., 3) positions, one per ray.  A dict shaped like render()'s over the rays' leading shape: rgb
+        (..., 3), packed, dist, ray_flags (bit 0: a ray of the tree had a non-finite origin), stats, work.  Rays with a zero direction are
+        no rays: not counted, their outputs stay zero."""
+        r = np.ascontiguousarray(rays18, np.float32)
+        lead = r.shape[:-1]
+        r = r.reshape(-1, 18)
+        cam = None
+        if camera is not None:
+            cam = np.ascontiguousarray(np.broadcast_to(np.asarray(camera, np.float32), lead + (3,))).reshape(-1, 3)
+        n = len(r)
+        rgb = np.zeros((n, 3), np.float32); packed = np.zeros(n, np.uint32); dist = np.zeros(n, np.float32); flags = np.zeros(n, np.int32)
+        stats, work = RtxStats(), RtxWork()
+        rc = lib().orc_shade_rays(C.byref(self.struct), n, r.ctypes.data, cam.ctypes.data if cam is not None else None, rgb.ctypes.data,
+                                  packed.ctypes.data, dist.ctypes.data, flags.ctypes.data, C.byref(stats), C.byref(work), threads)
+        if rc != 0:
+            raise RuntimeError(f"orc_shade_rays failed: {rc}")
+        return {"rgb": rgb.reshape(lead + (3,)), "packed": packed.reshape(lead), "dist": dist.reshape(lead), "ray_flags": flags.reshape(lead),
+                "stats": stats.as_dict(), "work": work.as_dict()}
 
     def trace_closest(self, rays18: np.ndarray, threads: int = 8) -> Tuple[np.ndarray, np.ndarray]:
         """Scene::trace_primitives of n rays: (hits (n, 27) float32 in orc_trace_closest's layout, ids (n, 3) int32: material, object,

@@ -123,6 +123,7 @@ int main(int argc, char ** argv) {
 	int W = 256, H = 256, bounces = NUMBER_OF_BOUNCES, frames = 1; float delta = 0.0f;
 	int unit_n = 0; unsigned unit_seed = 1;
 	std::string rayprobe_path; int rayprobe_n = 0;
+	std::string shadeprobe_path; int shadeprobe_n = 0;
 	bool keep_base = false, drop_base_meshes = false, have_camera = false, have_ambient = false;
 	Vector3 cam_pos; Quaternion cam_rot; Vector3 ambient;
 	std::vector<MeshSpec> meshes;
@@ -177,6 +178,7 @@ int main(int argc, char ** argv) {
 			else if (w[0] == "texprobe_file") { file_probes.push_back({ w[1], w[2] }); }
 			else if (w[0] == "unitprobe") { unit_n = atoi(w[1].c_str()); unit_seed = (unsigned)strtoul(w[2].c_str(), nullptr, 0); }
 			else if (w[0] == "rayprobe")  { rayprobe_path = w[1]; rayprobe_n = atoi(w[2].c_str()); }
+			else if (w[0] == "shadeprobe") { shadeprobe_path = w[1]; shadeprobe_n = atoi(w[2].c_str()); }
 			else { fprintf(stderr, "unknown script command '%s'\n", w[0].c_str()); return 2; }
 		}
 	}
@@ -716,6 +718,40 @@ int main(int argc, char ** argv) {
 				q[27 + k] = SIMD_float::all_false(scene.intersect_primitives(ray, SIMD_float(r[18 + k]))) ? 0.0f : 1.0f;
 		}
 		dump("rayprobe.f32", io.data(), io.size() * 4);
+	}
+
+	// ---- shade probes: caller-supplied primary rays (tests/shadeset.py) through Raytracer::bounce, each with a camera position of its own ------
+	// in:  <file> n records of SHADEPROBE_IN floats: origin, direction, dO_dx, dO_dy, dD_dx, dD_dy (18), the camera position of this ray (3)
+	// out: shadeprobe.f32 n records of SHADEPROBE_OUT floats: colour (3), distance (1), the primary, shadow, reflection and refraction ray
+	//      counts of this ray's tree (4).  A record whose direction is all zero is no ray: its output record stays zero.
+	// Scene::camera.position is written before each call (bounce reads it at Raytracer.cpp:152) and put back afterwards.
+	if (shadeprobe_n > 0) {
+		enum { SHADEPROBE_IN = 21, SHADEPROBE_OUT = 8 };
+		std::vector<float> in((size_t)shadeprobe_n * SHADEPROBE_IN), io((size_t)shadeprobe_n * SHADEPROBE_OUT, 0.0f);
+		FILE * f = fopen(shadeprobe_path.c_str(), "rb");
+		if (!f || fread(in.data(), 4, in.size(), f) != in.size()) { fprintf(stderr, "cannot read %d rays from %s\n", shadeprobe_n, shadeprobe_path.c_str()); return 2; }
+		fclose(f);
+		const Vector3 camera_kept = scene.camera.position;
+		for (int i = 0; i < shadeprobe_n; i++) {
+			const float * r = &in[(size_t)SHADEPROBE_IN * i];
+			float * q = &io[(size_t)SHADEPROBE_OUT * i];
+			if (r[3] == 0.0f && r[4] == 0.0f && r[5] == 0.0f) continue;
+			Ray ray;
+			ray.origin = SIMD_Vector3(Vector3(r[0], r[1], r[2])); ray.direction = SIMD_Vector3(Vector3(r[3], r[4], r[5]));
+#if RAY_DIFFERENTIALS_ENABLED
+			ray.dO_dx = SIMD_Vector3(Vector3(r[6], r[7], r[8]));    ray.dO_dy = SIMD_Vector3(Vector3(r[9], r[10], r[11]));
+			ray.dD_dx = SIMD_Vector3(Vector3(r[12], r[13], r[14])); ray.dD_dy = SIMD_Vector3(Vector3(r[15], r[16], r[17]));
+#endif
+			scene.camera.position = Vector3(r[18], r[19], r[20]);
+			PerformanceStats st = { 0, 0, 0, 0 };
+			st.num_primary_rays++;
+			SIMD_float distance;
+			SIMD_Vector3 colour = raytracer.bounce(ray, bounces, distance, st);
+			q[0] = colour.x[0]; q[1] = colour.y[0]; q[2] = colour.z[0]; q[3] = distance[0];
+			q[4] = (float)st.num_primary_rays; q[5] = (float)st.num_shadow_rays; q[6] = (float)st.num_reflection_rays; q[7] = (float)st.num_refraction_rays;
+		}
+		scene.camera.position = camera_kept;
+		dump("shadeprobe.f32", io.data(), io.size() * 4);
 	}
 
 	{

@@ -694,9 +694,15 @@ static v3 spot_light_calc(const rtx_spot_light * l, v3 normal, v3 to_light, v3 t
 /* ------------------------------------------------------------------------------------------------
  * Raytracer::bounce, Raytracer.cpp:87-400 (lane 1)
  * ---------------------------------------------------------------------------------------------- */
-static v3 bounce(const orc_scene * sc, const ray_t * ray, int bounces_left, float * distance, counters_t * c) {
+/* What one tree of rays carries besides the scene: `camera` is what :152 reads as scene->camera.position (orc_render_tiles: the frame's
+ * camera; orc_shade_rays: the caller's, or the primary ray's own origin), `flags` collects ORC_RAY_NONFINITE_ORIGIN over the tree. */
+typedef struct { v3 camera; int32_t flags; } tree_t;
+
+static v3 bounce(const orc_scene * sc, const ray_t * ray, int bounces_left, float * distance, counters_t * c, tree_t * tree) {
     const rtx_frame * fr = &sc->frame;
     v3 result = V3(0.0f, 0.0f, 0.0f);
+    if (!(fabsf(ray->origin.x) < INFINITY && fabsf(ray->origin.y) < INFINITY && fabsf(ray->origin.z) < INFINITY))
+        tree->flags |= ORC_RAY_NONFINITE_ORIGIN;                /* not the reference's: bookkeeping for the callers of orc_shade_rays */
 
     hit_t h;
     memset(&h, 0, sizeof(h));
@@ -715,6 +721,8 @@ static v3 bounce(const orc_scene * sc, const ray_t * ray, int bounces_left, floa
         return sky_sample(sc->sky, sc->sky_size, ray->direction);
     }
     *distance = h.distance;                                 /* :113 */
+    if (!(fabsf(h.point.x) < INFINITY && fabsf(h.point.y) < INFINITY && fabsf(h.point.z) < INFINITY))
+        tree->flags |= ORC_RAY_NONFINITE_ORIGIN;                /* the origin of this hit's shadow rays and children, flagged whether or not the hit spawns any */
 
     const rtx_material * mat = &sc->materials[h.material_id];
     c->work.shaded_hits++;
@@ -728,7 +736,7 @@ static v3 bounce(const orc_scene * sc, const ray_t * ray, int bounces_left, floa
 
     if (vdot(albedo, albedo) > 0.0f) {                      /* :143-201 */
         v3 diffuse = v3p(fr->ambient);
-        v3 to_camera = vnormalize(vsub(v3p(fr->camera.position), h.point));
+        v3 to_camera = vnormalize(vsub(tree->camera, h.point));
 
         for (int i = 0; i < fr->point_light_count; i++) {
             const rtx_point_light * l = &fr->point_lights[i];
@@ -781,7 +789,7 @@ static v3 bounce(const orc_scene * sc, const ray_t * ray, int bounces_left, floa
             c->stats.num_reflection_rays++;
             c->work.rays_spawned++;
             float rd;
-            colour_reflection = vmul(Ks, bounce(sc, &rr, bounces_left - 1, &rd, c));
+            colour_reflection = vmul(Ks, bounce(sc, &rr, bounces_left - 1, &rd, c, tree));
             result = vadd(result, colour_reflection);
         }
 
@@ -817,7 +825,7 @@ static v3 bounce(const orc_scene * sc, const ray_t * ray, int bounces_left, floa
             rf.dD_dy = vsub(vmuls(ray->dD_dy, eta), vmuls(vadds(vmul(h.dN_dy, h.normal), mu * D_dot_N), dDN_dy));
 
             float refraction_distance;
-            v3 colour_refraction = bounce(sc, &rf, bounces_left - 1, &refraction_distance, c);
+            v3 colour_refraction = bounce(sc, &rf, bounces_left - 1, &refraction_distance, c, tree);
 
             /* Beer's law, :348-376 */
             v3 absorption = vsub(Kt, V3(1.0f, 1.0f, 1.0f));
@@ -875,7 +883,8 @@ static void render_tile(const orc_scene * sc, int tile_x, int tile_y, int tile_w
             ray.direction = vmuls(d, inv);
             c->stats.num_primary_rays++;
             float distance;
-            v3 colour = bounce(sc, &ray, sc->config.bounces, &distance, c);
+            tree_t tree = { v3p(cam->position), 0 };
+            v3 colour = bounce(sc, &ray, sc->config.bounces, &distance, c, &tree);
             size_t p = (size_t)j * W + i;
             if (rgb)  { rgb[3 * p] = colour.x; rgb[3 * p + 1] = colour.y; rgb[3 * p + 2] = colour.z; }
             if (dist) dist[p] = distance;
@@ -997,6 +1006,8 @@ void orc_trace_closest_ids(const orc_scene * scene, const float r[18], float out
 typedef struct {
     const orc_scene * sc; const float * rays; const float * maxd; float * out; int32_t * ids; int32_t * occ;
     int32_t k, lo, hi;
+    /* orc_shade_rays alone: its inputs and outputs under their own names */
+    const float * camera; float * rgb; uint32_t * packed; float * dist; int32_t * ray_flags; counters_t * total;
 } batch_t;
 
 static void * closest_worker(void * p) {
@@ -1047,6 +1058,51 @@ int orc_trace_any_n(const orc_scene * scene, int32_t n, const float * rays18, in
     batch_t b; memset(&b, 0, sizeof(b));
     b.sc = scene; b.rays = rays18; b.k = k; b.maxd = max_distance; b.occ = occluded;
     return run_batch(&b, n, threads, any_worker);
+}
+
+/* Raytracer::bounce of n caller-supplied primary rays: what render_tile does per pixel (Raytracer.cpp:61-66) with the ray given instead
+ * of derived from the camera.  One bounce() for both entry points; the counters of a range are added to the call's under a lock. */
+static pthread_mutex_t shade_lock = PTHREAD_MUTEX_INITIALIZER;
+
+static void * shade_worker(void * p) {
+    const batch_t * b = (const batch_t *)p;
+    counters_t c; memset(&c, 0, sizeof(c));
+    for (int32_t i = b->lo; i < b->hi; i++) {
+        const float * r = b->rays + 18 * (size_t)i;
+        if (r[3] == 0.0f && r[4] == 0.0f && r[5] == 0.0f) continue;      /* no ray (+-0 direction; a NaN component compares unequal: a ray) */
+        ray_t ray;
+        ray.origin = v3p(r); ray.direction = v3p(r + 3);
+        ray.dO_dx = v3p(r + 6); ray.dO_dy = v3p(r + 9); ray.dD_dx = v3p(r + 12); ray.dD_dy = v3p(r + 15);
+        tree_t tree = { b->camera ? v3p(b->camera + 3 * (size_t)i) : ray.origin, 0 };
+        c.stats.num_primary_rays++;
+        float distance;
+        const v3 colour = bounce(b->sc, &ray, b->sc->config.bounces, &distance, &c, &tree);
+        if (b->rgb)    { float * o = b->rgb + 3 * (size_t)i; o[0] = colour.x; o[1] = colour.y; o[2] = colour.z; }
+        if (b->packed) { float cc[3] = { colour.x, colour.y, colour.z }; b->packed[i] = orc_plot(cc); }
+        if (b->dist)   b->dist[i] = distance;
+        if (b->ray_flags) b->ray_flags[i] = tree.flags;
+    }
+    pthread_mutex_lock(&shade_lock);
+    const uint64_t * src = (const uint64_t *)&c;
+    uint64_t * dst = (uint64_t *)b->total;
+    for (size_t k = 0; k < sizeof(counters_t) / 8; k++) dst[k] += src[k];
+    pthread_mutex_unlock(&shade_lock);
+    return NULL;
+}
+
+int orc_shade_rays(const orc_scene * scene, int32_t n, const float * rays18, const float * camera3, float * rgb, uint32_t * packed, float * dist,
+                   int32_t * ray_flags, rtx_stats * stats, rtx_work_counters * work, int32_t threads) {
+    if (!scene || n < 0 || (n > 0 && !rays18)) return RTX_ERR_INVALID_ARG;
+    if (scene->config.stack_size < 1 || scene->config.stack_size > RTX_MAX_STACK) return RTX_ERR_LIMIT;
+    pthread_once(&ewa_once, ewa_init);
+    counters_t total; memset(&total, 0, sizeof(total));
+    batch_t b; memset(&b, 0, sizeof(b));
+    b.sc = scene; b.rays = rays18; b.camera = camera3; b.rgb = rgb; b.packed = packed; b.dist = dist; b.ray_flags = ray_flags; b.total = &total;
+    const int rc = run_batch(&b, n, threads, shade_worker);
+    total.work.triangle_hits = 0;   /* as orc_render_tiles */
+    if (stats) *stats = total.stats;
+    if (work)  *work  = total.work;
+    return rc;
 }
 
 /* Texture::sample of n inputs (s, t, ds_dx, ds_dy, dt_dx, dt_dy) on one texture, and how many texels each sample fetched (what one lane of

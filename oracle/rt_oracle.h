@@ -49,6 +49,19 @@ int orc_render_tiles(const orc_scene * scene, int32_t first_tile, int32_t tile_s
                      float * rgb, uint32_t * packed, float * dist,
                      rtx_stats * stats, rtx_work_counters * work, int32_t threads);
 
+/* Raytracer::bounce (with scene->config.bounces) of n caller-supplied primary rays of 18 floats (layout as orc_trace_closest), on `threads`
+ * threads: what orc_render_tiles does per pixel, through the same bounce(), for rays that are no camera's.  Row i of camera3 (n x 3) stands in
+ * for frame.camera.position (Raytracer.cpp:152) in the whole tree of ray i; camera3 == NULL: the ray's own origin does, as in rtx_render_rays.
+ * A ray whose direction is (+-0, +-0, +-0) is no ray: it is not counted and its outputs are left as they are.
+ * rgb: n x 3, packed: n, dist: n (primary hit distance), ray_flags: n — each may be NULL.  ray_flags[i] has ORC_RAY_NONFINITE_ORIGIN set when
+ * a primary or secondary ray of the tree of ray i had a NaN or infinite origin component, or a hit point of the tree has one: that is where its
+ * shadow rays and children start, and it is flagged whether or not the hit spawns any, so the flag is a little wider than the rays themselves.
+ * (The device's packet walk is not defined for such a ray below level 0, csrc/rtx_trace.h ray_is_finite: the GPU tests keep those trees off
+ * the device.) */
+#define ORC_RAY_NONFINITE_ORIGIN 1
+int orc_shade_rays(const orc_scene * scene, int32_t n, const float * rays18, const float * camera3, float * rgb, uint32_t * packed, float * dist,
+                   int32_t * ray_flags, rtx_stats * stats, rtx_work_counters * work, int32_t threads);
+
 /* Window::draw_quad (Window.cpp:87-95): the packed frame through the full-screen triangle of Data/Shaders/vertex.glsl and
  * fragment_fxaa.glsl (fxaa != 0, Config.h:20) or fragment_identity.glsl, into an 8-bit display image (0x00RRGGBB).
  * PARITY UNPINNED: a GL driver runs the reference's shaders and none exists here; conventions assumed where GL leaves room are

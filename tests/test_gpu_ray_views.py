@@ -10,6 +10,8 @@ Everything is compared bit for bit (float arrays as uint32, NaN == NaN), with no
   * adversarial rays (tests/rayset.py, plus NaN / inf rays) and an orthographic grid: the primary-hit AOVs equal rtx_debug_trace_rays
     and the oracle;
   * state, errors, rebinding with work queued, hipGraph replay and several contexts in flight.
+The COLOUR of rays that are no camera's (origins of their own, so the per-ray camera at depth >= 1; adversarial materials and lights) is
+compared with the oracle and the reference's records in tests/test_gpu_shade_rays.py.
 """
 import ctypes as C
 
