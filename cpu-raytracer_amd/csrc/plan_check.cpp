@@ -1,0 +1,330 @@
+// plan_check.cpp — the launch plan of rtx_plan.h on the CPU: `make plan_check` builds this with -fsanitize=address,undefined and runs it.
+// Every traversal kernel produces the same bits, so which kernel a level is handed to shows in no image: the rules and their measured
+// thresholds are pinned here, as named cases of (inputs -> the plan fields that matter).  Needs no GPU and no ROCm.
+#include <stdio.h>
+#include <initializer_list>
+#include <type_traits>
+#include "rtx_plan.h"
+
+static_assert(std::is_trivially_copyable<RenderPlan>::value, "the graph key compares a plan's bytes");
+
+static int failures = 0;
+static const char * current = "";
+#define CASE(name) current = name
+#define CHECK(x) do { if (!(x)) { printf("FAILED [%s] line %d: %s\n", current, __LINE__, #x); failures++; } } while (0)
+
+enum { CW = RTX_RENDER_COUNT_WORK, SIMPLE = RTX_RENDER_SIMPLE_TRACE, CULL = RTX_RENDER_CULL_DEAD_SHADOW_RAYS, SERIAL = RTX_RENDER_SERIAL,
+       LANE = RTX_RENDER_LANE_TRACE, PSTAT = RTX_RENDER_PACKET_STATS, PKC = RTX_RENDER_PACKET_CLOSEST, AOV = RTX_RENDER_AOV };
+static const int NEVER = RTX_MAX_LEVELS + 1;      // a lane_from past every level
+
+// the default frame: one instance, two lights, NUMBER_OF_BOUNCES 3, a reflective material, every mesh with 4-wide records, a 64-tile frame in one batch
+static PlanInputs frame() {
+    PlanInputs in; memset(&in, 0, sizeof(in));
+    in.tile_count = 64; in.batch_tiles = 64;
+    Knobs & K = in.knobs;
+    K.slot_budget = 48ll * 1000 * 1000; K.item_bytes_max = 1ll << 30; K.shade_grid = 4; K.lane_from_level = -1; K.lane_from_level_any = -1;
+    K.split_items = 256; K.resolve_block = 256; K.pk4_order = 1; K.merge_any = true; K.lpt = -1;
+    in.instance_count = 1; in.light_count = 2; in.bounces = 3; in.can_spawn = true; in.all_wide = true;
+    in.stack = StackFigures{ false, 1, 10, 20 };
+    in.n_cu = 256; in.pk_blocks_closest = 1024; in.pk_blocks_any = 1280;
+    return in;
+}
+static PlanInputs frame(uint32_t flags) { PlanInputs in = frame(); in.flags = flags; return in; }
+
+static bool all_closest(const RenderPlan & p, int kernel) { for (int l = 0; l < p.levels; l++) if (p.closest[l] != kernel) return false; return true; }
+static bool all_shade(const RenderPlan & p, int kernel) { for (int l = 0; l < p.levels; l++) if (p.shade[l] != kernel) return false; return true; }
+static bool same(const RenderPlan & a, const RenderPlan & b) { return memcmp(&a, &b, sizeof(a)) == 0; }
+// the shadow-ray schedule as { after_level, stream, kernel, lo, hi, items } rows
+static bool schedule(const RenderPlan & p, std::initializer_list<AnyLaunch> want) {
+    if (p.n_any != (int)want.size()) return false;
+    int i = 0;
+    for (const AnyLaunch & w : want) { if (memcmp(&p.any[i], &w, sizeof(w)) != 0) return false; i++; }
+    return true;
+}
+
+static void modes_and_schedule() {
+    CASE("default frame");
+    {
+        const RenderPlan p = plan_render(frame());
+        CHECK(p.levels == 4 && p.overlap && !p.merged && !p.lane && !p.pstat && !p.cull && !p.plain && !p.heatmap);
+        CHECK(all_closest(p, CLOSEST_PACKET) && all_shade(p, SHADE_PLAIN));
+        CHECK(p.lane_from == NEVER && p.lane_from_closest == NEVER && p.split && p.item_cap == 256);
+        CHECK(schedule(p, { { 0, 1, ANY_PACKET_SPLIT, 0, 0, 1 }, { 3, 1, ANY_PACKET_SPLIT, 1, 3, 1 } }));
+        CHECK(p.shade_blocks == 1024 && p.stream_blocks == 2048 && p.resolve_block == 256 && p.pk_waves_closest == 1024 && p.stats_stride == 1024);
+        CHECK(plan_stats_n(p, 64 * 1024, 0) == 256 && plan_stats_n(p, 64 * 1024, 3) == 64 && plan_level_blocks(1 << 30, 0, 1024) == 1024);
+        const RenderPlan again = plan_render(frame());
+        CHECK(same(p, again));                                        // padding included: a plan starts as zeroes
+    }
+    CASE("instance counts and the split");
+    for (int split = 0; split <= 1; split++) {
+        const struct { int n, any, closest; } rule[] = { { 2, 2, 2 }, { 64, 2, 2 }, { 65, 2, 1 } };
+        for (const auto & r : rule) {
+            PlanInputs in = frame(); in.instance_count = r.n; if (!split) in.knobs.split_items = 0;
+            const RenderPlan p = plan_render(in);
+            CHECK(p.lane_from_closest == r.closest && p.lane_from == (split ? NEVER : r.any) && p.split == split);
+            for (int l = 0; l < p.levels; l++) CHECK(p.closest[l] == (l >= r.closest ? CLOSEST_LANE : CLOSEST_PACKET));
+            if (split) CHECK(schedule(p, { { 0, 1, ANY_PACKET_SPLIT, 0, 0, 1 }, { 3, 1, ANY_PACKET_SPLIT, 1, 3, 1 } }));      // shadow rays stay with the packets
+            else       CHECK(schedule(p, { { 0, 1, ANY_PACKET, 0, 0, 0 }, { 3, 1, ANY_PACKET, 1, 1, 0 }, { 3, 1, ANY_LANE, 2, 3, 0 } }));
+        }
+    }
+    CASE("split knob on, buffer not had");
+    {   // lane_from follows the KNOB: losing the item buffer changes the kernels of the schedule and nothing else
+        PlanInputs in = frame(); in.instance_count = 16;
+        RenderPlan p = plan_render(in);
+        plan_drop_split(p);
+        CHECK(!p.split && p.item_cap == 0 && p.lane_from == NEVER && p.lane_from_closest == 2);
+        CHECK(schedule(p, { { 0, 1, ANY_PACKET, 0, 0, 0 }, { 3, 1, ANY_PACKET, 1, 3, 0 } }));
+        in.all_wide = false;                                              // a mesh without 4-wide records: no split, and the rule of the instance count holds
+        p = plan_render(in);
+        CHECK(!p.split && p.lane_from == 2);
+    }
+    CASE("RTX_LANE_FROM_LEVEL");
+    for (int v : { 0, 1, 2, 99 }) {
+        PlanInputs in = frame(); in.instance_count = 100; in.knobs.lane_from_level = v;
+        const RenderPlan p = plan_render(in);
+        CHECK(p.lane_from == v && p.lane_from_closest == v);              // both rules and the split's raise are overridden
+        for (int l = 0; l < p.levels; l++) CHECK(p.closest[l] == (l >= v ? CLOSEST_LANE : CLOSEST_PACKET));
+        if (v == 0)  CHECK(schedule(p, { { 0, 1, ANY_LANE, 0, 0, 0 }, { 3, 1, ANY_LANE, 1, 3, 0 } }));
+        if (v == 1)  CHECK(schedule(p, { { 0, 1, ANY_PACKET_SPLIT, 0, 0, 1 }, { 3, 1, ANY_LANE, 1, 3, 0 } }));
+        if (v == 2)  CHECK(schedule(p, { { 0, 1, ANY_PACKET_SPLIT, 0, 0, 1 }, { 3, 1, ANY_PACKET_SPLIT, 1, 1, 1 }, { 3, 1, ANY_LANE, 2, 3, 0 } }));
+        if (v == 99) CHECK(schedule(p, { { 0, 1, ANY_PACKET_SPLIT, 0, 0, 1 }, { 3, 1, ANY_PACKET_SPLIT, 1, 3, 1 } }));
+    }
+    CASE("RTX_LANE_FROM_LEVEL_ANY");
+    for (int v : { 0, 1, 99 }) {
+        PlanInputs in = frame(); in.instance_count = 100; in.knobs.lane_from_level_any = v;
+        const RenderPlan p = plan_render(in);
+        CHECK(p.lane_from == v && p.lane_from_closest == 1);              // shadow rays only: closest hits keep their rule
+        in.knobs.lane_from_level = 3;
+        const RenderPlan p2 = plan_render(in);
+        CHECK(p2.lane_from == v && p2.lane_from_closest == 3);
+    }
+    CASE("no material spawns rays");
+    {
+        PlanInputs in = frame(); in.can_spawn = false;
+        for (int b : { 0, 3, 11 }) {
+            in.bounces = b;
+            const RenderPlan p = plan_render(in);
+            CHECK(p.levels == 1 && schedule(p, { { 0, 1, ANY_PACKET_SPLIT, 0, 0, 1 } }));
+        }
+        in.can_spawn = true; in.bounces = 11;
+        CHECK(plan_render(in).levels == RTX_MAX_LEVELS);
+        rtx_material m[2]; memset(m, 0, sizeof(m));
+        CHECK(!plan_can_spawn(m, 2) && !plan_can_spawn(m, 0));
+        m[1].transmittance[2] = -0.0f; CHECK(!plan_can_spawn(m, 2));
+        m[1].transmittance[2] = 1e-30f; CHECK(plan_can_spawn(m, 2));
+        m[1].transmittance[2] = 0.0f; m[0].reflection[1] = __builtin_nanf(""); CHECK(plan_can_spawn(m, 2));      // NaN counts as non-zero: conservative
+    }
+    CASE("no lights");
+    {
+        PlanInputs in = frame(); in.light_count = 0;
+        const RenderPlan p = plan_render(in);
+        CHECK(p.n_any == 0 && !p.overlap && !p.split && p.item_cap == 0 && p.merged);
+        in.flags = SERIAL;
+        CHECK(plan_render(in).n_any == 0);
+    }
+    CASE("serial");
+    {
+        PlanInputs in = frame(SERIAL);
+        RenderPlan p = plan_render(in);
+        CHECK(p.serial && !p.overlap && p.merged && schedule(p, { { 3, 0, ANY_PACKET_SPLIT, 0, 3, 1 } }));
+        in.knobs.merge_any = false;
+        p = plan_render(in);
+        CHECK(!p.merged && schedule(p, { { 0, 0, ANY_PACKET_SPLIT, 0, 0, 1 }, { 1, 0, ANY_PACKET_SPLIT, 1, 1, 1 }, { 2, 0, ANY_PACKET_SPLIT, 2, 2, 1 }, { 3, 0, ANY_PACKET_SPLIT, 3, 3, 1 } }));
+        in.knobs.split_items = 0; in.instance_count = 16;                 // a level at or past lane_from is one per-lane launch
+        p = plan_render(in);
+        CHECK(schedule(p, { { 0, 0, ANY_PACKET, 0, 0, 0 }, { 1, 0, ANY_PACKET, 1, 1, 0 }, { 2, 0, ANY_LANE, 2, 2, 0 }, { 3, 0, ANY_LANE, 3, 3, 0 } }));
+        in.knobs.merge_any = true;
+        p = plan_render(in);
+        CHECK(schedule(p, { { 3, 0, ANY_PACKET, 0, 1, 0 }, { 3, 0, ANY_LANE, 2, 3, 0 } }));
+    }
+}
+
+static void instrumented_modes() {
+    CASE("COUNT_WORK");
+    for (uint32_t extra : { 0u, (uint32_t)CULL, (uint32_t)PSTAT, (uint32_t)LANE, (uint32_t)(CULL | PSTAT | SIMPLE) }) {
+        const RenderPlan p = plan_render(frame(CW | extra));
+        CHECK(p.plain && !p.cull && !p.pstat && !p.overlap && !p.merged && !p.lpt);
+        CHECK(all_closest(p, CLOSEST_PLAIN_COUNT) && all_shade(p, SHADE_COUNT));
+        CHECK(schedule(p, { { 0, 0, ANY_PLAIN_COUNT, 0, 0, 0 }, { 1, 0, ANY_PLAIN_COUNT, 1, 1, 0 }, { 2, 0, ANY_PLAIN_COUNT, 2, 2, 0 }, { 3, 0, ANY_PLAIN_COUNT, 3, 3, 0 } }));
+    }
+    CASE("SIMPLE_TRACE");
+    for (uint32_t extra : { 0u, (uint32_t)CULL, (uint32_t)PSTAT, (uint32_t)LANE }) {
+        const RenderPlan p = plan_render(frame(SIMPLE | extra));
+        CHECK(p.plain && !p.cull && !p.pstat && !p.overlap && !p.merged);
+        CHECK(all_closest(p, CLOSEST_PLAIN) && all_shade(p, SHADE_PLAIN));
+        CHECK(schedule(p, { { 0, 0, ANY_PLAIN, 0, 0, 0 }, { 1, 0, ANY_PLAIN, 1, 1, 0 }, { 2, 0, ANY_PLAIN, 2, 2, 0 }, { 3, 0, ANY_PLAIN, 3, 3, 0 } }));
+    }
+    CASE("LANE_TRACE");
+    for (uint32_t extra : { 0u, (uint32_t)PSTAT }) {                      // pstat is dropped under lane
+        const RenderPlan p = plan_render(frame(LANE | extra));
+        CHECK(p.lane && !p.pstat && !p.plain && p.overlap && all_closest(p, CLOSEST_LANE) && all_shade(p, SHADE_PLAIN));
+        CHECK(schedule(p, { { 0, 1, ANY_LANE, 0, 0, 0 }, { 3, 1, ANY_LANE, 1, 3, 0 } }));
+    }
+    CASE("LANE_TRACE with CULL");
+    {
+        const RenderPlan p = plan_render(frame(LANE | CULL | SERIAL));
+        CHECK(p.cull && all_shade(p, SHADE_CULL) && schedule(p, { { 3, 0, ANY_LANE, 0, 3, 0 } }));
+    }
+    CASE("PACKET_STATS");
+    {
+        PlanInputs in = frame(PSTAT); in.instance_count = 100;            // the instrumented packet kernel at every level, whatever lane_from says
+        RenderPlan p = plan_render(in);
+        CHECK(p.pstat && all_closest(p, CLOSEST_PACKET_STATS) && all_shade(p, SHADE_PLAIN) && !p.lpt);
+        CHECK(schedule(p, { { 0, 1, ANY_PACKET_STATS, 0, 0, 0 }, { 3, 1, ANY_PACKET_STATS, 1, 3, 0 } }));
+        in.flags = PSTAT | CULL | SERIAL;
+        p = plan_render(in);
+        CHECK(p.pstat && p.cull && all_shade(p, SHADE_CULL) && schedule(p, { { 3, 0, ANY_PACKET_STATS, 0, 3, 0 } }));
+    }
+    CASE("CULL alone");
+    {
+        const RenderPlan p = plan_render(frame(CULL));
+        CHECK(p.cull && all_closest(p, CLOSEST_PACKET) && all_shade(p, SHADE_CULL));
+    }
+    CASE("fuse_shade");
+    {
+        PlanInputs in = frame(); in.knobs.fuse_shade = true;
+        RenderPlan p = plan_render(in);
+        CHECK(all_closest(p, CLOSEST_PACKET_FUSED) && all_shade(p, SHADE_NONE) && !p.lpt && plan_stats_n(p, 64 * 1024, 2) == p.pk_waves_closest);
+        in.flags = CULL;
+        p = plan_render(in);
+        CHECK(all_closest(p, CLOSEST_PACKET_FUSED_CULL) && all_shade(p, SHADE_NONE));
+        in.flags = AOV | CULL;                                            // level 0 of an AOV call is never fused
+        p = plan_render(in);
+        CHECK(p.aov && p.closest[0] == CLOSEST_PACKET && p.shade[0] == SHADE_AOV_CULL);
+        for (int l = 1; l < p.levels; l++) CHECK(p.closest[l] == CLOSEST_PACKET_FUSED_CULL && p.shade[l] == SHADE_NONE);
+        in.flags = 0; in.instance_count = 65;                            // lane_from_closest = 1 bounds the fused levels; lane_from (past every level) does not
+        p = plan_render(in);
+        CHECK(p.lane_from_closest == 1 && p.lane_from == NEVER && p.closest[0] == CLOSEST_PACKET_FUSED && p.shade[0] == SHADE_NONE);
+        for (int l = 1; l < p.levels; l++) CHECK(p.closest[l] == CLOSEST_LANE && p.shade[l] == SHADE_PLAIN);
+        for (uint32_t f : { (uint32_t)CW, (uint32_t)SIMPLE, (uint32_t)LANE, (uint32_t)PSTAT }) {      // only the production packet kernel fuses
+            in.flags = f;
+            p = plan_render(in);
+            for (int l = 0; l < p.levels; l++) CHECK(p.shade[l] != SHADE_NONE);
+        }
+    }
+    CASE("AOV");
+    {
+        RenderPlan p = plan_render(frame(AOV));
+        CHECK(p.shade[0] == SHADE_AOV && p.shade[1] == SHADE_PLAIN);
+        p = plan_render(frame(AOV | CW));
+        CHECK(p.shade[0] == SHADE_AOV_COUNT && p.shade[1] == SHADE_COUNT);
+    }
+    CASE("heat map");
+    {
+        PlanInputs in = frame(); in.heatmap = true;
+        RenderPlan p = plan_render(in);
+        CHECK(p.heatmap && p.plain && p.closest[0] == CLOSEST_PLAIN && p.n_any == 0 && !p.lpt);
+        in.flags = CW;
+        p = plan_render(in);
+        CHECK(p.closest[0] == CLOSEST_PLAIN_COUNT && p.n_any == 0);
+    }
+}
+
+static void stack_limits() {
+    CASE("stack limits");
+    const int S = RTX_PK_STACK;
+    auto limits = [](int dt, int blas_any, int blas_shared, bool unfit, bool & lane, bool & pkc) { lane = false; pkc = true; plan_stack_limits(StackFigures{ unfit, dt, blas_any, blas_shared }, lane, pkc); };
+    bool lane, pkc;
+    limits(10, S - 11, 0, false, lane, pkc); CHECK(!lane && pkc);          // dt + 1 + blas_any == RTX_PK_STACK
+    limits(10, S - 10, 0, false, lane, pkc); CHECK(lane && pkc);
+    limits((S - 1) / 2, 0, 0, false, lane, pkc); CHECK(!lane);              // 2 dt + 1 == RTX_PK_STACK - 1 (odd): the last depth that fits
+    limits((S - 1) / 2 + 1, 0, 0, false, lane, pkc); CHECK(lane);
+    limits(10, 0, S - 21, false, lane, pkc); CHECK(!lane && pkc);          // 2 dt + 1 + blas_shared == RTX_PK_STACK
+    limits(10, 0, S - 20, false, lane, pkc); CHECK(!lane && !pkc);
+    limits(1, 1, 1, true, lane, pkc); CHECK(lane && pkc);                   // a mesh beyond the packed entries
+    lane = true; pkc = false; plan_stack_limits(StackFigures{ false, 1, 1, 1 }, lane, pkc); CHECK(lane && !pkc);      // never turns lane off or pk_closest on
+    {   // in a plan: lane and pk_closest move separately, and a depth across a bound is a different plan (the graph-key property)
+        PlanInputs in = frame(PKC); in.stack = StackFigures{ false, 10, S - 11, S - 21 };
+        const RenderPlan fits = plan_render(in);
+        CHECK(!fits.lane && fits.pk_closest && all_closest(fits, CLOSEST_PACKET));
+        in.stack.blas_shared++;
+        const RenderPlan shared_over = plan_render(in);
+        CHECK(!shared_over.lane && !shared_over.pk_closest && !same(fits, shared_over));
+        in.stack.blas_shared--; in.stack.blas_any++;
+        const RenderPlan any_over = plan_render(in);
+        CHECK(any_over.lane && any_over.pk_closest && all_closest(any_over, CLOSEST_LANE) && !same(fits, any_over));
+        PlanInputs a = frame(), b = frame(); a.stack = StackFigures{ false, (S - 1) / 2, 0, 0 }; b.stack = a.stack; b.stack.dt++;
+        CHECK(!same(plan_render(a), plan_render(b)));
+        a.flags = b.flags = LANE | PSTAT;                                 // pstat yields to a lane the trees forced, too
+        CHECK(!plan_render(b).pstat);
+    }
+}
+
+static void lpt_items_graph() {
+    CASE("LPT");
+    {
+        PlanInputs in = frame(); in.tile_count = 4; in.pk_blocks_closest = 32;      // 64 packets over 32 waves: two per wave
+        RenderPlan p = plan_render(in);
+        CHECK(p.lpt && p.lpt_n == 64);
+        in.pk_blocks_closest = 33;
+        CHECK(!plan_render(in).lpt);
+        in.pk_blocks_closest = 32;
+        PlanInputs off = in; off.flags = SERIAL;          CHECK(!plan_render(off).lpt);
+        off = in; off.knobs.graph = true;                   CHECK(!plan_render(off).lpt);
+        off = in; off.batch_tiles = 3;                      CHECK(!plan_render(off).lpt);
+        off = in; off.flags = CW;                           CHECK(!plan_render(off).lpt);
+        off = in; off.flags = SIMPLE;                       CHECK(!plan_render(off).lpt);
+        off = in; off.flags = LANE;                         CHECK(!plan_render(off).lpt);
+        off = in; off.flags = PSTAT;                        CHECK(!plan_render(off).lpt);
+        off = in; off.heatmap = true;                       CHECK(!plan_render(off).lpt);
+        off = in; off.knobs.fuse_shade = true;              CHECK(!plan_render(off).lpt);
+        off = in; off.stack.unfit_mesh = true;              CHECK(!plan_render(off).lpt);
+        off = in; off.knobs.lpt = 0;                        CHECK(!plan_render(off).lpt);
+        PlanInputs on = in; on.knobs.lpt = 1; on.flags = SERIAL; on.pk_blocks_closest = 1024;
+        CHECK(plan_render(on).lpt);                                       // 1: whatever the shape
+        on.knobs.graph = true;
+        CHECK(!plan_render(on).lpt);                                      // but never in a graph call
+    }
+    CASE("item capacity");
+    {
+        PlanInputs in = frame();                                          // 1 280 chunks; expected average 0.45 * 1024 * tiles * lights / chunks
+        CHECK(plan_render(in).item_cap == 256);                           // 3.5 x 46 items: the floor at the knob's value
+        in.knobs.split_items = 64;
+        CHECK(plan_render(in).item_cap == 192);                           // 161 rounded up to whole units of 64
+        in = frame(); in.batch_tiles = 200; in.tile_count = 200;
+        CHECK(plan_render(in).item_cap == 512);                           // 3.5 x 144 = 504
+        in.knobs.item_bytes_max = 1280ll * 48 * 128;
+        CHECK(plan_render(in).item_cap == 128 && plan_render(in).split);  // the cap by item_bytes_max wins over the floor
+        in.knobs.item_bytes_max = 1280ll * 48 * 63;
+        const RenderPlan none = plan_render(in);
+        CHECK(none.item_cap == 0 && !none.split && none.lane_from == NEVER);      // below 64: no split (lane_from still follows the knob)
+        CHECK(schedule(none, { { 0, 1, ANY_PACKET, 0, 0, 0 }, { 3, 1, ANY_PACKET, 1, 3, 0 } }));
+        in = frame(); in.batch_tiles = 100000; in.tile_count = 100000; in.light_count = 4; in.knobs.item_bytes_max = 1ll << 36;
+        CHECK(plan_render(in).item_cap == 1 << 16);
+    }
+    CASE("graph");
+    {
+        PlanInputs in = frame(); in.knobs.graph = true;
+        CHECK(plan_render(in).graph_eligible);
+        in.timing = true;  CHECK(!plan_render(in).graph_eligible);
+        in.timing = false; in.knobs.graph = false; CHECK(!plan_render(in).graph_eligible);
+    }
+    CASE("more tiles than a batch");
+    {
+        PlanInputs in = frame(); in.knobs.graph = true; in.knobs.lpt = 1; in.tile_count = 65;
+        RenderPlan p = plan_render(in);
+        CHECK(!p.graph_eligible && !p.lpt);
+        in.knobs.graph = false;
+        p = plan_render(in);
+        CHECK(!p.graph_eligible && !p.lpt);
+        in.tile_count = 64;
+        CHECK(plan_render(in).lpt);
+    }
+    CASE("the key sees flags and views");
+    {
+        PlanInputs a = frame(), b = frame(); b.views = 1;      // a view call (RTX_CAM_VIEWS)
+        CHECK(!same(plan_render(a), plan_render(b)));
+        b = frame(CULL);
+        CHECK(!same(plan_render(a), plan_render(b)));
+    }
+}
+
+int main() {
+    modes_and_schedule();
+    instrumented_modes();
+    stack_limits();
+    lpt_items_graph();
+    if (failures) { printf("plan_check: %d FAILED\n", failures); return 1; }
+    printf("plan_check: ok\n");
+    return 0;
+}

@@ -34,11 +34,11 @@
 #include "rtx_query.h"
 #include <rocprim/device/device_radix_sort.hpp>      // rtx_update_instances, scenes beyond one workgroup: header-only, part of ROCm
 #include "rtx_hostmem.h"                             // DevBuf, StageRing, grow_keep: every device and pinned allocation has one owner
+#include "rtx_plan.h"                                // Knobs, plan_render: which kernels a render call launches (no HIP in it; plan_check.cpp)
 
 #define SLOT_BUDGET (48ll * 1000 * 1000)      // ray slots per batch of tiles (see plan_batch)
 
-// Tuning knobs (environment, A/B runs and tests): read ONCE per context in rtx_create, validated and clamped there; a value that does not
-// parse or lies outside its range leaves the default in place.  Nothing on the render path calls getenv.
+// Tuning knobs (struct Knobs, rtx_plan.h): read here, once per context in rtx_create
 static long long knob_int(const char * name, long long dflt, long long lo, long long hi) {
     const char * e = getenv(name);
     if (!e || !*e) return dflt;
@@ -53,20 +53,6 @@ static double knob_real(const char * name, double dflt, double lo, double hi) {
     if (end == e || *end != 0 || !(v >= lo && v <= hi)) { fprintf(stderr, "librtx_hip: %s=%s ignored (expected a number in [%g, %g])\n", name, e, lo, hi); return dflt; }
     return v;
 }
-struct Knobs {
-    long long slot_budget;       // RTX_SLOT_BUDGET        ray slots per batch of tiles (plan_batch)
-    long long item_bytes_max;    // RTX_PK_ITEM_BYTES      upper bound of the split walk's item buffer per context
-    int shade_grid;              // RTX_SHADE_GRID         k_shade workgroups per CU
-    int lane_from_level;         // RTX_LANE_FROM_LEVEL    per-lane kernels from this level on (-1: the rule in render_tiles_impl)
-    int lane_from_level_any;     // RTX_LANE_FROM_LEVEL_ANY  the same for shadow rays only (-1: follow the rule)
-    int split_items;             // RTX_PK_SPLIT           split shadow-ray walk: 0 = off, else the smallest item chunk
-    int resolve_block;           // RTX_RESOLVE_BLOCK      k_resolve workgroup size
-    int pk4_order;               // RTX_PK4_ORDER          slot order of the 4-wide records (0: smallest stack need first)
-    bool merge_any, no_wide, no_wide_closest, fail_item_alloc, graph; int lpt;
-    bool fuse_shade;             // RTX_FUSE_SHADE         the closest-hit packet kernel shades its own hits (0: a k_shade launch per level)
-    int update_small_max;        // RTX_UPDATE_SMALL_MAX   rtx_update_instances: scenes up to this many instances take the one-workgroup kernel (0: always the multi-launch path)
-};
-
 struct KernelTime { const char * name; hipEvent_t a, b; };
 
 struct rtx_ctx {
@@ -88,7 +74,7 @@ struct rtx_ctx {
     // rtx_alloc_blas / rtx_build_blas: the scratch block and the kernel arguments of a build
     struct BlasBuild { bool allocated = false; DevBuf block; DevBuild dev; void * sort_tmp = nullptr; size_t sort_bytes = 0; int levels = 0; };
     // max_local_material, inner_depth: for validate_references(), which checks every id a kernel will follow on the host before anything is
-    // launched; packet_ok: the tree fits the packet kernels' packed entries (packet_kernel_limits)
+    // launched; packet_ok: the tree fits the packet kernels' packed entries (plan_stack_limits)
     struct BlasHost { std::vector<DevBuf> arrays; int max_local_material = -1, inner_depth = -1; bool packet_ok = true; BlasRefit refit; BlasBuild build; };
     std::vector<DevBlas> h_blas;
     std::vector<BlasHost> blas;
@@ -1169,27 +1155,18 @@ extern "C" int rtx_read_blas(rtx_ctx * c, int32_t blas_id, rtx_bvh_node * nodes,
     return RTX_OK;
 }
 
-// What the uploaded trees allow the packet kernels (render_tiles_impl, the ray queries): lane = the call takes the per-lane kernels,
-// pk_closest = closest-hit packets may walk shared subtrees together.  Only ever turns lane on and pk_closest off.
-static void packet_kernel_limits(const rtx_ctx * c, bool & lane, bool & pk_closest) {
-    for (size_t b = 0; b < c->h_blas.size(); b++) if (c->h_blas[b].nodes && !c->blas[b].packet_ok) lane = true;      // limits of the packet kernels' packed entries
-    // The packet kernels keep ONE 64-entry stack per wave (RTX_PK_STACK) for the TLAS part and the BLAS part of a walk together, where the
-    // reference has a stack per BVH (BVH_TRAVERSAL_STACK_SIZE each).  Both depths are known here, so the choice is made on the host
-    // and pk_push's overflow path is never taken:  TLAS part = one pending far sibling per level + the iterator entry of the leaf being
-    // visited (closest-hit rays: + one parked sign-split entry per level); BLAS part = the 4-wide records' bound (pk4_need), or one far
-    // sibling per level of the binary walk; the shared closest-hit walk parks sign-split entries there too.  Scenes beyond the bound
-    // (e.g. a chain-shaped TLAS of 60 instances) are traced by the per-lane kernels, whose stacks are per BVH like the reference's.
-    const int dt = c->tlas_inner_depth < 0 ? 0 : c->tlas_inner_depth + 1;
-    int blas_any = 0, blas_shared = 0;
+// The three stack figures plan_stack_limits reads, from the uploaded trees: what render calls and ray queries both decide lane / pk_closest by
+static StackFigures stack_figures(const rtx_ctx * c) {
+    StackFigures s = { false, c->tlas_inner_depth < 0 ? 0 : c->tlas_inner_depth + 1, 0, 0 };
     for (size_t b = 0; b < c->h_blas.size(); b++) {
         if (!c->h_blas[b].nodes) continue;
+        if (!c->blas[b].packet_ok) s.unfit_mesh = true;
         const int depth = c->blas[b].inner_depth + 2;
         const int any = c->h_blas[b].pk4_nodes ? c->h_blas[b].pk4_need : depth;
-        if (any > blas_any) blas_any = any;
-        if (2 * depth > blas_shared) blas_shared = 2 * depth;
+        if (any > s.blas_any) s.blas_any = any;
+        if (2 * depth > s.blas_shared) s.blas_shared = 2 * depth;
     }
-    if (dt + 1 + blas_any > RTX_PK_STACK || 2 * dt + 1 > RTX_PK_STACK) lane = true;
-    if (2 * dt + 1 + blas_shared > RTX_PK_STACK) pk_closest = false;
+    return s;
 }
 
 static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_stride, int32_t tile_count, uint32_t flags, uint32_t * tile_major, int views = RTX_CAM_TILES);
@@ -1197,6 +1174,186 @@ static int aov_targets_of_call(rtx_ctx * c, int64_t pixels, DevAov & out);
 
 extern "C" int rtx_render_tiles(rtx_ctx * c, int32_t first_tile, int32_t tile_stride, int32_t tile_count, uint32_t flags) {
     return render_tiles_impl(c, first_tile, tile_stride, tile_count, flags, nullptr);
+}
+
+// ---- a render call: check -> plan -> allocate -> graph key -> run.  The decisions are plan_render's (rtx_plan.h); this is the only place
+// that collects what they read from the context
+static PlanInputs gather_plan_inputs(const rtx_ctx * c, uint32_t flags, int views, int tile_count, int batch_tiles, bool tile_major) {
+    PlanInputs in; memset(&in, 0, sizeof(in));
+    in.flags = flags; in.views = views; in.tile_count = tile_count; in.batch_tiles = batch_tiles; in.tile_major = tile_major; in.timing = c->timing;
+    in.knobs = c->knobs;
+    in.instance_count = c->scene.instance_count; in.light_count = c->scene.light_count; in.bounces = c->cfg.bounces; in.heatmap = c->scene.heatmap != 0;
+    in.can_spawn = plan_can_spawn(c->h_materials.data(), c->h_materials.size());
+    in.all_wide = all_meshes_wide(c);
+    in.stack = stack_figures(c);
+    in.n_cu = c->n_cu; in.pk_blocks_closest = c->pk_blocks_closest; in.pk_blocks_any = c->pk_blocks_any;
+    return in;
+}
+
+// What the plan wants of the context, before anything of the call is queued and before any capture begins: the stats partials, the split
+// walk's item buffer (the buffer only ever grows; if it cannot be had the plan loses its split, see plan_drop_split), the LPT buffers, and
+// every stream and event the launches will use
+static int alloc_for_plan(rtx_ctx * c, RenderPlan & plan) {
+    if (int rc = ensure(c, c->d_stats_partial, (size_t)(RTX_MAX_LEVELS + 1) * plan.stats_stride * 4 * sizeof(uint32_t))) return rc;
+    c->q.pk_items = nullptr; c->q.pk_item_count = nullptr; c->q.pk_item_cap = 0;
+    if (plan.split) {
+        const size_t chunks = (size_t)c->pk_blocks_any * (RTX_PK_BLOCK / RTX_WAVE);
+        int cap = plan.item_cap;
+        if (cap <= c->item_cap_alloc && c->d_pk_items.p && !c->knobs.fail_item_alloc) cap = c->item_cap_alloc;      // the buffer is there already
+        else {
+            c->item_cap_alloc = 0;
+            const size_t bytes = c->knobs.fail_item_alloc ? ((size_t)1 << 46) : chunks * (size_t)cap * 48;
+            if (ensure(c, c->d_pk_items, bytes) == 0 && ensure(c, c->d_pk_item_count, chunks * 4) == 0) c->item_cap_alloc = cap;
+            else { (void)hipGetLastError(); c->err.clear(); cap = 0; }       // fall back to the in-kernel per-lane phase
+        }
+        if (cap >= 64) { c->q.pk_items = (uint4 *)c->d_pk_items.p; c->q.pk_item_count = (uint32_t *)c->d_pk_item_count.p; c->q.pk_item_cap = cap; }
+        else plan_drop_split(plan);
+    }
+    c->q.pk_cost = nullptr; c->q.pk_lpt_order = nullptr;
+    if (plan.lpt) {
+        if (int rc = ensure(c, c->d_pk_cost, (size_t)plan.lpt_n * 4)) return rc;
+        if (int rc = ensure(c, c->d_pk_order, (size_t)plan.lpt_n * 4)) return rc;
+        if (!c->order_stream) HIP_OK(c, hipStreamCreateWithFlags(&c->order_stream, hipStreamNonBlocking));
+        if (!c->ev_cost) HIP_OK(c, hipEventCreateWithFlags(&c->ev_cost, hipEventDisableTiming));
+        if (!c->ev_order) HIP_OK(c, hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming));
+    }
+    if (plan.overlap && !c->any_stream) HIP_OK(c, hipStreamCreateWithFlags(&c->any_stream, hipStreamNonBlocking));
+    return RTX_OK;
+}
+
+// RTX_PK_LPT, before the launches: the order of the previous call is used only if that call covered the same packets; either way the main
+// stream waits for the previous call's sort, which still reads the cost buffer.  (An LPT call is never a graph call.)
+static int lpt_begin(rtx_ctx * c, const RenderPlan & plan, int32_t first_tile, int32_t tile_stride, int32_t tile_count) {
+    if (!plan.lpt) { c->lpt_valid = false; return RTX_OK; }
+    const int32_t key[5] = { first_tile, tile_stride, tile_count, plan.levels, plan.views };      // view calls and ray calls have key spaces of their own: packets over views x tiles
+    const bool use_order = c->lpt_valid && memcmp(key, c->lpt_key, sizeof(key)) == 0;
+    memcpy(c->lpt_key, key, sizeof(key));
+    c->q.pk_cost = (uint32_t *)c->d_pk_cost.p;
+    if (use_order) c->q.pk_lpt_order = (const uint32_t *)c->d_pk_order.p;
+    if (c->lpt_valid) HIP_OK(c, hipStreamWaitEvent(c->stream, c->ev_order, 0));
+    return RTX_OK;
+}
+
+// the launches that generate primary rays or read the camera take the VIEWS / RAYS instantiation of their kernel in a view / ray call
+template <typename F>
+static void with_views(int views, F && launch) {
+    if (views == RTX_CAM_RAYS) launch(std::integral_constant<int, RTX_CAM_RAYS>()); else if (views) launch(std::integral_constant<int, RTX_CAM_VIEWS>()); else launch(std::integral_constant<int, RTX_CAM_TILES>());
+}
+
+static void launch_closest(rtx_ctx * c, const RenderPlan & plan, const DevScene & sc, const DevQueues & q, int level) {
+    const int kernel = plan.closest[level];
+    const bool fused = kernel == CLOSEST_PACKET_FUSED || kernel == CLOSEST_PACKET_FUSED_CULL;
+    launch_timed(c, fused ? "k_trace_closest_shade" : "k_trace_closest", c->stream, [&] { with_views(plan.views, [&](auto V) { constexpr int VW = decltype(V)::value;
+        const dim3 plain(c->trace_blocks_count), lane(c->trace_blocks_closest), tb(RTX_TRACE_BLOCK), pk(c->pk_blocks_closest), pb(RTX_PK_BLOCK);
+        switch (kernel) {
+        case CLOSEST_PLAIN_COUNT:       hipLaunchKernelGGL((k_trace<false, true, VW>),  plain, tb, 0, c->stream, sc, q, level); break;
+        case CLOSEST_PLAIN:             hipLaunchKernelGGL((k_trace<false, false, VW>), plain, tb, 0, c->stream, sc, q, level); break;
+        case CLOSEST_LANE:              hipLaunchKernelGGL((k_trace_fast<false, VW>),   lane, tb, 0, c->stream, sc, q, level, level); break;
+        case CLOSEST_PACKET_STATS:      hipLaunchKernelGGL((k_packet<false, true, false, false, false, VW>),  pk, pb, 0, c->stream, sc, q, level, level); break;
+        case CLOSEST_PACKET_FUSED_CULL: hipLaunchKernelGGL((k_packet<false, false, false, true, true, VW>),   pk, pb, 0, c->stream, sc, q, level, level); break;
+        case CLOSEST_PACKET_FUSED:      hipLaunchKernelGGL((k_packet<false, false, false, true, false, VW>),  pk, pb, 0, c->stream, sc, q, level, level); break;
+        default:                        hipLaunchKernelGGL((k_packet<false, false, false, false, false, VW>), pk, pb, 0, c->stream, sc, q, level, level); break;
+        }
+    }); });
+}
+
+static void launch_shade(rtx_ctx * c, const RenderPlan & plan, const DevScene & sc, const DevQueues & q, const DevAov & aov_t, int level) {
+    if (plan.shade[level] == SHADE_NONE) return;
+    launch_timed(c, "k_shade", c->stream, [&] { with_views(plan.views, [&](auto V) { constexpr int VW = decltype(V)::value;
+        const dim3 g(plan_level_blocks(q.primary_slots, level, plan.shade_blocks)), b(RTX_SHADE_BLOCK);
+        switch (plan.shade[level]) {
+        case SHADE_AOV_COUNT: hipLaunchKernelGGL((k_shade<true, false, VW, true, DevAov>),  g, b, 0, c->stream, sc, q, level, aov_t); break;
+        case SHADE_AOV_CULL:  hipLaunchKernelGGL((k_shade<false, true, VW, true, DevAov>),  g, b, 0, c->stream, sc, q, level, aov_t); break;
+        case SHADE_AOV:       hipLaunchKernelGGL((k_shade<false, false, VW, true, DevAov>), g, b, 0, c->stream, sc, q, level, aov_t); break;
+        case SHADE_COUNT:     hipLaunchKernelGGL((k_shade<true, false, VW>),  g, b, 0, c->stream, sc, q, level); break;
+        case SHADE_CULL:      hipLaunchKernelGGL((k_shade<false, true, VW>),  g, b, 0, c->stream, sc, q, level); break;
+        default:              hipLaunchKernelGGL((k_shade<false, false, VW>), g, b, 0, c->stream, sc, q, level); break;
+        }
+    }); });
+}
+
+// one entry of the shadow-ray schedule; split walk (RTX_PK_SPLIT): q.pk_items / q.pk_item_cap were sized for the call's largest batch
+static void launch_any(rtx_ctx * c, const AnyLaunch & a, const DevScene & sc, const DevQueues & q) {
+    const hipStream_t st = a.stream ? c->any_stream : c->stream;
+    const dim3 plain(c->trace_blocks_count), lane(c->trace_blocks_any), tb(RTX_TRACE_BLOCK), pk(c->pk_blocks_any), pb(RTX_PK_BLOCK);
+    launch_timed(c, "k_trace_any", st, [&] {
+        switch (a.kernel) {
+        case ANY_PLAIN_COUNT:   hipLaunchKernelGGL((k_trace<true, true>),   plain, tb, 0, st, sc, q, a.lo); break;
+        case ANY_PLAIN:         hipLaunchKernelGGL((k_trace<true, false>),  plain, tb, 0, st, sc, q, a.lo); break;
+        case ANY_LANE:          hipLaunchKernelGGL((k_trace_fast<true>),    lane, tb, 0, st, sc, q, a.lo, a.hi); break;
+        case ANY_PACKET_STATS:  hipLaunchKernelGGL((k_packet<true, true>),  pk, pb, 0, st, sc, q, a.lo, a.hi); break;
+        case ANY_PACKET_SPLIT:  hipLaunchKernelGGL((k_packet<true, false, true>), pk, pb, 0, st, sc, q, a.lo, a.hi); break;
+        default:                hipLaunchKernelGGL((k_packet<true, false>), pk, pb, 0, st, sc, q, a.lo, a.hi); break;
+        }
+    });
+    if (a.items) launch_timed(c, "k_trace_items", st, [&] { hipLaunchKernelGGL(k_items, dim3(c->item_blocks), dim3(RTX_ITEM_BLOCK), 0, st, sc, q, c->pk_blocks_any * (RTX_PK_BLOCK / RTX_WAVE), a.lo); });
+}
+
+// Executes the plan for one batch of tiles (q: the batch's queues).  Main stream: closest(d) -> shade(d) for d = 0 .. levels-1, the shadow-ray
+// schedule's entries after the level they name — on the shadow-ray stream behind an event where the plan overlaps them — then k_resolve from
+// the deepest level up.
+static int run_batch(rtx_ctx * c, const RenderPlan & plan, const DevScene & sc, const DevQueues & q, const DevAov & aov_t, bool first_batch) {
+    begin_batch(c, q.counters, q.pk_heads, (uint32_t)q.primary_slots, plan.plain != 0, first_batch);
+    if (plan.heatmap) {
+        launch_closest(c, plan, sc, q, 0);
+        launch_timed(c, "k_heatmap", c->stream, [&] { with_views(plan.views, [&](auto V) { if constexpr (decltype(V)::value != RTX_CAM_RAYS) hipLaunchKernelGGL((k_heatmap<decltype(V)::value>), dim3(plan.stream_blocks), dim3(256), 0, c->stream, sc, q); }); });
+        return RTX_OK;
+    }
+    int next_any = 0;
+    for (int level = 0; level < plan.levels; level++) {
+        launch_closest(c, plan, sc, q, level);
+        if (plan.lpt && level == 0) {
+            HIP_OK(c, hipEventRecord(c->ev_cost, c->stream)); HIP_OK(c, hipStreamWaitEvent(c->order_stream, c->ev_cost, 0));
+            hipLaunchKernelGGL(k_packet_order, dim3(1), dim3(1024), 0, c->order_stream, (const uint32_t *)c->d_pk_cost.p, (uint32_t *)c->d_pk_order.p, plan.lpt_n);
+            HIP_OK(c, hipEventRecord(c->ev_order, c->order_stream));
+            c->lpt_valid = true;
+        }
+        launch_shade(c, plan, sc, q, aov_t, level);
+        bool joined = false;      // the shadow-ray stream waits for this level's k_shade once
+        for (; next_any < plan.n_any && plan.any[next_any].after_level == level; next_any++) {
+            if (plan.any[next_any].stream && !joined) {
+                const hipEvent_t ev = level == 0 ? c->ev_shade0 : c->ev_shade_last;
+                HIP_OK(c, hipEventRecord(ev, c->stream)); HIP_OK(c, hipStreamWaitEvent(c->any_stream, ev, 0));
+                joined = true;
+            }
+            launch_any(c, plan.any[next_any], sc, q);
+        }
+    }
+    if (plan.overlap) { HIP_OK(c, hipEventRecord(c->ev_any_done, c->any_stream)); HIP_OK(c, hipStreamWaitEvent(c->stream, c->ev_any_done, 0)); }
+    for (int level = plan.levels - 1; level >= 0; level--)
+        launch_timed(c, "k_resolve", c->stream, [&] { with_views(plan.views, [&](auto V) {
+            hipLaunchKernelGGL((k_resolve<decltype(V)::value>), dim3(plan_level_blocks(q.primary_slots, level, plan.stream_blocks) * (256 / plan.resolve_block)), dim3(plan.resolve_block), 0, c->stream, sc, q, level); }); });
+    return RTX_OK;
+}
+
+// hipGraph replay: the kernel arguments of a call are functions of (scene, queues, plan, tile range, AOV targets); while those bytes stay the
+// same the captured graph IS the call.  The plan holds the flags, the views mode and every decision drawn from knobs, tree depths and scene
+// counts, so nothing a launch depends on is missing from the key.  A view call's view range is its tile range (first_tile = first_view * tiles
+// per view) and its cameras are read from device memory at replay; a ray call carries the address of its rays in the queues: a rebind is a new
+// key, new values in the same buffer are read at replay.  The AOV targets are zero for a call without RTX_RENDER_AOV: a rebind is a new key.
+static std::vector<unsigned char> graph_key_of(const rtx_ctx * c, const RenderPlan & plan, int32_t first_tile, int32_t tile_stride, int32_t tile_count, const uint32_t * tile_major, const DevAov & aov_t) {
+    const int32_t range[3] = { first_tile, tile_stride, tile_count };
+    const struct { const void * p; size_t n; } parts[] = { { &c->scene, sizeof(DevScene) }, { &c->q, sizeof(DevQueues) }, { &plan, sizeof(plan) }, { range, sizeof(range) }, { &tile_major, sizeof(tile_major) }, { &aov_t, sizeof(aov_t) } };
+    std::vector<unsigned char> key;
+    for (const auto & part : parts) key.insert(key.end(), (const unsigned char *)part.p, (const unsigned char *)part.p + part.n);
+    return key;
+}
+
+// the end of a capture window, reached on every path out of it: the capture is ended first; on a failure (rc: of the launches) the graph is
+// discarded and graph_key cleared, so the next identical call starts over
+static int graph_finish(rtx_ctx * c, int rc) {
+    hipGraph_t g = nullptr;
+    const hipError_t ce = hipStreamEndCapture(c->stream, &g);
+    hipError_t ie = hipSuccess;
+    if (!rc && ce == hipSuccess && g) ie = hipGraphInstantiate(&c->graph_exec, g, nullptr, nullptr, 0);
+    if (g) hipGraphDestroy(g);
+    if (rc || ce != hipSuccess || !g || ie != hipSuccess) {
+        hipGetLastError(); c->graph_exec = nullptr; c->graph_key.clear();
+        if (!rc) c->err = (ce != hipSuccess || !g) ? "hipGraph capture failed" : "hipGraphInstantiate failed";
+        return rc ? rc : RTX_ERR_HIP;
+    }
+    HIP_OK(c, hipGraphLaunch(c->graph_exec, c->stream));
+    return RTX_OK;
 }
 
 // tile_major != nullptr: the packed level-0 pixels of the i-th rendered tile go to tile_major[i * 1024 ...] (slot order) instead of the framebuffer.
@@ -1209,21 +1366,9 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
     if (int bad = validate_references(c)) return bad;
     if (!views && tile_count > 0 && first_tile + (int64_t)(tile_count - 1) * tile_stride >= (int64_t)frame_tiles(c)) return RTX_ERR_INVALID_ARG;
     hipSetDevice(c->cfg.device);
-    // the launches below that generate primary rays or read the camera take the VIEWS instantiation of their kernel in a view call
-    auto with_views = [views](auto && launch) {
-        if (views == RTX_CAM_RAYS) launch(std::integral_constant<int, RTX_CAM_RAYS>()); else if (views) launch(std::integral_constant<int, RTX_CAM_VIEWS>()); else launch(std::integral_constant<int, RTX_CAM_TILES>());
-    };
-    const bool count_work = (flags & RTX_RENDER_COUNT_WORK) != 0;
-    const bool simple = (flags & RTX_RENDER_SIMPLE_TRACE) != 0;
-    const bool cull = (flags & RTX_RENDER_CULL_DEAD_SHADOW_RAYS) != 0 && !simple && !count_work;
-    bool lane = (flags & RTX_RENDER_LANE_TRACE) != 0;
-    bool pk_closest = (flags & RTX_RENDER_PACKET_CLOSEST) != 0;            // closest-hit packets walk shared subtrees together (default: lanes turn private at once)
-    packet_kernel_limits(c, lane, pk_closest);
-    const bool pstat = (flags & RTX_RENDER_PACKET_STATS) != 0 && !simple && !count_work && !lane;
     // RTX_RENDER_AOV: level 0 takes k_shade<.., AOV = true> with the bound channels' targets; the call's pixel range is the frame, or its views
-    const bool aov = (flags & RTX_RENDER_AOV) != 0;
     DevAov aov_t = {};
-    if (aov) {
+    if (flags & RTX_RENDER_AOV) {
         if (tile_major) { c->err = "RTX_RENDER_AOV is not supported on the rtx_group_* path"; return RTX_ERR_INVALID_ARG; }
         if (c->scene.heatmap) { c->err = "RTX_RENDER_AOV in heat-map mode (a heat-map frame has no shading)"; return RTX_ERR_STATE; }
         if (!c->aov_channels) { c->err = "RTX_RENDER_AOV without channels bound by rtx_bind_aovs"; return RTX_ERR_STATE; }
@@ -1238,93 +1383,20 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
 
     int batch_tiles = 0;
     plan_batch(c, tile_count, batch_tiles);
-    int rc = alloc_queues(c, batch_tiles);
-    if (rc) return rc;
+    if (int rc = alloc_queues(c, batch_tiles)) return rc;
     if (views) {
         // one field for both: the cameras of a view call, or (cast) the rtx_ray records of a ray call, read by the instantiation that knows which
         c->q.views = views == RTX_CAM_RAYS ? (const rtx_camera *)(c->ext_rays ? c->ext_rays : c->d_rays.p) : (const rtx_camera *)c->d_views.p;
         c->q.fb_rgb = (float *)(c->ext_vrgb ? c->ext_vrgb : c->d_vfb_rgb.p);
         c->q.fb_packed = (uint32_t *)(c->ext_vpacked ? c->ext_vpacked : c->d_vfb_packed.p);
     }
-    // Levels that can hold rays: a hit spawns a reflection / refraction ray only where its material's Ks / Kt is not all zero (Raytracer.cpp:204-213,
-    // rtx_shade.h reflection_mask / refraction_mask).  With no such material uploaded the levels >= 1 are provably empty, and their
-    // launches — three per level, each a floor of 7-9 us — are not queued (BASELINE configs[1]: diffuse Monkey.obj with NUMBER_OF_BOUNCES 3).
-    bool can_spawn = false;
-    for (const rtx_material & m : c->h_materials)
-        for (int a = 0; a < 3; a++) if (m.reflection[a] != 0.0f || m.transmittance[a] != 0.0f) can_spawn = true;      // != is true for NaN too: conservative
-    const int levels = can_spawn ? c->cfg.bounces + 1 : 1;
-    const int stream_blocks = c->n_cu * 8;          // k_resolve (256 threads)
-    const int shade_blocks = c->n_cu * c->knobs.shade_grid;      // k_shade (RTX_SHADE_BLOCK = 256 threads, 3 resident blocks per CU at 168 VGPRs)
-    const int pk_waves_closest = c->pk_blocks_closest * (RTX_PK_BLOCK / RTX_WAVE);
-    const int stats_stride = shade_blocks > pk_waves_closest ? shade_blocks : pk_waves_closest;      // per level: one entry per k_shade workgroup, or per wave of the fused packet kernel
-    rc = ensure(c, c->d_stats_partial, (size_t)(RTX_MAX_LEVELS + 1) * stats_stride * 4 * sizeof(uint32_t));
-    if (rc) return rc;
+    RenderPlan plan = plan_render(gather_plan_inputs(c, flags, views, tile_count, batch_tiles, tile_major != nullptr));
+    if (int rc = alloc_for_plan(c, plan)) return rc;
+    if (int rc = lpt_begin(c, plan, first_tile, tile_stride, tile_count)) return rc;
 
-    // Item chunks of the split shadow-ray walk (rtx_packet.h, k_items): one chunk per wave of the packet launch, sized ONCE per call for its
-    // largest batch — ≈0.3 items per shadow ray in the cfg3 frame, the fullest chunk 3x the average, so 3.5x the expected average, in
-    // whole units of 64 items.  The buffer only ever grows, never beyond knobs.item_bytes_max (1 GiB; a chunk that fills up merely makes the
-    // packet keep its nodes, which the kernel supports), and only here, before anything of this call is queued.  If the allocation
-    // fails the pending HIP error is cleared and the call continues with the non-split kernel: a correctly queued frame must not
-    // report RTX_ERR_HIP.  The split walk needs 4-wide records for every mesh.
-    c->q.pk_items = nullptr; c->q.pk_item_count = nullptr; c->q.pk_item_cap = 0;
-    const bool all_wide = all_meshes_wide(c);
-    if (c->knobs.split_items > 0 && c->scene.light_count > 0) {
-        if (all_wide) {
-            const size_t chunks = (size_t)c->pk_blocks_any * (RTX_PK_BLOCK / RTX_WAVE);
-            const double expect = 0.45 * 1024.0 * (double)batch_tiles * c->scene.light_count / (double)chunks;
-            long long cap = c->knobs.split_items;
-            if (cap < (long long)(3.5 * expect)) cap = ((long long)(3.5 * expect) + 63) & ~63ll;
-            const long long cap_max = (c->knobs.item_bytes_max / (long long)(chunks * 48)) & ~63ll;
-            if (cap > cap_max) cap = cap_max;
-            if (cap > (1 << 16)) cap = 1 << 16;
-            if (cap >= 64) {
-                if (cap <= c->item_cap_alloc && c->d_pk_items.p && !c->knobs.fail_item_alloc) cap = c->item_cap_alloc;      // the buffer is there already
-                else {
-                    c->item_cap_alloc = 0;
-                    const size_t bytes = c->knobs.fail_item_alloc ? ((size_t)1 << 46) : chunks * (size_t)cap * 48;
-                    if (ensure(c, c->d_pk_items, bytes) == 0 && ensure(c, c->d_pk_item_count, chunks * 4) == 0) c->item_cap_alloc = (int)cap;
-                    else { (void)hipGetLastError(); c->err.clear(); cap = 0; }       // fall back to the in-kernel per-lane phase
-                }
-                if (cap >= 64) { c->q.pk_items = (uint4 *)c->d_pk_items.p; c->q.pk_item_count = (uint32_t *)c->d_pk_item_count.p; c->q.pk_item_cap = (int)cap; }
-            }
-        }
-    }
-
-    // hipGraph replay: the kernel arguments of a call are functions of (scene, queues, tile range, flags, knobs); while those bytes stay the same the
-    // captured graph IS the call.  Only for single-batch calls without per-kernel timing.
-    // RTX_PK_LPT: the level-0 closest-hit launch takes its packets longest first, by what the same packets cost in the previous call of this context
-    // over the same tiles (costs written by the launch itself, sorted by k_packet_order on a side stream while the rest of the frame runs).
-    // Measured (cfg3): the launch 309 -> 223 us alone, one frame at a time 1.48 -> 1.41 ms; with three frames in flight the tail it removes was
-    // being filled by the other frames' kernels anyway (1.090 -> 1.098 ms), and a launch with one packet per wave has nothing to reorder: so by default only
-    // in the two-stream shape and with at least two packets per wave.
-    const uint32_t lpt_n = (uint32_t)tile_count * 16u;
-    const bool lpt_want = c->knobs.lpt > 0 || (c->knobs.lpt < 0 && !c->serial && lpt_n >= 2u * (uint32_t)pk_waves_closest);
-    const bool lpt = lpt_want && !c->knobs.graph && tile_count <= batch_tiles && !count_work && !simple && !lane && !pstat && !c->scene.heatmap && !c->knobs.fuse_shade;
-    c->q.pk_cost = nullptr; c->q.pk_lpt_order = nullptr;
-    if (lpt) {
-        int lrc = ensure(c, c->d_pk_cost, (size_t)lpt_n * 4); if (!lrc) lrc = ensure(c, c->d_pk_order, (size_t)lpt_n * 4);
-        if (lrc) return lrc;
-        if (!c->order_stream) { HIP_OK(c, hipStreamCreateWithFlags(&c->order_stream, hipStreamNonBlocking)); hipEventCreateWithFlags(&c->ev_cost, hipEventDisableTiming); hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming); }
-        const int32_t key[5] = { first_tile, tile_stride, tile_count, levels, views };      // view calls and ray calls have key spaces of their own: packets over views x tiles
-        const bool use_order = c->lpt_valid && memcmp(key, c->lpt_key, sizeof(key)) == 0;
-        memcpy(c->lpt_key, key, sizeof(key));
-        c->q.pk_cost = (uint32_t *)c->d_pk_cost.p;
-        if (use_order) { c->q.pk_lpt_order = (const uint32_t *)c->d_pk_order.p; hipStreamWaitEvent(c->stream, c->ev_order, 0); }
-        else if (c->lpt_valid) hipStreamWaitEvent(c->stream, c->ev_order, 0);      // the previous call's sort still reads the cost buffer
-    } else c->lpt_valid = false;
     bool capturing = false;
-    if (c->knobs.graph && !c->timing && tile_count <= batch_tiles) {
-        // a view call differs from a tiles call by the cameras and framebuffer pointers of the queues and the views flag; its view range is the
-        // tile range (first_tile = first_view * tiles per view); the cameras themselves are read from device memory at replay.  A ray call
-        // carries the address of its rays in the same field and its own value of the flag: a rebind is a new key, new values in the same buffer are read at replay
-        std::vector<unsigned char> key(sizeof(DevScene) + sizeof(DevQueues) + 6 * sizeof(int32_t) + sizeof(void *) + sizeof(uint32_t) + sizeof(DevAov));
-        unsigned char * kp = key.data();
-        memcpy(kp, &c->scene, sizeof(DevScene)); kp += sizeof(DevScene); memcpy(kp, &c->q, sizeof(DevQueues)); kp += sizeof(DevQueues);
-        const int32_t kv[6] = { first_tile, tile_stride, tile_count, (int32_t)flags, levels, views }; memcpy(kp, kv, sizeof(kv)); kp += sizeof(kv);
-        memcpy(kp, &tile_major, sizeof(void *)); kp += sizeof(void *);
-        // an AOV call also depends on the bound channels and their targets (zero for a call without RTX_RENDER_AOV): a rebind is a new key
-        const uint32_t aov_mask = aov ? c->aov_channels : 0u; memcpy(kp, &aov_mask, sizeof(aov_mask)); kp += sizeof(aov_mask);
-        memcpy(kp, &aov_t, sizeof(DevAov));
+    if (plan.graph_eligible) {
+        std::vector<unsigned char> key = graph_key_of(c, plan, first_tile, tile_stride, tile_count, tile_major, aov_t);
         if (c->graph_exec && key == c->graph_key) {
             HIP_OK(c, hipGraphLaunch(c->graph_exec, c->stream));
             c->stats_pending = true;
@@ -1332,146 +1404,24 @@ static int render_tiles_impl(rtx_ctx * c, int32_t first_tile, int32_t tile_strid
         }
         if (c->graph_exec) { hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
         if (c->graph_warm == key) {           // second identical call: capture (the first one ran eagerly: lazy allocations, stream creation)
-            if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) { capturing = true; c->graph_key = key; }
+            if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) { capturing = true; c->graph_key.swap(key); }
             else hipGetLastError();
-        } else c->graph_warm = key;
+        } else c->graph_warm.swap(key);
     }
-    for (int done = 0; done < tile_count; done += batch_tiles) {
+    int rc = RTX_OK;
+    for (int done = 0; done < tile_count && !rc; done += batch_tiles) {
         const int n = (tile_count - done) < batch_tiles ? (tile_count - done) : batch_tiles;
         DevQueues q = c->q;
-        if (pk_closest) q.pk_defer_t0_closest = q.pk_defer_t0_primary = q.pk_defer_t0;
+        if (plan.pk_closest) q.pk_defer_t0_closest = q.pk_defer_t0_primary = q.pk_defer_t0;
         q.first_tile = first_tile + done * tile_stride; q.tile_stride = tile_stride; q.tile_count = n; q.primary_slots = n * 1024;
         q.tm_packed = tile_major; q.tm_base = done * 1024;
-        q.cull = cull ? 1 : 0;
-        q.stats_partial = (uint32_t *)c->d_stats_partial.p; q.stats_stride = stats_stride;
-        for (int d = 0; d <= RTX_MAX_LEVELS; d++) q.stats_n[d] = 0;
-        const DevScene sc = c->scene;
-        const bool plain = count_work || simple || sc.heatmap;
-        begin_batch(c, q.counters, q.pk_heads, (uint32_t)q.primary_slots, plain, done == 0);
-        // Main stream: closest(d) -> shade(d) for d = 0..D.  Shadow rays depend only on shade, so in the default (fast)
-        // configuration they run on a second stream: any(level 0) starts after shade(0) and overlaps the deeper levels'
-        // closest/shade kernels; the shadow rays of levels 1..D are traced by ONE more launch after shade(D).  This removes
-        // three of the per-launch tails (a persistent trace launch has a ~0.17 ms floor set by its slowest rays).
-        const bool overlap = !count_work && !simple && sc.light_count > 0 && !c->serial;
-        if (overlap && !c->any_stream) HIP_OK(c, hipStreamCreateWithFlags(&c->any_stream, hipStreamNonBlocking));
-        const bool merged = !overlap && !count_work && !simple && c->knobs.merge_any;
-        if (sc.heatmap) {
-            // BVH_VISUALIZE_HEATMAP: bounce() returns right after the primary ray's trace (Raytracer.cpp:97-102), so a frame is one
-            // closest-hit pass in reference pop order (the plain kernel counts the steps) and one colouring pass
-            launch_timed(c, "k_trace_closest", c->stream, [&] { with_views([&](auto V) { constexpr int VW = decltype(V)::value;
-                if (count_work) hipLaunchKernelGGL((k_trace<false, true, VW>),  dim3(c->trace_blocks_count), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, 0);
-                else            hipLaunchKernelGGL((k_trace<false, false, VW>), dim3(c->trace_blocks_count), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, 0); }); });
-            launch_timed(c, "k_heatmap", c->stream, [&] { with_views([&](auto V) { if constexpr (decltype(V)::value != RTX_CAM_RAYS) hipLaunchKernelGGL((k_heatmap<decltype(V)::value>), dim3(stream_blocks), dim3(256), 0, c->stream, sc, q); }); });
-            continue;
-        }
-        // traversal kernels: packet walk (production), per-lane pair fetch (RTX_RENDER_LANE_TRACE), plain pop-and-test (SIMPLE / COUNT_WORK)
-        // Which kernel for which level: a packet's walk of the TLAS costs the UNION of its rays' instances, each entered with its own
-        // transform and per-lane phase, so for the incoherent rays of the deeper levels of a multi-instance scene the per-lane kernels
-        // (refill, per-lane TLAS walk) win by 2.5-4x (cfg5: closest-hit levels 2 / 3 0.43 / 0.45 -> 0.16 / 0.12 ms, shadow rays 0.41 / 0.35 ->
-        // 0.19 / 0.14 ms) while the packet kernels win everywhere else (tools/perlevel3.py).  Both produce the same bits.
-        // With hundreds of instances the closest-hit reflection rays of level 1 already prefer the per-lane kernel (tools/many_instances.py:
-        // 144 instances 0.52 vs 0.40 ms, 576 instances 0.70 vs 0.39 ms), the shadow rays of level 1 do not (0.48 vs 0.8 ms).
-        int lane_from = c->knobs.lane_from_level >= 0 ? c->knobs.lane_from_level : (sc.instance_count > 1 ? 2 : RTX_MAX_LEVELS + 1);
-        const int lane_from_closest = c->knobs.lane_from_level >= 0 ? c->knobs.lane_from_level : (sc.instance_count > 64 ? 1 : lane_from);
-        // With the split walk a shadow-ray packet that enters an instance with few lanes hands the whole visit over as items, and ONE packet
-        // launch for all levels beats a packet launch + a per-lane launch at every instance count measured (tools/any_rule.sh: 16 / 144 / 576
-        // instances 1.54 / 2.24 / 3.01 vs 1.66 / 2.41 / 3.05 ms per frame, cfg5 2.32 vs 2.42): shadow rays then stay with the packets
-        if (c->knobs.lane_from_level < 0 && c->knobs.split_items > 0 && sc.light_count > 0 && all_wide) lane_from = RTX_MAX_LEVELS + 1;
-        if (c->knobs.lane_from_level_any >= 0) lane_from = c->knobs.lane_from_level_any;      // shadow rays only (A/B runs)
-        // Which levels shade their own hits inside the closest-hit packet kernel (k_packet<.., FUSE>, rtx_packet.h) and which get a k_shade
-        // launch (every other closest-hit kernel: per-lane, plain, instrumented).  Decided before anything is launched: k_resolve is told
-        // how many partial tallies each level's shading pass leaves (q.stats_n).
-        // Level 0 of an AOV call always has its k_shade launch: the fused packet kernel has no AOV variant (its VGPR budget is tight).
-        auto level_is_fused = [&](int level) { return c->knobs.fuse_shade && !count_work && !simple && !pstat && !lane && level < lane_from_closest && !(aov && level == 0); };
-        // Grids of the streaming kernels (k_shade, k_resolve: grid-stride loops, any grid is correct) follow the batch: level d of a batch of P
-        // primary slots is given room for P / 2^d rays — the dispatcher spends ~16 ns per workgroup, which is most of a small launch's
-        // time (a 1/8 tile shard's k_shade launches of levels 1-3: 18 us each with 1 024 workgroups for 74 k / 6 k / 1 k rays).
-        auto level_blocks = [&](int level, int full) { const long long want = (((long long)q.primary_slots >> level) + 255) / 256; return (int)std::max(64ll, std::min((long long)full, want)); };
-        for (int level = 0; level < levels; level++) q.stats_n[level] = level_is_fused(level) ? pk_waves_closest : level_blocks(level, shade_blocks);
-        auto launch_closest = [&](int level) {
-            launch_timed(c, level_is_fused(level) ? "k_trace_closest_shade" : "k_trace_closest", c->stream, [&] { with_views([&](auto V) { constexpr int VW = decltype(V)::value;
-                if (count_work)     hipLaunchKernelGGL((k_trace<false, true, VW>),   dim3(c->trace_blocks_count), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, level);
-                else if (simple)    hipLaunchKernelGGL((k_trace<false, false, VW>),  dim3(c->trace_blocks_count), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, level);
-                else if (lane || (!pstat && level >= lane_from_closest)) hipLaunchKernelGGL((k_trace_fast<false, VW>),    dim3(c->trace_blocks_closest), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, level, level);
-                else if (pstat)     hipLaunchKernelGGL((k_packet<false, true, false, false, false, VW>),  dim3(c->pk_blocks_closest), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, level, level);
-                else if (level_is_fused(level) && cull) hipLaunchKernelGGL((k_packet<false, false, false, true, true, VW>),  dim3(c->pk_blocks_closest), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, level, level);
-                else if (level_is_fused(level))         hipLaunchKernelGGL((k_packet<false, false, false, true, false, VW>), dim3(c->pk_blocks_closest), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, level, level);
-                else                hipLaunchKernelGGL((k_packet<false, false, false, false, false, VW>), dim3(c->pk_blocks_closest), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, level, level);
-            }); });
-        };
-        // split shadow-ray walk (RTX_PK_SPLIT): q.pk_items / q.pk_item_cap were sized for this call's largest batch before the loop
-        const bool split = q.pk_items != nullptr;
-        auto launch_items = [&](hipStream_t st, int lo) {
-            if (!split) return;
-            launch_timed(c, "k_trace_items", st, [&] { hipLaunchKernelGGL(k_items, dim3(c->item_blocks), dim3(RTX_ITEM_BLOCK), 0, st, sc, q, c->pk_blocks_any * (RTX_PK_BLOCK / RTX_WAVE), lo); });
-        };
-        auto launch_any = [&](hipStream_t st, int lo, int hi) {
-            if (!count_work && !simple && !lane && !pstat && hi >= lane_from) {      // levels lo .. lane_from-1 by packets, the rest per lane
-                if (lo < lane_from) { launch_timed(c, "k_trace_any", st, [&] { if (split) hipLaunchKernelGGL((k_packet<true, false, true>), dim3(c->pk_blocks_any), dim3(RTX_PK_BLOCK), 0, st, sc, q, lo, lane_from - 1);
-                                                                                 else       hipLaunchKernelGGL((k_packet<true, false>), dim3(c->pk_blocks_any), dim3(RTX_PK_BLOCK), 0, st, sc, q, lo, lane_from - 1); }); launch_items(st, lo); }
-                const int l0 = lo > lane_from ? lo : lane_from;
-                launch_timed(c, "k_trace_any", st, [&] { hipLaunchKernelGGL((k_trace_fast<true>), dim3(c->trace_blocks_any), dim3(RTX_TRACE_BLOCK), 0, st, sc, q, l0, hi); });
-                return;
-            }
-            launch_timed(c, "k_trace_any", st, [&] {
-                if (count_work)     hipLaunchKernelGGL((k_trace<true, true>),   dim3(c->trace_blocks_count), dim3(RTX_TRACE_BLOCK), 0, st, sc, q, lo);
-                else if (simple)    hipLaunchKernelGGL((k_trace<true, false>),  dim3(c->trace_blocks_count), dim3(RTX_TRACE_BLOCK), 0, st, sc, q, lo);
-                else if (lane)      hipLaunchKernelGGL((k_trace_fast<true>),    dim3(c->trace_blocks_any), dim3(RTX_TRACE_BLOCK), 0, st, sc, q, lo, hi);
-                else if (pstat)     hipLaunchKernelGGL((k_packet<true, true>),  dim3(c->pk_blocks_any), dim3(RTX_PK_BLOCK), 0, st, sc, q, lo, hi);
-                else if (split)     hipLaunchKernelGGL((k_packet<true, false, true>), dim3(c->pk_blocks_any), dim3(RTX_PK_BLOCK), 0, st, sc, q, lo, hi);
-                else                hipLaunchKernelGGL((k_packet<true, false>), dim3(c->pk_blocks_any), dim3(RTX_PK_BLOCK), 0, st, sc, q, lo, hi);
-            });
-            if (!count_work && !simple && !lane && !pstat) launch_items(st, lo);
-        };
-        for (int level = 0; level < levels; level++) {
-            launch_closest(level);
-            if (lpt && level == 0) {
-                hipEventRecord(c->ev_cost, c->stream); hipStreamWaitEvent(c->order_stream, c->ev_cost, 0);
-                hipLaunchKernelGGL(k_packet_order, dim3(1), dim3(1024), 0, c->order_stream, (const uint32_t *)c->d_pk_cost.p, (uint32_t *)c->d_pk_order.p, lpt_n);
-                hipEventRecord(c->ev_order, c->order_stream);
-                c->lpt_valid = true;
-            }
-            if (!level_is_fused(level)) launch_timed(c, "k_shade", c->stream, [&] { with_views([&](auto V) { constexpr int VW = decltype(V)::value;
-                const int g = level_blocks(level, shade_blocks);
-                if (aov && level == 0) {
-                    if (count_work) hipLaunchKernelGGL((k_shade<true, false, VW, true, DevAov>),  dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level, aov_t);
-                    else if (cull)  hipLaunchKernelGGL((k_shade<false, true, VW, true, DevAov>),  dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level, aov_t);
-                    else            hipLaunchKernelGGL((k_shade<false, false, VW, true, DevAov>), dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level, aov_t);
-                }
-                else if (count_work) hipLaunchKernelGGL((k_shade<true, false, VW>),  dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level);
-                else if (cull)  hipLaunchKernelGGL((k_shade<false, true, VW>),  dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level);
-                else            hipLaunchKernelGGL((k_shade<false, false, VW>), dim3(g), dim3(RTX_SHADE_BLOCK), 0, c->stream, sc, q, level);
-            }); });
-            if (sc.light_count == 0) continue;
-            if (overlap) {
-                if (level == 0) {
-                    hipEventRecord(c->ev_shade0, c->stream);
-                    hipStreamWaitEvent(c->any_stream, c->ev_shade0, 0);
-                    launch_any(c->any_stream, 0, 0);
-                }
-                if (level == levels - 1 && levels > 1) {
-                    hipEventRecord(c->ev_shade_last, c->stream);
-                    hipStreamWaitEvent(c->any_stream, c->ev_shade_last, 0);
-                    launch_any(c->any_stream, 1, levels - 1);
-                }
-            } else if (merged) {
-                // shadow rays only feed k_resolve: all levels' shadow rays are traced by ONE launch after the last shade
-                if (level == levels - 1) launch_any(c->stream, 0, levels - 1);
-            } else launch_any(c->stream, level, level);
-        }
-        if (overlap) { hipEventRecord(c->ev_any_done, c->any_stream); hipStreamWaitEvent(c->stream, c->ev_any_done, 0); }
-        for (int level = levels - 1; level >= 0; level--)
-            launch_timed(c, "k_resolve", c->stream, [&] { with_views([&](auto V) {
-                hipLaunchKernelGGL((k_resolve<decltype(V)::value>), dim3(level_blocks(level, stream_blocks) * (256 / c->knobs.resolve_block)), dim3(c->knobs.resolve_block), 0, c->stream, sc, q, level); }); });
+        q.cull = plan.cull;
+        q.stats_partial = (uint32_t *)c->d_stats_partial.p; q.stats_stride = plan.stats_stride;
+        for (int d = 0; d <= RTX_MAX_LEVELS; d++) q.stats_n[d] = d < plan.levels && !plan.heatmap ? plan_stats_n(plan, q.primary_slots, d) : 0;
+        rc = run_batch(c, plan, c->scene, q, aov_t, done == 0);
     }
-    if (capturing) {
-        hipGraph_t g = nullptr;
-        if (hipStreamEndCapture(c->stream, &g) != hipSuccess || !g) { hipGetLastError(); c->graph_key.clear(); c->err = "hipGraph capture failed"; return RTX_ERR_HIP; }
-        hipError_t e = hipGraphInstantiate(&c->graph_exec, g, nullptr, nullptr, 0);
-        hipGraphDestroy(g);
-        if (e != hipSuccess) { hipGetLastError(); c->graph_exec = nullptr; c->graph_key.clear(); c->err = "hipGraphInstantiate failed"; return RTX_ERR_HIP; }
-        HIP_OK(c, hipGraphLaunch(c->graph_exec, c->stream));
-    }
+    if (capturing) rc = graph_finish(c, rc);      // no path leaves a capture window open
+    if (rc) return rc;
     HIP_OK(c, hipGetLastError());
     c->stats_pending = true;
     return RTX_OK;
@@ -2151,7 +2101,7 @@ extern "C" int rtx_query_closest(rtx_ctx * c, const void * rays_dev, int64_t n, 
     DevQueues q;
     if (int rc = query_queues(c, n, q)) return rc;
     bool lane = (flags & RTX_RENDER_LANE_TRACE) != 0, pk_closest = (flags & RTX_RENDER_PACKET_CLOSEST) != 0;
-    packet_kernel_limits(c, lane, pk_closest);
+    plan_stack_limits(stack_figures(c), lane, pk_closest);
     if (pk_closest) q.pk_defer_t0_closest = q.pk_defer_t0_primary = q.pk_defer_t0;
     const DevScene sc = c->scene;
     DevScene sc_resolve = sc; sc_resolve.diff_enabled = 0;          // the differentials are zero and no channel reports a RayHit differential
@@ -2184,7 +2134,7 @@ extern "C" int rtx_query_occluded(rtx_ctx * c, const void * segments_dev, int64_
     if (int rc = query_queues(c, n, q)) return rc;
     q.shadow_explicit = 1;
     bool lane = (flags & RTX_RENDER_LANE_TRACE) != 0, pk_closest = false;
-    packet_kernel_limits(c, lane, pk_closest);
+    plan_stack_limits(stack_figures(c), lane, pk_closest);
     DevScene sc = c->scene; sc.light_count = 1;                     // one explicit segment (k_query_fill_segments), whatever lights the frame has: none are read
     for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
         const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/rtx.h"
+#include "rtx_limits.h"          // RTX_MAX_LEVELS, RTX_WAVE, RTX_PK_BLOCK, RTX_PK_STACK
 
 // Per-lane pointers to BVH nodes / triangles / texels come out of device tables, so the compiler cannot prove their address space and
 // would emit FLAT loads (LDS-aperture check, lgkmcnt + vmcnt).  They always point into HBM: say so (global_load_dwordx4).
@@ -22,12 +23,10 @@ static __device__ __forceinline__ float3 gld3(rtx_gptr p, int i) {
     return make_float3(v.x, v.y, v.z);
 }
 
-#define RTX_MAX_LEVELS   12          // NUMBER_OF_BOUNCES + 1 wavefront levels supported
-#define RTX_TRI_STRIDE   4           // float4 per hot triangle on the device: p0, e1, e2 + padding = one 64-byte line per triangle
+#define RTX_TRI_STRIDE  4           // float4 per hot triangle on the device: p0, e1, e2 + padding = one 64-byte line per triangle
 #ifndef RTX_LDS_STACK
 #define RTX_LDS_STACK    16          // traversal stack entries kept in LDS per lane (4 KiB per wave); deeper entries spill to HBM
 #endif
-#define RTX_WAVE         64
 #define RTX_TRACE_BLOCK  256         // 4 waves per workgroup
 
 // prim codes stored in a hit record (w of h0)

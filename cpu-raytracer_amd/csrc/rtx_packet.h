@@ -38,11 +38,7 @@
 #include "rtx_trace.h"
 #include "rtx_shade.h"          // shade_ray: the closest-hit packet kernel shades its own hits (FUSE)
 
-#ifndef RTX_PK_BLOCK
-#define RTX_PK_BLOCK    64           // the waves of a packet launch are independent: one wave per workgroup finds room beside other frames' kernels
-                                     // soonest (with k_items at 64 too: 1.318 -> 1.275 ms per frame; either one alone: no change)
-#endif
-#define RTX_PK_STACK    64           // packet stack entries per wave = lanes of the stack VGPRs
+// RTX_PK_BLOCK and RTX_PK_STACK: rtx_limits.h (the host's launch plan reads them too)
 #define RTX_PK_CLASSES  8            // packet-queue heads per launch (packet k belongs to head k % 8): spreads the fetch atomics over 8 addresses
 #ifndef RTX_PK_WAVES_ANY
 #define RTX_PK_WAVES_ANY 5           // __launch_bounds__ min waves per SIMD (93 VGPRs unconstrained; forcing 8 waves spills 26 dwords per lane)

@@ -338,7 +338,7 @@ def test_shadow_walk_uses_wide_records_for_reference_trees_and_binary_walk_other
 @pytest.mark.parametrize("lane_from", ["99", "1", "3"])
 @pytest.mark.parametrize("name", ["dynamic", "tori16", "materials_aniso", "coincident"])
 def test_per_level_kernel_selection_changes_nothing(api, name, lane_from, monkeypatch):
-    """Multi-instance scenes trace levels >= 2 with the per-lane kernels by default (csrc/rtx_api.hip, `lane_from`); whatever the split —
+    """Multi-instance scenes trace levels >= 2 with the per-lane kernels by default (csrc/rtx_plan.h, `lane_from`); whatever the split —
     packets at every level (99), per-lane from level 1 or 3 — the frame is the reference's, in both launch shapes."""
     monkeypatch.setenv("RTX_LANE_FROM_LEVEL", lane_from)
     sc, g = util.load_golden(name)

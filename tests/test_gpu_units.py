@@ -366,6 +366,62 @@ def test_levels_that_cannot_hold_rays_are_not_launched(api):
     assert launches["mirror"].count("k_shade") == 4 and launches["mirror"].count("k_resolve") == 4 and launches["mirror"].count("k_trace_closest") == 4, launches["mirror"]
 
 
+# One call of the `dynamic` golden (6 instances, 3 lights, reflective and refractive materials, NUMBER_OF_BOUNCES 3) per mode: (tag, render
+# flags, knobs set while the context is created, the call's launches in queueing order).  C = k_trace_closest, CS = k_trace_closest_shade,
+# S = k_shade, A = k_trace_any, I = k_trace_items, R = k_resolve.  Recorded from the commit before the launch plan existed (d4ec3fe).
+PLAN_LAUNCH_NAMES = {"C": "k_trace_closest", "CS": "k_trace_closest_shade", "S": "k_shade", "A": "k_trace_any", "I": "k_trace_items", "R": "k_resolve"}
+PLAN_LAUNCHES = [
+    ('serial', {'serial': True}, {},
+     'C S C S C S C S A I R R R R'),
+    ('default', {}, {},
+     'C S A I C S C S C S A I R R R R'),
+    ('serial+lane_trace', {'serial': True, 'lane_trace': True}, {},
+     'C S C S C S C S A R R R R'),
+    ('serial+simple_trace', {'serial': True, 'simple_trace': True}, {},
+     'C S A C S A C S A C S A R R R R'),
+    ('serial+count_work', {'serial': True, 'count_work': True}, {},
+     'C S A C S A C S A C S A R R R R'),
+    ('serial+packet_stats', {'serial': True, 'packet_stats': True}, {},
+     'C S C S C S C S A R R R R'),
+    ('serial RTX_FUSE_SHADE=1', {'serial': True}, {'RTX_FUSE_SHADE': '1'},
+     'CS CS C S C S A I R R R R'),
+    ('serial RTX_LANE_FROM_LEVEL=1', {'serial': True}, {'RTX_LANE_FROM_LEVEL': '1'},
+     'C S C S C S C S A I A R R R R'),
+    ('serial RTX_SERIAL_MERGE_ANY=0', {'serial': True}, {'RTX_SERIAL_MERGE_ANY': '0'},
+     'C S A I C S A I C S A I C S A I R R R R'),
+    ('serial RTX_PK_SPLIT=0', {'serial': True}, {'RTX_PK_SPLIT': '0'},
+     'C S C S C S C S A A R R R R'),
+]
+
+
+def test_a_call_launches_what_its_plan_says(api, monkeypatch):
+    """Every traversal kernel produces the same bits, so the frame cannot show which kernel a level was handed to, nor how many launches
+    a call took: the launch plan (csrc/rtx_plan.h, pinned rule by rule on the CPU by csrc/plan_check.cpp) is checked here end to end, as the
+    ordered kernel names of one call per mode against the lists the code had before the plan was split out of the render call.  In the
+    default mode two streams interleave the records: the per-name counts are compared.  Each frame is also the golden's, bit for bit."""
+    import collections
+    sc, g = util.load_golden("dynamic")
+    assert len(sc.instances) > 1 and int(sc.config["bounces"][0]) >= 2 and float(np.asarray(sc.materials["reflection"]).max()) > 0.0
+    for tag, flags, env, launches in PLAN_LAUNCHES:
+        with monkeypatch.context() as m:
+            for k, v in env.items():
+                m.setenv(k, v)
+            r = api.Renderer(sc)                 # the knobs are read once, when the context is created
+        r.render(**flags)
+        r.enable_timing(True)
+        out = r.render(**flags)
+        names = [k for k, _ in r.kernel_times()]
+        r.enable_timing(False)
+        want = [PLAN_LAUNCH_NAMES[s] for s in launches.split()]
+        print(tag, names)
+        if "serial" in flags:
+            assert names == want, (tag, names)
+        else:
+            assert collections.Counter(names) == collections.Counter(want), (tag, names)
+        cmp = util.compare_to_golden(out, g)
+        assert cmp["stats_equal"] and cmp["max_abs"] == 0.0 and cmp["n_diff_pixels"] == 0 and cmp["packed_mismatch"] == 0, (tag, cmp)
+
+
 @pytest.mark.parametrize("name", ["materials_aniso", "dynamic", "monkey_small"])
 def test_graph_replay_of_identical_calls_changes_nothing(api, name, monkeypatch):
     """RTX_GRAPH=1: the second identical rtx_render_tiles call (same scene, queues, tile range, flags) is captured into a hipGraph, later ones replay it

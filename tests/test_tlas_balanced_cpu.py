@@ -4,7 +4,7 @@ sequentially, so what holds here is what the device tree is compared with bit fo
 Checked for every input: the indices are a permutation, every leaf box is its instance's box after AABB::fix_if_needed, the split-axis bits
 are 1..3, a NaN inner box covers only instances whose own box is not finite, the deepest inner node sits at the closed-form depth ceil(log2 n) - 1, holes are zero, two runs give the same bytes; for finite
 input also that every inner node's stored box encloses its children's stored boxes componentwise.  The bounds are not measured: they are
-the properties the host relies on before any kernel runs (validate_references, the packet-stack rule of render_tiles_impl).
+the properties the host relies on before any kernel runs (validate_references, the packet-stack rule of plan_stack_limits, csrc/rtx_plan.h).
 """
 import ctypes as C
 
