@@ -1155,6 +1155,40 @@ extern "C" int rtx_read_blas(rtx_ctx * c, int32_t blas_id, rtx_bvh_node * nodes,
     return RTX_OK;
 }
 
+// The layouts derived from the lane layout, as the kernels read them now: plain copies after a wait for the stream, nothing is launched and
+// nothing of the context changes.  blas_id -1: the TLAS of the frame in the packet layout.
+extern "C" int rtx_debug_read_layouts(rtx_ctx * c, int32_t blas_id, int32_t * info8, float * pk_nodes, float * pk4_nodes, float * pk4c_nodes,
+                                      float * planes_x, float * planes_y, float * planes_z) {
+    if (!c) return RTX_ERR_INVALID_ARG;
+    if (blas_id < -1 || blas_id >= (1 << 20)) { c->err = "rtx_debug_read_layouts: bad id"; return RTX_ERR_INVALID_ARG; }
+    int32_t info[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    if (blas_id == -1) {
+        if (!c->frame_set) { c->err = "rtx_debug_read_layouts before rtx_set_frame"; return RTX_ERR_STATE; }
+        hipSetDevice(c->cfg.device);
+        HIP_OK(c, hipStreamSynchronize(c->stream));
+        const DevScene & s = c->scene;
+        info[0] = s.tlas_node_count;
+        if (info8) memcpy(info8, info, sizeof(info));
+        if (pk_nodes && s.tlas_node_count) HIP_OK(c, hipMemcpy(pk_nodes, s.pk_tlas_nodes, (size_t)s.tlas_node_count * 32, hipMemcpyDeviceToHost));
+        return RTX_OK;
+    }
+    if ((size_t)blas_id >= c->h_blas.size() || !c->h_blas[blas_id].nodes) { c->err = "rtx_debug_read_layouts: no BLAS uploaded under that id"; return RTX_ERR_STATE; }
+    hipSetDevice(c->cfg.device);
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    const DevBlas & B = c->h_blas[blas_id];
+    info[0] = B.node_count; info[1] = B.pk4_nodes ? 1 : 0; info[2] = B.pk4c_nodes ? 1 : 0;
+    for (int a = 0; a < 3; a++) info[3 + a] = B.plane_count[a];
+    if (info8) memcpy(info8, info, sizeof(info));
+    const size_t wide_bytes = ((size_t)4 * B.node_count + 8) * 16;
+    if (pk_nodes) HIP_OK(c, hipMemcpy(pk_nodes, B.pk_nodes, (size_t)B.node_count * 32, hipMemcpyDeviceToHost));
+    if (pk4_nodes && B.pk4_nodes) HIP_OK(c, hipMemcpy(pk4_nodes, B.pk4_nodes, wide_bytes, hipMemcpyDeviceToHost));
+    if (pk4c_nodes && B.pk4c_nodes) HIP_OK(c, hipMemcpy(pk4c_nodes, B.pk4c_nodes, wide_bytes, hipMemcpyDeviceToHost));
+    float * const planes[3] = { planes_x, planes_y, planes_z };
+    for (int a = 0; a < 3; a++)
+        if (planes[a] && B.plane_count[a]) HIP_OK(c, hipMemcpy(planes[a], B.planes[a], (size_t)B.plane_count[a] * 4, hipMemcpyDeviceToHost));
+    return RTX_OK;
+}
+
 // The three stack figures plan_stack_limits reads, from the uploaded trees: what render calls and ray queries both decide lane / pk_closest by
 static StackFigures stack_figures(const rtx_ctx * c) {
     StackFigures s = { false, c->tlas_inner_depth < 0 ? 0 : c->tlas_inner_depth + 1, 0, 0 };

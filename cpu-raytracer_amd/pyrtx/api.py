@@ -26,7 +26,7 @@ EXPORTS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error", "rt
            "rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer", "rtx_bind_aovs", "rtx_read_aovs",
            "rtx_set_rays", "rtx_bind_rays", "rtx_render_rays", "rtx_update_instances", "rtx_read_frame_state",
            "rtx_bind_blas_vertices", "rtx_refit_blas", "rtx_read_blas", "rtx_alloc_blas", "rtx_build_blas",
-           "rtx_query_closest", "rtx_query_occluded"]
+           "rtx_query_closest", "rtx_query_occluded", "rtx_debug_read_layouts"]
 # newer than the A/B variants tools/ab.py may load (RTX_HIP_LIB = a library built from an older commit): bound when the library has them,
 # otherwise a call raises AttributeError (undefined symbol)
 VIEW_EXPORTS = ("rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer")
@@ -36,6 +36,7 @@ UPDATE_EXPORTS = ("rtx_update_instances", "rtx_read_frame_state")
 REFIT_EXPORTS = ("rtx_bind_blas_vertices", "rtx_refit_blas", "rtx_read_blas")
 BUILD_EXPORTS = ("rtx_alloc_blas", "rtx_build_blas")
 QUERY_EXPORTS = ("rtx_query_closest", "rtx_query_occluded")
+LAYOUT_EXPORTS = ("rtx_debug_read_layouts",)
 RTX_UPDATE_MAX_INSTANCES = 65536
 
 RTX_RENDER_COUNT_WORK = 1
@@ -152,8 +153,10 @@ def load_library(path: Optional[str] = None):
     if hasattr(lib, "rtx_query_closest"):
         lib.rtx_query_closest.argtypes = [vp, vp, C.c_int64, u32, C.POINTER(RtxQueryBuffers), u32]
         lib.rtx_query_occluded.argtypes = [vp, vp, C.c_int64, vp, u32]
+    if hasattr(lib, "rtx_debug_read_layouts"):
+        lib.rtx_debug_read_layouts.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
     for name in EXPORTS:
-        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS and not hasattr(lib, name):
+        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + LAYOUT_EXPORTS and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         if name not in ("rtx_last_error",):
@@ -833,6 +836,26 @@ class Renderer:
         nodes = np.zeros(n, sio.BVH_NODE); hot = np.zeros(m, sio.TRI_HOT); cold = np.zeros(m, sio.TRI_COLD)
         self._chk(self.lib.rtx_read_blas(self.ctx, int(blas_id), nodes.ctypes.data, hot.ctypes.data, cold.ctypes.data), "rtx_read_blas")
         return sio.Blas(nodes, hot, cold, off, src)
+
+    def debug_read_layouts(self, blas_id: int = -1) -> Dict:
+        """The node layouts derived from the lane layout, as the kernels read them now (rtx_debug_read_layouts; waits for the stream), as
+        uint32 bit patterns.  A BLAS id: {"pk": (n, 8), "pk4": (2n + 4, 8) or None, "pk4c": (2n + 4, 8) or None, "planes": [x, y, z]} — a
+        row is (min.x, min.y, max.x, max.y, min.z, max.z, first, count / meta), None = the mesh keeps that binary walk.  -1: {"pk": (n, 8)}
+        of the current frame's TLAS."""
+        info = np.zeros(8, np.int32)
+        self._chk(self.lib.rtx_debug_read_layouts(self.ctx, int(blas_id), info.ctypes.data, None, None, None, None, None, None), "rtx_debug_read_layouts")
+        n = int(info[0])
+        pk = np.zeros((n, 8), np.uint32)
+        if blas_id < 0:
+            self._chk(self.lib.rtx_debug_read_layouts(self.ctx, int(blas_id), None, pk.ctypes.data, None, None, None, None, None), "rtx_debug_read_layouts")
+            return {"pk": pk}
+        pk4 = np.zeros((2 * n + 4, 8), np.uint32) if info[1] else None
+        pk4c = np.zeros((2 * n + 4, 8), np.uint32) if info[2] else None
+        planes = [np.zeros(int(info[3 + a]), np.uint32) for a in range(3)]
+        self._chk(self.lib.rtx_debug_read_layouts(self.ctx, int(blas_id), None, pk.ctypes.data, None if pk4 is None else pk4.ctypes.data,
+                                                  None if pk4c is None else pk4c.ctypes.data, *(p.ctypes.data if p.size else None for p in planes)),
+                  "rtx_debug_read_layouts")
+        return {"pk": pk, "pk4": pk4, "pk4c": pk4c, "planes": planes}
 
     # ---- ray queries (include/rtx.h: rtx_query_closest / rtx_query_occluded) ---------------------------------------------------------
     def _query_rows(self, name: str, rows, width: int, n: Optional[int]):

@@ -657,6 +657,15 @@ int rtx_debug_blas_wide(rtx_ctx * ctx, int32_t blas_id, int32_t * stack_need);
 /* the per-lane part of the closest-hit packet walk of an uploaded mesh: *stack_need = stack entries a lane's walk of the ordered 4-wide records
  * can need, or -1 when the mesh keeps the binary walk (boxes not nested / a leaf of 16+ triangles / 2^24+ nodes or triangles) */
 int rtx_debug_blas_wide_closest(rtx_ctx * ctx, int32_t blas_id, int32_t * stack_need);
+/* the node layouts derived from the lane layout, as the kernels read them now, to host (beside rtx_read_blas / rtx_read_frame_state: waits
+ * for the stream, plain device-to-host copies, launches nothing, changes nothing).  info8[0] = node slots n, [1] / [2] = 1 when the mesh has the
+ * shadow-ray / the closest-hit 4-wide records, [3..5] = floats in the x / y / z plane list, [6..7] = 0.  pk_nodes: n x 8 floats (min.x, min.y,
+ * max.x, max.y, min.z, max.z, left_or_first, count); pk4_nodes, pk4c_nodes: (2n + 4) record slots x 8 floats (the same box order, first,
+ * leaf count / meta), left alone when the mesh has none; planes_*: the sorted plane lists.  Any pointer may be NULL (call once with the arrays
+ * NULL to learn the sizes).  blas_id -1: the TLAS of the current frame: info8[0] = its node slots, pk_nodes its packet layout, no other array
+ * is written.  RTX_ERR_INVALID_ARG: an id below -1 or above the id range; RTX_ERR_STATE: no BLAS uploaded under that id / before rtx_set_frame. */
+int rtx_debug_read_layouts(rtx_ctx * ctx, int32_t blas_id, int32_t * info8, float * pk_nodes, float * pk4_nodes, float * pk4c_nodes,
+                           float * planes_x, float * planes_y, float * planes_z);
 /* Sky::sample (Sky.cpp:28-68) of the uploaded sky at n directions */
 int rtx_debug_sky_sample(rtx_ctx * ctx, const float * directions_xyz, float * out_rgb, int32_t n);
 

@@ -184,7 +184,7 @@ def test_single_leaf_mesh(api, name, k):
 
 def test_group_attach_and_debug_entry_points_refuse_bad_arguments(api):
     """Status codes instead of faults: rtx_group_attach with a foreign resolution / the base itself / no group, rtx_debug_blas_wide with an
-    unknown mesh id."""
+    unknown mesh id, rtx_debug_read_layouts with a bad id, an id nothing was uploaded under and before a frame was set."""
     import ctypes as C
     sc, _ = util.load_golden("cube")
     sc2, _ = util.load_golden("monkey_small")
@@ -201,6 +201,21 @@ def test_group_attach_and_debug_entry_points_refuse_bad_arguments(api):
     need = C.c_int32(0)
     assert r.lib.rtx_debug_blas_wide(r.ctx, 99, C.byref(need)) == 1
     assert r.lib.rtx_debug_blas_wide(r.ctx, 0, None) == 1
+    # rtx_debug_read_layouts: the status codes of rtx_read_blas / rtx_read_frame_state, every destination optional
+    nul = (None,) * 7
+    assert r.lib.rtx_debug_read_layouts(None, 0, *nul) == 1
+    assert r.lib.rtx_debug_read_layouts(r.ctx, -2, *nul) == 1 and r.lib.rtx_debug_read_layouts(r.ctx, 1 << 20, *nul) == 1
+    assert r.lib.rtx_debug_read_layouts(r.ctx, 99, *nul) == 5                       # no BLAS uploaded under that id
+    r_empty = api.Renderer(sc, upload=False)
+    assert r.lib.rtx_debug_read_layouts(r_empty.ctx, -1, *nul) == 5 and r.lib.rtx_debug_read_layouts(r_empty.ctx, 0, *nul) == 5     # before rtx_set_frame / any upload
+    assert r.lib.rtx_debug_read_layouts(r.ctx, 0, *nul) == 0 and r.lib.rtx_debug_read_layouts(r.ctx, -1, *nul) == 0
+    info = np.full(8, -7, np.int32)
+    assert r.lib.rtx_debug_read_layouts(r.ctx, 0, info.ctypes.data, *nul[1:]) == 0
+    assert info[0] == len(sc.blas[0].nodes) and (info[3:6] > 0).all() and (info[6:] == 0).all()
+    lay = r.debug_read_layouts(0)
+    assert lay["pk"].shape == (info[0], 8) and [len(p) for p in lay["planes"]] == info[3:6].tolist()
+    assert (lay["pk4"] is not None) == bool(info[1]) == (r.debug_blas_wide(0) >= 0) and (lay["pk4c"] is not None) == bool(info[2]) == (r.debug_blas_wide_closest(0) >= 0)
+    assert r.debug_read_layouts(-1)["pk"].shape == (len(sc.tlas_nodes), 8)
     r_same.group_destroy(); r.group_destroy()
 
 
