@@ -34,6 +34,7 @@
 #include "rtx_query.h"
 #include <rocprim/device/device_radix_sort.hpp>      // rtx_update_instances, scenes beyond one workgroup: header-only, part of ROCm
 #include "rtx_hostmem.h"                             // DevBuf, StageRing, grow_keep: every device and pinned allocation has one owner
+#include "rtx_layout_host.h"                         // convert_nodes*, build_nodes_pk4*, parent_table, balanced_topology: trees to the layouts of rtx_layout.h (no HIP in it; layout_check.cpp)
 #include "rtx_plan.h"                                // Knobs, plan_render: which kernels a render call launches (no HIP in it; plan_check.cpp)
 
 #define SLOT_BUDGET (48ll * 1000 * 1000)      // ray slots per batch of tiles (see plan_batch)
@@ -135,146 +136,6 @@ struct rtx_ctx {
     std::vector<hipEvent_t> event_pool;
     size_t event_next = 0;
 };
-
-static void convert_nodes(const rtx_bvh_node * nodes, int n, std::vector<float4> & out) {
-    out.resize((size_t)2 * (n > 0 ? n : 1));
-    for (int i = 0; i < n; i++) {
-        float l, cnt;
-        memcpy(&l, &nodes[i].left_or_first, 4); memcpy(&cnt, &nodes[i].count, 4);
-        out[2 * i]     = make_float4(nodes[i].aabb_min[0], nodes[i].aabb_min[1], nodes[i].aabb_min[2], l);
-        out[2 * i + 1] = make_float4(nodes[i].aabb_max[0], nodes[i].aabb_max[1], nodes[i].aabb_max[2], cnt);
-    }
-}
-
-// the packet kernels' node record: every SGPR pair of a fetched node is one operand of a packed-fp32 instruction (rtx_packet.h)
-static void convert_nodes_pk(const rtx_bvh_node * nodes, int n, std::vector<float4> & out) {
-    out.resize((size_t)2 * (n > 0 ? n : 1));
-    for (int i = 0; i < n; i++) {
-        float l, cnt;
-        memcpy(&l, &nodes[i].left_or_first, 4); memcpy(&cnt, &nodes[i].count, 4);
-        out[2 * i]     = make_float4(nodes[i].aabb_min[0], nodes[i].aabb_min[1], nodes[i].aabb_max[0], nodes[i].aabb_max[1]);
-        out[2 * i + 1] = make_float4(nodes[i].aabb_min[2], nodes[i].aabb_max[2], l, cnt);
-    }
-}
-
-// The shadow-ray packet walk's 4-wide node records (rtx_packet.h, pk_blas_any_asm4).  BottomLevelBVH::intersect (BottomLevelBVH.cpp:398-437)
-// answers "is any triangle hit": the answer does not depend on the order the tree is walked in, and when every child box lies inside its
-// parent's box — componentwise, in the stored floats — it does not depend on the inner nodes either: AABB::intersect (AABB.cpp:38-52) is
-// monotone under nesting in floating point (x -> fl(x - o) and x -> fl(x * inv) are monotone, so t_near(parent) <= t_near(child) and
-// t_far(child) <= t_far(parent) hold exactly, and a ray that passes a child's strict test passes its parent's).  The set of leaves a ray
-// reaches is therefore the set of leaves whose own box it passes together with all ancestors' = (under nesting) the leaves reached through
-// ANY subset of the ancestors.  The record of inner node j lists its grandchildren (children where a child is a leaf): the packet walk
-// tests 4 boxes per fetch and takes half the dependent steps.  Trees that are not nested (or exceed the packed-entry limits) keep the
-// binary walk.  Slot order = visiting order: largest box first (the likeliest occluder), unless that would need too many packet-stack entries
-// at this node — then smallest stack need first, which bounds the occupancy by the tree's Strahler-like number.  *stack_need = the bound.
-//   record (128 B, at byte offset 64 * left-child index of j): 4 x { min.x, min.y, max.x, max.y, min.z, max.z, first, leaf count };
-//   first = left-child index of the slot node (inner, count 0) or first triangle (leaf); unused slots hold a point box, which never passes.
-// slot_map (may be null): for every record slot (index 2 * left + s of 2n + 4) the node whose box it carries, -1 for an unused slot (rtx_refit.h)
-static bool build_nodes_pk4(const rtx_bvh_node * nodes, int n, int tri_count, std::vector<float4> & out, int * stack_need, int order_mode, std::vector<int32_t> * slot_map = nullptr) {
-    if (n >= (1 << 24) || tri_count >= (1 << 24)) return false;
-    auto inside = [&](int c, int p) {
-        for (int a = 0; a < 3; a++) if (!(nodes[c].aabb_min[a] >= nodes[p].aabb_min[a] && nodes[c].aabb_max[a] <= nodes[p].aabb_max[a])) return false;
-        return true;
-    };
-    // reachable inner nodes in pre-order (validate_tree has already checked the structure)
-    std::vector<int> order, stack(1, 0);
-    while (!stack.empty()) {
-        const int i = stack.back(); stack.pop_back();
-        const int cnt = nodes[i].count & 0x3fffffff, f = nodes[i].left_or_first;
-        for (int a = 0; a < 3; a++) if (!(nodes[i].aabb_min[a] <= nodes[i].aabb_max[a])) return false;      // the sign-coherent slab test relies on min <= max
-        if (cnt > 0) { if (cnt >= 256) return false; continue; }
-        if (f & 1) return false;                                   // records are addressed by left / 2
-        if (!inside(f, i) || !inside(f + 1, i)) return false;      // nesting
-        order.push_back(i); stack.push_back(f); stack.push_back(f + 1);
-    }
-    out.assign((size_t)4 * (n > 0 ? n : 1) + 8, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-    if (slot_map) slot_map->assign((size_t)2 * (n > 0 ? n : 1) + 4, -1);
-    std::vector<int> need((size_t)n, 0);                            // packet-stack entries the walk of a subtree can have pending
-    // visiting order = slot order.  For a shadow ray any hit ends the walk, so the likeliest occluder should come first: largest box first
-    // (merged launch 0.652 -> 0.627 ms; by triangle count, density or an RTSAH-style area^2 / cost key: 0.635-0.70).  Where that order would
-    // need more packet-stack entries than the cap, the node falls back to the order that minimises the need (smallest need first).
-    // order_mode (RTX_PK4_ORDER) 0: always smallest need first (A/B runs)
-    auto area = [&](int i) { const double dx = (double)nodes[i].aabb_max[0] - nodes[i].aabb_min[0], dy = (double)nodes[i].aabb_max[1] - nodes[i].aabb_min[1], dz = (double)nodes[i].aabb_max[2] - nodes[i].aabb_min[2]; const double v = dx * dy + dy * dz + dz * dx; return v == v ? (v < 1e300 ? v : 1e300) : 0.0; };      // a total order even for infinite boxes
-    for (size_t k = order.size(); k-- > 0; ) {                      // children before parents
-        const int j = order[k], l = nodes[j].left_or_first;
-        int slot[4], ns = 0;
-        for (int c = l; c <= l + 1; c++) {
-            if ((nodes[c].count & 0x3fffffff) > 0) slot[ns++] = c;
-            else { slot[ns++] = nodes[c].left_or_first; slot[ns++] = nodes[c].left_or_first + 1; }
-        }
-        auto need_of = [&](const int * sl) { int nd = 0; for (int t = 0; t < ns; t++) nd = std::max(nd, (ns - 1 - t) + need[sl[t]]); return nd; };   // slot t is walked with ns-1-t siblings pending
-        int nd = RTX_PK4_MAX_NEED + 1;
-        if (order_mode != 0) { std::sort(slot, slot + ns, [&](int a, int b) { return area(a) > area(b); }); nd = need_of(slot); }
-        if (nd > RTX_PK4_MAX_NEED - 4) { std::sort(slot, slot + ns, [&](int a, int b) { return need[a] < need[b]; }); nd = need_of(slot); }
-        need[j] = nd;
-        float4 * rec = &out[(size_t)4 * l];                         // 64 B per unit of `left`, 128 B per record (left is even)
-        for (int s = 0; s < ns; s++) {
-            const rtx_bvh_node & c = nodes[slot[s]];
-            float f, cn; const int cnt = c.count & 0x3fffffff;
-            memcpy(&f, &c.left_or_first, 4); memcpy(&cn, &cnt, 4);
-            rec[2 * s]     = make_float4(c.aabb_min[0], c.aabb_min[1], c.aabb_max[0], c.aabb_max[1]);
-            rec[2 * s + 1] = make_float4(c.aabb_min[2], c.aabb_max[2], f, cn);
-            if (slot_map) (*slot_map)[(size_t)2 * l + s] = slot[s];
-        }
-    }
-    *stack_need = need[0];
-    return true;
-}
-
-// The closest-hit per-lane walk's 4-wide records (rtx_packet.h, pk_lane_phase_closest).  BottomLevelBVH::trace (BottomLevelBVH.cpp:355-396)
-// tests every node once, when it is popped, against the closest distance of that moment, and pushes an inner node's children untested, far
-// child first.  With nested boxes (see build_nodes_pk4: AABB::intersect is monotone under nesting in floating point) a node that passes at
-// its pop has a parent that passed at its own — earlier, hence against a distance at least as large — so the test of an inner child L of
-// node X can be skipped: its children LL, LR meet, at THEIR pops, exactly the closest distances they meet in the reference (no leaf is visited
-// between the pop of L and the pop of its near child), pass or fail as there, and reach the same leaves in the same order provided the four
-// grandchildren are taken in the order the two binary levels would take them: X's near child's near child first.  The record of inner node
-// j keeps the tree's shape for that: slots 0-1 = the left child's children (or the left child itself, a leaf, in slot 0), slots 2-3 the
-// right child's; the near / far axes of the two children ride in slots 0 and 2.  Half the dependent fetches per walk.
-//   record (128 B, at byte offset 64 * left-child index of j): 4 x { (min.x, min.y, max.x, max.y) (min.z, max.z, first, meta) },
-//   meta = leaf count (< 16) | axis of the slot's PARENT (slots 0 and 2; 0: the parent is a leaf, i.e. the slot itself) << 26 | axis of the slot node << 30;
-//   unused slots hold a point box, which never passes.  *stack_need = pending entries a lane's walk can have (bound over all visiting orders).
-static bool build_nodes_pk4c(const rtx_bvh_node * nodes, int n, int tri_count, std::vector<float4> & out, int * stack_need, std::vector<int32_t> * slot_map = nullptr) {
-    if (n >= (1 << 24) || tri_count >= (1 << 24)) return false;
-    auto inside = [&](int c, int p) {
-        for (int a = 0; a < 3; a++) if (!(nodes[c].aabb_min[a] >= nodes[p].aabb_min[a] && nodes[c].aabb_max[a] <= nodes[p].aabb_max[a])) return false;
-        return true;
-    };
-    std::vector<int> order, stack(1, 0);
-    while (!stack.empty()) {
-        const int i = stack.back(); stack.pop_back();
-        const int cnt = nodes[i].count & 0x3fffffff, f = nodes[i].left_or_first;
-        if (cnt > 0) { if (cnt >= 16) return false; continue; }      // work-list and stack entries pack (first, count) into one word
-        if (f & 1) return false;                                   // records are addressed by left / 2
-        if (!inside(f, i) || !inside(f + 1, i)) return false;      // nesting
-        order.push_back(i); stack.push_back(f); stack.push_back(f + 1);
-    }
-    out.assign((size_t)4 * (n > 0 ? n : 1) + 8, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-    if (slot_map) slot_map->assign((size_t)2 * (n > 0 ? n : 1) + 4, -1);
-    std::vector<int> need((size_t)n, 0);
-    for (size_t k = order.size(); k-- > 0; ) {                      // children before parents
-        const int j = order[k], l = nodes[j].left_or_first;
-        float4 * rec = &out[(size_t)4 * l];
-        int nd = 0, ns = 0;
-        for (int g = 0; g < 2; g++) {
-            const rtx_bvh_node & c = nodes[l + g];
-            const bool leaf = (c.count & 0x3fffffff) > 0;
-            const int slots = leaf ? 1 : 2;
-            for (int t = 0; t < slots; t++) {
-                const int si = leaf ? l + g : c.left_or_first + t;
-                const rtx_bvh_node & sn = nodes[si];
-                const uint32_t meta = ((uint32_t)sn.count & 0x3fffffffu) | (t == 0 && !leaf ? (((uint32_t)c.count >> 30) << 26) : 0u) | (((uint32_t)sn.count >> 30) << 30);
-                float f, m; memcpy(&f, &sn.left_or_first, 4); memcpy(&m, &meta, 4);
-                rec[2 * (2 * g + t)]     = make_float4(sn.aabb_min[0], sn.aabb_min[1], sn.aabb_max[0], sn.aabb_max[1]);      // the packet kernels' slot layout: the slab test runs in packed fp32
-                rec[2 * (2 * g + t) + 1] = make_float4(sn.aabb_min[2], sn.aabb_max[2], f, m);
-                if (slot_map) (*slot_map)[(size_t)2 * l + 2 * g + t] = si;
-                nd = std::max(nd, need[si]); ns++;
-            }
-        }
-        need[j] = nd + ns - 1;                                      // any slot may come first, with the others pending
-    }
-    *stack_need = need[0];
-    return true;
-}
 
 extern "C" int rtx_abi_version(void) { return RTX_ABI_VERSION; }
 
@@ -504,7 +365,7 @@ static int stage_blas(rtx_ctx * c, int32_t blas_id, const rtx_bvh_node * nodes, 
     std::vector<float4> ndp; convert_nodes_pk(nodes, node_count, ndp);
     rtx_ctx::BlasHost & H = S.H;
     std::vector<float4> nd4; int need4 = 0;
-    const bool wide = !c->knobs.no_wide && build_nodes_pk4(nodes, node_count, triangle_count, nd4, &need4, pk4_order, &H.refit.map4) && need4 <= RTX_PK4_MAX_NEED;
+    const bool wide = !c->knobs.no_wide && build_nodes_pk4(nodes, node_count, triangle_count, nd4, &need4, pk4_order, RTX_PK4_MAX_NEED, &H.refit.map4) && need4 <= RTX_PK4_MAX_NEED;
     std::vector<float4> nd4c; int need4c = 0;
     const bool wide_closest = !c->knobs.no_wide_closest && build_nodes_pk4c(nodes, node_count, triangle_count, nd4c, &need4c, &H.refit.map4c) && need4c <= RTX_MAX_STACK - 2;
     if (!wide) H.refit.map4.clear();
@@ -808,6 +669,34 @@ static bool all_meshes_wide(const rtx_ctx * c) {
     return true;
 }
 
+// ---- what the device-side builders below share on the host ------------------------------------------------------------------------------
+// n parts of one block, every part 256-byte aligned: off[k] = where part k of len[k] bytes starts; returns the block's size
+static size_t aligned_parts(const size_t * len, size_t * off, int n) {
+    size_t total = 0;
+    for (int k = 0; k < n; k++) { off[k] = total; total += (len[k] + 255) & ~(size_t)255; }
+    return total;
+}
+
+// rocPRIM's temporary storage for a radix sort of `count` keys of type Key over `bits` bits: a host-side query, nothing is launched
+template <typename Key> static int sort_storage_bytes(rtx_ctx * c, size_t count, unsigned int bits, size_t & bytes) {
+    bytes = 0;
+    if (rocprim::radix_sort_keys(nullptr, bytes, (const Key *)nullptr, (Key *)nullptr, (unsigned int)count, 0u, bits, c->stream) == hipSuccess) return RTX_OK;
+    hipGetLastError(); c->err = "rocprim::radix_sort_keys size query failed"; return RTX_ERR_HIP;
+}
+
+// a sort that failed: the sticky error is cleared, the context says why
+static int sort_failed(rtx_ctx * c, hipError_t se) {
+    hipGetLastError(); c->err = std::string("rocprim::radix_sort_keys: ") + hipGetErrorString(se); return RTX_ERR_HIP;
+}
+
+// a lane-layout array of n nodes in device memory back into the reference's records
+static int read_lane_nodes(rtx_ctx * c, const float4 * dev, int n, rtx_bvh_node * out) {
+    std::vector<float4> nd((size_t)2 * n);
+    HIP_OK(c, hipMemcpy(nd.data(), dev, nd.size() * 16, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; i++) rtxl::node_from_lane(nd.data(), i, out[i]);
+    return RTX_OK;
+}
+
 // ---- device-side scene update (include/rtx.h: rtx_update_instances / rtx_read_frame_state; kernels in rtx_update.h) -------------------
 // The instance records, the TLAS in both node layouts and its indices are rebuilt from poses in device memory into a block of their own
 // (d_upd), and the DevScene pointers are switched to it; spheres, planes, lights and the camera stay where rtx_set_frame put them.  Everything
@@ -835,8 +724,8 @@ extern "C" int rtx_update_instances(rtx_ctx * c, const void * positions_dev, con
     const bool small = n <= c->knobs.update_small_max;
     // [nodes, lane layout][nodes, packet layout][indices][instances][AABBs][sorted keys][bounds], every part 256-byte aligned
     const size_t len[7] = { (size_t)slots * 32, (size_t)slots * 32, (size_t)n * 4, (size_t)n * sizeof(rtx_instance), (size_t)n * 24, (size_t)n * 8, 24 };
-    size_t off[7], total = 0;
-    for (int k = 0; k < 7; k++) { off[k] = total; total += (len[k] + 255) & ~(size_t)255; }
+    size_t off[7];
+    const size_t total = aligned_parts(len, off, 7);
     if (n > c->upd_cap || total > c->d_upd.cap) {           // growth: never while the scene points into the block (the count is the frame's, the block holds it)
         HIP_OK(c, hipStreamSynchronize(c->stream));
         if (int rc = ensure(c, c->d_upd, total)) return rc;
@@ -844,8 +733,7 @@ extern "C" int rtx_update_instances(rtx_ctx * c, const void * positions_dev, con
     }
     size_t sort_bytes = 0;
     if (!small) {                                           // rocPRIM's temporary storage, sized for this n by a host-side query; grown only
-        if (rocprim::radix_sort_keys(nullptr, sort_bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr, (unsigned int)n, 0u, (unsigned int)RTXU_KEY_BITS, c->stream) != hipSuccess) {
-            hipGetLastError(); c->err = "rocprim::radix_sort_keys size query failed"; return RTX_ERR_HIP; }
+        if (int rc = sort_storage_bytes<uint64_t>(c, (size_t)n, RTXU_KEY_BITS, sort_bytes)) return rc;
         const size_t keys_in = ((size_t)n * 8 + 255) & ~(size_t)255;
         if (keys_in + sort_bytes > c->d_upd_sort.cap) {
             HIP_OK(c, hipStreamSynchronize(c->stream));
@@ -870,7 +758,7 @@ extern "C" int rtx_update_instances(rtx_ctx * c, const void * positions_dev, con
         launch_timed(c, "k_update_keys", c->stream, [&] { hipLaunchKernelGGL(k_update_keys, dim3(blocks), dim3(256), 0, c->stream, u, keys_in); });
         hipError_t se = hipSuccess;
         launch_timed(c, "update_radix_sort", c->stream, [&] { se = rocprim::radix_sort_keys(sort_tmp, sort_bytes, (const uint64_t *)keys_in, u.keys, (unsigned int)n, 0u, (unsigned int)RTXU_KEY_BITS, c->stream); });
-        if (se != hipSuccess) { hipGetLastError(); c->err = std::string("rocprim::radix_sort_keys: ") + hipGetErrorString(se); return RTX_ERR_HIP; }
+        if (se != hipSuccess) return sort_failed(c, se);
         for (int d = levels; d > RTX_UPDATE_TOP_LEVELS; d--)
             launch_timed(c, "k_update_level", c->stream, [&] { hipLaunchKernelGGL(k_update_level, dim3(((1 << d) + 255) / 256), dim3(256), 0, c->stream, u, d); });
         launch_timed(c, "k_update_top", c->stream, [&] { hipLaunchKernelGGL(k_update_top, dim3(1), dim3(RTX_UPDATE_BLOCK), 0, c->stream, u); });
@@ -893,16 +781,7 @@ extern "C" int rtx_read_frame_state(rtx_ctx * c, rtx_instance * instances, rtx_b
     if (tlas_node_count) *tlas_node_count = s.tlas_node_count;
     if (instances && s.instance_count) HIP_OK(c, hipMemcpy(instances, s.instances, (size_t)s.instance_count * sizeof(rtx_instance), hipMemcpyDeviceToHost));
     if (tlas_indices && s.tlas_index_count) HIP_OK(c, hipMemcpy(tlas_indices, s.tlas_indices, (size_t)s.tlas_index_count * 4, hipMemcpyDeviceToHost));
-    if (tlas_nodes && s.tlas_node_count) {                  // the lane layout back into the reference's (convert_nodes inverted)
-        std::vector<float4> nd((size_t)2 * s.tlas_node_count);
-        HIP_OK(c, hipMemcpy(nd.data(), s.tlas_nodes, nd.size() * 16, hipMemcpyDeviceToHost));
-        for (int i = 0; i < s.tlas_node_count; i++) {
-            const float4 a = nd[2 * (size_t)i], b = nd[2 * (size_t)i + 1];
-            tlas_nodes[i].aabb_min[0] = a.x; tlas_nodes[i].aabb_min[1] = a.y; tlas_nodes[i].aabb_min[2] = a.z;
-            tlas_nodes[i].aabb_max[0] = b.x; tlas_nodes[i].aabb_max[1] = b.y; tlas_nodes[i].aabb_max[2] = b.z;
-            memcpy(&tlas_nodes[i].left_or_first, &a.w, 4); memcpy(&tlas_nodes[i].count, &b.w, 4);
-        }
-    }
+    if (tlas_nodes && s.tlas_node_count) return read_lane_nodes(c, s.tlas_nodes, s.tlas_node_count, tlas_nodes);
     return RTX_OK;
 }
 
@@ -924,7 +803,7 @@ static int refit_launch_finish(rtx_ctx * c, rtx_ctx::BlasRefit & R, bool build =
             se = rocprim::radix_sort_keys(R.sort_tmp, bytes, (const float *)r.plane_keys[a], R.planes[a], (unsigned int)(2 * n), 0u, 32u, c->stream);
         }
     });
-    if (se != hipSuccess) { hipGetLastError(); c->err = std::string("rocprim::radix_sort_keys: ") + hipGetErrorString(se); return RTX_ERR_HIP; }
+    if (se != hipSuccess) return sort_failed(c, se);
     HIP_OK(c, hipGetLastError());
     return RTX_OK;
 }
@@ -938,23 +817,15 @@ static int plan_refit(rtx_ctx * c, DevBlas & B, rtx_ctx::BlasRefit & R, const in
     // the topology as uploaded: the lane layout's words (a refit never writes them)
     std::vector<float4> nd((size_t)2 * n);
     HIP_OK(c, hipMemcpy(nd.data(), B.nodes, nd.size() * 16, hipMemcpyDeviceToHost));
-    std::vector<int32_t> parent((size_t)n, RTX_REFIT_UNREACHABLE), stack(1, 0);
-    parent[0] = -1;
-    while (!stack.empty()) {                                        // the upload validated the tree: in range, no node reachable twice
-        const int i = stack.back(); stack.pop_back();
-        int32_t f, cw; memcpy(&f, &nd[2 * (size_t)i].w, 4); memcpy(&cw, &nd[2 * (size_t)i + 1].w, 4);
-        if ((cw & 0x3fffffff) > 0) continue;
-        parent[f] = i; parent[f + 1] = i; stack.push_back(f); stack.push_back(f + 1);
-    }
+    std::vector<int32_t> parent;
+    parent_table(nd.data(), n, parent);
     size_t sort_bytes = 0;
-    if (rocprim::radix_sort_keys(nullptr, sort_bytes, (const float *)nullptr, (float *)nullptr, (unsigned int)(2 * n), 0u, 32u, c->stream) != hipSuccess) {
-        hipGetLastError(); c->err = "rocprim::radix_sort_keys size query failed"; return RTX_ERR_HIP; }
+    if (int rc = sort_storage_bytes<float>(c, (size_t)2 * n, 32u, sort_bytes)) return rc;
     // [slot vertices][parents][arrival counters][pk4 slot map][pk4c slot map][3 x plane keys][3 x planes][sort storage], every part 256-byte aligned
     const size_t slots = (size_t)2 * n + 4, pl = (size_t)2 * n * 4;
     const size_t len[12] = { (size_t)(T > 0 ? T : 1) * 12, (size_t)n * 4, (size_t)n * 4, R.map4.empty() ? 0 : slots * 4, R.map4c.empty() ? 0 : slots * 4, pl, pl, pl, pl, pl, pl, sort_bytes };
-    size_t off[12], total = 0;
-    for (int k = 0; k < 12; k++) { off[k] = total; total += (len[k] + 255) & ~(size_t)255; }
-    if (int rc = ensure(c, R.block, total)) return rc;
+    size_t off[12];
+    if (int rc = ensure(c, R.block, aligned_parts(len, off, 12))) return rc;
     char * const bb = (char *)R.block.p;
     if (T) HIP_OK(c, hipMemcpy(bb + off[0], slot_vertices, (size_t)T * 12, hipMemcpyHostToDevice));
     HIP_OK(c, hipMemcpy(bb + off[1], parent.data(), (size_t)n * 4, hipMemcpyHostToDevice));
@@ -1029,21 +900,6 @@ extern "C" int rtx_refit_blas(rtx_ctx * c, int32_t blas_id, const void * positio
 // from a BLAS before a launch — inner_depth, packet_ok, pk4_need / pk4c_need, the 4-wide slot orders and maps, the refit plan — once,
 // by handing the topology with all-zero boxes (nested, min <= max) to the code rtx_upload_blas and rtx_bind_blas_vertices run.  A build is then
 // queued like a refit: it writes the arrays in place, touches no pointer and reads nothing back.
-static void balanced_topology(int T, std::vector<rtx_bvh_node> & nodes) {
-    const int levels = rtxb::tree_levels(T);
-    nodes.assign((size_t)rtxb::tree_node_count(T), rtx_bvh_node());
-    memset(nodes.data(), 0, nodes.size() * sizeof(rtx_bvh_node));
-    for (int d = 0; d <= levels; d++)
-        for (int j = 0; j < (1 << d); j++) {
-            int first;
-            const int cnt = rtxb::node_range(T, d, j, &first);
-            if (cnt == 0) continue;
-            rtx_bvh_node & nd = nodes[rtxu::node_slot(d, j)];
-            if (cnt <= RTX_BUILD_LEAF_MAX) { nd.left_or_first = first; nd.count = cnt; }
-            else { nd.left_or_first = (2 << d) | (2 * j); nd.count = 0; }
-        }
-}
-
 extern "C" int rtx_alloc_blas(rtx_ctx * c, int32_t blas_id, int32_t triangle_count, int32_t vertex_count, const int32_t * material_ids, int32_t material_offset) {
     if (!c) return RTX_ERR_INVALID_ARG;
     if (blas_id < 0 || blas_id >= (1 << 20) || triangle_count < 1 || vertex_count < 1) { c->err = "rtx_alloc_blas: bad id, no triangles or no vertices"; return RTX_ERR_INVALID_ARG; }
@@ -1075,14 +931,12 @@ extern "C" int rtx_alloc_blas(rtx_ctx * c, int32_t blas_id, int32_t triangle_cou
         if (int rc = plan_refit(c, S.B, S.H.refit, sv.data(), vertex_count)) return rc;
     }
     size_t sort_bytes = 0;
-    if (rocprim::radix_sort_keys(nullptr, sort_bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr, (unsigned int)T, 0u, (unsigned int)RTXB_KEY_BITS, c->stream) != hipSuccess) {
-        hipGetLastError(); c->err = "rocprim::radix_sort_keys size query failed"; return RTX_ERR_HIP; }
+    if (int rc = sort_storage_bytes<uint64_t>(c, (size_t)T, RTXB_KEY_BITS, sort_bytes)) return rc;
     // [material ids][bounds][unsorted keys][sorted keys][sort storage], every part 256-byte aligned
     const size_t len[5] = { (size_t)T * 4, 24, (size_t)T * 8, (size_t)T * 8, sort_bytes };
-    size_t off[5], total = 0;
-    for (int k = 0; k < 5; k++) { off[k] = total; total += (len[k] + 255) & ~(size_t)255; }
+    size_t off[5];
     rtx_ctx::BlasBuild & U = S.H.build;
-    if (int rc = ensure(c, U.block, total)) return rc;
+    if (int rc = ensure(c, U.block, aligned_parts(len, off, 5))) return rc;
     char * const bb = (char *)U.block.p;
     if (material_ids) HIP_OK(c, hipMemcpy(bb + off[0], material_ids, (size_t)T * 4, hipMemcpyHostToDevice));
     else HIP_OK(c, hipMemset(bb + off[0], 0, (size_t)T * 4));
@@ -1116,7 +970,7 @@ extern "C" int rtx_build_blas(rtx_ctx * c, int32_t blas_id, const void * positio
     launch_timed(c, "k_build_keys", c->stream, [&] { hipLaunchKernelGGL(k_build_keys, tri_grid, dim3(RTX_BUILD_BLOCK), 0, c->stream, b); });
     hipError_t se = hipSuccess;
     launch_timed(c, "build_radix_sort", c->stream, [&] { size_t bytes = U.sort_bytes; se = rocprim::radix_sort_keys(U.sort_tmp, bytes, (const uint64_t *)b.keys_in, b.keys, (unsigned int)T, 0u, (unsigned int)RTXB_KEY_BITS, c->stream); });
-    if (se != hipSuccess) { hipGetLastError(); c->err = std::string("rocprim::radix_sort_keys: ") + hipGetErrorString(se); return RTX_ERR_HIP; }
+    if (se != hipSuccess) return sort_failed(c, se);
     launch_timed(c, "k_build_scatter", c->stream, [&] { hipLaunchKernelGGL(k_build_scatter, tri_grid, dim3(RTX_BUILD_BLOCK), 0, c->stream, b, r); });
     for (int d = U.levels; d > RTX_BUILD_TOP_LEVELS; d--)
         launch_timed(c, "k_build_level", c->stream, [&] { hipLaunchKernelGGL(k_build_level, dim3(((1 << d) + RTX_BUILD_BLOCK - 1) / RTX_BUILD_BLOCK), dim3(RTX_BUILD_BLOCK), 0, c->stream, r, d); });
@@ -1131,16 +985,7 @@ extern "C" int rtx_read_blas(rtx_ctx * c, int32_t blas_id, rtx_bvh_node * nodes,
     hipSetDevice(c->cfg.device);
     HIP_OK(c, hipStreamSynchronize(c->stream));
     const DevBlas & B = c->h_blas[blas_id];
-    if (nodes) {                                                    // the lane layout back into the reference's (convert_nodes inverted)
-        std::vector<float4> nd((size_t)2 * B.node_count);
-        HIP_OK(c, hipMemcpy(nd.data(), B.nodes, nd.size() * 16, hipMemcpyDeviceToHost));
-        for (int i = 0; i < B.node_count; i++) {
-            const float4 a = nd[2 * (size_t)i], b = nd[2 * (size_t)i + 1];
-            nodes[i].aabb_min[0] = a.x; nodes[i].aabb_min[1] = a.y; nodes[i].aabb_min[2] = a.z;
-            nodes[i].aabb_max[0] = b.x; nodes[i].aabb_max[1] = b.y; nodes[i].aabb_max[2] = b.z;
-            memcpy(&nodes[i].left_or_first, &a.w, 4); memcpy(&nodes[i].count, &b.w, 4);
-        }
-    }
+    if (nodes) if (int rc = read_lane_nodes(c, B.nodes, B.node_count, nodes)) return rc;
     if (hot && B.tri_count) {
         std::vector<float4> th((size_t)RTX_TRI_STRIDE * B.tri_count);
         HIP_OK(c, hipMemcpy(th.data(), B.tri_hot, th.size() * 16, hipMemcpyDeviceToHost));

@@ -11,7 +11,7 @@
 //   k_build_level    one launch per level below RTX_BUILD_TOP_LEVELS, one lane per node of the level: a leaf's box from its slots, an inner
 //                    node's from its children's STORED boxes with the axis into bits 30-31 of `count`
 //   k_build_top      levels RTX_BUILD_TOP_LEVELS .. 0 in one workgroup, a barrier per level (the heap is regular: no arrival counters)
-//   k_build_finish   k_refit_finish's work (packet layout, 4-wide slot boxes, plane keys) and the axis fields of the pk4c meta words
+//   k_build_finish   k_refit_finish's pass (rtxl::finish_index, rtx_layout.h) with the axis fields of the pk4c meta words composed anew
 //   then the three plane sorts of the refit.
 // Indices come from the caller's device memory here: every one is checked against [0, vertex_count) before it is used as an address, in
 // every kernel that reads it.  All other addresses come from the lane's index, the alloc-time tables or the keys this file made.
@@ -20,6 +20,7 @@
 #include <stdint.h>
 #include "rtx_device.h"
 #include "rtx_refit.h"
+#include "rtx_update.h"                      // upd_reduce_bounds
 #include "rtx_build_math.h"
 
 #define RTX_BUILD_BLOCK       256
@@ -55,21 +56,14 @@ __global__ __launch_bounds__(RTX_BUILD_BLOCK) void k_build_bounds(const DevBuild
     float c[3];
     if (t < b.tri_count && build_centre(b, t, c))
         for (int a = 0; a < 3; a++) { const uint32_t k = rtxu::ordered_key(c[a]); k6[a] = k; k6[3 + a] = ~k; }
-    for (int a = 0; a < 6; a++) {                                      // wave64 min, then one atomic per wave and value
-        uint32_t v = k6[a];
-        for (int o = 32; o > 0; o >>= 1) { const uint32_t w = (uint32_t)__shfl_xor((int)v, o, 64); v = w < v ? w : v; }
-        if ((threadIdx.x & 63) == 0 && v != 0xffffffffu) atomicMin(&b.bounds[a], v);
-    }
+    upd_reduce_bounds(k6, b.bounds);
 }
 
 __global__ __launch_bounds__(RTX_BUILD_BLOCK) void k_build_keys(const DevBuild b) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= b.tri_count) return;
     uint32_t b6[6];
-    for (int a = 0; a < 3; a++) {                                      // a reduction nothing took part in still holds its initial value
-        const uint32_t lo = b.bounds[a], hc = b.bounds[3 + a];
-        b6[a] = lo == 0xffffffffu ? RTXU_KEY_LO_INIT : lo; b6[3 + a] = hc == 0xffffffffu ? RTXU_KEY_HI_INIT : ~hc;
-    }
+    rtxu::reduced_bounds(b.bounds, b6);
     float c[3] = { 0.0f, 0.0f, 0.0f };
     const bool ok = build_centre(b, t, c);
     b.keys_in[t] = rtxb::sort_key(c, b6, (uint32_t)t, ok);
@@ -122,22 +116,10 @@ static __device__ __forceinline__ void build_node(const DevRefit & r, const int 
     if (r.parent[i] == RTX_REFIT_UNREACHABLE) return;                                  // holes and index 1 stay zero
     const float lw = r.nodes[2 * (size_t)i].w, cw = r.nodes[2 * (size_t)i + 1].w;
     const int cnt = __float_as_int(cw) & 0x3fffffff, first = __float_as_int(lw);
-    if (cnt > 0) {
-        rtxu::Box b = rtxr::empty_box();
-        for (int k = first; k < first + cnt; k++) {                                    // slot order
-            const int32_t i0 = r.slot_vertices[3 * (size_t)k], i1 = r.slot_vertices[3 * (size_t)k + 1], i2 = r.slot_vertices[3 * (size_t)k + 2];
-            if (i0 < 0) continue;                                                      // an invalid triangle takes no part in any box
-            float v0[3], v1[3], v2[3];
-            refit_vertex(r.positions, i0, v0); refit_vertex(r.positions, i1, v1); refit_vertex(r.positions, i2, v2);
-            rtxr::expand_box(b, rtxr::triangle_box(v0, v1, v2));
-        }
-        rtxr::finish_leaf(b);
-        refit_store_box(r.nodes, i, b, lw, cw);
-        return;
-    }
+    if (cnt > 0) { rtxl::store_lane(r.nodes, i, refit_leaf_box(r, first, cnt), lw, cw); return; }
     const int left = first;
-    const rtxu::Box l = refit_load_box(r.nodes, left), rr = refit_load_box(r.nodes, left + 1);
-    refit_store_box(r.nodes, i, rtxr::join_children(l, rr), lw, __int_as_float((int32_t)((uint32_t)rtxb::join_axis(l, rr) << 30)));
+    const rtxu::Box l = rtxl::load_box(r.nodes, left), rr = rtxl::load_box(r.nodes, left + 1);
+    rtxl::store_lane(r.nodes, i, rtxr::join_children(l, rr), lw, __int_as_float((int32_t)((uint32_t)rtxb::join_axis(l, rr) << 30)));
 }
 
 // level d > RTX_BUILD_TOP_LEVELS: nodes 2^d .. 2^(d+1) - 1; the children come from the launch before
@@ -155,34 +137,7 @@ __global__ __launch_bounds__(RTX_BUILD_TOP_BLOCK) void k_build_top(const DevRefi
     }
 }
 
-// k_refit_finish, and the axis fields of the pk4c meta words (build_nodes_pk4c of rtx_api.hip: leaf count | axis of the slot's parent << 26
-// in slots 0 and 2 when that parent is a child of the record's node | axis of the slot node << 30)
+// k_refit_finish's pass, and the axis fields of the pk4c meta words from the count words the levels above have written
 __global__ __launch_bounds__(RTX_REFIT_BLOCK) void k_build_finish(const DevRefit r) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < r.node_count) {
-        const float4 a = r.nodes[2 * (size_t)i], c = r.nodes[2 * (size_t)i + 1];
-        if (r.parent[i] != RTX_REFIT_UNREACHABLE) {
-            r.pk_nodes[2 * (size_t)i]     = make_float4(a.x, a.y, c.x, c.y);
-            r.pk_nodes[2 * (size_t)i + 1] = make_float4(a.z, c.z, a.w, c.w);
-        }
-        *(float2 *)(r.plane_keys[0] + 2 * (size_t)i) = make_float2(refit_plane_key(a.x), refit_plane_key(c.x));
-        *(float2 *)(r.plane_keys[1] + 2 * (size_t)i) = make_float2(refit_plane_key(a.y), refit_plane_key(c.y));
-        *(float2 *)(r.plane_keys[2] + 2 * (size_t)i) = make_float2(refit_plane_key(a.z), refit_plane_key(c.z));
-    }
-    if (i < 2 * r.node_count + 4) {
-        if (r.map4)  { const int j = r.map4[i];  if (j >= 0) refit_wide_slot(r.pk4_nodes, i, refit_load_box(r.nodes, j)); }
-        if (r.map4c) {
-            const int j = r.map4c[i];
-            if (j >= 0) {
-                const rtxu::Box b = refit_load_box(r.nodes, j);
-                const int s = i & 3, child = ((i - s) >> 1) + (s >> 1);                // the record's node has its children at (i - s) / 2, + 1
-                const uint32_t cj = __float_as_uint(r.nodes[2 * (size_t)j + 1].w);
-                uint32_t meta = (cj & 0x3fffffffu) | ((cj >> 30) << 30);
-                if ((s & 1) == 0 && j != child) meta |= (__float_as_uint(r.nodes[2 * (size_t)child + 1].w) >> 30) << 26;
-                const float first = r.pk4c_nodes[2 * (size_t)i + 1].z;
-                r.pk4c_nodes[2 * (size_t)i]     = make_float4(b.mn[0], b.mn[1], b.mx[0], b.mx[1]);
-                r.pk4c_nodes[2 * (size_t)i + 1] = make_float4(b.mn[2], b.mx[2], first, __uint_as_float(meta));
-            }
-        }
-    }
+    rtxl::finish_index(r, blockIdx.x * blockDim.x + threadIdx.x, true);
 }

@@ -16,7 +16,7 @@
 #pragma once
 #include "rtx_refit_math.h"
 
-#define RTX_BUILD_LEAF_MAX      4            // triangles per leaf at most; must stay below the 16 of build_nodes_pk4c (rtx_api.hip)
+#define RTX_BUILD_LEAF_MAX      4            // triangles per leaf at most; must stay below the 16 of build_nodes_pk4c (rtx_layout_host.h)
 #define RTX_BUILD_MAX_TRIANGLES (1 << 24)    // exclusive: the wide walks pack triangle and node indices into 24 bits
 #define RTXB_INDEX_BITS 24                   // the source triangle index in the low bits of a sort key
 #define RTXB_KEY_BITS   55                   // index + 30 bits of Morton code + the valid bit

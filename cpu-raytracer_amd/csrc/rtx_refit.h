@@ -9,8 +9,8 @@
 //                      stored boxes, joins them left child first and goes on.  The result is a function of the input alone: which lane forms
 //                      a node does not matter, what it reads is the two stored boxes.  The second arrival puts the counter back to zero, so
 //                      the counters need no clearing between calls.  Nothing spins: a lane either stops or has all it needs.
-//   k_refit_finish     one lane per node: the packet layout of the node and its six plane keys (NaN -> +inf); one lane per 4-wide record
-//                      slot: the box of the node the slot carries (slot maps made at bind), first / meta words kept
+//   k_refit_finish     rtxl::finish_index (rtx_layout.h): one lane per node — its packet record and six plane keys — and per 4-wide record
+//                      slot — the box of the node the slot carries (slot maps made at bind), first / meta words kept
 //   then rocPRIM sorts the 2 * node_count plane keys of each axis into the list plane_member (rtx_trace.h) searches.
 // Every store is a vector store to an address computed from the lane's index or from tables the host filled and validated at bind
 // (parents, slot maps, vertex indices in [0, vertex_count)): no index comes from the caller's float data.  A slot table written by
@@ -20,9 +20,9 @@
 #include <stdint.h>
 #include "rtx_device.h"
 #include "rtx_refit_math.h"
+#include "rtx_layout.h"
 
 #define RTX_REFIT_BLOCK 256
-#define RTX_REFIT_UNREACHABLE (-2)         // parent[] of a node slot no traversal reaches: its bytes stay
 
 struct DevRefit {
     const float *   positions;             // caller's device memory, vertex_count x 3
@@ -73,15 +73,18 @@ __global__ __launch_bounds__(RTX_REFIT_BLOCK) void k_refit_triangles(const DevRe
     }
 }
 
-static __device__ __forceinline__ rtxu::Box refit_load_box(const float4 * nodes, const int i) {
-    const float4 a = nodes[2 * (size_t)i], c = nodes[2 * (size_t)i + 1];
-    rtxu::Box b; b.mn[0] = a.x; b.mn[1] = a.y; b.mn[2] = a.z; b.mx[0] = c.x; b.mx[1] = c.y; b.mx[2] = c.z;
+// the box of the leaf over slots [first, first + cnt), in slot order; an invalid triangle of rtx_build_blas takes no part in any box
+static __device__ __forceinline__ rtxu::Box refit_leaf_box(const DevRefit & r, const int first, const int cnt) {
+    rtxu::Box b = rtxr::empty_box();
+    for (int k = first; k < first + cnt; k++) {
+        const int32_t i0 = r.slot_vertices[3 * (size_t)k], i1 = r.slot_vertices[3 * (size_t)k + 1], i2 = r.slot_vertices[3 * (size_t)k + 2];
+        if (i0 < 0) continue;
+        float v0[3], v1[3], v2[3];
+        refit_vertex(r.positions, i0, v0); refit_vertex(r.positions, i1, v1); refit_vertex(r.positions, i2, v2);
+        rtxr::expand_box(b, rtxr::triangle_box(v0, v1, v2));
+    }
+    rtxr::finish_leaf(b);
     return b;
-}
-// the lane layout of a node with its topology words (left_or_first, count) as they are
-static __device__ __forceinline__ void refit_store_box(float4 * nodes, const int i, const rtxu::Box & b, const float l, const float c) {
-    nodes[2 * (size_t)i]     = make_float4(b.mn[0], b.mn[1], b.mn[2], l);
-    nodes[2 * (size_t)i + 1] = make_float4(b.mx[0], b.mx[1], b.mx[2], c);
 }
 
 __global__ __launch_bounds__(RTX_REFIT_BLOCK) void k_refit_climb(const DevRefit r) {
@@ -90,17 +93,8 @@ __global__ __launch_bounds__(RTX_REFIT_BLOCK) void k_refit_climb(const DevRefit 
     float lw = r.nodes[2 * (size_t)i].w, cw = r.nodes[2 * (size_t)i + 1].w;
     const int cnt = __float_as_int(cw) & 0x3fffffff, first = __float_as_int(lw);
     if (cnt == 0) return;                                                              // inner nodes are formed by the climb
-    rtxu::Box b = rtxr::empty_box();
-    for (int k = first; k < first + cnt; k++) {                                        // slot order
-        float v0[3], v1[3], v2[3];
-        if (r.slot_vertices[3 * (size_t)k] < 0) continue;                              // an invalid triangle of rtx_build_blas takes no part in any box
-        refit_vertex(r.positions, r.slot_vertices[3 * (size_t)k], v0);
-        refit_vertex(r.positions, r.slot_vertices[3 * (size_t)k + 1], v1);
-        refit_vertex(r.positions, r.slot_vertices[3 * (size_t)k + 2], v2);
-        rtxr::expand_box(b, rtxr::triangle_box(v0, v1, v2));
-    }
-    rtxr::finish_leaf(b);
-    refit_store_box(r.nodes, i, b, lw, cw);
+    rtxu::Box b = refit_leaf_box(r, first, cnt);
+    rtxl::store_lane(r.nodes, i, b, lw, cw);
     int cur = i;
     for (;;) {
         const int p = r.parent[cur];
@@ -111,36 +105,12 @@ __global__ __launch_bounds__(RTX_REFIT_BLOCK) void k_refit_climb(const DevRefit 
         __threadfence();                                                               // the sibling's box after its arrival
         lw = r.nodes[2 * (size_t)p].w; cw = r.nodes[2 * (size_t)p + 1].w;
         const int left = __float_as_int(lw);
-        b = rtxr::join_children(refit_load_box(r.nodes, left), refit_load_box(r.nodes, left + 1));
-        refit_store_box(r.nodes, p, b, lw, cw);
+        b = rtxr::join_children(rtxl::load_box(r.nodes, left), rtxl::load_box(r.nodes, left + 1));
+        rtxl::store_lane(r.nodes, p, b, lw, cw);
         cur = p;
     }
 }
 
-static __device__ __forceinline__ float refit_plane_key(const float v) { return v != v ? INFINITY : v; }
-
-// one 4-wide record slot: (min.x, min.y, max.x, max.y) (min.z, max.z, first, meta) — the box of node j, the two words kept
-static __device__ __forceinline__ void refit_wide_slot(float4 * recs, const int s, const rtxu::Box & b) {
-    const float4 q = recs[2 * (size_t)s + 1];
-    recs[2 * (size_t)s]     = make_float4(b.mn[0], b.mn[1], b.mx[0], b.mx[1]);
-    recs[2 * (size_t)s + 1] = make_float4(b.mn[2], b.mx[2], q.z, q.w);
-}
-
 __global__ __launch_bounds__(RTX_REFIT_BLOCK) void k_refit_finish(const DevRefit r) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < r.node_count) {
-        const float4 a = r.nodes[2 * (size_t)i], c = r.nodes[2 * (size_t)i + 1];
-        if (r.parent[i] != RTX_REFIT_UNREACHABLE) {                                    // convert_nodes_pk of rtx_api.hip
-            r.pk_nodes[2 * (size_t)i]     = make_float4(a.x, a.y, c.x, c.y);
-            r.pk_nodes[2 * (size_t)i + 1] = make_float4(a.z, c.z, a.w, c.w);
-        }
-        // unreachable slots keep their boxes, and their planes stay in the lists: a superset only sends a ray to the reference-form walker
-        *(float2 *)(r.plane_keys[0] + 2 * (size_t)i) = make_float2(refit_plane_key(a.x), refit_plane_key(c.x));
-        *(float2 *)(r.plane_keys[1] + 2 * (size_t)i) = make_float2(refit_plane_key(a.y), refit_plane_key(c.y));
-        *(float2 *)(r.plane_keys[2] + 2 * (size_t)i) = make_float2(refit_plane_key(a.z), refit_plane_key(c.z));
-    }
-    if (i < 2 * r.node_count + 4) {
-        if (r.map4)  { const int j = r.map4[i];  if (j >= 0) refit_wide_slot(r.pk4_nodes, i, refit_load_box(r.nodes, j)); }
-        if (r.map4c) { const int j = r.map4c[i]; if (j >= 0) refit_wide_slot(r.pk4c_nodes, i, refit_load_box(r.nodes, j)); }
-    }
+    rtxl::finish_index(r, blockIdx.x * blockDim.x + threadIdx.x, false);
 }

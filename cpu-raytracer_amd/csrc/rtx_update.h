@@ -3,7 +3,7 @@
 //   instance records   one lane per instance: Mesh::update (Mesh.cpp:9-15) and the world AABB of the BLAS root box, the expressions of
 //                      host/rtx_host.cpp in their order (rtx_update_math.h), so the records are the host's bit for bit
 //   TLAS               the balanced tree of rtx_update_math.h: sort by (box finite?, Morton code, index), implicit heap over the sorted range, boxes
-//                      bottom-up from the stored child boxes, both device node layouts (convert_nodes / convert_nodes_pk of rtx_api.hip)
+//                      bottom-up from the stored child boxes, both device node layouts (rtx_layout.h)
 //
 // Up to RTX_UPDATE_SMALL_MAX instances ONE workgroup does all of it in one launch (k_update_small): the scene is a few KiB, the work is a
 // chain of dependent steps, and a launch costs more than any of them — bounds by LDS atomics, a bitonic sort of the 64-bit keys in LDS
@@ -15,6 +15,7 @@
 #include <stdint.h>
 #include "rtx_device.h"
 #include "rtx_update_math.h"
+#include "rtx_layout.h"
 
 #define RTX_UPDATE_SMALL_MAX   1024
 #define RTX_UPDATE_BLOCK       1024
@@ -55,23 +56,13 @@ static __device__ __forceinline__ rtxu::Box upd_instance(const DevUpdate & u, in
     return b;
 }
 
-// both device layouts of one slot (convert_nodes, convert_nodes_pk)
-static __device__ __forceinline__ void upd_store_node(const DevUpdate & u, int slot, const rtxu::Box & b, int32_t left_or_first, int32_t count) {
-    const float l = __int_as_float(left_or_first), c = __int_as_float(count);
-    u.nodes[2 * slot]        = make_float4(b.mn[0], b.mn[1], b.mn[2], l);
-    u.nodes[2 * slot + 1]    = make_float4(b.mx[0], b.mx[1], b.mx[2], c);
-    u.pk_nodes[2 * slot]     = make_float4(b.mn[0], b.mn[1], b.mx[0], b.mx[1]);
-    u.pk_nodes[2 * slot + 1] = make_float4(b.mn[2], b.mx[2], l, c);
-}
-
 // Node (d, j).  LoadChild(slot) returns the stored box of a child written by level d + 1.  Returns false for a hole (zeroed).
 template <typename LoadChild>
 static __device__ __forceinline__ bool upd_node(const DevUpdate & u, int d, int j, rtxu::Box & b, LoadChild && load_child) {
     int first;
     const int cnt = rtxu::node_range(u.n, d, j, &first), slot = rtxu::node_slot(d, j);
     if (cnt == 0) {
-        const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        u.nodes[2 * slot] = z; u.nodes[2 * slot + 1] = z; u.pk_nodes[2 * slot] = z; u.pk_nodes[2 * slot + 1] = z;
+        rtxl::store_hole(u.nodes, u.pk_nodes, slot);
         return false;
     }
     if (cnt == 1) {
@@ -79,27 +70,22 @@ static __device__ __forceinline__ bool upd_node(const DevUpdate & u, int d, int 
         u.indices[first] = inst;
         for (int a = 0; a < 3; a++) { b.mn[a] = u.aabbs[6 * inst + a]; b.mx[a] = u.aabbs[6 * inst + 3 + a]; }
         rtxu::fix_if_needed(b);
-        upd_store_node(u, slot, b, first, 1);
+        rtxl::store_node(u.nodes, u.pk_nodes, slot, b, first, 1);
         return true;
     }
     const int left = (2 << d) | (2 * j);                              // slot of (d + 1, 2j); the root's children sit at 2, 3
     int axis;
     b = rtxu::join_boxes(load_child(left), load_child(left + 1), &axis);
-    upd_store_node(u, slot, b, left, (int32_t)((uint32_t)axis << 30));
+    rtxl::store_node(u.nodes, u.pk_nodes, slot, b, left, (int32_t)((uint32_t)axis << 30));
     return true;
 }
 
-static __device__ __forceinline__ rtxu::Box upd_load_box(const float4 * nodes, int slot) {
-    const float4 a = nodes[2 * slot], c = nodes[2 * slot + 1];
-    rtxu::Box b; b.mn[0] = a.x; b.mn[1] = a.y; b.mn[2] = a.z; b.mx[0] = c.x; b.mx[1] = c.y; b.mx[2] = c.z;
-    return b;
-}
-
-// the reduced bounds as sort_key wants them; a reduction nothing took part in (no finite coordinate on that axis) still holds its initial value
-static __device__ __forceinline__ void upd_bounds(const uint32_t * bounds, uint32_t b6[6]) {
-    for (int a = 0; a < 3; a++) {
-        const uint32_t lo = bounds[a], hc = bounds[3 + a];
-        b6[a] = lo == 0xffffffffu ? RTXU_KEY_LO_INIT : lo; b6[3 + a] = hc == 0xffffffffu ? RTXU_KEY_HI_INIT : ~hc;
+// the six ordered-integer bounds of a wave's lanes (0xffffffff: the lane takes no part): wave64 min, then one atomic per wave and value
+static __device__ __forceinline__ void upd_reduce_bounds(const uint32_t k6[6], uint32_t * bounds) {
+    for (int a = 0; a < 6; a++) {
+        uint32_t v = k6[a];
+        for (int o = 32; o > 0; o >>= 1) { const uint32_t w = (uint32_t)__shfl_xor((int)v, o, 64); v = w < v ? w : v; }
+        if ((threadIdx.x & 63) == 0 && v != 0xffffffffu) atomicMin(&bounds[a], v);
     }
 }
 
@@ -121,7 +107,7 @@ __global__ __launch_bounds__(RTX_UPDATE_BLOCK) void k_update_small(const DevUpda
     int P = 1; while (P < n) P <<= 1;                                  // bitonic sort over the next power of two; padding keys sort last
     if (tid < P) {
         uint64_t key = ~0ull;
-        if (tid < n) { uint32_t b6[6]; upd_bounds(s_bounds, b6); key = rtxu::sort_key(pos, b6, (uint32_t)tid, finite_box); }
+        if (tid < n) { uint32_t b6[6]; rtxu::reduced_bounds(s_bounds, b6); key = rtxu::sort_key(pos, b6, (uint32_t)tid, finite_box); }
         s_keys[tid] = key;
     }
     __syncthreads();
@@ -137,10 +123,7 @@ __global__ __launch_bounds__(RTX_UPDATE_BLOCK) void k_update_small(const DevUpda
         }
     if (tid < n) u.keys[tid] = s_keys[tid];
     __syncthreads();                                                   // keys and AABBs written above are read below by other lanes of this workgroup
-    if (tid == 0) {                                                    // index 1: unused in the reference's arrays, zero here
-        const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        u.nodes[2] = z; u.nodes[3] = z; u.pk_nodes[2] = z; u.pk_nodes[3] = z;
-    }
+    if (tid == 0) rtxl::store_hole(u.nodes, u.pk_nodes, 1);             // index 1: unused in the reference's arrays, zero here
     for (int d = u.levels; d >= 0; d--) {
         if (tid < (1 << d)) {
             rtxu::Box b;
@@ -160,18 +143,14 @@ __global__ __launch_bounds__(256) void k_update_instances(const DevUpdate u) {
         upd_instance(u, i, pos);
         for (int a = 0; a < 3; a++) if (rtxu::is_finite(pos[a])) { const uint32_t k = rtxu::ordered_key(pos[a]); k6[a] = k; k6[3 + a] = ~k; }
     }
-    for (int a = 0; a < 6; a++) {                                      // wave64 min, then one atomic per wave and value
-        uint32_t v = k6[a];
-        for (int o = 32; o > 0; o >>= 1) { const uint32_t w = (uint32_t)__shfl_xor((int)v, o, 64); v = w < v ? w : v; }
-        if ((threadIdx.x & 63) == 0 && v != 0xffffffffu) atomicMin(&u.bounds[a], v);
-    }
+    upd_reduce_bounds(k6, u.bounds);
 }
 
 __global__ __launch_bounds__(256) void k_update_keys(const DevUpdate u, uint64_t * __restrict__ keys_out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= u.n) return;
     uint32_t b6[6];
-    upd_bounds(u.bounds, b6);
+    rtxu::reduced_bounds(u.bounds, b6);
     const float pos[3] = { u.positions[3 * i], u.positions[3 * i + 1], u.positions[3 * i + 2] };
     rtxu::Box b;                                                       // the AABB k_update_instances stored
     for (int a = 0; a < 3; a++) { b.mn[a] = u.aabbs[6 * i + a]; b.mx[a] = u.aabbs[6 * i + 3 + a]; }
@@ -183,20 +162,17 @@ __global__ __launch_bounds__(256) void k_update_level(const DevUpdate u, const i
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= (1 << d)) return;
     rtxu::Box b;
-    upd_node(u, d, j, b, [&](int slot) { return upd_load_box(u.nodes, slot); });
+    upd_node(u, d, j, b, [&](int slot) { return rtxl::load_box(u.nodes, slot); });
 }
 
 // levels min(levels, RTX_UPDATE_TOP_LEVELS) .. 0 in one workgroup
 __global__ __launch_bounds__(RTX_UPDATE_BLOCK) void k_update_top(const DevUpdate u) {
     const int tid = threadIdx.x;
-    if (tid == 0) {
-        const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        u.nodes[2] = z; u.nodes[3] = z; u.pk_nodes[2] = z; u.pk_nodes[3] = z;
-    }
+    if (tid == 0) rtxl::store_hole(u.nodes, u.pk_nodes, 1);
     for (int d = u.levels < RTX_UPDATE_TOP_LEVELS ? u.levels : RTX_UPDATE_TOP_LEVELS; d >= 0; d--) {
         if (tid < (1 << d)) {
             rtxu::Box b;
-            upd_node(u, d, tid, b, [&](int slot) { return upd_load_box(u.nodes, slot); });
+            upd_node(u, d, tid, b, [&](int slot) { return rtxl::load_box(u.nodes, slot); });
         }
         __syncthreads();                                               // the level's global stores are visible to the workgroup's next level
     }

@@ -100,6 +100,14 @@ RTX_HD float ordered_value(uint32_t k) { const uint32_t u = (k & 0x80000000u) ? 
 RTX_HD bool is_finite(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return (u & 0x7f800000u) != 0x7f800000u; }
 #define RTXU_KEY_LO_INIT 0xff800000u     // ordered_key(+inf): the bounds when no position component is finite
 #define RTXU_KEY_HI_INIT 0x007fffffu     // ordered_key(-inf)
+// the bounds as sort_key wants them, from six min-reduced keys (lo.xyz as they are, hi.xyz complemented; 0xffffffff before the reduction): a
+// reduction nothing took part in (no finite coordinate on that axis) still holds its initial value
+RTX_HD void reduced_bounds(const uint32_t * bounds, uint32_t b6[6]) {
+    for (int a = 0; a < 3; a++) {
+        const uint32_t lo = bounds[a], hc = bounds[3 + a];
+        b6[a] = lo == 0xffffffffu ? RTXU_KEY_LO_INIT : lo; b6[3 + a] = hc == 0xffffffffu ? RTXU_KEY_HI_INIT : ~hc;
+    }
+}
 
 // one coordinate -> one of 1024 cells between the bounds of the finite coordinates of that axis.  Clamped; a NaN (a NaN coordinate, or
 // 0 / 0 when all coordinates are equal) is cell 0, so every float input has a cell and no conversion is out of range.

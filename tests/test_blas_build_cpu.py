@@ -63,7 +63,7 @@ def levels_of(n):
 
 
 def wide_conditions(nodes, tri_count):
-    """build_nodes_pk4 / build_nodes_pk4c of rtx_api.hip restated: min <= max, leaves below 16 triangles, even `left`, children nested in
+    """build_nodes_pk4 / build_nodes_pk4c of csrc/rtx_layout_host.h restated: min <= max, leaves below 16 triangles, even `left`, children nested in
     the stored floats, fewer than 2^24 nodes and triangles.  -> (pk4 need with smallest need first, pk4c need)"""
     n = len(nodes)
     assert n < (1 << 24) and tri_count < (1 << 24)

@@ -298,7 +298,7 @@ def test_group_frames_in_flight_share_one_communicator(api):
 
 
 def test_shadow_walk_uses_wide_records_for_reference_trees_and_binary_walk_otherwise(api):
-    """The shadow-ray packet walk takes the 4-wide records (csrc/rtx_api.hip build_nodes_pk4) only for meshes whose child boxes lie
+    """The shadow-ray packet walk takes the 4-wide records (csrc/rtx_layout_host.h build_nodes_pk4) only for meshes whose child boxes lie
     inside their parents' boxes — every tree the reference builds.  A tree that violates the nesting keeps the binary walk, and both
     produce the frame of the oracle, which walks the binary tree node by node as BottomLevelBVH::intersect does."""
     import copy

@@ -3,13 +3,18 @@ the device's read-back layouts with (tests/test_gpu_layouts.py) — on trees wri
 children of the root are leaves) and of 9 triangles (the left child a leaf of 4, the right child inner: a three-slot record whose third
 and fourth slots carry their parent's axis).  The expected records are spelled out here word by word, and every check is shown to fail on
 a record with one wrong word.  No GPU, no library."""
+import os
 import struct
+import subprocess
 
 import numpy as np
 import pytest
 
 import layoutset as ls
+import util
 from pyrtx import scene_io as sio
+
+CSRC = os.path.join(util.REPO, "cpu-raytracer_amd", "csrc")
 
 
 def bits(x):
@@ -164,3 +169,14 @@ def test_every_check_bites_on_one_wrong_word(name):
         swapped = good.copy(); swapped[[k, k + 1]] = good[[k + 1, k]]
         fails(ls.check_planes, nodes, a, swapped)
         fails(ls.check_planes, nodes, a, good[:-1])
+
+
+def test_layout_check_passes():
+    """csrc/layout_check.cpp: the record writers of csrc/rtx_layout.h and the host converters of csrc/rtx_layout_host.h against records spelled
+    out by hand (the rows above, as C literals), the lane record's round trip, and the finish pass of a refit and a build run on the host
+    over converted trees.  A stand-alone program built with the host compiler under -fsanitize=address,undefined; nothing is loaded into
+    Python and no GPU is needed."""
+    out = subprocess.run(["make", "-B", "-C", CSRC, "layout_check"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-4000:] + out.stderr[-4000:]
+    assert "layout_check: ok" in out.stdout.splitlines(), out.stdout[-4000:]
+    assert "FAILED" not in out.stdout
