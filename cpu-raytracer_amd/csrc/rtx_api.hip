@@ -32,6 +32,7 @@
 #include "rtx_refit.h"
 #include "rtx_build.h"
 #include "rtx_query.h"
+#include "rtx_texmip.h"
 #include <rocprim/device/device_radix_sort.hpp>      // rtx_update_instances, scenes beyond one workgroup: header-only, part of ROCm
 #include "rtx_hostmem.h"                             // DevBuf, StageRing, grow_keep: every device and pinned allocation has one owner
 #include "rtx_layout_host.h"                         // convert_nodes*, build_nodes_pk4*, parent_table, balanced_topology: trees to the layouts of rtx_layout.h (no HIP in it; layout_check.cpp)
@@ -82,6 +83,12 @@ struct rtx_ctx {
     DevBuf d_blas, d_materials, d_textures, d_sky, d_ewa;
     std::vector<DevTexture> h_tex;
     std::vector<DevBuf> tex_texels;             // per texture id, beside h_tex
+    // rtx_alloc_texture / rtx_update_texture: per texture id, beside h_tex — allocated: the chain is this project's own (rtx_upload_texture
+    // clears it), plan: the launches of an update, made once at the alloc; the byte -> linear table of RTX_TEXELS_RGBA8_SRGB, once per context
+    struct TexUpdate { bool allocated = false; rtxt::Plan plan; };
+    std::vector<TexUpdate> tex_update;
+    DevBuf d_srgb_lut;
+    bool sky_uploaded = false;                  // rtx_update_sky copies over the probe rtx_upload_sky made, not over the context's black default
     int material_count = 0, sky_size = 0;
     std::vector<rtx_material> h_materials; int tlas_inner_depth = -1; std::vector<int> frame_primitive_materials; bool refs_dirty = true; Knobs knobs; int item_blocks = 0, item_cap_alloc = 0; DevBuf d_pk_items, d_pk_item_count;
 
@@ -215,6 +222,7 @@ extern "C" int rtx_create(const rtx_config * config, rtx_ctx ** out_ctx) {
     K.no_wide_closest = knob_int("RTX_PK_WIDE_CLOSEST", 1, 0, 1) == 0;  // 0: binary per-lane phase of the closest-hit walk for every mesh
     K.fuse_shade = knob_int("RTX_FUSE_SHADE", 0, 0, 1) != 0;      // measured: 1.51 vs 1.28 ms per cfg3 frame with three frames in flight: off
     K.update_small_max = (int)knob_int("RTX_UPDATE_SMALL_MAX", RTX_UPDATE_SMALL_MAX, 0, RTX_UPDATE_SMALL_MAX);
+    K.tex_pass_levels = (int)knob_int("RTX_TEX_PASS_LEVELS", rtxt::DEFAULT_PASS_LEVELS, 1, rtxt::MAX_PASS_LEVELS);      // DESIGN.md 9, Device-side texture update
     K.fail_item_alloc = knob_int("RTX_DEBUG_FAIL_ITEM_ALLOC", 0, 0, 1) != 0;      // tests: the item buffer's allocation fails (a size no device has), the fallback kernel must take over
     int bpc = 0;
     hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k_trace_fast<false>, RTX_TRACE_BLOCK, 0);
@@ -417,6 +425,22 @@ extern "C" int rtx_upload_materials(rtx_ctx * c, const rtx_material * materials,
     return upload(c, c->d_materials, materials, (size_t)count * sizeof(rtx_material));
 }
 
+// texture_id now holds the texel array d with the descriptor desc: rtx_upload_texture and rtx_alloc_texture end here
+static int commit_texture(rtx_ctx * c, int32_t texture_id, const rtx_texture_desc & desc, DevBuf & d, const rtx_ctx::TexUpdate & update) {
+    if ((size_t)texture_id >= c->h_tex.size()) {
+        const size_t old = c->h_tex.size();
+        c->h_tex.resize(texture_id + 1); c->tex_texels.resize(texture_id + 1); c->tex_update.resize(texture_id + 1);
+        for (size_t i = old; i < c->h_tex.size(); i++) memset(&c->h_tex[i], 0, sizeof(DevTexture));
+    }
+    if (c->h_tex[texture_id].texels) HIP_OK(c, hipStreamSynchronize(c->stream));      // re-upload of an id: the old texel array is released after the frames that may still read it
+    c->h_tex[texture_id].desc = desc;
+    c->h_tex[texture_id].texels = (const float4 *)d.p;
+    c->tex_texels[texture_id] = std::move(d);
+    c->tex_update[texture_id] = update;
+    c->refs_dirty = true;
+    return upload(c, c->d_textures, c->h_tex.data(), c->h_tex.size() * sizeof(DevTexture));
+}
+
 extern "C" int rtx_upload_texture(rtx_ctx * c, int32_t texture_id, const rtx_texture_desc * desc, const float * texels_rgb, int64_t texel_count) {
     if (!c || texture_id < 0 || texture_id >= 4096 || !desc || !texels_rgb) return RTX_ERR_INVALID_ARG;
     if (desc->width <= 0 || desc->height <= 0 || desc->mip_levels < 1 || desc->mip_levels > RTX_MAX_MIP_LEVELS) return RTX_ERR_INVALID_ARG;
@@ -425,19 +449,13 @@ extern "C" int rtx_upload_texture(rtx_ctx * c, int32_t texture_id, const rtx_tex
         if (lw < 1 || lh < 1 || desc->mip_offsets[l] < 0 || desc->mip_offsets[l] + lw * lh > texel_count) return RTX_ERR_INVALID_ARG;
     }
     hipSetDevice(c->cfg.device);
-    if ((size_t)texture_id >= c->h_tex.size()) { size_t old = c->h_tex.size(); c->h_tex.resize(texture_id + 1); c->tex_texels.resize(texture_id + 1); for (size_t i = old; i < c->h_tex.size(); i++) memset(&c->h_tex[i], 0, sizeof(DevTexture)); }
     DevBuf d;
     {   // float3 texels of the ABI -> one float4 per texel on the device
         std::vector<float4> padded((size_t)texel_count);
         for (int64_t i = 0; i < texel_count; i++) padded[(size_t)i] = make_float4(texels_rgb[3 * i], texels_rgb[3 * i + 1], texels_rgb[3 * i + 2], 0.0f);
         if (int rc = upload(c, d, padded.data(), (size_t)texel_count * 16)) return rc;
     }
-    if (c->h_tex[texture_id].texels) HIP_OK(c, hipStreamSynchronize(c->stream));      // re-upload of an id: the old texel array is released after the frames that may still read it
-    c->h_tex[texture_id].desc = *desc;
-    c->h_tex[texture_id].texels = (const float4 *)d.p;
-    c->tex_texels[texture_id] = std::move(d);
-    c->refs_dirty = true;
-    return upload(c, c->d_textures, c->h_tex.data(), c->h_tex.size() * sizeof(DevTexture));
+    return commit_texture(c, texture_id, *desc, d, rtx_ctx::TexUpdate());
 }
 
 extern "C" int rtx_upload_sky(rtx_ctx * c, const float * texels_rgb, int32_t size) {
@@ -447,7 +465,9 @@ extern "C" int rtx_upload_sky(rtx_ctx * c, const float * texels_rgb, int32_t siz
     std::vector<float> padded((size_t)size * size * 3 + 3, 0.0f);
     memcpy(padded.data(), texels_rgb, (size_t)size * size * 12);
     c->sky_size = size;
-    return upload(c, c->d_sky, padded.data(), padded.size() * 4);
+    if (int rc = upload(c, c->d_sky, padded.data(), padded.size() * 4)) return rc;
+    c->sky_uploaded = true;
+    return RTX_OK;
 }
 
 extern "C" int rtx_set_frame(rtx_ctx * c, const rtx_frame * f) {
@@ -997,6 +1017,87 @@ extern "C" int rtx_read_blas(rtx_ctx * c, int32_t blas_id, rtx_bvh_node * nodes,
         }
     }
     if (cold && B.tri_count) HIP_OK(c, hipMemcpy(cold, B.tri_cold, (size_t)B.tri_count * sizeof(rtx_triangle_cold), hipMemcpyDeviceToHost));
+    return RTX_OK;
+}
+
+// ---- device-side texture and sky update (include/rtx.h: rtx_alloc_texture / rtx_update_texture / rtx_read_texture / rtx_update_sky;
+// kernels in rtx_texmip.h) ---------------------------------------------------------------------------------------------------------------
+// Everything the host decides about a chain — its shape, the passes that rewrite it — follows from (width, height, mipmapped, P) and is
+// decided at the alloc.  An update is then queued like a refit: it writes the texels in place, touches no pointer and reads nothing back.
+extern "C" int rtx_alloc_texture(rtx_ctx * c, int32_t texture_id, int32_t width, int32_t height, int32_t mipmapped) {
+    if (!c) return RTX_ERR_INVALID_ARG;
+    if (texture_id < 0 || texture_id >= 4096 || width < 1 || height < 1) { c->err = "rtx_alloc_texture: id outside [0, 4096) or an empty side"; return RTX_ERR_INVALID_ARG; }
+    rtx_texture_desc desc; int64_t texel_count = 0;
+    if (rtxt::chain_shape(width, height, mipmapped, &desc, &texel_count)) { c->err = "rtx_alloc_texture: more than RTX_MAX_MIP_LEVELS levels, or more texels than the int32_t offsets hold"; return RTX_ERR_LIMIT; }
+    hipSetDevice(c->cfg.device);
+    if (!c->d_srgb_lut.p) {
+        float lut[256];                                                     // colour_unpack + Math::gamma_to_linear as rtxh_texture_load evaluates them (host/rtx_image.cpp), host libm
+        for (int b = 0; b < 256; b++) {
+            const float x = float(b) * 0.00392156862f;
+            lut[b] = x <= 0.0f ? 0.0f : x >= 1.0f ? 1.0f : x < 0.04045f ? x / 12.92f : powf((x + 0.055f) / 1.055f, 2.4f);
+        }
+        DevBuf t;
+        if (int rc = upload(c, t, lut, sizeof(lut))) return rc;
+        c->d_srgb_lut = std::move(t);
+    }
+    DevBuf d;
+    if (int rc = ensure(c, d, (size_t)texel_count * 16)) return rc;
+    HIP_OK(c, hipMemsetAsync(d.p, 0, (size_t)texel_count * 16, c->stream));      // ordered before every update and render call; rtx_set_stream waits for it
+    rtx_ctx::TexUpdate U;
+    U.allocated = true;
+    U.plan = rtxt::plan_passes(width, height, desc.mip_levels, c->knobs.tex_pass_levels);
+    return commit_texture(c, texture_id, desc, d, U);
+}
+
+extern "C" int rtx_update_texture(rtx_ctx * c, int32_t texture_id, const void * texels_dev, int32_t format) {
+    if (!c) return RTX_ERR_INVALID_ARG;
+    if (!texels_dev || (format != RTX_TEXELS_RGB_F32 && format != RTX_TEXELS_RGBA8_SRGB) || (format == RTX_TEXELS_RGB_F32 && ((uintptr_t)texels_dev & 3))) {
+        c->err = "rtx_update_texture: null or misaligned texel pointer, or an unknown format"; return RTX_ERR_INVALID_ARG; }
+    if (texture_id < 0 || (size_t)texture_id >= c->h_tex.size() || !c->h_tex[texture_id].texels || !c->tex_update[texture_id].allocated) {
+        c->err = "rtx_update_texture: the id was not created by rtx_alloc_texture (or was uploaded again since)"; return RTX_ERR_STATE; }
+    hipSetDevice(c->cfg.device);
+    const rtxt::Plan & plan = c->tex_update[texture_id].plan;
+    float4 * const chain = (float4 *)c->tex_texels[texture_id].p;
+    const float * const lut = (const float *)c->d_srgb_lut.p;
+    for (int k = 0; k < plan.count; k++) {
+        const rtxt::Pass & p = plan.pass[k];
+        const dim3 grid((unsigned)(p.tiles_x * p.tiles_y)), block(rtxt::BLOCK);
+        if (k > 0) launch_timed(c, "k_texmip_chain", c->stream, [&] { hipLaunchKernelGGL(k_texmip<TEXMIP_CHAIN>, grid, block, 0, c->stream, p, (const void *)nullptr, chain, lut); });
+        else if (format == RTX_TEXELS_RGB_F32) launch_timed(c, "k_texmip_rgb_f32", c->stream, [&] { hipLaunchKernelGGL(k_texmip<TEXMIP_RGB_F32>, grid, block, 0, c->stream, p, texels_dev, chain, lut); });
+        else launch_timed(c, "k_texmip_rgba8", c->stream, [&] { hipLaunchKernelGGL(k_texmip<TEXMIP_RGBA8_SRGB>, grid, block, 0, c->stream, p, texels_dev, chain, lut); });
+    }
+    HIP_OK(c, hipGetLastError());
+    return RTX_OK;
+}
+
+extern "C" int rtx_read_texture(rtx_ctx * c, int32_t texture_id, rtx_texture_desc * desc, float * texels_rgb, int64_t capacity_texels) {
+    if (!c) return RTX_ERR_INVALID_ARG;
+    if (texture_id < 0 || texture_id >= 4096) { c->err = "rtx_read_texture: bad id"; return RTX_ERR_INVALID_ARG; }
+    if ((size_t)texture_id >= c->h_tex.size() || !c->h_tex[texture_id].texels) { c->err = "rtx_read_texture: no texture under that id"; return RTX_ERR_STATE; }
+    const DevTexture & T = c->h_tex[texture_id];
+    int64_t count = 0;                         // the end of the level that ends last: a caller-made chain need not be laid out in level order
+    for (int l = 0; l < T.desc.mip_levels; l++) {
+        const int64_t end = (int64_t)T.desc.mip_offsets[l] + (int64_t)(T.desc.width >> l) * (T.desc.height >> l);
+        if (end > count) count = end;
+    }
+    if (texels_rgb && capacity_texels < count) { c->err = "rtx_read_texture: capacity_texels is smaller than the chain"; return RTX_ERR_INVALID_ARG; }
+    if (desc) *desc = T.desc;
+    if (!texels_rgb) return RTX_OK;
+    hipSetDevice(c->cfg.device);
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    std::vector<float4> padded((size_t)count);
+    HIP_OK(c, hipMemcpy(padded.data(), T.texels, (size_t)count * 16, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < count; i++) { texels_rgb[3 * i] = padded[(size_t)i].x; texels_rgb[3 * i + 1] = padded[(size_t)i].y; texels_rgb[3 * i + 2] = padded[(size_t)i].z; }
+    return RTX_OK;
+}
+
+extern "C" int rtx_update_sky(rtx_ctx * c, const void * texels_dev, int32_t size) {
+    if (!c) return RTX_ERR_INVALID_ARG;
+    if (!texels_dev || ((uintptr_t)texels_dev & 3)) { c->err = "rtx_update_sky: null or misaligned texel pointer"; return RTX_ERR_INVALID_ARG; }
+    if (!c->sky_uploaded) { c->err = "rtx_update_sky: no probe to copy over (rtx_upload_sky)"; return RTX_ERR_STATE; }
+    if (size != c->sky_size) { c->err = "rtx_update_sky: size differs from the uploaded one"; return RTX_ERR_INVALID_ARG; }
+    hipSetDevice(c->cfg.device);
+    HIP_OK(c, hipMemcpyAsync(c->d_sky.p, texels_dev, (size_t)size * size * 12, hipMemcpyDeviceToDevice, c->stream));      // the padding texel behind stays zero
     return RTX_OK;
 }
 

@@ -25,6 +25,7 @@ struct Knobs {
     bool merge_any, no_wide, no_wide_closest, fail_item_alloc, graph; int lpt;
     bool fuse_shade;             // RTX_FUSE_SHADE         the closest-hit packet kernel shades its own hits (0: a k_shade launch per level)
     int update_small_max;        // RTX_UPDATE_SMALL_MAX   rtx_update_instances: scenes up to this many instances take the one-workgroup kernel (0: always the multi-launch path)
+    int tex_pass_levels;         // RTX_TEX_PASS_LEVELS    rtx_update_texture: mip levels one launch makes below the level it reads, 1 .. 5 (1: a launch per level)
 };
 
 // What the uploaded trees ask of the packet kernels' one stack (plan_stack_limits): unfit_mesh = some mesh exceeds the packet kernels' packed

@@ -8,6 +8,7 @@
 #include "../csrc/rtx_update_math.h"
 #include "../csrc/rtx_refit_math.h"
 #include "../csrc/rtx_build_math.h"
+#include "../csrc/rtx_texmip_math.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -547,33 +548,18 @@ extern "C" int rtxh_blas_build(const float * positions, int32_t n, int32_t bins,
 // Texture::load mip chain, Texture.cpp:76-117 (box filter, levels appended after level 0)
 extern "C" int rtxh_texture_mips(float * tx, int32_t width, int32_t height, rtx_texture_desc * desc, int64_t * texel_count_out) {
     if (!tx || !desc || width <= 0 || height <= 0) return RTX_ERR_INVALID_ARG;
-    memset(desc, 0, sizeof(*desc));
-    desc->width = width; desc->height = height;
-    const bool pow2 = ((width & (width - 1)) == 0) && ((height & (height - 1)) == 0);   // Math::is_power_of_two, Texture.cpp:50
-    if (!pow2) { desc->mipmapped = 0; desc->mip_levels = 1; if (texel_count_out) *texel_count_out = (int64_t)width * height; return RTX_OK; }
-    desc->mipmapped = 1;
-    desc->mip_levels = 1 + (int)log2f((float)(width < height ? width : height));
-    if (desc->mip_levels > RTX_MAX_MIP_LEVELS) return RTX_ERR_LIMIT;
-    int offset = width * height, offset_prev = 0;
-    int lw = width >> 1, lh = height >> 1, lwp = width;
-    int level = 1;
-    while (lw >= 1 && lh >= 1) {
-        for (int j = 0; j < lh; j++) for (int i = 0; i < lw; i++) {
-            const int ip = i << 1, jp = j << 1;
-            const float * c0 = tx + 3 * (size_t)(offset_prev + ip + jp * lwp);
-            const float * c1 = tx + 3 * (size_t)(offset_prev + (ip + 1) + jp * lwp);
-            const float * c2 = tx + 3 * (size_t)(offset_prev + ip + (jp + 1) * lwp);
-            const float * c3 = tx + 3 * (size_t)(offset_prev + (ip + 1) + (jp + 1) * lwp);
-            float * o = tx + 3 * (size_t)(offset + i + j * lw);
-            for (int k = 0; k < 3; k++) o[k] = (((c0[k] + c1[k]) + c2[k]) + c3[k]) * 0.25f;
+    int64_t count = 0;
+    if (int rc = rtxt::chain_shape(width, height, 1, desc, &count)) return rc;      // the shape and the filter the device chain has too (rtx_texmip_math.h)
+    for (int l = 1; l < desc->mip_levels; l++) {
+        const int lw = width >> l, lh = height >> l, lwp = width >> (l - 1);
+        const float * prev = tx + 3 * (size_t)desc->mip_offsets[l - 1];
+        float * o = tx + 3 * (size_t)desc->mip_offsets[l];
+        for (int j = 0; j < lh; j++) for (int i = 0; i < lw; i++, o += 3) {
+            const float * c0 = prev + 3 * ((size_t)(2 * i) + (size_t)(2 * j) * lwp), * c2 = c0 + 3 * (size_t)lwp;
+            for (int k = 0; k < 3; k++) o[k] = rtxt::box(c0[k], c0[3 + k], c2[k], c2[3 + k]);
         }
-        desc->mip_offsets[level++] = offset;
-        offset_prev = offset;
-        offset += lw * lh;
-        lwp = lw;
-        lw >>= 1; lh >>= 1;
     }
-    if (texel_count_out) *texel_count_out = offset;
+    if (texel_count_out) *texel_count_out = count;
     return RTX_OK;
 }
 

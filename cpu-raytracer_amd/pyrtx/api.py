@@ -26,7 +26,8 @@ EXPORTS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error", "rt
            "rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer", "rtx_bind_aovs", "rtx_read_aovs",
            "rtx_set_rays", "rtx_bind_rays", "rtx_render_rays", "rtx_update_instances", "rtx_read_frame_state",
            "rtx_bind_blas_vertices", "rtx_refit_blas", "rtx_read_blas", "rtx_alloc_blas", "rtx_build_blas",
-           "rtx_query_closest", "rtx_query_occluded", "rtx_debug_read_layouts"]
+           "rtx_query_closest", "rtx_query_occluded", "rtx_debug_read_layouts",
+           "rtx_alloc_texture", "rtx_update_texture", "rtx_read_texture", "rtx_update_sky"]
 # newer than the A/B variants tools/ab.py may load (RTX_HIP_LIB = a library built from an older commit): bound when the library has them,
 # otherwise a call raises AttributeError (undefined symbol)
 VIEW_EXPORTS = ("rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer")
@@ -37,6 +38,10 @@ REFIT_EXPORTS = ("rtx_bind_blas_vertices", "rtx_refit_blas", "rtx_read_blas")
 BUILD_EXPORTS = ("rtx_alloc_blas", "rtx_build_blas")
 QUERY_EXPORTS = ("rtx_query_closest", "rtx_query_occluded")
 LAYOUT_EXPORTS = ("rtx_debug_read_layouts",)
+TEXTURE_EXPORTS = ("rtx_alloc_texture", "rtx_update_texture", "rtx_read_texture", "rtx_update_sky")
+# texel formats of rtx_update_texture (include/rtx.h RTX_TEXELS_*)
+RTX_TEXELS_RGB_F32 = 0
+RTX_TEXELS_RGBA8_SRGB = 1
 RTX_UPDATE_MAX_INSTANCES = 65536
 
 RTX_RENDER_COUNT_WORK = 1
@@ -155,8 +160,13 @@ def load_library(path: Optional[str] = None):
         lib.rtx_query_occluded.argtypes = [vp, vp, C.c_int64, vp, u32]
     if hasattr(lib, "rtx_debug_read_layouts"):
         lib.rtx_debug_read_layouts.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "rtx_update_texture"):
+        lib.rtx_alloc_texture.argtypes = [vp, i32, i32, i32, i32]
+        lib.rtx_update_texture.argtypes = [vp, i32, vp, i32]
+        lib.rtx_read_texture.argtypes = [vp, i32, C.POINTER(RtxTextureDesc), vp, C.c_int64]
+        lib.rtx_update_sky.argtypes = [vp, vp, i32]
     for name in EXPORTS:
-        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + LAYOUT_EXPORTS and not hasattr(lib, name):
+        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + LAYOUT_EXPORTS + TEXTURE_EXPORTS and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         if name not in ("rtx_last_error",):
@@ -836,6 +846,72 @@ class Renderer:
         nodes = np.zeros(n, sio.BVH_NODE); hot = np.zeros(m, sio.TRI_HOT); cold = np.zeros(m, sio.TRI_COLD)
         self._chk(self.lib.rtx_read_blas(self.ctx, int(blas_id), nodes.ctypes.data, hot.ctypes.data, cold.ctypes.data), "rtx_read_blas")
         return sio.Blas(nodes, hot, cold, off, src)
+
+    # ---- device-side texture and sky update (include/rtx.h: rtx_alloc_texture / rtx_update_texture / rtx_read_texture / rtx_update_sky) ----
+    def alloc_texture(self, texture_id: int, width: int, height: int, mipmapped: Optional[bool] = None):
+        """Once per texture: a zeroed width x height texture under texture_id whose texels update_texture rewrites from device memory, with
+        the mip chain Texture::load would give it when mipmapped (None: the scene's texture_mode is the mipmap mode) and both sides are powers
+        of two.  May allocate and wait."""
+        if mipmapped is None:
+            mipmapped = int(self.scene.config["texture_mode"][0]) == 2
+        self._chk(self.lib.rtx_alloc_texture(self.ctx, int(texture_id), int(width), int(height), 1 if mipmapped else 0), "rtx_alloc_texture")
+
+    def _texture_shape(self, texture_id: int):
+        """(H, W) of the texture the context holds under texture_id, however it got there (the library's own descriptor: nothing waits), or
+        None when the id holds nothing."""
+        desc = RtxTextureDesc()
+        if self.lib.rtx_read_texture(self.ctx, int(texture_id), C.byref(desc), None, 0):
+            return None
+        return (int(desc.height), int(desc.width))
+
+    @staticmethod
+    def _texel_tensor(name: str, t, device: int, shape=None) -> int:
+        """The RTX_TEXELS_* format of a texel tensor ((H, W, 3) float32 or (H, W, 4) uint8, contiguous, on cuda:device, of `shape` = (H, W) when
+        given); ValueError before anything reaches the library."""
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch.Tensor, not {type(t).__name__}")
+        if t.dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"{name} must be torch.float32 (H, W, 3) or torch.uint8 (H, W, 4), not {t.dtype}")
+        channels = 3 if t.dtype == torch.float32 else 4
+        if t.dim() != 3 or t.shape[2] != channels or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"{name} of {t.dtype} must have shape (H, W, {channels}), not {tuple(t.shape)}")
+        if shape is not None and tuple(t.shape[:2]) != tuple(shape):
+            raise ValueError(f"{name} must be ({shape[0]}, {shape[1]}, {channels}), the size of the texture, not {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if t.device.type != "cuda" or t.device.index != device:
+            raise ValueError(f"{name} must be on cuda:{device} (this context's GPU), not {t.device}")
+        return RTX_TEXELS_RGB_F32 if t.dtype == torch.float32 else RTX_TEXELS_RGBA8_SRGB
+
+    def update_texture(self, texture_id: int, tensor):
+        """New texels of an alloc_texture id from DEVICE memory: a contiguous torch tensor on this context's GPU of the allocated size, (H, W, 3)
+        float32 in linear light (what render_views_into leaves in rgb[v]) or (H, W, 4) uint8 sRGB r, g, b, a (alpha dropped).  Level 0 and the
+        whole mip chain are rewritten in place, queued on torch's current stream like render_views_into; nothing is read back and no graph is
+        invalidated.  The tensor is read when the work runs.  Returns at once."""
+        fmt = self._texel_tensor("tensor", tensor, self.device, self._texture_shape(texture_id))      # no texture under the id: the library says so
+        self._on_torch_stream(lambda: self._chk(self.lib.rtx_update_texture(self.ctx, int(texture_id), tensor.data_ptr(), fmt), "rtx_update_texture"), (tensor,))
+
+    def read_texture(self, texture_id: int) -> sio.Texture:
+        """The descriptor and the texels (chain included, (n, 3) float32) the samplers currently read under an uploaded or allocated id
+        (waits for the stream)."""
+        desc = RtxTextureDesc()
+        self._chk(self.lib.rtx_read_texture(self.ctx, int(texture_id), C.byref(desc), None, 0), "rtx_read_texture")
+        count = max(desc.mip_offsets[l] + (desc.width >> l) * (desc.height >> l) for l in range(desc.mip_levels))
+        texels = np.zeros((count, 3), np.float32)
+        self._chk(self.lib.rtx_read_texture(self.ctx, int(texture_id), C.byref(desc), texels.ctypes.data, count), "rtx_read_texture")
+        d = np.zeros(1, sio.TEXTURE_DESC)
+        C.memmove(d.ctypes.data, C.byref(desc), C.sizeof(desc))
+        return sio.Texture(d, texels)
+
+    def update_sky(self, tensor):
+        """New texels of the uploaded sky probe from DEVICE memory: a contiguous (S, S, 3) float32 torch tensor on this context's GPU, S the
+        uploaded size.  One device-to-device copy queued on torch's current stream.  Returns at once."""
+        import torch
+        if isinstance(tensor, torch.Tensor) and (tensor.dtype != torch.float32 or tensor.dim() != 3 or tensor.shape[0] != tensor.shape[1] or tensor.shape[2] != 3):
+            raise ValueError(f"the sky must be (S, S, 3) torch.float32, not {tuple(tensor.shape)} {tensor.dtype}")
+        self._texel_tensor("tensor", tensor, self.device)
+        self._on_torch_stream(lambda: self._chk(self.lib.rtx_update_sky(self.ctx, tensor.data_ptr(), int(tensor.shape[0])), "rtx_update_sky"), (tensor,))
 
     def debug_read_layouts(self, blas_id: int = -1) -> Dict:
         """The node layouts derived from the lane layout, as the kernels read them now (rtx_debug_read_layouts; waits for the stream), as

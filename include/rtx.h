@@ -528,6 +528,55 @@ int rtx_alloc_blas(rtx_ctx * ctx, int32_t blas_id, int32_t triangle_count, int32
 int rtx_build_blas(rtx_ctx * ctx, int32_t blas_id, const void * positions_dev, const void * indices_dev, const void * normals_dev,
                    const void * texcoords_dev, void * order_out_dev);
 
+/* ---- device-side texture and sky update -----------------------------------------------------------------------------------------------
+ * What the surfaces look like, with the texels in DEVICE memory: a render shown on a screen or a portal inside the scene (a view
+ * framebuffer is [h][w][3] f32 in linear light), a decoded video frame, a generated albedo, an animated environment probe.  update -> render
+ * is a complete device-only step: the host copies nothing, filters nothing and waits for nothing.
+ *
+ * rtx_alloc_texture, once per texture, from the host; may allocate and wait.  Creates under texture_id (replacing what the id held, exactly as
+ * rtx_upload_texture does, its wait before an old texel array is released included) a texture of width x height with the shape Texture::load
+ * gives it (Texture.cpp:49-55, 76-117): with mipmapped != 0 and both sides powers of two, mip_levels = 1 + (int)log2f(min(width, height))
+ * levels, level l (width >> l) x (height >> l) texels at the cumulative offset from width * height; otherwise one level (mipmapped = 0 in
+ * the descriptor).  The whole chain is allocated and zeroed: a texture that was never updated is black and legal to render.  Uploads the
+ * texture table and, once per context, the 256-entry byte -> linear table of RTX_TEXELS_RGBA8_SRGB, computed on the host with the expression
+ * and the libm of rtxh_texture_load: the device never evaluates powf.  Checked in this order, nothing changes on an error:
+ * RTX_ERR_INVALID_ARG for an id outside [0, 4096), width < 1 or height < 1; RTX_ERR_LIMIT for a chain of more than RTX_MAX_MIP_LEVELS
+ * levels or of more texels than the int32_t offsets of rtx_texture_desc hold.
+ *
+ * rtx_update_texture, per step, from DEVICE memory: width x height texels of `format` (any address aligned to the element: 4 bytes for
+ * RTX_TEXELS_RGB_F32, 1 for RTX_TEXELS_RGBA8_SRGB).  Queued on the context's stream (rtx_set_stream: the caller's); never waits, allocates
+ * or reads back.  The buffer is read when the work runs.  Rewrites level 0 and every further level of the chain: a level is computed from
+ * the STORED fp32 texels of the level before it, (((c0 + c1) + c2) + c3) * 0.25f per channel with c0 = (2i, 2j), c1 = (2i + 1, 2j),
+ * c2 = (2i, 2j + 1), c3 = (2i + 1, 2j + 1) (Texture.cpp:99-104) — rtxh_texture_mips (rtx_host.h) builds the same bits on the host from the
+ * same code.  Any float is a legal texel (NaN, infinities, subnormals: nothing is flushed or clamped; which NaN a sum such as inf + -inf
+ * yields is the machine's).  No pointer and no descriptor field changes: a frame queued before the call samples the old texels, the next
+ * render call (any entry point, any flag) the new ones, RTX_GRAPH=1 graphs stay valid.  Checked in this order: RTX_ERR_INVALID_ARG for a null
+ * or misaligned texels_dev or an unknown format; RTX_ERR_STATE for an id that was not created by rtx_alloc_texture (or was uploaded again
+ * with rtx_upload_texture since).
+ *
+ * rtx_read_texture: what the samplers read now, of any uploaded or allocated id, to the host (waits for the stream; plain copies, nothing
+ * is launched and nothing changes, like rtx_read_blas).  *desc receives the descriptor, texels_rgb the chain as float3 in the layout
+ * rtx_upload_texture takes, from texel 0 to the end of the level that ends last: the largest mip_offsets[l] + (width >> l) * (height >> l)
+ * over the levels, which is every texel a sampler can read (for a chain laid out in level order, the end of the last level; texels a
+ * caller uploaded behind that end belong to no level and are not returned).  Either pointer may be NULL: call once with texels_rgb NULL
+ * to learn the size from the descriptor.  RTX_ERR_INVALID_ARG for a bad id, or a
+ * capacity_texels too small for a non-NULL texels_rgb; RTX_ERR_STATE for an id that holds nothing.
+ *
+ * rtx_update_sky: size x size float3 texels from DEVICE memory (4-byte aligned) over the probe rtx_upload_sky made: ONE copy on the
+ * context's stream, device to device; never waits or allocates.  The padding texel behind the probe (Sky.cpp:45's inclusive clamp) stays
+ * zero, the pointer and the size stay.  A frame queued before the call shows the old sky.  RTX_ERR_INVALID_ARG for a null or misaligned
+ * pointer; RTX_ERR_STATE before rtx_upload_sky; RTX_ERR_INVALID_ARG for a size that is not the uploaded one.
+ *
+ * Out of scope: materials from device memory (their texture ids are validated on the host before a launch; a device-side table would need
+ * a device-side check); updating a texture made by rtx_upload_texture (its chain may be the caller's own); formats other than the two
+ * below; per-view textures; the rtx_group_* path (every rank would have to make the same call); another size without a new alloc.        */
+enum { RTX_TEXELS_RGB_F32 = 0,      /* [h][w][3] float, linear light: what rtx_upload_texture takes as level 0, what a view framebuffer holds */
+       RTX_TEXELS_RGBA8_SRGB = 1 }; /* [h][w][4] uint8 r,g,b,a as stbi_load(..., STBI_rgb_alpha) returns them: colour_unpack + Math::gamma_to_linear per byte, alpha dropped */
+int rtx_alloc_texture (rtx_ctx * ctx, int32_t texture_id, int32_t width, int32_t height, int32_t mipmapped);
+int rtx_update_texture(rtx_ctx * ctx, int32_t texture_id, const void * texels_dev, int32_t format);
+int rtx_read_texture  (rtx_ctx * ctx, int32_t texture_id, rtx_texture_desc * desc, float * texels_rgb, int64_t capacity_texels);
+int rtx_update_sky    (rtx_ctx * ctx, const void * texels_dev, int32_t size);
+
 /* ---- ray queries -----------------------------------------------------------------------------------------------------------------------
  * Questions to the scene without rendering a frame: n arbitrary rays -> the closest hit of each, n segments -> whether each is blocked.
  * For sensors with non-rectangular patterns (lidar, depth), line of sight between point pairs, contact and collision probes, points sampled

@@ -167,7 +167,11 @@ int rtxh_scene_update(rtxh_tlas * tlas, int32_t instance_count, const float * po
                       int32_t * tlas_indices_out, int32_t * tlas_node_count_out);
 
 /* Appends the box-filter mip chain to level 0 (texels_rgb holds w*h float3 on entry and must have
- * room for w*h + w*h/3 + 1 texels); fills desc like Texture::load.                               */
+ * room for w*h + w*h/3 + 1 texels); fills desc like Texture::load.  The shape and the filter are
+ * the ones rtx_alloc_texture / rtx_update_texture use on the device (csrc/rtx_texmip_math.h), so
+ * the limits are theirs too: RTX_ERR_LIMIT for more than RTX_MAX_MIP_LEVELS levels and, since the
+ * two share the code, for an image of more texels than the int32_t offsets of rtx_texture_desc
+ * hold (such an image without a chain used to return RTX_OK with a 64-bit count).                */
 int rtxh_texture_mips(float * texels_rgb, int32_t width, int32_t height, rtx_texture_desc * desc, int64_t * texel_count_out);
 
 /* Texture::load (Texture.cpp:30-129): decodes a .png or .tga file the way the reference's vendored stb_image v2.19 does with
