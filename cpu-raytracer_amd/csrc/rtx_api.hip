@@ -125,6 +125,8 @@ struct rtx_ctx {
     // rtx_query_closest / rtx_query_occluded: a queue set of their own (query_queues), one chunk of query_cap slots, grown only; counters and
     // packet-queue heads of their own too, so a query never resets what rtx_get_stats has yet to read of a render call
     DevBuf d_query[4], d_query_counters, d_query_heads; int32_t query_cap = 0;
+    // RTX_QUERY_SORT: unsorted and sorted keys, the twelve bounds and rocPRIM's temporary storage, for query_sort_cap slots; nothing until the first sorted call
+    DevBuf d_query_sort; int32_t query_sort_cap = 0; size_t query_sort_tmp = 0;
     size_t slots_alloc = 0, shadow_alloc = 0;
     DevBuf d_dbg_s0, d_dbg_s1, d_stats_partial, d_pk_fifo, d_counters, d_spill, d_fb_rgb, d_fb_packed, d_display, d_gamma, d_pk_heads;
     int trace_blocks_closest = 0, trace_blocks_any = 0, trace_blocks_count = 0;
@@ -2030,7 +2032,8 @@ extern "C" int rtx_debug_group_loopback(rtx_ctx * c, int32_t world, uint32_t fla
 
 // ---- ray queries (include/rtx.h: rtx_query_closest / rtx_query_occluded; kernels in rtx_query.h) -------------------------------------
 // N rays or segments in device memory against the frame the context holds, answers into device memory: per chunk of at most
-// RTX_QUERY_CHUNK_RAYS rows  k_begin_batch -> fill -> the production traversal kernel -> resolve / store, all on the context's stream.
+// RTX_QUERY_CHUNK_RAYS rows  k_begin_batch -> fill -> the production traversal kernel -> resolve / store, all on the context's stream; with
+// RTX_QUERY_SORT the round starts with bounds -> keys -> rocPRIM's radix sort, and the fill and the resolve / store go through the sorted keys.
 // Nothing here waits, copies or allocates once the scratch holds a chunk of the call's size.
 //
 // The queue set is the queries' own.  The debug hooks below borrow the frame's: level 1 of the ray queue (which a context with
@@ -2038,16 +2041,47 @@ extern "C" int rtx_debug_group_loopback(rtx_ctx * c, int32_t world, uint32_t fla
 // alloc_queues.  Here: level 1 for rays and hits, level 0 for the node flags of the one explicit shadow segment, both at base 0 — a
 // closest-hit query touches r0 / r1 / h0 / h1, an occlusion query s0 / s1 / n0 / socc, and the two are stream-ordered, so they share four
 // buffers: 52 bytes per slot, 52 MiB for a full chunk.  DevScene and DevQueues travel by value: a frame queued before or after is untouched.
-static int query_queues(rtx_ctx * c, int64_t n, DevQueues & q) {
+//
+// RTX_QUERY_SORT (sort != null) adds a block of its own, made by the first sorted call and grown only: [unsorted keys][sorted keys][bounds]
+// [rocPRIM's temporary storage], 2 x 8 bytes per slot and what rocPRIM asks for a round of that many keys (a host-side query).  Both blocks
+// grow in the one branch that waits; a context that never sorts never allocates the second.
+struct QuerySort { uint64_t * keys_in, * keys; uint32_t * bounds; void * tmp; size_t tmp_bytes; };
+static int query_queues(rtx_ctx * c, int64_t n, DevQueues & q, QuerySort * sort = nullptr) {
     const int64_t rows = n < (int64_t)RTX_QUERY_CHUNK_RAYS ? n : (int64_t)RTX_QUERY_CHUNK_RAYS;
     const int32_t cap = (int32_t)((rows + RTX_WAVE - 1) & ~(int64_t)(RTX_WAVE - 1));      // whole packets: the fill marks the tail of the last one
-    if (cap > c->query_cap) {                              // growth: queued queries still use the old buffers
+    size_t sort_tmp = 0;
+    if (sort) {                                            // the largest round and the last one: rocPRIM picks its method by the count
+        size_t last = 0;
+        if (int rc = sort_storage_bytes<uint64_t>(c, (size_t)rows, (unsigned int)rtxq::KEY_BITS, sort_tmp)) return rc;
+        if (int rc = sort_storage_bytes<uint64_t>(c, (size_t)(n - (n - 1) / RTX_QUERY_CHUNK_RAYS * RTX_QUERY_CHUNK_RAYS), (unsigned int)rtxq::KEY_BITS, last)) return rc;
+        if (last > sort_tmp) sort_tmp = last;
+    }
+    const bool grow_sort = sort && (cap > c->query_sort_cap || sort_tmp > c->query_sort_tmp);
+    if (cap > c->query_cap || grow_sort) {                 // growth: queued queries still use the old buffers
         HIP_OK(c, hipStreamSynchronize(c->stream));
-        int rc = ensure(c, c->d_query_counters, sizeof(DevCounters));
-        if (!rc) rc = ensure(c, c->d_query_heads, (size_t)2 * (RTX_MAX_LEVELS + 1) * RTX_PK_CLASSES * 32 * sizeof(uint32_t));
-        for (int k = 0; k < 4 && !rc; k++) rc = ensure(c, c->d_query[k], (size_t)cap * (k < 3 ? 16 : 4));
-        if (rc) { c->query_cap = 0; return rc; }
-        c->query_cap = cap;
+        if (cap > c->query_cap) {
+            int rc = ensure(c, c->d_query_counters, sizeof(DevCounters));
+            if (!rc) rc = ensure(c, c->d_query_heads, (size_t)2 * (RTX_MAX_LEVELS + 1) * RTX_PK_CLASSES * 32 * sizeof(uint32_t));
+            for (int k = 0; k < 4 && !rc; k++) rc = ensure(c, c->d_query[k], (size_t)cap * (k < 3 ? 16 : 4));
+            if (rc) { c->query_cap = 0; return rc; }
+            c->query_cap = cap;
+        }
+        if (grow_sort) {
+            const int32_t scap = cap > c->query_sort_cap ? cap : c->query_sort_cap;
+            const size_t stmp = sort_tmp > c->query_sort_tmp ? sort_tmp : c->query_sort_tmp;
+            const size_t len[4] = { (size_t)scap * 8, (size_t)scap * 8, 2 * rtxq::COORDS * sizeof(uint32_t), stmp };
+            size_t off[4];
+            if (int rc = ensure(c, c->d_query_sort, aligned_parts(len, off, 4))) { c->query_sort_cap = 0; c->query_sort_tmp = 0; return rc; }
+            c->query_sort_cap = scap; c->query_sort_tmp = stmp;
+        }
+    }
+    if (sort) {
+        const size_t len[4] = { (size_t)c->query_sort_cap * 8, (size_t)c->query_sort_cap * 8, 2 * rtxq::COORDS * sizeof(uint32_t), c->query_sort_tmp };
+        size_t off[4];
+        aligned_parts(len, off, 4);
+        char * const sb = (char *)c->d_query_sort.p;
+        sort->keys_in = (uint64_t *)(sb + off[0]); sort->keys = (uint64_t *)(sb + off[1]); sort->bounds = (uint32_t *)(sb + off[2]);
+        sort->tmp = sb + off[3]; sort->tmp_bytes = c->query_sort_tmp;
     }
     q = c->q;                                              // the walkers' knobs (thresholds, spill_threads) as rtx_create read them
     for (int d = 0; d <= RTX_MAX_LEVELS; d++) { q.level_base[d] = 0; q.level_cap[d] = d < 2 ? c->query_cap : 0; q.shadow_base[d] = 0; q.stats_n[d] = 0; }
@@ -2064,11 +2098,24 @@ static int query_queues(rtx_ctx * c, int64_t n, DevQueues & q) {
     return RTX_OK;
 }
 
+// RTX_QUERY_SORT, one round: the bounds of the m rows at `rows` (ROW floats each), their keys, rocPRIM's radix sort -> S.keys, the order
+// the fill gathers by and the resolve scatters by.  Three launches and a 48-byte memset on the stream; the host learns nothing.
+template <int ROW> static int query_sort_round(rtx_ctx * c, const QuerySort & S, const float * rows, int m) {
+    const dim3 grid((m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK), block(RTX_QUERY_BLOCK);
+    HIP_OK(c, hipMemsetAsync(S.bounds, 0xff, 2 * rtxq::COORDS * sizeof(uint32_t), c->stream));
+    launch_timed(c, "k_query_sort_bounds", c->stream, [&] { hipLaunchKernelGGL((k_query_sort_bounds<ROW>), grid, block, 0, c->stream, rows, m, S.bounds); });
+    launch_timed(c, "k_query_sort_keys", c->stream, [&] { hipLaunchKernelGGL((k_query_sort_keys<ROW>), grid, block, 0, c->stream, rows, m, (const uint32_t *)S.bounds, S.keys_in); });
+    hipError_t se = hipSuccess;
+    launch_timed(c, "query_radix_sort", c->stream, [&] { size_t bytes = S.tmp_bytes; se = rocprim::radix_sort_keys(S.tmp, bytes, (const uint64_t *)S.keys_in, S.keys, (unsigned int)m, 0u, (unsigned int)rtxq::KEY_BITS, c->stream); });
+    if (se != hipSuccess) return sort_failed(c, se);
+    return RTX_OK;
+}
+
 // the checks both calls share, in the order the header lists them; nothing is queued on an error
 static int query_checks(rtx_ctx * c, const void * in, int64_t n, const void * out, uint32_t flags, const char * what) {
     if (!c) return RTX_ERR_INVALID_ARG;
     if (!in || !out || n < 1) { c->err = std::string(what) + ": null pointer or n < 1"; return RTX_ERR_INVALID_ARG; }
-    if (flags & ~(uint32_t)(RTX_RENDER_LANE_TRACE | RTX_RENDER_PACKET_CLOSEST)) { c->err = std::string(what) + ": flags other than RTX_RENDER_LANE_TRACE / RTX_RENDER_PACKET_CLOSEST"; return RTX_ERR_INVALID_ARG; }
+    if (flags & ~(uint32_t)(RTX_RENDER_LANE_TRACE | RTX_RENDER_PACKET_CLOSEST | RTX_QUERY_SORT)) { c->err = std::string(what) + ": flags other than RTX_RENDER_LANE_TRACE / RTX_RENDER_PACKET_CLOSEST / RTX_QUERY_SORT"; return RTX_ERR_INVALID_ARG; }
     if (!c->frame_set) { c->err = std::string(what) + " before rtx_set_frame"; return RTX_ERR_STATE; }
     if (c->scene.heatmap) { c->err = std::string(what) + " in heat-map mode"; return RTX_ERR_STATE; }
     return validate_references(c);
@@ -2079,7 +2126,10 @@ extern "C" int rtx_query_closest(rtx_ctx * c, const void * rays_dev, int64_t n, 
     if (int bad = query_checks(c, rays_dev, n, out, flags, "rtx_query_closest")) return bad;
     hipSetDevice(c->cfg.device);
     DevQueues q;
-    if (int rc = query_queues(c, n, q)) return rc;
+    QuerySort S;
+    const bool sorted = (flags & RTX_QUERY_SORT) != 0;
+    if (int rc = query_queues(c, n, q, sorted ? &S : nullptr)) return rc;
+    const uint64_t * const order = sorted ? S.keys : nullptr;
     bool lane = (flags & RTX_RENDER_LANE_TRACE) != 0, pk_closest = (flags & RTX_RENDER_PACKET_CLOSEST) != 0;
     plan_stack_limits(stack_figures(c), lane, pk_closest);
     if (pk_closest) q.pk_defer_t0_closest = q.pk_defer_t0_primary = q.pk_defer_t0;
@@ -2098,10 +2148,11 @@ extern "C" int rtx_query_closest(rtx_ctx * c, const void * rays_dev, int64_t n, 
         t.material_id = on(RTX_QUERY_MATERIAL_ID) && out->material_id ? out->material_id + first : nullptr;
         t.object_id = on(RTX_QUERY_OBJECT_ID) && out->object_id ? out->object_id + first : nullptr;
         t.triangle_id = on(RTX_QUERY_TRIANGLE_ID) && out->triangle_id ? out->triangle_id + first : nullptr;
+        if (sorted) if (int rc = query_sort_round<6>(c, S, (const float *)rays_dev + 6 * first, m)) return rc;
         begin_batch(c, q.counters, q.pk_heads, 0u, false, true);
-        launch_timed(c, "k_query_fill", c->stream, [&] { hipLaunchKernelGGL(k_query_fill, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, q, (const float *)rays_dev + 6 * first, m); });
+        launch_timed(c, "k_query_fill", c->stream, [&] { hipLaunchKernelGGL(k_query_fill, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, q, (const float *)rays_dev + 6 * first, m, order); });
         launch_timed(c, "k_trace_closest", c->stream, [&] { launch_closest_level1(c, sc, q, lane); });
-        launch_timed(c, "k_query_resolve", c->stream, [&] { hipLaunchKernelGGL(k_query_resolve, dim3((m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc_resolve, q, m, t); });
+        launch_timed(c, "k_query_resolve", c->stream, [&] { hipLaunchKernelGGL(k_query_resolve, dim3((m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc_resolve, q, m, t, order); });
     }
     HIP_OK(c, hipGetLastError());
     return RTX_OK;
@@ -2111,7 +2162,10 @@ extern "C" int rtx_query_occluded(rtx_ctx * c, const void * segments_dev, int64_
     if (int bad = query_checks(c, segments_dev, n, occluded_dev, flags, "rtx_query_occluded")) return bad;
     hipSetDevice(c->cfg.device);
     DevQueues q;
-    if (int rc = query_queues(c, n, q)) return rc;
+    QuerySort S;
+    const bool sorted = (flags & RTX_QUERY_SORT) != 0;
+    if (int rc = query_queues(c, n, q, sorted ? &S : nullptr)) return rc;
+    const uint64_t * const order = sorted ? S.keys : nullptr;
     q.shadow_explicit = 1;
     bool lane = (flags & RTX_RENDER_LANE_TRACE) != 0, pk_closest = false;
     plan_stack_limits(stack_figures(c), lane, pk_closest);
@@ -2120,10 +2174,31 @@ extern "C" int rtx_query_occluded(rtx_ctx * c, const void * segments_dev, int64_
         const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
         const int blocks = (((m + RTX_WAVE - 1) & ~(RTX_WAVE - 1)) + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK;
         q.tile_count = (m + 1023) / 1024;
+        if (sorted) if (int rc = query_sort_round<7>(c, S, (const float *)segments_dev + 7 * first, m)) return rc;
         begin_batch(c, q.counters, q.pk_heads, 0u, false, true);
-        launch_timed(c, "k_query_fill_segments", c->stream, [&] { hipLaunchKernelGGL(k_query_fill_segments, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, q, (const float *)segments_dev + 7 * first, m); });
+        launch_timed(c, "k_query_fill_segments", c->stream, [&] { hipLaunchKernelGGL(k_query_fill_segments, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, q, (const float *)segments_dev + 7 * first, m, order); });
         launch_timed(c, "k_trace_any", c->stream, [&] { launch_any_level0(c, sc, q, lane); });
-        launch_timed(c, "k_query_store_occluded", c->stream, [&] { hipLaunchKernelGGL(k_query_store_occluded, dim3((m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK), dim3(RTX_QUERY_BLOCK), 0, c->stream, q, m, occluded_dev + first); });
+        launch_timed(c, "k_query_store_occluded", c->stream, [&] { hipLaunchKernelGGL(k_query_store_occluded, dim3((m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK), dim3(RTX_QUERY_BLOCK), 0, c->stream, q, m, occluded_dev + first, order); });
+    }
+    HIP_OK(c, hipGetLastError());
+    return RTX_OK;
+}
+
+// the order RTX_QUERY_SORT traces n rows of row_floats (6: rays, 7: segments) floats in: the bounds, key and sort launches of every round and
+// nothing else, order_out[first + i] = first + the row of slot i of the round that starts at `first`.  Queued like the queries; their checks.
+extern "C" int rtx_debug_query_order(rtx_ctx * c, const void * rows_dev, int32_t row_floats, int64_t n, int32_t * order_out_dev) {
+    if (int bad = query_checks(c, rows_dev, n, order_out_dev, 0u, "rtx_debug_query_order")) return bad;
+    if (row_floats != 6 && row_floats != 7) { c->err = "rtx_debug_query_order: row_floats must be 6 or 7"; return RTX_ERR_INVALID_ARG; }
+    if (n > (int64_t)INT32_MAX) { c->err = "rtx_debug_query_order: more rows than an int32_t order holds"; return RTX_ERR_LIMIT; }
+    hipSetDevice(c->cfg.device);
+    DevQueues q;
+    QuerySort S;
+    if (int rc = query_queues(c, n, q, &S)) return rc;
+    for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
+        const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
+        const float * const rows = (const float *)rows_dev + (size_t)row_floats * first;
+        if (int rc = row_floats == 6 ? query_sort_round<6>(c, S, rows, m) : query_sort_round<7>(c, S, rows, m)) return rc;
+        launch_timed(c, "k_query_sort_order", c->stream, [&] { hipLaunchKernelGGL(k_query_sort_order, dim3((m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK), dim3(RTX_QUERY_BLOCK), 0, c->stream, (const uint64_t *)S.keys, m, (int32_t)first, order_out_dev + first); });
     }
     HIP_OK(c, hipGetLastError());
     return RTX_OK;

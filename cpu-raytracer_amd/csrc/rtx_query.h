@@ -5,6 +5,9 @@
 //   k_query_fill_segments   n x 7 floats (origin, direction, max distance) -> ONE explicit shadow segment of level 0 (q.shadow_explicit)
 //   k_query_store_occluded  that segment's occlusion flags                 -> int32 1 / 0
 //
+//   k_query_sort_bounds     RTX_QUERY_SORT: the rows of a round -> the twelve bounds of their six key coordinates (rtx_query_sort_math.h)
+//   k_query_sort_keys       the rows and those bounds -> one 64-bit key per row; rocPRIM's radix sort of the keys runs between this and the fill
+//
 // The walk in between is the production kernel of the render path, launched as a frame launches it (rtx_api.hip): a closest-hit launch over
 // level 1, a shadow-ray launch over level 0.  All four kernels stream: one slot per lane, a chunk (<= RTX_QUERY_CHUNK_RAYS rows) per launch.
 //
@@ -18,6 +21,7 @@
 // themselves and keeps the 0 the fill stored.
 #pragma once
 #include "rtx_device.h"
+#include "rtx_query_sort_math.h"
 
 #define RTX_QUERY_BLOCK 256
 
@@ -43,13 +47,66 @@ RTX_D bool query_row_is_ray(const v3 o, const v3 d) {
     return !((d.x == 0.0f) & (d.y == 0.0f) & (d.z == 0.0f)) && ray_is_finite(o, d);
 }
 
+// RTX_QUERY_SORT.  `order` is the round's sorted keys (rtxq::sort_key): slot i traces caller row rtxq::key_row(order[i]), and the answer of
+// slot i goes back to that row.  A null order is the caller's order, slot i = row i, through the staging above.
+// The row of slot i with an order: ROW dword loads at the row's own address (any 4-byte aligned address: no wider load is legal).  Slots at
+// and beyond m read as zeros, as in query_load_row.
+template <int ROW>
+RTX_D void query_gather_row(const uint64_t * __restrict__ order, const float * __restrict__ rows, const int m, const int i, float (&row)[ROW]) {
+    const uint32_t at = i < m ? rtxq::key_row(order[i]) : (uint32_t)m;      // < m for every key the key kernel wrote: nothing else is ever read
+    if (at < (uint32_t)m) {
+        const float * const src = rows + (size_t)at * ROW;
+        for (int k = 0; k < ROW; k++) row[k] = src[k];
+    } else for (int k = 0; k < ROW; k++) row[k] = 0.0f;
+}
+
+// The twelve bounds of a round's live rows, bounds[0..5] the minima as ordered keys, bounds[6..11] the maxima as complemented ordered keys:
+// both reduce by an unsigned min, one memset of 0xff per round initialises them (upd_reduce_bounds, rtx_update.h, does the same for six).
+// wave64 min, then at most one atomic per wave and bound: a wave that cannot lower the bound it reads does not issue one.  Measured
+// (DESIGN.md 9): 170 - 270 us per 2^20 rows all the same — as a sweep over an image proceeds most waves still improve a bound, and twelve
+// words of one cache line sustain few atomics and loads per microsecond.  A reduction per workgroup over several tiles is the next step.
+template <int ROW>
+__global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_sort_bounds(const float * __restrict__ rows, const int m, uint32_t * __restrict__ bounds) {
+    __shared__ float lds[ROW * RTX_QUERY_BLOCK];
+    float r[ROW];
+    query_load_row<ROW>(lds, rows, m, r);
+    const int i = blockIdx.x * RTX_QUERY_BLOCK + threadIdx.x;
+    uint32_t k12[2 * rtxq::COORDS];
+    for (int a = 0; a < 2 * rtxq::COORDS; a++) k12[a] = 0xffffffffu;
+    if (i < m && rtxq::row_is_live(r, ROW)) { float x[rtxq::COORDS]; rtxq::coordinates(r, x); rtxq::bounds_of_row(x, k12); }
+    for (int a = 0; a < 2 * rtxq::COORDS; a++) {
+        uint32_t v = k12[a];
+        for (int o = 32; o > 0; o >>= 1) { const uint32_t w = (uint32_t)__shfl_xor((int)v, o, 64); v = w < v ? w : v; }
+        if ((threadIdx.x & 63) == 0 && v < __hip_atomic_load(&bounds[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&bounds[a], v);
+    }
+}
+
+// keys[i] = rtxq::sort_key of row i.  The bounds are the same twelve words for every lane: scalar loads, one plan per wave.
+template <int ROW>
+__global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_sort_keys(const float * __restrict__ rows, const int m, const uint32_t * __restrict__ bounds, uint64_t * __restrict__ keys) {
+    __shared__ float lds[ROW * RTX_QUERY_BLOCK];
+    float r[ROW];
+    query_load_row<ROW>(lds, rows, m, r);
+    const int i = blockIdx.x * RTX_QUERY_BLOCK + threadIdx.x;
+    if (i >= m) return;
+    const rtxq::Plan plan = rtxq::make_plan(bounds);
+    keys[i] = rtxq::sort_key(plan, r, ROW, (uint32_t)i);
+}
+
+// the caller row of every slot of a sorted round, for rtx_debug_query_order: order_out[i] = first + row
+__global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_sort_order(const uint64_t * __restrict__ order, const int m, const int32_t first, int32_t * __restrict__ order_out) {
+    const int i = blockIdx.x * RTX_QUERY_BLOCK + threadIdx.x;
+    if (i < m) order_out[i] = first + (int32_t)rtxq::key_row(order[i]);
+}
+
 // slots [0, m rounded up to a packet) of level 1: the chunk's rays with zero differentials (r2 .. r4 are neither written nor read: the
-// traversal kernels take origin and direction, k_query_resolve knows the differentials are zero), pixel = the row, parent -1
-__global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_fill(const DevQueues q, const float * __restrict__ rays6, const int m) {
+// traversal kernels take origin and direction, k_query_resolve knows the differentials are zero), pixel = the slot, parent -1
+__global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_fill(const DevQueues q, const float * __restrict__ rays6, const int m, const uint64_t * __restrict__ order) {
     __shared__ float lds[6 * RTX_QUERY_BLOCK];
     float r[6];
-    query_load_row<6>(lds, rays6, m, r);
     const int i = blockIdx.x * RTX_QUERY_BLOCK + threadIdx.x;
+    if (order) query_gather_row<6>(order, rays6, m, i, r);      // a kernel argument: the same branch for every lane
+    else query_load_row<6>(lds, rays6, m, r);
     if (i == 0) q.counters->ray_count[1] = (uint32_t)m;
     if (i >= ((m + RTX_WAVE - 1) & ~(RTX_WAVE - 1))) return;
     const bool live = i < m && query_row_is_ray(V3(r[0], r[1], r[2]), V3(r[3], r[4], r[5]));
@@ -62,7 +119,7 @@ __global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_fill(const DevQueues 
 // primitive.  Position, normal and uv are RayHit fields the accept branches compute: the rebuild functions of the shading pass
 // (rtx_shade.h), entered only when one of the three is requested — a branch on kernel arguments, the same for every lane.
 // sc.diff_enabled is 0 here (the caller clears it in its copy): the rebuild's differential block feeds none of the channels.
-__global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_resolve(const DevScene sc, const DevQueues q, const int m, const DevQuery out) {
+__global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_resolve(const DevScene sc, const DevQueues q, const int m, const DevQuery out, const uint64_t * __restrict__ order) {
     const int i = blockIdx.x * RTX_QUERY_BLOCK + threadIdx.x;
     if (i >= m) return;
     const uint32_t s = (uint32_t)q.level_base[1] + (uint32_t)i;
@@ -88,7 +145,8 @@ __global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_resolve(const DevScen
             h.material_id = B.material_offset + B.tri_cold[tri].material_id;
         } else h.material_id = kind == PRIM_SPHERE ? sc.spheres[pi].material_id : sc.planes[pi].material_id;
     }
-    const size_t p = (size_t)i;
+    const size_t p = order ? (size_t)rtxq::key_row(order[i]) : (size_t)i;      // the caller's row of this slot
+    if (p >= (size_t)m) return;                                                // never: a sorted key holds a row of the round
     if (out.distance) out.distance[p] = is_hit ? h0.x : INFINITY;
     if (out.position) { out.position[3 * p + 0] = h.point.x; out.position[3 * p + 1] = h.point.y; out.position[3 * p + 2] = h.point.z; }
     if (out.normal) { out.normal[3 * p + 0] = h.normal.x; out.normal[3 * p + 1] = h.normal.y; out.normal[3 * p + 2] = h.normal.z; }
@@ -101,11 +159,12 @@ __global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_resolve(const DevScen
 
 // slots [0, m rounded up to a packet) of level 0 and of its one shadow segment (the caller's DevScene copy says light_count = 1, whatever
 // the frame holds): the node record only says whether the slot carries a segment (NF_LIT, shadow_slot_is_lit), the flag starts at 0
-__global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_fill_segments(const DevQueues q, const float * __restrict__ segments7, const int m) {
+__global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_fill_segments(const DevQueues q, const float * __restrict__ segments7, const int m, const uint64_t * __restrict__ order) {
     __shared__ float lds[7 * RTX_QUERY_BLOCK];
     float r[7];
-    query_load_row<7>(lds, segments7, m, r);
     const int i = blockIdx.x * RTX_QUERY_BLOCK + threadIdx.x;
+    if (order) query_gather_row<7>(order, segments7, m, i, r);
+    else query_load_row<7>(lds, segments7, m, r);
     if (i == 0) q.counters->ray_count[0] = (uint32_t)m;
     if (i >= ((m + RTX_WAVE - 1) & ~(RTX_WAVE - 1))) return;
     const bool live = i < m && query_row_is_ray(V3(r[0], r[1], r[2]), V3(r[3], r[4], r[5])) && r[6] == r[6];
@@ -116,8 +175,9 @@ __global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_fill_segments(const D
     q.socc[s] = 0u;
 }
 
-__global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_store_occluded(const DevQueues q, const int m, int32_t * __restrict__ occluded) {
+__global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_store_occluded(const DevQueues q, const int m, int32_t * __restrict__ occluded, const uint64_t * __restrict__ order) {
     const int i = blockIdx.x * RTX_QUERY_BLOCK + threadIdx.x;
     if (i >= m) return;
-    occluded[i] = q.socc[(uint32_t)q.shadow_base[0] + (uint32_t)i] != 0u ? 1 : 0;
+    const uint32_t p = order ? rtxq::key_row(order[i]) : (uint32_t)i;
+    if (p < (uint32_t)m) occluded[p] = q.socc[(uint32_t)q.shadow_base[0] + (uint32_t)i] != 0u ? 1 : 0;
 }

@@ -9,6 +9,7 @@
 #include "../csrc/rtx_refit_math.h"
 #include "../csrc/rtx_build_math.h"
 #include "../csrc/rtx_texmip_math.h"
+#include "../csrc/rtx_query_sort_math.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -560,6 +561,34 @@ extern "C" int rtxh_texture_mips(float * tx, int32_t width, int32_t height, rtx_
         }
     }
     if (texel_count_out) *texel_count_out = count;
+    return RTX_OK;
+}
+
+// =================================================================================================
+// RTX_QUERY_SORT on the host: the round structure of rtx_query_closest / rtx_query_occluded, the bounds as the twelve min-reduced words
+// k_query_sort_bounds leaves, the keys of rtx_query_sort_math.h, a sort of the 64-bit keys (a total order: any sort gives this result)
+extern "C" int rtxh_query_sort_order(const float * rows, int32_t row_floats, int64_t n, int32_t * order_out) {
+    if (!rows || !order_out || n < 1 || (row_floats != 6 && row_floats != 7)) return RTX_ERR_INVALID_ARG;
+    if (n > (int64_t)INT32_MAX) return RTX_ERR_LIMIT;
+    std::vector<uint64_t> keys;
+    for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
+        const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
+        const float * const r = rows + (size_t)row_floats * first;
+        uint32_t bounds[2 * rtxq::COORDS];
+        for (uint32_t & b : bounds) b = 0xffffffffu;
+        for (int i = 0; i < m; i++) {
+            if (!rtxq::row_is_live(r + (size_t)row_floats * i, row_floats)) continue;
+            float x[rtxq::COORDS]; uint32_t k12[2 * rtxq::COORDS];
+            rtxq::coordinates(r + (size_t)row_floats * i, x);
+            rtxq::bounds_of_row(x, k12);
+            for (int a = 0; a < 2 * rtxq::COORDS; a++) if (k12[a] < bounds[a]) bounds[a] = k12[a];
+        }
+        const rtxq::Plan plan = rtxq::make_plan(bounds);
+        keys.resize((size_t)m);
+        for (int i = 0; i < m; i++) keys[i] = rtxq::sort_key(plan, r + (size_t)row_floats * i, row_floats, (uint32_t)i);
+        std::sort(keys.begin(), keys.end());
+        for (int i = 0; i < m; i++) order_out[first + i] = (int32_t)first + (int32_t)rtxq::key_row(keys[i]);
+    }
     return RTX_OK;
 }
 

@@ -26,7 +26,7 @@ EXPORTS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error", "rt
            "rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer", "rtx_bind_aovs", "rtx_read_aovs",
            "rtx_set_rays", "rtx_bind_rays", "rtx_render_rays", "rtx_update_instances", "rtx_read_frame_state",
            "rtx_bind_blas_vertices", "rtx_refit_blas", "rtx_read_blas", "rtx_alloc_blas", "rtx_build_blas",
-           "rtx_query_closest", "rtx_query_occluded", "rtx_debug_read_layouts",
+           "rtx_query_closest", "rtx_query_occluded", "rtx_debug_query_order", "rtx_debug_read_layouts",
            "rtx_alloc_texture", "rtx_update_texture", "rtx_read_texture", "rtx_update_sky"]
 # newer than the A/B variants tools/ab.py may load (RTX_HIP_LIB = a library built from an older commit): bound when the library has them,
 # otherwise a call raises AttributeError (undefined symbol)
@@ -37,6 +37,7 @@ UPDATE_EXPORTS = ("rtx_update_instances", "rtx_read_frame_state")
 REFIT_EXPORTS = ("rtx_bind_blas_vertices", "rtx_refit_blas", "rtx_read_blas")
 BUILD_EXPORTS = ("rtx_alloc_blas", "rtx_build_blas")
 QUERY_EXPORTS = ("rtx_query_closest", "rtx_query_occluded")
+QUERY_SORT_EXPORTS = ("rtx_debug_query_order",)
 LAYOUT_EXPORTS = ("rtx_debug_read_layouts",)
 TEXTURE_EXPORTS = ("rtx_alloc_texture", "rtx_update_texture", "rtx_read_texture", "rtx_update_sky")
 # texel formats of rtx_update_texture (include/rtx.h RTX_TEXELS_*)
@@ -63,6 +64,7 @@ RTX_QUERY_OBJECT_ID = 64
 RTX_QUERY_TRIANGLE_ID = 128
 RTX_QUERY_ALL = 247
 RTX_QUERY_CHUNK_RAYS = 1 << 20
+RTX_QUERY_SORT = 256        # a bit of the query calls' flags: sort the rays of every round into coherent packets on the device
 # name -> (bit, numpy dtype, components per ray), in rtx_query_buffers order
 QUERY_CHANNELS = {"distance": (RTX_QUERY_DISTANCE, np.float32, 1), "position": (RTX_QUERY_POSITION, np.float32, 3),
                   "normal": (RTX_QUERY_NORMAL, np.float32, 3), "uv": (RTX_QUERY_UV, np.float32, 2),
@@ -158,6 +160,8 @@ def load_library(path: Optional[str] = None):
     if hasattr(lib, "rtx_query_closest"):
         lib.rtx_query_closest.argtypes = [vp, vp, C.c_int64, u32, C.POINTER(RtxQueryBuffers), u32]
         lib.rtx_query_occluded.argtypes = [vp, vp, C.c_int64, vp, u32]
+    if hasattr(lib, "rtx_debug_query_order"):
+        lib.rtx_debug_query_order.argtypes = [vp, vp, i32, C.c_int64, vp]
     if hasattr(lib, "rtx_debug_read_layouts"):
         lib.rtx_debug_read_layouts.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(lib, "rtx_update_texture"):
@@ -166,7 +170,7 @@ def load_library(path: Optional[str] = None):
         lib.rtx_read_texture.argtypes = [vp, i32, C.POINTER(RtxTextureDesc), vp, C.c_int64]
         lib.rtx_update_sky.argtypes = [vp, vp, i32]
     for name in EXPORTS:
-        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + LAYOUT_EXPORTS + TEXTURE_EXPORTS and not hasattr(lib, name):
+        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + QUERY_SORT_EXPORTS + LAYOUT_EXPORTS + TEXTURE_EXPORTS and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         if name not in ("rtx_last_error",):
@@ -983,13 +987,14 @@ class Renderer:
             if t.device.type != "cuda" or t.device.index != self.device:
                 raise ValueError(f"{name} must be on cuda:{self.device} (this context's GPU), not {t.device}")
 
-    def query_closest(self, rays, channels=("distance",), out: Optional[Dict] = None, n: Optional[int] = None, **flags) -> Dict:
+    def query_closest(self, rays, channels=("distance",), out: Optional[Dict] = None, n: Optional[int] = None, sort: bool = False, **flags) -> Dict:
         """The closest hit of n arbitrary rays against the frame the context holds (rtx_query_closest): rays = float32 torch tensor (n, 6)
         of (origin, direction) on this context's GPU; channels = names out of distance, position, normal, uv, material_id, object_id,
         triangle_id (or a RTX_QUERY_* mask).  Returns {name: tensor}: float32 / int32, (n,), (n, 3) or (n, 2), allocated on the device unless
         out = {name: tensor} supplies them.  A miss: distance inf, ids -1, the rest 0; a zero direction is no ray and a miss.  Queued on
         torch's current stream like render_views_into: torch work queued after the call sees the answers, nothing is read back.  flags:
-        lane_trace / packet_closest.  Raw device pointers: rays = address, n = rays, out = {name: address} for every channel wanted (then the
+        lane_trace / packet_closest.  sort=True (RTX_QUERY_SORT): the library sorts the rays of every round into coherent packets on the
+        device and scatters the answers back; the same answers, row for row.  Raw device pointers: rays = address, n = rays, out = {name: address} for every channel wanted (then the
         work goes to the stream set with set_stream).  Everything is checked before the library is reached.  Returns at once."""
         names = query_names(channels)
         ptr, n, rays_t = self._query_rows("rays", rays, 6, n)
@@ -1006,6 +1011,8 @@ class Renderer:
         fl = render_flags(**flags)
         if fl & ~(RTX_RENDER_LANE_TRACE | RTX_RENDER_PACKET_CLOSEST):
             raise ValueError("a query takes the flags lane_trace and packet_closest only")
+        if sort:
+            fl |= RTX_QUERY_SORT
         buf = RtxQueryBuffers()
         for name in out:
             _, dt, k = QUERY_CHANNELS[name]
@@ -1028,7 +1035,7 @@ class Renderer:
             launch()
         return {name: out[name] for name in names}
 
-    def query_occluded(self, segments, out=None, n: Optional[int] = None, **flags):
+    def query_occluded(self, segments, out=None, n: Optional[int] = None, sort: bool = False, **flags):
         """Whether each of n segments is blocked (rtx_query_occluded): segments = float32 torch tensor (n, 7) of (origin, direction, max
         distance) on this context's GPU; returns the int32 tensor (n,) of 1 / 0 (out, or a new one): 1 = something is hit at a distance
         strictly below the maximum.  Queued, checked and flagged like query_closest; raw device pointers: segments = address, n, out = address."""
@@ -1037,6 +1044,8 @@ class Renderer:
         fl = render_flags(**flags)
         if fl & ~(RTX_RENDER_LANE_TRACE | RTX_RENDER_PACKET_CLOSEST):
             raise ValueError("a query takes the flags lane_trace and packet_closest only")
+        if sort:
+            fl |= RTX_QUERY_SORT
         if out is None and raw:
             raise ValueError("with raw device pointers out must be the address of the result")
         optr = None if out is None else self._query_out("occluded", out, np.int32, n, 1, raw)
@@ -1053,6 +1062,24 @@ class Renderer:
             self._on_torch_stream(launch, tensors)
         else:
             launch()
+        return out
+
+    def debug_query_order(self, rows, n: Optional[int] = None):
+        """The order sort=True traces the rows in (rtx_debug_query_order): rows = float32 torch tensor (n, 6) of rays or (n, 7) of segments on
+        this context's GPU; returns the int32 tensor (n,): element first + i = the row traced in slot i of the round that starts at row
+        `first`.  Nothing is traced.  Queued on torch's current stream like the queries."""
+        import torch
+        width = rows.shape[1] if isinstance(rows, torch.Tensor) and rows.dim() == 2 else 0
+        if width not in (6, 7):
+            raise ValueError(f"rows must have shape (n, 6) or (n, 7), not {tuple(rows.shape) if isinstance(rows, torch.Tensor) else type(rows).__name__}")
+        ptr, n, rows_t = self._query_rows("rows", rows, width, n)
+        self._query_on_device({"rows": rows_t})
+        out = torch.empty((n,), dtype=torch.int32, device=rows_t.device)
+        optr = out.data_ptr()
+
+        def launch():
+            self._chk(self.lib.rtx_debug_query_order(self.ctx, ptr, width, n, optr), "rtx_debug_query_order")
+        self._on_torch_stream(launch, [rows_t, out])
         return out
 
     def enable_timing(self, on: bool = True):

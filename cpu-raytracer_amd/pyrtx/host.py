@@ -19,7 +19,7 @@ from .ctypes_structs import RtxCamera, RtxTextureDesc
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "..", "host", "librtx_host.so")
 EXPORTS = ["rtxh_camera_basis", "rtxh_camera_update", "rtxh_quaternion_axis_angle", "rtxh_scene_dynamic_animate", "rtxh_scene_update", "rtxh_instance_update", "rtxh_plane_update", "rtxh_tlas_create", "rtxh_tlas_destroy",
-           "rtxh_tlas_build", "rtxh_blas_build", "rtxh_blas_build_reference_bvh", "rtxh_blas_build_reference_sbvh", "rtxh_texture_mips", "rtxh_texture_load", "rtxh_texture_free", "rtxh_sky_load", "rtxh_image_load", "rtxh_image_free", "rtxh_image_save_png", "rtxh_atrium_generate", "rtxh_mesh_free",
+           "rtxh_tlas_build", "rtxh_blas_build", "rtxh_blas_build_reference_bvh", "rtxh_blas_build_reference_sbvh", "rtxh_texture_mips", "rtxh_query_sort_order", "rtxh_texture_load", "rtxh_texture_free", "rtxh_sky_load", "rtxh_image_load", "rtxh_image_free", "rtxh_image_save_png", "rtxh_atrium_generate", "rtxh_mesh_free",
            "rtxh_obj_load", "rtxh_obj_free", "rtxh_mtl_load", "rtxh_bvh_cache_load", "rtxh_bvh_cache_save", "rtxh_bvh_cache_free",
            "rtxh_tlas_build_balanced", "rtxh_scene_update_balanced", "rtxh_tlas_balanced_node_count", "rtxh_tlas_balanced_inner_depth", "rtxh_blas_refit",
            "rtxh_blas_build_balanced", "rtxh_blas_balanced_node_count", "rtxh_blas_balanced_inner_depth"]
@@ -79,6 +79,7 @@ def lib():
         l.rtxh_bvh_cache_save.argtypes = [C.c_char_p, C.POINTER(RtxhBvhCache)]
         l.rtxh_bvh_cache_free.argtypes = [C.POINTER(RtxhBvhCache)]
         l.rtxh_texture_mips.argtypes = [vp, i32, i32, C.POINTER(RtxTextureDesc), C.POINTER(C.c_int64)]
+        l.rtxh_query_sort_order.argtypes = [vp, i32, C.c_int64, vp]
         l.rtxh_atrium_generate.argtypes = [C.c_uint32, i32, C.POINTER(RtxhMesh)]
         l.rtxh_mesh_free.argtypes = [C.POINTER(RtxhMesh)]
         l.rtxh_tlas_build_balanced.argtypes = [i32, vp, vp, vp, vp, C.POINTER(i32)]
@@ -415,6 +416,23 @@ def save_bvh_cache(path: str, blas: sio.Blas) -> None:
         f.write(np.int32(n).tobytes()); f.write(np.ascontiguousarray(blas.tri_hot).tobytes()); f.write(np.ascontiguousarray(blas.tri_cold).tobytes())
         f.write(np.int32(len(blas.nodes)).tobytes()); f.write(np.ascontiguousarray(blas.nodes).tobytes())
         f.write(np.int32(n).tobytes()); f.write(np.arange(n, dtype=np.int32).tobytes())
+
+
+def query_sort_order(rows: np.ndarray) -> np.ndarray:
+    """The order Renderer.query_closest / query_occluded trace rows in with sort=True (rtxh_query_sort_order, the code of
+    csrc/rtx_query_sort_math.h on the host): rows (n, 6) rays or (n, 7) segments, float32 -> int32 (n,), element first + i = the row in
+    slot i of the round that starts at row `first`."""
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.shape[1] not in (6, 7) or rows.shape[0] < 1:
+        raise ValueError(f"rows must have shape (n, 6) or (n, 7) with n >= 1, not {rows.shape}")
+    if rows.dtype != np.float32:
+        raise TypeError(f"rows must be float32, not {rows.dtype}")
+    rows = np.ascontiguousarray(rows)
+    order = np.empty(rows.shape[0], np.int32)
+    rc = lib().rtxh_query_sort_order(rows.ctypes.data, rows.shape[1], rows.shape[0], order.ctypes.data)
+    if rc:
+        raise RuntimeError(f"rtxh_query_sort_order failed: {rc}")
+    return order
 
 
 def texture_with_mips(level0_rgb: np.ndarray) -> sio.Texture:

@@ -617,14 +617,26 @@ int rtx_update_sky    (rtx_ctx * ctx, const void * texels_dev, int32_t size);
  * flags: RTX_RENDER_LANE_TRACE / RTX_RENDER_PACKET_CLOSEST choose the kernel as for a render call (the answers are bit-identical);
  * scenes whose trees exceed the packet kernels' limits take the per-lane kernels as in a render call.  A packet is 64 consecutive rays:
  * rays that travel together are cheapest next to each other.
+ * RTX_QUERY_SORT (with either of the two, or alone): the library puts the rays of every round into a coherent order itself, on the device,
+ * and hands the answers back in the caller's order — for callers who do not choose their row order (lidar beams in firing order, point
+ * pairs, contact probes, surface samples).  Per round: the bounds of the rows, a 64-bit key per row (csrc/rtx_query_sort_math.h: a Morton code
+ * over the origin and the direction's point on the unit cube, quantised between the round's bounds; rtxh_query_sort_order in rtx_host.h
+ * is the same code on the host), rocPRIM's radix sort, the fill gathering rows in sorted order, the same traversal launch, the answers
+ * scattered to their rows.  Element i of every channel still belongs to row i, every channel and the occlusion bit are bit-identical to the
+ * call without the flag, nothing beyond element n - 1 is touched.  Rows that are not traced (zero direction, a non-finite component, a NaN
+ * maximum distance) sort last, so whole packets of them cost nothing.  Rounds are sorted on their own.  The host is not involved and the
+ * stream never waits; the flag adds 16 bytes per ray of a round (unsorted and sorted keys) and rocPRIM's temporary storage for a round,
+ * allocated by the first sorted call under the rule above — a context that never sorts pays nothing.
  * RTX_ERR_INVALID_ARG: n < 1, NULL rays_dev / segments_dev / out / occluded_dev, channels == 0 or with bits outside RTX_QUERY_ALL, any
  * other flag.  RTX_ERR_STATE: before rtx_set_frame, in heat-map mode, or for a scene a render call refuses (an id outside its table);
  * RTX_ERR_LIMIT: a BVH deeper than rtx_config.stack_size allows — the checks of rtx_render_tiles.  An error queues nothing.
- * Out of scope: sorting rays for coherence, barycentrics, albedo, the rtx_group_* path.                                                  */
+ * Out of scope: sorted rays handed back to the caller, sorting across rounds or ray views, a threshold that sorts by itself, barycentrics,
+ * albedo, the rtx_group_* path.                                                                                                          */
 enum { RTX_QUERY_DISTANCE = 1, RTX_QUERY_POSITION = 2, RTX_QUERY_NORMAL = 4, RTX_QUERY_UV = 16,
        RTX_QUERY_MATERIAL_ID = 32, RTX_QUERY_OBJECT_ID = 64, RTX_QUERY_TRIANGLE_ID = 128,
        RTX_QUERY_ALL = 247 };            /* the RTX_AOV_* bits of the same meaning; there is no albedo */
 enum { RTX_QUERY_CHUNK_RAYS = 1 << 20 }; /* rays traced per internal round */
+enum { RTX_QUERY_SORT = 256 };           /* a bit of `flags` of both query calls, next to the RTX_RENDER_* bits they take */
 typedef struct rtx_query_buffers {       /* device pointers, one per channel, NULL = not written */
     float   * distance;                  /* [n]     RayHit::distance, +INFINITY on a miss */
     float   * position;                  /* [n][3]  RayHit::point,  0 on a miss            */
@@ -638,6 +650,10 @@ int rtx_query_closest (rtx_ctx * ctx, const void * rays_dev /* [n][6] f32: origi
                        uint32_t channels, const rtx_query_buffers * out, uint32_t flags);
 int rtx_query_occluded(rtx_ctx * ctx, const void * segments_dev /* [n][7] f32: origin, direction, max distance */, int64_t n,
                        int32_t * occluded_dev /* [n]: 1 or 0 */, uint32_t flags);
+/* The order RTX_QUERY_SORT traces n rows in, without tracing them: the bounds, key and sort launches of every round, then
+ * order_out_dev[first + i] = first + the caller's row in slot i of the round that starts at row `first`.  row_floats: 6 (rays) or 7
+ * (segments), anything else is RTX_ERR_INVALID_ARG; otherwise queued and checked like the query calls (n beyond INT32_MAX: RTX_ERR_LIMIT). */
+int rtx_debug_query_order(rtx_ctx * ctx, const void * rows_dev, int32_t row_floats /* 6 or 7 */, int64_t n, int32_t * order_out_dev);
 
 /* Timing of every kernel launched since rtx_enable_kernel_timing(ctx, 1),
  * measured with HIP events on the stream the kernels are launched on.

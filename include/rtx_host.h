@@ -34,6 +34,7 @@
  *   rtxh_mtl_load            OBJLoader::load_mtl alone                       OBJLoader.cpp:43-68
  *   rtxh_bvh_cache_*         BottomLevelBVH::save_to_disk / load_from_disk   BottomLevelBVH.cpp:149-192
  *   rtxh_texture_mips        Texture::load's box-filter mip chain          Texture.cpp:76-117
+ *   rtxh_query_sort_order    the order RTX_QUERY_SORT traces query rows in, from the same code (csrc/rtx_query_sort_math.h)
  *   rtxh_texture_load        Texture::load: PNG / TGA file -> linear float3 texels + mips   Texture.cpp:30-129
  *   rtxh_image_load          the stbi_load(..., STBI_rgb_alpha) call inside it  Texture.cpp:40
  *   rtxh_sky_load            Sky::Sky: raw float3 angular-map probe file         Sky.cpp:8-26
@@ -173,6 +174,14 @@ int rtxh_scene_update(rtxh_tlas * tlas, int32_t instance_count, const float * po
  * two share the code, for an image of more texels than the int32_t offsets of rtx_texture_desc
  * hold (such an image without a chain used to return RTX_OK with a 64-bit count).                */
 int rtxh_texture_mips(float * texels_rgb, int32_t width, int32_t height, rtx_texture_desc * desc, int64_t * texel_count_out);
+
+/* The order rtx_query_closest / rtx_query_occluded trace n rows in under RTX_QUERY_SORT: rtx_debug_query_order's contract with host memory.
+ * rows: n x row_floats floats (6: origin, direction; 7: with a maximum distance).  Per round of at most RTX_QUERY_CHUNK_RAYS rows the bounds
+ * of the live rows, the key of every row (csrc/rtx_query_sort_math.h, the code the kernels compile) and a sort of the keys:
+ * order_out[first + i] = first + the row in slot i of the round that starts at `first`.  Dead rows (zero direction, a non-finite origin or
+ * direction, a NaN maximum distance) come last in row order.  RTX_ERR_INVALID_ARG: a null pointer, n < 1, row_floats other than 6 or 7;
+ * RTX_ERR_LIMIT: n beyond INT32_MAX.                                                                                                  */
+int rtxh_query_sort_order(const float * rows, int32_t row_floats, int64_t n, int32_t * order_out);
 
 /* Texture::load (Texture.cpp:30-129): decodes a .png or .tga file the way the reference's vendored stb_image v2.19 does with
  * STBI_rgb_alpha (Texture.cpp:40), converts r,g,b bytes to linear light (colour_unpack :13-20, Math::gamma_to_linear Math.h:67-77;
