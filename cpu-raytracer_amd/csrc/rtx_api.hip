@@ -128,7 +128,7 @@ struct rtx_ctx {
     // RTX_QUERY_SORT: unsorted and sorted keys, the twelve bounds and rocPRIM's temporary storage, for query_sort_cap slots; nothing until the first sorted call
     DevBuf d_query_sort; int32_t query_sort_cap = 0; size_t query_sort_tmp = 0;
     size_t slots_alloc = 0, shadow_alloc = 0;
-    DevBuf d_dbg_s0, d_dbg_s1, d_stats_partial, d_pk_fifo, d_counters, d_spill, d_fb_rgb, d_fb_packed, d_display, d_gamma, d_pk_heads;
+    DevBuf d_stats_partial, d_pk_fifo, d_counters, d_spill, d_fb_rgb, d_fb_packed, d_display, d_gamma, d_pk_heads;
     int trace_blocks_closest = 0, trace_blocks_any = 0, trace_blocks_count = 0;
     int pk_blocks_closest = 0, pk_blocks_any = 0;    // persistent grids of the packet kernels (even: waves % 8 == 0, see k_begin_batch)
 
@@ -607,7 +607,7 @@ static int alloc_queues(rtx_ctx * c, int batch_tiles) {
                      (void **)&c->q.sp, (void **)&c->q.sn };
     for (void ** p : f4) { if (!rc) rc = ensure(c, c->qb[k], slots * 16); *p = c->qb[k].p; k++; }
     if (!rc) rc = ensure(c, c->qb[k], slots * 4); c->q.h1 = (int32_t *)c->qb[k].p; k++;
-    c->q.views = nullptr; c->q.s0 = c->q.s1 = nullptr; c->q.shadow_explicit = 0; c->q.cull = 0;      // explicit shadow rays: rtx_debug_occluded allocates them (debug_explicit_rays)
+    c->q.views = nullptr; c->q.s0 = c->q.s1 = nullptr; c->q.shadow_explicit = 0; c->q.cull = 0;
     if (!rc) rc = ensure(c, c->qb[k], sslots * 4); c->q.socc = (uint32_t *)c->qb[k].p; k++;
     c->q.spill = (int32_t *)c->d_spill.p;
     c->q.counters = (DevCounters *)c->d_counters.p;
@@ -674,7 +674,7 @@ static void begin_batch(rtx_ctx * c, DevCounters * counters, uint32_t * pk_heads
                        (uint32_t)(c->pk_blocks_closest * (RTX_PK_BLOCK / RTX_WAVE)), (uint32_t)(c->pk_blocks_any * (RTX_PK_BLOCK / RTX_WAVE)), first_batch ? 1 : 0);
 }
 
-// the two launches a ray query and its debug hook share: the level-1 closest-hit walk and the level-0 shadow-ray walk, per lane or by packets
+// the two launches of a ray query's round (the debug hooks run the same rounds): the level-1 closest-hit walk and the level-0 shadow-ray walk, per lane or by packets
 static void launch_closest_level1(rtx_ctx * c, const DevScene & sc, const DevQueues & q, bool lane) {
     if (lane) hipLaunchKernelGGL((k_trace_fast<false>), dim3(c->trace_blocks_closest), dim3(RTX_TRACE_BLOCK), 0, c->stream, sc, q, 1, 1);
     else      hipLaunchKernelGGL((k_packet<false, false>), dim3(c->pk_blocks_closest), dim3(RTX_PK_BLOCK), 0, c->stream, sc, q, 1, 1);
@@ -2036,11 +2036,11 @@ extern "C" int rtx_debug_group_loopback(rtx_ctx * c, int32_t world, uint32_t fla
 // RTX_QUERY_SORT the round starts with bounds -> keys -> rocPRIM's radix sort, and the fill and the resolve / store go through the sorted keys.
 // Nothing here waits, copies or allocates once the scratch holds a chunk of the call's size.
 //
-// The queue set is the queries' own.  The debug hooks below borrow the frame's: level 1 of the ray queue (which a context with
-// bounces == 0 does not have) and light 0's shadow segment (which a frame without lights does not have), sized and re-sized by
-// alloc_queues.  Here: level 1 for rays and hits, level 0 for the node flags of the one explicit shadow segment, both at base 0 — a
-// closest-hit query touches r0 / r1 / h0 / h1, an occlusion query s0 / s1 / n0 / socc, and the two are stream-ordered, so they share four
-// buffers: 52 bytes per slot, 52 MiB for a full chunk.  DevScene and DevQueues travel by value: a frame queued before or after is untouched.
+// The queue set is the queries' own; the frame's (alloc_queues, c->q, d_counters) belongs to render calls.  Level 1 for rays and hits,
+// level 0 for the node flags of the one explicit shadow segment, both at base 0 — a closest-hit query touches r0 / r1 / h0 / h1, an
+// occlusion query s0 / s1 / n0 / socc, and the two are stream-ordered, so they share four buffers: 52 bytes per slot, 52 MiB for a full
+// chunk.  DevScene and DevQueues travel by value: a frame queued before or after is untouched.  The unit-test hooks rtx_debug_trace_rays /
+// rtx_debug_occluded (further down) run the same setup and the same rounds from host arrays.
 //
 // RTX_QUERY_SORT (sort != null) adds a block of its own, made by the first sorted call and grown only: [unsorted keys][sorted keys][bounds]
 // [rocPRIM's temporary storage], 2 x 8 bytes per slot and what rocPRIM asks for a round of that many keys (a host-side query).  Both blocks
@@ -2111,7 +2111,7 @@ template <int ROW> static int query_sort_round(rtx_ctx * c, const QuerySort & S,
     return RTX_OK;
 }
 
-// the checks both calls share, in the order the header lists them; nothing is queued on an error
+// the checks the two queries and the two debug hooks share, in the order the header lists them; nothing is queued on an error
 static int query_checks(rtx_ctx * c, const void * in, int64_t n, const void * out, uint32_t flags, const char * what) {
     if (!c) return RTX_ERR_INVALID_ARG;
     if (!in || !out || n < 1) { c->err = std::string(what) + ": null pointer or n < 1"; return RTX_ERR_INVALID_ARG; }
@@ -2121,24 +2121,64 @@ static int query_checks(rtx_ctx * c, const void * in, int64_t n, const void * ou
     return validate_references(c);
 }
 
-extern "C" int rtx_query_closest(rtx_ctx * c, const void * rays_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags) {
-    if (c && (channels == 0 || (channels & ~(uint32_t)RTX_QUERY_ALL))) { c->err = "rtx_query_closest: channels must be a non-empty subset of RTX_QUERY_ALL"; return RTX_ERR_INVALID_ARG; }
-    if (int bad = query_checks(c, rays_dev, n, out, flags, "rtx_query_closest")) return bad;
+// What a call decides once for all its rounds: the queue set, the sorted keys of a round (order; null = the caller's order), the kernels the
+// stack rule leaves the flags, the scene by value.  The two queries and the two debug hooks all start here.
+struct QueryCall { DevQueues q; QuerySort S; const uint64_t * order; bool lane; DevScene sc; };
+static int query_setup(rtx_ctx * c, const void * in, int64_t n, const void * out, uint32_t flags, const char * what, QueryCall & k) {
+    if (int bad = query_checks(c, in, n, out, flags, what)) return bad;
     hipSetDevice(c->cfg.device);
-    DevQueues q;
-    QuerySort S;
     const bool sorted = (flags & RTX_QUERY_SORT) != 0;
-    if (int rc = query_queues(c, n, q, sorted ? &S : nullptr)) return rc;
-    const uint64_t * const order = sorted ? S.keys : nullptr;
-    bool lane = (flags & RTX_RENDER_LANE_TRACE) != 0, pk_closest = (flags & RTX_RENDER_PACKET_CLOSEST) != 0;
-    plan_stack_limits(stack_figures(c), lane, pk_closest);
-    if (pk_closest) q.pk_defer_t0_closest = q.pk_defer_t0_primary = q.pk_defer_t0;
-    const DevScene sc = c->scene;
-    DevScene sc_resolve = sc; sc_resolve.diff_enabled = 0;          // the differentials are zero and no channel reports a RayHit differential
+    if (int rc = query_queues(c, n, k.q, sorted ? &k.S : nullptr)) return rc;
+    k.order = sorted ? k.S.keys : nullptr;
+    k.lane = (flags & RTX_RENDER_LANE_TRACE) != 0;
+    bool pk_closest = (flags & RTX_RENDER_PACKET_CLOSEST) != 0;
+    plan_stack_limits(stack_figures(c), k.lane, pk_closest);
+    if (pk_closest) k.q.pk_defer_t0_closest = k.q.pk_defer_t0_primary = k.q.pk_defer_t0;      // thresholds only closest-hit packets read
+    k.sc = c->scene;
+    return RTX_OK;
+}
+
+// The rounds of a call over n rows: round(first, m) queues rows [first, first + m), m <= RTX_QUERY_CHUNK_RAYS, back to back
+template <typename F> static int query_rounds(rtx_ctx * c, DevQueues & q, int64_t n, F && round) {
     for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
         const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
-        const int blocks = (((m + RTX_WAVE - 1) & ~(RTX_WAVE - 1)) + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK;
         q.tile_count = (m + 1023) / 1024;
+        if (int rc = round(first, m)) return rc;
+    }
+    HIP_OK(c, hipGetLastError());
+    return RTX_OK;
+}
+// the grid of a fill: the m rows of a round rounded up to whole packets
+static dim3 query_fill_grid(int m) { return dim3((((m + RTX_WAVE - 1) & ~(RTX_WAVE - 1)) + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK); }
+
+// One closest-hit round: the m rays at rays6 (device, 6 floats each) -> the hit records of slots [0, m) of level 1.  The caller reads them.
+static int query_closest_round(rtx_ctx * c, const QueryCall & k, const float * rays6, int m) {
+    if (k.order) if (int rc = query_sort_round<6>(c, k.S, rays6, m)) return rc;
+    begin_batch(c, k.q.counters, k.q.pk_heads, 0u, false, true);
+    launch_timed(c, "k_query_fill", c->stream, [&] { hipLaunchKernelGGL(k_query_fill, query_fill_grid(m), dim3(RTX_QUERY_BLOCK), 0, c->stream, k.q, rays6, m, k.order); });
+    launch_timed(c, "k_trace_closest", c->stream, [&] { launch_closest_level1(c, k.sc, k.q, k.lane); });
+    return RTX_OK;
+}
+
+// One occlusion round: the m segments at segments7 (device, 7 floats each) through ONE explicit shadow segment of level 0, whatever lights
+// the frame has (none are read), then occluded[row] = 1 / 0.
+static int query_occluded_round(rtx_ctx * c, const QueryCall & k, const float * segments7, int m, int32_t * occluded) {
+    DevQueues q = k.q; q.shadow_explicit = 1;
+    DevScene sc = k.sc; sc.light_count = 1;
+    if (k.order) if (int rc = query_sort_round<7>(c, k.S, segments7, m)) return rc;
+    begin_batch(c, q.counters, q.pk_heads, 0u, false, true);
+    launch_timed(c, "k_query_fill_segments", c->stream, [&] { hipLaunchKernelGGL(k_query_fill_segments, query_fill_grid(m), dim3(RTX_QUERY_BLOCK), 0, c->stream, q, segments7, m, k.order); });
+    launch_timed(c, "k_trace_any", c->stream, [&] { launch_any_level0(c, sc, q, k.lane); });
+    launch_timed(c, "k_query_store_occluded", c->stream, [&] { hipLaunchKernelGGL(k_query_store_occluded, dim3((m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK), dim3(RTX_QUERY_BLOCK), 0, c->stream, q, m, occluded, k.order); });
+    return RTX_OK;
+}
+
+extern "C" int rtx_query_closest(rtx_ctx * c, const void * rays_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags) {
+    if (c && (channels == 0 || (channels & ~(uint32_t)RTX_QUERY_ALL))) { c->err = "rtx_query_closest: channels must be a non-empty subset of RTX_QUERY_ALL"; return RTX_ERR_INVALID_ARG; }
+    QueryCall k;
+    if (int rc = query_setup(c, rays_dev, n, out, flags, "rtx_query_closest", k)) return rc;
+    DevScene sc_resolve = k.sc; sc_resolve.diff_enabled = 0;        // the differentials are zero and no channel reports a RayHit differential
+    return query_rounds(c, k.q, n, [&](int64_t first, int m) -> int {
         DevQuery t;
         auto on = [&](uint32_t bit) { return (channels & bit) != 0; };
         t.distance = on(RTX_QUERY_DISTANCE) && out->distance ? out->distance + first : nullptr;
@@ -2148,40 +2188,16 @@ extern "C" int rtx_query_closest(rtx_ctx * c, const void * rays_dev, int64_t n, 
         t.material_id = on(RTX_QUERY_MATERIAL_ID) && out->material_id ? out->material_id + first : nullptr;
         t.object_id = on(RTX_QUERY_OBJECT_ID) && out->object_id ? out->object_id + first : nullptr;
         t.triangle_id = on(RTX_QUERY_TRIANGLE_ID) && out->triangle_id ? out->triangle_id + first : nullptr;
-        if (sorted) if (int rc = query_sort_round<6>(c, S, (const float *)rays_dev + 6 * first, m)) return rc;
-        begin_batch(c, q.counters, q.pk_heads, 0u, false, true);
-        launch_timed(c, "k_query_fill", c->stream, [&] { hipLaunchKernelGGL(k_query_fill, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, q, (const float *)rays_dev + 6 * first, m, order); });
-        launch_timed(c, "k_trace_closest", c->stream, [&] { launch_closest_level1(c, sc, q, lane); });
-        launch_timed(c, "k_query_resolve", c->stream, [&] { hipLaunchKernelGGL(k_query_resolve, dim3((m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc_resolve, q, m, t, order); });
-    }
-    HIP_OK(c, hipGetLastError());
-    return RTX_OK;
+        if (int rc = query_closest_round(c, k, (const float *)rays_dev + 6 * first, m)) return rc;
+        launch_timed(c, "k_query_resolve", c->stream, [&] { hipLaunchKernelGGL(k_query_resolve, dim3((m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc_resolve, k.q, m, t, k.order); });
+        return RTX_OK;
+    });
 }
 
 extern "C" int rtx_query_occluded(rtx_ctx * c, const void * segments_dev, int64_t n, int32_t * occluded_dev, uint32_t flags) {
-    if (int bad = query_checks(c, segments_dev, n, occluded_dev, flags, "rtx_query_occluded")) return bad;
-    hipSetDevice(c->cfg.device);
-    DevQueues q;
-    QuerySort S;
-    const bool sorted = (flags & RTX_QUERY_SORT) != 0;
-    if (int rc = query_queues(c, n, q, sorted ? &S : nullptr)) return rc;
-    const uint64_t * const order = sorted ? S.keys : nullptr;
-    q.shadow_explicit = 1;
-    bool lane = (flags & RTX_RENDER_LANE_TRACE) != 0, pk_closest = false;
-    plan_stack_limits(stack_figures(c), lane, pk_closest);
-    DevScene sc = c->scene; sc.light_count = 1;                     // one explicit segment (k_query_fill_segments), whatever lights the frame has: none are read
-    for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
-        const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
-        const int blocks = (((m + RTX_WAVE - 1) & ~(RTX_WAVE - 1)) + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK;
-        q.tile_count = (m + 1023) / 1024;
-        if (sorted) if (int rc = query_sort_round<7>(c, S, (const float *)segments_dev + 7 * first, m)) return rc;
-        begin_batch(c, q.counters, q.pk_heads, 0u, false, true);
-        launch_timed(c, "k_query_fill_segments", c->stream, [&] { hipLaunchKernelGGL(k_query_fill_segments, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, q, (const float *)segments_dev + 7 * first, m, order); });
-        launch_timed(c, "k_trace_any", c->stream, [&] { launch_any_level0(c, sc, q, lane); });
-        launch_timed(c, "k_query_store_occluded", c->stream, [&] { hipLaunchKernelGGL(k_query_store_occluded, dim3((m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK), dim3(RTX_QUERY_BLOCK), 0, c->stream, q, m, occluded_dev + first, order); });
-    }
-    HIP_OK(c, hipGetLastError());
-    return RTX_OK;
+    QueryCall k;
+    if (int rc = query_setup(c, segments_dev, n, occluded_dev, flags, "rtx_query_occluded", k)) return rc;
+    return query_rounds(c, k.q, n, [&](int64_t first, int m) { return query_occluded_round(c, k, (const float *)segments_dev + 7 * first, m, occluded_dev + first); });
 }
 
 // the order RTX_QUERY_SORT traces n rows of row_floats (6: rays, 7: segments) floats in: the bounds, key and sort launches of every round and
@@ -2194,34 +2210,24 @@ extern "C" int rtx_debug_query_order(rtx_ctx * c, const void * rows_dev, int32_t
     DevQueues q;
     QuerySort S;
     if (int rc = query_queues(c, n, q, &S)) return rc;
-    for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
-        const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
+    return query_rounds(c, q, n, [&](int64_t first, int m) -> int {
         const float * const rows = (const float *)rows_dev + (size_t)row_floats * first;
         if (int rc = row_floats == 6 ? query_sort_round<6>(c, S, rows, m) : query_sort_round<7>(c, S, rows, m)) return rc;
         launch_timed(c, "k_query_sort_order", c->stream, [&] { hipLaunchKernelGGL(k_query_sort_order, dim3((m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK), dim3(RTX_QUERY_BLOCK), 0, c->stream, (const uint64_t *)S.keys, m, (int32_t)first, order_out_dev + first); });
-    }
-    HIP_OK(c, hipGetLastError());
-    return RTX_OK;
+        return RTX_OK;
+    });
 }
 
 // ---- unit-level entry points, second set: the traversal / hit / light / plot functions at caller-supplied inputs -------------------
-// rtx_debug_trace_rays: n rays (18 floats: origin, direction, dO_dx, dO_dy, dD_dx, dD_dy) through Scene::trace_primitives as the frame
-// kernels do it (the level-1 ray queue, the production closest-hit kernel, the accept-branch rebuild of k_shade), all RayHit fields out
-// (27 floats, layout of oracle orc_trace_closest); rtx_debug_occluded: Scene::intersect_primitives through the production shadow-ray
-// kernel (the level-0 shadow queue of light 0).
-__global__ void k_debug_fill_rays(DevQueues q, const float * rays, int n) {
+// rtx_debug_trace_rays: n rays (18 floats: origin, direction, dO_dx, dO_dy, dD_dx, dD_dy) from host memory through the closest-hit rounds of
+// the ray queries above (query_setup, query_closest_round), then the accept-branch rebuild of k_shade with the rays' differentials: all
+// RayHit fields out (27 floats, layout of oracle orc_trace_closest).  rtx_debug_occluded: n host segments through the queries' occlusion
+// rounds.  Both wait and copy back.
+// slots [0, m) of level 1 of a round -> out; the differentials come from the 18-float rows.  No hit (a miss, or a row the fill did not
+// walk): hit 0, distance +INFINITY, every other float 0, as the oracle's miss record.
+__global__ void k_debug_rebuild(DevScene sc, DevQueues q, const float * rays, float * out, int m) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) { q.counters->ray_count[1] = (uint32_t)n; }
-    if (i >= n) return;
-    const float * r = rays + 18 * (size_t)i;
-    const uint32_t s = (uint32_t)q.level_base[1] + (uint32_t)i;
-    q.r0[s] = make_float4(r[0], r[1], r[2], r[3]); q.r1[s] = make_float4(r[4], r[5], as_f(0), as_f(-1));      // (origin, d.x) (d.y, d.z, pixel, parent)
-    q.r2[s] = make_float4(r[8], r[9], r[10], r[11]); q.r3[s] = make_float4(r[12], r[13], r[14], r[15]);
-    q.r4[s] = make_float4(r[16], r[17], r[6], r[7]);
-}
-__global__ void k_debug_rebuild(DevScene sc, DevQueues q, const float * rays, float * out, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+    if (i >= m) return;
     const float * r = rays + 18 * (size_t)i;
     RayFull ray;
     ray.o = V3(r[0], r[1], r[2]); ray.d = V3(r[3], r[4], r[5]); ray.dO_dx = V3(r[6], r[7], r[8]); ray.dO_dy = V3(r[9], r[10], r[11]);
@@ -2230,83 +2236,55 @@ __global__ void k_debug_rebuild(DevScene sc, DevQueues q, const float * rays, fl
     const float4 h0 = q.h0[s]; const int tri = q.h1[s], prim = as_i(h0.w);
     float * o = out + 27 * (size_t)i;
     for (int k = 0; k < 27; k++) o[k] = 0.0f;
-    o[1] = h0.x;
+    o[1] = INFINITY;
     if (PRIM_KIND(prim) == PRIM_NONE) return;
     HitFull h; h.material_id = 0;
     h.point = h.normal = h.dO_dx = h.dO_dy = h.dN_dx = h.dN_dy = V3(0, 0, 0); h.u = h.v = h.ds_dx = h.ds_dy = h.dt_dx = h.dt_dy = 0.0f;
     if (PRIM_KIND(prim) == PRIM_TRI) rebuild_triangle_hit(sc, PRIM_INDEX(prim), tri, h0.x, h0.y, h0.z, ray, h);
     else if (PRIM_KIND(prim) == PRIM_SPHERE) rebuild_sphere_hit(sc, sc.spheres[PRIM_INDEX(prim)], h0.x, ray, h);
     else rebuild_plane_hit(sc, sc.planes[PRIM_INDEX(prim)], h0.x, ray, h);
-    o[0] = 1.0f; o[2] = h.point.x; o[3] = h.point.y; o[4] = h.point.z; o[5] = h.normal.x; o[6] = h.normal.y; o[7] = h.normal.z;
+    o[0] = 1.0f; o[1] = h0.x; o[2] = h.point.x; o[3] = h.point.y; o[4] = h.point.z; o[5] = h.normal.x; o[6] = h.normal.y; o[7] = h.normal.z;
     o[8] = (float)h.material_id; o[9] = h.u; o[10] = h.v; o[11] = h.ds_dx; o[12] = h.ds_dy; o[13] = h.dt_dx; o[14] = h.dt_dy;
     o[15] = h.dO_dx.x; o[16] = h.dO_dx.y; o[17] = h.dO_dx.z; o[18] = h.dO_dy.x; o[19] = h.dO_dy.y; o[20] = h.dO_dy.z;
     o[21] = h.dN_dx.x; o[22] = h.dN_dx.y; o[23] = h.dN_dx.z; o[24] = h.dN_dy.x; o[25] = h.dN_dy.y; o[26] = h.dN_dy.z;
 }
-__global__ void k_debug_fill_shadow(DevQueues q, int nL, const float * od7, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) q.counters->ray_count[0] = (uint32_t)n;
-    if (i >= n) return;
-    const float * r = od7 + 7 * (size_t)i;
-    q.n0[(uint32_t)q.level_base[0] + (uint32_t)i] = make_float4(0.0f, 0.0f, 0.0f, as_f(NF_HIT | NF_LIT));
-    for (int L = 0; L < nL; L++) {
-        const uint32_t s = (uint32_t)q.shadow_base[0] + (uint32_t)L * (uint32_t)q.level_cap[0] + (uint32_t)i;
-        q.s0[s] = make_float4(r[0], r[1], r[2], L == 0 ? r[6] : -1.0f);      // only light 0's segment carries rays; the others are marked culled
-        q.s1[s] = make_float4(r[3], r[4], r[5], 0.0f);
-        q.socc[s] = 0u;
-    }
-}
-
-static int debug_queues(rtx_ctx * c, int n) {
-    if (!c->frame_set) { c->err = "debug trace before rtx_set_frame"; return RTX_ERR_STATE; }
-    if (int bad = validate_references(c)) return bad;
-    const int tiles = (n + 1023) / 1024;
-    if (tiles > 4096) return RTX_ERR_LIMIT;
-    int rc = alloc_queues(c, tiles < 1 ? 1 : tiles);
-    if (rc) return rc;
-    begin_batch(c, (DevCounters *)c->d_counters.p, (uint32_t *)c->d_pk_heads.p, 0u, false, true);
-    return RTX_OK;
-}
 
 extern "C" int rtx_debug_trace_rays(rtx_ctx * c, const float * rays18, int32_t n, float * hits27, uint32_t flags) {
-    if (!c || !rays18 || !hits27 || n <= 0 || c->cfg.bounces < 1) return RTX_ERR_INVALID_ARG;
-    hipSetDevice(c->cfg.device);
-    int rc = debug_queues(c, n);
-    if (rc) return rc;
-    DevBuf din, dout;
-    rc = upload(c, din, rays18, (size_t)n * 72);
+    if (!c) return RTX_ERR_INVALID_ARG;
+    // bounces < 1: a plain argument check, kept from when the hook borrowed the frame's level-1 queue (no ray needs it); RTX_QUERY_SORT: slot i is row i here
+    if (c->cfg.bounces < 1 || (flags & RTX_QUERY_SORT)) { c->err = "rtx_debug_trace_rays: bounces < 1 or RTX_QUERY_SORT"; return RTX_ERR_INVALID_ARG; }
+    QueryCall k;
+    if (int rc = query_setup(c, rays18, n, hits27, flags, "rtx_debug_trace_rays", k)) return rc;
+    std::vector<float> rays6((size_t)n * 6);                        // the rows k_query_fill takes: origin and direction
+    for (int32_t i = 0; i < n; i++) memcpy(&rays6[(size_t)i * 6], rays18 + (size_t)i * 18, 24);
+    DevBuf din, din6, dout;
+    int rc = upload(c, din, rays18, (size_t)n * 72);
+    if (!rc) rc = upload(c, din6, rays6.data(), (size_t)n * 24);
     if (!rc) rc = ensure(c, dout, (size_t)n * 108);
+    if (!rc) rc = query_rounds(c, k.q, n, [&](int64_t first, int m) -> int {
+        if (int bad = query_closest_round(c, k, (const float *)din6.p + 6 * first, m)) return bad;
+        hipLaunchKernelGGL(k_debug_rebuild, dim3((m + 255) / 256), dim3(256), 0, c->stream, k.sc, k.q, (const float *)din.p + 18 * first, (float *)dout.p + 27 * first, m);
+        return RTX_OK;
+    });
+    HIP_OK(c, hipStreamSynchronize(c->stream));                     // also on an error: what was queued reads the buffers that go out of scope here
     if (rc) return rc;
-    DevQueues q = c->q; q.first_tile = 0; q.tile_stride = 1; q.tile_count = (n + 1023) / 1024; q.primary_slots = 0; q.tm_packed = nullptr;
-    const DevScene sc = c->scene;
-    const bool lane = (flags & RTX_RENDER_LANE_TRACE) != 0;
-    if (!lane && (flags & RTX_RENDER_PACKET_CLOSEST)) q.pk_defer_t0_closest = q.pk_defer_t0_primary = q.pk_defer_t0;
-    hipLaunchKernelGGL(k_debug_fill_rays, dim3((n + 255) / 256), dim3(256), 0, c->stream, q, (const float *)din.p, n);
-    launch_closest_level1(c, sc, q, lane);
-    hipLaunchKernelGGL(k_debug_rebuild, dim3((n + 255) / 256), dim3(256), 0, c->stream, sc, q, (const float *)din.p, (float *)dout.p, n);
-    HIP_OK(c, hipStreamSynchronize(c->stream));
     HIP_OK(c, hipMemcpy(hits27, dout.p, (size_t)n * 108, hipMemcpyDeviceToHost));
     return RTX_OK;
 }
 
 extern "C" int rtx_debug_occluded(rtx_ctx * c, const float * origin_direction_maxdist7, int32_t n, uint32_t * occluded, uint32_t flags) {
-    if (!c || !origin_direction_maxdist7 || !occluded || n <= 0 || c->scene.light_count < 1) return RTX_ERR_INVALID_ARG;
-    hipSetDevice(c->cfg.device);
-    int rc = debug_queues(c, n);
-    if (rc) return rc;
-    DevBuf din;
-    if ((rc = upload(c, din, origin_direction_maxdist7, (size_t)n * 28))) return rc;
-    DevQueues q = c->q; q.first_tile = 0; q.tile_stride = 1; q.tile_count = (n + 1023) / 1024; q.primary_slots = n; q.tm_packed = nullptr;
-    {   // explicit shadow rays (the frame kernels derive theirs from the hit's point and the light): origin + distance, direction per shadow slot of level 0
-        const size_t sslots = (size_t)q.level_cap[0] * (size_t)(c->scene.light_count > 0 ? c->scene.light_count : 1);
-        rc = ensure(c, c->d_dbg_s0, sslots * 16); if (!rc) rc = ensure(c, c->d_dbg_s1, sslots * 16);
-        if (rc) return rc;
-        q.s0 = (float4 *)c->d_dbg_s0.p; q.s1 = (float4 *)c->d_dbg_s1.p; q.shadow_explicit = 1;
-    }
-    const DevScene sc = c->scene;
-    hipLaunchKernelGGL(k_debug_fill_shadow, dim3((n + 255) / 256), dim3(256), 0, c->stream, q, sc.light_count, (const float *)din.p, n);
-    launch_any_level0(c, sc, q, (flags & RTX_RENDER_LANE_TRACE) != 0);
+    if (!c) return RTX_ERR_INVALID_ARG;
+    // no light: a plain argument check, kept from when the hook borrowed light 0's shadow segment (no segment needs one); RTX_QUERY_SORT: refused as above
+    if (c->scene.light_count < 1 || (flags & RTX_QUERY_SORT)) { c->err = "rtx_debug_occluded: a frame without lights or RTX_QUERY_SORT"; return RTX_ERR_INVALID_ARG; }
+    QueryCall k;
+    if (int rc = query_setup(c, origin_direction_maxdist7, n, occluded, flags, "rtx_debug_occluded", k)) return rc;
+    DevBuf din, dout;
+    int rc = upload(c, din, origin_direction_maxdist7, (size_t)n * 28);
+    if (!rc) rc = ensure(c, dout, (size_t)n * 4);
+    if (!rc) rc = query_rounds(c, k.q, n, [&](int64_t first, int m) { return query_occluded_round(c, k, (const float *)din.p + 7 * first, m, (int32_t *)dout.p + first); });
     HIP_OK(c, hipStreamSynchronize(c->stream));
-    HIP_OK(c, hipMemcpy(occluded, q.socc + q.shadow_base[0], (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (rc) return rc;
+    HIP_OK(c, hipMemcpy(occluded, dout.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return RTX_OK;
 }
 

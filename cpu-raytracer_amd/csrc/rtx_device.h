@@ -141,7 +141,7 @@ struct DevQueues {
     float4 *   sp; // hit point.xyz, -
     float4 *   sn; // hit normal.xyz, -
     uint32_t * socc; // 1 = occluded (with RTX_RENDER_CULL_DEAD_SHADOW_RAYS also pre-set by the shading pass: 1 = contributes nothing, do not trace; 0 = trace)
-    // explicit shadow rays (rtx_debug_occluded only): origin.xyz + max distance, direction.xyz
+    // explicit shadow rays (the occlusion queries: query_queues, k_query_fill_segments): origin.xyz + max distance, direction.xyz
     float4 *   s0;
     float4 *   s1;
     int32_t    shadow_explicit;   // 1: the shadow-ray kernels read s0 / s1 instead of deriving the rays

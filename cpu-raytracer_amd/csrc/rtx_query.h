@@ -10,6 +10,7 @@
 //
 // The walk in between is the production kernel of the render path, launched as a frame launches it (rtx_api.hip): a closest-hit launch over
 // level 1, a shadow-ray launch over level 0.  All four kernels stream: one slot per lane, a chunk (<= RTX_QUERY_CHUNK_RAYS rows) per launch.
+// The unit-test hooks rtx_debug_trace_rays / rtx_debug_occluded run the same rounds, so the rules below are theirs too.
 //
 // No ray: a row whose direction is (+-0, +-0, +-0), as for ray views (primary_pixel_v, rtx_trace.h).  Its slot is marked RAY_DEAD_PIXEL (not
 // NF_LIT for a segment), which both closest-hit kernels answer with the record of a clipped pixel: a miss.

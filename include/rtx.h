@@ -704,12 +704,22 @@ int rtx_group_slot_pixels(int32_t width, int32_t height, int32_t world, int32_t 
 int rtx_debug_libm(rtx_ctx * ctx, int32_t fn, const float * a, const float * b, float * out, int32_t n);
 /* Texture::sample (Texture.h:33-49) of an uploaded texture at n inputs (s,t,ds_dx,ds_dy,dt_dx,dt_dy) */
 int rtx_debug_texture_sample(rtx_ctx * ctx, int32_t texture_id, const float * in6, float * out_rgb, int32_t n);
-/* Scene::trace_primitives (Scene.cpp:173-180) of n rays (18 floats each: origin, direction, dO_dx, dO_dy, dD_dx, dD_dy) through the
- * production closest-hit kernel + the accept-branch rebuild of the shade kernel; out: 27 floats per ray = every RayHit field
+/* Scene::trace_primitives (Scene.cpp:173-180) of n rays (18 floats each: origin, direction, dO_dx, dO_dy, dD_dx, dD_dy) in host memory
+ * through the production closest-hit kernel + the accept-branch rebuild of the shade kernel; out: 27 floats per ray = every RayHit field
  * (RayHit.h:5-21): hit, distance, point[3], normal[3], material_id, u, v, ds_dx, ds_dy, dt_dx, dt_dy, dO_dx[3], dO_dy[3], dN_dx[3], dN_dy[3]
- * (zero on a miss except distance).  flags: RTX_RENDER_LANE_TRACE / RTX_RENDER_PACKET_CLOSEST select the kernel.  Needs bounces >= 1. */
+ * (a miss: hit 0, distance +INFINITY, everything else 0).  The call uploads the rays, runs the rounds of rtx_query_closest (above), waits
+ * and copies back; rtx_debug_occluded does the same through the rounds of rtx_query_occluded.  So, for both hooks:
+ *  - a row with an all-zero direction or a NaN / infinite origin or direction component is not walked and answers as a miss / not
+ *    occluded (0): the queries' rule, above;
+ *  - flags: RTX_RENDER_LANE_TRACE / RTX_RENDER_PACKET_CLOSEST choose the kernel as for a query, so scenes whose trees exceed the packet
+ *    kernels' limits take the per-lane kernels (the answers are bit-identical);
+ *  - the queries' checks and codes apply: heat-map mode is RTX_ERR_STATE, any other flag RTX_ERR_INVALID_ARG, and so is RTX_QUERY_SORT
+ *    (the hooks answer in the caller's order);
+ *  - any n >= 1 (rounds of RTX_QUERY_CHUNK_RAYS; the earlier limit of 4096 tiles of 1024 rays is gone); the frame's queues, a queued frame and what rtx_get_stats has yet to read are untouched.
+ * Still RTX_ERR_INVALID_ARG: rtx_debug_trace_rays on a context with bounces < 1, rtx_debug_occluded on a frame without lights. */
 int rtx_debug_trace_rays(rtx_ctx * ctx, const float * rays18, int32_t n, float * hits27, uint32_t flags);
-/* Scene::intersect_primitives (Scene.cpp:182-190) of n rays (7 floats: origin, direction, max distance) through the production shadow-ray kernel */
+/* Scene::intersect_primitives (Scene.cpp:182-190) of n segments (7 floats: origin, direction, max distance) in host memory through the
+ * production shadow-ray kernel: occluded[i] = 1 / 0.  See rtx_debug_trace_rays. */
 int rtx_debug_occluded(rtx_ctx * ctx, const float * origin_direction_maxdist7, int32_t n, uint32_t * occluded, uint32_t flags);
 /* Point / Spot / DirectionalLight::calc_lighting (10 floats in: normal, to_light, to_camera, distance^2; 9 out) and Window::plot */
 int rtx_debug_light_plot(rtx_ctx * ctx, const rtx_point_light * pl, const rtx_spot_light * sl, const rtx_directional_light * dl,

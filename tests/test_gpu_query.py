@@ -6,7 +6,9 @@ ids as the RTX_AOV_*_ID channels number them; trace_any at seven maximum distanc
   * batch sizes around a wave and a packet, and a call of more than two internal rounds (RTX_QUERY_CHUNK_RAYS);
   * zero and NaN directions, channel subsets, nothing written past n;
   * the AOV channels of a ray view over the same rays, and the frames around a query unchanged;
-  * a scene changed on the device (rtx_update_instances), stream order with torch, and every error code."""
+  * a scene changed on the device (rtx_update_instances), stream order with torch, and every error code;
+  * the unit-test hooks rtx_debug_trace_rays / rtx_debug_occluded, which run the queries' rounds from host arrays: the same answers as the
+    queries, a queued frame left alone, rows that are no ray, more than one round."""
 import copy
 import ctypes as C
 
@@ -15,7 +17,7 @@ import pytest
 
 import rayset
 import util
-from test_gpu_rays import LANE_TRACE, PACKET_CLOSEST, chain_blas_scene, many_instances_scene, check_occ
+from test_gpu_rays import LANE_TRACE, PACKET_CLOSEST, chain_blas_scene, many_instances_scene, check_occ, traceable
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -133,6 +135,32 @@ def test_queries_equal_the_oracle(api, name):
     check_scene(api, sc, rays, dist, labels, want, occ, name)
 
 
+MISS27 = np.array([0.0, np.inf] + [0.0] * 25, f32)                  # the oracle's miss record: hit 0, distance inf, every other RayHit float 0
+
+
+@pytest.mark.parametrize("name", ["materials_aniso", "cube"])
+def test_the_debug_hooks_equal_the_queries(api, name):
+    """rtx_debug_trace_rays with zero differentials against query_closest, column by channel, and rtx_debug_occluded against
+    query_occluded, on one context: the same rounds, bit for bit.  The hook's material_id is 0 where the query's is -1 (a miss)."""
+    sc, rays, dist, labels, want, occ = generated(name)
+    assert len(rays) <= 448
+    r = api.Renderer(traceable(sc))
+    rays_t = dev(rays)
+    for flags, kw in FLAGS.items():
+        hook = r.debug_trace_rays(zero_diff(rays), flags)
+        q = {k: host(v) for k, v in r.query_closest(rays_t, tuple(api.QUERY_CHANNELS), **kw).items()}
+        mat = np.where(q["material_id"] < 0, 0, q["material_id"]).astype(f32)
+        cols = {"hit": (hook[:, 0], (q["object_id"] >= 0).astype(f32)), "distance": (hook[:, 1], q["distance"]), "point": (hook[:, 2:5], q["position"]),
+                "normal": (hook[:, 5:8], q["normal"]), "material_id": (hook[:, 8], mat), "u, v": (hook[:, 9:11], q["uv"])}
+        bad = {k: np.flatnonzero(~same_bits(g, w))[:6].tolist() for k, (g, w) in cols.items() if not same_bits(g, w).all()}
+        assert not bad, (name, flags, bad)
+    seg = segments_of(rays, dist)
+    for flags in (0, LANE_TRACE):
+        hook = r.debug_occluded(seg, flags)
+        assert set(np.unique(hook)) <= {0, 1}
+        assert np.array_equal(hook != 0, host(r.query_occluded(dev(seg), **FLAGS[flags])) != 0), (name, flags)
+
+
 # ---- 2. no bounce level, no light ------------------------------------------------------------------------------------------------------
 def test_queries_need_neither_a_bounce_level_nor_a_light(api):
     sc, rays, dist, labels, want, occ = generated("cube", strip=True)
@@ -188,6 +216,19 @@ def test_more_than_two_internal_rounds(api):
     assert torch.equal(occ_big, dev(occ.astype(np.int32)).repeat(reps)[:N])
 
 
+def test_more_than_one_round_through_a_hook(api):
+    """n = RTX_QUERY_CHUNK_RAYS + 65: two rounds, the second ending in a partial packet.  Row i answers as row i mod len(rays) of a one-round call."""
+    sc, rays, dist, labels, want, occ = generated("materials_aniso")
+    r = api.Renderer(traceable(sc))
+    rays18, seg = zero_diff(rays), segments_of(rays, dist[:, 1:2])
+    small, small_occ = r.debug_trace_rays(rays18), r.debug_occluded(seg)
+    assert np.array_equal(small_occ != 0, occ[:, 1])
+    idx = np.arange(api.RTX_QUERY_CHUNK_RAYS + 65) % len(rays)
+    big = r.debug_trace_rays(rays18[idx])
+    assert big.shape == (len(idx), 27) and np.array_equal(big.view(np.uint32), small.view(np.uint32)[idx])
+    assert np.array_equal(r.debug_occluded(seg[idx]), small_occ[idx])
+
+
 # ---- 5. zero direction -----------------------------------------------------------------------------------------------------------------
 def test_zero_direction_is_no_ray_and_nan_is_one(api):
     import orc
@@ -216,6 +257,32 @@ def test_zero_direction_is_no_ray_and_nan_is_one(api):
         check_channels(r.query_closest(dev(rays), tuple(api.QUERY_CHANNELS), **kw), ref, labels, f"flags {flags}")
     for flags in (0, LANE_TRACE):
         assert np.array_equal(host(r.query_occluded(dev(seg), **FLAGS[flags])) != 0, occ_ref), flags
+
+
+def test_rows_that_are_no_ray_through_the_hooks(api):
+    """Zero, NaN and infinite rows through rtx_debug_trace_rays / rtx_debug_occluded: the fill does not walk them (a NaN origin in the
+    packet walk would never end), they answer as the miss record / not occluded, and their neighbours answer as without them."""
+    sc, rays, dist, labels, want, occ = generated("materials_aniso")
+    hit = np.flatnonzero(np.isfinite(want["distance"]))
+    rows = hit[[3, len(hit) // 2, len(hit) - 2, 1, len(hit) // 3]]                           # rays that hit something
+    assert len(set(rows.tolist())) == 5
+    edited = rays.copy()
+    edited[rows[0], 3:6] = (0.0, 0.0, 0.0)
+    edited[rows[1], 3:6] = (-0.0, 0.0, 0.0)
+    edited[rows[2], 3] = np.nan
+    edited[rows[3], 1] = np.nan
+    edited[rows[4], 2] = np.inf
+    untouched = np.setdiff1d(np.arange(len(rays)), rows)
+    r = api.Renderer(traceable(sc))
+    d7 = np.full((len(rays), 1), np.inf, f32)
+    for flags in FLAGS:
+        base, got = r.debug_trace_rays(zero_diff(rays), flags), r.debug_trace_rays(zero_diff(edited), flags)
+        assert (base[rows, 0] == 1.0).all(), flags
+        assert np.array_equal(got[rows].view(np.uint32), np.tile(MISS27, (5, 1)).view(np.uint32)), (flags, got[rows, :3])
+        assert np.array_equal(got[untouched].view(np.uint32), base[untouched].view(np.uint32)), flags
+    for flags in (0, LANE_TRACE):
+        base, got = r.debug_occluded(segments_of(rays, d7), flags), r.debug_occluded(segments_of(edited, d7), flags)
+        assert (got[rows] == 0).all() and np.array_equal(got[untouched], base[untouched]), flags
 
 
 # ---- 6. channel subsets and bounds -----------------------------------------------------------------------------------------------------
@@ -304,6 +371,21 @@ def test_a_query_leaves_a_queued_frame_and_its_stats_alone(api):
     rgb, packed = r.framebuffer()
     assert stats == ref["stats"] and util.bit_exact(rgb, ref["rgb"]) and np.array_equal(packed, ref["packed"])
     check_channels(got, want, labels)
+
+
+def test_a_hook_call_leaves_a_queued_frame_and_its_stats_alone(api):
+    """render, both debug hooks, read: the frame and rtx_get_stats are those of a context that made no hook call."""
+    sc, rays, dist, labels, want, occ = generated("materials_aniso")
+    sc = traceable(sc)
+    ref = api.Renderer(sc).render()
+    r = api.Renderer(sc)
+    r.render_async()
+    hits = r.debug_trace_rays(zero_diff(rays))
+    blocked = r.debug_occluded(segments_of(rays, dist[:, :1]))
+    stats, _ = r.stats()
+    rgb, packed = r.framebuffer()
+    assert stats == ref["stats"] and util.bit_exact(rgb, ref["rgb"]) and np.array_equal(packed, ref["packed"])
+    assert same_bits(hits[:, 1], want["distance"]).all() and np.array_equal(blocked != 0, occ[:, 0])
 
 
 # ---- 8. device-side scene changes are seen ---------------------------------------------------------------------------------------------
