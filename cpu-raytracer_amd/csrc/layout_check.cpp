@@ -1,6 +1,7 @@
 // layout_check.cpp — the device node layouts of rtx_layout.h on the CPU: `make layout_check` builds this with -fsanitize=address,undefined
 // and runs it.  The traversal kernels read these records with hand-written assembly, so a record writer that drifts is a wrong image only
-// some scenes show.  Pinned here, bit for bit: the records of small trees spelled out by hand, the lane record's round trip, and that the
+// some scenes show.  Pinned here, bit for bit: the records of small trees spelled out by hand, the lane record's round trip, the packed stack
+// and work-list entries of the per-lane walks (round trip at the field limits, the fit rules, the pk4c slot's reference), and that the
 // pass a refit and a build end with (rtxl::finish_index, the body of k_refit_finish / k_build_finish) gives back exactly what the host
 // converters of rtx_layout_host.h made — which is what plan_refit relies on when it runs the pass at bind, and where the pk4c meta word
 // composed from slot-index arithmetic meets the one composed from the tree walk.  Needs no GPU and no ROCm.
@@ -83,6 +84,42 @@ static void hand_spelled_records() {
     CHECK(rtxl::pk4c_meta(2u, 3u << 30, 0) == (2u | 3u << 26) && rtxl::pk4c_meta(2u, 3u << 30, 1) == 2u);          // the parent's axis rides in the first slot of the pair
     CHECK(rtxl::pk4c_meta(1u << 30, 2u << 30, 2) == (2u << 26 | 1u << 30) && rtxl::pk4c_meta(1u << 30, 2u << 30, 3) == 1u << 30);
     CHECK(rtxl::pk4c_meta(5u | 2u << 30, 5u | 2u << 30, 0) == (5u | 2u << 30));                                     // a leaf's own axis bits are its own, never a parent's
+}
+
+// ---- the packed stack and work-list entries of the per-lane walks ----------------------------------------------------------------------------
+static void packed_entries() {
+    CASE("leaf reference: round trip at the field limits, the fit rule, the bits the asm walkers spell");
+    const uint32_t first_max = (1u << 24) - 1u;
+    for (uint32_t axis = 0; axis <= 3u; axis++)
+        for (uint32_t leaf : { 0u, 1u, 15u })
+            for (uint32_t first : { 0u, 1u, first_max }) {
+                const uint32_t cw = leaf | axis << 30;
+                CHECK(rtxl::ref_fits(first, cw));
+                const int32_t e = rtxl::ref_pack(first, cw);
+                CHECK((uint32_t)e == (0x40000000u | axis << 28 | leaf << 24 | first));
+                CHECK(rtxl::ref_is_packed(e) && e > 0 && (uint32_t)rtxl::ref_first(e) == first && (uint32_t)rtxl::ref_count_word(e) == cw);
+            }
+    CHECK((uint32_t)rtxl::ref_pack(first_max, 15u | 3u << 30) == 0x7fffffffu && rtxl::REF_PACKED == 0x40000000u);
+    CHECK(!rtxl::ref_fits(1u << 24, 1u) && !rtxl::ref_fits(0u, 16u) && !rtxl::ref_fits(0u, 16u | 3u << 30) && !rtxl::ref_fits(0xffffffffu, 0u));
+    CHECK(!rtxl::ref_is_packed((int32_t)first_max) && !rtxl::ref_is_packed(0));          // a node index is never taken for a packed reference
+    CASE("leaf reference of a pk4c slot equals the one of its node's (first, count)");
+    for (int s = 0; s < 4; s++)
+        for (uint32_t child_count : { 3u, 1u << 30, 3u << 30 })
+            for (uint32_t slot_count : { 15u, 1u, 2u << 30, 3u << 30 }) {
+                const uint32_t meta = rtxl::pk4c_meta(slot_count, child_count, s);
+                CHECK(rtxl::ref_pack_meta(first_max, meta) == rtxl::ref_pack(first_max, slot_count));
+                CHECK(rtxl::ref_pack_meta(6u, meta) == rtxl::ref_pack(6u, slot_count));
+            }
+    CHECK(rtxl::pk4c_meta(2u, 3u << 30, 0) != 2u && rtxl::ref_pack_meta(4u, rtxl::pk4c_meta(2u, 3u << 30, 0)) == (int32_t)(0x40000000u | 2u << 24 | 4u));   // a parent axis rode in that meta word
+    CASE("4-wide entry: round trip at the field limits, the fit rule");
+    for (uint32_t count : { 0u, 1u, 255u })
+        for (uint32_t first : { 0u, 1u, first_max }) {
+            CHECK(rtxl::wide_fits(first, count));
+            const int32_t e = rtxl::wide_pack(first, count);
+            CHECK((uint32_t)e == (count << 24 | first) && (uint32_t)rtxl::wide_first(e) == first && (uint32_t)rtxl::wide_count(e) == count);
+        }
+    CHECK((uint32_t)rtxl::wide_pack(first_max, 255u) == 0xffffffffu);
+    CHECK(!rtxl::wide_fits(1u << 24, 1u) && !rtxl::wide_fits(0u, 256u));
 }
 
 // ---- the lane record's inverse --------------------------------------------------------------------------------------------------------------
@@ -200,6 +237,7 @@ static std::vector<rtx_bvh_node> unbalanced_tree() {
 int main() {
     hand_spelled_records();
     lane_round_trip();
+    packed_entries();
     for (int T : { 1, 4, 5, 9, 16, 17, 1025 })
         for (int order_mode = 0; order_mode <= 1; order_mode++) {
             char name[64];

@@ -8,6 +8,7 @@
 //                  one operand of a packed-fp32 instruction                                                       [packet kernels, rtx_packet.h]
 //   4-wide slot    the packet record's row with other words: (min.x, min.y, max.x, max.y) (min.z, max.z, first, meta); four slots per record,
 //                  the record of inner node j at row 2 * (left child of j).  pk4 (shadow rays): meta = leaf count.  pk4c (closest hit): pk4c_meta
+//   packed entries one word per pending node on the per-lane walks' stacks and work lists: ref_* (binary walks), wide_* (pk4 walks)  [both]
 //   plane keys     per axis 2 floats per node, (min, max), NaN -> +inf: the unsorted input of the plane lists plane_member searches
 #pragma once
 #include <stddef.h>
@@ -83,6 +84,28 @@ RTX_HD uint32_t pk4c_meta(uint32_t slot_count, uint32_t child_count, int s) {
     const bool parent_axis = (s & 1) == 0 && (child_count & 0x3fffffffu) == 0u;
     return (slot_count & 0x3fffffffu) | (parent_axis ? (child_count >> 30) << 26 : 0u) | ((slot_count >> 30) << 30);
 }
+
+// ---- stack and work-list entries of the per-lane walks: a node that passed its ray's slab test, as one word -----------------------------------
+// leaf reference (binary walks: k_trace_fast, pk_lane_phase_any, pk_lane_phase_closest; the work lists): the node's own words,
+// REF_PACKED | axis << 28 | leaf count << 24 | first — nothing to fetch before its children / triangles.  count_word = leaf count | axis << 30.
+// It fits when first < 2^24 and the leaf count < 16; a node that does not fit travels as its index (< 2^24, so bit 30 is clear) and is read back.
+// The asm walkers of rtx_packet.h spell the same bits (PKB_DEFER of pk_blas_any_asm, PK_ASM_REF).
+constexpr uint32_t REF_PACKED = 0x40000000u;
+RTX_HD bool ref_fits(uint32_t first, uint32_t count_word) { return first < (1u << 24) && (count_word & 0x3fffffffu) < 16u; }
+RTX_HD int32_t ref_pack(uint32_t first, uint32_t count_word) {
+    return (int32_t)(REF_PACKED | ((count_word >> 30) << 28) | ((count_word & 0x3fffffffu) << 24) | first);
+}
+// of a pk4c slot (first, meta = pk4c_meta): its parent-axis bits are not the node's; build_nodes_pk4c admits only trees whose every node fits
+RTX_HD int32_t ref_pack_meta(uint32_t first, uint32_t meta) { return ref_pack(first, meta & 0xc000000fu); }
+RTX_HD bool ref_is_packed(int32_t e) { return (e & (int32_t)REF_PACKED) != 0; }
+RTX_HD int32_t ref_first(int32_t e) { return e & 0x00ffffff; }
+RTX_HD int32_t ref_count_word(int32_t e) { return (int32_t)((((uint32_t)e >> 28) & 3u) << 30) | ((e >> 24) & 15); }
+// 4-wide entry (pk4 walks: pk_lane_phase_any4, k_items and the items pk_blas_any_asm4 writes): leaf count << 24 | first, no axis — any order
+// is exact for shadow rays.  build_nodes_pk4 admits only trees whose every node fits: first < 2^24, leaf count < 256.
+RTX_HD bool wide_fits(uint32_t first, uint32_t count) { return first < (1u << 24) && count < 256u; }
+RTX_HD int32_t wide_pack(uint32_t first, uint32_t count) { return (int32_t)((count << 24) | first); }
+RTX_HD int32_t wide_first(int32_t e) { return e & 0x00ffffff; }
+RTX_HD int32_t wide_count(int32_t e) { return (int32_t)((uint32_t)e >> 24); }
 
 // ---- plane keys ----------------------------------------------------------------------------------------------------------------------------
 RTX_HD float plane_key(float v) { return v != v ? INFINITY : v; }

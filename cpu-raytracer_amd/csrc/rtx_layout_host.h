@@ -48,7 +48,7 @@ static bool build_nodes_pk4(const rtx_bvh_node * nodes, int n, int tri_count, st
         const int i = stack.back(); stack.pop_back();
         const int cnt = nodes[i].count & 0x3fffffff, f = nodes[i].left_or_first;
         for (int a = 0; a < 3; a++) if (!(nodes[i].aabb_min[a] <= nodes[i].aabb_max[a])) return false;      // the sign-coherent slab test relies on min <= max
-        if (cnt > 0) { if (cnt >= 256) return false; continue; }
+        if (cnt > 0) { if (!rtxl::wide_fits((uint32_t)f, (uint32_t)cnt)) return false; continue; }      // stack entries and items pack (first, count) into one word
         if (f & 1) return false;                                   // records are addressed by left / 2
         if (!inside(f, i) || !inside(f + 1, i)) return false;      // nesting
         order.push_back(i); stack.push_back(f); stack.push_back(f + 1);
@@ -105,7 +105,7 @@ static bool build_nodes_pk4c(const rtx_bvh_node * nodes, int n, int tri_count, s
     while (!stack.empty()) {
         const int i = stack.back(); stack.pop_back();
         const int cnt = nodes[i].count & 0x3fffffff, f = nodes[i].left_or_first;
-        if (cnt > 0) { if (cnt >= 16) return false; continue; }      // work-list and stack entries pack (first, count) into one word
+        if (cnt > 0) { if (!rtxl::ref_fits((uint32_t)f, (uint32_t)nodes[i].count)) return false; continue; }      // work-list and stack entries pack (first, count) into one word
         if (f & 1) return false;                                   // records are addressed by left / 2
         if (!inside(f, i) || !inside(f + 1, i)) return false;      // nesting
         order.push_back(i); stack.push_back(f); stack.push_back(f + 1);

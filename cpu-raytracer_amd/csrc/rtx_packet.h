@@ -111,6 +111,26 @@ RTX_D bool pk_slab(float4 q0, float4 q1, const PkRay & r) {
     return t_near < t_far;
 }
 
+// One inner step of a lane's walk over the 4-wide records of build_nodes_pk4 (pk_lane_phase_any4, k_items): the whole record of the node
+// whose left child is `first` (one round trip: eight gathers), the four slab tests, then the bookkeeping.  The lowest passing slot is walked
+// next; slot k = 1 .. 3 is to be pushed (qk; entry ek, rtxl::wide_pack) when it passes and a lower slot passes too — 3 first, so that they
+// pop in slot order.  The storing stays with the caller.
+struct Pk4Step { int e1, e2, e3; bool q1, q2, q3; bool have_cur; int cur_first, cur_cnt; };
+RTX_D Pk4Step pk4_step(rtx_gptr nodes4, const int first, const PkRay & ray) {
+    const int base = 4 * first;
+    const float4 a0 = gld(nodes4, base), a1 = gld(nodes4, base + 1), b0 = gld(nodes4, base + 2), b1 = gld(nodes4, base + 3);
+    const float4 c0 = gld(nodes4, base + 4), c1 = gld(nodes4, base + 5), d0 = gld(nodes4, base + 6), d1 = gld(nodes4, base + 7);
+    const bool p0 = pk_slab<true>(a0, a1, ray), p1 = pk_slab<true>(b0, b1, ray), p2 = pk_slab<true>(c0, c1, ray), p3 = pk_slab<true>(d0, d1, ray);
+    Pk4Step r;
+    r.e1 = rtxl::wide_pack((uint32_t)as_i(b1.z), (uint32_t)as_i(b1.w)); r.q1 = p1 & p0;
+    r.e2 = rtxl::wide_pack((uint32_t)as_i(c1.z), (uint32_t)as_i(c1.w)); r.q2 = p2 & (p0 | p1);
+    r.e3 = rtxl::wide_pack((uint32_t)as_i(d1.z), (uint32_t)as_i(d1.w)); r.q3 = p3 & (p0 | p1 | p2);
+    r.have_cur = p0 | p1 | p2 | p3;
+    r.cur_first = p0 ? as_i(a1.z) : (p1 ? as_i(b1.z) : (p2 ? as_i(c1.z) : as_i(d1.z)));
+    r.cur_cnt   = p0 ? as_i(a1.w) : (p1 ? as_i(b1.w) : (p2 ? as_i(c1.w) : as_i(d1.w)));
+    return r;
+}
+
 #ifdef RTX_PK_PROF
 #define PK_T0() const unsigned long long pk_t0_ = __builtin_amdgcn_s_memtime()
 #define PK_T1(slot) do { W.prof[slot] += __builtin_amdgcn_s_memtime() - pk_t0_; W.prof[slot + 5]++; } while (0)
@@ -422,6 +442,7 @@ RTX_D void pk_descend(PkWalk & W, int stack_size, int ordered, int thr) {
 
 // triangles s98 .. s99-1 of W.tris against the lanes of m: triangle_intersect (BottomLevelBVH.cpp:311-346), the triangle in SGPRs
 // (labels PKB_TRI / PKB_NEXT / PKB_POP and the operands belong to the enclosing asm statement; s88 / s89 / s[84:87] are temporaries)
+// Must match tri_test_all (rtx_trace.h): the same operations in the same order, the same accept rule.
 #define PK_ASM_TRI_LOOP \
         "PKB_TRI_%=:\n\t"                                                                                                         \
         "s_lshl_b32 s89, s98, 6\n\t"                                                                                              \
@@ -597,7 +618,7 @@ RTX_D void pk_blas_any_asm(PkWalk & W, int stack_size, const uint32_t lane_lds, 
         // ---------------- defer: push the node on the private stacks of the lanes in m ----------------
         "PKB_DEFER_%=:\n\t"
         "s_and_b32 s88, %[cnt], 0xffff\n\t"
-        "s_cmp_ge_u32 s88, 16\n\t"                          // packable entry: leaf count < 16, first < 2^24
+        "s_cmp_ge_u32 s88, 16\n\t"                          // must match rtxl::ref_fits / ref_pack (rtx_layout.h): leaf count < 16, first < 2^24
         "s_cbranch_scc1 PKB_NODEFER_%=\n\t"
         "s_cmp_ge_u32 %[first], 0x1000000\n\t"
         "s_cbranch_scc1 PKB_NODEFER_%=\n\t"
@@ -812,7 +833,7 @@ RTX_D void pk_blas_any_asm4(PkWalk & W, rtx_cptr nodes4, const uint32_t lane_lds
         "s_add_u32 s88, %[icnt], 64\n\t"
         "s_cmp_gt_u32 s88, %[icap]\n\t"
         "s_cbranch_scc1 PKB_NODEFER_%=\n\t"                 // chunk full: the packet keeps the node
-        "s_lshl_b32 s89, %[cnt], 24\n\t"
+        "s_lshl_b32 s89, %[cnt], 24\n\t"                    // must match rtxl::wide_pack (rtx_layout.h)
         "s_or_b32 s89, s89, %[first]\n\t"
         "s_mov_b64 s[92:93], %[m]\n\t"
         "s_mov_b64 s[84:85], exec\n\t"
@@ -846,7 +867,7 @@ RTX_D void pk_blas_any_asm4(PkWalk & W, rtx_cptr nodes4, const uint32_t lane_lds
         "s_and_b64 s[84:85], vcc, %[m]\n\t"
         "s_cmp_lg_u64 s[84:85], 0\n\t"
         "s_cbranch_scc1 PKB_NODEFER_%=\n\t"
-        "s_lshl_b32 s89, %[cnt], 24\n\t"
+        "s_lshl_b32 s89, %[cnt], 24\n\t"                    // must match rtxl::wide_pack (rtx_layout.h)
         "s_or_b32 s89, s89, %[first]\n\t"
         "s_mov_b64 s[84:85], exec\n\t"
         "s_mov_b64 exec, %[m]\n\t"
@@ -903,7 +924,7 @@ struct PkHybrid { int * stk; float * stk_key; uint32_t lane_lds; int * spill; fl
 
 // ---- hybrid any-hit walk, per-lane phase -----------------------------------------------------------------------------------------
 // Walks the subtrees the packet walk handed to the lanes' private stacks (entries are nodes that already passed the lane's slab test,
-// packed like k_trace_fast's: 0x40000000 | axis << 28 | leaf count << 24 | first).  One ray per lane, per-lane gathers through the
+// packed like k_trace_fast's: rtxl::ref_pack, rtx_layout.h).  One ray per lane, per-lane gathers through the
 // vector memory path, private stack striped through LDS ([entry][lane], RTX_PK_PRIV entries, deeper ones in HBM): the part of the tree
 // where the rays of a packet no longer agree is walked the way the per-lane kernel walks it, the shared top of the tree was not.
 #define RTX_PK_PRIV 24
@@ -935,9 +956,8 @@ RTX_D void pk_lane_phase_any(PkWalk & W, const int lane, int * const stk, int * 
             const bool pl = slab_test_sel<true>(la, lb, co, cinv, tmax, k), pr = slab_test_sel<true>(ra, rb, co, cinv, tmax, k);
             if (pl) {
                 if (pr) {
-                    const int rf = as_i(ra.w), rc = as_i(rb.w), rl = rc & 0x3fffffff;
-                    if ((uint32_t)rf < (1u << 24) && rl < 16) push((int)(0x40000000u | (((uint32_t)rc >> 30) << 28) | ((uint32_t)rl << 24) | (uint32_t)rf));
-                    else push(left + 1);
+                    const uint32_t rf = (uint32_t)as_i(ra.w), rc = (uint32_t)as_i(rb.w);
+                    push(rtxl::ref_fits(rf, rc) ? rtxl::ref_pack(rf, rc) : left + 1);
                 }
                 cur_first = as_i(la.w); cur_cnt = as_i(lb.w);
             } else if (pr) { cur_first = as_i(ra.w); cur_cnt = as_i(rb.w); }
@@ -949,26 +969,15 @@ RTX_D void pk_lane_phase_any(PkWalk & W, const int lane, int * const stk, int * 
             const int cnt = cur_cnt & 0x3fffffff;
             for (int i = cur_first; i < cur_first + cnt; i++) {
                 const float4 p0 = gld(tris, RTX_TRI_STRIDE * i), e1 = gld(tris, RTX_TRI_STRIDE * i + 1), e2 = gld(tris, RTX_TRI_STRIDE * i + 2);
-                const v3 edge_1 = V3(e1.x, e1.y, e1.z), edge_2 = V3(e2.x, e2.y, e2.z);
-                const v3 h = vcross(cd, edge_2);
-                const float a = vdot(edge_1, h);
-                const float f = 1.0f / a;
-                const v3 s = vsub(co, V3(p0.x, p0.y, p0.z));
-                const float u = f * vdot(s, h);
-                if (!((u > 0.0f) & (u < 1.0f))) continue;
-                const v3 qq = vcross(s, edge_1);
-                const float v = f * vdot(cd, qq);
-                if (!((v > 0.0f) & ((u + v) < 1.0f))) continue;
-                const float t = f * vdot(edge_2, qq);
-                if (!((t > RAY_EPSILON) & (t < tmax))) continue;
-                live = false; break;
+                float t, u, v;
+                if (tri_test(v3q(p0), v3q(e1), v3q(e2), co, cd, tmax, t, u, v)) { live = false; break; }
             }
         }
         // pop
         if (live && !have_cur && psp > 0) {
             psp--;
             const int e = (psp < RTX_PK_PRIV) ? stk[psp * RTX_WAVE] : spill[(psp - RTX_PK_PRIV) * spill_stride];
-            if (e & 0x40000000) { cur_first = e & 0x00ffffff; cur_cnt = (int)((((uint32_t)e >> 28) & 3u) << 30) | ((e >> 24) & 15); }
+            if (rtxl::ref_is_packed(e)) { cur_first = rtxl::ref_first(e); cur_cnt = rtxl::ref_count_word(e); }
             else { const float4 na = gld(nodes, 2 * e), nb = gld(nodes, 2 * e + 1); cur_first = as_i(na.w); cur_cnt = as_i(nb.w); }
             have_cur = true;
         }
@@ -981,8 +990,8 @@ RTX_D void pk_lane_phase_any(PkWalk & W, const int lane, int * const stk, int * 
 #endif
 }
 
-// The per-lane phase over the 4-wide records (entries: leaf count << 24 | first, nodes that passed the lane's slab test): one 128-byte
-// gather feeds four slab tests, the lowest passing slot is walked next, the others go to the private stack.
+// The per-lane phase over the 4-wide records (entries: rtxl::wide_pack, nodes that passed the lane's slab test): one 128-byte
+// gather feeds four slab tests, the lowest passing slot is walked next, the others go to the private stack (pk4_step).
 RTX_D void pk_lane_phase_any4(PkWalk & W, const int lane, const uint32_t lane_lds, int * const spill, const int spill_stride, rtx_gptr nodes4, rtx_gptr tris) {
     typedef __attribute__((address_space(3))) int lds_int;
     lds_int * const stk = (lds_int *)(uintptr_t)lane_lds;           // ds_write / ds_read, not flat accesses
@@ -1000,47 +1009,26 @@ RTX_D void pk_lane_phase_any4(PkWalk & W, const int lane, const uint32_t lane_ld
     for (;;) {
         if (__ballot(live && (have_cur || psp > 0)) == 0ull) break;
         if (live && have_cur && cur_cnt == 0) {
-            // the whole record first (one round trip), the four tests, then the bookkeeping
-            const int base = 4 * cur_first;
-            const float4 a0 = gld(nodes4, base), a1 = gld(nodes4, base + 1), b0 = gld(nodes4, base + 2), b1 = gld(nodes4, base + 3);
-            const float4 c0 = gld(nodes4, base + 4), c1 = gld(nodes4, base + 5), d0 = gld(nodes4, base + 6), d1 = gld(nodes4, base + 7);
-            const bool p0 = pk_slab<true>(a0, a1, W.ray), p1 = pk_slab<true>(b0, b1, W.ray), p2 = pk_slab<true>(c0, c1, W.ray), p3 = pk_slab<true>(d0, d1, W.ray);
-            const int e1 = (int)(((uint32_t)as_i(b1.w) << 24) | (uint32_t)as_i(b1.z)), e2 = (int)(((uint32_t)as_i(c1.w) << 24) | (uint32_t)as_i(c1.z));
-            const int e3 = (int)(((uint32_t)as_i(d1.w) << 24) | (uint32_t)as_i(d1.z));
-            // slot k is pushed when it passes and a lower slot passes too (that one is walked first)
-            const bool q3 = p3 & (p0 | p1 | p2), q2 = p2 & (p0 | p1), q1 = p1 & p0;
-            if (psp + 3 <= RTX_PK_PRIV) {
-                if (q3) { stk[psp * RTX_WAVE] = e3; psp++; }
-                if (q2) { stk[psp * RTX_WAVE] = e2; psp++; }
-                if (q1) { stk[psp * RTX_WAVE] = e1; psp++; }
-            } else { if (q3) push(e3); if (q2) push(e2); if (q1) push(e1); }
-            have_cur = p0 | p1 | p2 | p3;
-            cur_first = p0 ? as_i(a1.z) : (p1 ? as_i(b1.z) : (p2 ? as_i(c1.z) : as_i(d1.z)));
-            cur_cnt   = p0 ? as_i(a1.w) : (p1 ? as_i(b1.w) : (p2 ? as_i(c1.w) : as_i(d1.w)));
+            const Pk4Step s = pk4_step(nodes4, cur_first, W.ray);
+            if (psp + 3 <= RTX_PK_PRIV) {          // room for all three: no bounds check per entry
+                if (s.q3) { stk[psp * RTX_WAVE] = s.e3; psp++; }
+                if (s.q2) { stk[psp * RTX_WAVE] = s.e2; psp++; }
+                if (s.q1) { stk[psp * RTX_WAVE] = s.e1; psp++; }
+            } else { if (s.q3) push(s.e3); if (s.q2) push(s.e2); if (s.q1) push(s.e1); }
+            have_cur = s.have_cur; cur_first = s.cur_first; cur_cnt = s.cur_cnt;
         }
         if (live && have_cur && cur_cnt > 0) {
             have_cur = false;
             for (int i = cur_first; i < cur_first + cur_cnt; i++) {
                 const float4 p0 = gld(tris, RTX_TRI_STRIDE * i), e1 = gld(tris, RTX_TRI_STRIDE * i + 1), e2 = gld(tris, RTX_TRI_STRIDE * i + 2);
-                const v3 edge_1 = V3(e1.x, e1.y, e1.z), edge_2 = V3(e2.x, e2.y, e2.z);
-                const v3 h = vcross(cd, edge_2);
-                const float a = vdot(edge_1, h);
-                const float f = 1.0f / a;
-                const v3 s = vsub(co, V3(p0.x, p0.y, p0.z));
-                const float u = f * vdot(s, h);
-                if (!((u > 0.0f) & (u < 1.0f))) continue;
-                const v3 qq = vcross(s, edge_1);
-                const float v = f * vdot(cd, qq);
-                if (!((v > 0.0f) & ((u + v) < 1.0f))) continue;
-                const float t = f * vdot(edge_2, qq);
-                if (!((t > RAY_EPSILON) & (t < tmax))) continue;
-                live = false; break;
+                float t, u, v;
+                if (tri_test(v3q(p0), v3q(e1), v3q(e2), co, cd, tmax, t, u, v)) { live = false; break; }
             }
         }
         if (live && !have_cur && psp > 0) {
             psp--;
             const int e = (psp < RTX_PK_PRIV) ? stk[psp * RTX_WAVE] : spill[(psp - RTX_PK_PRIV) * spill_stride];
-            cur_first = e & 0x00ffffff; cur_cnt = (int)((uint32_t)e >> 24);
+            cur_first = rtxl::wide_first(e); cur_cnt = rtxl::wide_count(e);
             have_cur = true;
         }
     }
@@ -1056,12 +1044,11 @@ RTX_D void pk_lane_phase_any4(PkWalk & W, const int lane, const uint32_t lane_ld
 // that point on: the far child re-tested at pop time against the then-current closest distance (entries not tested yet: the same test
 // on the node's own box), the lane's own near / far order, strict comparisons.  Results are those of the reference's per-ray loop.
 #define RTX_PK_FIFO 48                      // work-list entries per lane (HBM, [entry][thread]); a lane turns private only if the list cannot overflow
-// A work-list entry is (reference, key).  reference: 0x40000000 | axis << 28 | leaf count << 24 | first (the node's own (first, count): nothing to
-// fetch before its children / triangles; nodes with first >= 2^24 or 16+ triangles: the node index, fetched when its turn comes).  key: the
+// A work-list entry is (reference, key).  reference: rtxl::ref_pack (rtx_layout.h; the node's own (first, count): nothing to
+// fetch before its children / triangles; a node that does not fit: the node index, fetched when its turn comes).  key: the
 // lane's t_near of the node's box, computed by the shared walk when it popped the entry — the reference's pop-time test at the entry's turn is
 // exactly `key < closest distance then` (slab_test_key); -inf for a node the lane has passed already (hand-over, parked sign split); NaN =
 // "test the fetched box" (entries written by the compiled walk, which has no per-lane t_near at hand).
-#define PK_FIFO_PACKED 0x40000000
 #define PK_KEY_PASSED (-INFINITY)
 // WIDE: the inner step reads the ordered 4-wide record of the node (build_nodes_pk4c, rtx_api.hip: the four grandchildren in the tree's shape),
 // tests the four boxes and takes them in the order the two binary levels would — half the dependent fetches, and the two children's own tests
@@ -1113,8 +1100,8 @@ RTX_D void pk_lane_phase_closest(PkWalk & W, const int lane, const bool ordered,
             };
             const bool p0 = slab(a0, a1, k0), p1 = slab(b0, b1, k1), p2 = slab(c0, c1, k2), p3 = slab(d0, d1, k3);
             // a slot as a stack entry: its node's own (first, count, axis); a key of +inf marks a slot that failed (or is unused)
-            auto entry = [](const float4 & lo, const float4 & hi) { const uint32_t m = (uint32_t)as_i(hi.w); return (int)(0x40000000u | ((m >> 30) << 28) | ((m & 15u) << 24) | (uint32_t)as_i(hi.z)); };
-            int e0 = entry(a0, a1), e1 = entry(b0, b1), e2 = entry(c0, c1), e3 = entry(d0, d1);
+            auto entry = [](const float4 & hi) { return rtxl::ref_pack_meta((uint32_t)as_i(hi.z), (uint32_t)as_i(hi.w)); };
+            int e0 = entry(a1), e1 = entry(b1), e2 = entry(c1), e3 = entry(d1);
             k0 = p0 ? k0 : INFINITY; k1 = p1 ? k1 : INFINITY; k2 = p2 ? k2 : INFINITY; k3 = p3 ? k3 : INFINITY;
             // the lane's own near / far order at the node and at its two children (BVHNode.h:30-40); axis 0 = a leaf child: one slot, no order
             const bool lf_x = ((pos_bits >> ((uint32_t)cur_cnt >> 30)) & 1u) != 0u;
@@ -1131,7 +1118,7 @@ RTX_D void pk_lane_phase_closest(PkWalk & W, const int lane, const bool ordered,
             if (q1 && q0) push(e1, k1);
             const int e = q0 ? e0 : (q1 ? e1 : (q2 ? e2 : e3));
             have_cur = q0 | q1 | q2 | q3;
-            cur_first = e & 0x00ffffff; cur_cnt = (int)((((uint32_t)e >> 28) & 3u) << 30) | ((e >> 24) & 15);
+            cur_first = rtxl::ref_first(e); cur_cnt = rtxl::ref_count_word(e);
         }
         if (!WIDE && have_cur && (cur_cnt & 0x3fffffff) == 0) {
             const int left = cur_first;
@@ -1148,11 +1135,8 @@ RTX_D void pk_lane_phase_closest(PkWalk & W, const int lane, const bool ordered,
             const int far_first  = left_first ? as_i(ra.w) : as_i(la.w), far_cnt  = left_first ? as_i(rb.w) : as_i(lb.w);
             if (p_near) {
                 if (p_far) {
-                    const int far_leaf = far_cnt & 0x3fffffff;
                     const float far_key = left_first ? kr : kl;
-                    if ((uint32_t)far_first < (1u << 24) && far_leaf < 16)
-                        push((int)(0x40000000u | (((uint32_t)far_cnt >> 30) << 28) | ((uint32_t)far_leaf << 24) | (uint32_t)far_first), far_key);
-                    else push(left_first ? left + 1 : left, far_key);
+                    push(rtxl::ref_fits((uint32_t)far_first, (uint32_t)far_cnt) ? rtxl::ref_pack((uint32_t)far_first, (uint32_t)far_cnt) : (left_first ? left + 1 : left), far_key);
                 }
                 cur_first = near_first; cur_cnt = near_cnt;
             } else if (p_far) { cur_first = far_first; cur_cnt = far_cnt; }
@@ -1177,23 +1161,9 @@ RTX_D void pk_lane_phase_closest(PkWalk & W, const int lane, const bool ordered,
                 const float3 p0 = gld3(tris, RTX_TRI_STRIDE * i), e1 = gld3(tris, RTX_TRI_STRIDE * i + 1), e2 = gld3(tris, RTX_TRI_STRIDE * i + 2);
                 const float3 q0 = gld3(tris, RTX_TRI_STRIDE * j), f1 = gld3(tris, RTX_TRI_STRIDE * j + 1), f2 = gld3(tris, RTX_TRI_STRIDE * j + 2);
                 __builtin_amdgcn_sched_barrier(0);          // all six loads are issued before the first use (the scheduler had put the first test between the two triangles' loads)
-                auto test = [&](const float3 & a0, const float3 & a1, const float3 & a2, const int idx) {
-                    const v3 edge_1 = V3(a1.x, a1.y, a1.z), edge_2 = V3(a2.x, a2.y, a2.z);
-                    const v3 h = vcross(cd, edge_2);
-                    const float a = vdot(edge_1, h);
-                    const float f = 1.0f / a;
-                    const v3 s = vsub(co, V3(a0.x, a0.y, a0.z));
-                    const float u = f * vdot(s, h);
-                    if (!((u > 0.0f) & (u < 1.0f))) return;
-                    const v3 qq = vcross(s, edge_1);
-                    const float v = f * vdot(cd, qq);
-                    if (!((v > 0.0f) & ((u + v) < 1.0f))) return;
-                    const float t = f * vdot(edge_2, qq);
-                    if (!((t > RAY_EPSILON) & (t < tcur))) return;
-                    tcur = t; W.best_u = u; W.best_v = v; W.best_tri = idx; W.best_prim = PRIM_TRI | W.cur_inst;
-                };
-                test(p0, e1, e2, i);
-                if (two) test(q0, f1, f2, j);
+                float t, u, v;
+                if (tri_test(v3q(p0), v3q(e1), v3q(e2), co, cd, tcur, t, u, v)) { tcur = t; W.best_u = u; W.best_v = v; W.best_tri = i; W.best_prim = PRIM_TRI | W.cur_inst; }
+                if (two && tri_test(v3q(q0), v3q(f1), v3q(f2), co, cd, tcur, t, u, v)) { tcur = t; W.best_u = u; W.best_v = v; W.best_tri = j; W.best_prim = PRIM_TRI | W.cur_inst; }
             }
         }
 #ifdef RTX_LANE_PROF
@@ -1211,7 +1181,7 @@ RTX_D void pk_lane_phase_closest(PkWalk & W, const int lane, const bool ordered,
                 if (sp < RTX_LDS_STACK) { e = H.stk[sp * RTX_WAVE]; key = H.stk_key[sp * RTX_WAVE]; }
                 else { e = H.spill[(sp - RTX_LDS_STACK) * H.spill_stride]; key = H.spill_key[(sp - RTX_LDS_STACK) * H.spill_stride]; }
                 if (key < tcur) {                       // the reference's pop-time test (slab_test_key: t_near < closest distance now)
-                    if (e & 0x40000000) { cur_first = e & 0x00ffffff; cur_cnt = (int)((((uint32_t)e >> 28) & 3u) << 30) | ((e >> 24) & 15); }
+                    if (rtxl::ref_is_packed(e)) { cur_first = rtxl::ref_first(e); cur_cnt = rtxl::ref_count_word(e); }
                     else { const float4 na = gld(nodes, 2 * e), nb = gld(nodes, 2 * e + 1); cur_first = as_i(na.w); cur_cnt = as_i(nb.w); }
                     have_cur = true;
                 }
@@ -1219,8 +1189,8 @@ RTX_D void pk_lane_phase_closest(PkWalk & W, const int lane, const bool ordered,
                 const int e = nxt.x; const float key = as_f(nxt.y);
                 fi++;
                 if (fi < fifo_n) nxt = H.fifo[fi * H.fifo_stride];
-                if (e & PK_FIFO_PACKED) {
-                    if (key < tcur) { cur_first = e & 0x00ffffff; cur_cnt = (int)((((uint32_t)e >> 28) & 3u) << 30) | ((e >> 24) & 15); have_cur = true; }
+                if (rtxl::ref_is_packed(e)) {
+                    if (key < tcur) { cur_first = rtxl::ref_first(e); cur_cnt = rtxl::ref_count_word(e); have_cur = true; }
                 } else {
                     const float4 na = gld(nodes, 2 * e), nb = gld(nodes, 2 * e + 1);
                     float k;
@@ -1255,6 +1225,7 @@ RTX_D void pk_lane_phase_closest(PkWalk & W, const int lane, const bool ordered,
 // near / far order (a far child is pushed with the lanes that pass NOW and re-tested at pop time against their distances THEN).
 //   stack entry: a = first, b = count | axis << 30, mask, idx = node index, df = depth | PK_FLAG_PRETESTED
 //   SGPRs: s[64:79] child pair / triangle / popped node, s[80:93] temporaries, s[94:97] bases, s98 / s99 triangle loop; VGPRs v[24:31] + operands.
+// must match rtxl::ref_fits / ref_pack (rtx_layout.h)
 #define PK_ASM_REF /* s79 = work-list reference of the node in (first, cnt, idx): its packed (first, count) or, where that does not fit, its index */ \
         "s_and_b32 s76, %[cnt], 0x3fffffff\n\t"                                                                                     \
         "s_cmp_lt_u32 s76, 16\n\t"                                                                                                  \
@@ -1409,7 +1380,7 @@ RTX_D void pk_blas_closest_asm(PkWalk & W, const int stack_size, const int order
         "PKC_LEAF_%=:\n\t"
         "s_mov_b32 s98, %[first]\n\t"
         "s_add_i32 s99, %[first], s88\n\t"
-        "PKC_TRI_%=:\n\t"
+        "PKC_TRI_%=:\n\t"                                      // must match tri_test_all (rtx_trace.h), as PK_ASM_TRI_LOOP does
         "s_lshl_b32 s89, s98, 6\n\t"
         "s_load_dwordx8 s[64:71], s[96:97], s89\n\t"
         "s_add_u32 s89, s89, 32\n\t"
@@ -1601,16 +1572,8 @@ RTX_D bool pk_walk(const DevScene & sc, PkWalk & W, const int lane, const bool o
                     for (int i = W.cur_first; i < W.cur_first + leafc; i++) {
                         const float4 p0 = sld(W.tris, RTX_TRI_STRIDE * i), e1 = sld(W.tris, RTX_TRI_STRIDE * i + 1), e2 = sld(W.tris, RTX_TRI_STRIDE * i + 2);
                         if (PSTAT) { W.st_tris++; W.st_tri_lanes += (unsigned long long)__popcll(W.m); }
-                        const v3 edge_1 = V3(e1.x, e1.y, e1.z), edge_2 = V3(e2.x, e2.y, e2.z);
-                        const v3 h = vcross(cd, edge_2);
-                        const float a = vdot(edge_1, h);
-                        const float f = 1.0f / a;
-                        const v3 s = vsub(co, V3(p0.x, p0.y, p0.z));
-                        const float u = f * vdot(s, h);
-                        const v3 qq = vcross(s, edge_1);
-                        const float v = f * vdot(cd, qq);
-                        const float t = f * vdot(edge_2, qq);
-                        const bool hit = (u > 0.0f) & (u < 1.0f) & (v > 0.0f) & ((u + v) < 1.0f) & (t > RAY_EPSILON) & (t < W.ray.tcur);
+                        float t, u, v;
+                        const bool hit = tri_test_all(v3q(p0), v3q(e1), v3q(e2), co, cd, W.ray.tcur, t, u, v);
                         const unsigned long long hm = __ballot(hit) & W.m;
                         if (hm != 0ull) {
                             const bool mine = (hm >> lane) & 1ull;
@@ -1911,9 +1874,9 @@ void k_packet(const DevScene sc, const DevQueues q, const int level, const int l
                     }
                     else { clipped = true; W.valid = false; }
                 } else {
-                    const float4 r0 = q.r0[out_slot], r1 = q.r1[out_slot];
-                    if (as_i(r1.z) == RAY_DEAD_PIXEL) { clipped = true; W.valid = false; }      // unused slot of a wave's chunk (below): no ray
-                    else { wo = V3(r0.x, r0.y, r0.z); wd = V3(r0.w, r1.x, r1.y); }
+                    v3 o, d;          // not read into wo / wd directly: that costs the fused kernel k_packet<false,false,false,true,false,0> 4 B of scratch and 4 VGPR spills
+                    if (queued_ray(q, out_slot, o, d)) { wo = o; wd = d; }
+                    else { clipped = true; W.valid = false; }                                   // unused slot of a wave's chunk (below): no ray
                 }
             }
         }
@@ -1924,19 +1887,11 @@ void k_packet(const DevScene sc, const DevQueues q, const int level, const int l
             if (!W.valid) return;
             if (ANY) { float tm; load_shadow_ray(sc, q, any_level, any_light, any_rank, out_slot, o, d, tm); }
             else if (level == 0) { int px, py, view; primary_pixel_v<VIEWS, true>(sc, q, pix_idx, px, py, view); RayFull r; primary_ray_v<VIEWS>(sc, q, view, px, py, r, false); o = r.o; d = r.d; }
-            else { const float4 r0 = q.r0[out_slot], r1 = q.r1[out_slot]; o = V3(r0.x, r0.y, r0.z); d = V3(r0.w, r1.x, r1.y); }
+            else queued_ray(q, out_slot, o, d);
         };
         // Scene::trace_primitives / intersect_primitives: spheres, then planes, then the TLAS (Scene.cpp:173-190)
-        if (W.valid) {
-            for (int i = 0; i < sc.sphere_count; i++) {
-                if (ANY) { if (sphere_any(sc.spheres[i], wo, wd, W.ray.tcur)) { W.occluded = true; break; } }
-                else { float t; if (sphere_closest(sc.spheres[i], wo, wd, W.ray.tcur, t)) { W.ray.tcur = t; W.best_prim = PRIM_SPHERE | i; } }
-            }
-            if (!W.occluded) for (int i = 0; i < sc.plane_count; i++) {
-                const float t = plane_t(sc.planes[i], wo, wd);
-                if ((t > RAY_EPSILON) & (t < W.ray.tcur)) { if (ANY) { W.occluded = true; break; } else { W.ray.tcur = t; W.best_prim = PRIM_PLANE | i; } }
-            }
-        }
+        // (a ray view's non-finite ray, marked occluded above, goes through both loops too: it hits no sphere and no plane — ray_is_finite, rtx_trace.h)
+        if (W.valid && world_primitives<ANY>(sc, wo, wd, W.ray.tcur, W.best_prim)) W.occluded = true;
         W.psp = 0; W.pk_steps = 0; W.fifo_n = 0; W.item_slot = out_slot;
         W.alive = __ballot(W.valid && !W.occluded);     // any-hit: lanes leave when occluded; closest-hit: constant
         const unsigned long long alive0 = W.alive;
@@ -2087,7 +2042,7 @@ void k_items(const DevScene sc, const DevQueues q, const int n_chunks, const int
                 else { const DevBlas & B = sc.blas[q2.y]; nodes4 = RTX_GPTR(B.pk4_nodes); tris = RTX_GPTR(B.tri_hot); }
                 co = V3(as_f((int)q0.x), as_f((int)q0.y), as_f((int)q0.z)); cd = V3(as_f((int)q1.x), as_f((int)q1.y), as_f((int)q1.z));
                 pk_set_ray(ray, co, cd, vrcp(cd)); ray.tcur = as_f((int)q0.w);        // vrcp as at the instance entry of the packet walk: the same bits
-                cur_first = (int)(q2.x & 0x00ffffffu); cur_cnt = (int)(q2.x >> 24); have_cur = true; psp = 0;
+                cur_first = rtxl::wide_first((int)q2.x); cur_cnt = rtxl::wide_count((int)q2.x); have_cur = true; psp = 0;
                 busy = q.socc[slot] == 0u;                                            // already occluded: the item is void
 #ifdef RTX_ITEM_STATS
                 st_items++;
@@ -2101,34 +2056,18 @@ void k_items(const DevScene sc, const DevQueues q, const int n_chunks, const int
         st_iters++; st_busy += (unsigned long long)__popcll(__ballot(busy));
 #endif
         if (busy && have_cur && cur_cnt == 0) {
-            const int base = 4 * cur_first;
-            const float4 a0 = gld(nodes4, base), a1 = gld(nodes4, base + 1), b0 = gld(nodes4, base + 2), b1 = gld(nodes4, base + 3);
-            const float4 c0 = gld(nodes4, base + 4), c1 = gld(nodes4, base + 5), d0 = gld(nodes4, base + 6), d1 = gld(nodes4, base + 7);
-            const bool p0 = pk_slab<true>(a0, a1, ray), p1 = pk_slab<true>(b0, b1, ray), p2 = pk_slab<true>(c0, c1, ray), p3 = pk_slab<true>(d0, d1, ray);
-            if (p3 & (p0 | p1 | p2)) push((int)(((uint32_t)as_i(d1.w) << 24) | (uint32_t)as_i(d1.z)));
-            if (p2 & (p0 | p1))      push((int)(((uint32_t)as_i(c1.w) << 24) | (uint32_t)as_i(c1.z)));
-            if (p1 & p0)             push((int)(((uint32_t)as_i(b1.w) << 24) | (uint32_t)as_i(b1.z)));
-            have_cur = p0 | p1 | p2 | p3;
-            cur_first = p0 ? as_i(a1.z) : (p1 ? as_i(b1.z) : (p2 ? as_i(c1.z) : as_i(d1.z)));
-            cur_cnt   = p0 ? as_i(a1.w) : (p1 ? as_i(b1.w) : (p2 ? as_i(c1.w) : as_i(d1.w)));
+            const Pk4Step s = pk4_step(nodes4, cur_first, ray);
+            if (s.q3) push(s.e3);
+            if (s.q2) push(s.e2);
+            if (s.q1) push(s.e1);
+            have_cur = s.have_cur; cur_first = s.cur_first; cur_cnt = s.cur_cnt;
         }
         if (busy && have_cur && cur_cnt > 0) {
             have_cur = false;
             for (int t = cur_first; t < cur_first + cur_cnt; t++) {
                 const float4 p0 = gld(tris, RTX_TRI_STRIDE * t), e1 = gld(tris, RTX_TRI_STRIDE * t + 1), e2 = gld(tris, RTX_TRI_STRIDE * t + 2);
-                const v3 edge_1 = V3(e1.x, e1.y, e1.z), edge_2 = V3(e2.x, e2.y, e2.z);
-                const v3 h = vcross(cd, edge_2);
-                const float a = vdot(edge_1, h);
-                const float f = 1.0f / a;
-                const v3 sv = vsub(co, V3(p0.x, p0.y, p0.z));
-                const float uu = f * vdot(sv, h);
-                if (!((uu > 0.0f) & (uu < 1.0f))) continue;
-                const v3 qq = vcross(sv, edge_1);
-                const float v = f * vdot(cd, qq);
-                if (!((v > 0.0f) & ((uu + v) < 1.0f))) continue;
-                const float tt = f * vdot(edge_2, qq);
-                if (!((tt > RAY_EPSILON) & (tt < ray.tcur))) continue;
-                q.socc[slot] = 1u; busy = false; break;                      // occluded
+                float tt, uu, vv;
+                if (tri_test(v3q(p0), v3q(e1), v3q(e2), co, cd, ray.tcur, tt, uu, vv)) { q.socc[slot] = 1u; busy = false; break; }      // occluded
             }
         }
         if (busy && !have_cur) {
@@ -2136,7 +2075,7 @@ void k_items(const DevScene sc, const DevQueues q, const int n_chunks, const int
             else {
                 psp--;
                 const int e = psp < RTX_ITEM_LDS ? s_stk[psp][threadIdx.x] : ovf[psp - RTX_ITEM_LDS];
-                cur_first = e & 0x00ffffff; cur_cnt = (int)((uint32_t)e >> 24); have_cur = true;
+                cur_first = rtxl::wide_first(e); cur_cnt = rtxl::wide_count(e); have_cur = true;
             }
         }
     }

@@ -16,6 +16,7 @@
 #pragma once
 #include "rtx_math.h"
 #include "rtx_device.h"
+#include "rtx_layout.h"         // rtxl::ref_*: the packed stack entries
 
 #ifndef RTX_REFILL_MIN
 #define RTX_REFILL_MIN   48     // refill a wave when this many lanes are idle (A/B on MI355X: 16 -> 5.57 ms, 48 -> 4.39 ms per cfg3 frame)
@@ -300,6 +301,53 @@ RTX_D float plane_t(const rtx_plane & pl, v3 o, v3 d) {
     v3 n = v3p(pl.normal);
     return -(vdot(n, o) + pl.distance) / vdot(n, d);
 }
+// Scene::trace_primitives / intersect_primitives before the TLAS: spheres, then planes (Scene.cpp:173-190).  ANY: true = occluded, nothing
+// written; closest hit: tcur and best_prim take the nearest one, returns false.  ONE definition for k_trace, k_trace_fast and k_packet.
+template <bool ANY>
+RTX_D bool world_primitives(const DevScene & sc, const v3 wo, const v3 wd, float & tcur, int & best_prim) {
+    for (int i = 0; i < sc.sphere_count; i++) {
+        if (ANY) { if (sphere_any(sc.spheres[i], wo, wd, tcur)) return true; }
+        else { float t; if (sphere_closest(sc.spheres[i], wo, wd, tcur, t)) { tcur = t; best_prim = PRIM_SPHERE | i; } }
+    }
+    for (int i = 0; i < sc.plane_count; i++) {
+        const float t = plane_t(sc.planes[i], wo, wd);
+        if ((t > RAY_EPSILON) & (t < tcur)) { if (ANY) return true; tcur = t; best_prim = PRIM_PLANE | i; }
+    }
+    return false;
+}
+
+// triangle_trace / triangle_intersect, the hit test (BottomLevelBVH.cpp:214-346; the accept branch is rebuilt by k_shade).  ONE C++ spelling in
+// two forms, for every walker that is not hand-scheduled.  Accept rule: 0 < u < 1, 0 < v, u + v < 1 and RAY_EPSILON < t < tmax, every
+// comparison strict, so a NaN anywhere (a degenerate triangle: a == 0, f = +-inf) rejects; f = 1 / a is the correctly rounded division, the
+// sums are vdot's x + (y + z), nothing is fused.  tmax is the closest distance so far (shadow rays: the distance to the light).
+// Per lane, early out: u, v and t are meaningful only where the test returns true.
+RTX_D bool tri_test(const v3 p0, const v3 edge_1, const v3 edge_2, const v3 co, const v3 cd, const float tmax, float & t, float & u, float & v) {
+    const v3 h = vcross(cd, edge_2);
+    const float a = vdot(edge_1, h);
+    const float f = 1.0f / a;
+    const v3 s = vsub(co, p0);
+    u = f * vdot(s, h);
+    if (!((u > 0.0f) & (u < 1.0f))) return false;
+    const v3 qq = vcross(s, edge_1);
+    v = f * vdot(cd, qq);
+    if (!((v > 0.0f) & ((u + v) < 1.0f))) return false;
+    t = f * vdot(edge_2, qq);
+    return (t > RAY_EPSILON) & (t < tmax);
+}
+// Branch-free, for a wave that tests one triangle (in SGPRs) for all its lanes and ballots the result: the same values, every one computed.
+RTX_D bool tri_test_all(const v3 p0, const v3 edge_1, const v3 edge_2, const v3 co, const v3 cd, const float tmax, float & t, float & u, float & v) {
+    const v3 h = vcross(cd, edge_2);
+    const float a = vdot(edge_1, h);
+    const float f = 1.0f / a;
+    const v3 s = vsub(co, p0);
+    u = f * vdot(s, h);
+    const v3 qq = vcross(s, edge_1);
+    v = f * vdot(cd, qq);
+    t = f * vdot(edge_2, qq);
+    return (u > 0.0f) & (u < 1.0f) & (v > 0.0f) & ((u + v) < 1.0f) & (t > RAY_EPSILON) & (t < tmax);
+}
+RTX_D v3 v3q(const float4 q) { return V3(q.x, q.y, q.z); }          // a triangle record's quad as loaded: gld, sld, or (three words) gld3
+RTX_D v3 v3q(const float3 q) { return V3(q.x, q.y, q.z); }
 
 // Shadow queue of a level: one slot per ray of the level and light (slot = the ray's own index: k_shade does not compact), of which
 // only the rays with a lit hit carry a shadow ray — NF_LIT in the node record k_shade wrote.
@@ -335,6 +383,31 @@ RTX_D uint32_t shadow_slots(const DevCounters * ctr, const DevQueues & q, int le
 }
 RTX_D bool shadow_slot_is_lit(const DevQueues & q, int level, uint32_t rank) {
     return (as_i(q.n0[(uint32_t)q.level_base[level] + rank].w) & NF_LIT) != 0;
+}
+// The ray k_shade (or the fused packet kernel) queued in `slot` of a level >= 1: origin and direction; false = the slot holds no ray (the
+// unused tail of a wave's chunk, RAY_DEAD_PIXEL), which every consumer treats like a clipped pixel.
+RTX_D bool queued_ray(const DevQueues & q, const uint32_t slot, v3 & wo, v3 & wd) {
+    const float4 r0 = q.r0[slot], r1 = q.r1[slot];
+    wo = V3(r0.x, r0.y, r0.z); wd = V3(r0.w, r1.x, r1.y);
+    return as_i(r1.z) != RAY_DEAD_PIXEL;
+}
+// Refill of the per-lane kernels: the queue index of this lane for the wave's idle lanes (ballot `idle`); sets `exhausted` once the queue
+// holds nothing beyond this round.  Round one is a static assignment (thread i takes ray i): the queue head was initialised to the grid
+// size by k_begin_batch, so a launch with fewer rays than resident lanes performs no atomic at all.  Later rounds: one atomicAdd by the
+// first idle lane, a popcount-prefix rank per lane.
+RTX_D uint32_t refill_index(const unsigned long long idle, const int lane, const uint32_t gtid, const uint32_t total, uint32_t * const head, bool & first_round, bool & exhausted) {
+    if (first_round) {
+        first_round = false;
+        if ((uint32_t)(gridDim.x * blockDim.x) >= total) exhausted = true;
+        return gtid;
+    }
+    const uint32_t n_idle = (uint32_t)__popcll(idle);
+    const int leader = __ffsll((long long)idle) - 1;
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(head, n_idle);
+    base = __shfl(base, leader);
+    if (base + n_idle >= total) exhausted = true;
+    return base + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
 }
 
 template <bool ANY, bool COUNT, int VIEWS = 0>
@@ -384,21 +457,7 @@ void k_trace(const DevScene sc, const DevQueues q, const int level) {
         const unsigned long long idle = __ballot(!has_ray);
         const int n_idle = __popcll(idle);
         if (!exhausted && n_idle >= RTX_REFILL_MIN) {
-            uint32_t idx;
-            if (first_round) {
-                // round one is a static assignment (thread i takes ray i): the queue head was initialised to the grid size
-                // by k_begin_batch, so a launch with fewer rays than resident lanes performs no atomic at all
-                first_round = false;
-                idx = (uint32_t)gtid;
-                if ((uint32_t)(gridDim.x * blockDim.x) >= total) exhausted = true;
-            } else {
-                const int leader = __ffsll((long long)idle) - 1;
-                uint32_t base = 0;
-                if (lane == leader) base = atomicAdd(head, (uint32_t)n_idle);
-                base = __shfl(base, leader);
-                if (base + (uint32_t)n_idle >= total) exhausted = true;
-                idx = base + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-            }
+            const uint32_t idx = refill_index(idle, lane, (uint32_t)gtid, total, head, first_round, exhausted);
             if (!has_ray && idx < total) {
                 bool live = true;
                 if (ANY) {
@@ -414,28 +473,14 @@ void k_trace(const DevScene sc, const DevQueues q, const int level) {
                         live = primary_pixel_v<VIEWS, false>(sc, q, idx, px, py, view);
                         RayFull r;
                         if (live) { primary_ray_v<VIEWS>(sc, q, view, px, py, r, false); wo = r.o; wd = r.d; }
-                    } else {
-                        const float4 r0 = q.r0[out_slot], r1 = q.r1[out_slot];
-                        wo = V3(r0.x, r0.y, r0.z); wd = V3(r0.w, r1.x, r1.y);
-                        live = as_i(r1.z) != RAY_DEAD_PIXEL;          // unused slot of a wave's chunk (fused shading of the level above)
-                    }
+                    } else live = queued_ray(q, out_slot, wo, wd);
                     tcur = INFINITY;
                     best_prim = PRIM_NONE; best_tri = 0; best_u = 0.0f; best_v = 0.0f; bvh_steps = 0;
                 }
                 if (live) {
                     if (COUNT) n_rays++;
-                    bool done = false;
                     // Scene::trace_primitives / intersect_primitives: spheres, then planes, then the TLAS (Scene.cpp:173-190)
-                    for (int i = 0; i < sc.sphere_count; i++) {
-                        if (ANY) { if (sphere_any(sc.spheres[i], wo, wd, tcur)) { done = true; break; } }
-                        else { float t; if (sphere_closest(sc.spheres[i], wo, wd, tcur, t)) { tcur = t; best_prim = PRIM_SPHERE | i; } }
-                    }
-                    if (!done) for (int i = 0; i < sc.plane_count; i++) {
-                        const float t = plane_t(sc.planes[i], wo, wd);
-                        if (ANY) { if ((t > RAY_EPSILON) & (t < tcur)) { done = true; break; } }
-                        else if ((t > RAY_EPSILON) & (t < tcur)) { tcur = t; best_prim = PRIM_PLANE | i; }
-                    }
-                    if (ANY && done) {
+                    if (world_primitives<ANY>(sc, wo, wd, tcur, best_prim)) {
                         q.socc[out_slot] = 1u;
                     } else if (sc.tlas_node_count > 0) {
                         winv = vrcp(wd);
@@ -496,18 +541,8 @@ void k_trace(const DevScene sc, const DevQueues q, const int level) {
                     for (int i = first; i < first + cnt; i++) {
                         if (COUNT) n_tri++;
                         const float4 p0 = gld(cur_tris, RTX_TRI_STRIDE * i), e1 = gld(cur_tris, RTX_TRI_STRIDE * i + 1), e2 = gld(cur_tris, RTX_TRI_STRIDE * i + 2);
-                        const v3 edge_1 = V3(e1.x, e1.y, e1.z), edge_2 = V3(e2.x, e2.y, e2.z);
-                        const v3 h = vcross(cd, edge_2);
-                        const float a = vdot(edge_1, h);
-                        const float f = 1.0f / a;
-                        const v3 s = vsub(co, V3(p0.x, p0.y, p0.z));
-                        const float u = f * vdot(s, h);
-                        if (!((u > 0.0f) & (u < 1.0f))) continue;
-                        const v3 qq = vcross(s, edge_1);
-                        const float v = f * vdot(cd, qq);
-                        if (!((v > 0.0f) & ((u + v) < 1.0f))) continue;
-                        const float t = f * vdot(edge_2, qq);
-                        if (!((t > RAY_EPSILON) & (t < tcur))) continue;
+                        float t, u, v;
+                        if (!tri_test(v3q(p0), v3q(e1), v3q(e2), co, cd, tcur, t, u, v)) continue;
                         if (ANY) { q.socc[out_slot] = 1u; has_ray = false; break; }
                         tcur = t; best_u = u; best_v = v; best_tri = i; best_prim = PRIM_TRI | cur_inst;
                     }
@@ -624,21 +659,7 @@ void k_trace_fast(const DevScene sc, const DevQueues q, const int level, const i
         const unsigned long long idle = __ballot(!has_ray);
         const int n_idle = __popcll(idle);
         if (!exhausted && n_idle >= RTX_REFILL_MIN) {
-            uint32_t idx;
-            if (first_round) {
-                // round one is a static assignment (thread i takes ray i): the queue head was initialised to the grid size
-                // by k_begin_batch, so a launch with fewer rays than resident lanes performs no atomic at all
-                first_round = false;
-                idx = (uint32_t)gtid;
-                if ((uint32_t)(gridDim.x * blockDim.x) >= total) exhausted = true;
-            } else {
-                const int leader = __ffsll((long long)idle) - 1;
-                uint32_t base = 0;
-                if (lane == leader) base = atomicAdd(head, (uint32_t)n_idle);
-                base = __shfl(base, leader);
-                if (base + (uint32_t)n_idle >= total) exhausted = true;
-                idx = base + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-            }
+            const uint32_t idx = refill_index(idle, lane, (uint32_t)gtid, total, head, first_round, exhausted);
             if (!has_ray && idx < total) {
                 bool live = true;
                 if (ANY) {
@@ -657,26 +678,12 @@ void k_trace_fast(const DevScene sc, const DevQueues q, const int level, const i
                         live = primary_pixel_v<VIEWS, false>(sc, q, idx, px, py, view);
                         RayFull r;
                         if (live) { primary_ray_v<VIEWS>(sc, q, view, px, py, r, false); wo = r.o; wd = r.d; }
-                    } else {
-                        const float4 r0 = q.r0[out_slot], r1 = q.r1[out_slot];
-                        wo = V3(r0.x, r0.y, r0.z); wd = V3(r0.w, r1.x, r1.y);
-                        live = as_i(r1.z) != RAY_DEAD_PIXEL;
-                    }
+                    } else live = queued_ray(q, out_slot, wo, wd);
                     tcur = INFINITY;
                     best_prim = PRIM_NONE; best_tri = 0; best_u = 0.0f; best_v = 0.0f;
                 }
                 if (live) {
-                    bool done = false;
-                    for (int i = 0; i < sc.sphere_count; i++) {
-                        if (ANY) { if (sphere_any(sc.spheres[i], wo, wd, tcur)) { done = true; break; } }
-                        else { float t; if (sphere_closest(sc.spheres[i], wo, wd, tcur, t)) { tcur = t; best_prim = PRIM_SPHERE | i; } }
-                    }
-                    if (!done) for (int i = 0; i < sc.plane_count; i++) {
-                        const float t = plane_t(sc.planes[i], wo, wd);
-                        if (ANY) { if ((t > RAY_EPSILON) & (t < tcur)) { done = true; break; } }
-                        else if ((t > RAY_EPSILON) & (t < tcur)) { tcur = t; best_prim = PRIM_PLANE | i; }
-                    }
-                    if (ANY && done) {
+                    if (world_primitives<ANY>(sc, wo, wd, tcur, best_prim)) {
                         q.socc[out_slot] = 1u;
                     } else if (sc.tlas_node_count > 0) {
                         winv = vrcp(wd);
@@ -732,11 +739,8 @@ void k_trace_fast(const DevScene sc, const DevQueues q, const int level, const i
                     if (p_far) {
                         // the far child's (first, count) travel on the stack, so the pop needs no memory access: shadow rays never
                         // re-test it (their max distance is constant); closest-hit rays re-test it with its key (slab_test_key)
-                        const int far_leaf = far_cnt & 0x3fffffff;
                         const float far_key = left_first ? kr : kl;
-                        if ((uint32_t)far_first < (1u << 24) && far_leaf < 16)
-                            push((int)(0x40000000u | (((uint32_t)far_cnt >> 30) << 28) | ((uint32_t)far_leaf << 24) | (uint32_t)far_first), far_key);
-                        else push(left_first ? left + 1 : left, far_key);
+                        push(rtxl::ref_fits((uint32_t)far_first, (uint32_t)far_cnt) ? rtxl::ref_pack((uint32_t)far_first, (uint32_t)far_cnt) : (left_first ? left + 1 : left), far_key);
                     }
                     cur_first = near_first; cur_cnt = near_cnt;
                 } else if (p_far) {
@@ -751,18 +755,8 @@ void k_trace_fast(const DevScene sc, const DevQueues q, const int level, const i
                 if (floor_sp >= 0) {
                     for (int i = first; i < first + cnt; i++) {
                         const float4 p0 = gld(cur_tris, RTX_TRI_STRIDE * i), e1 = gld(cur_tris, RTX_TRI_STRIDE * i + 1), e2 = gld(cur_tris, RTX_TRI_STRIDE * i + 2);
-                        const v3 edge_1 = V3(e1.x, e1.y, e1.z), edge_2 = V3(e2.x, e2.y, e2.z);
-                        const v3 h = vcross(cd, edge_2);
-                        const float a = vdot(edge_1, h);
-                        const float f = 1.0f / a;
-                        const v3 s = vsub(co, V3(p0.x, p0.y, p0.z));
-                        const float u = f * vdot(s, h);
-                        if (!((u > 0.0f) & (u < 1.0f))) continue;
-                        const v3 qq = vcross(s, edge_1);
-                        const float v = f * vdot(cd, qq);
-                        if (!((v > 0.0f) & ((u + v) < 1.0f))) continue;
-                        const float t = f * vdot(edge_2, qq);
-                        if (!((t > RAY_EPSILON) & (t < tcur))) continue;
+                        float t, u, v;
+                        if (!tri_test(v3q(p0), v3q(e1), v3q(e2), co, cd, tcur, t, u, v)) continue;
                         if (ANY) { q.socc[out_slot] = 1u; has_ray = false; break; }
                         tcur = t; best_u = u; best_v = v; best_tri = i; best_prim = PRIM_TRI | cur_inst;
                     }
@@ -790,10 +784,8 @@ void k_trace_fast(const DevScene sc, const DevQueues q, const int level, const i
                     if (slab_test(na, nb, co, cinv, tcur)) { cur_first = as_i(na.w); cur_cnt = as_i(nb.w); have_cur = true; }
                 } else if (ANY || key < tcur) {
                     // far child: the reference tests it now, against the current closest distance == `key < tcur` (slab_test_key)
-                    if (e & 0x40000000) {
-                        cur_first = e & 0x00ffffff;
-                        cur_cnt = (int)((((uint32_t)e >> 28) & 3u) << 30) | ((e >> 24) & 15);
-                    } else {
+                    if (rtxl::ref_is_packed(e)) { cur_first = rtxl::ref_first(e); cur_cnt = rtxl::ref_count_word(e); }
+                    else {
                         const float4 na = gld(cur_nodes, 2 * e), nb = gld(cur_nodes, 2 * e + 1);   // too big to pack: read (first, count) back
                         cur_first = as_i(na.w); cur_cnt = as_i(nb.w);
                     }
