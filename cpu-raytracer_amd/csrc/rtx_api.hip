@@ -31,6 +31,7 @@
 #include "rtx_update.h"
 #include "rtx_refit.h"
 #include "rtx_build.h"
+#include "rtx_normals.h"
 #include "rtx_query.h"
 #include "rtx_texmip.h"
 #include <rocprim/device/device_radix_sort.hpp>      // rtx_update_instances, scenes beyond one workgroup: header-only, part of ROCm
@@ -77,7 +78,10 @@ struct rtx_ctx {
     struct BlasBuild { bool allocated = false; DevBuf block; DevBuild dev; void * sort_tmp = nullptr; size_t sort_bytes = 0; int levels = 0; };
     // max_local_material, inner_depth: for validate_references(), which checks every id a kernel will follow on the host before anything is
     // launched; packet_ok: the tree fits the packet kernels' packed entries (plan_stack_limits)
-    struct BlasHost { std::vector<DevBuf> arrays; int max_local_material = -1, inner_depth = -1; bool packet_ok = true; BlasRefit refit; BlasBuild build; };
+    // rtx_alloc_blas_topology / rtx_set_blas_topology / rtx_blas_vertex_normals: the block of the vertex normals' buffers and the kernel
+    // arguments that point into it; set: a topology has been queued since the alloc
+    struct BlasNormals { bool allocated = false, set = false; DevBuf block; DevNormals dev; void * sort_tmp = nullptr; size_t sort_bytes = 0; unsigned int key_bits = 0; };
+    struct BlasHost { std::vector<DevBuf> arrays; int max_local_material = -1, inner_depth = -1; bool packet_ok = true; BlasRefit refit; BlasBuild build; BlasNormals normals; };
     std::vector<DevBlas> h_blas;
     std::vector<BlasHost> blas;
     DevBuf d_blas, d_materials, d_textures, d_sky, d_ewa;
@@ -998,6 +1002,69 @@ extern "C" int rtx_build_blas(rtx_ctx * c, int32_t blas_id, const void * positio
         launch_timed(c, "k_build_level", c->stream, [&] { hipLaunchKernelGGL(k_build_level, dim3(((1 << d) + RTX_BUILD_BLOCK - 1) / RTX_BUILD_BLOCK), dim3(RTX_BUILD_BLOCK), 0, c->stream, r, d); });
     launch_timed(c, "k_build_top", c->stream, [&] { hipLaunchKernelGGL(k_build_top, dim3(1), dim3(RTX_BUILD_TOP_BLOCK), 0, c->stream, r, U.levels); });
     return refit_launch_finish(c, R, true);
+}
+
+// ---- device-side vertex normals (include/rtx.h: rtx_alloc_blas_topology / rtx_set_blas_topology / rtx_blas_vertex_normals; kernels in
+// rtx_normals.h) -------------------------------------------------------------------------------------------------------------------------
+// The state lives in the id's host record, so whatever replaces the record (rtx_upload_blas, rtx_alloc_blas: commit_blas) drops it.  The
+// alloc stages its block and swaps it in after waiting for the stream; the other two calls are queued like a refit and read nothing back.
+extern "C" int rtx_alloc_blas_topology(rtx_ctx * c, int32_t blas_id, int32_t triangle_count, int32_t vertex_count) {
+    if (!c) return RTX_ERR_INVALID_ARG;
+    if (blas_id < 0 || blas_id >= (1 << 20) || triangle_count < 1 || vertex_count < 1) { c->err = "rtx_alloc_blas_topology: bad id, no triangles or no vertices"; return RTX_ERR_INVALID_ARG; }
+    if (triangle_count > RTX_NORMALS_MAX_TRIANGLES) { c->err = "rtx_alloc_blas_topology supports at most 2^28 triangles (32-bit corner indices)"; return RTX_ERR_LIMIT; }
+    if ((size_t)blas_id >= c->h_blas.size() || !c->h_blas[blas_id].nodes) { c->err = "rtx_alloc_blas_topology: no BLAS uploaded or allocated under that id"; return RTX_ERR_STATE; }
+    hipSetDevice(c->cfg.device);
+    const size_t T = (size_t)triangle_count, V = (size_t)vertex_count;
+    rtx_ctx::BlasNormals N;
+    N.key_bits = rtxn::key_bits(vertex_count);
+    if (int rc = sort_storage_bytes<uint64_t>(c, 3 * T, N.key_bits, N.sort_bytes)) return rc;
+    // [indices][unsorted keys][sorted keys][sort storage][offsets][face vectors], every part 256-byte aligned
+    const size_t len[6] = { T * 12, 3 * T * 8, 3 * T * 8, N.sort_bytes, (V + 1) * 4, T * 16 };
+    size_t off[6];
+    if (int rc = ensure(c, N.block, aligned_parts(len, off, 6))) return rc;
+    char * const bb = (char *)N.block.p;
+    memset(&N.dev, 0, sizeof(N.dev));
+    N.dev.indices = (int32_t *)(bb + off[0]); N.dev.keys_in = (uint64_t *)(bb + off[1]); N.dev.keys = (uint64_t *)(bb + off[2]);
+    N.sort_tmp = bb + off[3]; N.dev.offset = (uint32_t *)(bb + off[4]); N.dev.face = (float4 *)(bb + off[5]);
+    N.dev.tri_count = triangle_count; N.dev.vertex_count = vertex_count;
+    N.allocated = true;
+    HIP_OK(c, hipStreamSynchronize(c->stream));                    // queued normals still read the block this call replaces
+    c->blas[blas_id].normals = std::move(N);
+    return RTX_OK;
+}
+
+extern "C" int rtx_set_blas_topology(rtx_ctx * c, int32_t blas_id, const void * indices_dev) {
+    if (!c) return RTX_ERR_INVALID_ARG;
+    if (!indices_dev || ((uintptr_t)indices_dev & 3)) { c->err = "rtx_set_blas_topology: null or misaligned index pointer"; return RTX_ERR_INVALID_ARG; }
+    if (blas_id < 0 || (size_t)blas_id >= c->blas.size() || !c->blas[blas_id].normals.allocated) { c->err = "rtx_set_blas_topology: no topology allocated under that id (rtx_alloc_blas_topology)"; return RTX_ERR_STATE; }
+    hipSetDevice(c->cfg.device);
+    rtx_ctx::BlasNormals & N = c->blas[blas_id].normals;
+    DevNormals & d = N.dev;
+    d.indices_src = (const int32_t *)indices_dev;
+    const uint32_t corners = 3u * (uint32_t)d.tri_count;
+    launch_timed(c, "k_normals_keys", c->stream, [&] { hipLaunchKernelGGL(k_normals_keys, dim3((corners + RTX_NORMALS_BLOCK - 1) / RTX_NORMALS_BLOCK), dim3(RTX_NORMALS_BLOCK), 0, c->stream, d); });
+    hipError_t se = hipSuccess;
+    launch_timed(c, "normals_radix_sort", c->stream, [&] { size_t bytes = N.sort_bytes; se = rocprim::radix_sort_keys(N.sort_tmp, bytes, (const uint64_t *)d.keys_in, d.keys, (unsigned int)corners, 0u, N.key_bits, c->stream); });
+    if (se != hipSuccess) return sort_failed(c, se);
+    launch_timed(c, "k_normals_offsets", c->stream, [&] { hipLaunchKernelGGL(k_normals_offsets, dim3(((uint32_t)d.vertex_count + 1 + RTX_NORMALS_BLOCK - 1) / RTX_NORMALS_BLOCK), dim3(RTX_NORMALS_BLOCK), 0, c->stream, d); });
+    HIP_OK(c, hipGetLastError());
+    N.set = true;
+    return RTX_OK;
+}
+
+extern "C" int rtx_blas_vertex_normals(rtx_ctx * c, int32_t blas_id, const void * positions_dev, void * normals_out_dev) {
+    if (!c) return RTX_ERR_INVALID_ARG;
+    if (!positions_dev || !normals_out_dev || (((uintptr_t)positions_dev | (uintptr_t)normals_out_dev) & 3)) { c->err = "rtx_blas_vertex_normals: null or misaligned pointer"; return RTX_ERR_INVALID_ARG; }
+    if (blas_id < 0 || (size_t)blas_id >= c->blas.size() || !c->blas[blas_id].normals.allocated) { c->err = "rtx_blas_vertex_normals: no topology allocated under that id (rtx_alloc_blas_topology)"; return RTX_ERR_STATE; }
+    rtx_ctx::BlasNormals & N = c->blas[blas_id].normals;
+    if (!N.set) { c->err = "rtx_blas_vertex_normals: no topology set since the alloc (rtx_set_blas_topology)"; return RTX_ERR_STATE; }
+    hipSetDevice(c->cfg.device);
+    DevNormals & d = N.dev;
+    d.positions = (const float *)positions_dev; d.normals_out = (float *)normals_out_dev;
+    launch_timed(c, "k_normals_faces", c->stream, [&] { hipLaunchKernelGGL(k_normals_faces, dim3(((uint32_t)d.tri_count + RTX_NORMALS_BLOCK - 1) / RTX_NORMALS_BLOCK), dim3(RTX_NORMALS_BLOCK), 0, c->stream, d); });
+    launch_timed(c, "k_normals_sum", c->stream, [&] { hipLaunchKernelGGL(k_normals_sum, dim3(((uint32_t)d.vertex_count + RTX_NORMALS_BLOCK - 1) / RTX_NORMALS_BLOCK), dim3(RTX_NORMALS_BLOCK), 0, c->stream, d); });
+    HIP_OK(c, hipGetLastError());
+    return RTX_OK;
 }
 
 extern "C" int rtx_read_blas(rtx_ctx * c, int32_t blas_id, rtx_bvh_node * nodes, rtx_triangle_hot * hot, rtx_triangle_cold * cold) {

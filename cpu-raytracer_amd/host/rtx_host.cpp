@@ -8,6 +8,7 @@
 #include "../csrc/rtx_update_math.h"
 #include "../csrc/rtx_refit_math.h"
 #include "../csrc/rtx_build_math.h"
+#include "../csrc/rtx_normals_math.h"
 #include "../csrc/rtx_texmip_math.h"
 #include "../csrc/rtx_query_sort_math.h"
 
@@ -829,6 +830,22 @@ extern "C" int rtxh_bvh_cache_free(rtxh_bvh_cache * c) {
     if (!c) return RTX_ERR_INVALID_ARG;
     free(c->hot); free(c->cold); free(c->nodes); free(c->indices);
     memset(c, 0, sizeof(*c));
+    return RTX_OK;
+}
+
+// ---- rtx_blas_vertex_normals on the host: csrc/rtx_normals_math.h driven the OTHER way round — the device gathers per vertex through a sorted
+// inverted index, this is the plain scatter loop over triangles and corners.  Both add a vertex's face vectors in ascending corner order.
+extern "C" int rtxh_vertex_normals(const float * positions, const int32_t * indices, int32_t triangle_count, int32_t vertex_count, float * normals_out) {
+    if (!positions || !indices || !normals_out || triangle_count < 1 || vertex_count < 1) return RTX_ERR_INVALID_ARG;
+    std::vector<float> acc((size_t)3 * vertex_count, 0.0f);
+    for (int32_t t = 0; t < triangle_count; t++) {
+        const int32_t * const tri = indices + 3 * (size_t)t;
+        if (!rtxn::valid_triangle(tri[0], tri[1], tri[2], vertex_count)) continue;
+        float f[3];
+        rtxn::face_vector(positions + 3 * (size_t)tri[0], positions + 3 * (size_t)tri[1], positions + 3 * (size_t)tri[2], f);
+        for (int k = 0; k < 3; k++) for (int a = 0; a < 3; a++) acc[3 * (size_t)tri[k] + a] += f[a];
+    }
+    for (int32_t v = 0; v < vertex_count; v++) rtxn::normalise(&acc[3 * (size_t)v], normals_out + 3 * (size_t)v);
     return RTX_OK;
 }
 

@@ -27,7 +27,8 @@ EXPORTS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error", "rt
            "rtx_set_rays", "rtx_bind_rays", "rtx_render_rays", "rtx_update_instances", "rtx_read_frame_state",
            "rtx_bind_blas_vertices", "rtx_refit_blas", "rtx_read_blas", "rtx_alloc_blas", "rtx_build_blas",
            "rtx_query_closest", "rtx_query_occluded", "rtx_debug_query_order", "rtx_debug_read_layouts",
-           "rtx_alloc_texture", "rtx_update_texture", "rtx_read_texture", "rtx_update_sky"]
+           "rtx_alloc_texture", "rtx_update_texture", "rtx_read_texture", "rtx_update_sky",
+           "rtx_alloc_blas_topology", "rtx_set_blas_topology", "rtx_blas_vertex_normals"]
 # newer than the A/B variants tools/ab.py may load (RTX_HIP_LIB = a library built from an older commit): bound when the library has them,
 # otherwise a call raises AttributeError (undefined symbol)
 VIEW_EXPORTS = ("rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer")
@@ -40,10 +41,12 @@ QUERY_EXPORTS = ("rtx_query_closest", "rtx_query_occluded")
 QUERY_SORT_EXPORTS = ("rtx_debug_query_order",)
 LAYOUT_EXPORTS = ("rtx_debug_read_layouts",)
 TEXTURE_EXPORTS = ("rtx_alloc_texture", "rtx_update_texture", "rtx_read_texture", "rtx_update_sky")
+NORMALS_EXPORTS = ("rtx_alloc_blas_topology", "rtx_set_blas_topology", "rtx_blas_vertex_normals")
 # texel formats of rtx_update_texture (include/rtx.h RTX_TEXELS_*)
 RTX_TEXELS_RGB_F32 = 0
 RTX_TEXELS_RGBA8_SRGB = 1
 RTX_UPDATE_MAX_INSTANCES = 65536
+RTX_ERR_STATE = 5
 
 RTX_RENDER_COUNT_WORK = 1
 RTX_RENDER_SIMPLE_TRACE = 2
@@ -169,8 +172,12 @@ def load_library(path: Optional[str] = None):
         lib.rtx_update_texture.argtypes = [vp, i32, vp, i32]
         lib.rtx_read_texture.argtypes = [vp, i32, C.POINTER(RtxTextureDesc), vp, C.c_int64]
         lib.rtx_update_sky.argtypes = [vp, vp, i32]
+    if hasattr(lib, "rtx_blas_vertex_normals"):
+        lib.rtx_alloc_blas_topology.argtypes = [vp, i32, i32, i32]
+        lib.rtx_set_blas_topology.argtypes = [vp, i32, vp]
+        lib.rtx_blas_vertex_normals.argtypes = [vp, i32, vp, vp]
     for name in EXPORTS:
-        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + QUERY_SORT_EXPORTS + LAYOUT_EXPORTS + TEXTURE_EXPORTS and not hasattr(lib, name):
+        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + QUERY_SORT_EXPORTS + LAYOUT_EXPORTS + TEXTURE_EXPORTS + NORMALS_EXPORTS and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         if name not in ("rtx_last_error",):
@@ -839,6 +846,63 @@ class Renderer:
         else:
             ptrs = [int(t) if t else None for _, t, _, _ in args]
         self._chk(self.lib.rtx_build_blas(self.ctx, int(blas_id), *ptrs), "rtx_build_blas")
+
+    # ---- device-side vertex normals (include/rtx.h: rtx_alloc_blas_topology / rtx_set_blas_topology / rtx_blas_vertex_normals) ----------
+    def _normals_tensor(self, name: str, t, dtype: str, rows: Optional[int] = None, letter: str = "V"):
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor, not {type(t).__name__}")
+        if t.dtype != getattr(torch, dtype):
+            raise TypeError(f"{name} must be torch.{dtype}, not {t.dtype}")
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{name} must have shape ({letter}, 3), not {tuple(t.shape)}")
+        if rows is not None and t.shape[0] != rows:
+            raise ValueError(f"{name} holds {t.shape[0]} rows, set_blas_topology was given {rows}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if t.device.type != "cuda" or t.device.index != self.device:
+            raise ValueError(f"{name} must be on cuda:{self.device} (this context's GPU), not {t.device}")
+
+    def set_blas_topology(self, blas_id: int, indices, vertex_count: int):
+        """The SOURCE index buffer of the mesh under blas_id, for vertex_normals: indices (T, 3) int32 torch tensor on this context's GPU
+        over vertex_count vertices; a triangle with an index outside [0, vertex_count) is invalid and contributes to no vertex (-1 pads).
+        Once for a refitted mesh, every step for a rebuilt one.  The first call for an id, or one with other counts, allocates (and may
+        wait); otherwise the inverted index is rebuilt on the context's stream and nothing is read back.  The tensor is read when the
+        work runs and must stay alive until then."""
+        self._normals_tensor("indices", indices, "int32", letter="T")
+        T, V = int(indices.shape[0]), int(vertex_count)
+        if T < 1 or V < 1:
+            raise ValueError(f"indices must hold at least one triangle and vertex_count must be at least 1, not {T} and {V}")
+        shapes = self.__dict__.setdefault("_topology_shapes", {})
+        rc = RTX_ERR_STATE
+        if shapes.get(int(blas_id)) == (T, V):       # an upload or alloc_blas over the id has dropped the topology: RTX_ERR_STATE, allocate again
+            rc = self.lib.rtx_set_blas_topology(self.ctx, int(blas_id), indices.data_ptr())
+        if rc == RTX_ERR_STATE:
+            shapes.pop(int(blas_id), None)
+            self.__dict__.setdefault("_normals_out", {}).pop(int(blas_id), None)
+            self._chk(self.lib.rtx_alloc_blas_topology(self.ctx, int(blas_id), T, V), "rtx_alloc_blas_topology")
+            shapes[int(blas_id)] = (T, V)
+            rc = self.lib.rtx_set_blas_topology(self.ctx, int(blas_id), indices.data_ptr())
+        self._chk(rc, "rtx_set_blas_topology")
+
+    def vertex_normals(self, blas_id: int, positions, out=None):
+        """Smooth, area-weighted vertex normals of the topology set under blas_id at the positions (V, 3) float32 torch tensor on this
+        context's GPU, written to out (V, 3) float32 — None: a tensor this Renderer owns per id, made once and reused — and returned, so
+        that r.refit_blas(i, pos, r.vertex_normals(i, pos)) is the whole step.  Bit-reproducible and bit-identical to host.vertex_normals;
+        a vertex no valid triangle uses, or whose face vectors cancel, gets (0, 0, 0).  Ordered on the context's stream; nothing is read
+        back.  The tensors are read and written when the work runs and must stay alive until then.  Returns at once."""
+        T, V = getattr(self, "_topology_shapes", {}).get(int(blas_id), (None, None))
+        self._normals_tensor("positions", positions, "float32", V)
+        if out is None:
+            import torch
+            owned = self.__dict__.setdefault("_normals_out", {})
+            out = owned.get(int(blas_id))
+            if out is None or out.shape != positions.shape:
+                out = owned[int(blas_id)] = torch.empty_like(positions)
+        else:
+            self._normals_tensor("out", out, "float32", int(positions.shape[0]))
+        self._chk(self.lib.rtx_blas_vertex_normals(self.ctx, int(blas_id), positions.data_ptr(), out.data_ptr()), "rtx_blas_vertex_normals")
+        return out
 
     def read_blas(self, blas_id: int) -> sio.Blas:
         """The BLAS arrays the kernels currently read (waits for the stream): after upload what was uploaded, after refit_blas what the device

@@ -22,7 +22,7 @@ EXPORTS = ["rtxh_camera_basis", "rtxh_camera_update", "rtxh_quaternion_axis_angl
            "rtxh_tlas_build", "rtxh_blas_build", "rtxh_blas_build_reference_bvh", "rtxh_blas_build_reference_sbvh", "rtxh_texture_mips", "rtxh_query_sort_order", "rtxh_texture_load", "rtxh_texture_free", "rtxh_sky_load", "rtxh_image_load", "rtxh_image_free", "rtxh_image_save_png", "rtxh_atrium_generate", "rtxh_mesh_free",
            "rtxh_obj_load", "rtxh_obj_free", "rtxh_mtl_load", "rtxh_bvh_cache_load", "rtxh_bvh_cache_save", "rtxh_bvh_cache_free",
            "rtxh_tlas_build_balanced", "rtxh_scene_update_balanced", "rtxh_tlas_balanced_node_count", "rtxh_tlas_balanced_inner_depth", "rtxh_blas_refit",
-           "rtxh_blas_build_balanced", "rtxh_blas_balanced_node_count", "rtxh_blas_balanced_inner_depth"]
+           "rtxh_blas_build_balanced", "rtxh_blas_balanced_node_count", "rtxh_blas_balanced_inner_depth", "rtxh_vertex_normals"]
 
 PI = np.float32(3.14159265359)          # Util.h:8
 
@@ -90,6 +90,7 @@ def lib():
         l.rtxh_blas_build_balanced.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, C.POINTER(i32), vp, vp, vp, vp]
         l.rtxh_blas_balanced_node_count.argtypes = [i32]
         l.rtxh_blas_balanced_inner_depth.argtypes = [i32]
+        l.rtxh_vertex_normals.argtypes = [vp, vp, i32, i32, vp]
         for n in EXPORTS:
             getattr(l, n).restype = C.c_int
         _lib = l
@@ -334,6 +335,18 @@ def blas_refit(blas: sio.Blas, slot_vertices: np.ndarray, positions: np.ndarray,
     if rc:
         raise ValueError(f"rtxh_blas_refit failed with status {rc}")
     return sio.Blas(nodes, hot, cold, blas.material_offset, blas.source_triangle_count, blas.order)
+
+
+def vertex_normals(positions, indices) -> np.ndarray:
+    """rtxh_vertex_normals: the smooth, area-weighted vertex normals (V, 3) that Renderer.vertex_normals writes on the device, from positions
+    (V, 3) and indices (T, 3); a triangle with an index outside [0, V) contributes nothing."""
+    pos = _f32(positions).reshape(-1, 3)
+    idx = np.ascontiguousarray(indices, np.int32).reshape(-1, 3)
+    out = np.zeros((len(pos), 3), np.float32)
+    rc = lib().rtxh_vertex_normals(pos.ctypes.data, idx.ctypes.data, len(idx), len(pos), out.ctypes.data)
+    if rc:
+        raise ValueError(f"rtxh_vertex_normals failed with status {rc}")
+    return out
 
 
 def blas_balanced_node_count(n: int) -> int:

@@ -481,8 +481,8 @@ int rtx_read_frame_state(rtx_ctx * ctx, rtx_instance * instances, rtx_bvh_node *
  * RTX_GRAPH=1 graphs stay valid (no pointer changes after the bind).  The instances' world boxes and the TLAS are NOT updated by this call:
  * follow with rtx_update_instances or rtx_set_frame when the root box moved.  Checked in this order, nothing changes on an error:
  * RTX_ERR_INVALID_ARG for a null or misaligned positions_dev or a misaligned normals_dev; RTX_ERR_STATE for an id that is not uploaded or
- * not bound; RTX_ERR_INVALID_ARG for a vertex_count that is not the bound one.  Out of scope: normals recomputed from positions (a new
- * topology: rtx_build_blas below), the rtx_group_* path (every rank would have to make the same call).
+ * not bound; RTX_ERR_INVALID_ARG for a vertex_count that is not the bound one.  Normals of the moved vertices: rtx_blas_vertex_normals below; a
+ * new topology: rtx_build_blas below.  Out of scope: the rtx_group_* path (every rank would have to make the same call).
  *
  * rtx_read_blas: what the kernels read now, to host (waits for the stream): node_count nodes in the reference layout, triangle_count hot and
  * cold records as given to rtx_upload_blas.  Any pointer may be NULL.  RTX_ERR_STATE: no BLAS uploaded under that id.                       */
@@ -522,11 +522,55 @@ int rtx_read_blas(rtx_ctx * ctx, int32_t blas_id, rtx_bvh_node * nodes, rtx_tria
  * with rtx_update_instances or rtx_set_frame.  Afterwards the mesh counts as bound for rtx_refit_blas(blas_id, positions, normals,
  * vertex_count), which keeps the topology and axis bits of the last build (the cold record of an invalid triangle stays as the build left it).
  * Checked in this order: RTX_ERR_INVALID_ARG for a null or misaligned positions / indices / normals pointer or a misaligned optional one;
- * RTX_ERR_STATE for an id that was not created by rtx_alloc_blas (or was uploaded again since).  Out of scope: normals computed from
- * positions, per-triangle material ids from device memory, a SAH-quality device builder, the rtx_group_* path.                            */
+ * RTX_ERR_STATE for an id that was not created by rtx_alloc_blas (or was uploaded again since).  Normals from positions: rtx_blas_vertex_normals
+ * below.  Out of scope: per-triangle material ids from device memory, a SAH-quality device builder, the rtx_group_* path.                  */
 int rtx_alloc_blas(rtx_ctx * ctx, int32_t blas_id, int32_t triangle_count, int32_t vertex_count, const int32_t * material_ids_host, int32_t material_offset);
 int rtx_build_blas(rtx_ctx * ctx, int32_t blas_id, const void * positions_dev, const void * indices_dev, const void * normals_dev,
                    const void * texcoords_dev, void * order_out_dev);
+
+/* ---- device-side vertex normals -------------------------------------------------------------------------------------------------------------
+ * A caller with positions and an index buffer in DEVICE memory and no normals (cloth, a skinned character, a learned deformation, an extracted
+ * iso-surface): smooth, area-weighted vertex normals computed on the context's stream into a device buffer that rtx_refit_blas and
+ * rtx_build_blas take as it is.  normals -> refit (or build) -> rtx_update_instances -> render is a complete device-only step.  The result is
+ * bit-reproducible — no float atomics: face vectors are stored, then summed per vertex in a fixed order — and bit-identical to
+ * rtxh_vertex_normals (rtx_host.h), which runs the same arithmetic (csrc/rtx_normals_math.h) as a plain loop over triangles and corners.
+ *   valid     a triangle is valid when its three indices lie in [0, vertex_count) (rtx_build_blas's rule; -1 pads a mesh).  Nothing is read
+ *             through the indices of an invalid triangle, and it contributes to no vertex.
+ *   face      e1 = p1 - p0, e2 = p2 - p0, f = e1 x e2 in unfused fp32: its length is twice the area, so the weighting is by area.  A face
+ *             vector with a NaN or infinite component counts as (+0, +0, +0): a bad vertex spoils its own normal and never a neighbour's.
+ *   sum       from (+0, +0, +0), f added once for every corner c = 3 * t + k that holds the vertex, in ascending c (a triangle that names a
+ *             vertex twice adds its — zero — face vector twice).
+ *   normal    m = max(|x|, |y|, |z|) of the sum.  m zero or not finite (a component of the sum is NaN or infinite): (+0, +0, +0).  Otherwise
+ *             a = s / m, d = a.x * a.x + (a.y * a.y + a.z * a.z), normal = a / sqrtf(d), with correctly rounded '/' and sqrtf: unit length to
+ *             2^-22 at any scale.  A vertex no valid triangle uses and a vertex whose contributions cancel get (+0, +0, +0): there is no
+ *             tie rule beyond that.  No output component is ever NaN or infinite.
+ *
+ * rtx_alloc_blas_topology, once per mesh; may allocate and wait.  Allocates under blas_id everything the other two calls need for
+ * triangle_count triangles over vertex_count vertices: the library's own copy of the indices, unsorted and sorted corner keys (3 *
+ * triangle_count x 8 bytes each), the sort's temporary storage, vertex_count + 1 list offsets and one 16-byte face vector per triangle.  The
+ * counts need not be the BLAS's own: an SBVH's slot table repeats triangles and would weight them twice, so the topology is the SOURCE index
+ * buffer.  Calling it again replaces the state; rtx_upload_blas or rtx_alloc_blas over the id drops it.  Checked in this order, nothing
+ * changes on an error: RTX_ERR_INVALID_ARG for a bad id, triangle_count < 1 or vertex_count < 1; RTX_ERR_LIMIT for triangle_count > 2^28
+ * (corner indices and the sort's count are 32-bit); RTX_ERR_STATE when no BLAS is uploaded or allocated under the id.
+ *
+ * rtx_set_blas_topology, per topology (once for a refitted mesh, every step for a rebuilt one), from DEVICE memory: indices triangle_count x 3
+ * i32 at any 4-byte aligned address, read when the work runs.  Queued on the context's stream (rtx_set_stream: the caller's); never waits,
+ * allocates or reads back.  Copies the indices and builds the inverted index: the key of corner c is (uint64)v << 32 | c, v the vertex at that
+ * corner, v = vertex_count for a corner of an invalid triangle (it sorts last); the keys are sorted (a total order: one result) and offset[v],
+ * v in [0, vertex_count], is the lower bound of v << 32 among them.  RTX_ERR_INVALID_ARG for a null or misaligned pointer; RTX_ERR_STATE for an
+ * id without rtx_alloc_blas_topology.
+ *
+ * rtx_blas_vertex_normals, per step, from DEVICE memory: positions vertex_count x 3 f32 in, normals_out vertex_count x 3 f32 out, caller-owned,
+ * any 4-byte aligned addresses; exactly vertex_count x 12 bytes are written.  Queued like rtx_set_blas_topology; the buffers are read and
+ * written when the work runs, in stream order with a following rtx_refit_blas / rtx_build_blas that reads normals_out.  Any float is a legal
+ * coordinate.  A vertex of high valence (the pole of a UV sphere, the apex of a fan) is summed by one lane: splitting its list would change
+ * the order of the additions and so the bits.  Checked in this order, nothing is queued on an error: RTX_ERR_INVALID_ARG for a null or
+ * misaligned pointer; RTX_ERR_STATE for an id without an allocated topology; RTX_ERR_STATE when no rtx_set_blas_topology has been queued since
+ * the alloc.  Out of scope: angle-weighted or crease-angle normals, flat normals, normals written straight into the cold records, the
+ * rtx_group_* path, texture-space tangents.                                                                                               */
+int rtx_alloc_blas_topology(rtx_ctx * ctx, int32_t blas_id, int32_t triangle_count, int32_t vertex_count);
+int rtx_set_blas_topology(rtx_ctx * ctx, int32_t blas_id, const void * indices_dev);
+int rtx_blas_vertex_normals(rtx_ctx * ctx, int32_t blas_id, const void * positions_dev, void * normals_out_dev);
 
 /* ---- device-side texture and sky update -----------------------------------------------------------------------------------------------
  * What the surfaces look like, with the texels in DEVICE memory: a render shown on a screen or a portal inside the scene (a view

@@ -23,6 +23,8 @@
  *                            from the same code (csrc/rtx_refit_math.h)
  *   rtxh_blas_build_balanced this repo's OWN balanced BLAS of an indexed mesh: the tree rtx_build_blas builds on the device, from the
  *                            same code (csrc/rtx_build_math.h)
+ *   rtxh_vertex_normals      this repo's OWN smooth, area-weighted vertex normals of an indexed mesh: what rtx_blas_vertex_normals writes on
+ *                            the device, from the same code (csrc/rtx_normals_math.h)
  *   rtxh_blas_build          a BottomLevelBVH for a triangle soup: this repo's OWN binned-SAH
  *                            builder (not the reference's SBVH), output in the
  *                            reference's node convention + flattened leaf order
@@ -152,6 +154,16 @@ int rtxh_blas_build_balanced(const float * positions, const int32_t * indices, c
                              const int32_t * material_ids_or_null, int32_t triangle_count, int32_t vertex_count,
                              rtx_bvh_node * nodes_out, int32_t * node_count_out, rtx_triangle_hot * hot_out, rtx_triangle_cold * cold_out,
                              int32_t * order_out, int32_t * slot_vertices_out);
+
+/* rtx_blas_vertex_normals (include/rtx.h) on the host, by the code the kernels run (csrc/rtx_normals_math.h): smooth, area-weighted vertex
+ * normals of an indexed mesh — positions V*3, indices T*3, normals_out V*3.  Written as the plain scatter loop (over triangles, over corners,
+ * acc[v] += f, then normalise), where the device gathers per vertex through a sorted inverted index: the same additions in the same order.
+ *   validity   a triangle with an index outside [0, vertex_count) contributes nothing and nothing is read through its indices;
+ *   face       f = (p1 - p0) x (p2 - p0); a face vector with a NaN or infinite component counts as (+0, +0, +0);
+ *   sum        from (+0, +0, +0), f once per corner c = 3t + k that holds the vertex, in ascending c;
+ *   normal     m = max |component| of the sum; zero or not finite: (+0, +0, +0); else a = s / m, n = a / sqrtf(a.x*a.x + (a.y*a.y + a.z*a.z)).
+ * Any float is a legal coordinate; no output component is NaN or infinite.  RTX_ERR_INVALID_ARG: null pointer, T < 1, V < 1.              */
+int rtxh_vertex_normals(const float * positions, const int32_t * indices, int32_t triangle_count, int32_t vertex_count, float * normals_out);
 
 /* Camera::update's input handling (Camera.cpp:18-39): keys = OR of RTXH_KEY_* held during this frame; position / rotation are
  * updated in place (follow with rtxh_camera_basis for the view pyramid, Camera.cpp:44-47).                                      */
