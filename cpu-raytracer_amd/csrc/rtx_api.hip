@@ -33,6 +33,7 @@
 #include "rtx_build.h"
 #include "rtx_normals.h"
 #include "rtx_query.h"
+#include "rtx_nearest.h"
 #include "rtx_texmip.h"
 #include <rocprim/device/device_radix_sort.hpp>      // rtx_update_instances, scenes beyond one workgroup: header-only, part of ROCm
 #include "rtx_hostmem.h"                             // DevBuf, StageRing, grow_keep: every device and pinned allocation has one owner
@@ -131,6 +132,8 @@ struct rtx_ctx {
     DevBuf d_query[4], d_query_counters, d_query_heads; int32_t query_cap = 0;
     // RTX_QUERY_SORT: unsorted and sorted keys, the twelve bounds and rocPRIM's temporary storage, for query_sort_cap slots; nothing until the first sorted call
     DevBuf d_query_sort; int32_t query_sort_cap = 0; size_t query_sort_tmp = 0;
+    // rtx_query_nearest: the tile counter of a round (4 bytes, made by the first call); RTX_NEAREST_FETCH=0: tiles by stride, no counter (A/B)
+    DevBuf d_nearest_head; bool nearest_fetch = true;
     size_t slots_alloc = 0, shadow_alloc = 0;
     DevBuf d_stats_partial, d_pk_fifo, d_counters, d_spill, d_fb_rgb, d_fb_packed, d_display, d_gamma, d_pk_heads;
     int trace_blocks_closest = 0, trace_blocks_any = 0, trace_blocks_count = 0;
@@ -229,6 +232,7 @@ extern "C" int rtx_create(const rtx_config * config, rtx_ctx ** out_ctx) {
     K.fuse_shade = knob_int("RTX_FUSE_SHADE", 0, 0, 1) != 0;      // measured: 1.51 vs 1.28 ms per cfg3 frame with three frames in flight: off
     K.update_small_max = (int)knob_int("RTX_UPDATE_SMALL_MAX", RTX_UPDATE_SMALL_MAX, 0, RTX_UPDATE_SMALL_MAX);
     K.tex_pass_levels = (int)knob_int("RTX_TEX_PASS_LEVELS", rtxt::DEFAULT_PASS_LEVELS, 1, rtxt::MAX_PASS_LEVELS);      // DESIGN.md 9, Device-side texture update
+    c->nearest_fetch = knob_int("RTX_NEAREST_FETCH", 1, 0, 1) != 0;     // rtx_query_nearest: workgroups fetch tiles from a counter (1) or take them by stride (0): DESIGN.md 9
     K.fail_item_alloc = knob_int("RTX_DEBUG_FAIL_ITEM_ALLOC", 0, 0, 1) != 0;      // tests: the item buffer's allocation fails (a size no device has), the fallback kernel must take over
     int bpc = 0;
     hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k_trace_fast<false>, RTX_TRACE_BLOCK, 0);
@@ -2113,7 +2117,7 @@ extern "C" int rtx_debug_group_loopback(rtx_ctx * c, int32_t world, uint32_t fla
 // [rocPRIM's temporary storage], 2 x 8 bytes per slot and what rocPRIM asks for a round of that many keys (a host-side query).  Both blocks
 // grow in the one branch that waits; a context that never sorts never allocates the second.
 struct QuerySort { uint64_t * keys_in, * keys; uint32_t * bounds; void * tmp; size_t tmp_bytes; };
-static int query_queues(rtx_ctx * c, int64_t n, DevQueues & q, QuerySort * sort = nullptr) {
+static int query_queues(rtx_ctx * c, int64_t n, DevQueues & q, QuerySort * sort = nullptr, bool rays = true) {      // rays = false: only the sort block (rtx_query_nearest has no queue set)
     const int64_t rows = n < (int64_t)RTX_QUERY_CHUNK_RAYS ? n : (int64_t)RTX_QUERY_CHUNK_RAYS;
     const int32_t cap = (int32_t)((rows + RTX_WAVE - 1) & ~(int64_t)(RTX_WAVE - 1));      // whole packets: the fill marks the tail of the last one
     size_t sort_tmp = 0;
@@ -2124,9 +2128,10 @@ static int query_queues(rtx_ctx * c, int64_t n, DevQueues & q, QuerySort * sort 
         if (last > sort_tmp) sort_tmp = last;
     }
     const bool grow_sort = sort && (cap > c->query_sort_cap || sort_tmp > c->query_sort_tmp);
-    if (cap > c->query_cap || grow_sort) {                 // growth: queued queries still use the old buffers
+    const bool grow_rays = rays && cap > c->query_cap;
+    if (grow_rays || grow_sort) {                          // growth: queued queries still use the old buffers
         HIP_OK(c, hipStreamSynchronize(c->stream));
-        if (cap > c->query_cap) {
+        if (grow_rays) {
             int rc = ensure(c, c->d_query_counters, sizeof(DevCounters));
             if (!rc) rc = ensure(c, c->d_query_heads, (size_t)2 * (RTX_MAX_LEVELS + 1) * RTX_PK_CLASSES * 32 * sizeof(uint32_t));
             for (int k = 0; k < 4 && !rc; k++) rc = ensure(c, c->d_query[k], (size_t)cap * (k < 3 ? 16 : 4));
@@ -2150,6 +2155,7 @@ static int query_queues(rtx_ctx * c, int64_t n, DevQueues & q, QuerySort * sort 
         sort->keys_in = (uint64_t *)(sb + off[0]); sort->keys = (uint64_t *)(sb + off[1]); sort->bounds = (uint32_t *)(sb + off[2]);
         sort->tmp = sb + off[3]; sort->tmp_bytes = c->query_sort_tmp;
     }
+    if (!rays) return RTX_OK;
     q = c->q;                                              // the walkers' knobs (thresholds, spill_threads) as rtx_create read them
     for (int d = 0; d <= RTX_MAX_LEVELS; d++) { q.level_base[d] = 0; q.level_cap[d] = d < 2 ? c->query_cap : 0; q.shadow_base[d] = 0; q.stats_n[d] = 0; }
     q.first_tile = 0; q.tile_stride = 1; q.tile_count = 0; q.primary_slots = 0;
@@ -2179,10 +2185,14 @@ template <int ROW> static int query_sort_round(rtx_ctx * c, const QuerySort & S,
 }
 
 // the checks the two queries and the two debug hooks share, in the order the header lists them; nothing is queued on an error
-static int query_checks(rtx_ctx * c, const void * in, int64_t n, const void * out, uint32_t flags, const char * what) {
+static int query_checks(rtx_ctx * c, const void * in, int64_t n, const void * out, uint32_t flags, const char * what,
+                        uint32_t allowed = RTX_RENDER_LANE_TRACE | RTX_RENDER_PACKET_CLOSEST | RTX_QUERY_SORT) {
     if (!c) return RTX_ERR_INVALID_ARG;
     if (!in || !out || n < 1) { c->err = std::string(what) + ": null pointer or n < 1"; return RTX_ERR_INVALID_ARG; }
-    if (flags & ~(uint32_t)(RTX_RENDER_LANE_TRACE | RTX_RENDER_PACKET_CLOSEST | RTX_QUERY_SORT)) { c->err = std::string(what) + ": flags other than RTX_RENDER_LANE_TRACE / RTX_RENDER_PACKET_CLOSEST / RTX_QUERY_SORT"; return RTX_ERR_INVALID_ARG; }
+    if (flags & ~allowed) {
+        c->err = std::string(what) + (allowed == (uint32_t)RTX_QUERY_SORT ? ": flags other than RTX_QUERY_SORT" : ": flags other than RTX_RENDER_LANE_TRACE / RTX_RENDER_PACKET_CLOSEST / RTX_QUERY_SORT");
+        return RTX_ERR_INVALID_ARG;
+    }
     if (!c->frame_set) { c->err = std::string(what) + " before rtx_set_frame"; return RTX_ERR_STATE; }
     if (c->scene.heatmap) { c->err = std::string(what) + " in heat-map mode"; return RTX_ERR_STATE; }
     return validate_references(c);
@@ -2267,11 +2277,60 @@ extern "C" int rtx_query_occluded(rtx_ctx * c, const void * segments_dev, int64_
     return query_rounds(c, k.q, n, [&](int64_t first, int m) { return query_occluded_round(c, k, (const float *)segments_dev + 7 * first, m, occluded_dev + first); });
 }
 
+// ---- nearest-point queries (include/rtx.h: rtx_query_nearest; kernel in rtx_nearest.h, arithmetic and walk in rtx_nearest_math.h) ------
+// n points with a maximum distance each, in device memory, against the frame the context holds: per round of at most RTX_QUERY_CHUNK_RAYS
+// rows ONE launch of k_query_nearest, which reads the rows and writes the channels; with RTX_QUERY_SORT the bounds, key and sort launches of
+// the ray queries run first over the 4-float rows, in the same sort block.  No queue set, no counters: nothing a render call or rtx_get_stats
+// reads is touched.  The stack lives in LDS and in regions 0 and 1 of the context's spill buffer, as for a closest-hit launch of this stream.
+// The stack rule: the ordered descent holds at most rtxnp::stack_need(TLAS inner depth, deepest BLAS inner depth) entries; a scene that needs
+// more than rtx_config.stack_size (itself <= RTX_MAX_STACK, what LDS and the spill region hold per lane) is refused here, on the host.
+extern "C" int rtx_query_nearest(rtx_ctx * c, const void * points_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags) {
+    if (c && (channels == 0 || (channels & ~(uint32_t)RTX_QUERY_ALL))) { c->err = "rtx_query_nearest: channels must be a non-empty subset of RTX_QUERY_ALL"; return RTX_ERR_INVALID_ARG; }
+    if (int bad = query_checks(c, points_dev, n, out, flags, "rtx_query_nearest", (uint32_t)RTX_QUERY_SORT)) return bad;
+    int blas_depth = -1;
+    for (size_t b = 0; b < c->blas.size(); b++) if (c->h_blas[b].nodes && c->blas[b].inner_depth > blas_depth) blas_depth = c->blas[b].inner_depth;
+    const int need = rtxnp::stack_need(c->tlas_inner_depth, blas_depth), have = c->cfg.stack_size < RTX_MAX_STACK ? c->cfg.stack_size : RTX_MAX_STACK;
+    if (need > have) {
+        c->err = "rtx_query_nearest: the ordered descent needs " + std::to_string(need) + " stack entries (TLAS inner depth " + std::to_string(c->tlas_inner_depth) +
+                 " + 1, BLAS inner depth " + std::to_string(blas_depth) + " + 1), rtx_config.stack_size allows " + std::to_string(have);
+        return RTX_ERR_LIMIT;
+    }
+    hipSetDevice(c->cfg.device);
+    const bool sorted = (flags & RTX_QUERY_SORT) != 0;
+    QuerySort S = {};
+    DevQueues unused;
+    if (sorted) if (int rc = query_queues(c, n, unused, &S, false)) return rc;
+    if (c->nearest_fetch) if (int rc = ensure(c, c->d_nearest_head, sizeof(uint32_t))) return rc;      // the first call only
+    uint32_t * const head = c->nearest_fetch ? (uint32_t *)c->d_nearest_head.p : nullptr;
+    const DevScene sc = c->scene;
+    const int max_blocks = c->q.spill_threads / RTX_QUERY_BLOCK;                  // the spill regions are indexed by the global thread id
+    for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
+        const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
+        const float * const rows = (const float *)points_dev + 4 * first;
+        DevQuery t;
+        auto on = [&](uint32_t bit) { return (channels & bit) != 0; };
+        t.distance = on(RTX_QUERY_DISTANCE) && out->distance ? out->distance + first : nullptr;
+        t.position = on(RTX_QUERY_POSITION) && out->position ? out->position + 3 * first : nullptr;
+        t.normal = on(RTX_QUERY_NORMAL) && out->normal ? out->normal + 3 * first : nullptr;
+        t.uv = on(RTX_QUERY_UV) && out->uv ? out->uv + 2 * first : nullptr;
+        t.material_id = on(RTX_QUERY_MATERIAL_ID) && out->material_id ? out->material_id + first : nullptr;
+        t.object_id = on(RTX_QUERY_OBJECT_ID) && out->object_id ? out->object_id + first : nullptr;
+        t.triangle_id = on(RTX_QUERY_TRIANGLE_ID) && out->triangle_id ? out->triangle_id + first : nullptr;
+        if (sorted) if (int rc = query_sort_round<4>(c, S, rows, m)) return rc;
+        const int tiles = (m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK, blocks = tiles < max_blocks ? tiles : max_blocks;
+        const uint64_t * const order = sorted ? S.keys : nullptr;
+        if (head) HIP_OK(c, hipMemsetAsync(head, 0, sizeof(uint32_t), c->stream));
+        launch_timed(c, "k_query_nearest", c->stream, [&] { hipLaunchKernelGGL(k_query_nearest, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head); });
+    }
+    HIP_OK(c, hipGetLastError());
+    return RTX_OK;
+}
+
 // the order RTX_QUERY_SORT traces n rows of row_floats (6: rays, 7: segments) floats in: the bounds, key and sort launches of every round and
 // nothing else, order_out[first + i] = first + the row of slot i of the round that starts at `first`.  Queued like the queries; their checks.
 extern "C" int rtx_debug_query_order(rtx_ctx * c, const void * rows_dev, int32_t row_floats, int64_t n, int32_t * order_out_dev) {
     if (int bad = query_checks(c, rows_dev, n, order_out_dev, 0u, "rtx_debug_query_order")) return bad;
-    if (row_floats != 6 && row_floats != 7) { c->err = "rtx_debug_query_order: row_floats must be 6 or 7"; return RTX_ERR_INVALID_ARG; }
+    if (row_floats != 4 && row_floats != 6 && row_floats != 7) { c->err = "rtx_debug_query_order: row_floats must be 4, 6 or 7"; return RTX_ERR_INVALID_ARG; }
     if (n > (int64_t)INT32_MAX) { c->err = "rtx_debug_query_order: more rows than an int32_t order holds"; return RTX_ERR_LIMIT; }
     hipSetDevice(c->cfg.device);
     DevQueues q;
@@ -2279,7 +2338,7 @@ extern "C" int rtx_debug_query_order(rtx_ctx * c, const void * rows_dev, int32_t
     if (int rc = query_queues(c, n, q, &S)) return rc;
     return query_rounds(c, q, n, [&](int64_t first, int m) -> int {
         const float * const rows = (const float *)rows_dev + (size_t)row_floats * first;
-        if (int rc = row_floats == 6 ? query_sort_round<6>(c, S, rows, m) : query_sort_round<7>(c, S, rows, m)) return rc;
+        if (int rc = row_floats == 4 ? query_sort_round<4>(c, S, rows, m) : row_floats == 6 ? query_sort_round<6>(c, S, rows, m) : query_sort_round<7>(c, S, rows, m)) return rc;
         launch_timed(c, "k_query_sort_order", c->stream, [&] { hipLaunchKernelGGL(k_query_sort_order, dim3((m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK), dim3(RTX_QUERY_BLOCK), 0, c->stream, (const uint64_t *)S.keys, m, (int32_t)first, order_out_dev + first); });
         return RTX_OK;
     });

@@ -1,0 +1,119 @@
+// rtx_nearest.h — nearest-surface-point queries (include/rtx.h: rtx_query_nearest): k_query_nearest, one kernel per round.
+//
+// One row (x, y, z, maximum distance) per lane, RTX_QUERY_BLOCK lanes per workgroup.  A workgroup walks one tile of RTX_QUERY_BLOCK rows to
+// the end, every lane its own row, then fetches the next tile from the round's counter (RTX_NEAREST_FETCH=0: tiles blockIdx.x, blockIdx.x +
+// gridDim.x, ...), so the grid never exceeds the threads the context's spill region was sized for.  No refill of single lanes (DESIGN.md 9,
+// Nearest-point queries).  The kernel reads the rows and writes the channels itself: no queue set, no resolve launch.  With an order
+// (RTX_QUERY_SORT) slot i walks row key_row(order[i]) and scatters its answer there, as k_query_resolve does.
+//
+// The walk is rtxnp::walk (rtx_nearest_math.h), the same function the host twin runs: a distance-ordered descent over the TLAS and the per-mesh
+// BVHs in the per-lane node layout (two global_load_dwordx4 per node, both children of an inner node fetched together), hot triangles the same
+// way.  The cold record is read after the walk and only if normal, uv or material is requested (a branch on kernel arguments).
+// Stack: entries (node, d2); the first RTX_LDS_STACK per lane in LDS, entry e of lane l at [e][l] like k_trace_fast's lds_stack / lds_key
+// (one dword per lane and instruction: conflict free), deeper ones in regions 0 and 1 of the context's spill buffer, which closest-hit
+// launches of the same stream use the same way.  At most rtxnp::stack_need() entries; the host refuses a scene that needs more than
+// min(stack_size, RTX_MAX_STACK) before the launch, so there is no overflow path here.  LDS: 4 KiB of staged rows + 2 x 16 KiB.
+#pragma once
+#include "rtx_query.h"
+#include "rtx_shade.h"
+#include "rtx_nearest_math.h"
+
+struct NearestScene {
+    const DevScene & sc;
+    rtx_gptr tlas, nodes, tris;
+    RTX_D int sphere_count() const { return sc.sphere_count; }
+    RTX_D int plane_count() const { return sc.plane_count; }
+    RTX_D int tlas_nodes() const { return sc.tlas_node_count; }
+    RTX_D void sphere(int i, rtxnp::P3 & c, float & r2) const { const rtx_sphere & s = sc.spheres[i]; c = rtxnp::ptr3(s.center); r2 = s.radius_squared; }
+    RTX_D void plane(int i, rtxnp::P3 & n, float & dist) const { const rtx_plane & pl = sc.planes[i]; n = rtxnp::ptr3(pl.normal); dist = pl.distance; }
+    static RTX_D void node(rtx_gptr base, int i, rtxnp::P3 & mn, rtxnp::P3 & mx, int & first, int & count) {
+        const float4 a = gld(base, 2 * i), b = gld(base, 2 * i + 1);
+        mn = rtxnp::mk(a.x, a.y, a.z); mx = rtxnp::mk(b.x, b.y, b.z); first = as_i(a.w); count = as_i(b.w);
+    }
+    RTX_D void tlas_node(int i, rtxnp::P3 & mn, rtxnp::P3 & mx, int & first, int & count) const { node(tlas, i, mn, mx, first, count); }
+    RTX_D void blas_node(int i, rtxnp::P3 & mn, rtxnp::P3 & mx, int & first, int & count) const { node(nodes, i, mn, mx, first, count); }
+    RTX_D int enter(int slot, rtxnp::P3 p, rtxnp::P3 & pl) {
+        const int inst = sc.tlas_indices[slot];
+        const rtx_instance & I = sc.instances[inst];
+        pl = rtxnp::xform_pos(I.world_inv, p);
+        const DevBlas & B = sc.blas[I.blas_id];
+        nodes = RTX_GPTR(B.nodes); tris = RTX_GPTR(B.tri_hot);
+        return inst;
+    }
+    RTX_D void triangle(int i, rtxnp::P3 & p0, rtxnp::P3 & e1, rtxnp::P3 & e2) const {
+        const float4 a = gld(tris, RTX_TRI_STRIDE * i), b = gld(tris, RTX_TRI_STRIDE * i + 1), c = gld(tris, RTX_TRI_STRIDE * i + 2);
+        p0 = rtxnp::mk(a.x, a.y, a.z); e1 = rtxnp::mk(b.x, b.y, b.z); e2 = rtxnp::mk(c.x, c.y, c.z);
+    }
+};
+
+struct NearestStack {
+    int * stk; float * key; int * spill; float * spill_key; int stride;
+    RTX_D void push(int sp, int node, float d2) {
+        if (sp < RTX_LDS_STACK) { stk[sp * RTX_WAVE] = node; key[sp * RTX_WAVE] = d2; }
+        else { spill[(sp - RTX_LDS_STACK) * stride] = node; spill_key[(sp - RTX_LDS_STACK) * stride] = d2; }
+    }
+    RTX_D void pop(int sp, int & node, float & d2) const {
+        if (sp < RTX_LDS_STACK) { node = stk[sp * RTX_WAVE]; d2 = key[sp * RTX_WAVE]; }
+        else { node = spill[(sp - RTX_LDS_STACK) * stride]; d2 = spill_key[(sp - RTX_LDS_STACK) * stride]; }
+    }
+};
+
+__global__ __launch_bounds__(RTX_QUERY_BLOCK)
+void k_query_nearest(const DevScene sc, const float * __restrict__ rows4, const int m, const DevQuery out, const uint64_t * __restrict__ order,
+                     int32_t * const spill_base, const int spill_threads, uint32_t * const head) {
+    __shared__ float lds_rows[4 * RTX_QUERY_BLOCK];
+    __shared__ int lds_stack[RTX_QUERY_BLOCK / RTX_WAVE][RTX_LDS_STACK][RTX_WAVE];
+    __shared__ float lds_key[RTX_QUERY_BLOCK / RTX_WAVE][RTX_LDS_STACK][RTX_WAVE];
+    __shared__ int lds_tile;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int gtid = blockIdx.x * RTX_QUERY_BLOCK + threadIdx.x;                  // < spill_threads: the host sizes the grid
+    const size_t spill_region = (size_t)spill_threads * (RTX_MAX_STACK - RTX_LDS_STACK);
+    NearestStack st = { &lds_stack[wave][0][lane], &lds_key[wave][0][lane], spill_base + gtid, (float *)(spill_base + spill_region) + gtid, spill_threads };
+    const bool cold = out.normal || out.uv || out.material_id;                    // kernel arguments: the same for every lane
+    const int tiles = (m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK;
+    // head: the round's tile counter (zeroed before the launch), the workgroup fetches its next tile when it has finished one — tiles near a
+    // dense part of the scene take many times longer than empty ones, and neighbours in a coherent order are alike; null: tiles blockIdx.x,
+    // blockIdx.x + gridDim.x, ... (the A/B: DESIGN.md 9)
+    int tile = blockIdx.x;
+    for (int k = 0; ; k++) {
+        if (head) {
+            __syncthreads();                                                      // every lane has taken its row and the number of the previous tile
+            if (threadIdx.x == 0) lds_tile = (int)atomicAdd(head, 1u);
+            __syncthreads();
+            tile = lds_tile;
+        } else if (k) tile += gridDim.x;
+        if (tile >= tiles) break;
+        const int i = tile * RTX_QUERY_BLOCK + threadIdx.x;
+        float r[4];
+        if (order) query_gather_row<4>(order, rows4, m, i, r);
+        else {
+            if (!head && k) __syncthreads();                                      // every lane has taken its row of the previous tile
+            query_load_row<4>(lds_rows, rows4, m, r, tile);
+        }
+        if (i >= m) continue;
+        NearestScene S = { sc, RTX_GPTR(sc.tlas_nodes), nullptr, nullptr };
+        rtxnp::Answer a;
+        rtxnp::walk(S, st, r, a);
+
+        const size_t p = order ? (size_t)rtxq::key_row(order[i]) : (size_t)i;      // the caller's row of this slot
+        if (p >= (size_t)m) continue;                                              // never: a sorted key holds a row of the round
+        const bool hit = a.kind != rtxnp::KIND_NONE;
+        rtxnp::P3 point = rtxnp::mk(0.0f, 0.0f, 0.0f), normal = point;
+        float tu = 0.0f, tv = 0.0f;
+        int material = -1;
+        if (hit && (out.position || cold)) {
+            const rtxnp::P3 q = rtxnp::mk(r[0], r[1], r[2]);
+            if (a.kind == rtxnp::KIND_TRI) nearest_triangle_outputs(sc, a.object, a.slot, a.u, a.v, out.position != nullptr, cold, point, normal, tu, tv, material);
+            else if (a.kind == rtxnp::KIND_SPHERE) nearest_sphere_outputs(sc.spheres[a.object], q, point, normal, tu, tv, material);
+            else nearest_plane_outputs(sc.planes[a.object], q, point, normal, tu, tv, material);
+        }
+        if (out.distance) out.distance[p] = hit ? rtxnp::root(a.d2) : INFINITY;
+        if (out.position) { out.position[3 * p + 0] = point.x; out.position[3 * p + 1] = point.y; out.position[3 * p + 2] = point.z; }
+        if (out.normal) { out.normal[3 * p + 0] = normal.x; out.normal[3 * p + 1] = normal.y; out.normal[3 * p + 2] = normal.z; }
+        if (out.uv) { out.uv[2 * p + 0] = tu; out.uv[2 * p + 1] = tv; }
+        if (out.material_id) out.material_id[p] = hit ? material : -1;
+        if (out.object_id)                                            // instances, then spheres, then planes: the numbering of rtx_query_closest
+            out.object_id[p] = !hit ? -1 : a.kind == rtxnp::KIND_TRI ? a.object : a.kind == rtxnp::KIND_SPHERE ? sc.instance_count + a.object : sc.instance_count + sc.sphere_count + a.object;
+        if (out.triangle_id) out.triangle_id[p] = a.kind == rtxnp::KIND_TRI ? a.slot : -1;
+    }
+}

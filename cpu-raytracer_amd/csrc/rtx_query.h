@@ -35,9 +35,10 @@ struct DevQuery {
 // Rows of ROW floats are 24 / 28 bytes: lane-per-row loads would be ROW loads of stride ROW * 4 B per lane.  The workgroup reads its
 // RTX_QUERY_BLOCK rows as one contiguous run of floats instead (consecutive lanes, consecutive dwords; any 4-byte aligned address) into LDS,
 // and every lane takes its row from there.  Rows at and beyond m read as zeros: no ray.  Every thread of the workgroup must call this.
+// `block`: the tile of RTX_QUERY_BLOCK rows to stage — the workgroup's own, or the one a workgroup that loops over tiles is at (k_query_nearest).
 template <int ROW>
-RTX_D void query_load_row(float (&lds)[ROW * RTX_QUERY_BLOCK], const float * __restrict__ rows, const int m, float (&row)[ROW]) {
-    const int first = blockIdx.x * RTX_QUERY_BLOCK;
+RTX_D void query_load_row(float (&lds)[ROW * RTX_QUERY_BLOCK], const float * __restrict__ rows, const int m, float (&row)[ROW], const int block = blockIdx.x) {
+    const int first = block * RTX_QUERY_BLOCK;
     const int have = (m - first < RTX_QUERY_BLOCK ? (m - first > 0 ? m - first : 0) : RTX_QUERY_BLOCK) * ROW;      // floats of this workgroup's rows
     const float * const src = rows + (size_t)first * ROW;
     for (int k = threadIdx.x; k < ROW * RTX_QUERY_BLOCK; k += RTX_QUERY_BLOCK) lds[k] = k < have ? src[k] : 0.0f;
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_sort_bounds(const flo
     const int i = blockIdx.x * RTX_QUERY_BLOCK + threadIdx.x;
     uint32_t k12[2 * rtxq::COORDS];
     for (int a = 0; a < 2 * rtxq::COORDS; a++) k12[a] = 0xffffffffu;
-    if (i < m && rtxq::row_is_live(r, ROW)) { float x[rtxq::COORDS]; rtxq::coordinates(r, x); rtxq::bounds_of_row(x, k12); }
+    if (i < m && rtxq::row_is_live(r, ROW)) { float x[rtxq::COORDS]; rtxq::coordinates(r, ROW, x); rtxq::bounds_of_row(x, k12); }
     for (int a = 0; a < 2 * rtxq::COORDS; a++) {
         uint32_t v = k12[a];
         for (int o = 32; o > 0; o >>= 1) { const uint32_t w = (uint32_t)__shfl_xor((int)v, o, 64); v = w < v ? w : v; }

@@ -14,6 +14,8 @@
 //   * q = min((uint32)(t * (2^b - 1)), 2^b - 1), t = (x - min) / (max - min), truncated.  When max - min overflows fp32 (origins at +-3e38)
 //     both differences are taken of the HALVED values instead, t = (x/2 - min/2) / (max/2 - min/2): halving is exact for such floats, the
 //     quotient is the same real number, and nothing is infinite.  t is in [0, 1] either way; a t that is not >= 0 would be cell 0;
+//   * a row of FOUR floats is a point with a maximum distance (rtx_query_nearest): live when x, y, z are finite and the maximum distance is
+//     > 0 (csrc/rtx_nearest_math.h), coordinates 0..2 the point, 3..5 the constant +0: degenerate, so the point takes all the key bits;
 //   * the Morton code takes the quantised coordinates bit by bit, most significant bit first, within a bit in the order o.x o.y o.z c.x c.y c.z;
 //   * key = dead << 63 | code << 20 | row in round.  A total order: any correct sort gives one result; dead rows come last in row order.
 #pragma once
@@ -43,6 +45,7 @@ RTX_HD float ordered_value(uint32_t k) { const uint32_t u = (k & 0x80000000u) ? 
 
 // what k_query_fill / k_query_fill_segments trace (query_row_is_ray, and r[6] == r[6] for a segment)
 RTX_HD bool row_is_live(const float * r, int row_floats) {
+    if (row_floats == 4) return is_finite(r[0]) && is_finite(r[1]) && is_finite(r[2]) && r[3] > 0.0f;      // a point row
     bool finite = true;
     for (int k = 0; k < 6; k++) finite = finite && is_finite(r[k]);
     const bool zero = (r[3] == 0.0f) & (r[4] == 0.0f) & (r[5] == 0.0f);
@@ -54,6 +57,12 @@ RTX_HD void coordinates(const float * r, float x[COORDS]) {
     const float ax = magnitude(r[3]), ay = magnitude(r[4]), az = magnitude(r[5]);
     float m = ax > ay ? ax : ay; m = m > az ? m : az;                  // > 0: the row is live
     for (int k = 0; k < 3; k++) { x[k] = canonical(r[k]); x[3 + k] = canonical(r[3 + k] / m); }
+}
+
+// ... of a live row of row_floats floats: a point row (4) has the point and three constant zeros
+RTX_HD void coordinates(const float * r, int row_floats, float x[COORDS]) {
+    if (row_floats == 4) { for (int k = 0; k < 3; k++) { x[k] = canonical(r[k]); x[3 + k] = 0.0f; } return; }
+    coordinates(r, x);
 }
 
 // The twelve bounds of a round as the kernels reduce them: lo[0..5] as ordered keys, hi[0..5] as COMPLEMENTED ordered keys, so that both
@@ -107,7 +116,7 @@ RTX_HD uint64_t morton(const Plan & p, const uint32_t q[COORDS]) {
 RTX_HD uint64_t sort_key(const Plan & p, const float * r, int row_floats, uint32_t row) {
     if (!row_is_live(r, row_floats)) return ((uint64_t)1 << DEAD_BIT) | (uint64_t)row;
     float x[COORDS]; uint32_t q[COORDS];
-    coordinates(r, x);
+    coordinates(r, row_floats, x);
     for (int a = 0; a < COORDS; a++) q[a] = ((p.used >> a) & 1u) ? quantise(p, a, x[a]) : 0u;
     return (morton(p, q) << ROW_BITS) | (uint64_t)row;
 }

@@ -16,6 +16,7 @@
 #include "rtx_device.h"
 #include "rtx_texture.h"
 #include "rtx_trace.h"
+#include "rtx_nearest_math.h"
 
 #ifndef RTX_SHADE_BLOCK
 #define RTX_SHADE_BLOCK 256     // 4 waves aggregate their queue appends into ONE global atomic; one wave per SIMD: a workgroup finds room beside other frames'
@@ -145,6 +146,35 @@ RTX_D void rebuild_plane_hit(const DevScene & sc, const rtx_plane & pl, float t,
         h.ds_dx = vdot(dP_dx, ua); h.ds_dy = vdot(dP_dy, ua);
         h.dt_dx = vdot(dP_dx, va); h.dt_dy = vdot(dP_dy, va);
     }
+}
+
+// ---- nearest-point queries (rtx_nearest.h): what RayHit::point, normal, u, v and material_id would hold at the nearest surface point ------
+// The arithmetic is rtx_nearest_math.h's (shared with the host twin); these read the records.  A triangle at the weights (u, v) of its
+// closest point: the hot record only for the position, the cold record only for normal, uv and material.
+RTX_D void nearest_triangle_outputs(const DevScene & sc, int inst, int tri, float u, float v, bool want_point, bool want_cold,
+                                    rtxnp::P3 & point, rtxnp::P3 & normal, float & tu, float & tv, int & material) {
+    const rtx_instance & I = sc.instances[inst];
+    const DevBlas & B = sc.blas[I.blas_id];
+    if (want_point) {
+        const rtx_gptr hp = RTX_GPTR(B.tri_hot);
+        const float4 p0 = gld(hp, RTX_TRI_STRIDE * tri), e1 = gld(hp, RTX_TRI_STRIDE * tri + 1), e2 = gld(hp, RTX_TRI_STRIDE * tri + 2);
+        point = rtxnp::xform_pos(I.world, rtxnp::triangle_point(rtxnp::mk(p0.x, p0.y, p0.z), rtxnp::mk(e1.x, e1.y, e1.z), rtxnp::mk(e2.x, e2.y, e2.z), u, v));
+    }
+    if (want_cold) {
+        const rtx_gptr cp = RTX_GPTR(B.tri_cold + tri);                 // 64-byte record = 4 x dwordx4, fields as in rebuild_triangle_hit
+        const float4 c0 = gld(cp, 0), c1 = gld(cp, 1), c2 = gld(cp, 2), c3 = gld(cp, 3);
+        const float t0[2] = { c0.x, c0.y }, te1[2] = { c0.z, c0.w }, te2[2] = { c1.x, c1.y };
+        rtxnp::triangle_outputs(I.world, rtxnp::mk(c1.z, c1.w, c2.x), rtxnp::mk(c2.y, c2.z, c2.w), rtxnp::mk(c3.x, c3.y, c3.z), t0, te1, te2, u, v, normal, tu, tv);
+        material = B.material_offset + as_i(c3.w);
+    }
+}
+RTX_D void nearest_sphere_outputs(const rtx_sphere & sp, rtxnp::P3 p, rtxnp::P3 & point, rtxnp::P3 & normal, float & tu, float & tv, int & material) {
+    rtxnp::sphere_outputs(p, rtxnp::ptr3(sp.center), sp.radius_squared, point, normal, tu, tv);
+    material = sp.material_id;
+}
+RTX_D void nearest_plane_outputs(const rtx_plane & pl, rtxnp::P3 p, rtxnp::P3 & point, rtxnp::P3 & normal, float & tu, float & tv, int & material) {
+    rtxnp::plane_outputs(p, rtxnp::ptr3(pl.normal), pl.distance, rtxnp::ptr3(pl.u_axis), rtxnp::ptr3(pl.v_axis), point, normal, tu, tv);
+    material = pl.material_id;
 }
 
 // Light::calc_lighting, Light.h:12-26

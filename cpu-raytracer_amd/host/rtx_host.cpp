@@ -11,6 +11,7 @@
 #include "../csrc/rtx_normals_math.h"
 #include "../csrc/rtx_texmip_math.h"
 #include "../csrc/rtx_query_sort_math.h"
+#include "../csrc/rtx_nearest_math.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -569,7 +570,7 @@ extern "C" int rtxh_texture_mips(float * tx, int32_t width, int32_t height, rtx_
 // RTX_QUERY_SORT on the host: the round structure of rtx_query_closest / rtx_query_occluded, the bounds as the twelve min-reduced words
 // k_query_sort_bounds leaves, the keys of rtx_query_sort_math.h, a sort of the 64-bit keys (a total order: any sort gives this result)
 extern "C" int rtxh_query_sort_order(const float * rows, int32_t row_floats, int64_t n, int32_t * order_out) {
-    if (!rows || !order_out || n < 1 || (row_floats != 6 && row_floats != 7)) return RTX_ERR_INVALID_ARG;
+    if (!rows || !order_out || n < 1 || (row_floats != 4 && row_floats != 6 && row_floats != 7)) return RTX_ERR_INVALID_ARG;
     if (n > (int64_t)INT32_MAX) return RTX_ERR_LIMIT;
     std::vector<uint64_t> keys;
     for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
@@ -580,7 +581,7 @@ extern "C" int rtxh_query_sort_order(const float * rows, int32_t row_floats, int
         for (int i = 0; i < m; i++) {
             if (!rtxq::row_is_live(r + (size_t)row_floats * i, row_floats)) continue;
             float x[rtxq::COORDS]; uint32_t k12[2 * rtxq::COORDS];
-            rtxq::coordinates(r + (size_t)row_floats * i, x);
+            rtxq::coordinates(r + (size_t)row_floats * i, row_floats, x);
             rtxq::bounds_of_row(x, k12);
             for (int a = 0; a < 2 * rtxq::COORDS; a++) if (k12[a] < bounds[a]) bounds[a] = k12[a];
         }
@@ -592,6 +593,153 @@ extern "C" int rtxh_query_sort_order(const float * rows, int32_t row_floats, int
     }
     return RTX_OK;
 }
+
+// =================================================================================================
+// rtx_query_nearest on the host: rtxnp::walk (csrc/rtx_nearest_math.h) over the reference-layout arrays, and the exhaustive search
+namespace {
+struct HostNearestScene {
+    const rtxh_nearest_scene & s;
+    const rtxh_nearest_blas * B = nullptr;
+    int sphere_count() const { return s.sphere_count; }
+    int plane_count() const { return s.plane_count; }
+    int tlas_nodes() const { return s.tlas_node_count; }
+    void sphere(int i, rtxnp::P3 & c, float & r2) const { c = rtxnp::ptr3(s.spheres[i].center); r2 = s.spheres[i].radius_squared; }
+    void plane(int i, rtxnp::P3 & n, float & dist) const { n = rtxnp::ptr3(s.planes[i].normal); dist = s.planes[i].distance; }
+    static void node(const rtx_bvh_node & nd, rtxnp::P3 & mn, rtxnp::P3 & mx, int & first, int & count) {
+        mn = rtxnp::ptr3(nd.aabb_min); mx = rtxnp::ptr3(nd.aabb_max); first = nd.left_or_first; count = nd.count;
+    }
+    void tlas_node(int i, rtxnp::P3 & mn, rtxnp::P3 & mx, int & first, int & count) const { node(s.tlas_nodes[i], mn, mx, first, count); }
+    void blas_node(int i, rtxnp::P3 & mn, rtxnp::P3 & mx, int & first, int & count) const { node(B->nodes[i], mn, mx, first, count); }
+    int enter(int slot, rtxnp::P3 p, rtxnp::P3 & pl) {
+        const int inst = s.tlas_indices[slot];
+        pl = rtxnp::xform_pos(s.instances[inst].world_inv, p);
+        B = &s.blas[s.instances[inst].blas_id];
+        return inst;
+    }
+    void triangle(int i, rtxnp::P3 & p0, rtxnp::P3 & e1, rtxnp::P3 & e2) const {
+        p0 = rtxnp::ptr3(B->hot[i].position_0); e1 = rtxnp::ptr3(B->hot[i].position_edge_1); e2 = rtxnp::ptr3(B->hot[i].position_edge_2);
+    }
+};
+struct HostNearestStack {
+    int node[RTX_MAX_STACK]; float d2[RTX_MAX_STACK]; int high = 0;
+    void push(int sp, int n, float d) { node[sp] = n; d2[sp] = d; if (sp + 1 > high) high = sp + 1; }
+    void pop(int sp, int & n, float & d) const { n = node[sp]; d = d2[sp]; }
+};
+int tree_inner_depth(const rtx_bvh_node * nodes, int node_count, int64_t primitive_count, int & depth_out) {      // -1: one leaf; error: a child or a range outside its array
+    depth_out = -1;
+    if (node_count < 1) return RTX_ERR_INVALID_ARG;
+    std::vector<std::pair<int, int>> todo(1, std::make_pair(0, 0));
+    size_t visited = 0;
+    while (!todo.empty()) {
+        const int i = todo.back().first, d = todo.back().second; todo.pop_back();
+        if (++visited > (size_t)node_count) return RTX_ERR_INVALID_ARG;      // a cycle
+        const int cnt = nodes[i].count & 0x3fffffff, f = nodes[i].left_or_first;
+        if (cnt > 0) { if (f < 0 || (int64_t)f + cnt > primitive_count) return RTX_ERR_INVALID_ARG; }
+        else { if (f < 0 || f + 1 >= node_count) return RTX_ERR_INVALID_ARG; if (d > depth_out) depth_out = d; todo.push_back(std::make_pair(f, d + 1)); todo.push_back(std::make_pair(f + 1, d + 1)); }
+    }
+    return RTX_OK;
+}
+int nearest_scene_check(const rtxh_nearest_scene * s, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out, bool trees) {
+    if (!s || !points || !out || n < 1 || channels == 0 || (channels & ~(uint32_t)RTX_QUERY_ALL)) return RTX_ERR_INVALID_ARG;
+    if (s->instance_count < 0 || s->tlas_node_count < 0 || s->tlas_index_count < 0 || s->blas_count < 0 || s->sphere_count < 0 || s->plane_count < 0) return RTX_ERR_INVALID_ARG;
+    if ((s->instance_count && !s->instances) || (s->tlas_node_count && !s->tlas_nodes) || (s->tlas_index_count && !s->tlas_indices) || (s->blas_count && !s->blas) ||
+        (s->sphere_count && !s->spheres) || (s->plane_count && !s->planes)) return RTX_ERR_INVALID_ARG;
+    for (int i = 0; i < s->instance_count; i++) if (s->instances[i].blas_id < 0 || s->instances[i].blas_id >= s->blas_count) return RTX_ERR_INVALID_ARG;
+    for (int b = 0; b < s->blas_count; b++) if (!s->blas[b].nodes || !s->blas[b].hot || !s->blas[b].cold || s->blas[b].node_count < 1 || s->blas[b].triangle_count < 0) return RTX_ERR_INVALID_ARG;
+    for (int i = 0; i < s->tlas_index_count; i++) if (s->tlas_indices[i] < 0 || s->tlas_indices[i] >= s->instance_count) return RTX_ERR_INVALID_ARG;
+    if (!trees) return RTX_OK;
+    int tlas_depth = -1, blas_depth = -1;
+    if (s->tlas_node_count > 0) if (int rc = tree_inner_depth(s->tlas_nodes, s->tlas_node_count, s->tlas_index_count, tlas_depth)) return rc;
+    for (int b = 0; b < s->blas_count; b++) {
+        int d = -1;
+        if (int rc = tree_inner_depth(s->blas[b].nodes, s->blas[b].node_count, s->blas[b].triangle_count, d)) return rc;
+        if (d > blas_depth) blas_depth = d;
+    }
+    return rtxnp::stack_need(tlas_depth, blas_depth) > RTX_MAX_STACK ? RTX_ERR_LIMIT : RTX_OK;
+}
+// the channels of row i from its answer: what k_query_nearest stores
+void nearest_store(const rtxh_nearest_scene & s, const float * row, const rtxnp::Answer & a, int64_t i, uint32_t channels, const rtx_query_buffers & out) {
+    const bool hit = a.kind != rtxnp::KIND_NONE;
+    rtxnp::P3 point = rtxnp::mk(0.0f, 0.0f, 0.0f), normal = point;
+    float tu = 0.0f, tv = 0.0f; int material = -1;
+    const rtxnp::P3 p = rtxnp::mk(row[0], row[1], row[2]);
+    if (a.kind == rtxnp::KIND_TRI) {
+        const rtx_instance & I = s.instances[a.object];
+        const rtxh_nearest_blas & B = s.blas[I.blas_id];
+        const rtx_triangle_hot & h = B.hot[a.slot]; const rtx_triangle_cold & c = B.cold[a.slot];
+        point = rtxnp::xform_pos(I.world, rtxnp::triangle_point(rtxnp::ptr3(h.position_0), rtxnp::ptr3(h.position_edge_1), rtxnp::ptr3(h.position_edge_2), a.u, a.v));
+        rtxnp::triangle_outputs(I.world, rtxnp::ptr3(c.normal_0), rtxnp::ptr3(c.normal_edge_1), rtxnp::ptr3(c.normal_edge_2), c.tex_coord_0, c.tex_coord_edge_1, c.tex_coord_edge_2, a.u, a.v, normal, tu, tv);
+        material = B.material_offset + c.material_id;
+    } else if (a.kind == rtxnp::KIND_SPHERE) {
+        const rtx_sphere & sp = s.spheres[a.object];
+        rtxnp::sphere_outputs(p, rtxnp::ptr3(sp.center), sp.radius_squared, point, normal, tu, tv); material = sp.material_id;
+    } else if (a.kind == rtxnp::KIND_PLANE) {
+        const rtx_plane & pl = s.planes[a.object];
+        rtxnp::plane_outputs(p, rtxnp::ptr3(pl.normal), pl.distance, rtxnp::ptr3(pl.u_axis), rtxnp::ptr3(pl.v_axis), point, normal, tu, tv); material = pl.material_id;
+    }
+    auto on = [&](uint32_t bit) { return (channels & bit) != 0; };
+    if (on(RTX_QUERY_DISTANCE) && out.distance) out.distance[i] = hit ? rtxnp::root(a.d2) : INFINITY;
+    if (on(RTX_QUERY_POSITION) && out.position) { out.position[3 * i] = point.x; out.position[3 * i + 1] = point.y; out.position[3 * i + 2] = point.z; }
+    if (on(RTX_QUERY_NORMAL) && out.normal) { out.normal[3 * i] = normal.x; out.normal[3 * i + 1] = normal.y; out.normal[3 * i + 2] = normal.z; }
+    if (on(RTX_QUERY_UV) && out.uv) { out.uv[2 * i] = tu; out.uv[2 * i + 1] = tv; }
+    if (on(RTX_QUERY_MATERIAL_ID) && out.material_id) out.material_id[i] = hit ? material : -1;
+    if (on(RTX_QUERY_OBJECT_ID) && out.object_id)
+        out.object_id[i] = !hit ? -1 : a.kind == rtxnp::KIND_TRI ? a.object : a.kind == rtxnp::KIND_SPHERE ? s.instance_count + a.object : s.instance_count + s.sphere_count + a.object;
+    if (on(RTX_QUERY_TRIANGLE_ID) && out.triangle_id) out.triangle_id[i] = a.kind == rtxnp::KIND_TRI ? a.slot : -1;
+}
+}  // namespace
+
+extern "C" int rtxh_query_nearest(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out, int32_t * stack_max_out) {
+    if (int rc = nearest_scene_check(scene, points, n, channels, out, true)) return rc;
+    int high = 0;
+    for (int64_t i = 0; i < n; i++) {
+        HostNearestScene S{ *scene };
+        HostNearestStack st;
+        rtxnp::Answer a;
+        rtxnp::walk(S, st, points + 4 * i, a);
+        if (st.high > high) high = st.high;
+        nearest_store(*scene, points + 4 * i, a, i, channels, *out);
+    }
+    if (stack_max_out) *stack_max_out = high;
+    return RTX_OK;
+}
+
+extern "C" int rtxh_query_nearest_exhaustive(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out) {
+    if (int rc = nearest_scene_check(scene, points, n, channels, out, false)) return rc;
+    const rtxh_nearest_scene & s = *scene;
+    for (int64_t i = 0; i < n; i++) {
+        const float * row = points + 4 * i;
+        rtxnp::Answer a; a.kind = rtxnp::KIND_NONE; a.object = -1; a.slot = -1; a.u = 0.0f; a.v = 0.0f; a.d2 = INFINITY;
+        if (rtxnp::row_is_live(row)) {
+            const rtxnp::P3 p = rtxnp::mk(row[0], row[1], row[2]);
+            a.d2 = row[3] * row[3];
+            for (int k = 0; k < s.sphere_count; k++) rtxnp::offer(a, rtxnp::sphere_d2(p, rtxnp::ptr3(s.spheres[k].center), s.spheres[k].radius_squared), rtxnp::KIND_SPHERE, k, -1, 0.0f, 0.0f);
+            for (int k = 0; k < s.plane_count; k++) rtxnp::offer(a, rtxnp::plane_d2(p, rtxnp::ptr3(s.planes[k].normal), s.planes[k].distance), rtxnp::KIND_PLANE, k, -1, 0.0f, 0.0f);
+            for (int k = 0; k < s.instance_count; k++) {
+                const rtxnp::P3 pl = rtxnp::xform_pos(s.instances[k].world_inv, p);
+                const rtxh_nearest_blas & B = s.blas[s.instances[k].blas_id];
+                for (int t = 0; t < B.triangle_count; t++) {
+                    float u, v;
+                    const float d2 = rtxnp::triangle_d2(rtxnp::sub(pl, rtxnp::ptr3(B.hot[t].position_0)), rtxnp::ptr3(B.hot[t].position_edge_1), rtxnp::ptr3(B.hot[t].position_edge_2), u, v);
+                    rtxnp::offer(a, d2, rtxnp::KIND_TRI, k, t, u, v);
+                }
+            }
+        }
+        nearest_store(s, row, a, i, channels, *out);
+    }
+    return RTX_OK;
+}
+
+extern "C" float rtxh_nearest_distance_bound(float local_scale, float world_scale) { return rtxnp::distance_bound(local_scale, world_scale); }
+extern "C" float rtxh_nearest_box_d2(const float p[3], const float box_min[3], const float box_max[3]) { return rtxnp::box_d2(rtxnp::ptr3(p), rtxnp::ptr3(box_min), rtxnp::ptr3(box_max)); }
+extern "C" float rtxh_nearest_triangle_d2(const float p[3], const rtx_triangle_hot * tri, float uv_out[2]) {
+    float u, v;
+    const float d2 = rtxnp::triangle_d2(rtxnp::sub(rtxnp::ptr3(p), rtxnp::ptr3(tri->position_0)), rtxnp::ptr3(tri->position_edge_1), rtxnp::ptr3(tri->position_edge_2), u, v);
+    if (uv_out) { uv_out[0] = u; uv_out[1] = v; }
+    return d2;
+}
+extern "C" float rtxh_nearest_sphere_d2(const float p[3], const rtx_sphere * sphere) { return rtxnp::sphere_d2(rtxnp::ptr3(p), rtxnp::ptr3(sphere->center), sphere->radius_squared); }
+extern "C" float rtxh_nearest_plane_d2(const float p[3], const rtx_plane * plane) { return rtxnp::plane_d2(rtxnp::ptr3(p), rtxnp::ptr3(plane->normal), plane->distance); }
 
 // =================================================================================================
 // Procedural atrium: a seeded Sponza-class stand-in (the real sponza.obj is absent from the mount).

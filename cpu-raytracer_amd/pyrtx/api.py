@@ -28,7 +28,7 @@ EXPORTS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error", "rt
            "rtx_bind_blas_vertices", "rtx_refit_blas", "rtx_read_blas", "rtx_alloc_blas", "rtx_build_blas",
            "rtx_query_closest", "rtx_query_occluded", "rtx_debug_query_order", "rtx_debug_read_layouts",
            "rtx_alloc_texture", "rtx_update_texture", "rtx_read_texture", "rtx_update_sky",
-           "rtx_alloc_blas_topology", "rtx_set_blas_topology", "rtx_blas_vertex_normals"]
+           "rtx_alloc_blas_topology", "rtx_set_blas_topology", "rtx_blas_vertex_normals", "rtx_query_nearest"]
 # newer than the A/B variants tools/ab.py may load (RTX_HIP_LIB = a library built from an older commit): bound when the library has them,
 # otherwise a call raises AttributeError (undefined symbol)
 VIEW_EXPORTS = ("rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer")
@@ -42,6 +42,7 @@ QUERY_SORT_EXPORTS = ("rtx_debug_query_order",)
 LAYOUT_EXPORTS = ("rtx_debug_read_layouts",)
 TEXTURE_EXPORTS = ("rtx_alloc_texture", "rtx_update_texture", "rtx_read_texture", "rtx_update_sky")
 NORMALS_EXPORTS = ("rtx_alloc_blas_topology", "rtx_set_blas_topology", "rtx_blas_vertex_normals")
+NEAREST_EXPORTS = ("rtx_query_nearest",)
 # texel formats of rtx_update_texture (include/rtx.h RTX_TEXELS_*)
 RTX_TEXELS_RGB_F32 = 0
 RTX_TEXELS_RGBA8_SRGB = 1
@@ -163,6 +164,8 @@ def load_library(path: Optional[str] = None):
     if hasattr(lib, "rtx_query_closest"):
         lib.rtx_query_closest.argtypes = [vp, vp, C.c_int64, u32, C.POINTER(RtxQueryBuffers), u32]
         lib.rtx_query_occluded.argtypes = [vp, vp, C.c_int64, vp, u32]
+    if hasattr(lib, "rtx_query_nearest"):
+        lib.rtx_query_nearest.argtypes = [vp, vp, C.c_int64, u32, C.POINTER(RtxQueryBuffers), u32]
     if hasattr(lib, "rtx_debug_query_order"):
         lib.rtx_debug_query_order.argtypes = [vp, vp, i32, C.c_int64, vp]
     if hasattr(lib, "rtx_debug_read_layouts"):
@@ -177,7 +180,7 @@ def load_library(path: Optional[str] = None):
         lib.rtx_set_blas_topology.argtypes = [vp, i32, vp]
         lib.rtx_blas_vertex_normals.argtypes = [vp, i32, vp, vp]
     for name in EXPORTS:
-        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + QUERY_SORT_EXPORTS + LAYOUT_EXPORTS + TEXTURE_EXPORTS + NORMALS_EXPORTS and not hasattr(lib, name):
+        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + QUERY_SORT_EXPORTS + LAYOUT_EXPORTS + TEXTURE_EXPORTS + NORMALS_EXPORTS + NEAREST_EXPORTS and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         if name not in ("rtx_last_error",):
@@ -1128,14 +1131,57 @@ class Renderer:
             launch()
         return out
 
+    def query_nearest(self, points, channels=("distance",), out: Optional[Dict] = None, n: Optional[int] = None, sort: bool = False) -> Dict:
+        """The nearest surface point of n points against the frame the context holds (rtx_query_nearest): points = float32 torch tensor
+        (n, 4) of (x, y, z, maximum distance) on this context's GPU; channels as for query_closest.  Returns {name: tensor}: distance to the
+        nearest surface point, that point, and what a hit there would report as normal, uv and ids.  No answer (nothing strictly nearer
+        than the maximum distance, a non-finite coordinate, a maximum distance that is NaN or not above 0): distance inf, ids -1, the rest 0;
+        +inf is a legal maximum distance.  Distances are measured in each instance's local space.  Queued on torch's current stream, checked
+        and shaped like query_closest; sort=True (RTX_QUERY_SORT) walks the points of every round in Morton order, same answers row for row.
+        Raw device pointers: points = address, n, out = {name: address} for every channel wanted."""
+        names = query_names(channels)
+        ptr, n, pts_t = self._query_rows("points", points, 4, n)
+        if out is not None and not isinstance(out, dict):
+            raise TypeError(f"out must be a dict {{channel name: tensor}}, not {type(out).__name__}")
+        out = dict(out or {})
+        query_names(list(out) or names)
+        extra = [k for k in out if k not in names]
+        if extra:
+            raise ValueError(f"out holds channels that were not requested: {', '.join(extra)}")
+        raw = pts_t is None
+        if raw and len(out) != len(names):
+            raise ValueError("with raw device pointers out must hold an address for every requested channel")
+        fl = RTX_QUERY_SORT if sort else 0
+        buf = RtxQueryBuffers()
+        for name in out:
+            _, dt, k = QUERY_CHANNELS[name]
+            setattr(buf, name, self._query_out(name, out[name], dt, n, k, raw))
+        self._query_on_device({k: t for k, t in [("points", pts_t)] + [(f"out[{k!r}]", t) for k, t in out.items()] if hasattr(t, "device")})
+        for name in names:
+            if name not in out:
+                import torch
+                _, dt, k = QUERY_CHANNELS[name]
+                out[name] = torch.empty((n, k) if k > 1 else (n,), dtype=torch.float32 if dt == np.float32 else torch.int32, device=pts_t.device)
+                setattr(buf, name, out[name].data_ptr())
+        mask = sum(QUERY_CHANNELS[name][0] for name in names)
+
+        def launch():
+            self._chk(self.lib.rtx_query_nearest(self.ctx, ptr, n, mask, C.byref(buf), fl), "rtx_query_nearest")
+        tensors = [t for t in [pts_t] + list(out.values()) if hasattr(t, "record_stream")]
+        if tensors:
+            self._on_torch_stream(launch, tensors)
+        else:
+            launch()
+        return {name: out[name] for name in names}
+
     def debug_query_order(self, rows, n: Optional[int] = None):
-        """The order sort=True traces the rows in (rtx_debug_query_order): rows = float32 torch tensor (n, 6) of rays or (n, 7) of segments on
-        this context's GPU; returns the int32 tensor (n,): element first + i = the row traced in slot i of the round that starts at row
+        """The order sort=True traces the rows in (rtx_debug_query_order): rows = float32 torch tensor (n, 6) of rays, (n, 7) of segments or (n, 4) of
+        query_nearest points on this context's GPU; returns the int32 tensor (n,): element first + i = the row traced in slot i of the round that starts at row
         `first`.  Nothing is traced.  Queued on torch's current stream like the queries."""
         import torch
         width = rows.shape[1] if isinstance(rows, torch.Tensor) and rows.dim() == 2 else 0
-        if width not in (6, 7):
-            raise ValueError(f"rows must have shape (n, 6) or (n, 7), not {tuple(rows.shape) if isinstance(rows, torch.Tensor) else type(rows).__name__}")
+        if width not in (4, 6, 7):
+            raise ValueError(f"rows must have shape (n, 4), (n, 6) or (n, 7), not {tuple(rows.shape) if isinstance(rows, torch.Tensor) else type(rows).__name__}")
         ptr, n, rows_t = self._query_rows("rows", rows, width, n)
         self._query_on_device({"rows": rows_t})
         out = torch.empty((n,), dtype=torch.int32, device=rows_t.device)

@@ -22,7 +22,10 @@ EXPORTS = ["rtxh_camera_basis", "rtxh_camera_update", "rtxh_quaternion_axis_angl
            "rtxh_tlas_build", "rtxh_blas_build", "rtxh_blas_build_reference_bvh", "rtxh_blas_build_reference_sbvh", "rtxh_texture_mips", "rtxh_query_sort_order", "rtxh_texture_load", "rtxh_texture_free", "rtxh_sky_load", "rtxh_image_load", "rtxh_image_free", "rtxh_image_save_png", "rtxh_atrium_generate", "rtxh_mesh_free",
            "rtxh_obj_load", "rtxh_obj_free", "rtxh_mtl_load", "rtxh_bvh_cache_load", "rtxh_bvh_cache_save", "rtxh_bvh_cache_free",
            "rtxh_tlas_build_balanced", "rtxh_scene_update_balanced", "rtxh_tlas_balanced_node_count", "rtxh_tlas_balanced_inner_depth", "rtxh_blas_refit",
-           "rtxh_blas_build_balanced", "rtxh_blas_balanced_node_count", "rtxh_blas_balanced_inner_depth", "rtxh_vertex_normals"]
+           "rtxh_blas_build_balanced", "rtxh_blas_balanced_node_count", "rtxh_blas_balanced_inner_depth", "rtxh_vertex_normals",
+           "rtxh_query_nearest", "rtxh_query_nearest_exhaustive", "rtxh_nearest_distance_bound", "rtxh_nearest_box_d2", "rtxh_nearest_triangle_d2",
+           "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2"]
+FLOAT_EXPORTS = ("rtxh_nearest_distance_bound", "rtxh_nearest_box_d2", "rtxh_nearest_triangle_d2", "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2")      # return a float, not a status
 
 PI = np.float32(3.14159265359)          # Util.h:8
 
@@ -39,6 +42,18 @@ class RtxhObj(C.Structure):
 class RtxhBvhCache(C.Structure):
     _fields_ = [("triangle_count", C.c_int32), ("node_count", C.c_int32), ("index_count", C.c_int32), ("pad", C.c_int32),
                 ("hot", C.c_void_p), ("cold", C.c_void_p), ("nodes", C.c_void_p), ("indices", C.c_void_p)]
+
+
+class RtxhNearestBlas(C.Structure):
+    _fields_ = [("nodes", C.c_void_p), ("hot", C.c_void_p), ("cold", C.c_void_p),
+                ("node_count", C.c_int32), ("triangle_count", C.c_int32), ("material_offset", C.c_int32), ("pad", C.c_int32)]
+
+
+class RtxhNearestScene(C.Structure):
+    _fields_ = [("instances", C.c_void_p), ("tlas_nodes", C.c_void_p), ("tlas_indices", C.c_void_p), ("blas", C.POINTER(RtxhNearestBlas)),
+                ("spheres", C.c_void_p), ("planes", C.c_void_p),
+                ("instance_count", C.c_int32), ("tlas_node_count", C.c_int32), ("tlas_index_count", C.c_int32), ("blas_count", C.c_int32),
+                ("sphere_count", C.c_int32), ("plane_count", C.c_int32)]
 
 
 TEXNAME_MAX = 512
@@ -91,8 +106,15 @@ def lib():
         l.rtxh_blas_balanced_node_count.argtypes = [i32]
         l.rtxh_blas_balanced_inner_depth.argtypes = [i32]
         l.rtxh_vertex_normals.argtypes = [vp, vp, i32, i32, vp]
+        l.rtxh_query_nearest.argtypes = [C.POINTER(RtxhNearestScene), vp, C.c_int64, C.c_uint32, vp, C.POINTER(i32)]
+        l.rtxh_query_nearest_exhaustive.argtypes = [C.POINTER(RtxhNearestScene), vp, C.c_int64, C.c_uint32, vp]
+        l.rtxh_nearest_distance_bound.argtypes = [C.c_float, C.c_float]
+        l.rtxh_nearest_box_d2.argtypes = [vp, vp, vp]
+        l.rtxh_nearest_triangle_d2.argtypes = [vp, vp, vp]
+        l.rtxh_nearest_sphere_d2.argtypes = [vp, vp]
+        l.rtxh_nearest_plane_d2.argtypes = [vp, vp]
         for n in EXPORTS:
-            getattr(l, n).restype = C.c_int
+            getattr(l, n).restype = C.c_float if n in FLOAT_EXPORTS else C.c_int
         _lib = l
     return _lib
 
@@ -433,11 +455,11 @@ def save_bvh_cache(path: str, blas: sio.Blas) -> None:
 
 def query_sort_order(rows: np.ndarray) -> np.ndarray:
     """The order Renderer.query_closest / query_occluded trace rows in with sort=True (rtxh_query_sort_order, the code of
-    csrc/rtx_query_sort_math.h on the host): rows (n, 6) rays or (n, 7) segments, float32 -> int32 (n,), element first + i = the row in
-    slot i of the round that starts at row `first`."""
+    csrc/rtx_query_sort_math.h on the host): rows (n, 6) rays, (n, 7) segments or (n, 4) points of query_nearest, float32 -> int32 (n,),
+    element first + i = the row in slot i of the round that starts at row `first`."""
     rows = np.asarray(rows)
-    if rows.ndim != 2 or rows.shape[1] not in (6, 7) or rows.shape[0] < 1:
-        raise ValueError(f"rows must have shape (n, 6) or (n, 7) with n >= 1, not {rows.shape}")
+    if rows.ndim != 2 or rows.shape[1] not in (4, 6, 7) or rows.shape[0] < 1:
+        raise ValueError(f"rows must have shape (n, 4), (n, 6) or (n, 7) with n >= 1, not {rows.shape}")
     if rows.dtype != np.float32:
         raise TypeError(f"rows must be float32, not {rows.dtype}")
     rows = np.ascontiguousarray(rows)
@@ -446,6 +468,103 @@ def query_sort_order(rows: np.ndarray) -> np.ndarray:
     if rc:
         raise RuntimeError(f"rtxh_query_sort_order failed: {rc}")
     return order
+
+
+# ---- nearest-point queries on the host (include/rtx_host.h: rtxh_query_nearest / rtxh_query_nearest_exhaustive) ---------------------------
+NEAREST_CHANNELS = {"distance": (1, np.float32, 1), "position": (2, np.float32, 3), "normal": (4, np.float32, 3), "uv": (16, np.float32, 2),
+                    "material_id": (32, np.int32, 1), "object_id": (64, np.int32, 1), "triangle_id": (128, np.int32, 1)}      # rtx_query_buffers order
+
+
+class _NearestBuffers(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in NEAREST_CHANNELS]
+
+
+def nearest_scene(scene, blas=None):
+    """The arrays a nearest-point query reads, as (RtxhNearestScene, keep-alive list): scene = a scene_io.Scene, or a tuple / dict
+    (instances, tlas_nodes, tlas_indices[, spheres, planes]) as Renderer.read_frame_state() returns them, with blas = the list of
+    scene_io.Blas from Renderer.read_blas()."""
+    if isinstance(scene, sio.Scene):
+        inst, nodes, idx, spheres, planes = scene.instances, scene.tlas_nodes, scene.tlas_indices, scene.spheres, scene.planes
+        blas = scene.blas if blas is None else blas
+    else:
+        if isinstance(scene, dict):
+            scene = (scene["instances"], scene["tlas_nodes"], scene["tlas_indices"], scene.get("spheres"), scene.get("planes"))
+        inst, nodes, idx = scene[0], scene[1], scene[2]
+        spheres = scene[3] if len(scene) > 3 and scene[3] is not None else np.zeros(0, sio.SPHERE)
+        planes = scene[4] if len(scene) > 4 and scene[4] is not None else np.zeros(0, sio.PLANE)
+        if blas is None:
+            raise ValueError("frame-state arrays need blas = the list of scene_io.Blas")
+    arr = lambda a, dt: np.ascontiguousarray(a, dt)
+    inst, nodes, idx = arr(inst, sio.INSTANCE), arr(nodes, sio.BVH_NODE), arr(idx, np.int32)
+    spheres, planes = arr(spheres, sio.SPHERE), arr(planes, sio.PLANE)
+    keep = [inst, nodes, idx, spheres, planes]
+    table = (RtxhNearestBlas * max(1, len(blas)))()
+    for b, bl in enumerate(blas):
+        n, h, c = arr(bl.nodes, sio.BVH_NODE), arr(bl.tri_hot, sio.TRI_HOT), arr(bl.tri_cold, sio.TRI_COLD)
+        keep += [n, h, c]
+        table[b] = RtxhNearestBlas(n.ctypes.data, h.ctypes.data, c.ctypes.data, len(n), len(h), int(bl.material_offset), 0)
+    keep.append(table)
+    ptr = lambda a: a.ctypes.data if len(a) else None
+    s = RtxhNearestScene(ptr(inst), ptr(nodes), ptr(idx), table, ptr(spheres), ptr(planes), len(inst), len(nodes), len(idx), len(blas), len(spheres), len(planes))
+    return s, keep
+
+
+def _nearest_names(channels):
+    if isinstance(channels, (int, np.integer)) and not isinstance(channels, bool):
+        if int(channels) & ~247 or int(channels) <= 0:
+            raise ValueError(f"channel mask {channels} must be a non-empty subset of RTX_QUERY_ALL")
+        return tuple(n for n, (bit, _, _) in NEAREST_CHANNELS.items() if int(channels) & bit)
+    if isinstance(channels, str):
+        channels = (channels,)
+    want = set(channels)
+    bad = [n for n in want if n not in NEAREST_CHANNELS]
+    if bad or not want:
+        raise ValueError(f"channels must be names out of {', '.join(NEAREST_CHANNELS)}, at least one; not {sorted(map(str, want))}")
+    return tuple(n for n in NEAREST_CHANNELS if n in want)
+
+
+def _query_nearest(fn_name, scene, points, channels, blas, with_stack):
+    pts = np.asarray(points)
+    if pts.ndim != 2 or pts.shape[1] != 4 or pts.shape[0] < 1:
+        raise ValueError(f"points must have shape (n, 4) with n >= 1, not {pts.shape}")
+    if pts.dtype != np.float32:
+        raise TypeError(f"points must be float32, not {pts.dtype}")
+    pts = np.ascontiguousarray(pts)
+    names = _nearest_names(channels)
+    s, keep = nearest_scene(scene, blas)
+    n = pts.shape[0]
+    out = {name: np.zeros((n, NEAREST_CHANNELS[name][2]) if NEAREST_CHANNELS[name][2] > 1 else (n,), NEAREST_CHANNELS[name][1]) for name in names}
+    buf = _NearestBuffers()
+    for name in names:
+        setattr(buf, name, out[name].ctypes.data)
+    mask = sum(NEAREST_CHANNELS[name][0] for name in names)
+    high = C.c_int32(0)
+    if with_stack:
+        rc = lib().rtxh_query_nearest(C.byref(s), pts.ctypes.data, n, mask, C.byref(buf), C.byref(high))
+    else:
+        rc = lib().rtxh_query_nearest_exhaustive(C.byref(s), pts.ctypes.data, n, mask, C.byref(buf))
+    if rc:
+        raise ValueError(f"{fn_name} failed with status {rc}")
+    if with_stack:
+        out["stack_max"] = int(high.value)
+    return out
+
+
+def query_nearest(scene, points, channels=("distance",), blas=None) -> dict:
+    """rtxh_query_nearest: what Renderer.query_nearest writes on the device for points float32 (n, 4) of (x, y, z, maximum distance), from the
+    same code (csrc/rtx_nearest_math.h) -> {channel: array} plus "stack_max", the most stack entries a row held.  scene: a scene_io.Scene,
+    or the arrays of Renderer.read_frame_state() (+ spheres, planes) with blas = [Renderer.read_blas(b), ...]: see nearest_scene."""
+    return _query_nearest("rtxh_query_nearest", scene, points, channels, blas, True)
+
+
+def query_nearest_exhaustive(scene, points, channels=("distance",), blas=None) -> dict:
+    """rtxh_query_nearest_exhaustive: the same candidate functions over every primitive, no tree; ties to the lowest (kind, object, slot)."""
+    return _query_nearest("rtxh_query_nearest_exhaustive", scene, points, channels, blas, False)
+
+
+def nearest_distance_bound(local_scale, world_scale=0.0) -> float:
+    """rtxnp::distance_bound of csrc/rtx_nearest_math.h: how far the walk's distance may exceed the exhaustive minimum."""
+    return float(lib().rtxh_nearest_distance_bound(C.c_float(float(local_scale)), C.c_float(float(world_scale))))
 
 
 def texture_with_mips(level0_rgb: np.ndarray) -> sio.Texture:

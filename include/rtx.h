@@ -696,8 +696,40 @@ int rtx_query_occluded(rtx_ctx * ctx, const void * segments_dev /* [n][7] f32: o
                        int32_t * occluded_dev /* [n]: 1 or 0 */, uint32_t flags);
 /* The order RTX_QUERY_SORT traces n rows in, without tracing them: the bounds, key and sort launches of every round, then
  * order_out_dev[first + i] = first + the caller's row in slot i of the round that starts at row `first`.  row_floats: 6 (rays) or 7
- * (segments), anything else is RTX_ERR_INVALID_ARG; otherwise queued and checked like the query calls (n beyond INT32_MAX: RTX_ERR_LIMIT). */
-int rtx_debug_query_order(rtx_ctx * ctx, const void * rows_dev, int32_t row_floats /* 6 or 7 */, int64_t n, int32_t * order_out_dev);
+ * (segments) or 4 (the points of rtx_query_nearest, below), anything else is RTX_ERR_INVALID_ARG; otherwise queued and checked like the query calls (n beyond INT32_MAX: RTX_ERR_LIMIT). */
+int rtx_debug_query_order(rtx_ctx * ctx, const void * rows_dev, int32_t row_floats /* 4, 6 or 7 */, int64_t n, int32_t * order_out_dev);
+
+/* ---- nearest-point queries -------------------------------------------------------------------------------------------------------------
+ * "How far is this point from the scene, and where is the nearest surface point": for contact and collision probes, cloth and particle
+ * steps, deformations that must stay near a surface.  rtx_query_nearest: row i = points_dev[4i .. 4i+3] = (x, y, z, maximum distance), fp32 at
+ * any 4-byte aligned address in DEVICE memory; the scene is the frame the context holds, device-side updates (rtx_update_instances,
+ * rtx_refit_blas, rtx_build_blas) included.  Queued on the context's stream, returns at once, nothing is read back; a steady-state call
+ * allocates and frees nothing.  Works with bounces == 0 and without lights; touches no queue, frame or counter of a render call.
+ * Channels and rtx_query_buffers are those of rtx_query_closest (RTX_QUERY_* bits); a channel is written only if its bit is set and its
+ * pointer is not NULL; element i belongs to row i; nothing beyond element n - 1 is touched.
+ * Channel                answer                                                                        no answer
+ *   DISTANCE             sqrtf of the winning squared distance                                           +INFINITY
+ *   POSITION             the nearest surface point, world space                                          0
+ *   NORMAL, UV           what RayHit::normal, u, v would hold at that point                              0
+ *   MATERIAL_ID, OBJECT_ID, TRIANGLE_ID   the numberings of rtx_query_closest                            -1
+ * No answer: nothing lies strictly nearer than the maximum distance; x, y or z is NaN or infinite; the maximum distance is NaN or not above
+ * 0; the point is so remote that every squared distance overflows.  +INFINITY is a legal maximum distance.
+ * The arithmetic, the order of the walk (which fixes who wins an exact tie) and the accuracy bound are specified in the header comment of
+ * csrc/rtx_nearest_math.h; rtxh_query_nearest in rtx_host.h is the same code on the host and gives the same bits.
+ * Any n >= 1, in rounds of RTX_QUERY_CHUNK_RAYS rows, one kernel launch per round.  flags: RTX_QUERY_SORT or 0.  With RTX_QUERY_SORT the
+ * rows of a round are walked in the Morton order of their points (rows without an answer by rule last, unwalked) and the answers scattered
+ * back: bit-identical, row for row; the sort scratch and its growth rule are those of the ray queries.
+ * Errors, in this order: RTX_ERR_INVALID_ARG: channels == 0 or with bits outside RTX_QUERY_ALL; a NULL ctx, points_dev or out, n < 1; any
+ * flag but RTX_QUERY_SORT.  RTX_ERR_STATE: before rtx_set_frame, in heat-map mode, a scene a render call refuses.  RTX_ERR_LIMIT: a BVH
+ * deeper than rtx_config.stack_size allows (the check of rtx_render_tiles); and the walk's own stack rule: it holds at most (TLAS inner
+ * depth + 1) + (deepest BLAS inner depth + 1) entries (inner depth: that of the deepest inner node, root 0; -1 for a single leaf), and a
+ * scene that needs more than rtx_config.stack_size is refused.  An error queues nothing.
+ * Limits: distances are measured in each instance's LOCAL space — for the rigid poses Mesh::update and rtx_update_instances make from unit
+ * quaternions that is the world metric up to rounding; a scaled world matrix handed to rtx_set_frame is measured in its local units.  The
+ * answer may depend on the tree within the bound: a refit, or a rebuild of the same triangles, may return another triangle at an equal
+ * or nearly equal distance.  Out of scope: signed distance, k nearest, all within a radius, barycentrics, the rtx_group_* path.        */
+int rtx_query_nearest(rtx_ctx * ctx, const void * points_dev /* [n][4] f32: x, y, z, maximum distance */, int64_t n,
+                      uint32_t channels, const rtx_query_buffers * out, uint32_t flags);
 
 /* Timing of every kernel launched since rtx_enable_kernel_timing(ctx, 1),
  * measured with HIP events on the stream the kernels are launched on.

@@ -37,6 +37,8 @@
  *   rtxh_bvh_cache_*         BottomLevelBVH::save_to_disk / load_from_disk   BottomLevelBVH.cpp:149-192
  *   rtxh_texture_mips        Texture::load's box-filter mip chain          Texture.cpp:76-117
  *   rtxh_query_sort_order    the order RTX_QUERY_SORT traces query rows in, from the same code (csrc/rtx_query_sort_math.h)
+ *   rtxh_query_nearest       rtx_query_nearest on the host: the walk and the arithmetic of csrc/rtx_nearest_math.h over plain arrays;
+ *                            rtxh_query_nearest_exhaustive the same candidate functions over every primitive, without a tree
  *   rtxh_texture_load        Texture::load: PNG / TGA file -> linear float3 texels + mips   Texture.cpp:30-129
  *   rtxh_image_load          the stbi_load(..., STBI_rgb_alpha) call inside it  Texture.cpp:40
  *   rtxh_sky_load            Sky::Sky: raw float3 angular-map probe file         Sky.cpp:8-26
@@ -191,9 +193,39 @@ int rtxh_texture_mips(float * texels_rgb, int32_t width, int32_t height, rtx_tex
  * rows: n x row_floats floats (6: origin, direction; 7: with a maximum distance).  Per round of at most RTX_QUERY_CHUNK_RAYS rows the bounds
  * of the live rows, the key of every row (csrc/rtx_query_sort_math.h, the code the kernels compile) and a sort of the keys:
  * order_out[first + i] = first + the row in slot i of the round that starts at `first`.  Dead rows (zero direction, a non-finite origin or
- * direction, a NaN maximum distance) come last in row order.  RTX_ERR_INVALID_ARG: a null pointer, n < 1, row_floats other than 6 or 7;
- * RTX_ERR_LIMIT: n beyond INT32_MAX.                                                                                                  */
+ * direction, a NaN maximum distance) come last in row order.  row_floats 4: the points of rtx_query_nearest (x, y, z, maximum distance) — live with
+ * finite x, y, z and a maximum distance > 0, sorted by the Morton code of the point alone.  RTX_ERR_INVALID_ARG: a null pointer, n < 1,
+ * row_floats other than 4, 6 or 7; RTX_ERR_LIMIT: n beyond INT32_MAX.                                                                 */
 int rtxh_query_sort_order(const float * rows, int32_t row_floats, int64_t n, int32_t * order_out);
+
+/* rtx_query_nearest (include/rtx.h) on the host, by the code the kernel runs (csrc/rtx_nearest_math.h, whose header comment is the
+ * specification: candidate functions, the order of the walk, the stack count, the accuracy bound).  The scene as plain arrays: what a
+ * scene file holds, or what rtx_read_frame_state / rtx_read_blas return, so a device-updated scene can be checked.  points: n x 4 floats
+ * (x, y, z, maximum distance); channels and out as for rtx_query_nearest, with host pointers; the answers are the device's bit for bit.
+ * stack_max_out (may be NULL): the most stack entries any row held.
+ * rtxh_query_nearest_exhaustive: the same candidate functions over every sphere, plane and (instance, slot) without a tree; an exact tie
+ * goes to the lowest (kind, object, slot), kinds in the order sphere, plane, triangle.  The walk's distance is never below the exhaustive
+ * one and exceeds it by at most rtxh_nearest_distance_bound(S, W) of the exhaustive winner (S = |p_l - p0| + |e1| + |e2|; W = |p| + |p_l|
+ * for an instance whose matrix is not the identity, else 0).
+ * RTX_ERR_INVALID_ARG: a null scene / points / out, n < 1, channels 0 or outside RTX_QUERY_ALL, a negative count, a count without its
+ * array, an instance whose blas_id is outside [0, blas_count); RTX_ERR_LIMIT: a tree deeper than RTX_MAX_STACK entries of the walk.     */
+typedef struct rtxh_nearest_blas {
+    const rtx_bvh_node * nodes; const rtx_triangle_hot * hot; const rtx_triangle_cold * cold;
+    int32_t node_count, triangle_count, material_offset, pad;
+} rtxh_nearest_blas;
+typedef struct rtxh_nearest_scene {
+    const rtx_instance * instances; const rtx_bvh_node * tlas_nodes; const int32_t * tlas_indices; const rtxh_nearest_blas * blas;
+    const rtx_sphere * spheres; const rtx_plane * planes;
+    int32_t instance_count, tlas_node_count, tlas_index_count, blas_count, sphere_count, plane_count;
+} rtxh_nearest_scene;
+int rtxh_query_nearest(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out, int32_t * stack_max_out);
+int rtxh_query_nearest_exhaustive(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out);
+float rtxh_nearest_distance_bound(float local_scale, float world_scale);
+/* the candidate functions on their own, for tests that restate them: squared distances (and the triangle's weights) */
+float rtxh_nearest_box_d2(const float p[3], const float box_min[3], const float box_max[3]);
+float rtxh_nearest_triangle_d2(const float p[3], const rtx_triangle_hot * tri, float uv_out[2]);
+float rtxh_nearest_sphere_d2(const float p[3], const rtx_sphere * sphere);
+float rtxh_nearest_plane_d2(const float p[3], const rtx_plane * plane);
 
 /* Texture::load (Texture.cpp:30-129): decodes a .png or .tga file the way the reference's vendored stb_image v2.19 does with
  * STBI_rgb_alpha (Texture.cpp:40), converts r,g,b bytes to linear light (colour_unpack :13-20, Math::gamma_to_linear Math.h:67-77;
