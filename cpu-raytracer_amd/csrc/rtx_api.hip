@@ -34,6 +34,7 @@
 #include "rtx_normals.h"
 #include "rtx_query.h"
 #include "rtx_nearest.h"
+#include "rtx_hits.h"
 #include "rtx_texmip.h"
 #include <rocprim/device/device_radix_sort.hpp>      // rtx_update_instances, scenes beyond one workgroup: header-only, part of ROCm
 #include "rtx_hostmem.h"                             // DevBuf, StageRing, grow_keep: every device and pinned allocation has one owner
@@ -2321,6 +2322,63 @@ extern "C" int rtx_query_nearest(rtx_ctx * c, const void * points_dev, int64_t n
         const uint64_t * const order = sorted ? S.keys : nullptr;
         if (head) HIP_OK(c, hipMemsetAsync(head, 0, sizeof(uint32_t), c->stream));
         launch_timed(c, "k_query_nearest", c->stream, [&] { hipLaunchKernelGGL(k_query_nearest, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head); });
+    }
+    HIP_OK(c, hipGetLastError());
+    return RTX_OK;
+}
+
+// ---- all-hits segment queries (include/rtx.h: rtx_query_hits; kernel in rtx_hits.h, arithmetic and walk in rtx_hits_math.h) ------------
+// n segments in device memory against the frame the context holds: per round of at most RTX_QUERY_CHUNK_RAYS rows ONE launch of k_query_hits,
+// which reads the rows and writes the first max_hits hits of every row, in order, and the row's count; with RTX_QUERY_SORT the bounds, key and
+// sort launches of the ray queries run first over the 7-float rows, in the same sort block.  No queue set, no counters; the stack as for
+// rtx_query_nearest, its stack rule, and its tile counter (the two calls are ordered by the stream).
+extern "C" int rtx_query_hits(rtx_ctx * c, const void * segments_dev, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
+                              int32_t * count_dev, uint32_t flags) {
+    if (c) {
+        const bool count_only = max_hits == 0 && channels == 0 && count_dev;
+        if (!count_only && (max_hits < 1 || max_hits > (int32_t)RTX_QUERY_MAX_HITS || channels == 0 || (channels & ~(uint32_t)RTX_QUERY_ALL))) {
+            c->err = "rtx_query_hits: max_hits must be in [1, RTX_QUERY_MAX_HITS] with channels a non-empty subset of RTX_QUERY_ALL, or max_hits == 0 and channels == 0 with a count_dev";
+            return RTX_ERR_INVALID_ARG;
+        }
+    }
+    if (int bad = query_checks(c, segments_dev, n, max_hits ? (const void *)out : (const void *)count_dev, flags, "rtx_query_hits", (uint32_t)RTX_QUERY_SORT)) return bad;
+    int blas_depth = -1;
+    for (size_t b = 0; b < c->blas.size(); b++) if (c->h_blas[b].nodes && c->blas[b].inner_depth > blas_depth) blas_depth = c->blas[b].inner_depth;
+    const int need = rtxnp::stack_need(c->tlas_inner_depth, blas_depth), have = c->cfg.stack_size < RTX_MAX_STACK ? c->cfg.stack_size : RTX_MAX_STACK;
+    if (need > have) {
+        c->err = "rtx_query_hits: the ordered descent needs " + std::to_string(need) + " stack entries (TLAS inner depth " + std::to_string(c->tlas_inner_depth) +
+                 " + 1, BLAS inner depth " + std::to_string(blas_depth) + " + 1), rtx_config.stack_size allows " + std::to_string(have);
+        return RTX_ERR_LIMIT;
+    }
+    hipSetDevice(c->cfg.device);
+    const bool sorted = (flags & RTX_QUERY_SORT) != 0;
+    QuerySort S = {};
+    DevQueues unused;
+    if (sorted) if (int rc = query_queues(c, n, unused, &S, false)) return rc;
+    if (int rc = ensure(c, c->d_nearest_head, sizeof(uint32_t))) return rc;      // the first call only
+    uint32_t * const head = (uint32_t *)c->d_nearest_head.p;
+    const DevScene sc = c->scene;
+    const int max_blocks = c->q.spill_threads / RTX_QUERY_BLOCK;                  // the spill regions are indexed by the global thread id
+    const int64_t K = max_hits;
+    for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
+        const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
+        const float * const rows = (const float *)segments_dev + 7 * first;
+        DevQuery t = {};
+        auto on = [&](uint32_t bit) { return K > 0 && (channels & bit) != 0; };
+        t.distance = on(RTX_QUERY_DISTANCE) && out->distance ? out->distance + K * first : nullptr;
+        t.position = on(RTX_QUERY_POSITION) && out->position ? out->position + 3 * K * first : nullptr;
+        t.normal = on(RTX_QUERY_NORMAL) && out->normal ? out->normal + 3 * K * first : nullptr;
+        t.uv = on(RTX_QUERY_UV) && out->uv ? out->uv + 2 * K * first : nullptr;
+        t.material_id = on(RTX_QUERY_MATERIAL_ID) && out->material_id ? out->material_id + K * first : nullptr;
+        t.object_id = on(RTX_QUERY_OBJECT_ID) && out->object_id ? out->object_id + K * first : nullptr;
+        t.triangle_id = on(RTX_QUERY_TRIANGLE_ID) && out->triangle_id ? out->triangle_id + K * first : nullptr;
+        int32_t * const count = count_dev ? count_dev + first : nullptr;
+        if (sorted) if (int rc = query_sort_round<7>(c, S, rows, m)) return rc;
+        const int tiles = (m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK, blocks = tiles < max_blocks ? tiles : max_blocks;
+        const uint64_t * const order = sorted ? S.keys : nullptr;
+        HIP_OK(c, hipMemsetAsync(head, 0, sizeof(uint32_t), c->stream));
+        if (K > 0) launch_timed(c, "k_query_hits", c->stream, [&] { hipLaunchKernelGGL(k_query_hits<true>, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, (int)K, t, count, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head); });
+        else launch_timed(c, "k_query_hits", c->stream, [&] { hipLaunchKernelGGL(k_query_hits<false>, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, 0, t, count, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head); });
     }
     HIP_OK(c, hipGetLastError());
     return RTX_OK;

@@ -12,6 +12,7 @@
 #include "../csrc/rtx_texmip_math.h"
 #include "../csrc/rtx_query_sort_math.h"
 #include "../csrc/rtx_nearest_math.h"
+#include "../csrc/rtx_hits_math.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -740,6 +741,120 @@ extern "C" float rtxh_nearest_triangle_d2(const float p[3], const rtx_triangle_h
 }
 extern "C" float rtxh_nearest_sphere_d2(const float p[3], const rtx_sphere * sphere) { return rtxnp::sphere_d2(rtxnp::ptr3(p), rtxnp::ptr3(sphere->center), sphere->radius_squared); }
 extern "C" float rtxh_nearest_plane_d2(const float p[3], const rtx_plane * plane) { return rtxnp::plane_d2(rtxnp::ptr3(p), rtxnp::ptr3(plane->normal), plane->distance); }
+
+// =================================================================================================
+// rtx_query_hits on the host: rtxhp::walk (csrc/rtx_hits_math.h) over the arrays of rtxh_query_nearest, and the exhaustive search
+namespace {
+struct HostHitsScene : HostNearestScene {
+    explicit HostHitsScene(const rtxh_nearest_scene & sc) : HostNearestScene{ sc } {}
+    int instance_count() const { return s.instance_count; }
+    int enter(int slot, rtxnp::P3 o, rtxnp::P3 d, rtxnp::P3 & co, rtxnp::P3 & cd) {
+        const int inst = s.tlas_indices[slot];
+        co = rtxnp::xform_pos(s.instances[inst].world_inv, o);
+        cd = rtxnp::xform_dir(s.instances[inst].world_inv, d);
+        B = &s.blas[s.instances[inst].blas_id];
+        return inst;
+    }
+};
+struct HostHitsList {
+    float t[rtxhp::MAX_HITS]; int32_t object[rtxhp::MAX_HITS], triangle[rtxhp::MAX_HITS];
+    void get(int j, float & t_, int32_t & o_, int32_t & s_) const { t_ = t[j]; o_ = object[j]; s_ = triangle[j]; }
+    void set(int j, float t_, int32_t o_, int32_t s_) { t[j] = t_; object[j] = o_; triangle[j] = s_; }
+};
+int hits_args_check(const rtxh_nearest_scene * s, const float * segments, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out, const int32_t * count_out, bool trees) {
+    const bool count_only = max_hits == 0 && channels == 0 && count_out;
+    if (!count_only && (max_hits < 1 || max_hits > rtxhp::MAX_HITS || channels == 0 || (channels & ~(uint32_t)RTX_QUERY_ALL) || !out)) return RTX_ERR_INVALID_ARG;
+    const rtx_query_buffers none = {};
+    return nearest_scene_check(s, segments, n, count_only ? (uint32_t)RTX_QUERY_DISTANCE : channels, count_only ? &none : out, trees);
+}
+// the channels of the K entries of row i from its list: what k_query_hits stores
+void hit_write(const rtxh_nearest_scene & s, const float * row, const HostHitsList & L, int held, int K, int64_t i, uint32_t channels, const rtx_query_buffers & out) {
+    auto on = [&](uint32_t bit) { return (channels & bit) != 0; };
+    const rtxnp::P3 o = rtxnp::mk(row[0], row[1], row[2]), d = rtxnp::mk(row[3], row[4], row[5]);
+    for (int j = 0; j < K; j++) {
+        const size_t e = (size_t)i * (size_t)K + (size_t)j;
+        const bool hit = j < held;
+        rtxnp::P3 point = rtxnp::mk(0.0f, 0.0f, 0.0f), normal = point;
+        float tu = 0.0f, tv = 0.0f; int material = -1;
+        const float t = hit ? L.t[j] : INFINITY;
+        const int32_t object = hit ? L.object[j] : -1, triangle = hit ? L.triangle[j] : -1;
+        if (hit && triangle >= 0) {
+            const rtx_instance & I = s.instances[object];
+            const rtxh_nearest_blas & B = s.blas[I.blas_id];
+            const rtx_triangle_hot & h = B.hot[triangle]; const rtx_triangle_cold & c = B.cold[triangle];
+            const rtxnp::P3 co = rtxnp::xform_pos(I.world_inv, o), cd = rtxnp::xform_dir(I.world_inv, d);
+            point = rtxnp::xform_pos(I.world, rtxhp::point_at(co, cd, t));
+            float t2, u = 0.0f, v = 0.0f;
+            rtxhp::tri_test(rtxnp::ptr3(h.position_0), rtxnp::ptr3(h.position_edge_1), rtxnp::ptr3(h.position_edge_2), co, cd, row[6], t2, u, v);
+            rtxnp::triangle_outputs(I.world, rtxnp::ptr3(c.normal_0), rtxnp::ptr3(c.normal_edge_1), rtxnp::ptr3(c.normal_edge_2), c.tex_coord_0, c.tex_coord_edge_1, c.tex_coord_edge_2, u, v, normal, tu, tv);
+            material = B.material_offset + c.material_id;
+        } else if (hit && object < s.instance_count + s.sphere_count) {
+            const rtx_sphere & sp = s.spheres[object - s.instance_count];
+            rtxhp::sphere_outputs(o, d, t, rtxnp::ptr3(sp.center), sp.radius_inv, point, normal, tu, tv); material = sp.material_id;
+        } else if (hit) {
+            const rtx_plane & pl = s.planes[object - s.instance_count - s.sphere_count];
+            rtxhp::plane_outputs(o, d, t, rtxnp::ptr3(pl.normal), rtxnp::ptr3(pl.u_axis), rtxnp::ptr3(pl.v_axis), point, normal, tu, tv); material = pl.material_id;
+        }
+        if (on(RTX_QUERY_DISTANCE) && out.distance) out.distance[e] = t;
+        if (on(RTX_QUERY_POSITION) && out.position) { out.position[3 * e] = point.x; out.position[3 * e + 1] = point.y; out.position[3 * e + 2] = point.z; }
+        if (on(RTX_QUERY_NORMAL) && out.normal) { out.normal[3 * e] = normal.x; out.normal[3 * e + 1] = normal.y; out.normal[3 * e + 2] = normal.z; }
+        if (on(RTX_QUERY_UV) && out.uv) { out.uv[2 * e] = tu; out.uv[2 * e + 1] = tv; }
+        if (on(RTX_QUERY_MATERIAL_ID) && out.material_id) out.material_id[e] = material;
+        if (on(RTX_QUERY_OBJECT_ID) && out.object_id) out.object_id[e] = object;
+        if (on(RTX_QUERY_TRIANGLE_ID) && out.triangle_id) out.triangle_id[e] = triangle;
+    }
+}
+}  // namespace
+
+extern "C" int rtxh_query_hits(const rtxh_nearest_scene * scene, const float * segments, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
+                               int32_t * count_out, int32_t * stack_max_out) {
+    if (int rc = hits_args_check(scene, segments, n, max_hits, channels, out, count_out, true)) return rc;
+    int high = 0;
+    for (int64_t i = 0; i < n; i++) {
+        HostHitsScene S(*scene);
+        HostNearestStack st;
+        HostHitsList L;
+        rtxhp::Tally w;
+        rtxhp::walk(S, st, L, segments + 7 * i, max_hits, count_out != nullptr, w);
+        if (st.high > high) high = st.high;
+        if (count_out) count_out[i] = w.count;
+        if (max_hits) hit_write(*scene, segments + 7 * i, L, w.held, max_hits, i, channels, *out);
+    }
+    if (stack_max_out) *stack_max_out = high;
+    return RTX_OK;
+}
+
+extern "C" int rtxh_query_hits_exhaustive(const rtxh_nearest_scene * scene, const float * segments, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
+                                          int32_t * count_out) {
+    if (int rc = hits_args_check(scene, segments, n, max_hits, channels, out, count_out, false)) return rc;
+    const rtxh_nearest_scene & s = *scene;
+    for (int64_t i = 0; i < n; i++) {
+        const float * row = segments + 7 * i;
+        HostHitsScene S(s);
+        HostHitsList L;
+        rtxhp::Tally w; w.count = 0; w.held = 0; w.bound = 0.0f;
+        if (rtxhp::row_is_live(row)) {
+            const rtxnp::P3 o = rtxnp::mk(row[0], row[1], row[2]), d = rtxnp::mk(row[3], row[4], row[5]);
+            const float D = row[6];
+            w.bound = D;
+            rtxhp::world_primitives(S, L, max_hits, false, w, o, d, D);
+            for (int k = 0; k < s.instance_count; k++) {
+                const rtxnp::P3 co = rtxnp::xform_pos(s.instances[k].world_inv, o), cd = rtxnp::xform_dir(s.instances[k].world_inv, d);
+                const rtxh_nearest_blas & B = s.blas[s.instances[k].blas_id];
+                for (int t = 0; t < B.triangle_count; t++) {
+                    float th, u, v;
+                    if (rtxhp::tri_test(rtxnp::ptr3(B.hot[t].position_0), rtxnp::ptr3(B.hot[t].position_edge_1), rtxnp::ptr3(B.hot[t].position_edge_2), co, cd, D, th, u, v))
+                        rtxhp::offer(L, max_hits, false, w, th, k, t);
+                }
+            }
+        }
+        if (count_out) count_out[i] = w.count;
+        if (max_hits) hit_write(s, row, L, w.held, max_hits, i, channels, *out);
+    }
+    return RTX_OK;
+}
+
+extern "C" float rtxh_hits_margin(float kappa, float scale) { return rtxhp::margin(kappa, scale); }
 
 // =================================================================================================
 // Procedural atrium: a seeded Sponza-class stand-in (the real sponza.obj is absent from the mount).

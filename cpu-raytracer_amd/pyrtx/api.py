@@ -28,7 +28,7 @@ EXPORTS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error", "rt
            "rtx_bind_blas_vertices", "rtx_refit_blas", "rtx_read_blas", "rtx_alloc_blas", "rtx_build_blas",
            "rtx_query_closest", "rtx_query_occluded", "rtx_debug_query_order", "rtx_debug_read_layouts",
            "rtx_alloc_texture", "rtx_update_texture", "rtx_read_texture", "rtx_update_sky",
-           "rtx_alloc_blas_topology", "rtx_set_blas_topology", "rtx_blas_vertex_normals", "rtx_query_nearest"]
+           "rtx_alloc_blas_topology", "rtx_set_blas_topology", "rtx_blas_vertex_normals", "rtx_query_nearest", "rtx_query_hits"]
 # newer than the A/B variants tools/ab.py may load (RTX_HIP_LIB = a library built from an older commit): bound when the library has them,
 # otherwise a call raises AttributeError (undefined symbol)
 VIEW_EXPORTS = ("rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer")
@@ -43,6 +43,8 @@ LAYOUT_EXPORTS = ("rtx_debug_read_layouts",)
 TEXTURE_EXPORTS = ("rtx_alloc_texture", "rtx_update_texture", "rtx_read_texture", "rtx_update_sky")
 NORMALS_EXPORTS = ("rtx_alloc_blas_topology", "rtx_set_blas_topology", "rtx_blas_vertex_normals")
 NEAREST_EXPORTS = ("rtx_query_nearest",)
+HITS_EXPORTS = ("rtx_query_hits",)
+RTX_QUERY_MAX_HITS = 8
 # texel formats of rtx_update_texture (include/rtx.h RTX_TEXELS_*)
 RTX_TEXELS_RGB_F32 = 0
 RTX_TEXELS_RGBA8_SRGB = 1
@@ -166,6 +168,8 @@ def load_library(path: Optional[str] = None):
         lib.rtx_query_occluded.argtypes = [vp, vp, C.c_int64, vp, u32]
     if hasattr(lib, "rtx_query_nearest"):
         lib.rtx_query_nearest.argtypes = [vp, vp, C.c_int64, u32, C.POINTER(RtxQueryBuffers), u32]
+    if hasattr(lib, "rtx_query_hits"):
+        lib.rtx_query_hits.argtypes = [vp, vp, C.c_int64, i32, u32, C.POINTER(RtxQueryBuffers), vp, u32]
     if hasattr(lib, "rtx_debug_query_order"):
         lib.rtx_debug_query_order.argtypes = [vp, vp, i32, C.c_int64, vp]
     if hasattr(lib, "rtx_debug_read_layouts"):
@@ -180,7 +184,7 @@ def load_library(path: Optional[str] = None):
         lib.rtx_set_blas_topology.argtypes = [vp, i32, vp]
         lib.rtx_blas_vertex_normals.argtypes = [vp, i32, vp, vp]
     for name in EXPORTS:
-        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + QUERY_SORT_EXPORTS + LAYOUT_EXPORTS + TEXTURE_EXPORTS + NORMALS_EXPORTS + NEAREST_EXPORTS and not hasattr(lib, name):
+        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + QUERY_SORT_EXPORTS + LAYOUT_EXPORTS + TEXTURE_EXPORTS + NORMALS_EXPORTS + NEAREST_EXPORTS + HITS_EXPORTS and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         if name not in ("rtx_last_error",):
@@ -1029,8 +1033,14 @@ class Renderer:
             raise ValueError(f"n must be in [1, {rows.shape[0]}] for {name} of shape {tuple(rows.shape)}, not {n}")
         return rows.data_ptr(), int(n), rows
 
-    def _query_out(self, name: str, t, dtype, n: int, k: int, raw: bool):
-        """Device pointer of an output: a caller tensor of n rows (checked), or with raw inputs a raw device pointer."""
+    @staticmethod
+    def _query_shape(n: int, k: int, hits: int = 0) -> tuple:
+        """Shape of a query channel of width k: (n,) or (n, k); with `hits` entries per row (query_hits) (n, hits) or (n, hits, k)."""
+        return (n,) + ((hits,) if hits else ()) + ((k,) if k > 1 else ())
+
+    def _query_out(self, name: str, t, dtype, n: int, k: int, raw: bool, hits: int = 0):
+        """Device pointer of an output: a caller tensor of n rows (checked; `hits` entries per row for query_hits), or with raw inputs a
+        raw device pointer."""
         if raw and isinstance(t, (int, np.integer)) and not isinstance(t, bool):
             if not t:
                 raise ValueError(f"out[{name!r}] is a null device pointer")
@@ -1041,7 +1051,7 @@ class Renderer:
             raise TypeError(f"out[{name!r}] must be a torch.Tensor, not {type(t).__name__}")
         if t.dtype != want_dt:
             raise TypeError(f"out[{name!r}] must be {want_dt}, not {t.dtype}")
-        shape = (n, k) if k > 1 else (n,)
+        shape = self._query_shape(n, k, hits)
         if tuple(t.shape) != shape:
             raise ValueError(f"out[{name!r}] must have shape {shape}, not {tuple(t.shape)}")
         if not t.is_contiguous():
@@ -1173,6 +1183,75 @@ class Renderer:
         else:
             launch()
         return {name: out[name] for name in names}
+
+    def query_hits(self, segments, max_hits: int = 4, channels=("distance",), count: bool = True, out: Optional[Dict] = None, n: Optional[int] = None,
+                   sort: bool = False) -> Dict:
+        """Every hit along n segments against the frame the context holds (rtx_query_hits): segments = float32 torch tensor (n, 7) of (origin,
+        direction, max distance) on this context's GPU, the rows of query_occluded.  Returns {name: tensor} of the nearest max_hits hits of
+        every row in ascending order — (n, K), (n, K, 3) or (n, K, 2), K = max_hits in [1, 8], channels as for query_closest — plus "count",
+        the int32 tensor (n,) of the row's hits (it may exceed K), unless count=False.  Entries past min(count, K): distance inf, ids -1, the
+        rest 0.  A sphere counts at both crossings; a dead row (zero direction, a non-finite component, a max distance that is NaN or not above
+        0) has count 0.  max_hits=0 with channels=() returns the count only.  out = {name: tensor} supplies the tensors ("count" included).
+        Queued on torch's current stream, checked like query_nearest; sort=True (RTX_QUERY_SORT): same answers row for row.  Raw device
+        pointers: segments = address, n, out = {name: address} for every channel wanted and for "count" if count."""
+        if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)):
+            raise TypeError(f"max_hits must be an int, not {type(max_hits).__name__}")
+        K = int(max_hits)
+        if not 0 <= K <= RTX_QUERY_MAX_HITS:
+            raise ValueError(f"max_hits must be in [0, {RTX_QUERY_MAX_HITS}], not {K}")
+        empty = not isinstance(channels, (str, int, np.integer)) and len(tuple(channels)) == 0 or (isinstance(channels, (int, np.integer)) and not isinstance(channels, bool) and int(channels) == 0)
+        if K == 0:
+            if not empty:
+                raise ValueError("max_hits=0 is the count-only form: channels must be ()")
+            if not count:
+                raise ValueError("max_hits=0 is the count-only form: count must be True")
+            names = ()
+        else:
+            names = query_names(channels)
+        ptr, n, seg_t = self._query_rows("segments", segments, 7, n)
+        if out is not None and not isinstance(out, dict):
+            raise TypeError(f"out must be a dict {{channel name: tensor}}, not {type(out).__name__}")
+        out = dict(out or {})
+        wanted = names + (("count",) if count else ())
+        for k in out:
+            if k != "count":
+                query_names((k,))
+        extra = [k for k in out if k not in wanted]
+        if extra:
+            raise ValueError(f"out holds channels that were not requested: {', '.join(extra)}")
+        raw = seg_t is None
+        if raw and len(out) != len(wanted):
+            raise ValueError("with raw device pointers out must hold an address for every requested channel and for the count")
+        fl = RTX_QUERY_SORT if sort else 0
+        buf = RtxQueryBuffers()
+        cptr = None
+        for name in out:
+            if name == "count":
+                cptr = self._query_out("count", out[name], np.int32, n, 1, raw)
+            else:
+                _, dt, k = QUERY_CHANNELS[name]
+                setattr(buf, name, self._query_out(name, out[name], dt, n, k, raw, K))
+        self._query_on_device({k: t for k, t in [("segments", seg_t)] + [(f"out[{k!r}]", t) for k, t in out.items()] if hasattr(t, "device")})
+        for name in wanted:
+            if name not in out:
+                import torch
+                if name == "count":
+                    out[name] = torch.empty((n,), dtype=torch.int32, device=seg_t.device)
+                    cptr = out[name].data_ptr()
+                else:
+                    _, dt, k = QUERY_CHANNELS[name]
+                    out[name] = torch.empty(self._query_shape(n, k, K), dtype=torch.float32 if dt == np.float32 else torch.int32, device=seg_t.device)
+                    setattr(buf, name, out[name].data_ptr())
+        mask = sum(QUERY_CHANNELS[name][0] for name in names)
+
+        def launch():
+            self._chk(self.lib.rtx_query_hits(self.ctx, ptr, n, K, mask, C.byref(buf), cptr, fl), "rtx_query_hits")
+        tensors = [t for t in [seg_t] + list(out.values()) if hasattr(t, "record_stream")]
+        if tensors:
+            self._on_torch_stream(launch, tensors)
+        else:
+            launch()
+        return {name: out[name] for name in wanted}
 
     def debug_query_order(self, rows, n: Optional[int] = None):
         """The order sort=True traces the rows in (rtx_debug_query_order): rows = float32 torch tensor (n, 6) of rays, (n, 7) of segments or (n, 4) of

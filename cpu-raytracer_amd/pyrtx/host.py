@@ -24,8 +24,8 @@ EXPORTS = ["rtxh_camera_basis", "rtxh_camera_update", "rtxh_quaternion_axis_angl
            "rtxh_tlas_build_balanced", "rtxh_scene_update_balanced", "rtxh_tlas_balanced_node_count", "rtxh_tlas_balanced_inner_depth", "rtxh_blas_refit",
            "rtxh_blas_build_balanced", "rtxh_blas_balanced_node_count", "rtxh_blas_balanced_inner_depth", "rtxh_vertex_normals",
            "rtxh_query_nearest", "rtxh_query_nearest_exhaustive", "rtxh_nearest_distance_bound", "rtxh_nearest_box_d2", "rtxh_nearest_triangle_d2",
-           "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2"]
-FLOAT_EXPORTS = ("rtxh_nearest_distance_bound", "rtxh_nearest_box_d2", "rtxh_nearest_triangle_d2", "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2")      # return a float, not a status
+           "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2", "rtxh_query_hits", "rtxh_query_hits_exhaustive", "rtxh_hits_margin"]
+FLOAT_EXPORTS = ("rtxh_nearest_distance_bound", "rtxh_nearest_box_d2", "rtxh_nearest_triangle_d2", "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2", "rtxh_hits_margin")      # return a float, not a status
 
 PI = np.float32(3.14159265359)          # Util.h:8
 
@@ -113,6 +113,9 @@ def lib():
         l.rtxh_nearest_triangle_d2.argtypes = [vp, vp, vp]
         l.rtxh_nearest_sphere_d2.argtypes = [vp, vp]
         l.rtxh_nearest_plane_d2.argtypes = [vp, vp]
+        l.rtxh_query_hits.argtypes = [C.POINTER(RtxhNearestScene), vp, C.c_int64, i32, C.c_uint32, vp, vp, C.POINTER(i32)]
+        l.rtxh_query_hits_exhaustive.argtypes = [C.POINTER(RtxhNearestScene), vp, C.c_int64, i32, C.c_uint32, vp, vp]
+        l.rtxh_hits_margin.argtypes = [C.c_float, C.c_float]
         for n in EXPORTS:
             getattr(l, n).restype = C.c_float if n in FLOAT_EXPORTS else C.c_int
         _lib = l
@@ -560,6 +563,63 @@ def query_nearest(scene, points, channels=("distance",), blas=None) -> dict:
 def query_nearest_exhaustive(scene, points, channels=("distance",), blas=None) -> dict:
     """rtxh_query_nearest_exhaustive: the same candidate functions over every primitive, no tree; ties to the lowest (kind, object, slot)."""
     return _query_nearest("rtxh_query_nearest_exhaustive", scene, points, channels, blas, False)
+
+
+# ---- all-hits segment queries on the host (include/rtx_host.h: rtxh_query_hits / rtxh_query_hits_exhaustive) ------------------------------
+def _query_hits(fn_name, scene, segments, max_hits, channels, count, blas, with_stack):
+    seg = np.asarray(segments)
+    if seg.ndim != 2 or seg.shape[1] != 7 or seg.shape[0] < 1:
+        raise ValueError(f"segments must have shape (n, 7) with n >= 1, not {seg.shape}")
+    if seg.dtype != np.float32:
+        raise TypeError(f"segments must be float32, not {seg.dtype}")
+    seg = np.ascontiguousarray(seg)
+    K = int(max_hits)
+    if not 0 <= K <= 8:
+        raise ValueError(f"max_hits must be in [0, 8], not {max_hits}")
+    if K == 0:
+        if not count or (not isinstance(channels, (str, int, np.integer)) and len(tuple(channels))) or (isinstance(channels, (str, int, np.integer)) and channels):
+            raise ValueError("max_hits=0 is the count-only form: channels=() and count=True")
+        names = ()
+    else:
+        names = _nearest_names(channels)
+    s, keep = nearest_scene(scene, blas)
+    n = seg.shape[0]
+    out = {name: np.zeros((n, K, NEAREST_CHANNELS[name][2]) if NEAREST_CHANNELS[name][2] > 1 else (n, K), NEAREST_CHANNELS[name][1]) for name in names}
+    buf = _NearestBuffers()
+    for name in names:
+        setattr(buf, name, out[name].ctypes.data)
+    mask = sum(NEAREST_CHANNELS[name][0] for name in names)
+    cnt = np.zeros(n, np.int32) if count else None
+    cptr = cnt.ctypes.data if count else None
+    high = C.c_int32(0)
+    if with_stack:
+        rc = lib().rtxh_query_hits(C.byref(s), seg.ctypes.data, n, K, mask, C.byref(buf), cptr, C.byref(high))
+    else:
+        rc = lib().rtxh_query_hits_exhaustive(C.byref(s), seg.ctypes.data, n, K, mask, C.byref(buf), cptr)
+    if rc:
+        raise ValueError(f"{fn_name} failed with status {rc}")
+    if count:
+        out["count"] = cnt
+    if with_stack:
+        out["stack_max"] = int(high.value)
+    return out
+
+
+def query_hits(scene, segments, max_hits=4, channels=("distance",), count=True, blas=None) -> dict:
+    """rtxh_query_hits: what Renderer.query_hits writes on the device for segments float32 (n, 7) of (origin, direction, max distance), from
+    the same code (csrc/rtx_hits_math.h) -> {channel: (n, K[, k]) array} plus "count" (n,) int32 if count, plus "stack_max".  max_hits=0 with
+    channels=() is the count-only form.  scene and blas as for query_nearest."""
+    return _query_hits("rtxh_query_hits", scene, segments, max_hits, channels, count, blas, True)
+
+
+def query_hits_exhaustive(scene, segments, max_hits=4, channels=("distance",), count=True, blas=None) -> dict:
+    """rtxh_query_hits_exhaustive: the same hit tests over every primitive with no box test, the same order rule; "count" = all hits."""
+    return _query_hits("rtxh_query_hits_exhaustive", scene, segments, max_hits, channels, count, blas, False)
+
+
+def hits_margin(kappa, scale) -> float:
+    """rtxhp::margin of csrc/rtx_hits_math.h: how far tri_test's u, v, t may lie from their exact values (linear in both arguments)."""
+    return float(lib().rtxh_hits_margin(C.c_float(float(kappa)), C.c_float(float(scale))))
 
 
 def nearest_distance_bound(local_scale, world_scale=0.0) -> float:

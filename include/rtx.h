@@ -731,6 +731,45 @@ int rtx_debug_query_order(rtx_ctx * ctx, const void * rows_dev, int32_t row_floa
 int rtx_query_nearest(rtx_ctx * ctx, const void * points_dev /* [n][4] f32: x, y, z, maximum distance */, int64_t n,
                       uint32_t channels, const rtx_query_buffers * out, uint32_t flags);
 
+/* ---- all-hits segment queries ----------------------------------------------------------------------------------------------------------
+ * "Everything this segment crosses": the nearest max_hits hits of every row in order, and how many there were.  For inside / outside by
+ * crossing parity (with rtx_query_nearest: the sign of the distance), thickness and penetration depth as entry / exit pairs, multi-echo
+ * lidar and depth peeling (the 2nd, 3rd, ... return), the number of surfaces between two points.  rtx_query_hits: row i =
+ * segments_dev[7i .. 7i+6] = (origin, direction, max distance D), the rows of rtx_query_occluded, fp32 at any 4-byte aligned address in
+ * DEVICE memory; the scene is the frame the context holds, device-side updates included.  Queued on the context's stream, returns at once,
+ * nothing is read back; a steady-state call allocates and frees nothing.  Works with bounces == 0 and without lights; touches no queue,
+ * frame or counter of a render call.
+ * A hit is anything the reference's own tests accept at RAY_EPSILON < t < D, every comparison strict: tri_test in the instance's local ray,
+ * Plane::trace's distance, and BOTH roots of Sphere::trace's quadratic (a ray through a sphere crosses it twice; a tangent gives two equal
+ * hits).  t is in units of |direction|.  Hits are ordered by (t, object_id, triangle_id) ascending.
+ * Channels are the RTX_QUERY_* bits and rtx_query_buffers is reused with stride K = max_hits: hit j of row i is element i*K + j of every
+ * written channel (times 3 or 2 for the vector channels); a channel is written only if its bit is set and its pointer is not NULL; nothing
+ * beyond row n - 1 is touched.  Position, normal, uv and material of a hit are what rtx_query_closest would report had that hit been the
+ * closest (the accept branches of the shading pass at that t, zero differentials).  Entries j >= min(count, K) hold the miss values of
+ * rtx_query_closest: +INFINITY, 0, -1.
+ * count_dev[i] (may be NULL) = the number of hits of row i; it may exceed K.  max_hits == 0 with channels == 0 and a non-NULL count_dev is the
+ * count-only form: no list is kept.  Otherwise 1 <= max_hits <= RTX_QUERY_MAX_HITS and channels != 0.
+ * A dead row — a zero direction, a NaN or infinite component, a D that is NaN or not above 0 — is not walked: count 0, miss values.
+ * +INFINITY is a legal D.
+ * The arithmetic, the order and the walk are specified in the header comment of csrc/rtx_hits_math.h; rtxh_query_hits in rtx_host.h is the
+ * same code on the host and gives the same bits.  Promised: every listed hit is a hit of the exhaustive search over all primitives, with the
+ * same bits, and count <= the exhaustive count.  Not promised: equality with the exhaustive list on every row — the reference's box test can
+ * reject a box whose triangle its triangle test accepts (a flat box, a box plane within an ulp of the hit), as for rtx_query_closest.  When
+ * no count is requested the box tests use the K-th hit's distance once the list is full; lists with and without a count may then differ on
+ * rows with such hits or with a hit exactly as far as the K-th.
+ * Any n >= 1, in rounds of RTX_QUERY_CHUNK_RAYS rows, one kernel launch per round.  flags: RTX_QUERY_SORT or 0; with it the rows of a round are
+ * walked in the order of the ray queries' 7-float keys and the answers scattered back: bit-identical, row for row.
+ * Errors, in this order: RTX_ERR_INVALID_ARG: a max_hits / channels / count_dev combination other than the two above, channels outside
+ * RTX_QUERY_ALL; a NULL ctx or segments_dev, a NULL out (a NULL count_dev in the count-only form), n < 1; any flag but RTX_QUERY_SORT.
+ * RTX_ERR_STATE and RTX_ERR_LIMIT: as for rtx_query_nearest, its stack rule included.  An error queues nothing.
+ * Limits: a BLAS whose leaves share triangles (the reference's SBVH with spatial splits) holds such a triangle once per slot, and every slot
+ * is a hit.  Out of scope: hits beyond RTX_QUERY_MAX_HITS per row, an any-hit callback or per-material filtering, a per-ray tmin other
+ * than RAY_EPSILON, signed distance as a single call, barycentrics as a channel, the rtx_group_* path.                                   */
+enum { RTX_QUERY_MAX_HITS = 8 };
+int rtx_query_hits(rtx_ctx * ctx, const void * segments_dev /* [n][7] f32: origin, direction, max distance */, int64_t n,
+                   int32_t max_hits /* K */, uint32_t channels, const rtx_query_buffers * out /* each channel [n][K] */,
+                   int32_t * count_dev /* [n] or NULL */, uint32_t flags /* RTX_QUERY_SORT or 0 */);
+
 /* Timing of every kernel launched since rtx_enable_kernel_timing(ctx, 1),
  * measured with HIP events on the stream the kernels are launched on.
  * names/ms hold up to `capacity` entries; *count receives the number of

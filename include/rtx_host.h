@@ -39,6 +39,8 @@
  *   rtxh_query_sort_order    the order RTX_QUERY_SORT traces query rows in, from the same code (csrc/rtx_query_sort_math.h)
  *   rtxh_query_nearest       rtx_query_nearest on the host: the walk and the arithmetic of csrc/rtx_nearest_math.h over plain arrays;
  *                            rtxh_query_nearest_exhaustive the same candidate functions over every primitive, without a tree
+ *   rtxh_query_hits          rtx_query_hits on the host: the walk and the arithmetic of csrc/rtx_hits_math.h over the same arrays;
+ *                            rtxh_query_hits_exhaustive the same hit tests over every primitive, without a box test
  *   rtxh_texture_load        Texture::load: PNG / TGA file -> linear float3 texels + mips   Texture.cpp:30-129
  *   rtxh_image_load          the stbi_load(..., STBI_rgb_alpha) call inside it  Texture.cpp:40
  *   rtxh_sky_load            Sky::Sky: raw float3 angular-map probe file         Sky.cpp:8-26
@@ -226,6 +228,20 @@ float rtxh_nearest_box_d2(const float p[3], const float box_min[3], const float 
 float rtxh_nearest_triangle_d2(const float p[3], const rtx_triangle_hot * tri, float uv_out[2]);
 float rtxh_nearest_sphere_d2(const float p[3], const rtx_sphere * sphere);
 float rtxh_nearest_plane_d2(const float p[3], const rtx_plane * plane);
+
+/* rtx_query_hits (include/rtx.h) on the host, by the code the kernel runs (csrc/rtx_hits_math.h, whose header comment is the specification:
+ * what a hit is, the order, the walk and its shrinking bound, what is promised).  The scene is rtxh_nearest_scene; segments: n x 7 floats
+ * (origin, direction, max distance); max_hits, channels, out and count_out as for rtx_query_hits, with host pointers and K = max_hits entries
+ * per row; the answers are the device's bit for bit.  stack_max_out (may be NULL): the most stack entries any row held.
+ * rtxh_query_hits_exhaustive: every sphere, plane and (instance, slot) tested with no box test, the same order rule; count_out is the number
+ * of all hits.  Every hit the walk lists is in the exhaustive list with the same bits, and the walk's count never exceeds the exhaustive one.
+ * rtxh_hits_margin(kappa, scale): rtxhp::margin, how far tri_test's u, v and t may lie from their exact values (MARGIN in that header).
+ * RTX_ERR_INVALID_ARG: the argument rules of rtx_query_hits and rtxh_query_nearest; RTX_ERR_LIMIT: a tree deeper than RTX_MAX_STACK entries. */
+int rtxh_query_hits(const rtxh_nearest_scene * scene, const float * segments, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
+                    int32_t * count_out, int32_t * stack_max_out);
+int rtxh_query_hits_exhaustive(const rtxh_nearest_scene * scene, const float * segments, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
+                               int32_t * count_out);
+float rtxh_hits_margin(float kappa, float scale);
 
 /* Texture::load (Texture.cpp:30-129): decodes a .png or .tga file the way the reference's vendored stb_image v2.19 does with
  * STBI_rgb_alpha (Texture.cpp:40), converts r,g,b bytes to linear light (colour_unpack :13-20, Math::gamma_to_linear Math.h:67-77;
