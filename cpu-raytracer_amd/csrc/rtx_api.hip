@@ -35,6 +35,7 @@
 #include "rtx_query.h"
 #include "rtx_nearest.h"
 #include "rtx_hits.h"
+#include "rtx_sweep.h"
 #include "rtx_texmip.h"
 #include <rocprim/device/device_radix_sort.hpp>      // rtx_update_instances, scenes beyond one workgroup: header-only, part of ROCm
 #include "rtx_hostmem.h"                             // DevBuf, StageRing, grow_keep: every device and pinned allocation has one owner
@@ -2174,11 +2175,17 @@ static int query_queues(rtx_ctx * c, int64_t n, DevQueues & q, QuerySort * sort 
 
 // RTX_QUERY_SORT, one round: the bounds of the m rows at `rows` (ROW floats each), their keys, rocPRIM's radix sort -> S.keys, the order
 // the fill gathers by and the resolve scatters by.  Three launches and a 48-byte memset on the stream; the host learns nothing.
-template <int ROW> static int query_sort_round(rtx_ctx * c, const QuerySort & S, const float * rows, int m) {
+// KEY < ROW: the key is taken over the first KEY floats of every row (rtx_query_sweep: the 7-float key of its 8-float rows).
+template <int ROW, int KEY = ROW> static int query_sort_round(rtx_ctx * c, const QuerySort & S, const float * rows, int m) {
     const dim3 grid((m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK), block(RTX_QUERY_BLOCK);
     HIP_OK(c, hipMemsetAsync(S.bounds, 0xff, 2 * rtxq::COORDS * sizeof(uint32_t), c->stream));
-    launch_timed(c, "k_query_sort_bounds", c->stream, [&] { hipLaunchKernelGGL((k_query_sort_bounds<ROW>), grid, block, 0, c->stream, rows, m, S.bounds); });
-    launch_timed(c, "k_query_sort_keys", c->stream, [&] { hipLaunchKernelGGL((k_query_sort_keys<ROW>), grid, block, 0, c->stream, rows, m, (const uint32_t *)S.bounds, S.keys_in); });
+    if constexpr (KEY == ROW) {
+        launch_timed(c, "k_query_sort_bounds", c->stream, [&] { hipLaunchKernelGGL((k_query_sort_bounds<ROW>), grid, block, 0, c->stream, rows, m, S.bounds); });
+        launch_timed(c, "k_query_sort_keys", c->stream, [&] { hipLaunchKernelGGL((k_query_sort_keys<ROW>), grid, block, 0, c->stream, rows, m, (const uint32_t *)S.bounds, S.keys_in); });
+    } else {
+        launch_timed(c, "k_query_sort_bounds", c->stream, [&] { hipLaunchKernelGGL((k_query_sort_bounds_of<ROW, KEY>), grid, block, 0, c->stream, rows, m, S.bounds); });
+        launch_timed(c, "k_query_sort_keys", c->stream, [&] { hipLaunchKernelGGL((k_query_sort_keys_of<ROW, KEY>), grid, block, 0, c->stream, rows, m, (const uint32_t *)S.bounds, S.keys_in); });
+    }
     hipError_t se = hipSuccess;
     launch_timed(c, "query_radix_sort", c->stream, [&] { size_t bytes = S.tmp_bytes; se = rocprim::radix_sort_keys(S.tmp, bytes, (const uint64_t *)S.keys_in, S.keys, (unsigned int)m, 0u, (unsigned int)rtxq::KEY_BITS, c->stream); });
     if (se != hipSuccess) return sort_failed(c, se);
@@ -2379,6 +2386,53 @@ extern "C" int rtx_query_hits(rtx_ctx * c, const void * segments_dev, int64_t n,
         HIP_OK(c, hipMemsetAsync(head, 0, sizeof(uint32_t), c->stream));
         if (K > 0) launch_timed(c, "k_query_hits", c->stream, [&] { hipLaunchKernelGGL(k_query_hits<true>, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, (int)K, t, count, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head); });
         else launch_timed(c, "k_query_hits", c->stream, [&] { hipLaunchKernelGGL(k_query_hits<false>, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, 0, t, count, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head); });
+    }
+    HIP_OK(c, hipGetLastError());
+    return RTX_OK;
+}
+
+// ---- swept-sphere queries (include/rtx.h: rtx_query_sweep; kernel in rtx_sweep.h, arithmetic and walk in rtx_sweep_math.h) ------------
+// n sweeps in device memory against the frame the context holds: per round of at most RTX_QUERY_CHUNK_RAYS rows ONE launch of k_query_sweep,
+// which reads the rows and writes the channels; with RTX_QUERY_SORT the bounds, key and sort launches of the ray queries run first over the
+// first seven floats of the 8-float rows, in the same sort block.  No queue set, no counters; the stack as for rtx_query_nearest, its stack
+// rule, and its tile counter (the calls are ordered by the stream).
+extern "C" int rtx_query_sweep(rtx_ctx * c, const void * sweeps_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags) {
+    if (c && (channels == 0 || (channels & ~(uint32_t)RTX_QUERY_ALL))) { c->err = "rtx_query_sweep: channels must be a non-empty subset of RTX_QUERY_ALL"; return RTX_ERR_INVALID_ARG; }
+    if (int bad = query_checks(c, sweeps_dev, n, out, flags, "rtx_query_sweep", (uint32_t)RTX_QUERY_SORT)) return bad;
+    int blas_depth = -1;
+    for (size_t b = 0; b < c->blas.size(); b++) if (c->h_blas[b].nodes && c->blas[b].inner_depth > blas_depth) blas_depth = c->blas[b].inner_depth;
+    const int need = rtxnp::stack_need(c->tlas_inner_depth, blas_depth), have = c->cfg.stack_size < RTX_MAX_STACK ? c->cfg.stack_size : RTX_MAX_STACK;
+    if (need > have) {
+        c->err = "rtx_query_sweep: the ordered descent needs " + std::to_string(need) + " stack entries (TLAS inner depth " + std::to_string(c->tlas_inner_depth) +
+                 " + 1, BLAS inner depth " + std::to_string(blas_depth) + " + 1), rtx_config.stack_size allows " + std::to_string(have);
+        return RTX_ERR_LIMIT;
+    }
+    hipSetDevice(c->cfg.device);
+    const bool sorted = (flags & RTX_QUERY_SORT) != 0;
+    QuerySort S = {};
+    DevQueues unused;
+    if (sorted) if (int rc = query_queues(c, n, unused, &S, false)) return rc;
+    if (int rc = ensure(c, c->d_nearest_head, sizeof(uint32_t))) return rc;      // the first call only
+    uint32_t * const head = (uint32_t *)c->d_nearest_head.p;
+    const DevScene sc = c->scene;
+    const int max_blocks = c->q.spill_threads / RTX_QUERY_BLOCK;                  // the spill regions are indexed by the global thread id
+    for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
+        const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
+        const float * const rows = (const float *)sweeps_dev + 8 * first;
+        DevQuery t;
+        auto on = [&](uint32_t bit) { return (channels & bit) != 0; };
+        t.distance = on(RTX_QUERY_DISTANCE) && out->distance ? out->distance + first : nullptr;
+        t.position = on(RTX_QUERY_POSITION) && out->position ? out->position + 3 * first : nullptr;
+        t.normal = on(RTX_QUERY_NORMAL) && out->normal ? out->normal + 3 * first : nullptr;
+        t.uv = on(RTX_QUERY_UV) && out->uv ? out->uv + 2 * first : nullptr;
+        t.material_id = on(RTX_QUERY_MATERIAL_ID) && out->material_id ? out->material_id + first : nullptr;
+        t.object_id = on(RTX_QUERY_OBJECT_ID) && out->object_id ? out->object_id + first : nullptr;
+        t.triangle_id = on(RTX_QUERY_TRIANGLE_ID) && out->triangle_id ? out->triangle_id + first : nullptr;
+        if (sorted) if (int rc = query_sort_round<8, 7>(c, S, rows, m)) return rc;
+        const int tiles = (m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK, blocks = tiles < max_blocks ? tiles : max_blocks;
+        const uint64_t * const order = sorted ? S.keys : nullptr;
+        HIP_OK(c, hipMemsetAsync(head, 0, sizeof(uint32_t), c->stream));
+        launch_timed(c, "k_query_sweep", c->stream, [&] { hipLaunchKernelGGL(k_query_sweep, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head); });
     }
     HIP_OK(c, hipGetLastError());
     return RTX_OK;

@@ -95,6 +95,36 @@ __global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_sort_keys(const float
     keys[i] = rtxq::sort_key(plan, r, ROW, (uint32_t)i);
 }
 
+// The same two kernels for rows whose key is taken over their first KEY floats only (rtx_query_sweep: the 7-float key of 8-float rows): the
+// row stride stays ROW.  Copies, not wrappers over one body with the two above: written that way (the body a forced-inline function, the LDS
+// array passed in or declared in it) hipcc allocates k_query_sort_bounds<4> 18 VGPRs instead of 22, and the ray queries' kernels are to
+// stay the code they were measured as.  A change to the reduction or the atomic guard goes into both pairs.
+template <int ROW, int KEY>
+__global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_sort_bounds_of(const float * __restrict__ rows, const int m, uint32_t * __restrict__ bounds) {
+    __shared__ float lds[ROW * RTX_QUERY_BLOCK];
+    float r[ROW];
+    query_load_row<ROW>(lds, rows, m, r);
+    const int i = blockIdx.x * RTX_QUERY_BLOCK + threadIdx.x;
+    uint32_t k12[2 * rtxq::COORDS];
+    for (int a = 0; a < 2 * rtxq::COORDS; a++) k12[a] = 0xffffffffu;
+    if (i < m && rtxq::row_is_live(r, KEY)) { float x[rtxq::COORDS]; rtxq::coordinates(r, KEY, x); rtxq::bounds_of_row(x, k12); }
+    for (int a = 0; a < 2 * rtxq::COORDS; a++) {
+        uint32_t v = k12[a];
+        for (int o = 32; o > 0; o >>= 1) { const uint32_t w = (uint32_t)__shfl_xor((int)v, o, 64); v = w < v ? w : v; }
+        if ((threadIdx.x & 63) == 0 && v < __hip_atomic_load(&bounds[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&bounds[a], v);
+    }
+}
+template <int ROW, int KEY>
+__global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_sort_keys_of(const float * __restrict__ rows, const int m, const uint32_t * __restrict__ bounds, uint64_t * __restrict__ keys) {
+    __shared__ float lds[ROW * RTX_QUERY_BLOCK];
+    float r[ROW];
+    query_load_row<ROW>(lds, rows, m, r);
+    const int i = blockIdx.x * RTX_QUERY_BLOCK + threadIdx.x;
+    if (i >= m) return;
+    const rtxq::Plan plan = rtxq::make_plan(bounds);
+    keys[i] = rtxq::sort_key(plan, r, KEY, (uint32_t)i);
+}
+
 // the caller row of every slot of a sorted round, for rtx_debug_query_order: order_out[i] = first + row
 __global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_sort_order(const uint64_t * __restrict__ order, const int m, const int32_t first, int32_t * __restrict__ order_out) {
     const int i = blockIdx.x * RTX_QUERY_BLOCK + threadIdx.x;

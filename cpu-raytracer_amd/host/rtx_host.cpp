@@ -13,6 +13,7 @@
 #include "../csrc/rtx_query_sort_math.h"
 #include "../csrc/rtx_nearest_math.h"
 #include "../csrc/rtx_hits_math.h"
+#include "../csrc/rtx_sweep_math.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -855,6 +856,83 @@ extern "C" int rtxh_query_hits_exhaustive(const rtxh_nearest_scene * scene, cons
 }
 
 extern "C" float rtxh_hits_margin(float kappa, float scale) { return rtxhp::margin(kappa, scale); }
+
+// =================================================================================================
+// rtx_query_sweep on the host: rtxsp::walk (csrc/rtx_sweep_math.h) over the arrays of rtxh_query_nearest, and the exhaustive search
+namespace {
+// the channels of row i from its answer: what k_query_sweep stores — the nearest-point channels at the contact's centre, the distance t
+void sweep_store(const rtxh_nearest_scene & s, const float * row, const rtxsp::Answer & a, int64_t i, uint32_t channels, const rtx_query_buffers & out) {
+    const bool hit = a.kind != rtxnp::KIND_NONE;
+    const rtxnp::P3 cc = rtxsp::centre_at(rtxnp::mk(row[0], row[1], row[2]), rtxnp::mk(row[3], row[4], row[5]), hit ? a.t : 0.0f);
+    const float at[4] = { cc.x, cc.y, cc.z, 0.0f };
+    rtxnp::Answer na; na.kind = a.kind; na.object = a.object; na.slot = a.slot; na.u = a.u; na.v = a.v; na.d2 = 0.0f;
+    rtx_query_buffers o = out; o.distance = nullptr;
+    nearest_store(s, at, na, i, channels, o);
+    if ((channels & RTX_QUERY_DISTANCE) && out.distance) out.distance[i] = hit ? a.t : INFINITY;
+}
+}  // namespace
+
+extern "C" int rtxh_query_sweep(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, uint32_t channels, const rtx_query_buffers * out, int32_t * stack_max_out) {
+    if (int rc = nearest_scene_check(scene, sweeps, n, channels, out, true)) return rc;
+    int high = 0;
+    for (int64_t i = 0; i < n; i++) {
+        HostHitsScene S(*scene);
+        HostNearestStack st;
+        rtxsp::Answer a;
+        rtxsp::walk(S, st, sweeps + 8 * i, a);
+        if (st.high > high) high = st.high;
+        sweep_store(*scene, sweeps + 8 * i, a, i, channels, *out);
+    }
+    if (stack_max_out) *stack_max_out = high;
+    return RTX_OK;
+}
+
+extern "C" int rtxh_query_sweep_exhaustive(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, uint32_t channels, const rtx_query_buffers * out) {
+    if (int rc = nearest_scene_check(scene, sweeps, n, channels, out, false)) return rc;
+    const rtxh_nearest_scene & s = *scene;
+    for (int64_t i = 0; i < n; i++) {
+        const float * row = sweeps + 8 * i;
+        HostHitsScene S(s);
+        rtxsp::Answer a; rtxsp::clear(a);
+        if (rtxsp::row_is_live(row)) {
+            const rtxnp::P3 o = rtxnp::mk(row[0], row[1], row[2]), d = rtxnp::mk(row[3], row[4], row[5]);
+            const float D = row[6], r = row[7];
+            a.t = D;
+            rtxsp::world_primitives(S, a, o, d, D, r);
+            for (int k = 0; k < s.instance_count; k++) {
+                const rtxnp::P3 co = rtxnp::xform_pos(s.instances[k].world_inv, o), cd = rtxnp::xform_dir(s.instances[k].world_inv, d);
+                const rtxh_nearest_blas & B = s.blas[s.instances[k].blas_id];
+                for (int j = 0; j < B.triangle_count; j++) {
+                    float t, u, v, d20;
+                    if (rtxsp::triangle_sweep(rtxnp::ptr3(B.hot[j].position_0), rtxnp::ptr3(B.hot[j].position_edge_1), rtxnp::ptr3(B.hot[j].position_edge_2), co, cd, r, a.t, t, u, v, d20))
+                        rtxsp::offer(a, D, t, d20, rtxnp::KIND_TRI, k, j, u, v);
+                }
+            }
+        }
+        sweep_store(s, row, a, i, channels, *out);
+    }
+    return RTX_OK;
+}
+
+extern "C" float rtxh_sweep_bound(float local_scale, float world_scale, float travelled, float radius) { return rtxsp::sweep_bound(local_scale, world_scale, travelled, radius); }
+extern "C" int rtxh_sweep_triangle(const float origin[3], const float direction[3], float radius, float bound, const rtx_triangle_hot * tri, float * t_out, float uv_out[2], float * d20_out) {
+    float t = 0.0f, u = 0.0f, v = 0.0f, d20 = 0.0f;
+    const bool any = rtxsp::triangle_sweep(rtxnp::ptr3(tri->position_0), rtxnp::ptr3(tri->position_edge_1), rtxnp::ptr3(tri->position_edge_2), rtxnp::ptr3(origin), rtxnp::ptr3(direction), radius, bound, t, u, v, d20);
+    if (any) { *t_out = t; uv_out[0] = u; uv_out[1] = v; *d20_out = d20; }
+    return any ? 1 : 0;
+}
+extern "C" int rtxh_sweep_sphere(const float origin[3], const float direction[3], float radius, const rtx_sphere * sphere, float * t_out, float * d20_out) {
+    float t = 0.0f, d20 = 0.0f;
+    const bool any = rtxsp::sphere_sweep(rtxnp::ptr3(sphere->center), sphere->radius_squared, rtxnp::ptr3(origin), rtxnp::ptr3(direction), radius, t, d20);
+    if (any) { *t_out = t; *d20_out = d20; }
+    return any ? 1 : 0;
+}
+extern "C" int rtxh_sweep_plane(const float origin[3], const float direction[3], float radius, const rtx_plane * plane, float * t_out, float * d20_out) {
+    float t = 0.0f, d20 = 0.0f;
+    const bool any = rtxsp::plane_sweep(rtxnp::ptr3(plane->normal), plane->distance, rtxnp::ptr3(origin), rtxnp::ptr3(direction), radius, t, d20);
+    if (any) { *t_out = t; *d20_out = d20; }
+    return any ? 1 : 0;
+}
 
 // =================================================================================================
 // Procedural atrium: a seeded Sponza-class stand-in (the real sponza.obj is absent from the mount).

@@ -28,7 +28,7 @@ EXPORTS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error", "rt
            "rtx_bind_blas_vertices", "rtx_refit_blas", "rtx_read_blas", "rtx_alloc_blas", "rtx_build_blas",
            "rtx_query_closest", "rtx_query_occluded", "rtx_debug_query_order", "rtx_debug_read_layouts",
            "rtx_alloc_texture", "rtx_update_texture", "rtx_read_texture", "rtx_update_sky",
-           "rtx_alloc_blas_topology", "rtx_set_blas_topology", "rtx_blas_vertex_normals", "rtx_query_nearest", "rtx_query_hits"]
+           "rtx_alloc_blas_topology", "rtx_set_blas_topology", "rtx_blas_vertex_normals", "rtx_query_nearest", "rtx_query_hits", "rtx_query_sweep"]
 # newer than the A/B variants tools/ab.py may load (RTX_HIP_LIB = a library built from an older commit): bound when the library has them,
 # otherwise a call raises AttributeError (undefined symbol)
 VIEW_EXPORTS = ("rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer")
@@ -44,6 +44,9 @@ TEXTURE_EXPORTS = ("rtx_alloc_texture", "rtx_update_texture", "rtx_read_texture"
 NORMALS_EXPORTS = ("rtx_alloc_blas_topology", "rtx_set_blas_topology", "rtx_blas_vertex_normals")
 NEAREST_EXPORTS = ("rtx_query_nearest",)
 HITS_EXPORTS = ("rtx_query_hits",)
+SWEEP_EXPORTS = ("rtx_query_sweep",)
+OPTIONAL_EXPORTS = (VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + QUERY_SORT_EXPORTS + LAYOUT_EXPORTS
+                    + TEXTURE_EXPORTS + NORMALS_EXPORTS + NEAREST_EXPORTS + HITS_EXPORTS + SWEEP_EXPORTS)
 RTX_QUERY_MAX_HITS = 8
 # texel formats of rtx_update_texture (include/rtx.h RTX_TEXELS_*)
 RTX_TEXELS_RGB_F32 = 0
@@ -168,6 +171,8 @@ def load_library(path: Optional[str] = None):
         lib.rtx_query_occluded.argtypes = [vp, vp, C.c_int64, vp, u32]
     if hasattr(lib, "rtx_query_nearest"):
         lib.rtx_query_nearest.argtypes = [vp, vp, C.c_int64, u32, C.POINTER(RtxQueryBuffers), u32]
+    if hasattr(lib, "rtx_query_sweep"):
+        lib.rtx_query_sweep.argtypes = [vp, vp, C.c_int64, u32, C.POINTER(RtxQueryBuffers), u32]
     if hasattr(lib, "rtx_query_hits"):
         lib.rtx_query_hits.argtypes = [vp, vp, C.c_int64, i32, u32, C.POINTER(RtxQueryBuffers), vp, u32]
     if hasattr(lib, "rtx_debug_query_order"):
@@ -184,7 +189,7 @@ def load_library(path: Optional[str] = None):
         lib.rtx_set_blas_topology.argtypes = [vp, i32, vp]
         lib.rtx_blas_vertex_normals.argtypes = [vp, i32, vp, vp]
     for name in EXPORTS:
-        if name in VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + QUERY_SORT_EXPORTS + LAYOUT_EXPORTS + TEXTURE_EXPORTS + NORMALS_EXPORTS + NEAREST_EXPORTS + HITS_EXPORTS and not hasattr(lib, name):
+        if name in OPTIONAL_EXPORTS and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         if name not in ("rtx_last_error",):
@@ -1149,8 +1154,12 @@ class Renderer:
         +inf is a legal maximum distance.  Distances are measured in each instance's local space.  Queued on torch's current stream, checked
         and shaped like query_closest; sort=True (RTX_QUERY_SORT) walks the points of every round in Morton order, same answers row for row.
         Raw device pointers: points = address, n, out = {name: address} for every channel wanted."""
+        return self._query_rows_to_channels("rtx_query_nearest", "points", points, 4, channels, out, n, sort)
+
+    def _query_rows_to_channels(self, fn, label, rows, width, channels, out, n, sort) -> Dict:
+        """query_nearest and query_sweep: rows of `width` floats in, one element of every requested channel per row out."""
         names = query_names(channels)
-        ptr, n, pts_t = self._query_rows("points", points, 4, n)
+        ptr, n, pts_t = self._query_rows(label, rows, width, n)
         if out is not None and not isinstance(out, dict):
             raise TypeError(f"out must be a dict {{channel name: tensor}}, not {type(out).__name__}")
         out = dict(out or {})
@@ -1166,7 +1175,7 @@ class Renderer:
         for name in out:
             _, dt, k = QUERY_CHANNELS[name]
             setattr(buf, name, self._query_out(name, out[name], dt, n, k, raw))
-        self._query_on_device({k: t for k, t in [("points", pts_t)] + [(f"out[{k!r}]", t) for k, t in out.items()] if hasattr(t, "device")})
+        self._query_on_device({k: t for k, t in [(label, pts_t)] + [(f"out[{k!r}]", t) for k, t in out.items()] if hasattr(t, "device")})
         for name in names:
             if name not in out:
                 import torch
@@ -1176,13 +1185,25 @@ class Renderer:
         mask = sum(QUERY_CHANNELS[name][0] for name in names)
 
         def launch():
-            self._chk(self.lib.rtx_query_nearest(self.ctx, ptr, n, mask, C.byref(buf), fl), "rtx_query_nearest")
+            self._chk(getattr(self.lib, fn)(self.ctx, ptr, n, mask, C.byref(buf), fl), fn)
         tensors = [t for t in [pts_t] + list(out.values()) if hasattr(t, "record_stream")]
         if tensors:
             self._on_torch_stream(launch, tensors)
         else:
             launch()
         return {name: out[name] for name in names}
+
+    def query_sweep(self, sweeps, channels=("distance",), out: Optional[Dict] = None, n: Optional[int] = None, sort: bool = False) -> Dict:
+        """The first contact of n moving balls with the frame the context holds (rtx_query_sweep): sweeps = float32 torch tensor (n, 8) of
+        (origin, direction, max distance D, radius r) on this context's GPU; channels as for query_closest.  The centre moves along
+        origin + t * direction; "distance" is the smallest t in [0, D) at which the ball touches the surface query_nearest measures (0 when
+        it touches at its origin), "position" the contact point on the surface, normal, uv and ids what query_nearest reports for that
+        point; the geometric contact normal is (origin + t * direction - position) / r.  No answer (nothing touched before D, a zero
+        direction, a non-finite component, D or r NaN or not above 0, r infinite): distance inf, ids -1, the rest 0; +inf is a legal D.
+        r and distances are measured in each instance's local space.  Queued on torch's current stream, checked and shaped like
+        query_nearest; sort=True (RTX_QUERY_SORT) walks the rows of every round in the ray queries' order, same answers row for row.
+        Raw device pointers: sweeps = address, n, out = {name: address} for every channel wanted."""
+        return self._query_rows_to_channels("rtx_query_sweep", "sweeps", sweeps, 8, channels, out, n, sort)
 
     def query_hits(self, segments, max_hits: int = 4, channels=("distance",), count: bool = True, out: Optional[Dict] = None, n: Optional[int] = None,
                    sort: bool = False) -> Dict:

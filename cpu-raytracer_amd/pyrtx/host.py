@@ -24,8 +24,9 @@ EXPORTS = ["rtxh_camera_basis", "rtxh_camera_update", "rtxh_quaternion_axis_angl
            "rtxh_tlas_build_balanced", "rtxh_scene_update_balanced", "rtxh_tlas_balanced_node_count", "rtxh_tlas_balanced_inner_depth", "rtxh_blas_refit",
            "rtxh_blas_build_balanced", "rtxh_blas_balanced_node_count", "rtxh_blas_balanced_inner_depth", "rtxh_vertex_normals",
            "rtxh_query_nearest", "rtxh_query_nearest_exhaustive", "rtxh_nearest_distance_bound", "rtxh_nearest_box_d2", "rtxh_nearest_triangle_d2",
-           "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2", "rtxh_query_hits", "rtxh_query_hits_exhaustive", "rtxh_hits_margin"]
-FLOAT_EXPORTS = ("rtxh_nearest_distance_bound", "rtxh_nearest_box_d2", "rtxh_nearest_triangle_d2", "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2", "rtxh_hits_margin")      # return a float, not a status
+           "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2", "rtxh_query_hits", "rtxh_query_hits_exhaustive", "rtxh_hits_margin",
+           "rtxh_query_sweep", "rtxh_query_sweep_exhaustive", "rtxh_sweep_bound", "rtxh_sweep_triangle", "rtxh_sweep_sphere", "rtxh_sweep_plane"]
+FLOAT_EXPORTS = ("rtxh_nearest_distance_bound", "rtxh_nearest_box_d2", "rtxh_nearest_triangle_d2", "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2", "rtxh_hits_margin", "rtxh_sweep_bound")      # return a float, not a status
 
 PI = np.float32(3.14159265359)          # Util.h:8
 
@@ -116,6 +117,12 @@ def lib():
         l.rtxh_query_hits.argtypes = [C.POINTER(RtxhNearestScene), vp, C.c_int64, i32, C.c_uint32, vp, vp, C.POINTER(i32)]
         l.rtxh_query_hits_exhaustive.argtypes = [C.POINTER(RtxhNearestScene), vp, C.c_int64, i32, C.c_uint32, vp, vp]
         l.rtxh_hits_margin.argtypes = [C.c_float, C.c_float]
+        l.rtxh_query_sweep.argtypes = [C.POINTER(RtxhNearestScene), vp, C.c_int64, C.c_uint32, vp, C.POINTER(i32)]
+        l.rtxh_query_sweep_exhaustive.argtypes = [C.POINTER(RtxhNearestScene), vp, C.c_int64, C.c_uint32, vp]
+        l.rtxh_sweep_bound.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float]
+        l.rtxh_sweep_triangle.argtypes = [vp, vp, C.c_float, C.c_float, vp, vp, vp, vp]
+        l.rtxh_sweep_sphere.argtypes = [vp, vp, C.c_float, vp, vp, vp]
+        l.rtxh_sweep_plane.argtypes = [vp, vp, C.c_float, vp, vp, vp]
         for n in EXPORTS:
             getattr(l, n).restype = C.c_float if n in FLOAT_EXPORTS else C.c_int
         _lib = l
@@ -526,12 +533,12 @@ def _nearest_names(channels):
     return tuple(n for n in NEAREST_CHANNELS if n in want)
 
 
-def _query_nearest(fn_name, scene, points, channels, blas, with_stack):
+def _query_nearest(fn_name, scene, points, channels, blas, with_stack, width=4, label="points"):
     pts = np.asarray(points)
-    if pts.ndim != 2 or pts.shape[1] != 4 or pts.shape[0] < 1:
-        raise ValueError(f"points must have shape (n, 4) with n >= 1, not {pts.shape}")
+    if pts.ndim != 2 or pts.shape[1] != width or pts.shape[0] < 1:
+        raise ValueError(f"{label} must have shape (n, {width}) with n >= 1, not {pts.shape}")
     if pts.dtype != np.float32:
-        raise TypeError(f"points must be float32, not {pts.dtype}")
+        raise TypeError(f"{label} must be float32, not {pts.dtype}")
     pts = np.ascontiguousarray(pts)
     names = _nearest_names(channels)
     s, keep = nearest_scene(scene, blas)
@@ -543,9 +550,9 @@ def _query_nearest(fn_name, scene, points, channels, blas, with_stack):
     mask = sum(NEAREST_CHANNELS[name][0] for name in names)
     high = C.c_int32(0)
     if with_stack:
-        rc = lib().rtxh_query_nearest(C.byref(s), pts.ctypes.data, n, mask, C.byref(buf), C.byref(high))
+        rc = getattr(lib(), fn_name)(C.byref(s), pts.ctypes.data, n, mask, C.byref(buf), C.byref(high))
     else:
-        rc = lib().rtxh_query_nearest_exhaustive(C.byref(s), pts.ctypes.data, n, mask, C.byref(buf))
+        rc = getattr(lib(), fn_name)(C.byref(s), pts.ctypes.data, n, mask, C.byref(buf))
     if rc:
         raise ValueError(f"{fn_name} failed with status {rc}")
     if with_stack:
@@ -615,6 +622,23 @@ def query_hits(scene, segments, max_hits=4, channels=("distance",), count=True, 
 def query_hits_exhaustive(scene, segments, max_hits=4, channels=("distance",), count=True, blas=None) -> dict:
     """rtxh_query_hits_exhaustive: the same hit tests over every primitive with no box test, the same order rule; "count" = all hits."""
     return _query_hits("rtxh_query_hits_exhaustive", scene, segments, max_hits, channels, count, blas, False)
+
+
+# ---- swept-sphere queries on the host (include/rtx_host.h: rtxh_query_sweep / rtxh_query_sweep_exhaustive) ---------------------------------
+def query_sweep(scene, sweeps, channels=("distance",), blas=None) -> dict:
+    """rtxh_query_sweep: what Renderer.query_sweep writes on the device for sweeps float32 (n, 8) of (origin, direction, max distance,
+    radius), from the same code (csrc/rtx_sweep_math.h) -> {channel: array} plus "stack_max".  scene and blas as for query_nearest."""
+    return _query_nearest("rtxh_query_sweep", scene, sweeps, channels, blas, True, 8, "sweeps")
+
+
+def query_sweep_exhaustive(scene, sweeps, channels=("distance",), blas=None) -> dict:
+    """rtxh_query_sweep_exhaustive: the same candidate functions over every primitive with no box test, the same order rule."""
+    return _query_nearest("rtxh_query_sweep_exhaustive", scene, sweeps, channels, blas, False, 8, "sweeps")
+
+
+def sweep_bound(local_scale, world_scale=0.0, travelled=0.0, radius=0.0) -> float:
+    """rtxsp::sweep_bound of csrc/rtx_sweep_math.h: how far, in distance, a returned contact may lie from touching exactly."""
+    return float(lib().rtxh_sweep_bound(C.c_float(float(local_scale)), C.c_float(float(world_scale)), C.c_float(float(travelled)), C.c_float(float(radius))))
 
 
 def hits_margin(kappa, scale) -> float:

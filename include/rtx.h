@@ -770,6 +770,40 @@ int rtx_query_hits(rtx_ctx * ctx, const void * segments_dev /* [n][7] f32: origi
                    int32_t max_hits /* K */, uint32_t channels, const rtx_query_buffers * out /* each channel [n][K] */,
                    int32_t * count_dev /* [n] or NULL */, uint32_t flags /* RTX_QUERY_SORT or 0 */);
 
+/* ---- swept-sphere queries --------------------------------------------------------------------------------------------------------------
+ * "How far can this ball travel along this direction before it touches something, and where does it touch": a particle with a radius, a
+ * collision proxy, a camera boom, a thick lidar beam, a conservative-advancement step.  rtx_query_sweep: row i = sweeps_dev[8i .. 8i+7] =
+ * (origin, direction, max distance D, radius r), fp32 at any 4-byte aligned address in DEVICE memory; the scene is the frame the context
+ * holds, device-side updates included.  Queued on the context's stream, returns at once, nothing is read back; a steady-state call allocates
+ * and frees nothing.  Works with bounces == 0 and without lights; touches no queue, frame or counter of a render call.
+ * The ball's centre moves along c(t) = origin + t * direction, the direction used as given, t in units of |direction|; r is in world units.
+ * The answer is the smallest t in [0, D) (D itself excluded) at which the distance from c(t) to the surface rtx_query_nearest measures —
+ * two-sided triangles, sphere shells (a ball inside a large sphere travels until it touches the shell from inside), two-sided planes — is
+ * <= r.  A ball that touches something at its origin answers t = 0 with the primitive and the surface point rtx_query_nearest reports for
+ * (origin, r): candidates are ordered by (t, squared distance from the origin), an exact tie goes to the lowest (kind, object, slot).
+ * A dead row — a zero direction, a NaN or infinite origin or direction component, a D that is NaN or not above 0, an r that is NaN, infinite
+ * or not above 0 — is not walked and gets the no-answer values.  +INFINITY is a legal D.
+ * Channels and rtx_query_buffers are those of rtx_query_closest; a channel is written only if its bit is set and its pointer is not NULL;
+ * element i belongs to row i; nothing beyond row n - 1 is touched.
+ * Channel                answer                                                                        no answer
+ *   DISTANCE             t                                                                               +INFINITY
+ *   POSITION             the contact point on the surface, world space                                   0
+ *   NORMAL, UV           what rtx_query_nearest reports for that surface point                           0
+ *   MATERIAL_ID, OBJECT_ID, TRIANGLE_ID   the numberings of rtx_query_closest                            -1
+ * NORMAL is the surface's shading normal.  The geometric contact normal is (c(t) - position) / r; there is no channel for it.
+ * The arithmetic, the order of the walk and the accuracy bound (stated in distance: for the returned t the distance from c(t) to the
+ * returned primitive is within the bound of r, and nothing is nearer than r minus the bound before t) are specified in the header comment
+ * of csrc/rtx_sweep_math.h; rtxh_query_sweep in rtx_host.h is the same code on the host and gives the same bits.
+ * Any n >= 1, in rounds of RTX_QUERY_CHUNK_RAYS rows, one kernel launch per round.  flags: RTX_QUERY_SORT or 0; with it the rows of a round are
+ * walked in the order of the ray queries' 7-float keys, taken over each row's first seven floats, and the answers scattered back:
+ * bit-identical, row for row.
+ * Errors, in this order and with the codes of rtx_query_nearest, its stack rule included.  An error queues nothing.
+ * Limits: r and the distances are measured in each instance's LOCAL space, as for rtx_query_nearest — the world metric for rigid poses, local
+ * units under a scaled world matrix.  The answer may depend on the tree within the bound.  Out of scope: swept capsules, boxes or rotating
+ * shapes, all contacts along the sweep, a contact-normal channel, the rtx_group_* path.                                                    */
+int rtx_query_sweep(rtx_ctx * ctx, const void * sweeps_dev /* [n][8] f32: origin, direction, max distance, radius */, int64_t n,
+                    uint32_t channels, const rtx_query_buffers * out, uint32_t flags /* RTX_QUERY_SORT or 0 */);
+
 /* Timing of every kernel launched since rtx_enable_kernel_timing(ctx, 1),
  * measured with HIP events on the stream the kernels are launched on.
  * names/ms hold up to `capacity` entries; *count receives the number of

@@ -39,6 +39,7 @@
  *   rtxh_query_sort_order    the order RTX_QUERY_SORT traces query rows in, from the same code (csrc/rtx_query_sort_math.h)
  *   rtxh_query_nearest       rtx_query_nearest on the host: the walk and the arithmetic of csrc/rtx_nearest_math.h over plain arrays;
  *                            rtxh_query_nearest_exhaustive the same candidate functions over every primitive, without a tree
+ *   rtxh_query_sweep         rtx_query_sweep on the host: the walk and the arithmetic of csrc/rtx_sweep_math.h over the same arrays;
  *   rtxh_query_hits          rtx_query_hits on the host: the walk and the arithmetic of csrc/rtx_hits_math.h over the same arrays;
  *                            rtxh_query_hits_exhaustive the same hit tests over every primitive, without a box test
  *   rtxh_texture_load        Texture::load: PNG / TGA file -> linear float3 texels + mips   Texture.cpp:30-129
@@ -242,6 +243,27 @@ int rtxh_query_hits(const rtxh_nearest_scene * scene, const float * segments, in
 int rtxh_query_hits_exhaustive(const rtxh_nearest_scene * scene, const float * segments, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
                                int32_t * count_out);
 float rtxh_hits_margin(float kappa, float scale);
+
+/* rtx_query_sweep (include/rtx.h) on the host, by the code the kernel runs (csrc/rtx_sweep_math.h, whose header comment is the specification:
+ * candidate functions, the order rule, the walk, the accuracy bound).  The scene is rtxh_nearest_scene; sweeps: n x 8 floats (origin,
+ * direction, max distance, radius); channels and out as for rtx_query_sweep, with host pointers; the answers are the device's bit for bit.
+ * stack_max_out (may be NULL): the most stack entries any row held.
+ * rtxh_query_sweep_exhaustive: the same candidate functions over every sphere, plane and (instance, slot) without a box test, the same order
+ * rule.  Within an instance the box tests skip no candidate the exhaustive search would accept; the two still meet the triangles in different
+ * orders, and the plane early-out of the triangle test depends on the order within its rounding (ORDER in that header): their t can differ
+ * by that much, either way round, and both satisfy the accuracy bound.
+ * rtxh_sweep_bound(S, W, T, r): rtxsp::sweep_bound, the bound in distance of ACCURACY in that header (local scale, world scale, length
+ * travelled, radius).
+ * The candidate functions on their own, for tests that restate them: 1 and *t_out (a triangle's weights in uv_out, the squared distance from
+ * the origin in d20_out) when the primitive yields a candidate, else 0.  rtxh_sweep_triangle takes the LOCAL ray and the walk's bound
+ * (no answer's d20: the "settled" early-out of the header, which changes no answer, never applies).
+ * RTX_ERR_INVALID_ARG and RTX_ERR_LIMIT: as for rtxh_query_nearest.                                                                     */
+int rtxh_query_sweep(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, uint32_t channels, const rtx_query_buffers * out, int32_t * stack_max_out);
+int rtxh_query_sweep_exhaustive(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, uint32_t channels, const rtx_query_buffers * out);
+float rtxh_sweep_bound(float local_scale, float world_scale, float travelled, float radius);
+int rtxh_sweep_triangle(const float origin[3], const float direction[3], float radius, float bound, const rtx_triangle_hot * tri, float * t_out, float uv_out[2], float * d20_out);
+int rtxh_sweep_sphere(const float origin[3], const float direction[3], float radius, const rtx_sphere * sphere, float * t_out, float * d20_out);
+int rtxh_sweep_plane(const float origin[3], const float direction[3], float radius, const rtx_plane * plane, float * t_out, float * d20_out);
 
 /* Texture::load (Texture.cpp:30-129): decodes a .png or .tga file the way the reference's vendored stb_image v2.19 does with
  * STBI_rgb_alpha (Texture.cpp:40), converts r,g,b bytes to linear light (colour_unpack :13-20, Math::gamma_to_linear Math.h:67-77;
