@@ -136,6 +136,8 @@ struct rtx_ctx {
     DevBuf d_query_sort; int32_t query_sort_cap = 0; size_t query_sort_tmp = 0;
     // rtx_query_nearest: the tile counter of a round (4 bytes, made by the first call); RTX_NEAREST_FETCH=0: tiles by stride, no counter (A/B)
     DevBuf d_nearest_head; bool nearest_fetch = true;
+    // rtx_query_nearest / rtx_query_hits / rtx_query_sweep: RTX_QUERY_GRID=g caps their grids at g workgroups (0: the spill region's size alone decides)
+    int query_grid = 0;
     size_t slots_alloc = 0, shadow_alloc = 0;
     DevBuf d_stats_partial, d_pk_fifo, d_counters, d_spill, d_fb_rgb, d_fb_packed, d_display, d_gamma, d_pk_heads;
     int trace_blocks_closest = 0, trace_blocks_any = 0, trace_blocks_count = 0;
@@ -235,6 +237,7 @@ extern "C" int rtx_create(const rtx_config * config, rtx_ctx ** out_ctx) {
     K.update_small_max = (int)knob_int("RTX_UPDATE_SMALL_MAX", RTX_UPDATE_SMALL_MAX, 0, RTX_UPDATE_SMALL_MAX);
     K.tex_pass_levels = (int)knob_int("RTX_TEX_PASS_LEVELS", rtxt::DEFAULT_PASS_LEVELS, 1, rtxt::MAX_PASS_LEVELS);      // DESIGN.md 9, Device-side texture update
     c->nearest_fetch = knob_int("RTX_NEAREST_FETCH", 1, 0, 1) != 0;     // rtx_query_nearest: workgroups fetch tiles from a counter (1) or take them by stride (0): DESIGN.md 9
+    c->query_grid = (int)knob_int("RTX_QUERY_GRID", 0, 0, 1 << 20);    // the walk queries: at most this many workgroups, each takes tile after tile (0: no cap); tests/test_gpu_query_tiles.py
     K.fail_item_alloc = knob_int("RTX_DEBUG_FAIL_ITEM_ALLOC", 0, 0, 1) != 0;      // tests: the item buffer's allocation fails (a size no device has), the fallback kernel must take over
     int bpc = 0;
     hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k_trace_fast<false>, RTX_TRACE_BLOCK, 0);
@@ -2285,6 +2288,13 @@ extern "C" int rtx_query_occluded(rtx_ctx * c, const void * segments_dev, int64_
     return query_rounds(c, k.q, n, [&](int64_t first, int m) { return query_occluded_round(c, k, (const float *)segments_dev + 7 * first, m, occluded_dev + first); });
 }
 
+// the grid limit of the walk queries (k_query_nearest, k_query_hits, k_query_sweep): the spill regions are indexed by the global thread id;
+// RTX_QUERY_GRID lowers it, so that a workgroup walks several tiles of a small call
+static int query_max_blocks(const rtx_ctx * c) {
+    const int fit = c->q.spill_threads / RTX_QUERY_BLOCK;
+    return c->query_grid > 0 && c->query_grid < fit ? c->query_grid : fit;
+}
+
 // ---- nearest-point queries (include/rtx.h: rtx_query_nearest; kernel in rtx_nearest.h, arithmetic and walk in rtx_nearest_math.h) ------
 // n points with a maximum distance each, in device memory, against the frame the context holds: per round of at most RTX_QUERY_CHUNK_RAYS
 // rows ONE launch of k_query_nearest, which reads the rows and writes the channels; with RTX_QUERY_SORT the bounds, key and sort launches of
@@ -2311,7 +2321,7 @@ extern "C" int rtx_query_nearest(rtx_ctx * c, const void * points_dev, int64_t n
     if (c->nearest_fetch) if (int rc = ensure(c, c->d_nearest_head, sizeof(uint32_t))) return rc;      // the first call only
     uint32_t * const head = c->nearest_fetch ? (uint32_t *)c->d_nearest_head.p : nullptr;
     const DevScene sc = c->scene;
-    const int max_blocks = c->q.spill_threads / RTX_QUERY_BLOCK;                  // the spill regions are indexed by the global thread id
+    const int max_blocks = query_max_blocks(c);
     for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
         const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
         const float * const rows = (const float *)points_dev + 4 * first;
@@ -2365,7 +2375,7 @@ extern "C" int rtx_query_hits(rtx_ctx * c, const void * segments_dev, int64_t n,
     if (int rc = ensure(c, c->d_nearest_head, sizeof(uint32_t))) return rc;      // the first call only
     uint32_t * const head = (uint32_t *)c->d_nearest_head.p;
     const DevScene sc = c->scene;
-    const int max_blocks = c->q.spill_threads / RTX_QUERY_BLOCK;                  // the spill regions are indexed by the global thread id
+    const int max_blocks = query_max_blocks(c);
     const int64_t K = max_hits;
     for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
         const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
@@ -2415,7 +2425,7 @@ extern "C" int rtx_query_sweep(rtx_ctx * c, const void * sweeps_dev, int64_t n, 
     if (int rc = ensure(c, c->d_nearest_head, sizeof(uint32_t))) return rc;      // the first call only
     uint32_t * const head = (uint32_t *)c->d_nearest_head.p;
     const DevScene sc = c->scene;
-    const int max_blocks = c->q.spill_threads / RTX_QUERY_BLOCK;                  // the spill regions are indexed by the global thread id
+    const int max_blocks = query_max_blocks(c);
     for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
         const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
         const float * const rows = (const float *)sweeps_dev + 8 * first;

@@ -1,7 +1,7 @@
 """rtx_query_hits on the GPU: segments in device tensors, the first K hits of every row and its count in device tensors, every channel bit for
 bit (NaN == NaN) against the host twin (host.query_hits, the same code of csrc/rtx_hits_math.h) run on the arrays read back from the context:
   * the segment classes of tests/hitset.py over seven scenes (a stack past RTX_LDS_STACK, a deep TLAS, rows with more than K hits), K in
-    {1, 2, 8}, with and without a count, the count-only form, sorted rounds;
+    {1, 2, 8} and on two of them every K from 1 to 8, with and without a count, the count-only form, sorted rounds;
   * batch sizes around a wave and a workgroup, one call that crosses a round;
   * consistency with the merged queries on the device: query_closest's hit is in the list and never nearer than its head, the head's channels
     are query_closest's, query_occluded is count > 0 where the scene has no sphere;
@@ -105,7 +105,7 @@ def test_device_equals_the_host_walk(api, name):
     check(got, twin(r, sc, seg, 8), labels, f"{name}, arrays read back")
     assert (to_host(got["count"]) > 0).sum() > len(seg) // 3
     check(r.query_hits(seg_t, 8, ALL, sort=True), want, labels, f"{name} sorted")
-    for K in (1, 2, 8):
+    for K in range(1, 9) if name in ("quad_stack", "materials_aniso") else (1, 2, 8):      # every K: the sorted insert, the K-th-hit bound and the stride p * K + j at odd K too
         for count in (True, False):
             if K == 8 and count:
                 continue

@@ -267,6 +267,44 @@ def test_smaller_k_is_a_prefix_and_count_only_is_the_count(host, name):
     assert all(same(got[ch], w[ch]).all() for ch in ALL) and np.array_equal(got["count"], w["count"])
 
 
+@pytest.mark.parametrize("name", ["quad_stack", "materials_aniso"])
+def test_every_k_from_3_to_7_against_exhaustive_search(host, name):
+    """The K the other tests leave out, on the two scenes the device is compared at every K: the sorted insert and the K-th-hit bound at odd
+    and even K.  With a count the list is the first K of the K = 8 walk, and where that walk found every hit of a row (count equal to the
+    exhaustive count, at most 8) it is the exhaustive search's list at K bit for bit; without a count every listed hit is real, in order,
+    and the list is as long as min(K, count)."""
+    sc, seg, lab, w, e = segment_set(host, name)
+    complete = (w["count"] == e["count"]) & (e["count"] <= 8)
+    assert complete.sum() > len(seg) // 2
+    if name == "quad_stack":
+        assert ((w["count"] > 3) & complete).sum() >= 12 and (w["count"] > 8).sum() >= 12
+    for K in range(3, 8):
+        eK = host.query_hits_exhaustive(sc, seg, K, ALL)
+        assert np.array_equal(eK["count"], e["count"])
+        wK = host.query_hits(sc, seg, K, ALL)
+        assert np.array_equal(wK["count"], w["count"])
+        for ch in ALL:
+            assert wK[ch].shape[:2] == (len(seg), K)
+            assert same(wK[ch], w[ch][:, :K]).all(), (name, K, ch)          # one node set: the first K of what the walk found
+            assert same(wK[ch][complete], eK[ch][complete]).all(), (name, K, ch, np.flatnonzero(complete)[~same(wK[ch][complete], eK[ch][complete])][:6])
+        s = host.query_hits(sc, seg, K, ALL, count=False)
+        assert "count" not in s
+        differ = 0
+        for i in range(len(seg)):
+            held = int(np.isfinite(s["distance"][i]).sum())
+            assert held == min(K, int(w["count"][i])), (name, K, i, held, w["count"][i])      # the bound only moves once the list is full
+            assert np.isinf(s["distance"][i, held:]).all() and (s["object_id"][i, held:] == -1).all() and (s["triangle_id"][i, held:] == -1).all()
+            keys = list(zip(s["distance"][i, :held].tolist(), s["object_id"][i, :held].tolist(), s["triangle_id"][i, :held].tolist()))
+            assert keys == sorted(keys), (name, K, i, keys)
+            ke = int(min(e["count"][i], 8))
+            known = {(int(bits(e["distance"][i, j:j + 1])[0]), int(e["object_id"][i, j]), int(e["triangle_id"][i, j])) for j in range(ke)}
+            for j in range(held):
+                k = (int(bits(s["distance"][i, j:j + 1])[0]), int(s["object_id"][i, j]), int(s["triangle_id"][i, j]))
+                assert k in known or (e["count"][i] > 8 and keys[j] > (float(e["distance"][i, 7]), int(e["object_id"][i, 7]), int(e["triangle_id"][i, 7]))), (name, K, i, j)
+            differ += not all(same(s[ch][i:i + 1], wK[ch][i:i + 1]).all() for ch in ALL)
+        print(f"{name} K {K}: {int(complete.sum())} of {len(seg)} rows equal the exhaustive list, {differ} rows differ between the shrinking and the fixed bound")
+
+
 @pytest.mark.parametrize("name", SCENES)
 def test_without_a_count_every_listed_hit_is_real(host, name):
     """The shrinking bound on every set, hostile ones included: lists may differ from the fixed bound's, but never hold an invention."""
