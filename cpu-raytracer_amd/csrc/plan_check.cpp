@@ -319,7 +319,73 @@ static void lpt_items_graph() {
     }
 }
 
+// Grids of a device with very few compute units (or RTX_GRID_CUS): n_cu 1, 2 and 8 with 8 to 32 one-wave packet workgroups, the 60 tiles of a
+// 320 x 180 frame.  shade_blocks = 4 n_cu is then below the floor of plan_level_blocks, which a k_shade launch has all the same.
+static void small_grids() {
+    const struct { int n_cu, pk_closest, pk_any; } grids[] = { { 1, 8, 8 }, { 1, 16, 8 }, { 2, 16, 24 }, { 2, 32, 32 }, { 8, 32, 32 }, { 8, 8, 16 } };
+    auto small = [](int n_cu, int pkc, int pka, uint32_t flags) {
+        PlanInputs in = frame(flags); in.n_cu = n_cu; in.pk_blocks_closest = pkc; in.pk_blocks_any = pka; in.tile_count = in.batch_tiles = 60;
+        return in;
+    };
+    CASE("small grids: a level's partial tallies fit its stride");
+    for (const auto & g : grids)
+        for (int fuse = 0; fuse <= 1; fuse++)
+            for (uint32_t flags : { 0u, (uint32_t)SERIAL, (uint32_t)LANE, (uint32_t)CW, (uint32_t)SIMPLE, (uint32_t)AOV, (uint32_t)(CULL | SERIAL) }) {
+                PlanInputs in = small(g.n_cu, g.pk_closest, g.pk_any, flags); in.knobs.fuse_shade = fuse != 0; in.bounces = RTX_MAX_LEVELS - 1;
+                for (int shade_grid : { 1, 4, 64 }) {
+                    in.knobs.shade_grid = shade_grid;
+                    const RenderPlan p = plan_render(in);
+                    CHECK(p.levels == RTX_MAX_LEVELS && p.shade_blocks == g.n_cu * shade_grid && p.pk_waves_closest == g.pk_closest);
+                    CHECK(p.stats_stride >= 64 && p.stats_stride >= p.shade_blocks && p.stats_stride >= p.pk_waves_closest);
+                    for (int slots : { 1024, 60 * 1024, 2025 * 1024 })
+                        for (int l = 0; l < p.levels; l++) {
+                            const int n = plan_stats_n(p, slots, l);
+                            CHECK(n >= 1 && n <= p.stats_stride);          // entry level * stride + n - 1 stays inside the level's own stride
+                            CHECK(n == (p.shade[l] == SHADE_NONE ? g.pk_closest : plan_level_blocks(slots, l, p.shade_blocks)));
+                        }
+                    if (fuse && flags == 0u) CHECK(all_shade(p, SHADE_NONE));      // the fused shape was among them
+                    if (!fuse) for (int l = 0; l < p.levels; l++) CHECK(p.shade[l] != SHADE_NONE);
+                }
+            }
+    {   // one compute unit, four k_shade workgroups wanted: 64 are launched, and level 11's last entry is (11 * stride + 63) of (12 + 1) * stride
+        const RenderPlan p = plan_render(small(1, 8, 8, 0u));
+        CHECK(p.shade_blocks == 4 && p.stats_stride == 64 && plan_stats_n(p, 60 * 1024, 0) == 64 && plan_stats_n(p, 60 * 1024, 3) == 64);
+        CHECK(plan_render(small(8, 32, 32, 0u)).stats_stride == 64 && plan_render(small(32, 96, 96, 0u)).stats_stride == 128);
+        CHECK(plan_render(frame()).stats_stride == 1024);                 // the full device: as before
+    }
+    CASE("small grids: item capacity follows the chunk count");
+    {   // expected average 0.45 * 1024 * 60 tiles * 2 lights / chunks, 3.5 x that in whole units of 64
+        CHECK(plan_render(small(1, 8, 8, 0u)).item_cap == 24192);         // 8 chunks: 3.5 x 6 912
+        CHECK(plan_render(small(2, 16, 16, 0u)).item_cap == 12096);       // 16 chunks: 3.5 x 3 456
+        CHECK(plan_render(small(8, 32, 32, 0u)).item_cap == 6080);        // 32 chunks: 3.5 x 1 728 = 6 048, rounded up
+        PlanInputs in = small(1, 8, 8, 0u); in.tile_count = in.batch_tiles = 200;
+        CHECK(plan_render(in).item_cap == 1 << 16 && plan_render(in).split);      // 3.5 x 23 040 = 80 640: clipped
+        in.knobs.item_bytes_max = 8ll * 48 * 128;
+        CHECK(plan_render(in).item_cap == 128 && plan_render(in).split);  // the buffer's bound wins
+        in.knobs.item_bytes_max = 8ll * 48 * 63;
+        CHECK(plan_render(in).item_cap == 0 && !plan_render(in).split);
+        in = small(1, 8, 8, 0u); in.knobs.split_items = 64; in.tile_count = in.batch_tiles = 1; in.light_count = 1;
+        CHECK(plan_render(in).item_cap == 256);                           // one tile, one light: 3.5 x 57.6 = 201, in whole units
+    }
+    CASE("small grids: the LPT default rule");
+    for (const auto & g : grids) {
+        PlanInputs in = small(g.n_cu, g.pk_closest, g.pk_any, 0u);      // 960 packets over at most 32 waves
+        RenderPlan p = plan_render(in);
+        CHECK(p.lpt && p.lpt_n == 960);
+        in.flags = SERIAL;
+        CHECK(!plan_render(in).lpt);
+        in.knobs.lpt = 1;
+        CHECK(plan_render(in).lpt);
+        in.flags = 0; in.knobs.lpt = 0;
+        CHECK(!plan_render(in).lpt);
+        in.knobs.lpt = -1; in.tile_count = in.batch_tiles = g.pk_closest / 8;      // exactly two packets per wave, and one tile less
+        CHECK(plan_render(in).lpt);
+        if (g.pk_closest > 8) { in.tile_count = in.batch_tiles = g.pk_closest / 8 - 1; CHECK(!plan_render(in).lpt); }
+    }
+}
+
 int main() {
+    small_grids();
     modes_and_schedule();
     instrumented_modes();
     stack_limits();

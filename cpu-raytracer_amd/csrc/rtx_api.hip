@@ -183,6 +183,11 @@ extern "C" int rtx_create(const rtx_config * config, rtx_ctx ** out_ctx) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, config->device) != hipSuccess) { delete c; return RTX_ERR_HIP; }
     c->n_cu = prop.multiProcessorCount;
+    {   // RTX_GRID_CUS=n (tests, A/B runs): every grid below is sized as if the device had n compute units, 1 .. the device's count (more: the
+        // device's count).  The persistent kernels then go through their dynamic rounds on frames of a few tiles (tests/test_gpu_small_grids.py)
+        const long long cus = knob_int("RTX_GRID_CUS", c->n_cu, 1, 1 << 20);
+        if (cus < c->n_cu) c->n_cu = (int)cus;
+    }
     if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) { delete c; return RTX_ERR_HIP; }
     c->stream = c->own_stream;
     // any_stream is created on first use (two-stream mode only): HIP multiplexes streams onto a few hardware queues, and an unused
@@ -261,6 +266,8 @@ extern "C" int rtx_create(const rtx_config * config, rtx_ctx ** out_ctx) {
     {   // the packet queues hand out packets k * 8 + head after a static first round of one packet per wave: whole rounds only, so waves % 8 == 0
         const int g = RTX_PK_CLASSES * RTX_WAVE / RTX_PK_BLOCK > 1 ? RTX_PK_CLASSES * RTX_WAVE / RTX_PK_BLOCK : 1;
         c->pk_blocks_any = (c->pk_blocks_any + g - 1) / g * g; c->pk_blocks_closest = (c->pk_blocks_closest + g - 1) / g * g;
+        if (c->pk_blocks_any < g) c->pk_blocks_any = g;      // a fraction of very few compute units (RTX_PK_GRID_* with RTX_GRID_CUS) rounds to no workgroup at all
+        if (c->pk_blocks_closest < g) c->pk_blocks_closest = g;
     }
     // threads of the largest launch that indexes the per-thread spill / work-list regions with its global thread id
     long long max_threads = (long long)(c->trace_blocks_closest > c->trace_blocks_any ? c->trace_blocks_closest : c->trace_blocks_any) * RTX_TRACE_BLOCK;
@@ -1842,6 +1849,14 @@ extern "C" int rtx_debug_blas_wide(rtx_ctx * c, int32_t blas_id, int32_t * stack
 extern "C" int rtx_debug_blas_wide_closest(rtx_ctx * c, int32_t blas_id, int32_t * stack_need) {
     if (!c || !stack_need || blas_id < 0 || (size_t)blas_id >= c->h_blas.size() || !c->h_blas[blas_id].nodes) return RTX_ERR_INVALID_ARG;
     *stack_need = c->h_blas[blas_id].pk4c_nodes ? c->h_blas[blas_id].pk4c_need : -1;
+    return RTX_OK;
+}
+
+// the grids rtx_create sized (from the device, RTX_GRID_CUS and the grid knobs), as the launches use them: launches nothing, waits for nothing
+extern "C" int rtx_debug_grids(rtx_ctx * c, int32_t out[8]) {
+    if (!c || !out) return RTX_ERR_INVALID_ARG;
+    out[0] = c->n_cu; out[1] = c->trace_blocks_closest; out[2] = c->trace_blocks_any; out[3] = c->trace_blocks_count;
+    out[4] = c->pk_blocks_closest; out[5] = c->pk_blocks_any; out[6] = c->item_blocks; out[7] = c->q.spill_threads;
     return RTX_OK;
 }
 

@@ -90,10 +90,11 @@ static inline void plan_stack_limits(const StackFigures & s, bool & lane, bool &
 // Grids of the streaming kernels (k_shade, k_resolve: grid-stride loops, any grid is correct) follow the batch: level d of a batch of P
 // primary slots is given room for P / 2^d rays — the dispatcher spends ~16 ns per workgroup, which is most of a small launch's
 // time (a 1/8 tile shard's k_shade launches of levels 1-3: 18 us each with 1 024 workgroups for 74 k / 6 k / 1 k rays).
+#define PLAN_LEVEL_BLOCKS_MIN 64      // never fewer workgroups than this, whatever `full` is: stats_stride (plan_render) allows for it
 static inline int plan_level_blocks(int primary_slots, int level, int full) {
     const long long want = (((long long)primary_slots >> level) + 255) / 256;
     const long long most = (long long)full < want ? (long long)full : want;
-    return (int)(most > 64 ? most : 64);
+    return (int)(most > PLAN_LEVEL_BLOCKS_MIN ? most : PLAN_LEVEL_BLOCKS_MIN);
 }
 
 // Partial tallies level `level`'s shading pass leaves for k_resolve: one per wave of the fused packet kernel, or one per k_shade workgroup
@@ -148,6 +149,8 @@ static inline RenderPlan plan_render(const PlanInputs & in) {
     p.shade_blocks = in.n_cu * K.shade_grid;      // k_shade (RTX_SHADE_BLOCK = 256 threads, 3 resident blocks per CU at 168 VGPRs)
     p.pk_waves_closest = in.pk_blocks_closest * (RTX_PK_BLOCK / RTX_WAVE);
     p.stats_stride = p.shade_blocks > p.pk_waves_closest ? p.shade_blocks : p.pk_waves_closest;      // per level: one entry per k_shade workgroup, or per wave of the fused packet kernel
+    // a k_shade launch has plan_level_blocks' floor of workgroups even where shade_blocks is smaller (few CUs, RTX_GRID_CUS): each writes its entry
+    if (p.stats_stride < PLAN_LEVEL_BLOCKS_MIN) p.stats_stride = PLAN_LEVEL_BLOCKS_MIN;
 
     // Item chunks of the split shadow-ray walk (rtx_packet.h, k_items): one chunk per wave of the packet launch, sized ONCE per call for its
     // largest batch — ≈0.3 items per shadow ray in the cfg3 frame, the fullest chunk 3x the average, so 3.5x the expected average, in

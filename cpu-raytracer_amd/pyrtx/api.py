@@ -28,7 +28,8 @@ EXPORTS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error", "rt
            "rtx_bind_blas_vertices", "rtx_refit_blas", "rtx_read_blas", "rtx_alloc_blas", "rtx_build_blas",
            "rtx_query_closest", "rtx_query_occluded", "rtx_debug_query_order", "rtx_debug_read_layouts",
            "rtx_alloc_texture", "rtx_update_texture", "rtx_read_texture", "rtx_update_sky",
-           "rtx_alloc_blas_topology", "rtx_set_blas_topology", "rtx_blas_vertex_normals", "rtx_query_nearest", "rtx_query_hits", "rtx_query_sweep"]
+           "rtx_alloc_blas_topology", "rtx_set_blas_topology", "rtx_blas_vertex_normals", "rtx_query_nearest", "rtx_query_hits", "rtx_query_sweep",
+           "rtx_debug_grids"]
 # newer than the A/B variants tools/ab.py may load (RTX_HIP_LIB = a library built from an older commit): bound when the library has them,
 # otherwise a call raises AttributeError (undefined symbol)
 VIEW_EXPORTS = ("rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer")
@@ -45,8 +46,9 @@ NORMALS_EXPORTS = ("rtx_alloc_blas_topology", "rtx_set_blas_topology", "rtx_blas
 NEAREST_EXPORTS = ("rtx_query_nearest",)
 HITS_EXPORTS = ("rtx_query_hits",)
 SWEEP_EXPORTS = ("rtx_query_sweep",)
+GRID_EXPORTS = ("rtx_debug_grids",)
 OPTIONAL_EXPORTS = (VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + QUERY_SORT_EXPORTS + LAYOUT_EXPORTS
-                    + TEXTURE_EXPORTS + NORMALS_EXPORTS + NEAREST_EXPORTS + HITS_EXPORTS + SWEEP_EXPORTS)
+                    + TEXTURE_EXPORTS + NORMALS_EXPORTS + NEAREST_EXPORTS + HITS_EXPORTS + SWEEP_EXPORTS + GRID_EXPORTS)
 RTX_QUERY_MAX_HITS = 8
 # texel formats of rtx_update_texture (include/rtx.h RTX_TEXELS_*)
 RTX_TEXELS_RGB_F32 = 0
@@ -179,6 +181,8 @@ def load_library(path: Optional[str] = None):
         lib.rtx_debug_query_order.argtypes = [vp, vp, i32, C.c_int64, vp]
     if hasattr(lib, "rtx_debug_read_layouts"):
         lib.rtx_debug_read_layouts.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "rtx_debug_grids"):
+        lib.rtx_debug_grids.argtypes = [vp, vp]
     if hasattr(lib, "rtx_update_texture"):
         lib.rtx_alloc_texture.argtypes = [vp, i32, i32, i32, i32]
         lib.rtx_update_texture.argtypes = [vp, i32, vp, i32]
@@ -1014,6 +1018,17 @@ class Renderer:
         return {"pk": pk, "pk4": pk4, "pk4c": pk4c, "planes": planes}
 
     # ---- ray queries (include/rtx.h: rtx_query_closest / rtx_query_occluded) ---------------------------------------------------------
+    GRID_NAMES = ("cus", "trace_blocks_closest", "trace_blocks_any", "trace_blocks_count", "pk_blocks_closest", "pk_blocks_any", "item_blocks",
+                  "spill_threads")
+
+    def debug_grids(self) -> np.ndarray:
+        """The grids this context launches (rtx_debug_grids), in GRID_NAMES order: the compute units they are sized for (RTX_GRID_CUS, else the
+        device's), the workgroups of the per-lane closest-hit, per-lane shadow-ray and plain traversal launches (256 threads each), of the
+        closest-hit and shadow-ray packet launches and of the item launch (one wave each), and the threads the spill regions hold."""
+        out = np.zeros(8, np.int32)
+        self._chk(self.lib.rtx_debug_grids(self.ctx, out.ctypes.data), "rtx_debug_grids")
+        return out
+
     def _query_rows(self, name: str, rows, width: int, n: Optional[int]):
         """(device pointer, n, tensor or None) of a query's input: a float32 torch tensor (n, width), or a raw device pointer with n.
         Raises before anything reaches the library; _query_on_device checks where the tensor lives."""

@@ -890,6 +890,11 @@ int rtx_debug_blas_wide_closest(rtx_ctx * ctx, int32_t blas_id, int32_t * stack_
  * is written.  RTX_ERR_INVALID_ARG: an id below -1 or above the id range; RTX_ERR_STATE: no BLAS uploaded under that id / before rtx_set_frame. */
 int rtx_debug_read_layouts(rtx_ctx * ctx, int32_t blas_id, int32_t * info8, float * pk_nodes, float * pk4_nodes, float * pk4c_nodes,
                            float * planes_x, float * planes_y, float * planes_z);
+/* the grids the context launches, as rtx_create sized them from the device, RTX_GRID_CUS and the grid knobs (launches nothing): out[0] = compute
+ * units the grids are sized for, [1..3] = workgroups of the per-lane closest-hit, the per-lane shadow-ray and the plain traversal launches
+ * (256 threads each), [4..5] = workgroups of the closest-hit and the shadow-ray packet launches (one wave each), [6] = workgroups of the item
+ * launch (one wave each), [7] = threads the per-thread spill regions hold */
+int rtx_debug_grids(rtx_ctx * ctx, int32_t out[8]);
 /* Sky::sample (Sky.cpp:28-68) of the uploaded sky at n directions */
 int rtx_debug_sky_sample(rtx_ctx * ctx, const float * directions_xyz, float * out_rgb, int32_t n);
 

@@ -240,10 +240,14 @@ def test_invalid_knob_values_are_ignored(api, monkeypatch):
     """Knobs are parsed once in rtx_create, validated and clamped: zero / negative / non-numeric values keep the defaults (a zero-size
     k_shade grid or a negative shift count in the asm walkers would otherwise break production rendering through an inherited variable)."""
     for k, v in {"RTX_SHADE_GRID": "0", "RTX_PK_DEFER": "-5", "RTX_PK_GROW": "-3", "RTX_PK_SPLIT": "-64", "RTX_PK_DEFER_LEAF": "banana",
-                 "RTX_SLOT_BUDGET": "-1", "RTX_ITEM_GRID": "0", "RTX_PK_GRID_ANY": "-2", "RTX_RESOLVE_BLOCK": "100", "RTX_LANE_FROM_LEVEL_ANY": "-7"}.items():
+                 "RTX_SLOT_BUDGET": "-1", "RTX_ITEM_GRID": "0", "RTX_PK_GRID_ANY": "-2", "RTX_RESOLVE_BLOCK": "100", "RTX_LANE_FROM_LEVEL_ANY": "-7",
+                 "RTX_GRID_CUS": "0"}.items():
         monkeypatch.setenv(k, v)
+    import torch
     sc, g = util.load_golden("materials_aniso")
-    cmp = util.compare_to_golden(api.Renderer(sc).render(), g)
+    r = api.Renderer(sc)
+    assert r.debug_grids()[0] == torch.cuda.get_device_properties(0).multi_processor_count      # no grid of no compute units
+    cmp = util.compare_to_golden(r.render(), g)
     assert cmp["stats_equal"] and cmp["max_abs"] == 0.0 and cmp["packed_mismatch"] == 0, cmp
 
 
