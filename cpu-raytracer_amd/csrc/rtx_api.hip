@@ -1786,13 +1786,16 @@ __global__ void k_debug_libm(int fn, const float * a, const float * b, float * o
         case 3: r = rtx_log2f(a[i]); break;
         case 4: r = rtx_atanf(a[i]); break;
         case 5: r = (float)f2i_rn_x86(a[i]); break;
-        default: r = 1.0f / sqrtf(a[i]); break;
+        case 6: r = 1.0f / sqrtf(a[i]); break;                  // the reciprocal length of vnormalize
+        case 7: r = (float)f2i_trunc_x86(a[i]); break;
+        case 8: r = pow2_128(a[i]); break;
+        default: return;                                        // rtx_debug_libm refuses every other id before the launch
     }
     out[i] = r;
 }
 
 extern "C" int rtx_debug_libm(rtx_ctx * c, int32_t fn, const float * a, const float * b, float * out, int32_t n) {
-    if (!c || !a || !out || n <= 0) return RTX_ERR_INVALID_ARG;
+    if (!c || !a || !out || n <= 0 || fn < 0 || fn > 8) return RTX_ERR_INVALID_ARG;
     hipSetDevice(c->cfg.device);
     DevBuf da, db, dout;                 // scratch of this call: released on every way out
     int rc = upload(c, da, a, (size_t)n * 4);

@@ -7,14 +7,19 @@
 // from the host's libm would flip texels.  They are therefore implemented here as the classic
 // fdlibm single-precision algorithms (the algorithm glibc 2.35's libm uses for these two
 // functions: pure fp32 +,-,*,/ and sqrt, all correctly rounded on gfx950), and are checked
-// bit-for-bit against the host libm in tests/test_libm.py (exhaustively for acosf and atanf).
-// The file also compiles for the host (plain C++) for exactly that test.
+// bit-for-bit against the host libm.  Which build is swept where:
+//   host build   (gcc; the file also compiles as plain C / C++)  tests/native/libm_check.c: all 2^32 inputs of acosf, atanf, expf, log2f
+//                and 2e9 atan2f pairs; tests/test_libm.py runs it with a stride
+//   device build (hipcc for gfx950, the code the kernels run; the host's bits only under csrc/Makefile's -ffp-contract=off, -fno-fast-math,
+//                -fhip-fp32-correctly-rounded-divide-sqrt, -fno-gpu-flush-denormals-to-zero)  tests/test_gpu_libm_sweep.py through
+//                rtx_debug_libm, on the sets of tests/libmset.py: every exponent, subnormals and specials, every 509th bit pattern, +-2048
+//                patterns around each constant compared against below, all inputs with subnormal results, atan2f pairs whose quotient underflows
 //
 // expf / log2f (Beer attenuation, mip LOD — the LOD is floored into a mip level, so it decides discretely too) are glibc 2.35's
 // own algorithms: the table-driven double-precision routines of ARM's optimized-routines (exp2f_data N = 32, log2f_data N = 16),
 // in the operation order AND fused-multiply-add pattern of the variant glibc selects on every FMA-capable x86-64 CPU
 // (`__expf_fma`, `__log2f_fma`, read off the disassembly of libm.so.6; tables and constants extracted from its .rodata).  fp64 +, *
-// and fma are correctly rounded on gfx950, so the results are the host's bit for bit (tests/test_libm.py, exhaustive sweep available).
+// and fma are correctly rounded on gfx950, so the results are the host's bit for bit (swept as above, on both builds).
 #pragma once
 #include <stdint.h>
 

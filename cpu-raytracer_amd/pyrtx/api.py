@@ -1348,6 +1348,8 @@ class Renderer:
 
     # ---- unit-level hooks ---------------------------------------------------------------------------
     def debug_libm(self, fn: int, a: np.ndarray, b: Optional[np.ndarray] = None) -> np.ndarray:
+        """rtx_debug_libm: fn 0 acosf 1 atan2f(a, b) 2 expf 3 log2f 4 atanf 5 f2i_rn_x86 6 1 / sqrtf 7 f2i_trunc_x86 8 pow2_128, as the device
+        build computes them; 5 and 7 come back as floats.  Any other id raises RtxError (RTX_ERR_INVALID_ARG)."""
         a = np.ascontiguousarray(a, np.float32)
         bb = np.ascontiguousarray(b, np.float32) if b is not None else a
         out = np.zeros_like(a)

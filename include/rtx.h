@@ -849,7 +849,9 @@ int rtx_group_slot_pixels(int32_t width, int32_t height, int32_t world, int32_t 
 /* ---- unit-level entry points: one reference function each, evaluated on the device -------------
  * (used by the parity tests; not needed by a renderer)                                          */
 
-/* fn: 0 acosf(a) 1 atan2f(a,b) 2 expf(a) 3 log2f(a) 4 atanf(a) 5 Util::float_to_int(a) 6 1/sqrtf(a) */
+/* fn: 0 acosf(a) 1 atan2f(a,b) 2 expf(a) 3 log2f(a) 4 atanf(a) 5 Util::float_to_int(a) = cvtss2si 6 1/sqrtf(a) 7 (int)a = cvttss2si
+ * 8 Math::pow2<128>(a), n values each; 5 and 7 return the integer as a float (exact: 24 significant bits at most, the indefinite value
+ * is -2^31).  Any other fn: RTX_ERR_INVALID_ARG, nothing allocated or launched. */
 int rtx_debug_libm(rtx_ctx * ctx, int32_t fn, const float * a, const float * b, float * out, int32_t n);
 /* Texture::sample (Texture.h:33-49) of an uploaded texture at n inputs (s,t,ds_dx,ds_dy,dt_dx,dt_dy) */
 int rtx_debug_texture_sample(rtx_ctx * ctx, int32_t texture_id, const float * in6, float * out_rgb, int32_t n);

@@ -184,7 +184,8 @@ def test_single_leaf_mesh(api, name, k):
 
 def test_group_attach_and_debug_entry_points_refuse_bad_arguments(api):
     """Status codes instead of faults: rtx_group_attach with a foreign resolution / the base itself / no group, rtx_debug_blas_wide with an
-    unknown mesh id, rtx_debug_read_layouts with a bad id, an id nothing was uploaded under and before a frame was set."""
+    unknown mesh id, rtx_debug_libm with an unknown function id, rtx_debug_read_layouts with a bad id, an id nothing was uploaded under and
+    before a frame was set."""
     import ctypes as C
     sc, _ = util.load_golden("cube")
     sc2, _ = util.load_golden("monkey_small")
@@ -201,6 +202,15 @@ def test_group_attach_and_debug_entry_points_refuse_bad_arguments(api):
     need = C.c_int32(0)
     assert r.lib.rtx_debug_blas_wide(r.ctx, 99, C.byref(need)) == 1
     assert r.lib.rtx_debug_blas_wide(r.ctx, 0, None) == 1
+    # rtx_debug_libm: ids 0 .. 8 only (an unknown id used to answer with 1 / sqrtf); the refusal comes before anything is written
+    one = np.array([4.0], np.float32)
+    for bad_id in (-1, 9, 10, 255, 1 << 30, -(1 << 31)):
+        res = np.array([-7.0], np.float32)
+        assert r.lib.rtx_debug_libm(r.ctx, bad_id, one.ctypes.data, one.ctypes.data, res.ctypes.data, 1) == 1, bad_id
+        assert res[0] == -7.0, bad_id
+        with pytest.raises(api.RtxError):
+            r.debug_libm(bad_id, one)
+    assert r.debug_libm(6, one).tolist() == [0.5] and r.debug_libm(7, np.array([-2.75], np.float32)).tolist() == [-2.0] and r.debug_libm(8, np.array([0.5], np.float32)).tolist() == [2.0 ** -128]
     # rtx_debug_read_layouts: the status codes of rtx_read_blas / rtx_read_frame_state, every destination optional
     nul = (None,) * 7
     assert r.lib.rtx_debug_read_layouts(None, 0, *nul) == 1
