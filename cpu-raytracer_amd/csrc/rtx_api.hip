@@ -138,6 +138,9 @@ struct rtx_ctx {
     DevBuf d_nearest_head; bool nearest_fetch = true;
     // rtx_query_nearest / rtx_query_hits / rtx_query_sweep: RTX_QUERY_GRID=g caps their grids at g workgroups (0: the spill region's size alone decides)
     int query_grid = 0;
+    // rtx_set_object_masks / rtx_update_object_masks: the table the filtered walk queries read (M uint32_t, grown only, filled through a staging
+    // ring of its own like the cameras), whether there is one, and (I, S, P) of the frame it was set for
+    DevBuf d_object_masks; StageRing mask_ring; bool masks_set = false; int32_t mask_counts[3] = { 0, 0, 0 };
     size_t slots_alloc = 0, shadow_alloc = 0;
     DevBuf d_stats_partial, d_pk_fifo, d_counters, d_spill, d_fb_rgb, d_fb_packed, d_display, d_gamma, d_pk_heads;
     int trace_blocks_closest = 0, trace_blocks_any = 0, trace_blocks_count = 0;
@@ -2313,6 +2316,85 @@ static int query_max_blocks(const rtx_ctx * c) {
     return c->query_grid > 0 && c->query_grid < fit ? c->query_grid : fit;
 }
 
+// ---- object masks (include/rtx.h: rtx_set_object_masks ...; the rule is FILTER of rtx_nearest_math.h) -----------------------------------
+// The table is the context's: M = I + S + P uint32_t in the numbering of RTX_AOV_OBJECT_ID, grown only (the one branch that waits), filled by
+// a copy on the context's stream, so a query queued before a change reads the old masks and one queued after it the new ones.  Dropping the
+// table keeps its memory.  The filtered queries take the pointer by value; rtx_set_frame, rtx_update_instances, refit and build never touch it.
+static int32_t frame_object_count(const rtx_ctx * c) { return c->scene.instance_count + c->scene.sphere_count + c->scene.plane_count; }
+static int object_mask_checks(rtx_ctx * c, const void * masks, int32_t count, const char * what, bool & drop) {
+    if (!c) return RTX_ERR_INVALID_ARG;
+    if (!c->frame_set) { c->err = std::string(what) + " before rtx_set_frame"; return RTX_ERR_STATE; }
+    drop = !masks && count == 0;
+    if (drop) return RTX_OK;
+    if (!masks || count != frame_object_count(c)) {
+        c->err = std::string(what) + ": count must be instances + spheres + planes of the current frame (" + std::to_string(frame_object_count(c)) + "), or 0 with a null pointer to drop the table";
+        return RTX_ERR_INVALID_ARG;
+    }
+    return RTX_OK;
+}
+static int object_mask_room(rtx_ctx * c, size_t bytes) {
+    if (bytes <= c->d_object_masks.cap && c->d_object_masks.p) return RTX_OK;
+    HIP_OK(c, hipStreamSynchronize(c->stream));                // growth: queued queries still read the old table
+    return ensure(c, c->d_object_masks, bytes);
+}
+static void object_masks_remember(rtx_ctx * c) {
+    c->masks_set = true;
+    c->mask_counts[0] = c->scene.instance_count; c->mask_counts[1] = c->scene.sphere_count; c->mask_counts[2] = c->scene.plane_count;
+}
+extern "C" int rtx_set_object_masks(rtx_ctx * c, const uint32_t * masks_host, int32_t count) {
+    bool drop = false;
+    if (int bad = object_mask_checks(c, masks_host, count, "rtx_set_object_masks", drop)) return bad;
+    if (drop) { c->masks_set = false; return RTX_OK; }
+    hipSetDevice(c->cfg.device);
+    const size_t bytes = (size_t)count * sizeof(uint32_t);
+    if (int rc = object_mask_room(c, bytes)) return rc;
+    if (bytes) if (int rc = stage_copy(c, c->mask_ring, c->d_object_masks.p, masks_host, bytes)) return rc;
+    object_masks_remember(c);
+    return RTX_OK;
+}
+extern "C" int rtx_update_object_masks(rtx_ctx * c, const void * masks_dev, int32_t count) {
+    bool drop = false;
+    if (int bad = object_mask_checks(c, masks_dev, count, "rtx_update_object_masks", drop)) return bad;
+    if (drop) { c->masks_set = false; return RTX_OK; }
+    if ((uintptr_t)masks_dev & 3u) { c->err = "rtx_update_object_masks: the masks must be 4-byte aligned"; return RTX_ERR_INVALID_ARG; }
+    hipSetDevice(c->cfg.device);
+    const size_t bytes = (size_t)count * sizeof(uint32_t);
+    if (int rc = object_mask_room(c, bytes)) return rc;
+    if (bytes) HIP_OK(c, hipMemcpyAsync(c->d_object_masks.p, masks_dev, bytes, hipMemcpyDeviceToDevice, c->stream));
+    object_masks_remember(c);
+    return RTX_OK;
+}
+extern "C" int rtx_read_object_masks(rtx_ctx * c, uint32_t * out, int32_t capacity, int32_t * count) {
+    if (!c || capacity < 0 || (!out && !count)) return RTX_ERR_INVALID_ARG;
+    if (!c->frame_set) { c->err = "rtx_read_object_masks before rtx_set_frame"; return RTX_ERR_STATE; }
+    const int32_t have = c->masks_set ? c->mask_counts[0] + c->mask_counts[1] + c->mask_counts[2] : 0;
+    if (count) *count = have;
+    if (!out || have == 0) return RTX_OK;
+    if (capacity < have) { c->err = "rtx_read_object_masks: capacity below the table's " + std::to_string(have) + " masks"; return RTX_ERR_INVALID_ARG; }
+    hipSetDevice(c->cfg.device);
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    HIP_OK(c, hipMemcpy(out, c->d_object_masks.p, (size_t)have * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RTX_OK;
+}
+// the state rule of a filtered query, after the checks of the unfiltered call: a table set for other counts than the frame's
+static int filter_checks(rtx_ctx * c, const rtx_query_filter * filter, const char * what) {
+    if (!filter || !c->masks_set) return RTX_OK;
+    if (c->mask_counts[0] != c->scene.instance_count || c->mask_counts[1] != c->scene.sphere_count || c->mask_counts[2] != c->scene.plane_count) {
+        c->err = std::string(what) + "_filtered: the object masks were set for " + std::to_string(c->mask_counts[0]) + " instances, " + std::to_string(c->mask_counts[1]) + " spheres and " +
+                 std::to_string(c->mask_counts[2]) + " planes, the frame has other counts (set the masks again, or drop them)";
+        return RTX_ERR_STATE;
+    }
+    return RTX_OK;
+}
+// the kernel arguments of a filtered round that starts at caller row `first`
+static QueryMasks<true> filter_masks(const rtx_ctx * c, const rtx_query_filter * filter, int64_t first) {
+    QueryMasks<true> k;
+    k.table = c->masks_set ? (const uint32_t *)c->d_object_masks.p : nullptr;
+    k.rows = filter->row_masks_dev ? filter->row_masks_dev + first : nullptr;
+    k.row = filter->row_mask;
+    return k;
+}
+
 // ---- nearest-point queries (include/rtx.h: rtx_query_nearest; kernel in rtx_nearest.h, arithmetic and walk in rtx_nearest_math.h) ------
 // n points with a maximum distance each, in device memory, against the frame the context holds: per round of at most RTX_QUERY_CHUNK_RAYS
 // rows ONE launch of k_query_nearest, which reads the rows and writes the channels; with RTX_QUERY_SORT the bounds, key and sort launches of
@@ -2320,7 +2402,7 @@ static int query_max_blocks(const rtx_ctx * c) {
 // reads is touched.  The stack lives in LDS and in regions 0 and 1 of the context's spill buffer, as for a closest-hit launch of this stream.
 // The stack rule: the ordered descent holds at most rtxnp::stack_need(TLAS inner depth, deepest BLAS inner depth) entries; a scene that needs
 // more than rtx_config.stack_size (itself <= RTX_MAX_STACK, what LDS and the spill region hold per lane) is refused here, on the host.
-extern "C" int rtx_query_nearest(rtx_ctx * c, const void * points_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags) {
+static int query_nearest_impl(rtx_ctx * c, const void * points_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags, const rtx_query_filter * filter) {
     if (c && (channels == 0 || (channels & ~(uint32_t)RTX_QUERY_ALL))) { c->err = "rtx_query_nearest: channels must be a non-empty subset of RTX_QUERY_ALL"; return RTX_ERR_INVALID_ARG; }
     if (int bad = query_checks(c, points_dev, n, out, flags, "rtx_query_nearest", (uint32_t)RTX_QUERY_SORT)) return bad;
     int blas_depth = -1;
@@ -2331,6 +2413,7 @@ extern "C" int rtx_query_nearest(rtx_ctx * c, const void * points_dev, int64_t n
                  " + 1, BLAS inner depth " + std::to_string(blas_depth) + " + 1), rtx_config.stack_size allows " + std::to_string(have);
         return RTX_ERR_LIMIT;
     }
+    if (int bad = filter_checks(c, filter, "rtx_query_nearest")) return bad;
     hipSetDevice(c->cfg.device);
     const bool sorted = (flags & RTX_QUERY_SORT) != 0;
     QuerySort S = {};
@@ -2356,10 +2439,19 @@ extern "C" int rtx_query_nearest(rtx_ctx * c, const void * points_dev, int64_t n
         const int tiles = (m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK, blocks = tiles < max_blocks ? tiles : max_blocks;
         const uint64_t * const order = sorted ? S.keys : nullptr;
         if (head) HIP_OK(c, hipMemsetAsync(head, 0, sizeof(uint32_t), c->stream));
-        launch_timed(c, "k_query_nearest", c->stream, [&] { hipLaunchKernelGGL(k_query_nearest, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head); });
+        if (filter) {
+            const QueryMasks<true> km = filter_masks(c, filter, first);
+            launch_timed(c, "k_query_nearest", c->stream, [&] { hipLaunchKernelGGL(k_query_nearest<true>, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, km); });
+        } else launch_timed(c, "k_query_nearest", c->stream, [&] { hipLaunchKernelGGL(k_query_nearest<false>, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, QueryMasks<false>()); });
     }
     HIP_OK(c, hipGetLastError());
     return RTX_OK;
+}
+extern "C" int rtx_query_nearest(rtx_ctx * c, const void * points_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags) {
+    return query_nearest_impl(c, points_dev, n, channels, out, flags, nullptr);
+}
+extern "C" int rtx_query_nearest_filtered(rtx_ctx * c, const void * points_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags, const rtx_query_filter * filter) {
+    return query_nearest_impl(c, points_dev, n, channels, out, flags, filter);
 }
 
 // ---- all-hits segment queries (include/rtx.h: rtx_query_hits; kernel in rtx_hits.h, arithmetic and walk in rtx_hits_math.h) ------------
@@ -2367,8 +2459,8 @@ extern "C" int rtx_query_nearest(rtx_ctx * c, const void * points_dev, int64_t n
 // which reads the rows and writes the first max_hits hits of every row, in order, and the row's count; with RTX_QUERY_SORT the bounds, key and
 // sort launches of the ray queries run first over the 7-float rows, in the same sort block.  No queue set, no counters; the stack as for
 // rtx_query_nearest, its stack rule, and its tile counter (the two calls are ordered by the stream).
-extern "C" int rtx_query_hits(rtx_ctx * c, const void * segments_dev, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
-                              int32_t * count_dev, uint32_t flags) {
+static int query_hits_impl(rtx_ctx * c, const void * segments_dev, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
+                           int32_t * count_dev, uint32_t flags, const rtx_query_filter * filter) {
     if (c) {
         const bool count_only = max_hits == 0 && channels == 0 && count_dev;
         if (!count_only && (max_hits < 1 || max_hits > (int32_t)RTX_QUERY_MAX_HITS || channels == 0 || (channels & ~(uint32_t)RTX_QUERY_ALL))) {
@@ -2385,6 +2477,7 @@ extern "C" int rtx_query_hits(rtx_ctx * c, const void * segments_dev, int64_t n,
                  " + 1, BLAS inner depth " + std::to_string(blas_depth) + " + 1), rtx_config.stack_size allows " + std::to_string(have);
         return RTX_ERR_LIMIT;
     }
+    if (int bad = filter_checks(c, filter, "rtx_query_hits")) return bad;
     hipSetDevice(c->cfg.device);
     const bool sorted = (flags & RTX_QUERY_SORT) != 0;
     QuerySort S = {};
@@ -2412,11 +2505,24 @@ extern "C" int rtx_query_hits(rtx_ctx * c, const void * segments_dev, int64_t n,
         const int tiles = (m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK, blocks = tiles < max_blocks ? tiles : max_blocks;
         const uint64_t * const order = sorted ? S.keys : nullptr;
         HIP_OK(c, hipMemsetAsync(head, 0, sizeof(uint32_t), c->stream));
-        if (K > 0) launch_timed(c, "k_query_hits", c->stream, [&] { hipLaunchKernelGGL(k_query_hits<true>, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, (int)K, t, count, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head); });
-        else launch_timed(c, "k_query_hits", c->stream, [&] { hipLaunchKernelGGL(k_query_hits<false>, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, 0, t, count, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head); });
+        if (filter) {
+            const QueryMasks<true> km = filter_masks(c, filter, first);
+            if (K > 0) launch_timed(c, "k_query_hits", c->stream, [&] { hipLaunchKernelGGL((k_query_hits<true, true>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, (int)K, t, count, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, km); });
+            else launch_timed(c, "k_query_hits", c->stream, [&] { hipLaunchKernelGGL((k_query_hits<false, true>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, 0, t, count, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, km); });
+        }
+        else if (K > 0) launch_timed(c, "k_query_hits", c->stream, [&] { hipLaunchKernelGGL((k_query_hits<true, false>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, (int)K, t, count, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, QueryMasks<false>()); });
+        else launch_timed(c, "k_query_hits", c->stream, [&] { hipLaunchKernelGGL((k_query_hits<false, false>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, 0, t, count, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, QueryMasks<false>()); });
     }
     HIP_OK(c, hipGetLastError());
     return RTX_OK;
+}
+extern "C" int rtx_query_hits(rtx_ctx * c, const void * segments_dev, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
+                              int32_t * count_dev, uint32_t flags) {
+    return query_hits_impl(c, segments_dev, n, max_hits, channels, out, count_dev, flags, nullptr);
+}
+extern "C" int rtx_query_hits_filtered(rtx_ctx * c, const void * segments_dev, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
+                                       int32_t * count_dev, uint32_t flags, const rtx_query_filter * filter) {
+    return query_hits_impl(c, segments_dev, n, max_hits, channels, out, count_dev, flags, filter);
 }
 
 // ---- swept-sphere queries (include/rtx.h: rtx_query_sweep; kernel in rtx_sweep.h, arithmetic and walk in rtx_sweep_math.h) ------------
@@ -2424,7 +2530,7 @@ extern "C" int rtx_query_hits(rtx_ctx * c, const void * segments_dev, int64_t n,
 // which reads the rows and writes the channels; with RTX_QUERY_SORT the bounds, key and sort launches of the ray queries run first over the
 // first seven floats of the 8-float rows, in the same sort block.  No queue set, no counters; the stack as for rtx_query_nearest, its stack
 // rule, and its tile counter (the calls are ordered by the stream).
-extern "C" int rtx_query_sweep(rtx_ctx * c, const void * sweeps_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags) {
+static int query_sweep_impl(rtx_ctx * c, const void * sweeps_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags, const rtx_query_filter * filter) {
     if (c && (channels == 0 || (channels & ~(uint32_t)RTX_QUERY_ALL))) { c->err = "rtx_query_sweep: channels must be a non-empty subset of RTX_QUERY_ALL"; return RTX_ERR_INVALID_ARG; }
     if (int bad = query_checks(c, sweeps_dev, n, out, flags, "rtx_query_sweep", (uint32_t)RTX_QUERY_SORT)) return bad;
     int blas_depth = -1;
@@ -2435,6 +2541,7 @@ extern "C" int rtx_query_sweep(rtx_ctx * c, const void * sweeps_dev, int64_t n, 
                  " + 1, BLAS inner depth " + std::to_string(blas_depth) + " + 1), rtx_config.stack_size allows " + std::to_string(have);
         return RTX_ERR_LIMIT;
     }
+    if (int bad = filter_checks(c, filter, "rtx_query_sweep")) return bad;
     hipSetDevice(c->cfg.device);
     const bool sorted = (flags & RTX_QUERY_SORT) != 0;
     QuerySort S = {};
@@ -2460,10 +2567,19 @@ extern "C" int rtx_query_sweep(rtx_ctx * c, const void * sweeps_dev, int64_t n, 
         const int tiles = (m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK, blocks = tiles < max_blocks ? tiles : max_blocks;
         const uint64_t * const order = sorted ? S.keys : nullptr;
         HIP_OK(c, hipMemsetAsync(head, 0, sizeof(uint32_t), c->stream));
-        launch_timed(c, "k_query_sweep", c->stream, [&] { hipLaunchKernelGGL(k_query_sweep, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head); });
+        if (filter) {
+            const QueryMasks<true> km = filter_masks(c, filter, first);
+            launch_timed(c, "k_query_sweep", c->stream, [&] { hipLaunchKernelGGL(k_query_sweep<true>, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, km); });
+        } else launch_timed(c, "k_query_sweep", c->stream, [&] { hipLaunchKernelGGL(k_query_sweep<false>, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, QueryMasks<false>()); });
     }
     HIP_OK(c, hipGetLastError());
     return RTX_OK;
+}
+extern "C" int rtx_query_sweep(rtx_ctx * c, const void * sweeps_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags) {
+    return query_sweep_impl(c, sweeps_dev, n, channels, out, flags, nullptr);
+}
+extern "C" int rtx_query_sweep_filtered(rtx_ctx * c, const void * sweeps_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags, const rtx_query_filter * filter) {
+    return query_sweep_impl(c, sweeps_dev, n, channels, out, flags, filter);
 }
 
 // the order RTX_QUERY_SORT traces n rows of row_floats (6: rays, 7: segments) floats in: the bounds, key and sort launches of every round and

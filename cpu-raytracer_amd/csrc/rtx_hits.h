@@ -101,10 +101,11 @@ RTX_D void hit_write_miss(const DevQuery & out, const size_t e) {
 }
 
 // rows7: the m segments of the round; out: the channel arrays advanced to the round's first row (K entries per row); count: likewise, or null
-template <bool LIST>
+// FILTERED: the masks of rtx_query_hits_filtered (rtx_nearest.h); the list, the stack and the tile counter are the same
+template <bool LIST, bool FILTERED>
 __global__ __launch_bounds__(RTX_QUERY_BLOCK)
 void k_query_hits(const DevScene sc, const float * __restrict__ rows7, const int m, const int K, const DevQuery out, int32_t * __restrict__ count,
-                  const uint64_t * __restrict__ order, int32_t * const spill_base, const int spill_threads, uint32_t * const head) {
+                  const uint64_t * __restrict__ order, int32_t * const spill_base, const int spill_threads, uint32_t * const head, const QueryMasks<FILTERED> masks) {
     __shared__ float lds_rows[7 * RTX_QUERY_BLOCK];
     __shared__ int lds_stack[RTX_QUERY_BLOCK / RTX_WAVE][RTX_LDS_STACK][RTX_WAVE];
     __shared__ float lds_key[RTX_QUERY_BLOCK / RTX_WAVE][RTX_LDS_STACK][RTX_WAVE];
@@ -127,11 +128,17 @@ void k_query_hits(const DevScene sc, const float * __restrict__ rows7, const int
         if (order) query_gather_row<7>(order, rows7, m, i, r);
         else query_load_row<7>(lds_rows, rows7, m, r, tile);
         if (i >= m) continue;
-        HitsScene S = { { sc, RTX_GPTR(sc.tlas_nodes), nullptr, nullptr } };
         rtxhp::Tally w;
         typename std::conditional<LIST, HitsList, HitsNoList>::type L;
         if constexpr (LIST) L.base = &lds_list[threadIdx.x];
-        rtxhp::walk(S, st, L, r, LIST ? K : 0, count != nullptr, w);
+        if constexpr (FILTERED) {
+            const size_t pr = order ? (size_t)rtxq::key_row(order[i]) : (size_t)i;
+            Masked<HitsScene> S = { { { sc, RTX_GPTR(sc.tlas_nodes), nullptr, nullptr } }, masks.table, pr < (size_t)m ? query_row_mask(masks, pr) : 0u };
+            rtxhp::walk(S, st, L, r, LIST ? K : 0, count != nullptr, w);
+        } else {
+            HitsScene S = { { sc, RTX_GPTR(sc.tlas_nodes), nullptr, nullptr } };
+            rtxhp::walk(S, st, L, r, LIST ? K : 0, count != nullptr, w);
+        }
 
         const size_t p = order ? (size_t)rtxq::key_row(order[i]) : (size_t)i;      // the caller's row of this slot
         if (p >= (size_t)m) continue;                                              // never: a sorted key holds a row of the round

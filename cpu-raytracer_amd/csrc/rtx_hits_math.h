@@ -33,6 +33,9 @@
 //      (slab_test_key, rtx_trace.h), so the re-test reads no memory.
 //   6. A TLAS leaf takes its instances in tlas_indices order, stepped through in two registers, not on the stack; a BLAS leaf its slots in order.
 //   7. The triangle test always uses tmax = D: only boxes see the shrunken bound.  A hit at or beyond the K-th of a full list changes nothing.
+//   FILTER (rtx_query_hits_filtered): the rule and the places of rtx_nearest_math.h's FILTER — a row whose mask is 0 has count 0 and an empty
+//   list without a walk, a hidden sphere or plane is passed over in step 1, a hidden instance in step 6 before its matrix or its BLAS is
+//   touched.  Hidden objects are neither listed nor counted; PROMISED holds against the exhaustive search over the visible primitives.
 //   With a count the bound never moves and the walk visits exactly the nodes a segment of length D passes: the node set of the reference's
 //   any-hit walk had it not stopped at its first hit.  STACK: a push happens only at an inner node and leaves one sibling per level of the
 //   current path: at most rtxnp::stack_need() entries, by the argument of rtx_nearest_math.h.  The caller checks it; there is no overflow path.
@@ -57,7 +60,7 @@
 //            scale = (|s| + |e1| + |e2|) / |cd|         for t.
 //          A transformed instance moves co by 4u W and cd likewise, W = |o| + |co| (xform_pos rounds four times): add 8 W / min(|e1|, |e2|)
 //          resp. 8 W / |cd| to the scale.  An identity matrix is exact: W = 0.  margin(kappa, scale) = 16 * 2^-24 * kappa * scale.
-// OUT OF SCOPE  hits beyond RTX_QUERY_MAX_HITS per row, an any-hit callback or per-material filtering, a per-ray tmin other than RAY_EPSILON,
+// OUT OF SCOPE  hits beyond RTX_QUERY_MAX_HITS per row, an any-hit callback or per-material filtering (FILTER hides whole objects by mask, nothing finer), a per-ray tmin other than RAY_EPSILON,
 //          signed distance as a single call, barycentrics as a channel, the rtx_group_* path.
 #pragma once
 #include <stdint.h>
@@ -190,6 +193,7 @@ template <typename Scene, typename List>
 RTX_HDF void world_primitives(Scene & sc, List & L, const int K, const bool shrink, Tally & w, const P3 o, const P3 d, const float D) {
     const int32_t ic = sc.instance_count(), sn = sc.sphere_count();
     for (int i = 0; i < sn; i++) {
+        if (!sc.sphere_visible(i)) continue;
         P3 c; float r2, t0, t1;
         sc.sphere(i, c, r2);
         if (!sphere_roots(c, r2, o, d, t0, t1)) continue;
@@ -197,6 +201,7 @@ RTX_HDF void world_primitives(Scene & sc, List & L, const int K, const bool shri
         if (in_range(t1, D)) offer(L, K, shrink, w, t1, ic + i, -1);
     }
     for (int i = 0; i < sc.plane_count(); i++) {
+        if (!sc.plane_visible(i)) continue;
         P3 n; float dist;
         sc.plane(i, n, dist);
         const float t = plane_t(n, dist, o, d);
@@ -205,12 +210,12 @@ RTX_HDF void world_primitives(Scene & sc, List & L, const int K, const bool shri
 }
 
 // The walk.  Scene gives the records as for rtxnp::walk, plus instance_count() and enter(slot, o, d, co, cd) (makes the BLAS of instance
-// tlas_indices[slot] current, gives the local ray, returns that instance).  Stack gives push(sp, node, key) and pop(sp, node, key).
+// tlas_indices[slot] current, gives the local ray, returns that instance) and FILTER's predicates.  Stack gives push(sp, node, key) and pop(sp, node, key).
 // counted: a count is requested, the bound stays D.
 template <typename Scene, typename Stack, typename List>
 RTX_HDF void walk(Scene & sc, Stack & st, List & L, const float * row, const int K, const bool counted, Tally & w) {
     w.count = 0; w.held = 0; w.bound = 0.0f;
-    if (!row_is_live(row)) return;
+    if (!row_is_live(row) || !sc.row_visible()) return;
     const P3 o = mk(row[0], row[1], row[2]), d = mk(row[3], row[4], row[5]);
     const float D = row[6];
     const bool shrink = !counted;
@@ -227,6 +232,7 @@ RTX_HDF void walk(Scene & sc, Stack & st, List & L, const float * row, const int
         if (cur < 0) {
             if (in_blas && sp == floor_sp) { in_blas = false; co = o; cd = d; cinv = winv; }      // this instance is done: back to world space
             if (!in_blas && tl_i < tl_end) {                                                      // the next instance of the TLAS leaf
+                if (!sc.instance_visible(tl_i)) { tl_i++; continue; }                             // FILTER: hidden from this row
                 inst = sc.enter(tl_i++, o, d, co, cd);
                 cinv = rcp(cd);
                 P3 mn, mx; sc.blas_node(0, mn, mx, first, count);

@@ -13,6 +13,14 @@
 // (one dword per lane and instruction: conflict free), deeper ones in regions 0 and 1 of the context's spill buffer, which closest-hit
 // launches of the same stream use the same way.  At most rtxnp::stack_need() entries; the host refuses a scene that needs more than
 // min(stack_size, RTX_MAX_STACK) before the launch, so there is no overflow path here.  LDS: 4 KiB of staged rows + 2 x 16 KiB.
+//
+// FILTERED (rtx_query_nearest_filtered; the same in k_query_hits and k_query_sweep): the instantiation whose Scene answers FILTER's
+// predicates of rtx_nearest_math.h from the context's object-mask table and the row's mask.  It takes three more kernel arguments
+// (QueryMasks<true>: the table or null, the row masks or null, the scalar); DevScene is the same.  The row's mask is loaded once with the
+// row — at the caller's row, so through the order of a sorted round like the row itself — and stays in one register; a tile's lanes set it
+// anew.  An instance's mask is one dword at table[tlas_indices[slot]], read at the TLAS leaf ahead of the instance's 64-byte matrix; the
+// masks of spheres and planes are read at an index every lane shares.  Stack, spill addressing, staged rows and the tile counter are those
+// of the unfiltered instantiation, which is the code it was: its Scene's predicates are constants.
 #pragma once
 #include "rtx_query.h"
 #include "rtx_shade.h"
@@ -21,6 +29,7 @@
 struct NearestScene {
     const DevScene & sc;
     rtx_gptr tlas, nodes, tris;
+    RTX_WALK_UNFILTERED
     RTX_D int sphere_count() const { return sc.sphere_count; }
     RTX_D int plane_count() const { return sc.plane_count; }
     RTX_D int tlas_nodes() const { return sc.tlas_node_count; }
@@ -46,6 +55,21 @@ struct NearestScene {
     }
 };
 
+// the extra kernel arguments of a FILTERED instantiation; none otherwise
+template <bool FILTERED> struct QueryMasks {};
+template <> struct QueryMasks<true> { const uint32_t * table; const uint32_t * rows; uint32_t row; };
+// the mask of caller row p of the round
+RTX_D uint32_t query_row_mask(const QueryMasks<true> & k, const size_t p) { return k.rows ? k.rows[p] : k.row; }
+
+// a Scene (NearestScene, HitsScene) that answers FILTER's predicates: table = the M object masks (null: all ones), row_mask = this lane's
+template <typename Base> struct Masked : Base {
+    const uint32_t * table; uint32_t row_mask;
+    RTX_D bool row_visible() const { return row_mask != 0u; }
+    RTX_D bool sphere_visible(int i) const { return !table || rtxnp::mask_visible(table[this->sc.instance_count + i], row_mask); }
+    RTX_D bool plane_visible(int i) const { return !table || rtxnp::mask_visible(table[this->sc.instance_count + this->sc.sphere_count + i], row_mask); }
+    RTX_D bool instance_visible(int slot) const { return !table || rtxnp::mask_visible(table[this->sc.tlas_indices[slot]], row_mask); }
+};
+
 struct NearestStack {
     int * stk; float * key; int * spill; float * spill_key; int stride;
     RTX_D void push(int sp, int node, float d2) {
@@ -58,9 +82,10 @@ struct NearestStack {
     }
 };
 
+template <bool FILTERED>
 __global__ __launch_bounds__(RTX_QUERY_BLOCK)
 void k_query_nearest(const DevScene sc, const float * __restrict__ rows4, const int m, const DevQuery out, const uint64_t * __restrict__ order,
-                     int32_t * const spill_base, const int spill_threads, uint32_t * const head) {
+                     int32_t * const spill_base, const int spill_threads, uint32_t * const head, const QueryMasks<FILTERED> masks) {
     __shared__ float lds_rows[4 * RTX_QUERY_BLOCK];
     __shared__ int lds_stack[RTX_QUERY_BLOCK / RTX_WAVE][RTX_LDS_STACK][RTX_WAVE];
     __shared__ float lds_key[RTX_QUERY_BLOCK / RTX_WAVE][RTX_LDS_STACK][RTX_WAVE];
@@ -91,9 +116,15 @@ void k_query_nearest(const DevScene sc, const float * __restrict__ rows4, const 
             query_load_row<4>(lds_rows, rows4, m, r, tile);
         }
         if (i >= m) continue;
-        NearestScene S = { sc, RTX_GPTR(sc.tlas_nodes), nullptr, nullptr };
         rtxnp::Answer a;
-        rtxnp::walk(S, st, r, a);
+        if constexpr (FILTERED) {
+            const size_t pr = order ? (size_t)rtxq::key_row(order[i]) : (size_t)i;
+            Masked<NearestScene> S = { { sc, RTX_GPTR(sc.tlas_nodes), nullptr, nullptr }, masks.table, pr < (size_t)m ? query_row_mask(masks, pr) : 0u };
+            rtxnp::walk(S, st, r, a);
+        } else {
+            NearestScene S = { sc, RTX_GPTR(sc.tlas_nodes), nullptr, nullptr };
+            rtxnp::walk(S, st, r, a);
+        }
 
         const size_t p = order ? (size_t)rtxq::key_row(order[i]) : (size_t)i;      // the caller's row of this slot
         if (p >= (size_t)m) continue;                                              // never: a sorted key holds a row of the round

@@ -40,6 +40,14 @@
 //   8. A TLAS leaf takes its instances in tlas_indices order: p_l = xform_pos(world_inv, p), the BLAS from its root with p_l and the same b2.
 //      The instances of a leaf are stepped through in two registers, not on the stack.
 //   9. A BLAS leaf tests its slots in order.
+//   FILTER (rtx_query_nearest_filtered; the same rule in rtx_hits_math.h and rtx_sweep_math.h).  Objects are numbered as RTX_AOV_OBJECT_ID
+//   numbers them: instance i -> i, sphere s -> I + s, plane p -> I + S + p.  An object EXISTS for a row iff (object_mask & row_mask) != 0;
+//   without a table every object_mask is 0xFFFFFFFF.  The Scene answers sphere_visible(i), plane_visible(i), instance_visible(slot) and
+//   row_visible() (the row's mask is not 0); an unfiltered Scene answers true at compile time and the walk is the code it was.  A row that is
+//   not visible is answered like a dead row, without a walk.  A hidden sphere or plane is not offered in step 3.  A hidden instance is passed
+//   over in step 8, where the walk takes it from its TLAS leaf and before its matrix or its BLAS is touched: the leaf's next instance, if
+//   any, is taken by the same loop.  Nothing else changes: TLAS boxes still contain hidden instances, and the order, the tie rules, the
+//   stack rule and stack_need() are the same.  ACCURACY then holds against the exhaustive search over the visible primitives.
 //   The first of several exact ties therefore wins.  STACK: a push happens only at an inner node and leaves one sibling per level of the
 //   current path, so at most (TLAS inner depth + 1) + (BLAS inner depth + 1) entries are ever held (inner depth: the depth of the deepest inner
 //   node, root 0, -1 for a tree that is one leaf): stack_need().  The caller checks it before a walk; there is no overflow path.
@@ -174,17 +182,27 @@ RTX_HDF void offer(Answer & a, float d2, int32_t kind, int32_t object, int32_t s
 
 // The walk.  Scene gives the records: sphere_count(), sphere(i, c, r2), plane_count(), plane(i, n, dist), tlas_nodes() (count, 0 = none),
 // tlas_node(i, mn, mx, first, count), enter(slot, p, p_l) (makes the BLAS of instance tlas_indices[slot] current, returns that instance),
-// blas_node(i, mn, mx, first, count), triangle(i, p0, e1, e2); count's low 30 bits > 0 = a leaf, children of an inner node at first, first + 1.
+// blas_node(i, mn, mx, first, count), triangle(i, p0, e1, e2); count's low 30 bits > 0 = a leaf, children of an inner node at first, first + 1;
+// and FILTER's predicates row_visible(), sphere_visible(i), plane_visible(i), instance_visible(slot) (RTX_WALK_UNFILTERED below: all true).
 // Stack gives push(sp, node, d2) and pop(sp, node, d2) for entry sp.
+// FILTER's predicates of a Scene that hides nothing, for the body of its struct: constants, so that the tests on them leave no code behind
+#define RTX_WALK_UNFILTERED \
+    static constexpr bool row_visible() { return true; } \
+    static constexpr bool sphere_visible(int) { return true; } \
+    static constexpr bool plane_visible(int) { return true; } \
+    static constexpr bool instance_visible(int) { return true; }
+// FILTER's rule
+RTX_HDF bool mask_visible(uint32_t object_mask, uint32_t row_mask) { return (object_mask & row_mask) != 0u; }
+
 template <typename Scene, typename Stack>
 RTX_HDF void walk(Scene & sc, Stack & st, const float * row, Answer & a) {
     a.kind = KIND_NONE; a.object = -1; a.slot = -1; a.u = 0.0f; a.v = 0.0f; a.d2 = infinity();
-    if (!row_is_live(row)) return;
+    if (!row_is_live(row) || !sc.row_visible()) return;
     const P3 p = mk(row[0], row[1], row[2]);
     P3 pl = p;
     a.d2 = row[3] * row[3];
-    for (int i = 0; i < sc.sphere_count(); i++) { P3 c; float r2; sc.sphere(i, c, r2); offer(a, sphere_d2(p, c, r2), KIND_SPHERE, i, -1, 0.0f, 0.0f); }
-    for (int i = 0; i < sc.plane_count(); i++) { P3 n; float dist; sc.plane(i, n, dist); offer(a, plane_d2(p, n, dist), KIND_PLANE, i, -1, 0.0f, 0.0f); }
+    for (int i = 0; i < sc.sphere_count(); i++) { if (!sc.sphere_visible(i)) continue; P3 c; float r2; sc.sphere(i, c, r2); offer(a, sphere_d2(p, c, r2), KIND_SPHERE, i, -1, 0.0f, 0.0f); }
+    for (int i = 0; i < sc.plane_count(); i++) { if (!sc.plane_visible(i)) continue; P3 n; float dist; sc.plane(i, n, dist); offer(a, plane_d2(p, n, dist), KIND_PLANE, i, -1, 0.0f, 0.0f); }
     if (sc.tlas_nodes() <= 0) return;
     int sp = 0, floor_sp = 0, cur = -1, first = 0, count = 0, tl_i = 0, tl_end = 0, inst = 0;
     bool in_blas = false;
@@ -193,6 +211,7 @@ RTX_HDF void walk(Scene & sc, Stack & st, const float * row, Answer & a) {
         if (cur < 0) {
             if (in_blas && sp == floor_sp) in_blas = false;               // this instance is done
             if (!in_blas && tl_i < tl_end) {                              // the next instance of the TLAS leaf
+                if (!sc.instance_visible(tl_i)) { tl_i++; continue; }     // FILTER: hidden from this row
                 inst = sc.enter(tl_i++, p, pl);
                 P3 mn, mx; sc.blas_node(0, mn, mx, first, count);
                 in_blas = true; floor_sp = sp;

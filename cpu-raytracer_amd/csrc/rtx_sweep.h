@@ -13,9 +13,11 @@
 #include "rtx_hits.h"
 #include "rtx_sweep_math.h"
 
+// FILTERED: the masks of rtx_query_sweep_filtered (rtx_nearest.h); the stack and the tile counter are the same
+template <bool FILTERED>
 __global__ __launch_bounds__(RTX_QUERY_BLOCK)
 void k_query_sweep(const DevScene sc, const float * __restrict__ rows8, const int m, const DevQuery out, const uint64_t * __restrict__ order,
-                   int32_t * const spill_base, const int spill_threads, uint32_t * const head) {
+                   int32_t * const spill_base, const int spill_threads, uint32_t * const head, const QueryMasks<FILTERED> masks) {
     __shared__ float lds_rows[8 * RTX_QUERY_BLOCK];
     __shared__ int lds_stack[RTX_QUERY_BLOCK / RTX_WAVE][RTX_LDS_STACK][RTX_WAVE];
     __shared__ float lds_key[RTX_QUERY_BLOCK / RTX_WAVE][RTX_LDS_STACK][RTX_WAVE];
@@ -37,9 +39,15 @@ void k_query_sweep(const DevScene sc, const float * __restrict__ rows8, const in
         if (order) query_gather_row<8>(order, rows8, m, i, r);
         else query_load_row<8>(lds_rows, rows8, m, r, tile);
         if (i >= m) continue;
-        HitsScene S = { { sc, RTX_GPTR(sc.tlas_nodes), nullptr, nullptr } };
         rtxsp::Answer a;
-        rtxsp::walk(S, st, r, a);
+        if constexpr (FILTERED) {
+            const size_t pr = order ? (size_t)rtxq::key_row(order[i]) : (size_t)i;
+            Masked<HitsScene> S = { { { sc, RTX_GPTR(sc.tlas_nodes), nullptr, nullptr } }, masks.table, pr < (size_t)m ? query_row_mask(masks, pr) : 0u };
+            rtxsp::walk(S, st, r, a);
+        } else {
+            HitsScene S = { { sc, RTX_GPTR(sc.tlas_nodes), nullptr, nullptr } };
+            rtxsp::walk(S, st, r, a);
+        }
 
         const size_t p = order ? (size_t)rtxq::key_row(order[i]) : (size_t)i;      // the caller's row of this slot
         if (p >= (size_t)m) continue;                                              // never: a sorted key holds a row of the round

@@ -78,6 +78,9 @@
 //   7. A TLAS leaf takes its instances in tlas_indices order, stepped through in two registers, not on the stack; a BLAS leaf its slots in order.
 //   STACK: a push happens only at an inner node and leaves one sibling per level of the current path: at most rtxnp::stack_need() entries.
 //   The caller checks it; there is no overflow path.
+//   FILTER (rtx_query_sweep_filtered): the rule and the places of rtx_nearest_math.h's FILTER — a row whose mask is 0 gets the no-answer
+//   record without a walk, a hidden sphere or plane is passed over in step 2, a hidden instance in step 7 before its matrix or its BLAS is
+//   touched.  Hidden objects neither stop the ball nor overlap it; ACCURACY holds against the exhaustive search over the visible primitives.
 //
 // ACCURACY (sweep_bound() below), stated in DISTANCE: t itself is ill-conditioned for a grazing contact (it moves by sqrt of the error),
 //   the distance from c(t) is not.  u = 2^-24.  S = |co - p0| + |e1| + |e2| for a triangle, |o - c| + R for a sphere, |o| + |distance| for a
@@ -263,11 +266,13 @@ RTX_HDF bool node_pass(const Answer & a, P3 mn, P3 mx, P3 o, P3 inv, float r, fl
 template <typename Scene>
 RTX_HDF void world_primitives(Scene & sc, Answer & a, const P3 o, const P3 d, const float D, const float r) {
     for (int i = 0; i < sc.sphere_count(); i++) {
+        if (!sc.sphere_visible(i)) continue;
         P3 c; float r2, t, d20;
         sc.sphere(i, c, r2);
         if (sphere_sweep(c, r2, o, d, r, t, d20)) offer(a, D, t, d20, KIND_SPHERE, i, -1, 0.0f, 0.0f);
     }
     for (int i = 0; i < sc.plane_count(); i++) {
+        if (!sc.plane_visible(i)) continue;
         P3 n; float dist, t, d20;
         sc.plane(i, n, dist);
         if (plane_sweep(n, dist, o, d, r, t, d20)) offer(a, D, t, d20, KIND_PLANE, i, -1, 0.0f, 0.0f);
@@ -275,11 +280,11 @@ RTX_HDF void world_primitives(Scene & sc, Answer & a, const P3 o, const P3 d, co
 }
 
 // The walk.  Scene gives the records as for rtxhp::walk (enter(slot, o, d, co, cd) makes the BLAS of instance tlas_indices[slot] current,
-// gives the local ray, returns that instance).  Stack gives push(sp, node, key) and pop(sp, node, key).
+// gives the local ray, returns that instance; FILTER's predicates).  Stack gives push(sp, node, key) and pop(sp, node, key).
 template <typename Scene, typename Stack>
 RTX_HDF void walk(Scene & sc, Stack & st, const float * row, Answer & a) {
     clear(a);
-    if (!row_is_live(row)) return;
+    if (!row_is_live(row) || !sc.row_visible()) return;
     const P3 o = mk(row[0], row[1], row[2]), d = mk(row[3], row[4], row[5]);
     const float D = row[6], r = row[7];
     a.t = D;
@@ -295,6 +300,7 @@ RTX_HDF void walk(Scene & sc, Stack & st, const float * row, Answer & a) {
         if (cur < 0) {
             if (in_blas && sp == floor_sp) { in_blas = false; co = o; cd = d; cinv = winv; }      // this instance is done: back to world space
             if (!in_blas && tl_i < tl_end) {                                                      // the next instance of the TLAS leaf
+                if (!sc.instance_visible(tl_i)) { tl_i++; continue; }                             // FILTER: hidden from this row
                 inst = sc.enter(tl_i++, o, d, co, cd);
                 cinv = rtxhp::rcp(cd);
                 P3 mn, mx; sc.blas_node(0, mn, mx, first, count);

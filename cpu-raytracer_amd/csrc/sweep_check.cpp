@@ -124,6 +124,7 @@ static void make_tlas(Scene & s, int shape, int leaf_max) {
 
 struct Access {
     const Scene & s; const Mesh * M = nullptr;
+    RTX_WALK_UNFILTERED
     int sphere_count() const { return (int)s.spheres.size(); }
     int plane_count() const { return (int)s.planes.size(); }
     int tlas_nodes() const { return (int)s.tlas.size(); }

@@ -602,6 +602,7 @@ namespace {
 struct HostNearestScene {
     const rtxh_nearest_scene & s;
     const rtxh_nearest_blas * B = nullptr;
+    RTX_WALK_UNFILTERED
     int sphere_count() const { return s.sphere_count; }
     int plane_count() const { return s.plane_count; }
     int tlas_nodes() const { return s.tlas_node_count; }
@@ -621,6 +622,20 @@ struct HostNearestScene {
     void triangle(int i, rtxnp::P3 & p0, rtxnp::P3 & e1, rtxnp::P3 & e2) const {
         p0 = rtxnp::ptr3(B->hot[i].position_0); e1 = rtxnp::ptr3(B->hot[i].position_edge_1); e2 = rtxnp::ptr3(B->hot[i].position_edge_2);
     }
+};
+// FILTER of rtx_nearest_math.h over plain arrays: table = M object masks (null: all ones), row_mask = the row's
+struct HostMasks {
+    const uint32_t * table; const uint32_t * rows; uint32_t row;
+    uint32_t of_row(int64_t i) const { return rows ? rows[i] : row; }
+};
+template <typename Base> struct HostMasked : Base {
+    const uint32_t * table; uint32_t row_mask;
+    HostMasked(const rtxh_nearest_scene & sc, const uint32_t * table_, uint32_t row_mask_) : Base{ sc }, table(table_), row_mask(row_mask_) {}
+    bool row_visible() const { return row_mask != 0u; }
+    bool object_visible(int object) const { return !table || rtxnp::mask_visible(table[object], row_mask); }
+    bool sphere_visible(int i) const { return object_visible(this->s.instance_count + i); }
+    bool plane_visible(int i) const { return object_visible(this->s.instance_count + this->s.sphere_count + i); }
+    bool instance_visible(int slot) const { return object_visible(this->s.tlas_indices[slot]); }
 };
 struct HostNearestStack {
     int node[RTX_MAX_STACK]; float d2[RTX_MAX_STACK]; int high = 0;
@@ -691,14 +706,14 @@ void nearest_store(const rtxh_nearest_scene & s, const float * row, const rtxnp:
 }
 }  // namespace
 
-extern "C" int rtxh_query_nearest(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out, int32_t * stack_max_out) {
+static int query_nearest_host(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out, int32_t * stack_max_out, const HostMasks * km) {
     if (int rc = nearest_scene_check(scene, points, n, channels, out, true)) return rc;
     int high = 0;
     for (int64_t i = 0; i < n; i++) {
-        HostNearestScene S{ *scene };
         HostNearestStack st;
         rtxnp::Answer a;
-        rtxnp::walk(S, st, points + 4 * i, a);
+        if (km) { HostMasked<HostNearestScene> S(*scene, km->table, km->of_row(i)); rtxnp::walk(S, st, points + 4 * i, a); }
+        else { HostNearestScene S{ *scene }; rtxnp::walk(S, st, points + 4 * i, a); }
         if (st.high > high) high = st.high;
         nearest_store(*scene, points + 4 * i, a, i, channels, *out);
     }
@@ -706,18 +721,29 @@ extern "C" int rtxh_query_nearest(const rtxh_nearest_scene * scene, const float 
     return RTX_OK;
 }
 
-extern "C" int rtxh_query_nearest_exhaustive(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out) {
+extern "C" int rtxh_query_nearest(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out, int32_t * stack_max_out) {
+    return query_nearest_host(scene, points, n, channels, out, stack_max_out, nullptr);
+}
+extern "C" int rtxh_query_nearest_filtered(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out, int32_t * stack_max_out,
+                                           const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask) {
+    const HostMasks km = { object_masks, row_masks, row_mask };
+    return query_nearest_host(scene, points, n, channels, out, stack_max_out, &km);
+}
+
+static int query_nearest_exhaustive_host(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out, const HostMasks km) {
     if (int rc = nearest_scene_check(scene, points, n, channels, out, false)) return rc;
     const rtxh_nearest_scene & s = *scene;
     for (int64_t i = 0; i < n; i++) {
         const float * row = points + 4 * i;
+        const HostMasked<HostNearestScene> vis(s, km.table, km.of_row(i));
         rtxnp::Answer a; a.kind = rtxnp::KIND_NONE; a.object = -1; a.slot = -1; a.u = 0.0f; a.v = 0.0f; a.d2 = INFINITY;
-        if (rtxnp::row_is_live(row)) {
+        if (rtxnp::row_is_live(row) && vis.row_visible()) {
             const rtxnp::P3 p = rtxnp::mk(row[0], row[1], row[2]);
             a.d2 = row[3] * row[3];
-            for (int k = 0; k < s.sphere_count; k++) rtxnp::offer(a, rtxnp::sphere_d2(p, rtxnp::ptr3(s.spheres[k].center), s.spheres[k].radius_squared), rtxnp::KIND_SPHERE, k, -1, 0.0f, 0.0f);
-            for (int k = 0; k < s.plane_count; k++) rtxnp::offer(a, rtxnp::plane_d2(p, rtxnp::ptr3(s.planes[k].normal), s.planes[k].distance), rtxnp::KIND_PLANE, k, -1, 0.0f, 0.0f);
+            for (int k = 0; k < s.sphere_count; k++) if (vis.sphere_visible(k)) rtxnp::offer(a, rtxnp::sphere_d2(p, rtxnp::ptr3(s.spheres[k].center), s.spheres[k].radius_squared), rtxnp::KIND_SPHERE, k, -1, 0.0f, 0.0f);
+            for (int k = 0; k < s.plane_count; k++) if (vis.plane_visible(k)) rtxnp::offer(a, rtxnp::plane_d2(p, rtxnp::ptr3(s.planes[k].normal), s.planes[k].distance), rtxnp::KIND_PLANE, k, -1, 0.0f, 0.0f);
             for (int k = 0; k < s.instance_count; k++) {
+                if (!vis.object_visible(k)) continue;
                 const rtxnp::P3 pl = rtxnp::xform_pos(s.instances[k].world_inv, p);
                 const rtxh_nearest_blas & B = s.blas[s.instances[k].blas_id];
                 for (int t = 0; t < B.triangle_count; t++) {
@@ -730,6 +756,15 @@ extern "C" int rtxh_query_nearest_exhaustive(const rtxh_nearest_scene * scene, c
         nearest_store(s, row, a, i, channels, *out);
     }
     return RTX_OK;
+}
+static const HostMasks kNoMasks = { nullptr, nullptr, 0xffffffffu };      // every object, every row: the unfiltered exhaustive searches
+extern "C" int rtxh_query_nearest_exhaustive(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out) {
+    return query_nearest_exhaustive_host(scene, points, n, channels, out, kNoMasks);
+}
+extern "C" int rtxh_query_nearest_exhaustive_filtered(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out,
+                                                      const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask) {
+    const HostMasks km = { object_masks, row_masks, row_mask };
+    return query_nearest_exhaustive_host(scene, points, n, channels, out, km);
 }
 
 extern "C" float rtxh_nearest_distance_bound(float local_scale, float world_scale) { return rtxnp::distance_bound(local_scale, world_scale); }
@@ -807,16 +842,16 @@ void hit_write(const rtxh_nearest_scene & s, const float * row, const HostHitsLi
 }
 }  // namespace
 
-extern "C" int rtxh_query_hits(const rtxh_nearest_scene * scene, const float * segments, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
-                               int32_t * count_out, int32_t * stack_max_out) {
+static int query_hits_host(const rtxh_nearest_scene * scene, const float * segments, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
+                           int32_t * count_out, int32_t * stack_max_out, const HostMasks * km) {
     if (int rc = hits_args_check(scene, segments, n, max_hits, channels, out, count_out, true)) return rc;
     int high = 0;
     for (int64_t i = 0; i < n; i++) {
-        HostHitsScene S(*scene);
         HostNearestStack st;
         HostHitsList L;
         rtxhp::Tally w;
-        rtxhp::walk(S, st, L, segments + 7 * i, max_hits, count_out != nullptr, w);
+        if (km) { HostMasked<HostHitsScene> S(*scene, km->table, km->of_row(i)); rtxhp::walk(S, st, L, segments + 7 * i, max_hits, count_out != nullptr, w); }
+        else { HostHitsScene S(*scene); rtxhp::walk(S, st, L, segments + 7 * i, max_hits, count_out != nullptr, w); }
         if (st.high > high) high = st.high;
         if (count_out) count_out[i] = w.count;
         if (max_hits) hit_write(*scene, segments + 7 * i, L, w.held, max_hits, i, channels, *out);
@@ -825,21 +860,32 @@ extern "C" int rtxh_query_hits(const rtxh_nearest_scene * scene, const float * s
     return RTX_OK;
 }
 
-extern "C" int rtxh_query_hits_exhaustive(const rtxh_nearest_scene * scene, const float * segments, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
-                                          int32_t * count_out) {
+extern "C" int rtxh_query_hits(const rtxh_nearest_scene * scene, const float * segments, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
+                               int32_t * count_out, int32_t * stack_max_out) {
+    return query_hits_host(scene, segments, n, max_hits, channels, out, count_out, stack_max_out, nullptr);
+}
+extern "C" int rtxh_query_hits_filtered(const rtxh_nearest_scene * scene, const float * segments, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
+                                        int32_t * count_out, int32_t * stack_max_out, const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask) {
+    const HostMasks km = { object_masks, row_masks, row_mask };
+    return query_hits_host(scene, segments, n, max_hits, channels, out, count_out, stack_max_out, &km);
+}
+
+static int query_hits_exhaustive_host(const rtxh_nearest_scene * scene, const float * segments, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
+                                      int32_t * count_out, const HostMasks km) {
     if (int rc = hits_args_check(scene, segments, n, max_hits, channels, out, count_out, false)) return rc;
     const rtxh_nearest_scene & s = *scene;
     for (int64_t i = 0; i < n; i++) {
         const float * row = segments + 7 * i;
-        HostHitsScene S(s);
+        HostMasked<HostHitsScene> S(s, km.table, km.of_row(i));
         HostHitsList L;
         rtxhp::Tally w; w.count = 0; w.held = 0; w.bound = 0.0f;
-        if (rtxhp::row_is_live(row)) {
+        if (rtxhp::row_is_live(row) && S.row_visible()) {
             const rtxnp::P3 o = rtxnp::mk(row[0], row[1], row[2]), d = rtxnp::mk(row[3], row[4], row[5]);
             const float D = row[6];
             w.bound = D;
             rtxhp::world_primitives(S, L, max_hits, false, w, o, d, D);
             for (int k = 0; k < s.instance_count; k++) {
+                if (!S.object_visible(k)) continue;
                 const rtxnp::P3 co = rtxnp::xform_pos(s.instances[k].world_inv, o), cd = rtxnp::xform_dir(s.instances[k].world_inv, d);
                 const rtxh_nearest_blas & B = s.blas[s.instances[k].blas_id];
                 for (int t = 0; t < B.triangle_count; t++) {
@@ -853,6 +899,15 @@ extern "C" int rtxh_query_hits_exhaustive(const rtxh_nearest_scene * scene, cons
         if (max_hits) hit_write(s, row, L, w.held, max_hits, i, channels, *out);
     }
     return RTX_OK;
+}
+extern "C" int rtxh_query_hits_exhaustive(const rtxh_nearest_scene * scene, const float * segments, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
+                                          int32_t * count_out) {
+    return query_hits_exhaustive_host(scene, segments, n, max_hits, channels, out, count_out, kNoMasks);
+}
+extern "C" int rtxh_query_hits_exhaustive_filtered(const rtxh_nearest_scene * scene, const float * segments, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
+                                                   int32_t * count_out, const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask) {
+    const HostMasks km = { object_masks, row_masks, row_mask };
+    return query_hits_exhaustive_host(scene, segments, n, max_hits, channels, out, count_out, km);
 }
 
 extern "C" float rtxh_hits_margin(float kappa, float scale) { return rtxhp::margin(kappa, scale); }
@@ -872,14 +927,14 @@ void sweep_store(const rtxh_nearest_scene & s, const float * row, const rtxsp::A
 }
 }  // namespace
 
-extern "C" int rtxh_query_sweep(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, uint32_t channels, const rtx_query_buffers * out, int32_t * stack_max_out) {
+static int query_sweep_host(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, uint32_t channels, const rtx_query_buffers * out, int32_t * stack_max_out, const HostMasks * km) {
     if (int rc = nearest_scene_check(scene, sweeps, n, channels, out, true)) return rc;
     int high = 0;
     for (int64_t i = 0; i < n; i++) {
-        HostHitsScene S(*scene);
         HostNearestStack st;
         rtxsp::Answer a;
-        rtxsp::walk(S, st, sweeps + 8 * i, a);
+        if (km) { HostMasked<HostHitsScene> S(*scene, km->table, km->of_row(i)); rtxsp::walk(S, st, sweeps + 8 * i, a); }
+        else { HostHitsScene S(*scene); rtxsp::walk(S, st, sweeps + 8 * i, a); }
         if (st.high > high) high = st.high;
         sweep_store(*scene, sweeps + 8 * i, a, i, channels, *out);
     }
@@ -887,19 +942,29 @@ extern "C" int rtxh_query_sweep(const rtxh_nearest_scene * scene, const float * 
     return RTX_OK;
 }
 
-extern "C" int rtxh_query_sweep_exhaustive(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, uint32_t channels, const rtx_query_buffers * out) {
+extern "C" int rtxh_query_sweep(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, uint32_t channels, const rtx_query_buffers * out, int32_t * stack_max_out) {
+    return query_sweep_host(scene, sweeps, n, channels, out, stack_max_out, nullptr);
+}
+extern "C" int rtxh_query_sweep_filtered(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, uint32_t channels, const rtx_query_buffers * out, int32_t * stack_max_out,
+                                         const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask) {
+    const HostMasks km = { object_masks, row_masks, row_mask };
+    return query_sweep_host(scene, sweeps, n, channels, out, stack_max_out, &km);
+}
+
+static int query_sweep_exhaustive_host(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, uint32_t channels, const rtx_query_buffers * out, const HostMasks km) {
     if (int rc = nearest_scene_check(scene, sweeps, n, channels, out, false)) return rc;
     const rtxh_nearest_scene & s = *scene;
     for (int64_t i = 0; i < n; i++) {
         const float * row = sweeps + 8 * i;
-        HostHitsScene S(s);
+        HostMasked<HostHitsScene> S(s, km.table, km.of_row(i));
         rtxsp::Answer a; rtxsp::clear(a);
-        if (rtxsp::row_is_live(row)) {
+        if (rtxsp::row_is_live(row) && S.row_visible()) {
             const rtxnp::P3 o = rtxnp::mk(row[0], row[1], row[2]), d = rtxnp::mk(row[3], row[4], row[5]);
             const float D = row[6], r = row[7];
             a.t = D;
             rtxsp::world_primitives(S, a, o, d, D, r);
             for (int k = 0; k < s.instance_count; k++) {
+                if (!S.object_visible(k)) continue;
                 const rtxnp::P3 co = rtxnp::xform_pos(s.instances[k].world_inv, o), cd = rtxnp::xform_dir(s.instances[k].world_inv, d);
                 const rtxh_nearest_blas & B = s.blas[s.instances[k].blas_id];
                 for (int j = 0; j < B.triangle_count; j++) {
@@ -912,6 +977,14 @@ extern "C" int rtxh_query_sweep_exhaustive(const rtxh_nearest_scene * scene, con
         sweep_store(s, row, a, i, channels, *out);
     }
     return RTX_OK;
+}
+extern "C" int rtxh_query_sweep_exhaustive(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, uint32_t channels, const rtx_query_buffers * out) {
+    return query_sweep_exhaustive_host(scene, sweeps, n, channels, out, kNoMasks);
+}
+extern "C" int rtxh_query_sweep_exhaustive_filtered(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, uint32_t channels, const rtx_query_buffers * out,
+                                                    const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask) {
+    const HostMasks km = { object_masks, row_masks, row_mask };
+    return query_sweep_exhaustive_host(scene, sweeps, n, channels, out, km);
 }
 
 extern "C" float rtxh_sweep_bound(float local_scale, float world_scale, float travelled, float radius) { return rtxsp::sweep_bound(local_scale, world_scale, travelled, radius); }

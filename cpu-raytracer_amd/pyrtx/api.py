@@ -12,7 +12,7 @@ from typing import Dict, List, Optional
 import numpy as np
 
 from . import scene_io as sio
-from .ctypes_structs import RtxConfig, RtxFrame, RtxStats, RtxWork, RtxTextureDesc, RtxAovBuffers, RtxRay, AOV_CHANNELS, RTX_AOV_ALL, fill_frame
+from .ctypes_structs import RtxConfig, RtxFrame, RtxStats, RtxWork, RtxTextureDesc, RtxAovBuffers, RtxRay, RtxQueryFilter, AOV_CHANNELS, RTX_AOV_ALL, fill_frame
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "..", "csrc", "librtx_hip.so")
@@ -29,7 +29,8 @@ EXPORTS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error", "rt
            "rtx_query_closest", "rtx_query_occluded", "rtx_debug_query_order", "rtx_debug_read_layouts",
            "rtx_alloc_texture", "rtx_update_texture", "rtx_read_texture", "rtx_update_sky",
            "rtx_alloc_blas_topology", "rtx_set_blas_topology", "rtx_blas_vertex_normals", "rtx_query_nearest", "rtx_query_hits", "rtx_query_sweep",
-           "rtx_debug_grids"]
+           "rtx_debug_grids", "rtx_set_object_masks", "rtx_update_object_masks", "rtx_read_object_masks",
+           "rtx_query_nearest_filtered", "rtx_query_hits_filtered", "rtx_query_sweep_filtered"]
 # newer than the A/B variants tools/ab.py may load (RTX_HIP_LIB = a library built from an older commit): bound when the library has them,
 # otherwise a call raises AttributeError (undefined symbol)
 VIEW_EXPORTS = ("rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer")
@@ -47,8 +48,10 @@ NEAREST_EXPORTS = ("rtx_query_nearest",)
 HITS_EXPORTS = ("rtx_query_hits",)
 SWEEP_EXPORTS = ("rtx_query_sweep",)
 GRID_EXPORTS = ("rtx_debug_grids",)
+MASK_EXPORTS = ("rtx_set_object_masks", "rtx_update_object_masks", "rtx_read_object_masks",
+                "rtx_query_nearest_filtered", "rtx_query_hits_filtered", "rtx_query_sweep_filtered")
 OPTIONAL_EXPORTS = (VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + QUERY_SORT_EXPORTS + LAYOUT_EXPORTS
-                    + TEXTURE_EXPORTS + NORMALS_EXPORTS + NEAREST_EXPORTS + HITS_EXPORTS + SWEEP_EXPORTS + GRID_EXPORTS)
+                    + TEXTURE_EXPORTS + NORMALS_EXPORTS + NEAREST_EXPORTS + HITS_EXPORTS + SWEEP_EXPORTS + GRID_EXPORTS + MASK_EXPORTS)
 RTX_QUERY_MAX_HITS = 8
 # texel formats of rtx_update_texture (include/rtx.h RTX_TEXELS_*)
 RTX_TEXELS_RGB_F32 = 0
@@ -177,6 +180,13 @@ def load_library(path: Optional[str] = None):
         lib.rtx_query_sweep.argtypes = [vp, vp, C.c_int64, u32, C.POINTER(RtxQueryBuffers), u32]
     if hasattr(lib, "rtx_query_hits"):
         lib.rtx_query_hits.argtypes = [vp, vp, C.c_int64, i32, u32, C.POINTER(RtxQueryBuffers), vp, u32]
+    if hasattr(lib, "rtx_set_object_masks"):
+        lib.rtx_set_object_masks.argtypes = [vp, vp, i32]
+        lib.rtx_update_object_masks.argtypes = [vp, vp, i32]
+        lib.rtx_read_object_masks.argtypes = [vp, vp, i32, C.POINTER(i32)]
+        lib.rtx_query_nearest_filtered.argtypes = [vp, vp, C.c_int64, u32, C.POINTER(RtxQueryBuffers), u32, C.POINTER(RtxQueryFilter)]
+        lib.rtx_query_sweep_filtered.argtypes = [vp, vp, C.c_int64, u32, C.POINTER(RtxQueryBuffers), u32, C.POINTER(RtxQueryFilter)]
+        lib.rtx_query_hits_filtered.argtypes = [vp, vp, C.c_int64, i32, u32, C.POINTER(RtxQueryBuffers), vp, u32, C.POINTER(RtxQueryFilter)]
     if hasattr(lib, "rtx_debug_query_order"):
         lib.rtx_debug_query_order.argtypes = [vp, vp, i32, C.c_int64, vp]
     if hasattr(lib, "rtx_debug_read_layouts"):
@@ -1161,17 +1171,85 @@ class Renderer:
             launch()
         return out
 
-    def query_nearest(self, points, channels=("distance",), out: Optional[Dict] = None, n: Optional[int] = None, sort: bool = False) -> Dict:
+    # ---- object masks: the filtered walk queries (include/rtx.h: rtx_set_object_masks ... rtx_query_*_filtered) ---------------------
+    def set_object_masks(self, masks):
+        """The object masks the filtered queries (mask=...) test: one 32-bit mask per object of the current frame, instances first, then
+        spheres, then planes (the numbering of the object_id channel).  A numpy array goes through rtx_set_object_masks (a staged copy on
+        the context's stream); a torch tensor on this context's GPU through rtx_update_object_masks (device to device, queued on torch's
+        current stream, nothing read back).  int32 and uint32 are both accepted and the bits taken as they are (torch has no general
+        uint32).  None drops the table: every object's mask is all ones again.  An object exists for a row iff object mask & row mask != 0."""
+        if masks is None:
+            self._chk(self.lib.rtx_set_object_masks(self.ctx, None, 0), "rtx_set_object_masks")
+            return
+        if hasattr(masks, "data_ptr"):
+            import torch
+            if not isinstance(masks, torch.Tensor):
+                raise TypeError(f"masks must be a numpy array, a torch.Tensor or None, not {type(masks).__name__}")
+            if masks.dtype not in (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ()):
+                raise TypeError(f"masks must be torch.int32 (or uint32), not {masks.dtype}")
+            if masks.dim() != 1:
+                raise ValueError(f"masks must have shape (M,), not {tuple(masks.shape)}")
+            if not masks.is_contiguous():
+                raise ValueError("masks must be contiguous")
+            self._query_on_device({"masks": masks})
+            count = int(masks.shape[0])
+            self._on_torch_stream(lambda: self._chk(self.lib.rtx_update_object_masks(self.ctx, masks.data_ptr() if count else None, count), "rtx_update_object_masks"), [masks])
+            return
+        a = np.asarray(masks)
+        if a.dtype not in (np.dtype(np.int32), np.dtype(np.uint32)):
+            raise TypeError(f"masks must be int32 or uint32, not {a.dtype}")
+        if a.ndim != 1:
+            raise ValueError(f"masks must have shape (M,), not {a.shape}")
+        a = np.ascontiguousarray(a)
+        keep = a if len(a) else np.zeros(1, np.uint32)      # M = 0 with an array: an empty table, not a dropped one
+        self._chk(self.lib.rtx_set_object_masks(self.ctx, keep.ctypes.data, len(a)), "rtx_set_object_masks")
+
+    def read_object_masks(self) -> Optional[np.ndarray]:
+        """The object masks the kernels see (rtx_read_object_masks; waits for the stream): uint32 (M,), or None when there is no table."""
+        cnt = C.c_int32()
+        self._chk(self.lib.rtx_read_object_masks(self.ctx, None, 0, C.byref(cnt)), "rtx_read_object_masks")
+        if cnt.value == 0:
+            return None
+        out = np.zeros(cnt.value, np.uint32)
+        self._chk(self.lib.rtx_read_object_masks(self.ctx, out.ctypes.data, cnt.value, C.byref(cnt)), "rtx_read_object_masks")
+        return out[:cnt.value]
+
+    def _query_filter(self, mask, n: int):
+        """(RtxQueryFilter or None, the row-mask tensor or None) of a query's mask keyword: None = the unfiltered call; an int = that mask for
+        every row; an int32 torch tensor (n,) on this context's GPU = the row masks; with raw device pointers an ("address", ptr) is not
+        offered: pass a tensor."""
+        if mask is None:
+            return None, None
+        if isinstance(mask, (int, np.integer)) and not isinstance(mask, bool):
+            if not -(1 << 31) <= int(mask) <= 0xFFFFFFFF:
+                raise ValueError(f"mask {mask} does not fit 32 bits")
+            return RtxQueryFilter(None, int(mask) & 0xFFFFFFFF), None
+        import torch
+        if not isinstance(mask, torch.Tensor):
+            raise TypeError(f"mask must be None, an int or a torch.Tensor of row masks, not {type(mask).__name__}")
+        if mask.dtype not in (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ()):
+            raise TypeError(f"mask must be torch.int32 (or uint32), not {mask.dtype}")
+        if tuple(mask.shape) != (n,):
+            raise ValueError(f"mask must have shape ({n},), not {tuple(mask.shape)}")
+        if not mask.is_contiguous():
+            raise ValueError("mask must be contiguous")
+        self._query_on_device({"mask": mask})
+        return RtxQueryFilter(mask.data_ptr(), 0), mask
+
+    def query_nearest(self, points, channels=("distance",), out: Optional[Dict] = None, n: Optional[int] = None, sort: bool = False, mask=None) -> Dict:
         """The nearest surface point of n points against the frame the context holds (rtx_query_nearest): points = float32 torch tensor
         (n, 4) of (x, y, z, maximum distance) on this context's GPU; channels as for query_closest.  Returns {name: tensor}: distance to the
         nearest surface point, that point, and what a hit there would report as normal, uv and ids.  No answer (nothing strictly nearer
         than the maximum distance, a non-finite coordinate, a maximum distance that is NaN or not above 0): distance inf, ids -1, the rest 0;
         +inf is a legal maximum distance.  Distances are measured in each instance's local space.  Queued on torch's current stream, checked
         and shaped like query_closest; sort=True (RTX_QUERY_SORT) walks the points of every round in Morton order, same answers row for row.
-        Raw device pointers: points = address, n, out = {name: address} for every channel wanted."""
-        return self._query_rows_to_channels("rtx_query_nearest", "points", points, 4, channels, out, n, sort)
+        Raw device pointers: points = address, n, out = {name: address} for every channel wanted.
+        mask (here, on query_hits and on query_sweep): None = this call; an int = the row mask of every row; an int32 tensor (n,) on this
+        context's GPU = one mask per row.  A row sees the objects whose mask (set_object_masks; all ones without a table) shares a bit with
+        its own; a row whose mask is 0 gets the no-answer values (rtx_query_*_filtered)."""
+        return self._query_rows_to_channels("rtx_query_nearest", "points", points, 4, channels, out, n, sort, mask)
 
-    def _query_rows_to_channels(self, fn, label, rows, width, channels, out, n, sort) -> Dict:
+    def _query_rows_to_channels(self, fn, label, rows, width, channels, out, n, sort, mask=None) -> Dict:
         """query_nearest and query_sweep: rows of `width` floats in, one element of every requested channel per row out."""
         names = query_names(channels)
         ptr, n, pts_t = self._query_rows(label, rows, width, n)
@@ -1186,6 +1264,7 @@ class Renderer:
         if raw and len(out) != len(names):
             raise ValueError("with raw device pointers out must hold an address for every requested channel")
         fl = RTX_QUERY_SORT if sort else 0
+        filt, mask_t = self._query_filter(mask, n)
         buf = RtxQueryBuffers()
         for name in out:
             _, dt, k = QUERY_CHANNELS[name]
@@ -1197,18 +1276,21 @@ class Renderer:
                 _, dt, k = QUERY_CHANNELS[name]
                 out[name] = torch.empty((n, k) if k > 1 else (n,), dtype=torch.float32 if dt == np.float32 else torch.int32, device=pts_t.device)
                 setattr(buf, name, out[name].data_ptr())
-        mask = sum(QUERY_CHANNELS[name][0] for name in names)
+        bits = sum(QUERY_CHANNELS[name][0] for name in names)
 
         def launch():
-            self._chk(getattr(self.lib, fn)(self.ctx, ptr, n, mask, C.byref(buf), fl), fn)
-        tensors = [t for t in [pts_t] + list(out.values()) if hasattr(t, "record_stream")]
+            if filt is None:
+                self._chk(getattr(self.lib, fn)(self.ctx, ptr, n, bits, C.byref(buf), fl), fn)
+            else:
+                self._chk(getattr(self.lib, fn + "_filtered")(self.ctx, ptr, n, bits, C.byref(buf), fl, C.byref(filt)), fn + "_filtered")
+        tensors = [t for t in [pts_t, mask_t] + list(out.values()) if hasattr(t, "record_stream")]
         if tensors:
             self._on_torch_stream(launch, tensors)
         else:
             launch()
         return {name: out[name] for name in names}
 
-    def query_sweep(self, sweeps, channels=("distance",), out: Optional[Dict] = None, n: Optional[int] = None, sort: bool = False) -> Dict:
+    def query_sweep(self, sweeps, channels=("distance",), out: Optional[Dict] = None, n: Optional[int] = None, sort: bool = False, mask=None) -> Dict:
         """The first contact of n moving balls with the frame the context holds (rtx_query_sweep): sweeps = float32 torch tensor (n, 8) of
         (origin, direction, max distance D, radius r) on this context's GPU; channels as for query_closest.  The centre moves along
         origin + t * direction; "distance" is the smallest t in [0, D) at which the ball touches the surface query_nearest measures (0 when
@@ -1217,11 +1299,12 @@ class Renderer:
         direction, a non-finite component, D or r NaN or not above 0, r infinite): distance inf, ids -1, the rest 0; +inf is a legal D.
         r and distances are measured in each instance's local space.  Queued on torch's current stream, checked and shaped like
         query_nearest; sort=True (RTX_QUERY_SORT) walks the rows of every round in the ray queries' order, same answers row for row.
-        Raw device pointers: sweeps = address, n, out = {name: address} for every channel wanted."""
-        return self._query_rows_to_channels("rtx_query_sweep", "sweeps", sweeps, 8, channels, out, n, sort)
+        Raw device pointers: sweeps = address, n, out = {name: address} for every channel wanted.  mask: as for query_nearest — hidden
+        objects neither stop the ball nor overlap it."""
+        return self._query_rows_to_channels("rtx_query_sweep", "sweeps", sweeps, 8, channels, out, n, sort, mask)
 
     def query_hits(self, segments, max_hits: int = 4, channels=("distance",), count: bool = True, out: Optional[Dict] = None, n: Optional[int] = None,
-                   sort: bool = False) -> Dict:
+                   sort: bool = False, mask=None) -> Dict:
         """Every hit along n segments against the frame the context holds (rtx_query_hits): segments = float32 torch tensor (n, 7) of (origin,
         direction, max distance) on this context's GPU, the rows of query_occluded.  Returns {name: tensor} of the nearest max_hits hits of
         every row in ascending order — (n, K), (n, K, 3) or (n, K, 2), K = max_hits in [1, 8], channels as for query_closest — plus "count",
@@ -1229,7 +1312,9 @@ class Renderer:
         rest 0.  A sphere counts at both crossings; a dead row (zero direction, a non-finite component, a max distance that is NaN or not above
         0) has count 0.  max_hits=0 with channels=() returns the count only.  out = {name: tensor} supplies the tensors ("count" included).
         Queued on torch's current stream, checked like query_nearest; sort=True (RTX_QUERY_SORT): same answers row for row.  Raw device
-        pointers: segments = address, n, out = {name: address} for every channel wanted and for "count" if count."""
+        pointers: segments = address, n, out = {name: address} for every channel wanted and for "count" if count.  mask: as for
+        query_nearest — hidden objects are neither listed nor counted; max_hits=1 is the filtered closest hit, the count-only form the
+        filtered occlusion test."""
         if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)):
             raise TypeError(f"max_hits must be an int, not {type(max_hits).__name__}")
         K = int(max_hits)
@@ -1259,6 +1344,7 @@ class Renderer:
         if raw and len(out) != len(wanted):
             raise ValueError("with raw device pointers out must hold an address for every requested channel and for the count")
         fl = RTX_QUERY_SORT if sort else 0
+        filt, mask_t = self._query_filter(mask, n)
         buf = RtxQueryBuffers()
         cptr = None
         for name in out:
@@ -1278,11 +1364,14 @@ class Renderer:
                     _, dt, k = QUERY_CHANNELS[name]
                     out[name] = torch.empty(self._query_shape(n, k, K), dtype=torch.float32 if dt == np.float32 else torch.int32, device=seg_t.device)
                     setattr(buf, name, out[name].data_ptr())
-        mask = sum(QUERY_CHANNELS[name][0] for name in names)
+        bits = sum(QUERY_CHANNELS[name][0] for name in names)
 
         def launch():
-            self._chk(self.lib.rtx_query_hits(self.ctx, ptr, n, K, mask, C.byref(buf), cptr, fl), "rtx_query_hits")
-        tensors = [t for t in [seg_t] + list(out.values()) if hasattr(t, "record_stream")]
+            if filt is None:
+                self._chk(self.lib.rtx_query_hits(self.ctx, ptr, n, K, bits, C.byref(buf), cptr, fl), "rtx_query_hits")
+            else:
+                self._chk(self.lib.rtx_query_hits_filtered(self.ctx, ptr, n, K, bits, C.byref(buf), cptr, fl, C.byref(filt)), "rtx_query_hits_filtered")
+        tensors = [t for t in [seg_t, mask_t] + list(out.values()) if hasattr(t, "record_stream")]
         if tensors:
             self._on_torch_stream(launch, tensors)
         else:

@@ -89,7 +89,12 @@ class RtxAovBuffers(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in AOV_CHANNELS]
 
 
-assert C.sizeof(RtxAovBuffers) == 64
+class RtxQueryFilter(C.Structure):
+    """rtx_query_filter: the row masks of a filtered query — a device array of n uint32, or None and one mask for every row."""
+    _fields_ = [("row_masks_dev", C.c_void_p), ("row_mask", C.c_uint32)]
+
+
+assert C.sizeof(RtxAovBuffers) == 64 and C.sizeof(RtxQueryFilter) == 16
 assert C.sizeof(RtxConfig) == 64 and C.sizeof(RtxTextureDesc) == 80 and C.sizeof(RtxCamera) == 48
 assert C.sizeof(RtxWork) == 160
 assert C.sizeof(RtxRay) == 72

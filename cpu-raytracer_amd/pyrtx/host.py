@@ -25,7 +25,9 @@ EXPORTS = ["rtxh_camera_basis", "rtxh_camera_update", "rtxh_quaternion_axis_angl
            "rtxh_blas_build_balanced", "rtxh_blas_balanced_node_count", "rtxh_blas_balanced_inner_depth", "rtxh_vertex_normals",
            "rtxh_query_nearest", "rtxh_query_nearest_exhaustive", "rtxh_nearest_distance_bound", "rtxh_nearest_box_d2", "rtxh_nearest_triangle_d2",
            "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2", "rtxh_query_hits", "rtxh_query_hits_exhaustive", "rtxh_hits_margin",
-           "rtxh_query_sweep", "rtxh_query_sweep_exhaustive", "rtxh_sweep_bound", "rtxh_sweep_triangle", "rtxh_sweep_sphere", "rtxh_sweep_plane"]
+           "rtxh_query_sweep", "rtxh_query_sweep_exhaustive", "rtxh_sweep_bound", "rtxh_sweep_triangle", "rtxh_sweep_sphere", "rtxh_sweep_plane",
+           "rtxh_query_nearest_filtered", "rtxh_query_nearest_exhaustive_filtered", "rtxh_query_hits_filtered", "rtxh_query_hits_exhaustive_filtered",
+           "rtxh_query_sweep_filtered", "rtxh_query_sweep_exhaustive_filtered"]
 FLOAT_EXPORTS = ("rtxh_nearest_distance_bound", "rtxh_nearest_box_d2", "rtxh_nearest_triangle_d2", "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2", "rtxh_hits_margin", "rtxh_sweep_bound")      # return a float, not a status
 
 PI = np.float32(3.14159265359)          # Util.h:8
@@ -119,6 +121,13 @@ def lib():
         l.rtxh_hits_margin.argtypes = [C.c_float, C.c_float]
         l.rtxh_query_sweep.argtypes = [C.POINTER(RtxhNearestScene), vp, C.c_int64, C.c_uint32, vp, C.POINTER(i32)]
         l.rtxh_query_sweep_exhaustive.argtypes = [C.POINTER(RtxhNearestScene), vp, C.c_int64, C.c_uint32, vp]
+        masks3 = [vp, vp, C.c_uint32]                              # object_masks, row_masks, row_mask
+        l.rtxh_query_nearest_filtered.argtypes = l.rtxh_query_nearest.argtypes + masks3
+        l.rtxh_query_nearest_exhaustive_filtered.argtypes = l.rtxh_query_nearest_exhaustive.argtypes + masks3
+        l.rtxh_query_hits_filtered.argtypes = l.rtxh_query_hits.argtypes + masks3
+        l.rtxh_query_hits_exhaustive_filtered.argtypes = l.rtxh_query_hits_exhaustive.argtypes + masks3
+        l.rtxh_query_sweep_filtered.argtypes = l.rtxh_query_sweep.argtypes + masks3
+        l.rtxh_query_sweep_exhaustive_filtered.argtypes = l.rtxh_query_sweep_exhaustive.argtypes + masks3
         l.rtxh_sweep_bound.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float]
         l.rtxh_sweep_triangle.argtypes = [vp, vp, C.c_float, C.c_float, vp, vp, vp, vp]
         l.rtxh_sweep_sphere.argtypes = [vp, vp, C.c_float, vp, vp, vp]
@@ -533,7 +542,39 @@ def _nearest_names(channels):
     return tuple(n for n in NEAREST_CHANNELS if n in want)
 
 
-def _query_nearest(fn_name, scene, points, channels, blas, with_stack, width=4, label="points"):
+def _mask_bits(name, a, n):
+    """n masks as a contiguous uint32 array: int32 and uint32 are both accepted and the bits taken as they are."""
+    a = np.asarray(a)
+    if a.dtype not in (np.dtype(np.int32), np.dtype(np.uint32)):
+        raise TypeError(f"{name} must be int32 or uint32, not {a.dtype}")
+    if a.shape != (n,):
+        raise ValueError(f"{name} must have shape ({n},), not {a.shape}")
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _filter_args(s, n, mask, object_masks):
+    """None (the unfiltered call: mask and object_masks both None) or the three trailing arguments of a rtxh_*_filtered function and
+    what keeps them alive.  mask: an int (every row), or n row masks; None with object_masks = all ones."""
+    if mask is None and object_masks is None:
+        return None
+    keep = []
+    optr = rptr = None
+    scalar = 0xFFFFFFFF
+    if object_masks is not None:
+        om = _mask_bits("object_masks", object_masks, s.instance_count + s.sphere_count + s.plane_count)
+        keep.append(om); optr = om.ctypes.data if len(om) else None
+    if mask is not None:
+        if isinstance(mask, (int, np.integer)) and not isinstance(mask, bool):
+            if not -(1 << 31) <= int(mask) <= 0xFFFFFFFF:
+                raise ValueError(f"mask {mask} does not fit 32 bits")
+            scalar = int(mask) & 0xFFFFFFFF
+        else:
+            rm = _mask_bits("mask", mask, n)
+            keep.append(rm); rptr = rm.ctypes.data
+    return [optr, rptr, scalar], keep
+
+
+def _query_nearest(fn_name, scene, points, channels, blas, with_stack, width=4, label="points", mask=None, object_masks=None):
     pts = np.asarray(points)
     if pts.ndim != 2 or pts.shape[1] != width or pts.shape[0] < 1:
         raise ValueError(f"{label} must have shape (n, {width}) with n >= 1, not {pts.shape}")
@@ -547,12 +588,14 @@ def _query_nearest(fn_name, scene, points, channels, blas, with_stack, width=4, 
     buf = _NearestBuffers()
     for name in names:
         setattr(buf, name, out[name].ctypes.data)
-    mask = sum(NEAREST_CHANNELS[name][0] for name in names)
+    bits = sum(NEAREST_CHANNELS[name][0] for name in names)
     high = C.c_int32(0)
-    if with_stack:
-        rc = getattr(lib(), fn_name)(C.byref(s), pts.ctypes.data, n, mask, C.byref(buf), C.byref(high))
-    else:
-        rc = getattr(lib(), fn_name)(C.byref(s), pts.ctypes.data, n, mask, C.byref(buf))
+    filt = _filter_args(s, n, mask, object_masks)
+    args = [C.byref(s), pts.ctypes.data, n, bits, C.byref(buf)] + ([C.byref(high)] if with_stack else [])
+    if filt:
+        fn_name += "_filtered"
+        args += filt[0]
+    rc = getattr(lib(), fn_name)(*args)
     if rc:
         raise ValueError(f"{fn_name} failed with status {rc}")
     if with_stack:
@@ -560,20 +603,23 @@ def _query_nearest(fn_name, scene, points, channels, blas, with_stack, width=4, 
     return out
 
 
-def query_nearest(scene, points, channels=("distance",), blas=None) -> dict:
+def query_nearest(scene, points, channels=("distance",), blas=None, mask=None, object_masks=None) -> dict:
     """rtxh_query_nearest: what Renderer.query_nearest writes on the device for points float32 (n, 4) of (x, y, z, maximum distance), from the
     same code (csrc/rtx_nearest_math.h) -> {channel: array} plus "stack_max", the most stack entries a row held.  scene: a scene_io.Scene,
-    or the arrays of Renderer.read_frame_state() (+ spheres, planes) with blas = [Renderer.read_blas(b), ...]: see nearest_scene."""
-    return _query_nearest("rtxh_query_nearest", scene, points, channels, blas, True)
+    or the arrays of Renderer.read_frame_state() (+ spheres, planes) with blas = [Renderer.read_blas(b), ...]: see nearest_scene.
+    mask / object_masks (here and on the other five query functions below): the filtered form (rtxh_*_filtered) — object_masks = the M
+    masks of the objects, instances then spheres then planes (None: all ones), mask = an int for every row or n row masks (None with
+    object_masks: all ones); int32 or uint32, the bits as they are.  Both None: the unfiltered call."""
+    return _query_nearest("rtxh_query_nearest", scene, points, channels, blas, True, mask=mask, object_masks=object_masks)
 
 
-def query_nearest_exhaustive(scene, points, channels=("distance",), blas=None) -> dict:
+def query_nearest_exhaustive(scene, points, channels=("distance",), blas=None, mask=None, object_masks=None) -> dict:
     """rtxh_query_nearest_exhaustive: the same candidate functions over every primitive, no tree; ties to the lowest (kind, object, slot)."""
-    return _query_nearest("rtxh_query_nearest_exhaustive", scene, points, channels, blas, False)
+    return _query_nearest("rtxh_query_nearest_exhaustive", scene, points, channels, blas, False, mask=mask, object_masks=object_masks)
 
 
 # ---- all-hits segment queries on the host (include/rtx_host.h: rtxh_query_hits / rtxh_query_hits_exhaustive) ------------------------------
-def _query_hits(fn_name, scene, segments, max_hits, channels, count, blas, with_stack):
+def _query_hits(fn_name, scene, segments, max_hits, channels, count, blas, with_stack, mask=None, object_masks=None):
     seg = np.asarray(segments)
     if seg.ndim != 2 or seg.shape[1] != 7 or seg.shape[0] < 1:
         raise ValueError(f"segments must have shape (n, 7) with n >= 1, not {seg.shape}")
@@ -595,14 +641,16 @@ def _query_hits(fn_name, scene, segments, max_hits, channels, count, blas, with_
     buf = _NearestBuffers()
     for name in names:
         setattr(buf, name, out[name].ctypes.data)
-    mask = sum(NEAREST_CHANNELS[name][0] for name in names)
+    bits = sum(NEAREST_CHANNELS[name][0] for name in names)
     cnt = np.zeros(n, np.int32) if count else None
     cptr = cnt.ctypes.data if count else None
     high = C.c_int32(0)
-    if with_stack:
-        rc = lib().rtxh_query_hits(C.byref(s), seg.ctypes.data, n, K, mask, C.byref(buf), cptr, C.byref(high))
-    else:
-        rc = lib().rtxh_query_hits_exhaustive(C.byref(s), seg.ctypes.data, n, K, mask, C.byref(buf), cptr)
+    filt = _filter_args(s, n, mask, object_masks)
+    args = [C.byref(s), seg.ctypes.data, n, K, bits, C.byref(buf), cptr] + ([C.byref(high)] if with_stack else [])
+    if filt:
+        fn_name += "_filtered"
+        args += filt[0]
+    rc = getattr(lib(), fn_name)(*args)
     if rc:
         raise ValueError(f"{fn_name} failed with status {rc}")
     if count:
@@ -612,28 +660,28 @@ def _query_hits(fn_name, scene, segments, max_hits, channels, count, blas, with_
     return out
 
 
-def query_hits(scene, segments, max_hits=4, channels=("distance",), count=True, blas=None) -> dict:
+def query_hits(scene, segments, max_hits=4, channels=("distance",), count=True, blas=None, mask=None, object_masks=None) -> dict:
     """rtxh_query_hits: what Renderer.query_hits writes on the device for segments float32 (n, 7) of (origin, direction, max distance), from
     the same code (csrc/rtx_hits_math.h) -> {channel: (n, K[, k]) array} plus "count" (n,) int32 if count, plus "stack_max".  max_hits=0 with
     channels=() is the count-only form.  scene and blas as for query_nearest."""
-    return _query_hits("rtxh_query_hits", scene, segments, max_hits, channels, count, blas, True)
+    return _query_hits("rtxh_query_hits", scene, segments, max_hits, channels, count, blas, True, mask, object_masks)
 
 
-def query_hits_exhaustive(scene, segments, max_hits=4, channels=("distance",), count=True, blas=None) -> dict:
+def query_hits_exhaustive(scene, segments, max_hits=4, channels=("distance",), count=True, blas=None, mask=None, object_masks=None) -> dict:
     """rtxh_query_hits_exhaustive: the same hit tests over every primitive with no box test, the same order rule; "count" = all hits."""
-    return _query_hits("rtxh_query_hits_exhaustive", scene, segments, max_hits, channels, count, blas, False)
+    return _query_hits("rtxh_query_hits_exhaustive", scene, segments, max_hits, channels, count, blas, False, mask, object_masks)
 
 
 # ---- swept-sphere queries on the host (include/rtx_host.h: rtxh_query_sweep / rtxh_query_sweep_exhaustive) ---------------------------------
-def query_sweep(scene, sweeps, channels=("distance",), blas=None) -> dict:
+def query_sweep(scene, sweeps, channels=("distance",), blas=None, mask=None, object_masks=None) -> dict:
     """rtxh_query_sweep: what Renderer.query_sweep writes on the device for sweeps float32 (n, 8) of (origin, direction, max distance,
     radius), from the same code (csrc/rtx_sweep_math.h) -> {channel: array} plus "stack_max".  scene and blas as for query_nearest."""
-    return _query_nearest("rtxh_query_sweep", scene, sweeps, channels, blas, True, 8, "sweeps")
+    return _query_nearest("rtxh_query_sweep", scene, sweeps, channels, blas, True, 8, "sweeps", mask, object_masks)
 
 
-def query_sweep_exhaustive(scene, sweeps, channels=("distance",), blas=None) -> dict:
+def query_sweep_exhaustive(scene, sweeps, channels=("distance",), blas=None, mask=None, object_masks=None) -> dict:
     """rtxh_query_sweep_exhaustive: the same candidate functions over every primitive with no box test, the same order rule."""
-    return _query_nearest("rtxh_query_sweep_exhaustive", scene, sweeps, channels, blas, False, 8, "sweeps")
+    return _query_nearest("rtxh_query_sweep_exhaustive", scene, sweeps, channels, blas, False, 8, "sweeps", mask, object_masks)
 
 
 def sweep_bound(local_scale, world_scale=0.0, travelled=0.0, radius=0.0) -> float:

@@ -763,8 +763,8 @@ int rtx_query_nearest(rtx_ctx * ctx, const void * points_dev /* [n][4] f32: x, y
  * RTX_QUERY_ALL; a NULL ctx or segments_dev, a NULL out (a NULL count_dev in the count-only form), n < 1; any flag but RTX_QUERY_SORT.
  * RTX_ERR_STATE and RTX_ERR_LIMIT: as for rtx_query_nearest, its stack rule included.  An error queues nothing.
  * Limits: a BLAS whose leaves share triangles (the reference's SBVH with spatial splits) holds such a triangle once per slot, and every slot
- * is a hit.  Out of scope: hits beyond RTX_QUERY_MAX_HITS per row, an any-hit callback or per-material filtering, a per-ray tmin other
- * than RAY_EPSILON, signed distance as a single call, barycentrics as a channel, the rtx_group_* path.                                   */
+ * is a hit.  Out of scope: hits beyond RTX_QUERY_MAX_HITS per row, an any-hit callback or per-material filtering (whole objects are
+ * hidden by mask: filtered queries, below), a per-ray tmin other than RAY_EPSILON, signed distance as a single call, barycentrics as a channel, the rtx_group_* path.                                   */
 enum { RTX_QUERY_MAX_HITS = 8 };
 int rtx_query_hits(rtx_ctx * ctx, const void * segments_dev /* [n][7] f32: origin, direction, max distance */, int64_t n,
                    int32_t max_hits /* K */, uint32_t channels, const rtx_query_buffers * out /* each channel [n][K] */,
@@ -803,6 +803,59 @@ int rtx_query_hits(rtx_ctx * ctx, const void * segments_dev /* [n][7] f32: origi
  * shapes, all contacts along the sweep, a contact-normal channel, the rtx_group_* path.                                                    */
 int rtx_query_sweep(rtx_ctx * ctx, const void * sweeps_dev /* [n][8] f32: origin, direction, max distance, radius */, int64_t n,
                     uint32_t channels, const rtx_query_buffers * out, uint32_t flags /* RTX_QUERY_SORT or 0 */);
+
+/* ---- filtered queries: object masks -----------------------------------------------------------------------------------------------------
+ * "Each row sees only some objects": a cloth vertex that must not find its own mesh, a ball swept from a robot's link that must not touch
+ * that link, a lidar on a body, a line of sight between two objects — while the body stays part of the one frame that is also rendered.
+ * The instance / layer masks of other ray-query interfaces, for the three walk queries above.
+ * Objects are numbered as RTX_AOV_OBJECT_ID numbers them: instance i -> i, sphere s -> I + s, plane p -> I + S + p; M = I + S + P.
+ * Object masks: a table of M uint32_t owned by the context; without a table every object's mask is 0xFFFFFFFF.
+ * Row masks: one uint32_t per row, from the device array rtx_query_filter.row_masks_dev[n], or the scalar row_mask for every row when that
+ * pointer is NULL.
+ * Rule: an object exists for a row iff (object_mask & row_mask) != 0.  A hidden sphere or plane is not offered as a candidate; a hidden
+ * instance is passed over where the walk takes it from its TLAS leaf, before its matrix or its BLAS is touched; nothing else in the walk
+ * changes (TLAS boxes still contain hidden instances; order, tie rules and the stack rule are the same): FILTER in the header comment of
+ * csrc/rtx_nearest_math.h.  rtx_query_hits neither lists nor counts a hidden object; for rtx_query_sweep it neither stops the ball nor
+ * overlaps it.  A row whose mask is 0 is answered without a walk: the no-answer values, count 0.  The accuracy bounds of the three queries
+ * and what rtx_query_hits promises hold unchanged against the exhaustive search over the visible primitives; the rtxh_*_filtered functions
+ * of rtx_host.h are the same code on the host and give the same bits.
+ *
+ * rtx_set_object_masks copies count masks from HOST memory (through a pinned staging ring, one copy on the context's stream: a query queued
+ * before the call reads the old table, one queued after it the new).  rtx_update_object_masks copies them from DEVICE memory on the stream:
+ * nothing is read back, no pointer changes.  The table's allocation only grows (a call that grows it waits for the stream first); a
+ * steady-state call allocates nothing.  rtx_read_object_masks waits for the stream and reads back what the kernels see: *count = the
+ * table's length (0: no table), out[0 .. *count) if out is not NULL.
+ * Errors of the three, in this order: a NULL ctx: RTX_ERR_INVALID_ARG.  Before rtx_set_frame: RTX_ERR_STATE.  NULL masks with count 0 drops
+ * the table (its memory is kept).  Otherwise count must equal M of the current frame and masks must not be NULL (masks_dev 4-byte aligned):
+ * RTX_ERR_INVALID_ARG.  rtx_read_object_masks: out and count both NULL, capacity < 0 or below the table's length: RTX_ERR_INVALID_ARG.
+ * The context remembers (I, S, P) as they were when the table was set.  A later rtx_set_frame keeps the table; rtx_update_instances,
+ * rtx_refit_blas and rtx_build_blas do not touch it.  A filtered query whose frame has other counts than the remembered ones is
+ * RTX_ERR_STATE and queues nothing: set the masks again, or drop them.
+ *
+ * rtx_query_nearest_filtered, rtx_query_hits_filtered, rtx_query_sweep_filtered: the arguments, channels, flags, errors (in their order) and
+ * every rule of the call without the suffix, plus the filter; after those errors, the state rule above.  A NULL filter IS the call without
+ * the suffix: the same kernel, the same bits.  A filter without a table and with row_mask 0xFFFFFFFF, or with a table of all ones and row masks
+ * of all ones, gives the unfiltered answers bit for bit (by another kernel instantiation).  With RTX_QUERY_SORT the mask of slot i is that
+ * of the caller's row in that slot, gathered like the row itself; the sort key does not know the masks; answers are bit-identical, row for
+ * row, to the unsorted filtered call.  row_masks_dev is read during the call's kernels: keep it alive and unchanged until they have run.
+ * rtx_query_closest and rtx_query_occluded run on the render path's traversal kernels and stay unfiltered: a filtered closest hit is
+ * rtx_query_hits_filtered with max_hits = 1 (its one listed hit is the closest visible one), a filtered occlusion test its count-only
+ * form (count > 0).
+ * Out of scope: filtering in rtx_query_closest, rtx_query_occluded and render calls; exclusion by object or triangle id; per-material
+ * filtering; skipping the triangles next to a vertex (self-collision within one object); a per-ray tmin; the rtx_group_* path.             */
+typedef struct rtx_query_filter {
+    const uint32_t * row_masks_dev;      /* [n] in device memory, or NULL: row_mask for every row */
+    uint32_t row_mask;
+} rtx_query_filter;
+int rtx_set_object_masks(rtx_ctx * ctx, const uint32_t * masks_host /* [count] */, int32_t count /* M, or 0 with NULL */);
+int rtx_update_object_masks(rtx_ctx * ctx, const void * masks_dev /* [count] u32 */, int32_t count);
+int rtx_read_object_masks(rtx_ctx * ctx, uint32_t * out /* [capacity] or NULL */, int32_t capacity, int32_t * count);
+int rtx_query_nearest_filtered(rtx_ctx * ctx, const void * points_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags,
+                               const rtx_query_filter * filter);
+int rtx_query_hits_filtered(rtx_ctx * ctx, const void * segments_dev, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
+                            int32_t * count_dev, uint32_t flags, const rtx_query_filter * filter);
+int rtx_query_sweep_filtered(rtx_ctx * ctx, const void * sweeps_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags,
+                             const rtx_query_filter * filter);
 
 /* Timing of every kernel launched since rtx_enable_kernel_timing(ctx, 1),
  * measured with HIP events on the stream the kernels are launched on.

@@ -40,6 +40,7 @@
  *   rtxh_query_nearest       rtx_query_nearest on the host: the walk and the arithmetic of csrc/rtx_nearest_math.h over plain arrays;
  *                            rtxh_query_nearest_exhaustive the same candidate functions over every primitive, without a tree
  *   rtxh_query_sweep         rtx_query_sweep on the host: the walk and the arithmetic of csrc/rtx_sweep_math.h over the same arrays;
+ *   rtxh_query_*_filtered    the three walk queries under object masks (rtx_query_*_filtered), and their exhaustive searches over the visible primitives
  *   rtxh_query_hits          rtx_query_hits on the host: the walk and the arithmetic of csrc/rtx_hits_math.h over the same arrays;
  *                            rtxh_query_hits_exhaustive the same hit tests over every primitive, without a box test
  *   rtxh_texture_load        Texture::load: PNG / TGA file -> linear float3 texels + mips   Texture.cpp:30-129
@@ -264,6 +265,24 @@ float rtxh_sweep_bound(float local_scale, float world_scale, float travelled, fl
 int rtxh_sweep_triangle(const float origin[3], const float direction[3], float radius, float bound, const rtx_triangle_hot * tri, float * t_out, float uv_out[2], float * d20_out);
 int rtxh_sweep_sphere(const float origin[3], const float direction[3], float radius, const rtx_sphere * sphere, float * t_out, float * d20_out);
 int rtxh_sweep_plane(const float origin[3], const float direction[3], float radius, const rtx_plane * plane, float * t_out, float * d20_out);
+
+/* The filtered walk queries (include/rtx.h: filtered queries) on the host: the same walks with FILTER's predicates of csrc/rtx_nearest_math.h,
+ * so they give the device's bits.  The arguments of the function without the suffix, then object_masks (M = instance_count + sphere_count +
+ * plane_count masks in the numbering of RTX_AOV_OBJECT_ID, or NULL: all ones), row_masks (n masks, or NULL: row_mask for every row) and
+ * row_mask.  The _exhaustive_filtered forms search the visible primitives only: the promises of the three headers hold against them.
+ * The functions without the suffix are unchanged: the same walk over a scene that hides nothing.  Errors as without the suffix.            */
+int rtxh_query_nearest_filtered(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out, int32_t * stack_max_out,
+                                const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask);
+int rtxh_query_nearest_exhaustive_filtered(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out,
+                                           const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask);
+int rtxh_query_hits_filtered(const rtxh_nearest_scene * scene, const float * segments, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
+                             int32_t * count_out, int32_t * stack_max_out, const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask);
+int rtxh_query_hits_exhaustive_filtered(const rtxh_nearest_scene * scene, const float * segments, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
+                                        int32_t * count_out, const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask);
+int rtxh_query_sweep_filtered(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, uint32_t channels, const rtx_query_buffers * out, int32_t * stack_max_out,
+                              const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask);
+int rtxh_query_sweep_exhaustive_filtered(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, uint32_t channels, const rtx_query_buffers * out,
+                                         const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask);
 
 /* Texture::load (Texture.cpp:30-129): decodes a .png or .tga file the way the reference's vendored stb_image v2.19 does with
  * STBI_rgb_alpha (Texture.cpp:40), converts r,g,b bytes to linear light (colour_unpack :13-20, Math::gamma_to_linear Math.h:67-77;

@@ -17,6 +17,7 @@ alternate within each of `--rounds` rounds, the medians are reported.  The sorte
 and k1's distance against query_closest's.
 
   python tools/query_hits_bench.py --out profiles/query_hits_bench.json
+  python tools/query_hits_bench.py --mask rows      the filtered calls: none (default), ones, half, rows — tools/query_masks.py
 """
 import argparse
 import json
@@ -29,6 +30,8 @@ sys.path[:0] = [os.path.join(REPO, "cpu-raytracer_amd"), os.path.join(REPO, "tes
 ORDERS = ("coherent", "shuffled", "sorted")
 VARIANTS = ("k1", "closest", "k4", "k4_count", "count", "occluded", "k4_all")
 
+import query_masks  # noqa: E402
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -36,6 +39,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", help="write the rows and medians as JSON here")
+    query_masks.add_argument(ap)
     args = ap.parse_args()
 
     import numpy as np
@@ -47,6 +51,7 @@ def main():
     n = SIDE * SIDE
     r = api.Renderer(sc)
     stream = torch.cuda.Stream()
+    mask = query_masks.setup(r, sc, args.mask, n)                        # --mask: the filtered calls (tools/query_masks.py)
     sets, _ = ray_sets(sc)
     rays = {"coherent": torch.from_numpy(sets["coherent"]).cuda(), "shuffled": torch.from_numpy(sets["incoherent"]).cuda()}
     rays["sorted"] = rays["shuffled"]
@@ -63,19 +68,19 @@ def main():
     def call(variant, order):
         s = order == "sorted"
         if variant == "k1":
-            r.query_hits(seg[order], 1, ("distance",), count=False, out={"distance": dist1}, sort=s)
+            r.query_hits(seg[order], 1, ("distance",), count=False, out={"distance": dist1}, sort=s, mask=mask)
         elif variant == "closest":
             r.query_closest(rays[order], ("distance",), out={"distance": dist}, sort=s)
         elif variant == "k4":
-            r.query_hits(seg[order], K, ("distance",), count=False, out={"distance": out4["distance"]}, sort=s)
+            r.query_hits(seg[order], K, ("distance",), count=False, out={"distance": out4["distance"]}, sort=s, mask=mask)
         elif variant == "k4_count":
-            r.query_hits(seg[order], K, ("distance",), out={"distance": out4["distance"], "count": count}, sort=s)
+            r.query_hits(seg[order], K, ("distance",), out={"distance": out4["distance"], "count": count}, sort=s, mask=mask)
         elif variant == "count":
-            r.query_hits(seg[order], 0, (), out={"count": count}, sort=s)
+            r.query_hits(seg[order], 0, (), out={"count": count}, sort=s, mask=mask)
         elif variant == "occluded":
             r.query_occluded(seg[order], out=occ, sort=s)
         else:
-            r.query_hits(seg[order], K, tuple(api.QUERY_CHANNELS), out=dict(out4, count=count), sort=s)
+            r.query_hits(seg[order], K, tuple(api.QUERY_CHANNELS), out=dict(out4, count=count), sort=s, mask=mask)
 
     def timed(variant, order):
         with torch.cuda.stream(stream):
@@ -117,7 +122,7 @@ def main():
     summary = {k: {"median_mrows_per_s": sorted(v)[len(v) // 2], "min": min(v), "max": max(v)} for k, v in summary.items()}
     ratios = {f"k1_over_closest/{o}": summary[f"k1/{o}"]["median_mrows_per_s"] / summary[f"closest/{o}"]["median_mrows_per_s"] for o in ORDERS}
     ratios.update({f"count_over_occluded/{o}": summary[f"count/{o}"]["median_mrows_per_s"] / summary[f"occluded/{o}"]["median_mrows_per_s"] for o in ORDERS})
-    res = {"tool": "tools/query_hits_bench.py", "scene": "atrium stand-in 1920x1080", "rows_per_call": n, "steps": args.steps, "rounds": args.rounds,
+    res = {"tool": "tools/query_hits_bench.py", "scene": "atrium stand-in 1920x1080", "rows_per_call": n, "steps": args.steps, "rounds": args.rounds, "mask": args.mask,
            "count_histogram_to_16": hist, "k1_rows_differing_from_closest": k1_differs, "summary": summary, "ratios": ratios, "rows": rows}
     print(json.dumps(summary, indent=1))
     print(json.dumps({"ratios": ratios, "count_histogram_to_16": hist, "k1_rows_differing_from_closest": k1_differs}, indent=1))

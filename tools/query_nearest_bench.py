@@ -16,6 +16,7 @@ Timed with events around `--steps` calls queued back to back on one non-default 
 alternate within each of `--rounds` rounds, the medians are reported.  The sorted and the unsorted answers are compared bit for bit first.
 
   python tools/query_nearest_bench.py --out profiles/query_nearest_bench.json
+  python tools/query_nearest_bench.py --mask rows      the filtered calls: none (default), ones, half, rows — tools/query_masks.py
 """
 import argparse
 import json
@@ -39,6 +40,8 @@ def morton_order(p, lo, hi, bits=7):
             code = (code << 1) | ((q[:, a] >> k) & 1)
     return np.argsort(code, kind="stable")
 
+import query_masks  # noqa: E402
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -46,6 +49,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", help="write the rows and medians as JSON here")
+    query_masks.add_argument(ap)
     args = ap.parse_args()
 
     import numpy as np
@@ -57,6 +61,7 @@ def main():
     n = SIDE * SIDE
     r = api.Renderer(sc)
     stream = torch.cuda.Stream()
+    mask = query_masks.setup(r, sc, args.mask, n)                        # --mask: the filtered calls (tools/query_masks.py)
     rays = torch.from_numpy(ray_sets(sc)[0]["coherent"]).cuda()
     hit = r.query_closest(rays, ("distance", "position", "normal"))
     rng = np.random.default_rng(2026)
@@ -82,9 +87,9 @@ def main():
         if name == "closest":
             r.query_closest(rays, ("distance",), out={"distance": out_all["distance"]})
         elif channels == "distance":
-            r.query_nearest(pts[(name, order)], ("distance",), out={"distance": out_all["distance"]}, sort=order == "sorted")
+            r.query_nearest(pts[(name, order)], ("distance",), out={"distance": out_all["distance"]}, sort=order == "sorted", mask=mask)
         else:
-            r.query_nearest(pts[(name, order)], tuple(api.QUERY_CHANNELS), out=out_all, sort=order == "sorted")
+            r.query_nearest(pts[(name, order)], tuple(api.QUERY_CHANNELS), out=out_all, sort=order == "sorted", mask=mask)
 
     def timed(name, order, channels):
         with torch.cuda.stream(stream):
@@ -123,7 +128,7 @@ def main():
     summary = {k: {"median_mrows_per_s": sorted(v)[len(v) // 2], "min": min(v), "max": max(v)} for k, v in summary.items()}
     ratios = {f"{s}/{c}": summary[f"{s}/sorted/{c}"]["median_mrows_per_s"] / summary[f"{s}/shuffled/{c}"]["median_mrows_per_s"] for s in SETS for c in CHANNELS}
     res = {"tool": "tools/query_nearest_bench.py", "scene": "atrium stand-in 1920x1080", "rows_per_call": n, "answered": answered, "steps": args.steps,
-           "rounds": args.rounds, "summary": summary, "sorted_over_shuffled": ratios, "rows": rows}
+           "rounds": args.rounds, "mask": args.mask, "summary": summary, "sorted_over_shuffled": ratios, "rows": rows}
     print(json.dumps(summary, indent=1))
     print(json.dumps({"sorted_over_shuffled": ratios, "answered": answered}, indent=1))
     if args.out:

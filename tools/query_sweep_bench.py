@@ -15,6 +15,7 @@ alternate within each of `--rounds` rounds, the medians are reported.  The sorte
 and the ball's t against the ray's distance: a ball touches no later than its centre's ray hits.
 
   python tools/query_sweep_bench.py --out profiles/query_sweep_bench.json
+  python tools/query_sweep_bench.py --mask rows      the filtered calls: none (default), ones, half, rows — tools/query_masks.py
 """
 import argparse
 import json
@@ -27,6 +28,8 @@ sys.path[:0] = [os.path.join(REPO, "cpu-raytracer_amd"), os.path.join(REPO, "tes
 ORDERS = ("coherent", "shuffled", "sorted")
 VARIANTS = ("r1e-3", "closest", "r1e-2", "r1e-2_all")
 
+import query_masks  # noqa: E402
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -34,6 +37,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", help="write the rows and medians as JSON here")
+    query_masks.add_argument(ap)
     args = ap.parse_args()
 
     import numpy as np
@@ -48,6 +52,7 @@ def main():
     n = SIDE * SIDE
     r = api.Renderer(sc)
     stream = torch.cuda.Stream()
+    mask = query_masks.setup(r, sc, args.mask, n)                        # --mask: the filtered calls (tools/query_masks.py)
     sets, _ = ray_sets(sc)
     rays = {"coherent": torch.from_numpy(sets["coherent"]).cuda(), "shuffled": torch.from_numpy(sets["incoherent"]).cuda()}
     rays["sorted"] = rays["shuffled"]
@@ -65,9 +70,9 @@ def main():
         if variant == "closest":
             r.query_closest(rays[order], ("distance",), out={"distance": dist}, sort=s)
         elif variant == "r1e-2_all":
-            r.query_sweep(rows[("r1e-2", order)], tuple(api.QUERY_CHANNELS), out=out, sort=s)
+            r.query_sweep(rows[("r1e-2", order)], tuple(api.QUERY_CHANNELS), out=out, sort=s, mask=mask)
         else:
-            r.query_sweep(rows[(variant, order)], ("distance",), out={"distance": out["distance"]}, sort=s)
+            r.query_sweep(rows[(variant, order)], ("distance",), out={"distance": out["distance"]}, sort=s, mask=mask)
 
     def timed(variant, order):
         with torch.cuda.stream(stream):
@@ -110,7 +115,7 @@ def main():
         summary.setdefault(f"{row['variant']}/{row['order']}", []).append(row["mrows_per_s"])
     summary = {k: {"median_mrows_per_s": sorted(v)[len(v) // 2], "min": min(v), "max": max(v)} for k, v in summary.items()}
     ratios = {f"{v}_over_closest/{o}": summary[f"{v}/{o}"]["median_mrows_per_s"] / summary[f"closest/{o}"]["median_mrows_per_s"] for o in ORDERS for v in VARIANTS if v != "closest"}
-    res = {"tool": "tools/query_sweep_bench.py", "scene": "atrium stand-in 1920x1080", "scene_size": size, "rows_per_call": n, "steps": args.steps, "rounds": args.rounds,
+    res = {"tool": "tools/query_sweep_bench.py", "scene": "atrium stand-in 1920x1080", "scene_size": size, "rows_per_call": n, "steps": args.steps, "rounds": args.rounds, "mask": args.mask,
            "rows_answered_r1e-3_coherent": answered, "rows_later_than_the_centre_ray": later, "summary": summary, "ratios": ratios, "rows": results}
     print(json.dumps(summary, indent=1))
     print(json.dumps({"ratios": ratios, "rows_answered_r1e-3_coherent": answered, "rows_later_than_the_centre_ray": later}, indent=1))
