@@ -84,7 +84,10 @@ struct rtx_ctx {
     // rtx_alloc_blas_topology / rtx_set_blas_topology / rtx_blas_vertex_normals: the block of the vertex normals' buffers and the kernel
     // arguments that point into it; set: a topology has been queued since the alloc
     struct BlasNormals { bool allocated = false, set = false; DevBuf block; DevNormals dev; void * sort_tmp = nullptr; size_t sort_bytes = 0; unsigned int key_bits = 0; };
-    struct BlasHost { std::vector<DevBuf> arrays; int max_local_material = -1, inner_depth = -1; bool packet_ok = true; BlasRefit refit; BlasBuild build; BlasNormals normals; };
+    // rtx_blas_pseudonormals: the block of the pseudonormal tables (face records, vert_pn, edge_pn) and the kernel arguments that point into
+    // it and into the topology's and the refit plan's blocks; made by the first call for an id
+    struct BlasSide { bool allocated = false; DevBuf block; DevSide dev; };
+    struct BlasHost { std::vector<DevBuf> arrays; int max_local_material = -1, inner_depth = -1; bool packet_ok = true; BlasRefit refit; BlasBuild build; BlasNormals normals; BlasSide side; };
     std::vector<DevBlas> h_blas;
     std::vector<BlasHost> blas;
     DevBuf d_blas, d_materials, d_textures, d_sky, d_ewa;
@@ -141,6 +144,10 @@ struct rtx_ctx {
     // rtx_set_object_masks / rtx_update_object_masks: the table the filtered walk queries read (M uint32_t, grown only, filled through a staging
     // ring of its own like the cameras), whether there is one, and (I, S, P) of the frame it was set for
     DevBuf d_object_masks; StageRing mask_ring; bool masks_set = false; int32_t mask_counts[3] = { 0, 0, 0 };
+    // rtx_query_signed_distance: one DevSideBlas per BLAS id (all null: no tables), beside h_blas / d_blas and not in them, so DevBlas and the
+    // render kernels are what they were.  h_side follows the ids' states (rtx_blas_pseudonormals sets an entry, commit_blas and a replaced
+    // topology clear it); the device copy is brought up to date by the next signed query, on the stream, through a staging ring of its own
+    std::vector<DevSideBlas> h_side; DevBuf d_side; StageRing side_ring; bool side_dirty = true;
     size_t slots_alloc = 0, shadow_alloc = 0;
     DevBuf d_stats_partial, d_pk_fifo, d_counters, d_spill, d_fb_rgb, d_fb_packed, d_display, d_gamma, d_pk_heads;
     int trace_blocks_closest = 0, trace_blocks_any = 0, trace_blocks_count = 0;
@@ -360,6 +367,12 @@ static int upload_blas_table(rtx_ctx * c) {
     return RTX_OK;
 }
 
+// the id has no pseudonormal tables (any more): the next signed query uploads the entry before it launches, and none is queued now — every
+// caller has waited for the stream
+static void drop_side_entry(rtx_ctx * c, int32_t blas_id) {
+    if ((size_t)blas_id < c->h_side.size() && c->h_side[blas_id].vert_pn) { memset(&c->h_side[blas_id], 0, sizeof(DevSideBlas)); c->side_dirty = true; }
+}
+
 // The one place an id's state changes hands.  Queued work may still read the old arrays and the table: it is waited for explicitly, then the
 // table is uploaded with the new entry, and only then does the old record — arrays, refit plan, build scratch — go.
 static int commit_blas(rtx_ctx * c, int32_t blas_id, BlasStaged & S) {
@@ -371,6 +384,7 @@ static int commit_blas(rtx_ctx * c, int32_t blas_id, BlasStaged & S) {
     if (int rc = upload_blas_table(c)) { c->h_blas[blas_id] = old; c->h_blas.resize(had); c->blas.resize(had); return rc; }
     c->blas[blas_id] = std::move(S.H);
     c->refs_dirty = true;
+    drop_side_entry(c, blas_id);                                    // the pseudonormal tables went with the old record
     return RTX_OK;
 }
 
@@ -1049,6 +1063,8 @@ extern "C" int rtx_alloc_blas_topology(rtx_ctx * c, int32_t blas_id, int32_t tri
     N.allocated = true;
     HIP_OK(c, hipStreamSynchronize(c->stream));                    // queued normals still read the block this call replaces
     c->blas[blas_id].normals = std::move(N);
+    c->blas[blas_id].side = rtx_ctx::BlasSide();                   // the pseudonormal tables were made over the replaced topology
+    drop_side_entry(c, blas_id);
     return RTX_OK;
 }
 
@@ -1083,6 +1099,66 @@ extern "C" int rtx_blas_vertex_normals(rtx_ctx * c, int32_t blas_id, const void 
     launch_timed(c, "k_normals_faces", c->stream, [&] { hipLaunchKernelGGL(k_normals_faces, dim3(((uint32_t)d.tri_count + RTX_NORMALS_BLOCK - 1) / RTX_NORMALS_BLOCK), dim3(RTX_NORMALS_BLOCK), 0, c->stream, d); });
     launch_timed(c, "k_normals_sum", c->stream, [&] { hipLaunchKernelGGL(k_normals_sum, dim3(((uint32_t)d.vertex_count + RTX_NORMALS_BLOCK - 1) / RTX_NORMALS_BLOCK), dim3(RTX_NORMALS_BLOCK), 0, c->stream, d); });
     HIP_OK(c, hipGetLastError());
+    return RTX_OK;
+}
+
+// ---- pseudonormal tables (include/rtx.h: rtx_blas_pseudonormals / rtx_read_blas_pseudonormals; kernels in rtx_side.h, arithmetic in
+// rtx_side_math.h) ----------------------------------------------------------------------------------------------------------------------
+// The state lives in the id's host record beside the topology it is made from.  The first call for an id stages its block, waits for the
+// stream and swaps it in (a refused allocation changes nothing); later calls only queue the three kernels.  The kernels read the topology's
+// block (indices, sorted keys, offsets) and the refit plan's slot table: whatever replaces either (commit_blas, rtx_alloc_blas_topology) drops
+// this state with it.
+extern "C" int rtx_blas_pseudonormals(rtx_ctx * c, int32_t blas_id, const void * positions_dev) {
+    if (!c) return RTX_ERR_INVALID_ARG;
+    if (!positions_dev || ((uintptr_t)positions_dev & 3)) { c->err = "rtx_blas_pseudonormals: null or misaligned pointer"; return RTX_ERR_INVALID_ARG; }
+    if (blas_id < 0 || (size_t)blas_id >= c->blas.size() || !c->blas[blas_id].normals.allocated) { c->err = "rtx_blas_pseudonormals: no topology allocated under that id (rtx_alloc_blas_topology)"; return RTX_ERR_STATE; }
+    rtx_ctx::BlasHost & H = c->blas[blas_id];
+    if (!H.normals.set) { c->err = "rtx_blas_pseudonormals: no topology set since the alloc (rtx_set_blas_topology)"; return RTX_ERR_STATE; }
+    if (!H.refit.bound) { c->err = "rtx_blas_pseudonormals: no vertices bound to the id (rtx_bind_blas_vertices, or rtx_alloc_blas)"; return RTX_ERR_STATE; }
+    if (H.normals.dev.vertex_count != H.refit.vertex_count) {
+        c->err = "rtx_blas_pseudonormals: the topology's vertex_count (" + std::to_string(H.normals.dev.vertex_count) + ") differs from the bound one (" + std::to_string(H.refit.vertex_count) + ")";
+        return RTX_ERR_INVALID_ARG;
+    }
+    hipSetDevice(c->cfg.device);
+    const size_t T = (size_t)H.normals.dev.tri_count, V = (size_t)H.normals.dev.vertex_count, slots = (size_t)c->h_blas[blas_id].tri_count;
+    if (!H.side.allocated) {
+        rtx_ctx::BlasSide N;
+        // [face records][vertex pseudonormals][edge pseudonormals], every part 256-byte aligned
+        const size_t len[3] = { T * RTX_SIDE_RECORD * 16, V * 16, (slots ? slots : 1) * 3 * 16 };
+        size_t off[3];
+        if (int rc = ensure(c, N.block, aligned_parts(len, off, 3))) return rc;
+        char * const bb = (char *)N.block.p;
+        memset(&N.dev, 0, sizeof(N.dev));
+        N.dev.record = (float4 *)(bb + off[0]); N.dev.vert_pn = (float4 *)(bb + off[1]); N.dev.edge_pn = (float4 *)(bb + off[2]);
+        N.dev.indices = H.normals.dev.indices; N.dev.keys = H.normals.dev.keys; N.dev.offset = H.normals.dev.offset;
+        N.dev.slot_vertices = H.refit.dev.slot_vertices;
+        N.dev.tri_count = (int32_t)T; N.dev.vertex_count = (int32_t)V; N.dev.slots = (int32_t)slots;
+        N.allocated = true;
+        if (c->h_side.size() < c->h_blas.size()) { DevSideBlas none; memset(&none, 0, sizeof(none)); c->h_side.resize(c->h_blas.size(), none); }
+        HIP_OK(c, hipStreamSynchronize(c->stream));
+        H.side = std::move(N);
+        DevSideBlas & e = c->h_side[blas_id];
+        e.vert_pn = H.side.dev.vert_pn; e.edge_pn = H.side.dev.edge_pn; e.slot_vertices = H.side.dev.slot_vertices; e.vertex_count = (int32_t)V; e.pad = 0;
+        c->side_dirty = true;
+    }
+    DevSide & d = H.side.dev;
+    d.positions = (const float *)positions_dev;
+    launch_timed(c, "k_side_faces", c->stream, [&] { hipLaunchKernelGGL(k_side_faces, dim3(((uint32_t)d.tri_count + RTX_SIDE_BLOCK - 1) / RTX_SIDE_BLOCK), dim3(RTX_SIDE_BLOCK), 0, c->stream, d); });
+    launch_timed(c, "k_side_vertices", c->stream, [&] { hipLaunchKernelGGL(k_side_vertices, dim3(((uint32_t)d.vertex_count + RTX_SIDE_BLOCK - 1) / RTX_SIDE_BLOCK), dim3(RTX_SIDE_BLOCK), 0, c->stream, d); });
+    if (d.slots) launch_timed(c, "k_side_edges", c->stream, [&] { hipLaunchKernelGGL(k_side_edges, dim3((3u * (uint32_t)d.slots + RTX_SIDE_BLOCK - 1) / RTX_SIDE_BLOCK), dim3(RTX_SIDE_BLOCK), 0, c->stream, d); });
+    HIP_OK(c, hipGetLastError());
+    return RTX_OK;
+}
+
+extern "C" int rtx_read_blas_pseudonormals(rtx_ctx * c, int32_t blas_id, float * vert_out, float * edge_out) {
+    if (!c) return RTX_ERR_INVALID_ARG;
+    if (blas_id < 0 || blas_id >= (1 << 20) || (!vert_out && !edge_out)) { c->err = "rtx_read_blas_pseudonormals: bad id or nothing to read into"; return RTX_ERR_INVALID_ARG; }
+    if ((size_t)blas_id >= c->blas.size() || !c->blas[blas_id].side.allocated) { c->err = "rtx_read_blas_pseudonormals: no pseudonormal tables under that id (rtx_blas_pseudonormals)"; return RTX_ERR_STATE; }
+    hipSetDevice(c->cfg.device);
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    const DevSide & d = c->blas[blas_id].side.dev;
+    if (vert_out) HIP_OK(c, hipMemcpy(vert_out, d.vert_pn, (size_t)d.vertex_count * 16, hipMemcpyDeviceToHost));
+    if (edge_out && d.slots) HIP_OK(c, hipMemcpy(edge_out, d.edge_pn, (size_t)d.slots * 3 * 16, hipMemcpyDeviceToHost));
     return RTX_OK;
 }
 
@@ -2402,9 +2478,34 @@ static QueryMasks<true> filter_masks(const rtx_ctx * c, const rtx_query_filter *
 // reads is touched.  The stack lives in LDS and in regions 0 and 1 of the context's spill buffer, as for a closest-hit launch of this stream.
 // The stack rule: the ordered descent holds at most rtxnp::stack_need(TLAS inner depth, deepest BLAS inner depth) entries; a scene that needs
 // more than rtx_config.stack_size (itself <= RTX_MAX_STACK, what LDS and the spill region hold per lane) is refused here, on the host.
-static int query_nearest_impl(rtx_ctx * c, const void * points_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags, const rtx_query_filter * filter) {
-    if (c && (channels == 0 || (channels & ~(uint32_t)RTX_QUERY_ALL))) { c->err = "rtx_query_nearest: channels must be a non-empty subset of RTX_QUERY_ALL"; return RTX_ERR_INVALID_ARG; }
-    if (int bad = query_checks(c, points_dev, n, out, flags, "rtx_query_nearest", (uint32_t)RTX_QUERY_SORT)) return bad;
+// rtx_query_signed_distance is the same call with two more outputs (sg: signed_dev [n], feature_dev [n] or null) and the SIGNED
+// instantiations; its channels may be empty, and then out may be null.
+struct QuerySigned { float * signed_dev; int32_t * feature_dev; };
+// the device copy of h_side covers every BLAS id and is current: growth waits for the stream (queued signed queries read the old table), an
+// update is a staged copy on the stream, a steady-state call does neither
+static int side_table_current(rtx_ctx * c) {
+    const size_t ids = c->h_blas.size(), bytes = ids * sizeof(DevSideBlas);
+    if (c->h_side.size() < ids) { DevSideBlas none; memset(&none, 0, sizeof(none)); c->h_side.resize(ids, none); c->side_dirty = true; }
+    if (!c->d_side.p || bytes > c->d_side.cap) {
+        DevBuf nb;
+        if (int rc = ensure(c, nb, bytes)) return rc;
+        HIP_OK(c, hipStreamSynchronize(c->stream));
+        c->d_side = std::move(nb);
+        c->side_dirty = true;
+    }
+    if (c->side_dirty && bytes) if (int rc = stage_copy(c, c->side_ring, c->d_side.p, c->h_side.data(), bytes)) return rc;
+    c->side_dirty = false;
+    return RTX_OK;
+}
+static int query_nearest_impl(rtx_ctx * c, const void * points_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags, const rtx_query_filter * filter,
+                              const QuerySigned * sg = nullptr) {
+    if (c && sg) {
+        if (channels & ~(uint32_t)RTX_QUERY_ALL) { c->err = "rtx_query_signed_distance: channels must be a subset of RTX_QUERY_ALL"; return RTX_ERR_INVALID_ARG; }
+        if (!sg->signed_dev || (((uintptr_t)sg->signed_dev | (uintptr_t)sg->feature_dev) & 3)) { c->err = "rtx_query_signed_distance: null or misaligned signed-distance or feature pointer"; return RTX_ERR_INVALID_ARG; }
+        static const rtx_query_buffers no_buffers = {};
+        if (channels == 0 && !out) out = &no_buffers;                  // no channel bit is set: nothing of it is read
+    } else if (c && (channels == 0 || (channels & ~(uint32_t)RTX_QUERY_ALL))) { c->err = "rtx_query_nearest: channels must be a non-empty subset of RTX_QUERY_ALL"; return RTX_ERR_INVALID_ARG; }
+    if (int bad = query_checks(c, points_dev, n, out, flags, sg ? "rtx_query_signed_distance" : "rtx_query_nearest", (uint32_t)RTX_QUERY_SORT)) return bad;
     int blas_depth = -1;
     for (size_t b = 0; b < c->blas.size(); b++) if (c->h_blas[b].nodes && c->blas[b].inner_depth > blas_depth) blas_depth = c->blas[b].inner_depth;
     const int need = rtxnp::stack_need(c->tlas_inner_depth, blas_depth), have = c->cfg.stack_size < RTX_MAX_STACK ? c->cfg.stack_size : RTX_MAX_STACK;
@@ -2413,12 +2514,13 @@ static int query_nearest_impl(rtx_ctx * c, const void * points_dev, int64_t n, u
                  " + 1, BLAS inner depth " + std::to_string(blas_depth) + " + 1), rtx_config.stack_size allows " + std::to_string(have);
         return RTX_ERR_LIMIT;
     }
-    if (int bad = filter_checks(c, filter, "rtx_query_nearest")) return bad;
+    if (int bad = filter_checks(c, filter, sg ? "rtx_query_signed_distance" : "rtx_query_nearest")) return bad;
     hipSetDevice(c->cfg.device);
     const bool sorted = (flags & RTX_QUERY_SORT) != 0;
     QuerySort S = {};
     DevQueues unused;
     if (sorted) if (int rc = query_queues(c, n, unused, &S, false)) return rc;
+    if (sg) if (int rc = side_table_current(c)) return rc;
     if (c->nearest_fetch) if (int rc = ensure(c, c->d_nearest_head, sizeof(uint32_t))) return rc;      // the first call only
     uint32_t * const head = c->nearest_fetch ? (uint32_t *)c->d_nearest_head.p : nullptr;
     const DevScene sc = c->scene;
@@ -2439,10 +2541,14 @@ static int query_nearest_impl(rtx_ctx * c, const void * points_dev, int64_t n, u
         const int tiles = (m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK, blocks = tiles < max_blocks ? tiles : max_blocks;
         const uint64_t * const order = sorted ? S.keys : nullptr;
         if (head) HIP_OK(c, hipMemsetAsync(head, 0, sizeof(uint32_t), c->stream));
+        QuerySide<true> ks = { nullptr, nullptr, nullptr };
+        if (sg) { ks.blas = (const DevSideBlas *)c->d_side.p; ks.signed_out = sg->signed_dev + first; ks.feature = sg->feature_dev ? sg->feature_dev + first : nullptr; }
         if (filter) {
             const QueryMasks<true> km = filter_masks(c, filter, first);
-            launch_timed(c, "k_query_nearest", c->stream, [&] { hipLaunchKernelGGL(k_query_nearest<true>, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, km); });
-        } else launch_timed(c, "k_query_nearest", c->stream, [&] { hipLaunchKernelGGL(k_query_nearest<false>, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, QueryMasks<false>()); });
+            if (sg) launch_timed(c, "k_query_nearest", c->stream, [&] { hipLaunchKernelGGL((k_query_nearest<true, true>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, km, ks); });
+            else launch_timed(c, "k_query_nearest", c->stream, [&] { hipLaunchKernelGGL((k_query_nearest<true, false>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, km, QuerySide<false>()); });
+        } else if (sg) launch_timed(c, "k_query_nearest", c->stream, [&] { hipLaunchKernelGGL((k_query_nearest<false, true>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, QueryMasks<false>(), ks); });
+        else launch_timed(c, "k_query_nearest", c->stream, [&] { hipLaunchKernelGGL((k_query_nearest<false, false>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, QueryMasks<false>(), QuerySide<false>()); });
     }
     HIP_OK(c, hipGetLastError());
     return RTX_OK;
@@ -2452,6 +2558,11 @@ extern "C" int rtx_query_nearest(rtx_ctx * c, const void * points_dev, int64_t n
 }
 extern "C" int rtx_query_nearest_filtered(rtx_ctx * c, const void * points_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags, const rtx_query_filter * filter) {
     return query_nearest_impl(c, points_dev, n, channels, out, flags, filter);
+}
+extern "C" int rtx_query_signed_distance(rtx_ctx * c, const void * points_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out,
+                                         float * signed_dev, int32_t * feature_dev, uint32_t flags, const rtx_query_filter * filter) {
+    const QuerySigned sg = { signed_dev, feature_dev };
+    return query_nearest_impl(c, points_dev, n, channels, out, flags, filter, &sg);
 }
 
 // ---- all-hits segment queries (include/rtx.h: rtx_query_hits; kernel in rtx_hits.h, arithmetic and walk in rtx_hits_math.h) ------------

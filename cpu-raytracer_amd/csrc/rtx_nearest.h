@@ -21,10 +21,18 @@
 // anew.  An instance's mask is one dword at table[tlas_indices[slot]], read at the TLAS leaf ahead of the instance's 64-byte matrix; the
 // masks of spheres and planes are read at an index every lane shares.  Stack, spill addressing, staged rows and the tile counter are those
 // of the unfiltered instantiation, which is the code it was: its Scene's predicates are constants.
+//
+// SIGNED (rtx_query_signed_distance): the instantiations that also write the signed distance and the feature code of rtx_side_math.h.  They
+// take QuerySide<true> (the per-BLAS table array, the signed-distance pointer, the feature pointer or null), empty otherwise like
+// QueryMasks.  The sign is computed after the walk has returned, next to the cold-record reads: the winner's matrix and three 16-byte hot
+// loads, the region chain, then the mesh's 32-byte DevSideBlas entry and behind it an edge record, or a slot vertex and its record: up to
+// three dependent loads (a face needs only the entry's null test).  walk(), the stack, the staged
+// rows and the tile counter are the same; the two instantiations without it are the code they were.
 #pragma once
 #include "rtx_query.h"
 #include "rtx_shade.h"
 #include "rtx_nearest_math.h"
+#include "rtx_side.h"
 
 struct NearestScene {
     const DevScene & sc;
@@ -82,10 +90,44 @@ struct NearestStack {
     }
 };
 
-template <bool FILTERED>
+// the extra kernel arguments of a SIGNED instantiation (rtx_query_signed_distance); none otherwise.  blas: one DevSideBlas per BLAS id, beside
+// the DevBlas table, so DevBlas / DevScene and every kernel that takes them are what they were; signed_out: n floats; feature: n or null
+template <bool SIGNED> struct QuerySide {};
+template <> struct QuerySide<true> { const DevSideBlas * blas; float * signed_out; int32_t * feature; };
+
+// the tables of one mesh as SIDE of rtx_side_math.h reads them: one 16-byte load per edge, an index and a 16-byte load per vertex
+struct SideTables {
+    const DevSideBlas & t;
+    RTX_D bool has_tables() const { return t.vert_pn != nullptr; }
+    RTX_D rtxnp::P3 edge(int i) const { const float4 n = gld(RTX_GPTR(t.edge_pn), i); return rtxnp::mk(n.x, n.y, n.z); }
+    RTX_D rtxnp::P3 vertex(int slot, int k) const {
+        const int32_t v = t.slot_vertices[3 * (size_t)slot + k];
+        if (v < 0 || v >= t.vertex_count) return rtxnp::mk(0.0f, 0.0f, 0.0f);
+        const float4 n = gld(RTX_GPTR(t.vert_pn), v); return rtxnp::mk(n.x, n.y, n.z);
+    }
+};
+
+// SIDE of rtx_side_math.h for the walk's answer a of the row at p: the sign and the FEATURE code.  After the walk, next to the cold-record
+// reads: the instance's matrix, three 16-byte hot loads, the region chain, the mesh's table entry and at most two more dependent loads
+RTX_D int nearest_side(const DevScene & sc, const DevSideBlas * side, const rtxnp::Answer & a, const rtxnp::P3 p, bool & negative) {
+    negative = false;
+    if (a.kind == rtxnp::KIND_TRI) {
+        const rtx_instance & I = sc.instances[a.object];
+        const rtx_gptr hp = RTX_GPTR(sc.blas[I.blas_id].tri_hot);
+        const float4 p0 = gld(hp, RTX_TRI_STRIDE * a.slot), e1 = gld(hp, RTX_TRI_STRIDE * a.slot + 1), e2 = gld(hp, RTX_TRI_STRIDE * a.slot + 2);
+        const rtxnp::P3 pl = rtxnp::xform_pos(I.world_inv, p);
+        const SideTables tb = { side[I.blas_id] };
+        return rtxsd::triangle_side(rtxnp::sub(pl, rtxnp::mk(p0.x, p0.y, p0.z)), rtxnp::mk(e1.x, e1.y, e1.z), rtxnp::mk(e2.x, e2.y, e2.z), a.slot, tb, negative);
+    }
+    if (a.kind == rtxnp::KIND_SPHERE) { const rtx_sphere & s = sc.spheres[a.object]; negative = rtxsd::sphere_side(p, rtxnp::ptr3(s.center), s.radius_squared); return rtxsd::FEATURE_SPHERE; }
+    if (a.kind == rtxnp::KIND_PLANE) { const rtx_plane & pl = sc.planes[a.object]; negative = rtxsd::plane_side(p, rtxnp::ptr3(pl.normal), pl.distance); return rtxsd::FEATURE_PLANE; }
+    return rtxsd::FEATURE_NONE;
+}
+
+template <bool FILTERED, bool SIGNED>
 __global__ __launch_bounds__(RTX_QUERY_BLOCK)
 void k_query_nearest(const DevScene sc, const float * __restrict__ rows4, const int m, const DevQuery out, const uint64_t * __restrict__ order,
-                     int32_t * const spill_base, const int spill_threads, uint32_t * const head, const QueryMasks<FILTERED> masks) {
+                     int32_t * const spill_base, const int spill_threads, uint32_t * const head, const QueryMasks<FILTERED> masks, const QuerySide<SIGNED> side) {
     __shared__ float lds_rows[4 * RTX_QUERY_BLOCK];
     __shared__ int lds_stack[RTX_QUERY_BLOCK / RTX_WAVE][RTX_LDS_STACK][RTX_WAVE];
     __shared__ float lds_key[RTX_QUERY_BLOCK / RTX_WAVE][RTX_LDS_STACK][RTX_WAVE];
@@ -146,5 +188,11 @@ void k_query_nearest(const DevScene sc, const float * __restrict__ rows4, const 
         if (out.object_id)                                            // instances, then spheres, then planes: the numbering of rtx_query_closest
             out.object_id[p] = !hit ? -1 : a.kind == rtxnp::KIND_TRI ? a.object : a.kind == rtxnp::KIND_SPHERE ? sc.instance_count + a.object : sc.instance_count + sc.sphere_count + a.object;
         if (out.triangle_id) out.triangle_id[p] = a.kind == rtxnp::KIND_TRI ? a.slot : -1;
+        if constexpr (SIGNED) {
+            bool negative;
+            const int feature = nearest_side(sc, side.blas, a, rtxnp::mk(r[0], r[1], r[2]), negative);
+            side.signed_out[p] = hit ? rtxsd::signed_distance(a.d2, negative) : INFINITY;
+            if (side.feature) side.feature[p] = feature;
+        }
     }
 }

@@ -121,19 +121,26 @@ RTX_HDF float box_d2(P3 p, P3 mn, P3 mx) {
     return dx * dx + (dy * dy + dz * dz);
 }
 
-// the weights (u, v) of the closest point of triangle (p0, e1, e2) to p0 + ap, and its squared distance
-RTX_HDF float triangle_d2(P3 ap, P3 e1, P3 e2, float & u, float & v) {
+// The region chain of TRIANGLE, in its one place: the weights (u, v) of the closest point of triangle (p0, e1, e2) to p0 + ap, and the branch
+// that gave them — REGION_VERTEX_A .. REGION_FACE, the feature of the triangle that holds the point (rtx_side_math.h reads it; triangle_d2
+// below drops it, and its code is what it was).
+enum { REGION_VERTEX_A = 0, REGION_VERTEX_B = 1, REGION_VERTEX_C = 2, REGION_EDGE_AB = 3, REGION_EDGE_BC = 4, REGION_EDGE_AC = 5, REGION_FACE = 6 };
+RTX_HDF int triangle_weights(P3 ap, P3 e1, P3 e2, float & u, float & v) {
     const float d1 = dot(e1, ap), d2 = dot(e2, ap);
     const float aa = dot(e1, e1), ab = dot(e1, e2), cc = dot(e2, e2);
     const float d3 = d1 - aa, d4 = d2 - ab, d5 = d1 - ab, d6 = d2 - cc;
     const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
-    if (d1 <= 0.0f && d2 <= 0.0f) { u = 0.0f; v = 0.0f; }
-    else if (d3 >= 0.0f && d4 <= d3) { u = 1.0f; v = 0.0f; }
-    else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) { u = d1 / (d1 - d3); v = 0.0f; }
-    else if (d6 >= 0.0f && d5 <= d6) { u = 0.0f; v = 1.0f; }
-    else if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) { u = 0.0f; v = d2 / (d2 - d6); }
-    else if (va <= 0.0f && (d4 - d3) >= 0.0f && (d5 - d6) >= 0.0f) { const float w = (d4 - d3) / ((d4 - d3) + (d5 - d6)); u = 1.0f - w; v = w; }
-    else { const float k = 1.0f / (va + (vb + vc)); u = vb * k; v = vc * k; }
+    if (d1 <= 0.0f && d2 <= 0.0f) { u = 0.0f; v = 0.0f; return REGION_VERTEX_A; }
+    else if (d3 >= 0.0f && d4 <= d3) { u = 1.0f; v = 0.0f; return REGION_VERTEX_B; }
+    else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) { u = d1 / (d1 - d3); v = 0.0f; return REGION_EDGE_AB; }
+    else if (d6 >= 0.0f && d5 <= d6) { u = 0.0f; v = 1.0f; return REGION_VERTEX_C; }
+    else if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) { u = 0.0f; v = d2 / (d2 - d6); return REGION_EDGE_AC; }
+    else if (va <= 0.0f && (d4 - d3) >= 0.0f && (d5 - d6) >= 0.0f) { const float w = (d4 - d3) / ((d4 - d3) + (d5 - d6)); u = 1.0f - w; v = w; return REGION_EDGE_BC; }
+    else { const float k = 1.0f / (va + (vb + vc)); u = vb * k; v = vc * k; return REGION_FACE; }
+}
+// the weights (u, v) of the closest point of triangle (p0, e1, e2) to p0 + ap, and its squared distance
+RTX_HDF float triangle_d2(P3 ap, P3 e1, P3 e2, float & u, float & v) {
+    triangle_weights(ap, e1, e2, u, v);
     const P3 w = add(scale(e1, u), scale(e2, v));
     const P3 r = sub(ap, w);
     return dot(r, r);

@@ -12,6 +12,7 @@
 #include "../csrc/rtx_texmip_math.h"
 #include "../csrc/rtx_query_sort_math.h"
 #include "../csrc/rtx_nearest_math.h"
+#include "../csrc/rtx_side_math.h"
 #include "../csrc/rtx_hits_math.h"
 #include "../csrc/rtx_sweep_math.h"
 
@@ -656,8 +657,9 @@ int tree_inner_depth(const rtx_bvh_node * nodes, int node_count, int64_t primiti
     }
     return RTX_OK;
 }
-int nearest_scene_check(const rtxh_nearest_scene * s, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out, bool trees) {
-    if (!s || !points || !out || n < 1 || channels == 0 || (channels & ~(uint32_t)RTX_QUERY_ALL)) return RTX_ERR_INVALID_ARG;
+int nearest_scene_check(const rtxh_nearest_scene * s, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out, bool trees, bool may_be_empty = false) {
+    if (!s || !points || n < 1 || (channels & ~(uint32_t)RTX_QUERY_ALL)) return RTX_ERR_INVALID_ARG;
+    if (may_be_empty ? (channels != 0 && !out) : (!out || channels == 0)) return RTX_ERR_INVALID_ARG;      // a signed query may ask for no channel
     if (s->instance_count < 0 || s->tlas_node_count < 0 || s->tlas_index_count < 0 || s->blas_count < 0 || s->sphere_count < 0 || s->plane_count < 0) return RTX_ERR_INVALID_ARG;
     if ((s->instance_count && !s->instances) || (s->tlas_node_count && !s->tlas_nodes) || (s->tlas_index_count && !s->tlas_indices) || (s->blas_count && !s->blas) ||
         (s->sphere_count && !s->spheres) || (s->plane_count && !s->planes)) return RTX_ERR_INVALID_ARG;
@@ -704,10 +706,38 @@ void nearest_store(const rtxh_nearest_scene & s, const float * row, const rtxnp:
         out.object_id[i] = !hit ? -1 : a.kind == rtxnp::KIND_TRI ? a.object : a.kind == rtxnp::KIND_SPHERE ? s.instance_count + a.object : s.instance_count + s.sphere_count + a.object;
     if (on(RTX_QUERY_TRIANGLE_ID) && out.triangle_id) out.triangle_id[i] = a.kind == rtxnp::KIND_TRI ? a.slot : -1;
 }
+// SIDE of csrc/rtx_side_math.h over plain arrays: the tables of one mesh (null: none), and what k_query_nearest<.., SIGNED> stores for row i
+struct HostSideTables {
+    const rtxh_side_blas * t;
+    bool has_tables() const { return t && t->vert_pn && t->edge_pn && t->slot_vertices; }
+    rtxnp::P3 edge(int i) const { return rtxnp::ptr3(t->edge_pn + 4 * (size_t)i); }
+    rtxnp::P3 vertex(int slot, int k) const {
+        const int32_t v = t->slot_vertices[3 * (size_t)slot + k];
+        return v < 0 || v >= t->vertex_count ? rtxnp::mk(0.0f, 0.0f, 0.0f) : rtxnp::ptr3(t->vert_pn + 4 * (size_t)v);
+    }
+};
+struct HostSigned { const rtxh_side_blas * side; float * signed_out; int32_t * feature_out; };
+void signed_store(const rtxh_nearest_scene & s, const float * row, const rtxnp::Answer & a, int64_t i, const HostSigned & sg) {
+    const rtxnp::P3 p = rtxnp::mk(row[0], row[1], row[2]);
+    bool negative = false; int feature = rtxsd::FEATURE_NONE;
+    if (a.kind == rtxnp::KIND_TRI) {
+        const rtx_instance & I = s.instances[a.object];
+        const rtx_triangle_hot & h = s.blas[I.blas_id].hot[a.slot];
+        const HostSideTables tb = { sg.side ? sg.side + I.blas_id : nullptr };
+        feature = rtxsd::triangle_side(rtxnp::sub(rtxnp::xform_pos(I.world_inv, p), rtxnp::ptr3(h.position_0)), rtxnp::ptr3(h.position_edge_1), rtxnp::ptr3(h.position_edge_2), a.slot, tb, negative);
+    } else if (a.kind == rtxnp::KIND_SPHERE) { negative = rtxsd::sphere_side(p, rtxnp::ptr3(s.spheres[a.object].center), s.spheres[a.object].radius_squared); feature = rtxsd::FEATURE_SPHERE; }
+    else if (a.kind == rtxnp::KIND_PLANE) { negative = rtxsd::plane_side(p, rtxnp::ptr3(s.planes[a.object].normal), s.planes[a.object].distance); feature = rtxsd::FEATURE_PLANE; }
+    sg.signed_out[i] = a.kind != rtxnp::KIND_NONE ? rtxsd::signed_distance(a.d2, negative) : INFINITY;
+    if (sg.feature_out) sg.feature_out[i] = feature;
+}
+const rtx_query_buffers kNoBuffers = {};
 }  // namespace
 
-static int query_nearest_host(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out, int32_t * stack_max_out, const HostMasks * km) {
-    if (int rc = nearest_scene_check(scene, points, n, channels, out, true)) return rc;
+static int query_nearest_host(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out, int32_t * stack_max_out, const HostMasks * km,
+                              const HostSigned * sg = nullptr) {
+    if (sg && !sg->signed_out) return RTX_ERR_INVALID_ARG;
+    if (int rc = nearest_scene_check(scene, points, n, channels, out, true, sg != nullptr)) return rc;
+    if (!out) out = &kNoBuffers;
     int high = 0;
     for (int64_t i = 0; i < n; i++) {
         HostNearestStack st;
@@ -716,6 +746,7 @@ static int query_nearest_host(const rtxh_nearest_scene * scene, const float * po
         else { HostNearestScene S{ *scene }; rtxnp::walk(S, st, points + 4 * i, a); }
         if (st.high > high) high = st.high;
         nearest_store(*scene, points + 4 * i, a, i, channels, *out);
+        if (sg) signed_store(*scene, points + 4 * i, a, i, *sg);
     }
     if (stack_max_out) *stack_max_out = high;
     return RTX_OK;
@@ -730,8 +761,11 @@ extern "C" int rtxh_query_nearest_filtered(const rtxh_nearest_scene * scene, con
     return query_nearest_host(scene, points, n, channels, out, stack_max_out, &km);
 }
 
-static int query_nearest_exhaustive_host(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out, const HostMasks km) {
-    if (int rc = nearest_scene_check(scene, points, n, channels, out, false)) return rc;
+static int query_nearest_exhaustive_host(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out, const HostMasks km,
+                                         const HostSigned * sg = nullptr) {
+    if (sg && !sg->signed_out) return RTX_ERR_INVALID_ARG;
+    if (int rc = nearest_scene_check(scene, points, n, channels, out, false, sg != nullptr)) return rc;
+    if (!out) out = &kNoBuffers;
     const rtxh_nearest_scene & s = *scene;
     for (int64_t i = 0; i < n; i++) {
         const float * row = points + 4 * i;
@@ -754,6 +788,7 @@ static int query_nearest_exhaustive_host(const rtxh_nearest_scene * scene, const
             }
         }
         nearest_store(s, row, a, i, channels, *out);
+        if (sg) signed_store(s, row, a, i, *sg);
     }
     return RTX_OK;
 }
@@ -765,6 +800,32 @@ extern "C" int rtxh_query_nearest_exhaustive_filtered(const rtxh_nearest_scene *
                                                       const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask) {
     const HostMasks km = { object_masks, row_masks, row_mask };
     return query_nearest_exhaustive_host(scene, points, n, channels, out, km);
+}
+
+// rtx_query_signed_distance on the host: the nearest-point searches above, then SIDE of csrc/rtx_side_math.h for the winner
+extern "C" int rtxh_query_signed_distance(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out,
+                                          const rtxh_side_blas * side, float * signed_out, int32_t * feature_out, int32_t * stack_max_out) {
+    const HostSigned sg = { side, signed_out, feature_out };
+    return query_nearest_host(scene, points, n, channels, out, stack_max_out, nullptr, &sg);
+}
+extern "C" int rtxh_query_signed_distance_filtered(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out,
+                                                   const rtxh_side_blas * side, float * signed_out, int32_t * feature_out, int32_t * stack_max_out,
+                                                   const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask) {
+    const HostSigned sg = { side, signed_out, feature_out };
+    const HostMasks km = { object_masks, row_masks, row_mask };
+    return query_nearest_host(scene, points, n, channels, out, stack_max_out, &km, &sg);
+}
+extern "C" int rtxh_query_signed_distance_exhaustive(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out,
+                                                     const rtxh_side_blas * side, float * signed_out, int32_t * feature_out) {
+    const HostSigned sg = { side, signed_out, feature_out };
+    return query_nearest_exhaustive_host(scene, points, n, channels, out, kNoMasks, &sg);
+}
+extern "C" int rtxh_query_signed_distance_exhaustive_filtered(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out,
+                                                              const rtxh_side_blas * side, float * signed_out, int32_t * feature_out,
+                                                              const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask) {
+    const HostSigned sg = { side, signed_out, feature_out };
+    const HostMasks km = { object_masks, row_masks, row_mask };
+    return query_nearest_exhaustive_host(scene, points, n, channels, out, km, &sg);
 }
 
 extern "C" float rtxh_nearest_distance_bound(float local_scale, float world_scale) { return rtxnp::distance_bound(local_scale, world_scale); }
@@ -1260,6 +1321,45 @@ extern "C" int rtxh_vertex_normals(const float * positions, const int32_t * indi
         for (int k = 0; k < 3; k++) for (int a = 0; a < 3; a++) acc[3 * (size_t)tri[k] + a] += f[a];
     }
     for (int32_t v = 0; v < vertex_count; v++) rtxn::normalise(&acc[3 * (size_t)v], normals_out + 3 * (size_t)v);
+    return RTX_OK;
+}
+
+// ---- rtx_blas_pseudonormals on the host: csrc/rtx_side_math.h driven the OTHER way round — the device gathers per vertex and per slot edge
+// through the sorted inverted index, this is the plain loop over triangles and corners: the vertex sums are scattered, and the corner lists an
+// edge walks are filled by counting, both in ascending corner order.
+extern "C" int rtxh_blas_pseudonormals(const float * positions, const int32_t * indices, int32_t triangle_count, int32_t vertex_count,
+                                       const int32_t * slot_vertices, int32_t slots, float * vert_out, float * edge_out) {
+    if (!positions || !indices || triangle_count < 1 || vertex_count < 1 || slots < 0 || (slots && edge_out && !slot_vertices) || (!vert_out && !edge_out)) return RTX_ERR_INVALID_ARG;
+    const size_t T = (size_t)triangle_count, V = (size_t)vertex_count;
+    std::vector<float> rec(16 * T);
+    for (size_t t = 0; t < T; t++) rtxsd::triangle_record(indices, positions, (uint32_t)t, vertex_count, &rec[16 * t]);
+    if (vert_out) {
+        std::vector<float> acc(3 * V, 0.0f);
+        for (size_t t = 0; t < T; t++) {
+            const int32_t * const tri = indices + 3 * t;
+            if (!rtxn::valid_triangle(tri[0], tri[1], tri[2], vertex_count)) continue;
+            for (int k = 0; k < 3; k++) for (int a = 0; a < 3; a++) acc[3 * (size_t)tri[k] + a] += rec[16 * t + 4 + 4 * k + a];
+        }
+        for (size_t v = 0; v < V; v++) rtxsd::finish_sum(&acc[3 * v], vert_out + 4 * v);
+    }
+    if (edge_out && slots) {
+        std::vector<uint32_t> first(V + 1, 0u);                      // the corner lists: triangles in ascending corner order
+        for (size_t t = 0; t < T; t++) { const int32_t * const tri = indices + 3 * t; if (rtxn::valid_triangle(tri[0], tri[1], tri[2], vertex_count)) for (int k = 0; k < 3; k++) first[(size_t)tri[k] + 1]++; }
+        for (size_t v = 0; v < V; v++) first[v + 1] += first[v];
+        std::vector<uint32_t> fill(first.begin(), first.end() - 1), list(first[V]);
+        for (size_t t = 0; t < T; t++) { const int32_t * const tri = indices + 3 * t; if (rtxn::valid_triangle(tri[0], tri[1], tri[2], vertex_count)) for (int k = 0; k < 3; k++) list[fill[tri[k]]++] = (uint32_t)t; }
+        for (size_t e = 0; e < 3 * (size_t)slots; e++) {
+            int32_t x, y;
+            rtxsd::edge_vertices(slot_vertices + 3 * (e / 3), (int)(e % 3), x, y);
+            float s[3] = { 0.0f, 0.0f, 0.0f };
+            if (x >= 0 && x < vertex_count && y >= 0 && y < vertex_count)
+                for (uint32_t k = first[x]; k < first[x + 1]; k++) {
+                    const uint32_t t = list[k];
+                    if (rtxsd::has_vertex(indices + 3 * (size_t)t, y)) for (int a = 0; a < 3; a++) s[a] += rec[16 * (size_t)t + a];
+                }
+            rtxsd::finish_sum(s, edge_out + 4 * e);
+        }
+    }
     return RTX_OK;
 }
 

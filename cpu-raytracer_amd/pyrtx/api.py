@@ -30,7 +30,8 @@ EXPORTS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error", "rt
            "rtx_alloc_texture", "rtx_update_texture", "rtx_read_texture", "rtx_update_sky",
            "rtx_alloc_blas_topology", "rtx_set_blas_topology", "rtx_blas_vertex_normals", "rtx_query_nearest", "rtx_query_hits", "rtx_query_sweep",
            "rtx_debug_grids", "rtx_set_object_masks", "rtx_update_object_masks", "rtx_read_object_masks",
-           "rtx_query_nearest_filtered", "rtx_query_hits_filtered", "rtx_query_sweep_filtered"]
+           "rtx_query_nearest_filtered", "rtx_query_hits_filtered", "rtx_query_sweep_filtered",
+           "rtx_blas_pseudonormals", "rtx_read_blas_pseudonormals", "rtx_query_signed_distance"]
 # newer than the A/B variants tools/ab.py may load (RTX_HIP_LIB = a library built from an older commit): bound when the library has them,
 # otherwise a call raises AttributeError (undefined symbol)
 VIEW_EXPORTS = ("rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer")
@@ -45,13 +46,14 @@ LAYOUT_EXPORTS = ("rtx_debug_read_layouts",)
 TEXTURE_EXPORTS = ("rtx_alloc_texture", "rtx_update_texture", "rtx_read_texture", "rtx_update_sky")
 NORMALS_EXPORTS = ("rtx_alloc_blas_topology", "rtx_set_blas_topology", "rtx_blas_vertex_normals")
 NEAREST_EXPORTS = ("rtx_query_nearest",)
+SIGNED_EXPORTS = ("rtx_blas_pseudonormals", "rtx_read_blas_pseudonormals", "rtx_query_signed_distance")
 HITS_EXPORTS = ("rtx_query_hits",)
 SWEEP_EXPORTS = ("rtx_query_sweep",)
 GRID_EXPORTS = ("rtx_debug_grids",)
 MASK_EXPORTS = ("rtx_set_object_masks", "rtx_update_object_masks", "rtx_read_object_masks",
                 "rtx_query_nearest_filtered", "rtx_query_hits_filtered", "rtx_query_sweep_filtered")
 OPTIONAL_EXPORTS = (VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + QUERY_SORT_EXPORTS + LAYOUT_EXPORTS
-                    + TEXTURE_EXPORTS + NORMALS_EXPORTS + NEAREST_EXPORTS + HITS_EXPORTS + SWEEP_EXPORTS + GRID_EXPORTS + MASK_EXPORTS)
+                    + TEXTURE_EXPORTS + NORMALS_EXPORTS + NEAREST_EXPORTS + HITS_EXPORTS + SWEEP_EXPORTS + GRID_EXPORTS + MASK_EXPORTS + SIGNED_EXPORTS)
 RTX_QUERY_MAX_HITS = 8
 # texel formats of rtx_update_texture (include/rtx.h RTX_TEXELS_*)
 RTX_TEXELS_RGB_F32 = 0
@@ -202,6 +204,10 @@ def load_library(path: Optional[str] = None):
         lib.rtx_alloc_blas_topology.argtypes = [vp, i32, i32, i32]
         lib.rtx_set_blas_topology.argtypes = [vp, i32, vp]
         lib.rtx_blas_vertex_normals.argtypes = [vp, i32, vp, vp]
+    if hasattr(lib, "rtx_query_signed_distance"):
+        lib.rtx_blas_pseudonormals.argtypes = [vp, i32, vp]
+        lib.rtx_read_blas_pseudonormals.argtypes = [vp, i32, vp, vp]
+        lib.rtx_query_signed_distance.argtypes = [vp, vp, C.c_int64, u32, C.POINTER(RtxQueryBuffers), vp, vp, u32, C.POINTER(RtxQueryFilter)]
     for name in EXPORTS:
         if name in OPTIONAL_EXPORTS and not hasattr(lib, name):
             continue
@@ -930,6 +936,31 @@ class Renderer:
         self._chk(self.lib.rtx_blas_vertex_normals(self.ctx, int(blas_id), positions.data_ptr(), out.data_ptr()), "rtx_blas_vertex_normals")
         return out
 
+    # ---- pseudonormal tables (include/rtx.h: rtx_blas_pseudonormals / rtx_read_blas_pseudonormals) --------------------------------------
+    def blas_pseudonormals(self, blas_id: int, positions):
+        """The angle-weighted pseudonormal tables of the mesh under blas_id at the positions (V, 3) float32 torch tensor on this context's
+        GPU (or a raw device pointer), which query_signed_distance reads near edges and vertices.  Needs set_blas_topology (the SOURCE
+        indices) and bound slot vertices (bind_blas_vertices, or alloc_blas + build_blas), over the same V.  The first call for an id
+        allocates and may wait; later calls are queued on the context's stream and read nothing back.  The per-step idiom:
+        r.refit_blas(i, pos, r.vertex_normals(i, pos)); r.blas_pseudonormals(i, pos).  The tables are as current as the last call."""
+        if hasattr(positions, "data_ptr"):
+            T, V = getattr(self, "_topology_shapes", {}).get(int(blas_id), (None, None))
+            self._normals_tensor("positions", positions, "float32", V)
+            positions = positions.data_ptr()
+        self._chk(self.lib.rtx_blas_pseudonormals(self.ctx, int(blas_id), int(positions) if positions else None), "rtx_blas_pseudonormals")
+
+    def read_blas_pseudonormals(self, blas_id: int):
+        """The tables the kernels currently read (waits for the stream) -> (vert (V, 4), edge (slots, 3, 4)) float32: what
+        host.blas_pseudonormals computes from the same positions, indices and slot vertices, bit for bit."""
+        T, V = getattr(self, "_topology_shapes", {}).get(int(blas_id), (None, None))
+        if V is None or not (0 <= blas_id < len(self._blas_shapes)) or not self._blas_shapes[blas_id]:
+            self._chk(self.lib.rtx_read_blas_pseudonormals(self.ctx, int(blas_id), None, None), "rtx_read_blas_pseudonormals")
+            raise ValueError(f"BLAS {blas_id} has no topology set through this Renderer")
+        slots = self._blas_shapes[blas_id][1]
+        vert = np.zeros((V, 4), np.float32); edge = np.zeros((slots, 3, 4), np.float32)
+        self._chk(self.lib.rtx_read_blas_pseudonormals(self.ctx, int(blas_id), vert.ctypes.data, edge.ctypes.data), "rtx_read_blas_pseudonormals")
+        return vert, edge
+
     def read_blas(self, blas_id: int) -> sio.Blas:
         """The BLAS arrays the kernels currently read (waits for the stream): after upload what was uploaded, after refit_blas what the device
         wrote."""
@@ -1249,46 +1280,80 @@ class Renderer:
         its own; a row whose mask is 0 gets the no-answer values (rtx_query_*_filtered)."""
         return self._query_rows_to_channels("rtx_query_nearest", "points", points, 4, channels, out, n, sort, mask)
 
-    def _query_rows_to_channels(self, fn, label, rows, width, channels, out, n, sort, mask=None) -> Dict:
-        """query_nearest and query_sweep: rows of `width` floats in, one element of every requested channel per row out."""
-        names = query_names(channels)
+    def query_signed_distance(self, points, channels=(), out: Optional[Dict] = None, n: Optional[int] = None, sort: bool = False, mask=None,
+                              feature: bool = False) -> Dict:
+        """query_nearest with a sign (rtx_query_signed_distance): returns {"signed_distance": (n,) float32[, "feature": (n,) int32], and
+        the requested channels of query_nearest, bit for bit}.  The distance is negative where the point lies behind the surface: for a
+        closed, outward-oriented mesh inside it; for an open one (a cloth) below it.  The side is decided by the angle-weighted pseudonormal
+        of the face, edge or vertex that holds the nearest point (blas_pseudonormals makes the tables), so it is right near convex and
+        concave edges and vertices, where the nearest triangle's face normal is not.  Spheres are negative inside, planes on the side
+        their normal points away from; a row without an answer gets +inf; a point on the surface +0.  feature: 0 none, 1 face, 2 edge,
+        3 vertex, 4 sphere, 5 plane, + 8 when the winning mesh has no tables (the face rule everywhere).  The sign is relative to the object
+        that owns the nearest point, not to a union of overlapping solids.  Checked, shaped and queued like query_nearest; channels may be
+        empty.  out may hold "signed_distance" and "feature" tensors too.  Raw device pointers: points = address, n, out = {name: address}
+        for "signed_distance", for "feature" when wanted, and for every channel."""
+        return self._query_rows_to_channels("rtx_query_nearest", "points", points, 4, channels, out, n, sort, mask, signed={"feature": bool(feature)})
+
+    def _query_rows_to_channels(self, fn, label, rows, width, channels, out, n, sort, mask=None, signed=None) -> Dict:
+        """query_nearest and query_sweep: rows of `width` floats in, one element of every requested channel per row out.  signed (a dict):
+        query_signed_distance — the channels may be empty, and "signed_distance" (and "feature") come first in the result."""
+        if signed is not None and not isinstance(channels, (str, int, np.integer)) and len(tuple(channels)) == 0:
+            names = ()
+        else:
+            names = query_names(channels)
+        side = {} if signed is None else {"signed_distance": np.float32, **({"feature": np.int32} if signed["feature"] else {})}
+        if out is not None and isinstance(out, dict):
+            side_out = {k: out[k] for k in side if k in out}
+            out = {k: v for k, v in out.items() if k not in side}
+        else:
+            side_out = {}
         ptr, n, pts_t = self._query_rows(label, rows, width, n)
         if out is not None and not isinstance(out, dict):
             raise TypeError(f"out must be a dict {{channel name: tensor}}, not {type(out).__name__}")
         out = dict(out or {})
-        query_names(list(out) or names)
+        if out or names:
+            query_names(list(out) or names)
         extra = [k for k in out if k not in names]
         if extra:
             raise ValueError(f"out holds channels that were not requested: {', '.join(extra)}")
         raw = pts_t is None
-        if raw and len(out) != len(names):
+        if raw and (len(out) != len(names) or len(side_out) != len(side)):
             raise ValueError("with raw device pointers out must hold an address for every requested channel")
         fl = RTX_QUERY_SORT if sort else 0
         filt, mask_t = self._query_filter(mask, n)
+        side_ptr = {k: self._query_out(k, t, side[k], n, 1, raw) for k, t in side_out.items()}
         buf = RtxQueryBuffers()
         for name in out:
             _, dt, k = QUERY_CHANNELS[name]
             setattr(buf, name, self._query_out(name, out[name], dt, n, k, raw))
-        self._query_on_device({k: t for k, t in [(label, pts_t)] + [(f"out[{k!r}]", t) for k, t in out.items()] if hasattr(t, "device")})
+        self._query_on_device({k: t for k, t in [(label, pts_t)] + [(f"out[{k!r}]", t) for k, t in list(out.items()) + list(side_out.items())] if hasattr(t, "device")})
         for name in names:
             if name not in out:
                 import torch
                 _, dt, k = QUERY_CHANNELS[name]
                 out[name] = torch.empty((n, k) if k > 1 else (n,), dtype=torch.float32 if dt == np.float32 else torch.int32, device=pts_t.device)
                 setattr(buf, name, out[name].data_ptr())
+        for name, dt in side.items():
+            if name not in side_out:
+                import torch
+                side_out[name] = torch.empty((n,), dtype=torch.float32 if dt == np.float32 else torch.int32, device=pts_t.device)
+                side_ptr[name] = side_out[name].data_ptr()
         bits = sum(QUERY_CHANNELS[name][0] for name in names)
 
         def launch():
-            if filt is None:
+            if signed is not None:
+                self._chk(self.lib.rtx_query_signed_distance(self.ctx, ptr, n, bits, C.byref(buf), side_ptr["signed_distance"], side_ptr.get("feature"), fl,
+                                                             None if filt is None else C.byref(filt)), "rtx_query_signed_distance")
+            elif filt is None:
                 self._chk(getattr(self.lib, fn)(self.ctx, ptr, n, bits, C.byref(buf), fl), fn)
             else:
                 self._chk(getattr(self.lib, fn + "_filtered")(self.ctx, ptr, n, bits, C.byref(buf), fl, C.byref(filt)), fn + "_filtered")
-        tensors = [t for t in [pts_t, mask_t] + list(out.values()) if hasattr(t, "record_stream")]
+        tensors = [t for t in [pts_t, mask_t] + list(out.values()) + list(side_out.values()) if hasattr(t, "record_stream")]
         if tensors:
             self._on_torch_stream(launch, tensors)
         else:
             launch()
-        return {name: out[name] for name in names}
+        return {**{name: side_out[name] for name in side}, **{name: out[name] for name in names}}
 
     def query_sweep(self, sweeps, channels=("distance",), out: Optional[Dict] = None, n: Optional[int] = None, sort: bool = False, mask=None) -> Dict:
         """The first contact of n moving balls with the frame the context holds (rtx_query_sweep): sweeps = float32 torch tensor (n, 8) of

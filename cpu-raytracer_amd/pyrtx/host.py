@@ -27,7 +27,8 @@ EXPORTS = ["rtxh_camera_basis", "rtxh_camera_update", "rtxh_quaternion_axis_angl
            "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2", "rtxh_query_hits", "rtxh_query_hits_exhaustive", "rtxh_hits_margin",
            "rtxh_query_sweep", "rtxh_query_sweep_exhaustive", "rtxh_sweep_bound", "rtxh_sweep_triangle", "rtxh_sweep_sphere", "rtxh_sweep_plane",
            "rtxh_query_nearest_filtered", "rtxh_query_nearest_exhaustive_filtered", "rtxh_query_hits_filtered", "rtxh_query_hits_exhaustive_filtered",
-           "rtxh_query_sweep_filtered", "rtxh_query_sweep_exhaustive_filtered"]
+           "rtxh_query_sweep_filtered", "rtxh_query_sweep_exhaustive_filtered", "rtxh_blas_pseudonormals",
+           "rtxh_query_signed_distance", "rtxh_query_signed_distance_filtered", "rtxh_query_signed_distance_exhaustive", "rtxh_query_signed_distance_exhaustive_filtered"]
 FLOAT_EXPORTS = ("rtxh_nearest_distance_bound", "rtxh_nearest_box_d2", "rtxh_nearest_triangle_d2", "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2", "rtxh_hits_margin", "rtxh_sweep_bound")      # return a float, not a status
 
 PI = np.float32(3.14159265359)          # Util.h:8
@@ -57,6 +58,10 @@ class RtxhNearestScene(C.Structure):
                 ("spheres", C.c_void_p), ("planes", C.c_void_p),
                 ("instance_count", C.c_int32), ("tlas_node_count", C.c_int32), ("tlas_index_count", C.c_int32), ("blas_count", C.c_int32),
                 ("sphere_count", C.c_int32), ("plane_count", C.c_int32)]
+
+
+class RtxhSideBlas(C.Structure):
+    _fields_ = [("vert_pn", C.c_void_p), ("edge_pn", C.c_void_p), ("slot_vertices", C.c_void_p), ("vertex_count", C.c_int32), ("pad", C.c_int32)]
 
 
 TEXNAME_MAX = 512
@@ -128,6 +133,12 @@ def lib():
         l.rtxh_query_hits_exhaustive_filtered.argtypes = l.rtxh_query_hits_exhaustive.argtypes + masks3
         l.rtxh_query_sweep_filtered.argtypes = l.rtxh_query_sweep.argtypes + masks3
         l.rtxh_query_sweep_exhaustive_filtered.argtypes = l.rtxh_query_sweep_exhaustive.argtypes + masks3
+        l.rtxh_blas_pseudonormals.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp]
+        side3 = [C.POINTER(RtxhSideBlas), vp, vp]                  # side, signed_out, feature_out
+        l.rtxh_query_signed_distance.argtypes = l.rtxh_query_nearest.argtypes[:5] + side3 + [C.POINTER(i32)]
+        l.rtxh_query_signed_distance_exhaustive.argtypes = l.rtxh_query_nearest_exhaustive.argtypes[:5] + side3
+        l.rtxh_query_signed_distance_filtered.argtypes = l.rtxh_query_signed_distance.argtypes + masks3
+        l.rtxh_query_signed_distance_exhaustive_filtered.argtypes = l.rtxh_query_signed_distance_exhaustive.argtypes + masks3
         l.rtxh_sweep_bound.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float]
         l.rtxh_sweep_triangle.argtypes = [vp, vp, C.c_float, C.c_float, vp, vp, vp, vp]
         l.rtxh_sweep_sphere.argtypes = [vp, vp, C.c_float, vp, vp, vp]
@@ -390,6 +401,23 @@ def vertex_normals(positions, indices) -> np.ndarray:
     return out
 
 
+def blas_pseudonormals(positions, indices, slot_vertices):
+    """rtxh_blas_pseudonormals: the angle-weighted pseudonormal tables that Renderer.blas_pseudonormals writes on the device (csrc/
+    rtx_side_math.h), from positions (V, 3), the SOURCE indices (T, 3) and the slot -> vertex table (slots, 3) of the BLAS (-1: a pad slot)
+    -> (vert (V, 4), edge (slots, 3, 4)) float32: per vertex the sum of angle * unit face normal over its corners, per slot edge ab, bc,
+    ac the sum of the unit normals of the faces at the edge; w is 0."""
+    pos = _f32(positions).reshape(-1, 3)
+    idx = np.ascontiguousarray(indices, np.int32).reshape(-1, 3)
+    sv = np.ascontiguousarray(slot_vertices, np.int32).reshape(-1, 3)
+    vert = np.zeros((len(pos), 4), np.float32)
+    edge = np.zeros((len(sv), 3, 4), np.float32)
+    rc = lib().rtxh_blas_pseudonormals(pos.ctypes.data, idx.ctypes.data, len(idx), len(pos), sv.ctypes.data if len(sv) else None, len(sv), vert.ctypes.data,
+                                       edge.ctypes.data if len(sv) else None)
+    if rc:
+        raise ValueError(f"rtxh_blas_pseudonormals failed with status {rc}")
+    return vert, edge
+
+
 def blas_balanced_node_count(n: int) -> int:
     """Node slots of the balanced BLAS of n triangles (2 << L, L the first level with ceil(n / 2^L) <= 4; holes and index 1 included); 0
     outside 1 .. 2^24 - 1."""
@@ -574,14 +602,35 @@ def _filter_args(s, n, mask, object_masks):
     return [optr, rptr, scalar], keep
 
 
-def _query_nearest(fn_name, scene, points, channels, blas, with_stack, width=4, label="points", mask=None, object_masks=None):
+def _side_table(blas_count, pseudonormals, slot_vertices):
+    """The rtxh_side_blas array of a signed query: pseudonormals = {blas_id: (vert, edge)} or {blas_id: (vert, edge, slot_vertices)};
+    slot_vertices = {blas_id: (slots, 3) int32} for the two-element form.  A mesh without an entry has no tables."""
+    table = (RtxhSideBlas * max(1, blas_count))()
+    keep = [table]
+    for b, rec in (pseudonormals or {}).items():
+        if not 0 <= int(b) < blas_count:
+            raise ValueError(f"pseudonormals names BLAS {b}, the scene has {blas_count}")
+        sv = rec[2] if len(rec) > 2 else (slot_vertices or {}).get(b)
+        if sv is None:
+            raise ValueError(f"pseudonormals[{b}] needs the slot -> vertex table: (vert, edge, slot_vertices)")
+        vert, edge, sv = _f32(rec[0]).reshape(-1, 4), _f32(rec[1]).reshape(-1, 4), np.ascontiguousarray(sv, np.int32).reshape(-1, 3)
+        if len(edge) != 3 * len(sv):
+            raise ValueError(f"pseudonormals[{b}]: edge holds {len(edge)} records, slot_vertices {len(sv)} slots")
+        keep += [vert, edge, sv]
+        table[int(b)] = RtxhSideBlas(vert.ctypes.data, edge.ctypes.data, sv.ctypes.data, len(vert), 0)
+    return table, keep
+
+
+def _query_nearest(fn_name, scene, points, channels, blas, with_stack, width=4, label="points", mask=None, object_masks=None, signed=None):
     pts = np.asarray(points)
     if pts.ndim != 2 or pts.shape[1] != width or pts.shape[0] < 1:
         raise ValueError(f"{label} must have shape (n, {width}) with n >= 1, not {pts.shape}")
     if pts.dtype != np.float32:
         raise TypeError(f"{label} must be float32, not {pts.dtype}")
     pts = np.ascontiguousarray(pts)
-    names = _nearest_names(channels)
+    scalar = isinstance(channels, (str, int, np.integer))
+    empty = signed is not None and (channels is None or (not scalar and len(channels) == 0) or (scalar and not isinstance(channels, (str, bool)) and int(channels) == 0))
+    names = () if empty else _nearest_names(channels)          # a signed query may ask for no channel
     s, keep = nearest_scene(scene, blas)
     n = pts.shape[0]
     out = {name: np.zeros((n, NEAREST_CHANNELS[name][2]) if NEAREST_CHANNELS[name][2] > 1 else (n,), NEAREST_CHANNELS[name][1]) for name in names}
@@ -591,7 +640,14 @@ def _query_nearest(fn_name, scene, points, channels, blas, with_stack, width=4, 
     bits = sum(NEAREST_CHANNELS[name][0] for name in names)
     high = C.c_int32(0)
     filt = _filter_args(s, n, mask, object_masks)
-    args = [C.byref(s), pts.ctypes.data, n, bits, C.byref(buf)] + ([C.byref(high)] if with_stack else [])
+    args = [C.byref(s), pts.ctypes.data, n, bits, C.byref(buf)]
+    if signed is not None:
+        table, keep_side = _side_table(s.blas_count, signed.get("pseudonormals"), signed.get("slot_vertices"))
+        out["signed_distance"] = np.zeros(n, np.float32)
+        if signed.get("feature", True):
+            out["feature"] = np.zeros(n, np.int32)
+        args += [table, out["signed_distance"].ctypes.data, out["feature"].ctypes.data if "feature" in out else None]
+    args += [C.byref(high)] if with_stack else []
     if filt:
         fn_name += "_filtered"
         args += filt[0]
@@ -616,6 +672,21 @@ def query_nearest(scene, points, channels=("distance",), blas=None, mask=None, o
 def query_nearest_exhaustive(scene, points, channels=("distance",), blas=None, mask=None, object_masks=None) -> dict:
     """rtxh_query_nearest_exhaustive: the same candidate functions over every primitive, no tree; ties to the lowest (kind, object, slot)."""
     return _query_nearest("rtxh_query_nearest_exhaustive", scene, points, channels, blas, False, mask=mask, object_masks=object_masks)
+
+
+def query_signed_distance(scene, points, channels=(), blas=None, pseudonormals=None, mask=None, object_masks=None, feature=True, slot_vertices=None,
+                          exhaustive=False) -> dict:
+    """rtxh_query_signed_distance: what Renderer.query_signed_distance writes on the device -> {"signed_distance": (n,) f32, "feature":
+    (n,) i32 (feature=True), channel: array ..., "stack_max"}.  pseudonormals = {blas_id: (vert, edge, slot_vertices)} — the tables of
+    blas_pseudonormals or Renderer.read_blas_pseudonormals and the slot -> vertex table they were made with (or (vert, edge) with
+    slot_vertices = {blas_id: table}); a mesh without an entry has no tables: feature + 8, the naive face rule.  channels may be empty.
+    exhaustive=True: rtxh_query_signed_distance_exhaustive, the search without a tree.
+    The slot -> vertex table is part of every entry because a vertex-region lookup goes through it and a scene_io.Blas does not carry it:
+    a bare (vert, edge) — what Renderer.read_blas_pseudonormals returns — is not enough on its own and raises a ValueError unless
+    slot_vertices= supplies the table; append it, read_blas_pseudonormals(b) + (slot_vertices_b,), as the GPU tests do."""
+    sg = {"pseudonormals": pseudonormals, "slot_vertices": slot_vertices, "feature": feature}
+    name = "rtxh_query_signed_distance_exhaustive" if exhaustive else "rtxh_query_signed_distance"
+    return _query_nearest(name, scene, points, channels, blas, not exhaustive, mask=mask, object_masks=object_masks, signed=sg)
 
 
 # ---- all-hits segment queries on the host (include/rtx_host.h: rtxh_query_hits / rtxh_query_hits_exhaustive) ------------------------------

@@ -572,6 +572,32 @@ int rtx_alloc_blas_topology(rtx_ctx * ctx, int32_t blas_id, int32_t triangle_cou
 int rtx_set_blas_topology(rtx_ctx * ctx, int32_t blas_id, const void * indices_dev);
 int rtx_blas_vertex_normals(rtx_ctx * ctx, int32_t blas_id, const void * positions_dev, void * normals_out_dev);
 
+/* ---- pseudonormal tables: the sign of a distance -----------------------------------------------------------------------------------------
+ * What rtx_query_signed_distance (below) needs of a mesh to tell the two sides of its surface apart near edges and vertices, where the face
+ * normal of the nearest triangle is wrong: the angle-weighted pseudonormals of Baerentzen and Aanaes (2005) — per vertex the sum of the unit
+ * normals of its faces weighted by their corner angles, per edge the sum of the unit normals of the faces at the edge.  Computed on the
+ * context's stream from positions in DEVICE memory, over the topology of rtx_set_blas_topology (the SOURCE index buffer) and the slot ->
+ * vertex table of rtx_bind_blas_vertices / rtx_alloc_blas + rtx_build_blas.  Bit-reproducible — no float atomics: per-triangle records are
+ * stored, then summed per vertex and per slot edge in ascending corner order — and bit-identical to rtxh_blas_pseudonormals (rtx_host.h).
+ * The arithmetic (FACE, ANGLE, VERTEX, EDGE) is specified in the header comment of csrc/rtx_side_math.h.
+ *
+ * rtx_blas_pseudonormals, per step, after the positions of the mesh changed (r.refit_blas, then this): positions vertex_count x 3 f32 at any
+ * 4-byte aligned address, read when the work runs.  The first call for an id allocates the tables (64 bytes per source triangle, 16 per
+ * vertex, 48 per triangle slot) and may wait for the stream; a refused allocation changes nothing.  Later calls only queue three kernels, read
+ * nothing back and move no pointer.  The tables are as current as the last call: a refit or a build without it leaves them stale (and, after
+ * a build, indexed by the slots of the previous build) — the contract the vertex normals have.  rtx_upload_blas or rtx_alloc_blas over the
+ * id, and rtx_alloc_blas_topology over the id, drop the tables: the mesh then has none (feature + 8) until the next call.  Checked in this
+ * order, nothing is queued on an error: RTX_ERR_INVALID_ARG for a null ctx, a null or misaligned pointer; RTX_ERR_STATE for an id without an
+ * allocated topology; RTX_ERR_STATE when no rtx_set_blas_topology has been queued since the alloc; RTX_ERR_STATE when no vertices are bound to
+ * the id; RTX_ERR_INVALID_ARG when the topology's vertex_count is not the bound one; then RTX_ERR_OOM / RTX_ERR_HIP of the first call's
+ * allocation.
+ *
+ * rtx_read_blas_pseudonormals (waits for the stream): vert_out vertex_count x 4 floats, edge_out slots x 3 x 4 floats (edge ab, bc, ac of
+ * every triangle slot; w of every record is 0); either may be NULL.  RTX_ERR_INVALID_ARG for a null ctx, a bad id or two null outputs;
+ * RTX_ERR_STATE for an id without tables.                                                                                              */
+int rtx_blas_pseudonormals(rtx_ctx * ctx, int32_t blas_id, const void * positions_dev /* [V][3] f32 */);
+int rtx_read_blas_pseudonormals(rtx_ctx * ctx, int32_t blas_id, float * vert_out /* [V][4] */, float * edge_out /* [slots][3][4] */);
+
 /* ---- device-side texture and sky update -----------------------------------------------------------------------------------------------
  * What the surfaces look like, with the texels in DEVICE memory: a render shown on a screen or a portal inside the scene (a view
  * framebuffer is [h][w][3] f32 in linear light), a decoded video frame, a generated albedo, an animated environment probe.  update -> render
@@ -727,13 +753,14 @@ int rtx_debug_query_order(rtx_ctx * ctx, const void * rows_dev, int32_t row_floa
  * Limits: distances are measured in each instance's LOCAL space — for the rigid poses Mesh::update and rtx_update_instances make from unit
  * quaternions that is the world metric up to rounding; a scaled world matrix handed to rtx_set_frame is measured in its local units.  The
  * answer may depend on the tree within the bound: a refit, or a rebuild of the same triangles, may return another triangle at an equal
- * or nearly equal distance.  Out of scope: signed distance, k nearest, all within a radius, barycentrics, the rtx_group_* path.        */
+ * or nearly equal distance.  The side of the surface: rtx_query_signed_distance, below.  Out of scope: k nearest, all within a radius,
+ * barycentrics, the rtx_group_* path.                                                                                                    */
 int rtx_query_nearest(rtx_ctx * ctx, const void * points_dev /* [n][4] f32: x, y, z, maximum distance */, int64_t n,
                       uint32_t channels, const rtx_query_buffers * out, uint32_t flags);
 
 /* ---- all-hits segment queries ----------------------------------------------------------------------------------------------------------
  * "Everything this segment crosses": the nearest max_hits hits of every row in order, and how many there were.  For inside / outside by
- * crossing parity (with rtx_query_nearest: the sign of the distance), thickness and penetration depth as entry / exit pairs, multi-echo
+ * crossing parity (the sign of the distance in one call, open surfaces included: rtx_query_signed_distance), thickness and penetration depth as entry / exit pairs, multi-echo
  * lidar and depth peeling (the 2nd, 3rd, ... return), the number of surfaces between two points.  rtx_query_hits: row i =
  * segments_dev[7i .. 7i+6] = (origin, direction, max distance D), the rows of rtx_query_occluded, fp32 at any 4-byte aligned address in
  * DEVICE memory; the scene is the frame the context holds, device-side updates included.  Queued on the context's stream, returns at once,
@@ -856,6 +883,31 @@ int rtx_query_hits_filtered(rtx_ctx * ctx, const void * segments_dev, int64_t n,
                             int32_t * count_dev, uint32_t flags, const rtx_query_filter * filter);
 int rtx_query_sweep_filtered(rtx_ctx * ctx, const void * sweeps_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags,
                              const rtx_query_filter * filter);
+
+/* ---- signed-distance queries ------------------------------------------------------------------------------------------------------------
+ * "On which side of the surface is this point": rtx_query_nearest with a sign.  rtx_query_signed_distance walks the rows exactly as
+ * rtx_query_nearest / rtx_query_nearest_filtered do (filter NULL: unfiltered) and writes the channels of the same call bit for bit — channels
+ * may be 0, and then out may be NULL — plus signed_dev[i] (required): the distance of row i, NEGATIVE iff r . N < 0, where r is the vector
+ * from the nearest surface point to the row's point and N the pseudonormal of the feature of the nearest triangle that holds that point: the
+ * face normal e1 x e2 of the slot, the edge's or the vertex's record of the tables rtx_blas_pseudonormals made.  r . N == 0, a zero N and a
+ * NaN are positive; a point on the surface gets +0.  Both vectors are in the instance's local space, so rigid, scaled and mirrored instances
+ * need nothing more.  A sphere is negative inside (l < r with the two roots of its distance), a plane where n.p + distance < 0.  A row
+ * without an answer gets +INFINITY.  feature_dev[i] (or NULL): 0 none, 1 face, 2 edge, 3 vertex, 4 sphere, 5 plane; + 8 when the winning
+ * mesh has no tables — then e1 x e2 is used in every region, the naive rule, which is wrong near convex and concave edges and vertices.
+ * For a closed, consistently oriented mesh negative is inside; for an open one it is the side the orientation calls back.  The sign rule is
+ * specified in the header comment of csrc/rtx_side_math.h (SIDE, FEATURE, LIMITS); rtxh_query_signed_distance in rtx_host.h gives the same
+ * bits.  One launch per round, the walk's kernel; after the walk the winner's matrix and three 16-byte hot loads, the region chain, then the
+ * mesh's 32-byte table entry and, behind it, one record (an edge) or a slot vertex and its record (a vertex): up to three dependent loads.
+ * Errors, in this order: RTX_ERR_INVALID_ARG: a NULL ctx; channels with bits outside RTX_QUERY_ALL; a NULL or misaligned signed_dev, a
+ * misaligned feature_dev; a NULL points_dev, a NULL out with channels != 0, n < 1; any flag but RTX_QUERY_SORT.  Then RTX_ERR_STATE and
+ * RTX_ERR_LIMIT as for rtx_query_nearest, its stack rule included, and the state rule of the filtered queries.  An error queues nothing.
+ * Limits: the sign is relative to the OBJECT that owns the nearest point — for overlapping solids it is not the sign of their union.  Within
+ * the accuracy bound of rtx_query_nearest of a surface, and where r is within rounding of perpendicular to N, the sign is not determined.
+ * Out of scope: signed sweeps, generalized winding numbers, the sign of a union, the rtx_group_* path.                                    */
+int rtx_query_signed_distance(rtx_ctx * ctx, const void * points_dev /* [n][4] f32 */, int64_t n, uint32_t channels /* may be 0 */,
+                              const rtx_query_buffers * out /* may be NULL iff channels == 0 */, float * signed_dev /* [n], required */,
+                              int32_t * feature_dev /* [n] or NULL */, uint32_t flags /* RTX_QUERY_SORT or 0 */,
+                              const rtx_query_filter * filter /* NULL: unfiltered */);
 
 /* Timing of every kernel launched since rtx_enable_kernel_timing(ctx, 1),
  * measured with HIP events on the stream the kernels are launched on.

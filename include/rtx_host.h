@@ -41,6 +41,8 @@
  *                            rtxh_query_nearest_exhaustive the same candidate functions over every primitive, without a tree
  *   rtxh_query_sweep         rtx_query_sweep on the host: the walk and the arithmetic of csrc/rtx_sweep_math.h over the same arrays;
  *   rtxh_query_*_filtered    the three walk queries under object masks (rtx_query_*_filtered), and their exhaustive searches over the visible primitives
+ *   rtxh_blas_pseudonormals  rtx_blas_pseudonormals on the host: the angle-weighted pseudonormal tables of csrc/rtx_side_math.h as a plain loop;
+ *   rtxh_query_signed_distance  rtx_query_signed_distance on the host (and its _exhaustive / _filtered forms): rtxh_query_nearest with the sign
  *   rtxh_query_hits          rtx_query_hits on the host: the walk and the arithmetic of csrc/rtx_hits_math.h over the same arrays;
  *                            rtxh_query_hits_exhaustive the same hit tests over every primitive, without a box test
  *   rtxh_texture_load        Texture::load: PNG / TGA file -> linear float3 texels + mips   Texture.cpp:30-129
@@ -283,6 +285,31 @@ int rtxh_query_sweep_filtered(const rtxh_nearest_scene * scene, const float * sw
                               const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask);
 int rtxh_query_sweep_exhaustive_filtered(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, uint32_t channels, const rtx_query_buffers * out,
                                          const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask);
+
+/* rtx_blas_pseudonormals (include/rtx.h) on the host, by the code the kernels run (csrc/rtx_side_math.h, whose header comment is the
+ * specification: FACE, ANGLE, VERTEX, EDGE): the angle-weighted pseudonormal tables of an indexed mesh — positions V*3, indices T*3 (the SOURCE
+ * topology; an index outside [0, V) makes a triangle invalid), slot_vertices slots*3 (the vertices of every triangle slot of the BLAS, -1 for a
+ * pad slot), vert_out V*4, edge_out slots*3*4 (either may be NULL; w of every record is 0).  Written as the plain loop over triangles and
+ * corners, where the device gathers through a sorted inverted index: the same additions in the same order, the same bits.  No output
+ * component is NaN or infinite.  RTX_ERR_INVALID_ARG: a null pointer that is needed, T < 1, V < 1, slots < 0, nothing to write.            */
+int rtxh_blas_pseudonormals(const float * positions, const int32_t * indices, int32_t triangle_count, int32_t vertex_count,
+                            const int32_t * slot_vertices, int32_t slots, float * vert_out, float * edge_out);
+/* rtx_query_signed_distance (include/rtx.h) on the host: rtxh_query_nearest (or its _exhaustive / _filtered forms), then SIDE of
+ * csrc/rtx_side_math.h for every row's winner — the device's bits.  side: one rtxh_side_blas per BLAS id of the scene (tables as
+ * rtxh_blas_pseudonormals or rtx_read_blas_pseudonormals give them; a null pointer in an entry: that mesh has no tables, feature + 8), or
+ * NULL: no mesh has tables.  signed_out: n floats, required; feature_out: n codes or NULL.  channels may be 0, and then out may be NULL.
+ * Errors otherwise as for the function it extends.                                                                                       */
+typedef struct rtxh_side_blas { const float * vert_pn; const float * edge_pn; const int32_t * slot_vertices; int32_t vertex_count, pad; } rtxh_side_blas;
+int rtxh_query_signed_distance(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out,
+                               const rtxh_side_blas * side, float * signed_out, int32_t * feature_out, int32_t * stack_max_out);
+int rtxh_query_signed_distance_filtered(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out,
+                                        const rtxh_side_blas * side, float * signed_out, int32_t * feature_out, int32_t * stack_max_out,
+                                        const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask);
+int rtxh_query_signed_distance_exhaustive(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out,
+                                          const rtxh_side_blas * side, float * signed_out, int32_t * feature_out);
+int rtxh_query_signed_distance_exhaustive_filtered(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out,
+                                                   const rtxh_side_blas * side, float * signed_out, int32_t * feature_out,
+                                                   const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask);
 
 /* Texture::load (Texture.cpp:30-129): decodes a .png or .tga file the way the reference's vendored stb_image v2.19 does with
  * STBI_rgb_alpha (Texture.cpp:40), converts r,g,b bytes to linear light (colour_unpack :13-20, Math::gamma_to_linear Math.h:67-77;
