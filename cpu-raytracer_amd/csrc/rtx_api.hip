@@ -300,6 +300,7 @@ extern "C" int rtx_create(const rtx_config * config, rtx_ctx ** out_ctx) {
       const double f = knob_real("RTX_ITEM_GRID", 0.0, 0.05, 64.0); if (f > 0.0) c->item_blocks = (int)(c->n_cu * f) > 0 ? (int)(c->n_cu * f) : 1; }
     c->q.pk_items = nullptr; c->q.pk_item_count = nullptr; c->q.pk_item_cap = 0;      // sized per render call (render_tiles_impl)
     if (rc) { rtx_destroy(c); return rc; }
+    bind_tables(c);                      // the default material and sky; from here on every change of a table rebinds (replace_table)
     *out_ctx = c;
     return RTX_OK;
 }
@@ -357,14 +358,10 @@ template <typename T> static int stage_array(rtx_ctx * c, std::vector<DevBuf> & 
     return RTX_OK;
 }
 
-// the device table follows h_blas.  A table that has to grow is built beside the old one, which a failure leaves in place.
-static int upload_blas_table(rtx_ctx * c) {
-    const size_t bytes = c->h_blas.size() * sizeof(DevBlas);
-    if (bytes <= c->d_blas.cap && c->d_blas.p) return upload(c, c->d_blas, c->h_blas.data(), bytes);
-    DevBuf nb;
-    if (int rc = upload(c, nb, c->h_blas.data(), bytes)) return rc;
-    c->d_blas = std::move(nb);
-    return RTX_OK;
+// the device table and h_blas become `table` (replace_table: a table that has to grow is built beside the old one, which a failure leaves in
+// place, and the scene is bound to what the context then holds); accept() is the rest of the host state that changes with it
+template <typename Accept> static int upload_blas_table(rtx_ctx * c, std::vector<DevBlas> & table, Accept && accept) {
+    return replace_table(c, c->d_blas, table.data(), table.size() * sizeof(DevBlas), [&] { c->h_blas.swap(table); accept(); });
 }
 
 // the id has no pseudonormal tables (any more): the next signed query uploads the entry before it launches, and none is queued now — every
@@ -374,18 +371,17 @@ static void drop_side_entry(rtx_ctx * c, int32_t blas_id) {
 }
 
 // The one place an id's state changes hands.  Queued work may still read the old arrays and the table: it is waited for explicitly, then the
-// table is uploaded with the new entry, and only then does the old record — arrays, refit plan, build scratch — go.
+// table is uploaded with the new entry (replace_table does both), and only then does the old record — arrays, refit plan, build scratch — go.
 static int commit_blas(rtx_ctx * c, int32_t blas_id, BlasStaged & S) {
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    const size_t had = c->h_blas.size();
-    if ((size_t)blas_id >= had) { DevBlas none; memset(&none, 0, sizeof(none)); c->h_blas.resize(blas_id + 1, none); c->blas.resize(blas_id + 1); }
-    const DevBlas old = c->h_blas[blas_id];
-    c->h_blas[blas_id] = S.B;
-    if (int rc = upload_blas_table(c)) { c->h_blas[blas_id] = old; c->h_blas.resize(had); c->blas.resize(had); return rc; }
-    c->blas[blas_id] = std::move(S.H);
-    c->refs_dirty = true;
-    drop_side_entry(c, blas_id);                                    // the pseudonormal tables went with the old record
-    return RTX_OK;
+    std::vector<DevBlas> table = c->h_blas;
+    if ((size_t)blas_id >= table.size()) { DevBlas none; memset(&none, 0, sizeof(none)); table.resize(blas_id + 1, none); }
+    table[blas_id] = S.B;
+    return upload_blas_table(c, table, [&] {
+        if (c->blas.size() < c->h_blas.size()) c->blas.resize(c->h_blas.size());
+        c->blas[blas_id] = std::move(S.H);
+        c->refs_dirty = true;
+        drop_side_entry(c, blas_id);                                // the pseudonormal tables went with the old record
+    });
 }
 
 // All checks, then all allocations and copies, into S; the context is only read.
@@ -459,25 +455,27 @@ extern "C" int rtx_upload_materials(rtx_ctx * c, const rtx_material * materials,
     if (!c || !materials || count <= 0) return RTX_ERR_INVALID_ARG;
     if (count > RTX_MAX_MATERIALS) return RTX_ERR_LIMIT;       // "Max Material limit reached!" Material.h:33-37
     hipSetDevice(c->cfg.device);
-    c->material_count = count;
-    c->h_materials.assign(materials, materials + count); c->refs_dirty = true;
-    return upload(c, c->d_materials, materials, (size_t)count * sizeof(rtx_material));
+    return replace_table(c, c->d_materials, materials, (size_t)count * sizeof(rtx_material), [&] {
+        c->material_count = count;
+        c->h_materials.assign(materials, materials + count); c->refs_dirty = true;
+    });
 }
 
 // texture_id now holds the texel array d with the descriptor desc: rtx_upload_texture and rtx_alloc_texture end here
 static int commit_texture(rtx_ctx * c, int32_t texture_id, const rtx_texture_desc & desc, DevBuf & d, const rtx_ctx::TexUpdate & update) {
-    if ((size_t)texture_id >= c->h_tex.size()) {
-        const size_t old = c->h_tex.size();
-        c->h_tex.resize(texture_id + 1); c->tex_texels.resize(texture_id + 1); c->tex_update.resize(texture_id + 1);
-        for (size_t i = old; i < c->h_tex.size(); i++) memset(&c->h_tex[i], 0, sizeof(DevTexture));
-    }
-    if (c->h_tex[texture_id].texels) HIP_OK(c, hipStreamSynchronize(c->stream));      // re-upload of an id: the old texel array is released after the frames that may still read it
-    c->h_tex[texture_id].desc = desc;
-    c->h_tex[texture_id].texels = (const float4 *)d.p;
-    c->tex_texels[texture_id] = std::move(d);
-    c->tex_update[texture_id] = update;
-    c->refs_dirty = true;
-    return upload(c, c->d_textures, c->h_tex.data(), c->h_tex.size() * sizeof(DevTexture));
+    std::vector<DevTexture> table = c->h_tex;
+    if ((size_t)texture_id >= table.size()) { DevTexture none; memset(&none, 0, sizeof(none)); table.resize(texture_id + 1, none); }
+    table[texture_id].desc = desc;
+    table[texture_id].texels = (const float4 *)d.p;
+    // replace_table waits for the stream first: the table is rewritten, and on a re-upload of an id the old texel array is released, after
+    // the frames that may still read them
+    return replace_table(c, c->d_textures, table.data(), table.size() * sizeof(DevTexture), [&] {
+        c->h_tex.swap(table);
+        if (c->tex_texels.size() < c->h_tex.size()) { c->tex_texels.resize(c->h_tex.size()); c->tex_update.resize(c->h_tex.size()); }
+        c->tex_texels[texture_id] = std::move(d);
+        c->tex_update[texture_id] = update;
+        c->refs_dirty = true;
+    });
 }
 
 extern "C" int rtx_upload_texture(rtx_ctx * c, int32_t texture_id, const rtx_texture_desc * desc, const float * texels_rgb, int64_t texel_count) {
@@ -503,10 +501,7 @@ extern "C" int rtx_upload_sky(rtx_ctx * c, const float * texels_rgb, int32_t siz
     // Sky::sample clamps the texel index to size*size INCLUSIVE (Sky.cpp:45): one zero texel of padding
     std::vector<float> padded((size_t)size * size * 3 + 3, 0.0f);
     memcpy(padded.data(), texels_rgb, (size_t)size * size * 12);
-    c->sky_size = size;
-    if (int rc = upload(c, c->d_sky, padded.data(), padded.size() * 4)) return rc;
-    c->sky_uploaded = true;
-    return RTX_OK;
+    return replace_table(c, c->d_sky, padded.data(), padded.size() * 4, [&] { c->sky_size = size; c->sky_uploaded = true; });
 }
 
 extern "C" int rtx_set_frame(rtx_ctx * c, const rtx_frame * f) {
@@ -556,10 +551,7 @@ extern "C" int rtx_set_frame(rtx_ctx * c, const rtx_frame * f) {
     memcpy(s.cam_pos, f->camera.position, 12); memcpy(s.cam_tl, f->camera.rotated_top_left_corner, 12);
     memcpy(s.cam_x, f->camera.rotated_x_axis, 12); memcpy(s.cam_y, f->camera.rotated_y_axis, 12);
     memcpy(s.ambient, f->ambient, 12);
-    s.blas = (const DevBlas *)c->d_blas.p; s.blas_count = (int)c->h_blas.size();
-    s.materials = (const rtx_material *)c->d_materials.p; s.material_count = c->material_count;
-    s.textures = (const DevTexture *)c->d_textures.p; s.texture_count = (int)c->h_tex.size();
-    s.sky = (const float *)c->d_sky.p; s.sky_size = c->sky_size;
+    bind_tables(c);                 // BLAS, materials, textures, sky: the same binding every later change of a table ends with (replace_table)
     s.ewa_table = (const float *)c->d_ewa.p;
     s.tlas_nodes = (const float4 *)(fb + off[0]); s.tlas_node_count = f->tlas_node_count; s.pk_tlas_nodes = (const float4 *)(fb + off[1]);
     s.tlas_indices = (const int32_t *)(fb + off[2]); s.tlas_index_count = f->tlas_index_count;
@@ -931,11 +923,9 @@ extern "C" int rtx_bind_blas_vertices(rtx_ctx * c, int32_t blas_id, const int32_
     DevBlas B = c->h_blas[blas_id];
     rtx_ctx::BlasRefit N; N.map4 = R.map4; N.map4c = R.map4c;
     if (int rc = plan_refit(c, B, N, slot_vertices, vertex_count)) return rc;
-    const DevBlas old = c->h_blas[blas_id];
-    c->h_blas[blas_id] = B;
-    if (int rc = upload_blas_table(c)) { c->h_blas[blas_id] = old; return rc; }
-    R = std::move(N);
-    return RTX_OK;
+    std::vector<DevBlas> table = c->h_blas;
+    table[blas_id] = B;
+    return upload_blas_table(c, table, [&] { c->blas[blas_id].refit = std::move(N); });
 }
 
 extern "C" int rtx_refit_blas(rtx_ctx * c, int32_t blas_id, const void * positions_dev, const void * normals_dev, int32_t vertex_count) {
@@ -1902,7 +1892,7 @@ extern "C" int rtx_debug_texture_sample(rtx_ctx * c, int32_t texture_id, const f
     hipSetDevice(c->cfg.device);
     DevScene sc = c->scene;
     sc.texture_mode = c->cfg.texture_mode; sc.mip_filter = c->cfg.mip_filter; sc.max_anisotropy = c->cfg.max_anisotropy;
-    sc.textures = (const DevTexture *)c->d_textures.p; sc.ewa_table = (const float *)c->d_ewa.p;
+    sc.ewa_table = (const float *)c->d_ewa.p;                  // the texture table is bound since rtx_create (bind_tables)
     DevBuf din, dout;
     int rc = upload(c, din, in6, (size_t)n * 24);
     if (!rc) rc = ensure(c, dout, (size_t)n * 12);

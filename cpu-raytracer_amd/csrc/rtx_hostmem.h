@@ -3,6 +3,7 @@
 //   DevBuf      one device allocation; move-only, freed by its destructor
 //   StageRing   three pinned staging buffers with their events; stage_copy() is the one stream-ordered host -> device upload
 //   grow_keep   a bigger device buffer with the old contents in front and zeros behind
+//   bind_tables / replace_table   the scene's view of the BLAS, material, texture and sky tables follows every change of a table
 //
 // One failure rule: a helper that fails leaves every buffer it was given as it found it, and whatever it allocated on the way is released
 // by the owner going out of scope.  The context type C only has to carry `std::string err`; stage_copy also reads `c->stream`.  The
@@ -62,6 +63,32 @@ template <typename C> static int grow_keep(C * c, DevBuf & b, size_t old_bytes, 
     if (int rc = grown_copy(c, b, old_bytes, new_bytes, what, nb)) return rc;
     b = std::move(nb);
     return RTX_OK;
+}
+
+// ---- the four tables kernels reach through the scene they receive by value: BLAS, materials, textures, sky ----
+// Binding rule: what a launch sees of a table is what the context holds when the call is made, whether or not a frame was set since the
+// table last moved.  bind_tables is the ONE place that writes the eight fields (pointer and count of each table; no memory: no entries), and
+// replace_table the one place a table changes: both end every path through it, so no launch site can copy a scene that names a table the
+// context no longer holds.  C carries scene, stream, d_blas / h_blas, d_materials / material_count, d_textures / h_tex, d_sky / sky_size.
+template <typename C> static void bind_tables(C * c) {
+    auto & s = c->scene;
+    s.blas = (decltype(s.blas))c->d_blas.p;                s.blas_count = c->d_blas.p ? (int)c->h_blas.size() : 0;
+    s.materials = (decltype(s.materials))c->d_materials.p; s.material_count = c->d_materials.p ? c->material_count : 0;
+    s.textures = (decltype(s.textures))c->d_textures.p;    s.texture_count = c->d_textures.p ? (int)c->h_tex.size() : 0;
+    s.sky = (decltype(s.sky))c->d_sky.p;                   s.sky_size = c->d_sky.p ? c->sky_size : 0;
+}
+
+// table = the `bytes` at src: after a wait for the context's stream (queued work still reads the old contents, and a table that moves is
+// freed here), in place where it fits, else built beside the old table and swapped in.  Then accept() — the host state that goes with the
+// new table: counts, host copies — and the binding.  On failure accept() does not run: table, host state and binding stay what they were.
+template <typename C, typename Accept> static int replace_table(C * c, DevBuf & table, const void * src, size_t bytes, Accept && accept) {
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    int rc;
+    if (bytes <= table.cap && table.p) rc = upload(c, table, src, bytes);
+    else { DevBuf nb; rc = upload(c, nb, src, bytes); if (!rc) table = std::move(nb); }
+    if (!rc) accept();
+    bind_tables(c);
+    return rc;
 }
 
 // Three pinned buffers taken in turn: the host fills one and queues its copy without waiting for the GPU; a slot is waited for only when

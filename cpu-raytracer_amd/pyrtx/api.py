@@ -438,22 +438,43 @@ class Renderer:
         except Exception:
             pass
 
+    # The plain uploads (include/rtx.h, "scene data that lives across frames").  Each may be called at any time, also after set_frame: it
+    # waits for the queued work and takes effect at the next render or query call, with no set_frame in between.
+    def upload_blas(self, blas_id: int, b: sio.Blas):
+        """b under blas_id (new, or replacing what the id held: a vertex binding and what alloc_blas made of the id go with it)."""
+        nodes = np.ascontiguousarray(b.nodes); hot = np.ascontiguousarray(b.tri_hot); cold = np.ascontiguousarray(b.tri_cold)
+        self._chk(self.lib.rtx_upload_blas(self.ctx, int(blas_id), nodes.ctypes.data, len(nodes), hot.ctypes.data, cold.ctypes.data,
+                                           len(hot), b.material_offset), "rtx_upload_blas")
+        self._blas_shapes += [None] * (blas_id + 1 - len(self._blas_shapes))
+        self._blas_shapes[blas_id] = (len(nodes), len(hot), b.material_offset, b.source_triangle_count)
+        getattr(self, "_built_shapes", {}).pop(int(blas_id), None)      # no longer an alloc_blas id
+
+    def upload_materials(self, materials):
+        """The whole material table (scene_io.MATERIAL array), of any count >= 1."""
+        mats = np.ascontiguousarray(materials)
+        if mats.ndim != 1 or mats.dtype.itemsize != sio.MATERIAL.itemsize:
+            raise ValueError(f"materials must be a 1-d array of scene_io.MATERIAL, not {mats.dtype} {mats.shape}")
+        self._chk(self.lib.rtx_upload_materials(self.ctx, mats.ctypes.data, len(mats)), "rtx_upload_materials")
+
+    def upload_texture(self, texture_id: int, t: sio.Texture):
+        """t (descriptor and float texels, chain included) under texture_id."""
+        desc = RtxTextureDesc()
+        C.memmove(C.byref(desc), t.desc.ctypes.data, C.sizeof(RtxTextureDesc))
+        tex = np.ascontiguousarray(t.texels, np.float32)
+        self._chk(self.lib.rtx_upload_texture(self.ctx, int(texture_id), C.byref(desc), tex.ctypes.data, len(tex)), "rtx_upload_texture")
+
+    def upload_sky(self, sky):
+        """The sky probe, (S, S, 3) float32 of any size S."""
+        sky = np.ascontiguousarray(sky, np.float32)
+        self._chk(self.lib.rtx_upload_sky(self.ctx, sky.ctypes.data, sky.shape[0]), "rtx_upload_sky")
+
     def upload_scene(self, sc: sio.Scene):
         for i, b in enumerate(sc.blas):
-            nodes = np.ascontiguousarray(b.nodes); hot = np.ascontiguousarray(b.tri_hot); cold = np.ascontiguousarray(b.tri_cold)
-            self._chk(self.lib.rtx_upload_blas(self.ctx, i, nodes.ctypes.data, len(nodes), hot.ctypes.data, cold.ctypes.data,
-                                               len(hot), b.material_offset), "rtx_upload_blas")
-            self._blas_shapes += [None] * (i + 1 - len(self._blas_shapes))
-            self._blas_shapes[i] = (len(nodes), len(hot), b.material_offset, b.source_triangle_count)
-        mats = np.ascontiguousarray(sc.materials)
-        self._chk(self.lib.rtx_upload_materials(self.ctx, mats.ctypes.data, len(mats)), "rtx_upload_materials")
+            self.upload_blas(i, b)
+        self.upload_materials(sc.materials)
         for i, t in enumerate(sc.textures):
-            desc = RtxTextureDesc()
-            C.memmove(C.byref(desc), t.desc.ctypes.data, C.sizeof(RtxTextureDesc))
-            tex = np.ascontiguousarray(t.texels, np.float32)
-            self._chk(self.lib.rtx_upload_texture(self.ctx, i, C.byref(desc), tex.ctypes.data, len(tex)), "rtx_upload_texture")
-        sky = np.ascontiguousarray(sc.sky, np.float32)
-        self._chk(self.lib.rtx_upload_sky(self.ctx, sky.ctypes.data, sky.shape[0]), "rtx_upload_sky")
+            self.upload_texture(i, t)
+        self.upload_sky(sc.sky)
 
     def set_frame(self, sc: sio.Scene):
         fr = RtxFrame()

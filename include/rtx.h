@@ -223,6 +223,19 @@ const char * rtx_last_error(const rtx_ctx * ctx);
 int rtx_abi_version(void);
 
 /* ---- scene data that lives across frames -------------------------------- */
+/* BLAS, materials, textures and the sky belong to the context, not to a
+ * frame.  Any of the uploads and allocs below (and rtx_alloc_blas,
+ * rtx_alloc_texture further down) may be called at any time, also after
+ * rtx_set_frame and under ids the context has never seen: the call waits for
+ * the work already queued on the context's stream — which keeps the state it
+ * was queued with — and takes effect at the NEXT render or query call,
+ * however large the context's tables have become and wherever they now lie.
+ * rtx_set_frame is needed only for what it carries itself: instances, TLAS,
+ * spheres, planes, lights and the camera.  What a call must not leave behind
+ * is checked at the next render or query call, not at the upload: a material
+ * table that no longer covers an id in use is RTX_ERR_STATE there.  A call
+ * that fails (RTX_ERR_OOM, RTX_ERR_HIP) leaves the table it was to replace,
+ * its count and the ids in it as they were.                                   */
 
 /* A flattened BottomLevelBVH (BottomLevelBVH.h:5-34 after flatten(),
  * BottomLevelBVH.cpp:196-212): nodes, and hot/cold triangles already in leaf
