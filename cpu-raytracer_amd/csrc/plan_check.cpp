@@ -384,8 +384,74 @@ static void small_grids() {
     }
 }
 
+// The plan at the limit: RTX_MAX_LEVELS levels (bounces 11), for every combination of the call's flags and of the knobs a level index enters.
+// Whatever the combination, the per-level arrays are filled for all 12 levels and for no more, the shadow-ray schedule fits its array
+// and covers every level exactly once, and nothing is queued after a level that does not exist.
+static void twelve_levels() {
+    CASE("twelve levels");
+    const int L = RTX_MAX_LEVELS;
+    static_assert(sizeof(((RenderPlan *)0)->any) / sizeof(AnyLaunch) == RTX_MAX_LEVELS && sizeof(((RenderPlan *)0)->closest) / sizeof(int32_t) == RTX_MAX_LEVELS &&
+                  sizeof(((RenderPlan *)0)->shade) / sizeof(int32_t) == RTX_MAX_LEVELS, "the plan's per-level arrays");
+    long plans = 0;
+    for (uint32_t bits = 0; bits < 256; bits++) {
+        const uint32_t flags = (bits & 1 ? SERIAL : 0) | (bits & 2 ? LANE : 0) | (bits & 4 ? PKC : 0) | (bits & 8 ? CULL : 0) | (bits & 16 ? CW : 0) |
+                               (bits & 32 ? SIMPLE : 0) | (bits & 64 ? PSTAT : 0) | (bits & 128 ? AOV : 0);
+        for (int lights : { 1, 33 }) for (int instances : { 1, 2, 65 }) for (int fuse = 0; fuse <= 1; fuse++) for (int split : { 0, 64 })
+        for (int merge = 0; merge <= 1; merge++) for (int lane_from : { -1, 0, 5, 11 }) for (int lane_from_any : { -1, 5 }) {
+            PlanInputs in = frame(flags);
+            in.bounces = L - 1; in.can_spawn = true; in.light_count = lights; in.instance_count = instances;
+            in.knobs.fuse_shade = fuse != 0; in.knobs.split_items = split; in.knobs.merge_any = merge != 0;
+            in.knobs.lane_from_level = lane_from; in.knobs.lane_from_level_any = lane_from_any;
+            const RenderPlan p = plan_render(in);
+            plans++;
+            CHECK(p.levels == L);
+            CHECK(p.n_any >= 1 && p.n_any <= L);
+            const bool plain = (flags & (CW | SIMPLE)) != 0;
+            for (int l = 0; l < L; l++) {
+                const int c = p.closest[l], s = p.shade[l];
+                CHECK(c >= CLOSEST_PLAIN && c <= CLOSEST_PACKET_FUSED_CULL && s >= SHADE_NONE && s <= SHADE_AOV_CULL);
+                CHECK((c == CLOSEST_PLAIN || c == CLOSEST_PLAIN_COUNT) == plain);              // 0 is a kernel too: only a plain call may hold it
+                CHECK((s == SHADE_NONE) == (c == CLOSEST_PACKET_FUSED || c == CLOSEST_PACKET_FUSED_CULL));      // a level without a k_shade launch shaded its own hits
+                CHECK((s == SHADE_AOV || s == SHADE_AOV_COUNT || s == SHADE_AOV_CULL) == ((flags & AOV) != 0 && l == 0));
+                const int n = plan_stats_n(p, in.batch_tiles * 1024, l);
+                CHECK(n >= 1 && n <= p.stats_stride);
+            }
+            int covered[RTX_MAX_LEVELS] = { 0 };
+            int last_after = -1;
+            for (int i = 0; i < p.n_any && i < L; i++) {
+                const AnyLaunch & a = p.any[i];
+                CHECK(a.lo >= 0 && a.lo <= a.hi && a.hi <= L - 1);
+                CHECK(a.after_level >= a.hi && a.after_level <= p.levels - 1);      // after the k_shade that filled its last level, and no later than the last one
+                CHECK(a.after_level >= last_after); last_after = a.after_level;      // in queueing order
+                CHECK(a.stream == (p.overlap ? 1 : 0));
+                CHECK(a.kernel >= ANY_PLAIN && a.kernel <= ANY_PACKET_SPLIT && (a.items == 0 || a.kernel == ANY_PACKET_SPLIT));
+                if (a.kernel == ANY_PLAIN || a.kernel == ANY_PLAIN_COUNT) CHECK(a.lo == a.hi);      // the plain kernels take lo only
+                for (int l = a.lo; l <= a.hi && l < L; l++) if (l >= 0) covered[l]++;
+            }
+            for (int l = 0; l < L; l++) CHECK(covered[l] == 1);
+            if (p.split) CHECK(p.item_cap >= 64 && p.item_cap <= (1 << 16));
+        }
+    }
+    CHECK(plans == 256l * 2 * 3 * 2 * 2 * 2 * 4 * 2);
+    {   // the merged launch of the one-stream shape is ONE launch over 0 .. 11, after level 11; the two-stream shape's second launch covers 1 .. 11
+        PlanInputs in = frame(SERIAL); in.bounces = L - 1; in.light_count = 33;
+        CHECK(schedule(plan_render(in), { { 11, 0, ANY_PACKET_SPLIT, 0, 11, 1 } }));
+        in.flags = 0;
+        CHECK(schedule(plan_render(in), { { 0, 1, ANY_PACKET_SPLIT, 0, 0, 1 }, { 11, 1, ANY_PACKET_SPLIT, 1, 11, 1 } }));
+        in.instance_count = 2; in.knobs.split_items = 0;                 // per-lane from level 2: three launches
+        CHECK(schedule(plan_render(in), { { 0, 1, ANY_PACKET, 0, 0, 0 }, { 11, 1, ANY_PACKET, 1, 1, 0 }, { 11, 1, ANY_LANE, 2, 11, 0 } }));
+        in.knobs.lane_from_level = 11;                                   // the last level alone goes per lane
+        const RenderPlan p = plan_render(in);
+        CHECK(p.closest[10] == CLOSEST_PACKET && p.closest[11] == CLOSEST_LANE);
+        CHECK(schedule(p, { { 0, 1, ANY_PACKET, 0, 0, 0 }, { 11, 1, ANY_PACKET, 1, 10, 0 }, { 11, 1, ANY_LANE, 11, 11, 0 } }));
+        in.flags = SERIAL; in.knobs.merge_any = false;                    // one launch per level: the array is exactly full
+        CHECK(plan_render(in).n_any == L);
+    }
+}
+
 int main() {
     small_grids();
+    twelve_levels();
     modes_and_schedule();
     instrumented_modes();
     stack_limits();
