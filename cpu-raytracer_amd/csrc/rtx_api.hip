@@ -36,6 +36,7 @@
 #include "rtx_nearest.h"
 #include "rtx_hits.h"
 #include "rtx_sweep.h"
+#include "rtx_overlap.h"
 #include "rtx_texmip.h"
 #include <rocprim/device/device_radix_sort.hpp>      // rtx_update_instances, scenes beyond one workgroup: header-only, part of ROCm
 #include "rtx_hostmem.h"                             // DevBuf, StageRing, grow_keep: every device and pinned allocation has one owner
@@ -139,7 +140,7 @@ struct rtx_ctx {
     DevBuf d_query_sort; int32_t query_sort_cap = 0; size_t query_sort_tmp = 0;
     // rtx_query_nearest: the tile counter of a round (4 bytes, made by the first call); RTX_NEAREST_FETCH=0: tiles by stride, no counter (A/B)
     DevBuf d_nearest_head; bool nearest_fetch = true;
-    // rtx_query_nearest / rtx_query_hits / rtx_query_sweep: RTX_QUERY_GRID=g caps their grids at g workgroups (0: the spill region's size alone decides)
+    // rtx_query_nearest / rtx_query_hits / rtx_query_sweep / rtx_query_overlap: RTX_QUERY_GRID=g caps their grids at g workgroups (0: the spill region's size alone decides)
     int query_grid = 0;
     // rtx_set_object_masks / rtx_update_object_masks: the table the filtered walk queries read (M uint32_t, grown only, filled through a staging
     // ring of its own like the cameras), whether there is one, and (I, S, P) of the frame it was set for
@@ -2288,7 +2289,9 @@ static int query_checks(rtx_ctx * c, const void * in, int64_t n, const void * ou
     if (!c) return RTX_ERR_INVALID_ARG;
     if (!in || !out || n < 1) { c->err = std::string(what) + ": null pointer or n < 1"; return RTX_ERR_INVALID_ARG; }
     if (flags & ~allowed) {
-        c->err = std::string(what) + (allowed == (uint32_t)RTX_QUERY_SORT ? ": flags other than RTX_QUERY_SORT" : ": flags other than RTX_RENDER_LANE_TRACE / RTX_RENDER_PACKET_CLOSEST / RTX_QUERY_SORT");
+        c->err = std::string(what) + (allowed == (uint32_t)RTX_QUERY_SORT ? ": flags other than RTX_QUERY_SORT" :
+                                      (allowed & (uint32_t)RTX_OVERLAP_ANY) ? ": flags other than RTX_QUERY_SORT / RTX_OVERLAP_OBJECTS / RTX_OVERLAP_ANY" :
+                                      ": flags other than RTX_RENDER_LANE_TRACE / RTX_RENDER_PACKET_CLOSEST / RTX_QUERY_SORT");
         return RTX_ERR_INVALID_ARG;
     }
     if (!c->frame_set) { c->err = std::string(what) + " before rtx_set_frame"; return RTX_ERR_STATE; }
@@ -2375,7 +2378,7 @@ extern "C" int rtx_query_occluded(rtx_ctx * c, const void * segments_dev, int64_
     return query_rounds(c, k.q, n, [&](int64_t first, int m) { return query_occluded_round(c, k, (const float *)segments_dev + 7 * first, m, occluded_dev + first); });
 }
 
-// the grid limit of the walk queries (k_query_nearest, k_query_hits, k_query_sweep): the spill regions are indexed by the global thread id;
+// the grid limit of the walk queries (k_query_nearest, k_query_hits, k_query_sweep, k_query_overlap): the spill regions are indexed by the global thread id;
 // RTX_QUERY_GRID lowers it, so that a workgroup walks several tiles of a small call
 static int query_max_blocks(const rtx_ctx * c) {
     const int fit = c->q.spill_threads / RTX_QUERY_BLOCK;
@@ -2681,6 +2684,80 @@ extern "C" int rtx_query_sweep(rtx_ctx * c, const void * sweeps_dev, int64_t n, 
 }
 extern "C" int rtx_query_sweep_filtered(rtx_ctx * c, const void * sweeps_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags, const rtx_query_filter * filter) {
     return query_sweep_impl(c, sweeps_dev, n, channels, out, flags, filter);
+}
+
+// ---- box-overlap queries (include/rtx.h: rtx_query_overlap; kernel in rtx_overlap.h, arithmetic and walk in rtx_overlap_math.h) ---------
+// n boxes in device memory against the frame the context holds: per round of at most RTX_QUERY_CHUNK_RAYS rows ONE launch of k_query_overlap,
+// which reads the rows and writes the ids of the max_hits smallest overlaps of every row and the row's count; with RTX_QUERY_SORT the bounds,
+// key and sort launches of the ray queries run first over the first four floats of the 10-float rows — the position key of rtx_query_nearest;
+// its fourth float is h.x here, so a box with h.x == 0 sorts with the dead rows, last, and is walked all the same — in the same sort block.
+// No queue set, no counters; the stack as for rtx_query_nearest (region 0 of the spill buffer only), its stack rule, and its tile counter
+// (the calls are ordered by the stream).
+template <int FORM> static void query_overlap_launch(rtx_ctx * c, const rtx_query_filter * filter, int64_t first, int blocks, const DevScene & sc, const float * rows, int m, int K,
+                                                     int32_t * object_id, int32_t * triangle_id, int32_t * count, const uint64_t * order, uint32_t * head) {
+    if (filter) {
+        const QueryMasks<true> km = filter_masks(c, filter, first);
+        launch_timed(c, "k_query_overlap", c->stream, [&] { hipLaunchKernelGGL((k_query_overlap<FORM, true>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, K, object_id, triangle_id, count, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, km); });
+    } else launch_timed(c, "k_query_overlap", c->stream, [&] { hipLaunchKernelGGL((k_query_overlap<FORM, false>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, K, object_id, triangle_id, count, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, QueryMasks<false>()); });
+}
+static int query_overlap_impl(rtx_ctx * c, const void * boxes_dev, int64_t n, int32_t max_hits, int32_t * object_id_dev, int32_t * triangle_id_dev, int32_t * count_dev,
+                              uint32_t flags, const rtx_query_filter * filter) {
+    const bool any = (flags & RTX_OVERLAP_ANY) != 0, objects = (flags & RTX_OVERLAP_OBJECTS) != 0;
+    if (c) {
+        const char * bad = nullptr;
+        if (max_hits < 0 || max_hits > (int32_t)RTX_QUERY_MAX_HITS) bad = "max_hits must be in [0, RTX_QUERY_MAX_HITS]";
+        else if (any && (max_hits != 0 || objects)) bad = "RTX_OVERLAP_ANY needs max_hits == 0 and excludes RTX_OVERLAP_OBJECTS";
+        else if (objects && triangle_id_dev) bad = "RTX_OVERLAP_OBJECTS reports no triangle ids: triangle_id_dev must be NULL";
+        else if (max_hits == 0 && !count_dev) bad = "max_hits == 0 is the count-only form (or RTX_OVERLAP_ANY) and needs a count_dev";
+        else if (max_hits > 0 && !object_id_dev && !triangle_id_dev) bad = "max_hits > 0 needs object_id_dev or triangle_id_dev";
+        if (bad) { c->err = std::string("rtx_query_overlap: ") + bad; return RTX_ERR_INVALID_ARG; }
+    }
+    const void * const some_out = object_id_dev ? (const void *)object_id_dev : triangle_id_dev ? (const void *)triangle_id_dev : (const void *)count_dev;
+    if (int bad = query_checks(c, boxes_dev, n, some_out, flags, "rtx_query_overlap", (uint32_t)RTX_QUERY_SORT | (uint32_t)RTX_OVERLAP_OBJECTS | (uint32_t)RTX_OVERLAP_ANY)) return bad;
+    int blas_depth = -1;
+    for (size_t b = 0; b < c->blas.size(); b++) if (c->h_blas[b].nodes && c->blas[b].inner_depth > blas_depth) blas_depth = c->blas[b].inner_depth;
+    const int need = rtxnp::stack_need(c->tlas_inner_depth, blas_depth), have = c->cfg.stack_size < RTX_MAX_STACK ? c->cfg.stack_size : RTX_MAX_STACK;
+    if (need > have) {
+        c->err = "rtx_query_overlap: the descent needs " + std::to_string(need) + " stack entries (TLAS inner depth " + std::to_string(c->tlas_inner_depth) +
+                 " + 1, BLAS inner depth " + std::to_string(blas_depth) + " + 1), rtx_config.stack_size allows " + std::to_string(have);
+        return RTX_ERR_LIMIT;
+    }
+    if (int bad = filter_checks(c, filter, "rtx_query_overlap")) return bad;
+    hipSetDevice(c->cfg.device);
+    const bool sorted = (flags & RTX_QUERY_SORT) != 0;
+    QuerySort S = {};
+    DevQueues unused;
+    if (sorted) if (int rc = query_queues(c, n, unused, &S, false)) return rc;
+    if (int rc = ensure(c, c->d_nearest_head, sizeof(uint32_t))) return rc;      // the first call only
+    uint32_t * const head = (uint32_t *)c->d_nearest_head.p;
+    const DevScene sc = c->scene;
+    const int max_blocks = query_max_blocks(c);
+    const int64_t K = max_hits;
+    for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
+        const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
+        const float * const rows = (const float *)boxes_dev + rtxop::ROW_FLOATS * first;
+        int32_t * const object_id = K > 0 && object_id_dev ? object_id_dev + K * first : nullptr;
+        int32_t * const triangle_id = K > 0 && triangle_id_dev ? triangle_id_dev + K * first : nullptr;
+        int32_t * const count = count_dev ? count_dev + first : nullptr;
+        if (sorted) if (int rc = query_sort_round<rtxop::ROW_FLOATS, 4>(c, S, rows, m)) return rc;
+        const int tiles = (m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK, blocks = tiles < max_blocks ? tiles : max_blocks;
+        const uint64_t * const order = sorted ? S.keys : nullptr;
+        HIP_OK(c, hipMemsetAsync(head, 0, sizeof(uint32_t), c->stream));
+        if (any) query_overlap_launch<rtxop::FORM_ANY>(c, filter, first, blocks, sc, rows, m, 0, nullptr, nullptr, count, order, head);
+        else if (objects && K > 0) query_overlap_launch<rtxop::FORM_OBJECTS>(c, filter, first, blocks, sc, rows, m, (int)K, object_id, nullptr, count, order, head);
+        else if (objects) query_overlap_launch<rtxop::FORM_OBJECTS | OVERLAP_COUNT_ONLY>(c, filter, first, blocks, sc, rows, m, 0, nullptr, nullptr, count, order, head);
+        else if (K > 0) query_overlap_launch<rtxop::FORM_TRIANGLES>(c, filter, first, blocks, sc, rows, m, (int)K, object_id, triangle_id, count, order, head);
+        else query_overlap_launch<rtxop::FORM_TRIANGLES | OVERLAP_COUNT_ONLY>(c, filter, first, blocks, sc, rows, m, 0, nullptr, nullptr, count, order, head);
+    }
+    HIP_OK(c, hipGetLastError());
+    return RTX_OK;
+}
+extern "C" int rtx_query_overlap(rtx_ctx * c, const void * boxes_dev, int64_t n, int32_t max_hits, int32_t * object_id_dev, int32_t * triangle_id_dev, int32_t * count_dev, uint32_t flags) {
+    return query_overlap_impl(c, boxes_dev, n, max_hits, object_id_dev, triangle_id_dev, count_dev, flags, nullptr);
+}
+extern "C" int rtx_query_overlap_filtered(rtx_ctx * c, const void * boxes_dev, int64_t n, int32_t max_hits, int32_t * object_id_dev, int32_t * triangle_id_dev, int32_t * count_dev,
+                                          uint32_t flags, const rtx_query_filter * filter) {
+    return query_overlap_impl(c, boxes_dev, n, max_hits, object_id_dev, triangle_id_dev, count_dev, flags, filter);
 }
 
 // the order RTX_QUERY_SORT traces n rows of row_floats (6: rays, 7: segments) floats in: the bounds, key and sort launches of every round and

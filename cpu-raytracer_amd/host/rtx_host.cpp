@@ -14,6 +14,7 @@
 #include "../csrc/rtx_nearest_math.h"
 #include "../csrc/rtx_side_math.h"
 #include "../csrc/rtx_hits_math.h"
+#include "../csrc/rtx_overlap_math.h"
 #include "../csrc/rtx_sweep_math.h"
 
 #include <math.h>
@@ -1067,6 +1068,132 @@ extern "C" int rtxh_sweep_plane(const float origin[3], const float direction[3],
     if (any) { *t_out = t; *d20_out = d20; }
     return any ? 1 : 0;
 }
+
+// =================================================================================================
+// rtx_query_overlap on the host: rtxop::walk (csrc/rtx_overlap_math.h) over the arrays of rtxh_query_nearest, and the exhaustive search
+namespace {
+struct HostOverlapScene : HostNearestScene {
+    explicit HostOverlapScene(const rtxh_nearest_scene & sc) : HostNearestScene{ sc } {}
+    int instance_count() const { return s.instance_count; }
+    int enter(int slot, rtxop::Frame & F) {
+        const int inst = s.tlas_indices[slot];
+        F = rtxop::local_frame(F, s.instances[inst].world_inv);
+        B = &s.blas[s.instances[inst].blas_id];
+        return inst;
+    }
+};
+struct HostOverlapStack {
+    int node[RTX_MAX_STACK]; int high = 0;
+    void push(int sp, int n) { node[sp] = n; if (sp + 1 > high) high = sp + 1; }
+    void pop(int sp, int & n) const { n = node[sp]; }
+};
+struct HostOverlapList {
+    int32_t object[rtxop::MAX_HITS], triangle[rtxop::MAX_HITS];
+    void get(int j, int32_t & o_, int32_t & s_) const { o_ = object[j]; s_ = triangle[j]; }
+    void set(int j, int32_t o_, int32_t s_) { object[j] = o_; triangle[j] = s_; }
+};
+// the argument rules of rtx_query_overlap, in its order
+int overlap_args_check(const rtxh_nearest_scene * s, const float * boxes, int64_t n, int32_t max_hits, const int32_t * object_out, const int32_t * triangle_out, const int32_t * count_out,
+                       uint32_t flags, bool trees) {
+    const bool any = (flags & RTX_OVERLAP_ANY) != 0, objects = (flags & RTX_OVERLAP_OBJECTS) != 0;
+    if (max_hits < 0 || max_hits > rtxop::MAX_HITS) return RTX_ERR_INVALID_ARG;
+    if (any && (max_hits != 0 || objects)) return RTX_ERR_INVALID_ARG;
+    if (objects && triangle_out) return RTX_ERR_INVALID_ARG;
+    if (max_hits == 0 && !count_out) return RTX_ERR_INVALID_ARG;
+    if (max_hits > 0 && !object_out && !triangle_out) return RTX_ERR_INVALID_ARG;
+    if (flags & ~((uint32_t)RTX_QUERY_SORT | (uint32_t)RTX_OVERLAP_OBJECTS | (uint32_t)RTX_OVERLAP_ANY)) return RTX_ERR_INVALID_ARG;
+    const rtx_query_buffers none = {};
+    return nearest_scene_check(s, boxes, n, (uint32_t)RTX_QUERY_DISTANCE, &none, trees);
+}
+// the K entries of row i from its list, and its count: what k_query_overlap stores
+void overlap_write(const HostOverlapList & L, const rtxop::Tally & w, int K, int64_t i, int32_t * object_out, int32_t * triangle_out, int32_t * count_out) {
+    if (count_out) count_out[i] = w.count;
+    for (int j = 0; j < K; j++) {
+        const size_t e = (size_t)i * (size_t)K + (size_t)j;
+        if (object_out) object_out[e] = j < w.held ? L.object[j] : -1;
+        if (triangle_out) triangle_out[e] = j < w.held ? L.triangle[j] : -1;
+    }
+}
+template <int FORM, typename Scene>
+void overlap_exhaustive_row(const rtxh_nearest_scene & s, Scene & S, HostOverlapList & L, const float * row, int K, rtxop::Tally & w) {
+    w.count = 0; w.held = 0;
+    if (!rtxop::row_is_live(row) || !S.row_visible()) return;
+    const rtxop::Frame W = rtxop::world_frame(row);
+    if (rtxop::world_primitives<FORM>(S, L, K, w, W)) return;
+    for (int k = 0; k < s.instance_count; k++) {
+        if (!S.object_visible(k)) continue;
+        const rtxop::Frame F = rtxop::local_frame(W, s.instances[k].world_inv);
+        const rtxh_nearest_blas & B = s.blas[s.instances[k].blas_id];
+        for (int t = 0; t < B.triangle_count; t++) {
+            if (!rtxop::triangle_overlaps(F, rtxnp::ptr3(B.hot[t].position_0), rtxnp::ptr3(B.hot[t].position_edge_1), rtxnp::ptr3(B.hot[t].position_edge_2))) continue;
+            if (FORM == rtxop::FORM_TRIANGLES) { rtxop::offer(L, K, w, k, t); continue; }
+            rtxop::offer(L, K, w, k, -1);
+            if (FORM == rtxop::FORM_ANY) return;
+            break;
+        }
+    }
+}
+}  // namespace
+
+static int query_overlap_host(const rtxh_nearest_scene * scene, const float * boxes, int64_t n, int32_t max_hits, int32_t * object_out, int32_t * triangle_out, int32_t * count_out,
+                              uint32_t flags, int32_t * stack_max_out, const HostMasks * km) {
+    if (int rc = overlap_args_check(scene, boxes, n, max_hits, object_out, triangle_out, count_out, flags, true)) return rc;
+    const int form = (flags & RTX_OVERLAP_ANY) ? rtxop::FORM_ANY : (flags & RTX_OVERLAP_OBJECTS) ? rtxop::FORM_OBJECTS : rtxop::FORM_TRIANGLES;
+    int high = 0;
+    for (int64_t i = 0; i < n; i++) {
+        HostOverlapStack st;
+        HostOverlapList L;
+        rtxop::Tally w;
+        const float * row = boxes + rtxop::ROW_FLOATS * i;
+        auto run = [&](auto & S) {
+            if (form == rtxop::FORM_ANY) rtxop::walk<rtxop::FORM_ANY>(S, st, L, row, 0, w);
+            else if (form == rtxop::FORM_OBJECTS) rtxop::walk<rtxop::FORM_OBJECTS>(S, st, L, row, max_hits, w);
+            else rtxop::walk<rtxop::FORM_TRIANGLES>(S, st, L, row, max_hits, w);
+        };
+        if (km) { HostMasked<HostOverlapScene> S(*scene, km->table, km->of_row(i)); run(S); }
+        else { HostOverlapScene S(*scene); run(S); }
+        if (st.high > high) high = st.high;
+        overlap_write(L, w, max_hits, i, object_out, triangle_out, count_out);
+    }
+    if (stack_max_out) *stack_max_out = high;
+    return RTX_OK;
+}
+extern "C" int rtxh_query_overlap(const rtxh_nearest_scene * scene, const float * boxes, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
+                                  int32_t * count_out, uint32_t flags, int32_t * stack_max_out) {
+    return query_overlap_host(scene, boxes, n, max_hits, object_id_out, triangle_id_out, count_out, flags, stack_max_out, nullptr);
+}
+extern "C" int rtxh_query_overlap_filtered(const rtxh_nearest_scene * scene, const float * boxes, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
+                                           int32_t * count_out, uint32_t flags, int32_t * stack_max_out, const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask) {
+    const HostMasks km = { object_masks, row_masks, row_mask };
+    return query_overlap_host(scene, boxes, n, max_hits, object_id_out, triangle_id_out, count_out, flags, stack_max_out, &km);
+}
+
+static int query_overlap_exhaustive_host(const rtxh_nearest_scene * scene, const float * boxes, int64_t n, int32_t max_hits, int32_t * object_out, int32_t * triangle_out,
+                                         int32_t * count_out, uint32_t flags, const HostMasks km) {
+    if (int rc = overlap_args_check(scene, boxes, n, max_hits, object_out, triangle_out, count_out, flags, false)) return rc;
+    const rtxh_nearest_scene & s = *scene;
+    for (int64_t i = 0; i < n; i++) {
+        const float * row = boxes + rtxop::ROW_FLOATS * i;
+        HostMasked<HostOverlapScene> S(s, km.table, km.of_row(i));
+        HostOverlapList L;
+        rtxop::Tally w;
+        if (flags & RTX_OVERLAP_ANY) overlap_exhaustive_row<rtxop::FORM_ANY>(s, S, L, row, 0, w);
+        else if (flags & RTX_OVERLAP_OBJECTS) overlap_exhaustive_row<rtxop::FORM_OBJECTS>(s, S, L, row, max_hits, w);
+        else overlap_exhaustive_row<rtxop::FORM_TRIANGLES>(s, S, L, row, max_hits, w);
+        overlap_write(L, w, max_hits, i, object_out, triangle_out, count_out);
+    }
+    return RTX_OK;
+}
+extern "C" int rtxh_query_overlap_exhaustive(const rtxh_nearest_scene * scene, const float * boxes, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
+                                             int32_t * count_out, uint32_t flags) {
+    return query_overlap_exhaustive_host(scene, boxes, n, max_hits, object_id_out, triangle_id_out, count_out, flags, kNoMasks);
+}
+extern "C" int rtxh_query_overlap_exhaustive_filtered(const rtxh_nearest_scene * scene, const float * boxes, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
+                                                      int32_t * count_out, uint32_t flags, const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask) {
+    const HostMasks km = { object_masks, row_masks, row_mask };
+    return query_overlap_exhaustive_host(scene, boxes, n, max_hits, object_id_out, triangle_id_out, count_out, flags, km);
+}
+extern "C" float rtxh_overlap_margin(float local_scale, float world_scale, float kappa) { return rtxop::margin(local_scale, world_scale, kappa); }
 
 // =================================================================================================
 // Procedural atrium: a seeded Sponza-class stand-in (the real sponza.obj is absent from the mount).

@@ -31,7 +31,8 @@ EXPORTS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error", "rt
            "rtx_alloc_blas_topology", "rtx_set_blas_topology", "rtx_blas_vertex_normals", "rtx_query_nearest", "rtx_query_hits", "rtx_query_sweep",
            "rtx_debug_grids", "rtx_set_object_masks", "rtx_update_object_masks", "rtx_read_object_masks",
            "rtx_query_nearest_filtered", "rtx_query_hits_filtered", "rtx_query_sweep_filtered",
-           "rtx_blas_pseudonormals", "rtx_read_blas_pseudonormals", "rtx_query_signed_distance"]
+           "rtx_blas_pseudonormals", "rtx_read_blas_pseudonormals", "rtx_query_signed_distance",
+           "rtx_query_overlap", "rtx_query_overlap_filtered"]
 # newer than the A/B variants tools/ab.py may load (RTX_HIP_LIB = a library built from an older commit): bound when the library has them,
 # otherwise a call raises AttributeError (undefined symbol)
 VIEW_EXPORTS = ("rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer")
@@ -52,7 +53,8 @@ SWEEP_EXPORTS = ("rtx_query_sweep",)
 GRID_EXPORTS = ("rtx_debug_grids",)
 MASK_EXPORTS = ("rtx_set_object_masks", "rtx_update_object_masks", "rtx_read_object_masks",
                 "rtx_query_nearest_filtered", "rtx_query_hits_filtered", "rtx_query_sweep_filtered")
-OPTIONAL_EXPORTS = (VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + QUERY_SORT_EXPORTS + LAYOUT_EXPORTS
+OVERLAP_EXPORTS = ("rtx_query_overlap", "rtx_query_overlap_filtered")
+OPTIONAL_EXPORTS = (OVERLAP_EXPORTS + VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + QUERY_SORT_EXPORTS + LAYOUT_EXPORTS
                     + TEXTURE_EXPORTS + NORMALS_EXPORTS + NEAREST_EXPORTS + HITS_EXPORTS + SWEEP_EXPORTS + GRID_EXPORTS + MASK_EXPORTS + SIGNED_EXPORTS)
 RTX_QUERY_MAX_HITS = 8
 # texel formats of rtx_update_texture (include/rtx.h RTX_TEXELS_*)
@@ -80,6 +82,8 @@ RTX_QUERY_OBJECT_ID = 64
 RTX_QUERY_TRIANGLE_ID = 128
 RTX_QUERY_ALL = 247
 RTX_QUERY_CHUNK_RAYS = 1 << 20
+RTX_OVERLAP_OBJECTS = 512   # bits of rtx_query_overlap's flags: the distinct objects; 0 / 1 per row
+RTX_OVERLAP_ANY = 1024
 RTX_QUERY_SORT = 256        # a bit of the query calls' flags: sort the rays of every round into coherent packets on the device
 # name -> (bit, numpy dtype, components per ray), in rtx_query_buffers order
 QUERY_CHANNELS = {"distance": (RTX_QUERY_DISTANCE, np.float32, 1), "position": (RTX_QUERY_POSITION, np.float32, 3),
@@ -208,6 +212,9 @@ def load_library(path: Optional[str] = None):
         lib.rtx_blas_pseudonormals.argtypes = [vp, i32, vp]
         lib.rtx_read_blas_pseudonormals.argtypes = [vp, i32, vp, vp]
         lib.rtx_query_signed_distance.argtypes = [vp, vp, C.c_int64, u32, C.POINTER(RtxQueryBuffers), vp, vp, u32, C.POINTER(RtxQueryFilter)]
+    if hasattr(lib, "rtx_query_overlap"):
+        lib.rtx_query_overlap.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp, u32]
+        lib.rtx_query_overlap_filtered.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp, u32, C.POINTER(RtxQueryFilter)]
     for name in EXPORTS:
         if name in OPTIONAL_EXPORTS and not hasattr(lib, name):
             continue
@@ -373,6 +380,34 @@ def rays_from_directions(origins, directions) -> np.ndarray:
                 out[:-1] = f; out[-1] = f[-1]
         return out
     return np.ascontiguousarray(np.concatenate([o, d, diff(o, 1), diff(o, 0), diff(d, 1), diff(d, 0)], axis=2), np.float32)
+
+
+def grid_boxes(origin, cell, shape, device=None):
+    """The query_overlap rows of a voxel grid: float32 (X*Y*Z, 10), voxel (x, y, z) at row x + X * (y + Y * z) — x fastest — with centre
+    origin + (index + 0.5) * cell, half extents cell / 2 and the identity quaternion.  origin = the grid's minimum corner (3,), cell = the
+    voxel size (a number or (3,)), shape = (X, Y, Z).  device=None: a numpy array; otherwise a torch tensor on that device, so that
+    query_overlapped(grid_boxes(...)).view(Z, Y, X) is an occupancy grid."""
+    o = np.asarray(origin, np.float64).reshape(-1)
+    c = np.asarray(cell, np.float64).reshape(-1)
+    if c.size == 1:
+        c = np.repeat(c, 3)
+    dims = tuple(int(v) for v in shape)
+    if o.size != 3 or c.size != 3 or len(dims) != 3:
+        raise ValueError("origin and cell must have 3 components (cell may be one number) and shape must be (X, Y, Z)")
+    if min(dims) < 1 or not np.all(np.isfinite(o)) or not np.all(np.isfinite(c)) or np.any(c <= 0):
+        raise ValueError(f"shape {dims} must be positive and origin / cell finite with cell > 0")
+    X, Y, Z = dims
+    rows = np.zeros((Z, Y, X, 10), np.float32)
+    rows[..., 0] = (o[0] + (np.arange(X) + 0.5) * c[0])[None, None, :]
+    rows[..., 1] = (o[1] + (np.arange(Y) + 0.5) * c[1])[None, :, None]
+    rows[..., 2] = (o[2] + (np.arange(Z) + 0.5) * c[2])[:, None, None]
+    rows[..., 3:6] = (0.5 * c).astype(np.float32)
+    rows[..., 9] = 1.0
+    rows = rows.reshape(-1, 10)
+    if device is None:
+        return rows
+    import torch
+    return torch.from_numpy(rows).to(device)
 
 
 def group_layout(width: int, height: int, world: int, rank: int):
@@ -1463,6 +1498,72 @@ class Renderer:
         else:
             launch()
         return {name: out[name] for name in wanted}
+
+    def _query_overlap(self, boxes, K: int, count: bool, flags: int, out: Optional[Dict], n: Optional[int], sort: bool, mask, wanted: tuple) -> Dict:
+        """query_overlap and query_overlapped: rows of 10 floats in, the int32 tensors named in `wanted` out."""
+        ptr, n, box_t = self._query_rows("boxes", boxes, 10, n)
+        if out is not None and not isinstance(out, dict):
+            raise TypeError(f"out must be a dict {{name: tensor}}, not {type(out).__name__}")
+        out = dict(out or {})
+        extra = [k for k in out if k not in wanted]
+        if extra:
+            raise ValueError(f"out holds outputs that were not requested: {', '.join(map(str, extra))}")
+        raw = box_t is None
+        if raw and len(out) != len(wanted):
+            raise ValueError("with raw device pointers out must hold an address for every output: " + ", ".join(wanted))
+        fl = flags | (RTX_QUERY_SORT if sort else 0)
+        filt, mask_t = self._query_filter(mask, n)
+        ptrs = {name: self._query_out(name, t, np.int32, n, 1, raw, 0 if name == "count" else K) for name, t in out.items()}
+        self._query_on_device({k: t for k, t in [("boxes", box_t)] + [(f"out[{k!r}]", t) for k, t in out.items()] if hasattr(t, "device")})
+        for name in wanted:
+            if name not in out:
+                import torch
+                out[name] = torch.empty((n,) if name == "count" else (n, K), dtype=torch.int32, device=box_t.device)
+                ptrs[name] = out[name].data_ptr()
+
+        def launch():
+            args = (self.ctx, ptr, n, K, ptrs.get("object_id"), ptrs.get("triangle_id"), ptrs.get("count"), fl)
+            if filt is None:
+                self._chk(self.lib.rtx_query_overlap(*args), "rtx_query_overlap")
+            else:
+                self._chk(self.lib.rtx_query_overlap_filtered(*args, C.byref(filt)), "rtx_query_overlap_filtered")
+        tensors = [t for t in [box_t, mask_t] + list(out.values()) if hasattr(t, "record_stream")]
+        if tensors:
+            self._on_torch_stream(launch, tensors)
+        else:
+            launch()
+        return {name: out[name] for name in wanted}
+
+    def query_overlap(self, boxes, max_hits: int = 4, count: bool = True, objects: bool = False, out: Optional[Dict] = None, n: Optional[int] = None,
+                      sort: bool = False, mask=None) -> Dict:
+        """What n oriented boxes touch in the frame the context holds (rtx_query_overlap): boxes = float32 torch tensor (n, 10) of (centre,
+        half extents, rotation quaternion x y z w — update_instances' convention, normalised by the library) on this context's GPU.  Returns
+        {"object_id": (n, K), "triangle_id": (n, K), "count": (n,)} int32, K = max_hits in [1, 8]: the K smallest (object, triangle slot)
+        overlaps of every row in ascending order, entries past the count -1, triangle_id -1 for spheres and planes; "count" (unless
+        count=False) is the number of all overlaps and may exceed K.  objects=True (RTX_OVERLAP_OBJECTS): the distinct objects — an instance
+        counts once — and no "triangle_id".  max_hits=0 gives the count alone.  A triangle overlaps when the box touches it (touching
+        counts), a sphere when its shell meets the box, a plane when the box reaches it; a dead row (a non-finite float, a negative half
+        extent, a zero quaternion) overlaps nothing; zero half extents are fine.  out = {name: tensor} supplies the tensors.  Queued on
+        torch's current stream, checked like query_nearest; sort=True (RTX_QUERY_SORT): the rows are walked in the Morton order of their
+        centres, same answers row for row.  Raw device pointers: boxes = address, n, out = {name: address} for every output.  mask: as for
+        query_nearest — hidden objects are neither listed nor counted."""
+        if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)):
+            raise TypeError(f"max_hits must be an int, not {type(max_hits).__name__}")
+        K = int(max_hits)
+        if not 0 <= K <= RTX_QUERY_MAX_HITS:
+            raise ValueError(f"max_hits must be in [0, {RTX_QUERY_MAX_HITS}], not {K}")
+        if K == 0 and not count:
+            raise ValueError("max_hits=0 is the count-only form: count must be True")
+        wanted = (("object_id",) + (() if objects else ("triangle_id",)) if K else ()) + (("count",) if count else ())
+        return self._query_overlap(boxes, K, bool(count), RTX_OVERLAP_OBJECTS if objects else 0, out, n, sort, mask, wanted)
+
+    def query_overlapped(self, boxes, out=None, n: Optional[int] = None, sort: bool = False, mask=None):
+        """Whether each of n oriented boxes touches anything (rtx_query_overlap with RTX_OVERLAP_ANY): the int32 tensor (n,) of 1 / 0 (out,
+        or a new one) — the sibling of query_occluded; a row's walk ends at its first overlap.  boxes, sort, mask, raw pointers and checks
+        as for query_overlap; grid_boxes() makes the rows of a voxel grid."""
+        if out is None and isinstance(boxes, (int, np.integer)) and not isinstance(boxes, bool):
+            raise ValueError("with raw device pointers out must be the address of the result")
+        return self._query_overlap(boxes, 0, True, RTX_OVERLAP_ANY, None if out is None else {"count": out}, n, sort, mask, ("count",))["count"]
 
     def debug_query_order(self, rows, n: Optional[int] = None):
         """The order sort=True traces the rows in (rtx_debug_query_order): rows = float32 torch tensor (n, 6) of rays, (n, 7) of segments or (n, 4) of

@@ -28,8 +28,9 @@ EXPORTS = ["rtxh_camera_basis", "rtxh_camera_update", "rtxh_quaternion_axis_angl
            "rtxh_query_sweep", "rtxh_query_sweep_exhaustive", "rtxh_sweep_bound", "rtxh_sweep_triangle", "rtxh_sweep_sphere", "rtxh_sweep_plane",
            "rtxh_query_nearest_filtered", "rtxh_query_nearest_exhaustive_filtered", "rtxh_query_hits_filtered", "rtxh_query_hits_exhaustive_filtered",
            "rtxh_query_sweep_filtered", "rtxh_query_sweep_exhaustive_filtered", "rtxh_blas_pseudonormals",
-           "rtxh_query_signed_distance", "rtxh_query_signed_distance_filtered", "rtxh_query_signed_distance_exhaustive", "rtxh_query_signed_distance_exhaustive_filtered"]
-FLOAT_EXPORTS = ("rtxh_nearest_distance_bound", "rtxh_nearest_box_d2", "rtxh_nearest_triangle_d2", "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2", "rtxh_hits_margin", "rtxh_sweep_bound")      # return a float, not a status
+           "rtxh_query_signed_distance", "rtxh_query_signed_distance_filtered", "rtxh_query_signed_distance_exhaustive", "rtxh_query_signed_distance_exhaustive_filtered",
+           "rtxh_query_overlap", "rtxh_query_overlap_exhaustive", "rtxh_query_overlap_filtered", "rtxh_query_overlap_exhaustive_filtered", "rtxh_overlap_margin"]
+FLOAT_EXPORTS = ("rtxh_nearest_distance_bound", "rtxh_nearest_box_d2", "rtxh_nearest_triangle_d2", "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2", "rtxh_hits_margin", "rtxh_sweep_bound", "rtxh_overlap_margin")      # return a float, not a status
 
 PI = np.float32(3.14159265359)          # Util.h:8
 
@@ -139,6 +140,11 @@ def lib():
         l.rtxh_query_signed_distance_exhaustive.argtypes = l.rtxh_query_nearest_exhaustive.argtypes[:5] + side3
         l.rtxh_query_signed_distance_filtered.argtypes = l.rtxh_query_signed_distance.argtypes + masks3
         l.rtxh_query_signed_distance_exhaustive_filtered.argtypes = l.rtxh_query_signed_distance_exhaustive.argtypes + masks3
+        l.rtxh_query_overlap.argtypes = [C.POINTER(RtxhNearestScene), vp, C.c_int64, i32, vp, vp, vp, C.c_uint32, C.POINTER(i32)]
+        l.rtxh_query_overlap_exhaustive.argtypes = [C.POINTER(RtxhNearestScene), vp, C.c_int64, i32, vp, vp, vp, C.c_uint32]
+        l.rtxh_query_overlap_filtered.argtypes = l.rtxh_query_overlap.argtypes + masks3
+        l.rtxh_query_overlap_exhaustive_filtered.argtypes = l.rtxh_query_overlap_exhaustive.argtypes + masks3
+        l.rtxh_overlap_margin.argtypes = [C.c_float, C.c_float, C.c_float]
         l.rtxh_sweep_bound.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float]
         l.rtxh_sweep_triangle.argtypes = [vp, vp, C.c_float, C.c_float, vp, vp, vp, vp]
         l.rtxh_sweep_sphere.argtypes = [vp, vp, C.c_float, vp, vp, vp]
@@ -753,6 +759,71 @@ def query_sweep(scene, sweeps, channels=("distance",), blas=None, mask=None, obj
 def query_sweep_exhaustive(scene, sweeps, channels=("distance",), blas=None, mask=None, object_masks=None) -> dict:
     """rtxh_query_sweep_exhaustive: the same candidate functions over every primitive with no box test, the same order rule."""
     return _query_nearest("rtxh_query_sweep_exhaustive", scene, sweeps, channels, blas, False, 8, "sweeps", mask, object_masks)
+
+
+# ---- box-overlap queries on the host (include/rtx_host.h: rtxh_query_overlap / rtxh_query_overlap_exhaustive) -----------------------------
+RTX_OVERLAP_OBJECTS = 512
+RTX_OVERLAP_ANY = 1024
+
+
+def _query_overlap(scene, boxes, max_hits, count, objects, any_form, blas, exhaustive, mask, object_masks):
+    bx = np.asarray(boxes)
+    if bx.ndim != 2 or bx.shape[1] != 10 or bx.shape[0] < 1:
+        raise ValueError(f"boxes must have shape (n, 10) with n >= 1, not {bx.shape}")
+    if bx.dtype != np.float32:
+        raise TypeError(f"boxes must be float32, not {bx.dtype}")
+    bx = np.ascontiguousarray(bx)
+    if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)):
+        raise TypeError(f"max_hits must be an int, not {type(max_hits).__name__}")
+    K = int(max_hits)
+    if not 0 <= K <= 8:
+        raise ValueError(f"max_hits must be in [0, 8], not {max_hits}")
+    if K == 0 and not count:
+        raise ValueError("max_hits=0 is the count-only form: count must be True")
+    s, keep = nearest_scene(scene, blas)
+    n = bx.shape[0]
+    out = {}
+    if K > 0:
+        out["object_id"] = np.zeros((n, K), np.int32)
+        if not objects:
+            out["triangle_id"] = np.zeros((n, K), np.int32)
+    cnt = np.zeros(n, np.int32) if count else None
+    flags = RTX_OVERLAP_ANY if any_form else RTX_OVERLAP_OBJECTS if objects else 0
+    high = C.c_int32(0)
+    filt = _filter_args(s, n, mask, object_masks)
+    ptr = lambda name: out[name].ctypes.data if name in out else None
+    args = [C.byref(s), bx.ctypes.data, n, K, ptr("object_id"), ptr("triangle_id"), cnt.ctypes.data if count else None, flags] + ([] if exhaustive else [C.byref(high)])
+    fn_name = "rtxh_query_overlap_exhaustive" if exhaustive else "rtxh_query_overlap"
+    if filt:
+        fn_name += "_filtered"
+        args += filt[0]
+    rc = getattr(lib(), fn_name)(*args)
+    if rc:
+        raise ValueError(f"{fn_name} failed with status {rc}")
+    if count:
+        out["count"] = cnt
+    if not exhaustive:
+        out["stack_max"] = int(high.value)
+    return out
+
+
+def query_overlap(scene, boxes, max_hits=4, count=True, objects=False, blas=None, exhaustive=False, mask=None, object_masks=None) -> dict:
+    """rtxh_query_overlap: what Renderer.query_overlap writes on the device for boxes float32 (n, 10) of (centre, half extents, quaternion
+    x y z w), from the same code (csrc/rtx_overlap_math.h) -> {"object_id": (n, K), "triangle_id": (n, K) (absent with objects=True),
+    "count": (n,) if count, "stack_max"}; max_hits=0 gives the count alone.  exhaustive=True: rtxh_query_overlap_exhaustive, every primitive
+    with no node test (no "stack_max").  scene and blas as for query_nearest, mask / object_masks as there."""
+    return _query_overlap(scene, boxes, max_hits, count, bool(objects), False, blas, bool(exhaustive), mask, object_masks)
+
+
+def query_overlapped(scene, boxes, blas=None, exhaustive=False, mask=None, object_masks=None) -> np.ndarray:
+    """The ANY form (RTX_OVERLAP_ANY): int32 (n,) of 0 / 1, what Renderer.query_overlapped writes."""
+    return _query_overlap(scene, boxes, 0, True, False, True, blas, bool(exhaustive), mask, object_masks)["count"]
+
+
+def overlap_margin(local_scale, world_scale=0.0, kappa=1.0) -> float:
+    """rtxop::margin of csrc/rtx_overlap_math.h: how far, as a distance, the computed triangle test may be from the exact one on an axis of
+    conditioning kappa."""
+    return float(lib().rtxh_overlap_margin(C.c_float(float(local_scale)), C.c_float(float(world_scale)), C.c_float(float(kappa))))
 
 
 def sweep_bound(local_scale, world_scale=0.0, travelled=0.0, radius=0.0) -> float:

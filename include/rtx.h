@@ -922,6 +922,42 @@ int rtx_query_signed_distance(rtx_ctx * ctx, const void * points_dev /* [n][4] f
                               int32_t * feature_dev /* [n] or NULL */, uint32_t flags /* RTX_QUERY_SORT or 0 */,
                               const rtx_query_filter * filter /* NULL: unfiltered */);
 
+/* ---- box-overlap queries ----------------------------------------------------------------------------------------------------------------
+ * "What does this volume touch": a collision proxy (is this oriented box free), a trigger volume or broad phase (which objects are in this
+ * region), voxelisation (one box per voxel: occupancy, conservative voxelisation, surface-voxel counts), a gather (which triangles lie under
+ * this footprint).  rtx_query_overlap: row i = boxes_dev[10i .. 10i+9] = (centre c, half extents h, rotation quaternion x, y, z, w — the
+ * convention of rtx_update_instances; normalised by the library).  A row is live when all ten floats are finite, every half extent is >= 0
+ * (zero is allowed: a point, a segment, a rectangle) and the quaternion is not zero; a dead row overlaps nothing.  Surfaces are what the
+ * query family measures everywhere: a triangle overlaps by the 13-axis separating-axis test (touching is overlapping), a sphere when its
+ * shell meets the box (a box strictly inside the ball does not overlap), a plane when the box reaches it.  Everything is specified in the
+ * header comment of csrc/rtx_overlap_math.h (ROW, TRIANGLE, SPHERE, PLANE, NODE, ORDER, WALK, FORMS, MARGIN, PROMISED); rtxh_query_overlap in
+ * rtx_host.h gives the same bits.  Like rtx_query_nearest the test runs in each instance's local frame: exact for rigid poses.
+ * Three forms, chosen by flags:
+ *   0                      the (object, triangle slot) overlaps of every row, ordered by (object_id, triangle_id) ascending — object ids in
+ *                          the numbering of RTX_QUERY_OBJECT_ID, triangle_id -1 for spheres and planes: object_id_dev / triangle_id_dev
+ *                          [n][max_hits] hold the max_hits smallest (either may be NULL), entries past the count -1; count_dev[n] (or NULL)
+ *                          the number of all overlaps of the row, which may exceed max_hits.
+ *   RTX_OVERLAP_OBJECTS    the distinct objects: an instance counts once, however many of its triangles overlap.  triangle_id_dev must be NULL.
+ *   RTX_OVERLAP_ANY        count_dev[i] = 1 if anything overlaps, else 0; the walk of a row ends at its first overlap.  max_hits must be 0.
+ * max_hits in [0, RTX_QUERY_MAX_HITS]; max_hits == 0 is the count-only form and needs count_dev; max_hits > 0 needs at least one id array.
+ * Any n >= 1, in rounds of RTX_QUERY_CHUNK_RAYS rows, one kernel launch per round.  RTX_QUERY_SORT: the rows of a round are walked in the
+ * Morton order of their centres (the position key of rtx_query_nearest over the first three floats of a row); the answers come back in the
+ * caller's order, bit for bit those of the unsorted call.  The call runs on the context's stream; nothing is read back, frames, render calls
+ * and rtx_get_stats are unchanged.  rtx_query_overlap_filtered: the same with the object masks of the filtered queries above — a hidden
+ * object is neither listed nor counted, a row whose mask is 0 overlaps nothing.
+ * Errors, in this order: RTX_ERR_INVALID_ARG: a NULL ctx; max_hits outside [0, RTX_QUERY_MAX_HITS]; RTX_OVERLAP_ANY with max_hits != 0 or
+ * with RTX_OVERLAP_OBJECTS; RTX_OVERLAP_OBJECTS with a triangle_id_dev; max_hits == 0 without a count_dev; max_hits > 0 without an id array;
+ * a NULL boxes_dev, n < 1; any flag but RTX_QUERY_SORT, RTX_OVERLAP_OBJECTS, RTX_OVERLAP_ANY.  Then RTX_ERR_STATE and RTX_ERR_LIMIT as for
+ * rtx_query_nearest, its stack rule included, and the state rule of the filtered queries.  An error queues nothing.
+ * Out of scope: capsules, spheres and convex hulls as query volumes, swept boxes, penetration depth or contact points, more than
+ * RTX_QUERY_MAX_HITS entries per row, the rtx_group_* path.                                                                              */
+enum { RTX_OVERLAP_OBJECTS = 512, RTX_OVERLAP_ANY = 1024 };      /* bits of rtx_query_overlap's flags, beside RTX_QUERY_SORT */
+int rtx_query_overlap(rtx_ctx * ctx, const void * boxes_dev /* [n][10] f32: centre, half extents, quaternion */, int64_t n, int32_t max_hits,
+                      int32_t * object_id_dev /* [n][max_hits] or NULL */, int32_t * triangle_id_dev /* [n][max_hits] or NULL */,
+                      int32_t * count_dev /* [n] or NULL */, uint32_t flags /* RTX_QUERY_SORT, RTX_OVERLAP_OBJECTS, RTX_OVERLAP_ANY or 0 */);
+int rtx_query_overlap_filtered(rtx_ctx * ctx, const void * boxes_dev, int64_t n, int32_t max_hits, int32_t * object_id_dev, int32_t * triangle_id_dev,
+                               int32_t * count_dev, uint32_t flags, const rtx_query_filter * filter);
+
 /* Timing of every kernel launched since rtx_enable_kernel_timing(ctx, 1),
  * measured with HIP events on the stream the kernels are launched on.
  * names/ms hold up to `capacity` entries; *count receives the number of

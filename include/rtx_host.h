@@ -268,6 +268,27 @@ int rtxh_sweep_triangle(const float origin[3], const float direction[3], float r
 int rtxh_sweep_sphere(const float origin[3], const float direction[3], float radius, const rtx_sphere * sphere, float * t_out, float * d20_out);
 int rtxh_sweep_plane(const float origin[3], const float direction[3], float radius, const rtx_plane * plane, float * t_out, float * d20_out);
 
+/* rtx_query_overlap (include/rtx.h) on the host, by the code the kernel runs (csrc/rtx_overlap_math.h, whose header comment is the
+ * specification: the row, the triangle / sphere / plane / node tests, the order, the walk, the three forms, the margin, what is promised).  The
+ * scene is rtxh_nearest_scene; boxes: n x 10 floats (centre, half extents, quaternion); max_hits, the id arrays, count_out and flags as for
+ * rtx_query_overlap, with host pointers and K = max_hits entries per row (RTX_QUERY_SORT is accepted and changes nothing); the answers are the
+ * device's bit for bit.  stack_max_out (may be NULL): the most stack entries any row held.
+ * rtxh_query_overlap_exhaustive: every sphere, plane and (instance, slot) tested with no node test, the same functions and the same order
+ * rule; count_out is the number of all overlaps.  Every overlap the walk lists is in the exhaustive list, and the walk's count never exceeds
+ * the exhaustive one.  The _filtered forms take object_masks, row_masks and row_mask as the filtered walk queries below.
+ * rtxh_overlap_margin(S, W, kappa): rtxop::margin, how far as a distance the computed triangle test may be from the exact one on an axis of
+ * conditioning kappa (MARGIN in that header).
+ * RTX_ERR_INVALID_ARG: the argument rules of rtx_query_overlap and rtxh_query_nearest; RTX_ERR_LIMIT: a tree deeper than RTX_MAX_STACK entries. */
+int rtxh_query_overlap(const rtxh_nearest_scene * scene, const float * boxes, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
+                       int32_t * count_out, uint32_t flags, int32_t * stack_max_out);
+int rtxh_query_overlap_exhaustive(const rtxh_nearest_scene * scene, const float * boxes, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
+                                  int32_t * count_out, uint32_t flags);
+int rtxh_query_overlap_filtered(const rtxh_nearest_scene * scene, const float * boxes, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
+                                int32_t * count_out, uint32_t flags, int32_t * stack_max_out, const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask);
+int rtxh_query_overlap_exhaustive_filtered(const rtxh_nearest_scene * scene, const float * boxes, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
+                                           int32_t * count_out, uint32_t flags, const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask);
+float rtxh_overlap_margin(float local_scale, float world_scale, float kappa);
+
 /* The filtered walk queries (include/rtx.h: filtered queries) on the host: the same walks with FILTER's predicates of csrc/rtx_nearest_math.h,
  * so they give the device's bits.  The arguments of the function without the suffix, then object_masks (M = instance_count + sphere_count +
  * plane_count masks in the numbering of RTX_AOV_OBJECT_ID, or NULL: all ones), row_masks (n masks, or NULL: row_mask for every row) and
