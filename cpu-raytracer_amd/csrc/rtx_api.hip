@@ -2210,7 +2210,7 @@ extern "C" int rtx_debug_group_loopback(rtx_ctx * c, int32_t world, uint32_t fla
 // [rocPRIM's temporary storage], 2 x 8 bytes per slot and what rocPRIM asks for a round of that many keys (a host-side query).  Both blocks
 // grow in the one branch that waits; a context that never sorts never allocates the second.
 struct QuerySort { uint64_t * keys_in, * keys; uint32_t * bounds; void * tmp; size_t tmp_bytes; };
-static int query_queues(rtx_ctx * c, int64_t n, DevQueues & q, QuerySort * sort = nullptr, bool rays = true) {      // rays = false: only the sort block (rtx_query_nearest has no queue set)
+static int query_queues(rtx_ctx * c, int64_t n, DevQueues * qp, QuerySort * sort = nullptr) {      // qp == null: only the sort block (the walk queries have no queue set)
     const int64_t rows = n < (int64_t)RTX_QUERY_CHUNK_RAYS ? n : (int64_t)RTX_QUERY_CHUNK_RAYS;
     const int32_t cap = (int32_t)((rows + RTX_WAVE - 1) & ~(int64_t)(RTX_WAVE - 1));      // whole packets: the fill marks the tail of the last one
     size_t sort_tmp = 0;
@@ -2221,7 +2221,7 @@ static int query_queues(rtx_ctx * c, int64_t n, DevQueues & q, QuerySort * sort 
         if (last > sort_tmp) sort_tmp = last;
     }
     const bool grow_sort = sort && (cap > c->query_sort_cap || sort_tmp > c->query_sort_tmp);
-    const bool grow_rays = rays && cap > c->query_cap;
+    const bool grow_rays = qp && cap > c->query_cap;
     if (grow_rays || grow_sort) {                          // growth: queued queries still use the old buffers
         HIP_OK(c, hipStreamSynchronize(c->stream));
         if (grow_rays) {
@@ -2248,7 +2248,8 @@ static int query_queues(rtx_ctx * c, int64_t n, DevQueues & q, QuerySort * sort 
         sort->keys_in = (uint64_t *)(sb + off[0]); sort->keys = (uint64_t *)(sb + off[1]); sort->bounds = (uint32_t *)(sb + off[2]);
         sort->tmp = sb + off[3]; sort->tmp_bytes = c->query_sort_tmp;
     }
-    if (!rays) return RTX_OK;
+    if (!qp) return RTX_OK;
+    DevQueues & q = *qp;
     q = c->q;                                              // the walkers' knobs (thresholds, spill_threads) as rtx_create read them
     for (int d = 0; d <= RTX_MAX_LEVELS; d++) { q.level_base[d] = 0; q.level_cap[d] = d < 2 ? c->query_cap : 0; q.shadow_base[d] = 0; q.stats_n[d] = 0; }
     q.first_tile = 0; q.tile_stride = 1; q.tile_count = 0; q.primary_slots = 0;
@@ -2306,7 +2307,7 @@ static int query_setup(rtx_ctx * c, const void * in, int64_t n, const void * out
     if (int bad = query_checks(c, in, n, out, flags, what)) return bad;
     hipSetDevice(c->cfg.device);
     const bool sorted = (flags & RTX_QUERY_SORT) != 0;
-    if (int rc = query_queues(c, n, k.q, sorted ? &k.S : nullptr)) return rc;
+    if (int rc = query_queues(c, n, &k.q, sorted ? &k.S : nullptr)) return rc;
     k.order = sorted ? k.S.keys : nullptr;
     k.lane = (flags & RTX_RENDER_LANE_TRACE) != 0;
     bool pk_closest = (flags & RTX_RENDER_PACKET_CLOSEST) != 0;
@@ -2316,15 +2317,31 @@ static int query_setup(rtx_ctx * c, const void * in, int64_t n, const void * out
     return RTX_OK;
 }
 
-// The rounds of a call over n rows: round(first, m) queues rows [first, first + m), m <= RTX_QUERY_CHUNK_RAYS, back to back
-template <typename F> static int query_rounds(rtx_ctx * c, DevQueues & q, int64_t n, F && round) {
+// The rounds of a call over n rows: round(first, m) queues rows [first, first + m), m <= RTX_QUERY_CHUNK_RAYS, back to back.  q: the call's
+// queue set, null for the walk queries, which have none
+template <typename F> static int query_rounds(rtx_ctx * c, DevQueues * q, int64_t n, F && round) {
     for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
         const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
-        q.tile_count = (m + 1023) / 1024;
+        if (q) q->tile_count = (m + 1023) / 1024;
         if (int rc = round(first, m)) return rc;
     }
     HIP_OK(c, hipGetLastError());
     return RTX_OK;
+}
+// The channel targets of the round that starts at caller row `first`: the requested arrays of `out` advanced to that row, K elements per row
+// (rtx_query_hits: max_hits); null = not requested.  K == 0 is a count-only call: no targets, and `out` is not read
+static DevQuery query_targets(uint32_t channels, const rtx_query_buffers * out, int64_t first, int64_t K = 1) {
+    DevQuery t = {};
+    if (K == 0) return t;
+    auto at = [&](uint32_t bit, auto * array, int width) { return (channels & bit) && array ? array + width * K * first : nullptr; };
+    t.distance = at(RTX_QUERY_DISTANCE, out->distance, 1);
+    t.position = at(RTX_QUERY_POSITION, out->position, 3);
+    t.normal = at(RTX_QUERY_NORMAL, out->normal, 3);
+    t.uv = at(RTX_QUERY_UV, out->uv, 2);
+    t.material_id = at(RTX_QUERY_MATERIAL_ID, out->material_id, 1);
+    t.object_id = at(RTX_QUERY_OBJECT_ID, out->object_id, 1);
+    t.triangle_id = at(RTX_QUERY_TRIANGLE_ID, out->triangle_id, 1);
+    return t;
 }
 // the grid of a fill: the m rows of a round rounded up to whole packets
 static dim3 query_fill_grid(int m) { return dim3((((m + RTX_WAVE - 1) & ~(RTX_WAVE - 1)) + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK); }
@@ -2356,16 +2373,8 @@ extern "C" int rtx_query_closest(rtx_ctx * c, const void * rays_dev, int64_t n, 
     QueryCall k;
     if (int rc = query_setup(c, rays_dev, n, out, flags, "rtx_query_closest", k)) return rc;
     DevScene sc_resolve = k.sc; sc_resolve.diff_enabled = 0;        // the differentials are zero and no channel reports a RayHit differential
-    return query_rounds(c, k.q, n, [&](int64_t first, int m) -> int {
-        DevQuery t;
-        auto on = [&](uint32_t bit) { return (channels & bit) != 0; };
-        t.distance = on(RTX_QUERY_DISTANCE) && out->distance ? out->distance + first : nullptr;
-        t.position = on(RTX_QUERY_POSITION) && out->position ? out->position + 3 * first : nullptr;
-        t.normal = on(RTX_QUERY_NORMAL) && out->normal ? out->normal + 3 * first : nullptr;
-        t.uv = on(RTX_QUERY_UV) && out->uv ? out->uv + 2 * first : nullptr;
-        t.material_id = on(RTX_QUERY_MATERIAL_ID) && out->material_id ? out->material_id + first : nullptr;
-        t.object_id = on(RTX_QUERY_OBJECT_ID) && out->object_id ? out->object_id + first : nullptr;
-        t.triangle_id = on(RTX_QUERY_TRIANGLE_ID) && out->triangle_id ? out->triangle_id + first : nullptr;
+    return query_rounds(c, &k.q, n, [&](int64_t first, int m) -> int {
+        const DevQuery t = query_targets(channels, out, first);
         if (int rc = query_closest_round(c, k, (const float *)rays_dev + 6 * first, m)) return rc;
         launch_timed(c, "k_query_resolve", c->stream, [&] { hipLaunchKernelGGL(k_query_resolve, dim3((m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc_resolve, k.q, m, t, k.order); });
         return RTX_OK;
@@ -2375,7 +2384,7 @@ extern "C" int rtx_query_closest(rtx_ctx * c, const void * rays_dev, int64_t n, 
 extern "C" int rtx_query_occluded(rtx_ctx * c, const void * segments_dev, int64_t n, int32_t * occluded_dev, uint32_t flags) {
     QueryCall k;
     if (int rc = query_setup(c, segments_dev, n, occluded_dev, flags, "rtx_query_occluded", k)) return rc;
-    return query_rounds(c, k.q, n, [&](int64_t first, int m) { return query_occluded_round(c, k, (const float *)segments_dev + 7 * first, m, occluded_dev + first); });
+    return query_rounds(c, &k.q, n, [&](int64_t first, int m) { return query_occluded_round(c, k, (const float *)segments_dev + 7 * first, m, occluded_dev + first); });
 }
 
 // the grid limit of the walk queries (k_query_nearest, k_query_hits, k_query_sweep, k_query_overlap): the spill regions are indexed by the global thread id;
@@ -2464,13 +2473,68 @@ static QueryMasks<true> filter_masks(const rtx_ctx * c, const rtx_query_filter *
     return k;
 }
 
+// ---- the walk queries' frame on the host: rtx_query_nearest / _signed_distance / _hits / _sweep / _overlap (kernels' frame: rtx_nearest.h) --
+// n rows in device memory against the frame the context holds: per round of at most RTX_QUERY_CHUNK_RAYS rows ONE launch of the call's
+// kernel, which reads the rows and writes the outputs; with RTX_QUERY_SORT the bounds, key and sort launches of the ray queries run first over
+// the rows' key floats, in the same sort block.  No queue set, no counters: nothing a render call or rtx_get_stats reads is touched.  The
+// stack lives in LDS and in the context's spill buffer, as for a closest-hit launch of this stream; all calls share one tile counter (they
+// are ordered by the stream).
+// The stack rule: a descent holds at most rtxnp::stack_need(TLAS inner depth, deepest BLAS inner depth) entries; a scene that needs more than
+// rtx_config.stack_size (itself <= RTX_MAX_STACK, what LDS and the spill region hold per lane) is refused here, on the host.
+// What a call decides once for all its rounds: the sort block and the sorted keys of a round (order; null = the caller's order), the tile
+// counter (head; null only for rtx_query_nearest under RTX_NEAREST_FETCH=0), the scene by value, the spill buffer and the grid limit it sets, the filter (null: none).
+struct WalkCall { QuerySort S; const uint64_t * order; uint32_t * head; DevScene sc; int32_t * spill; int spill_threads, max_blocks; const rtx_query_filter * filter; };
+// after the call's own argument checks and query_checks, in this order: the stack rule, the filter's state rule, then what allocates
+// (rtx_query_signed_distance brings its side tables up to date behind it: side_table_current, which allocates and queues a copy, now
+// follows the tile counter's allocation; before, it came between the sort block and the counter)
+static int walk_setup(rtx_ctx * c, const char * what, const char * descent_word, int64_t n, uint32_t flags, const rtx_query_filter * filter, WalkCall & k, bool counter = true) {
+    int blas_depth = -1;
+    for (size_t b = 0; b < c->blas.size(); b++) if (c->h_blas[b].nodes && c->blas[b].inner_depth > blas_depth) blas_depth = c->blas[b].inner_depth;
+    const int need = rtxnp::stack_need(c->tlas_inner_depth, blas_depth), have = c->cfg.stack_size < RTX_MAX_STACK ? c->cfg.stack_size : RTX_MAX_STACK;
+    if (need > have) {
+        c->err = std::string(what) + ": the " + descent_word + " needs " + std::to_string(need) + " stack entries (TLAS inner depth " + std::to_string(c->tlas_inner_depth) +
+                 " + 1, BLAS inner depth " + std::to_string(blas_depth) + " + 1), rtx_config.stack_size allows " + std::to_string(have);
+        return RTX_ERR_LIMIT;
+    }
+    if (int bad = filter_checks(c, filter, what)) return bad;
+    hipSetDevice(c->cfg.device);
+    k.S = {};
+    k.order = nullptr;
+    if (flags & RTX_QUERY_SORT) {
+        if (int rc = query_queues(c, n, nullptr, &k.S)) return rc;
+        k.order = k.S.keys;
+    }
+    if (counter) if (int rc = ensure(c, c->d_nearest_head, sizeof(uint32_t))) return rc;      // the first call only
+    k.head = counter ? (uint32_t *)c->d_nearest_head.p : nullptr;
+    k.sc = c->scene;
+    k.spill = (int32_t *)c->d_spill.p; k.spill_threads = c->q.spill_threads;
+    k.max_blocks = query_max_blocks(c);
+    k.filter = filter;
+    return RTX_OK;
+}
+// The rounds of a walk query over n rows of ROW floats (sort key: the first KEY): the sort, the grid and the counter's reset of every round,
+// then launch(first, rows, m, blocks) for the one kernel launch over rows [first, first + m) at `rows`
+template <int ROW, int KEY = ROW, typename F> static int walk_rounds(rtx_ctx * c, const WalkCall & k, const void * rows_dev, int64_t n, F && launch) {
+    return query_rounds(c, nullptr, n, [&](int64_t first, int m) -> int {
+        const float * const rows = (const float *)rows_dev + ROW * first;
+        if (k.order) if (int rc = query_sort_round<ROW, KEY>(c, k.S, rows, m)) return rc;
+        const int tiles = (m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK, blocks = tiles < k.max_blocks ? tiles : k.max_blocks;
+        if (k.head) HIP_OK(c, hipMemsetAsync(k.head, 0, sizeof(uint32_t), c->stream));
+        launch(first, rows, m, blocks);
+        return RTX_OK;
+    });
+}
+// The launch of the round that starts at caller row `first`, timed as `name`: kernel(masks) launches the instantiation for the type of
+// masks (its ::filtered is the template argument) — QueryMasks<true>, the filter's masks from that row on, or QueryMasks<false>
+template <typename Launch> static void walk_launch(rtx_ctx * c, const WalkCall & k, const char * name, int64_t first, Launch && kernel) {
+    launch_timed(c, name, c->stream, [&] {
+        if (k.filter) kernel(filter_masks(c, k.filter, first));
+        else kernel(QueryMasks<false>());
+    });
+}
+
 // ---- nearest-point queries (include/rtx.h: rtx_query_nearest; kernel in rtx_nearest.h, arithmetic and walk in rtx_nearest_math.h) ------
-// n points with a maximum distance each, in device memory, against the frame the context holds: per round of at most RTX_QUERY_CHUNK_RAYS
-// rows ONE launch of k_query_nearest, which reads the rows and writes the channels; with RTX_QUERY_SORT the bounds, key and sort launches of
-// the ray queries run first over the 4-float rows, in the same sort block.  No queue set, no counters: nothing a render call or rtx_get_stats
-// reads is touched.  The stack lives in LDS and in regions 0 and 1 of the context's spill buffer, as for a closest-hit launch of this stream.
-// The stack rule: the ordered descent holds at most rtxnp::stack_need(TLAS inner depth, deepest BLAS inner depth) entries; a scene that needs
-// more than rtx_config.stack_size (itself <= RTX_MAX_STACK, what LDS and the spill region hold per lane) is refused here, on the host.
+// The walk queries' frame over n points with a maximum distance each: k_query_nearest writes the channels; the sort key is the 4-float row.
 // rtx_query_signed_distance is the same call with two more outputs (sg: signed_dev [n], feature_dev [n] or null) and the SIGNED
 // instantiations; its channels may be empty, and then out may be null.
 struct QuerySigned { float * signed_dev; int32_t * feature_dev; };
@@ -2492,59 +2556,29 @@ static int side_table_current(rtx_ctx * c) {
 }
 static int query_nearest_impl(rtx_ctx * c, const void * points_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags, const rtx_query_filter * filter,
                               const QuerySigned * sg = nullptr) {
+    const char * const what = sg ? "rtx_query_signed_distance" : "rtx_query_nearest";
     if (c && sg) {
         if (channels & ~(uint32_t)RTX_QUERY_ALL) { c->err = "rtx_query_signed_distance: channels must be a subset of RTX_QUERY_ALL"; return RTX_ERR_INVALID_ARG; }
         if (!sg->signed_dev || (((uintptr_t)sg->signed_dev | (uintptr_t)sg->feature_dev) & 3)) { c->err = "rtx_query_signed_distance: null or misaligned signed-distance or feature pointer"; return RTX_ERR_INVALID_ARG; }
         static const rtx_query_buffers no_buffers = {};
         if (channels == 0 && !out) out = &no_buffers;                  // no channel bit is set: nothing of it is read
     } else if (c && (channels == 0 || (channels & ~(uint32_t)RTX_QUERY_ALL))) { c->err = "rtx_query_nearest: channels must be a non-empty subset of RTX_QUERY_ALL"; return RTX_ERR_INVALID_ARG; }
-    if (int bad = query_checks(c, points_dev, n, out, flags, sg ? "rtx_query_signed_distance" : "rtx_query_nearest", (uint32_t)RTX_QUERY_SORT)) return bad;
-    int blas_depth = -1;
-    for (size_t b = 0; b < c->blas.size(); b++) if (c->h_blas[b].nodes && c->blas[b].inner_depth > blas_depth) blas_depth = c->blas[b].inner_depth;
-    const int need = rtxnp::stack_need(c->tlas_inner_depth, blas_depth), have = c->cfg.stack_size < RTX_MAX_STACK ? c->cfg.stack_size : RTX_MAX_STACK;
-    if (need > have) {
-        c->err = "rtx_query_nearest: the ordered descent needs " + std::to_string(need) + " stack entries (TLAS inner depth " + std::to_string(c->tlas_inner_depth) +
-                 " + 1, BLAS inner depth " + std::to_string(blas_depth) + " + 1), rtx_config.stack_size allows " + std::to_string(have);
-        return RTX_ERR_LIMIT;
-    }
-    if (int bad = filter_checks(c, filter, sg ? "rtx_query_signed_distance" : "rtx_query_nearest")) return bad;
-    hipSetDevice(c->cfg.device);
-    const bool sorted = (flags & RTX_QUERY_SORT) != 0;
-    QuerySort S = {};
-    DevQueues unused;
-    if (sorted) if (int rc = query_queues(c, n, unused, &S, false)) return rc;
+    if (int bad = query_checks(c, points_dev, n, out, flags, what, (uint32_t)RTX_QUERY_SORT)) return bad;
+    WalkCall k;
+    if (int rc = walk_setup(c, what, "ordered descent", n, flags, filter, k, c->nearest_fetch)) return rc;
     if (sg) if (int rc = side_table_current(c)) return rc;
-    if (c->nearest_fetch) if (int rc = ensure(c, c->d_nearest_head, sizeof(uint32_t))) return rc;      // the first call only
-    uint32_t * const head = c->nearest_fetch ? (uint32_t *)c->d_nearest_head.p : nullptr;
-    const DevScene sc = c->scene;
-    const int max_blocks = query_max_blocks(c);
-    for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
-        const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
-        const float * const rows = (const float *)points_dev + 4 * first;
-        DevQuery t;
-        auto on = [&](uint32_t bit) { return (channels & bit) != 0; };
-        t.distance = on(RTX_QUERY_DISTANCE) && out->distance ? out->distance + first : nullptr;
-        t.position = on(RTX_QUERY_POSITION) && out->position ? out->position + 3 * first : nullptr;
-        t.normal = on(RTX_QUERY_NORMAL) && out->normal ? out->normal + 3 * first : nullptr;
-        t.uv = on(RTX_QUERY_UV) && out->uv ? out->uv + 2 * first : nullptr;
-        t.material_id = on(RTX_QUERY_MATERIAL_ID) && out->material_id ? out->material_id + first : nullptr;
-        t.object_id = on(RTX_QUERY_OBJECT_ID) && out->object_id ? out->object_id + first : nullptr;
-        t.triangle_id = on(RTX_QUERY_TRIANGLE_ID) && out->triangle_id ? out->triangle_id + first : nullptr;
-        if (sorted) if (int rc = query_sort_round<4>(c, S, rows, m)) return rc;
-        const int tiles = (m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK, blocks = tiles < max_blocks ? tiles : max_blocks;
-        const uint64_t * const order = sorted ? S.keys : nullptr;
-        if (head) HIP_OK(c, hipMemsetAsync(head, 0, sizeof(uint32_t), c->stream));
+    return walk_rounds<4>(c, k, points_dev, n, [&](int64_t first, const float * rows, int m, int blocks) {
+        const DevQuery t = query_targets(channels, out, first);
         QuerySide<true> ks = { nullptr, nullptr, nullptr };
         if (sg) { ks.blas = (const DevSideBlas *)c->d_side.p; ks.signed_out = sg->signed_dev + first; ks.feature = sg->feature_dev ? sg->feature_dev + first : nullptr; }
-        if (filter) {
-            const QueryMasks<true> km = filter_masks(c, filter, first);
-            if (sg) launch_timed(c, "k_query_nearest", c->stream, [&] { hipLaunchKernelGGL((k_query_nearest<true, true>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, km, ks); });
-            else launch_timed(c, "k_query_nearest", c->stream, [&] { hipLaunchKernelGGL((k_query_nearest<true, false>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, km, QuerySide<false>()); });
-        } else if (sg) launch_timed(c, "k_query_nearest", c->stream, [&] { hipLaunchKernelGGL((k_query_nearest<false, true>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, QueryMasks<false>(), ks); });
-        else launch_timed(c, "k_query_nearest", c->stream, [&] { hipLaunchKernelGGL((k_query_nearest<false, false>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, QueryMasks<false>(), QuerySide<false>()); });
-    }
-    HIP_OK(c, hipGetLastError());
-    return RTX_OK;
+        walk_launch(c, k, "k_query_nearest", first, [&](auto km) {
+            auto go = [&](auto side) {
+                hipLaunchKernelGGL((k_query_nearest<decltype(km)::filtered, decltype(side)::is_signed>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream,
+                                   k.sc, rows, m, t, k.order, k.spill, k.spill_threads, k.head, km, side);
+            };
+            if (sg) go(ks); else go(QuerySide<false>());
+        });
+    });
 }
 extern "C" int rtx_query_nearest(rtx_ctx * c, const void * points_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags) {
     return query_nearest_impl(c, points_dev, n, channels, out, flags, nullptr);
@@ -2559,10 +2593,8 @@ extern "C" int rtx_query_signed_distance(rtx_ctx * c, const void * points_dev, i
 }
 
 // ---- all-hits segment queries (include/rtx.h: rtx_query_hits; kernel in rtx_hits.h, arithmetic and walk in rtx_hits_math.h) ------------
-// n segments in device memory against the frame the context holds: per round of at most RTX_QUERY_CHUNK_RAYS rows ONE launch of k_query_hits,
-// which reads the rows and writes the first max_hits hits of every row, in order, and the row's count; with RTX_QUERY_SORT the bounds, key and
-// sort launches of the ray queries run first over the 7-float rows, in the same sort block.  No queue set, no counters; the stack as for
-// rtx_query_nearest, its stack rule, and its tile counter (the two calls are ordered by the stream).
+// The walk queries' frame over n segments: k_query_hits writes the first max_hits hits of every row, in order, and the row's count; the sort
+// key is the 7-float row.
 static int query_hits_impl(rtx_ctx * c, const void * segments_dev, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
                            int32_t * count_dev, uint32_t flags, const rtx_query_filter * filter) {
     if (c) {
@@ -2573,52 +2605,20 @@ static int query_hits_impl(rtx_ctx * c, const void * segments_dev, int64_t n, in
         }
     }
     if (int bad = query_checks(c, segments_dev, n, max_hits ? (const void *)out : (const void *)count_dev, flags, "rtx_query_hits", (uint32_t)RTX_QUERY_SORT)) return bad;
-    int blas_depth = -1;
-    for (size_t b = 0; b < c->blas.size(); b++) if (c->h_blas[b].nodes && c->blas[b].inner_depth > blas_depth) blas_depth = c->blas[b].inner_depth;
-    const int need = rtxnp::stack_need(c->tlas_inner_depth, blas_depth), have = c->cfg.stack_size < RTX_MAX_STACK ? c->cfg.stack_size : RTX_MAX_STACK;
-    if (need > have) {
-        c->err = "rtx_query_hits: the ordered descent needs " + std::to_string(need) + " stack entries (TLAS inner depth " + std::to_string(c->tlas_inner_depth) +
-                 " + 1, BLAS inner depth " + std::to_string(blas_depth) + " + 1), rtx_config.stack_size allows " + std::to_string(have);
-        return RTX_ERR_LIMIT;
-    }
-    if (int bad = filter_checks(c, filter, "rtx_query_hits")) return bad;
-    hipSetDevice(c->cfg.device);
-    const bool sorted = (flags & RTX_QUERY_SORT) != 0;
-    QuerySort S = {};
-    DevQueues unused;
-    if (sorted) if (int rc = query_queues(c, n, unused, &S, false)) return rc;
-    if (int rc = ensure(c, c->d_nearest_head, sizeof(uint32_t))) return rc;      // the first call only
-    uint32_t * const head = (uint32_t *)c->d_nearest_head.p;
-    const DevScene sc = c->scene;
-    const int max_blocks = query_max_blocks(c);
+    WalkCall k;
+    if (int rc = walk_setup(c, "rtx_query_hits", "ordered descent", n, flags, filter, k)) return rc;
     const int64_t K = max_hits;
-    for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
-        const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
-        const float * const rows = (const float *)segments_dev + 7 * first;
-        DevQuery t = {};
-        auto on = [&](uint32_t bit) { return K > 0 && (channels & bit) != 0; };
-        t.distance = on(RTX_QUERY_DISTANCE) && out->distance ? out->distance + K * first : nullptr;
-        t.position = on(RTX_QUERY_POSITION) && out->position ? out->position + 3 * K * first : nullptr;
-        t.normal = on(RTX_QUERY_NORMAL) && out->normal ? out->normal + 3 * K * first : nullptr;
-        t.uv = on(RTX_QUERY_UV) && out->uv ? out->uv + 2 * K * first : nullptr;
-        t.material_id = on(RTX_QUERY_MATERIAL_ID) && out->material_id ? out->material_id + K * first : nullptr;
-        t.object_id = on(RTX_QUERY_OBJECT_ID) && out->object_id ? out->object_id + K * first : nullptr;
-        t.triangle_id = on(RTX_QUERY_TRIANGLE_ID) && out->triangle_id ? out->triangle_id + K * first : nullptr;
+    return walk_rounds<7>(c, k, segments_dev, n, [&](int64_t first, const float * rows, int m, int blocks) {
+        const DevQuery t = query_targets(channels, out, first, K);
         int32_t * const count = count_dev ? count_dev + first : nullptr;
-        if (sorted) if (int rc = query_sort_round<7>(c, S, rows, m)) return rc;
-        const int tiles = (m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK, blocks = tiles < max_blocks ? tiles : max_blocks;
-        const uint64_t * const order = sorted ? S.keys : nullptr;
-        HIP_OK(c, hipMemsetAsync(head, 0, sizeof(uint32_t), c->stream));
-        if (filter) {
-            const QueryMasks<true> km = filter_masks(c, filter, first);
-            if (K > 0) launch_timed(c, "k_query_hits", c->stream, [&] { hipLaunchKernelGGL((k_query_hits<true, true>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, (int)K, t, count, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, km); });
-            else launch_timed(c, "k_query_hits", c->stream, [&] { hipLaunchKernelGGL((k_query_hits<false, true>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, 0, t, count, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, km); });
-        }
-        else if (K > 0) launch_timed(c, "k_query_hits", c->stream, [&] { hipLaunchKernelGGL((k_query_hits<true, false>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, (int)K, t, count, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, QueryMasks<false>()); });
-        else launch_timed(c, "k_query_hits", c->stream, [&] { hipLaunchKernelGGL((k_query_hits<false, false>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, 0, t, count, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, QueryMasks<false>()); });
-    }
-    HIP_OK(c, hipGetLastError());
-    return RTX_OK;
+        walk_launch(c, k, "k_query_hits", first, [&](auto km) {
+            auto go = [&](auto list) {
+                hipLaunchKernelGGL((k_query_hits<decltype(list)::value, decltype(km)::filtered>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream,
+                                   k.sc, rows, m, (int)K, t, count, k.order, k.spill, k.spill_threads, k.head, km);
+            };
+            if (K > 0) go(std::true_type()); else go(std::false_type());
+        });
+    });
 }
 extern "C" int rtx_query_hits(rtx_ctx * c, const void * segments_dev, int64_t n, int32_t max_hits, uint32_t channels, const rtx_query_buffers * out,
                               int32_t * count_dev, uint32_t flags) {
@@ -2630,54 +2630,19 @@ extern "C" int rtx_query_hits_filtered(rtx_ctx * c, const void * segments_dev, i
 }
 
 // ---- swept-sphere queries (include/rtx.h: rtx_query_sweep; kernel in rtx_sweep.h, arithmetic and walk in rtx_sweep_math.h) ------------
-// n sweeps in device memory against the frame the context holds: per round of at most RTX_QUERY_CHUNK_RAYS rows ONE launch of k_query_sweep,
-// which reads the rows and writes the channels; with RTX_QUERY_SORT the bounds, key and sort launches of the ray queries run first over the
-// first seven floats of the 8-float rows, in the same sort block.  No queue set, no counters; the stack as for rtx_query_nearest, its stack
-// rule, and its tile counter (the calls are ordered by the stream).
+// The walk queries' frame over n sweeps: k_query_sweep writes the channels; the sort key is the first seven floats of the 8-float rows.
 static int query_sweep_impl(rtx_ctx * c, const void * sweeps_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags, const rtx_query_filter * filter) {
     if (c && (channels == 0 || (channels & ~(uint32_t)RTX_QUERY_ALL))) { c->err = "rtx_query_sweep: channels must be a non-empty subset of RTX_QUERY_ALL"; return RTX_ERR_INVALID_ARG; }
     if (int bad = query_checks(c, sweeps_dev, n, out, flags, "rtx_query_sweep", (uint32_t)RTX_QUERY_SORT)) return bad;
-    int blas_depth = -1;
-    for (size_t b = 0; b < c->blas.size(); b++) if (c->h_blas[b].nodes && c->blas[b].inner_depth > blas_depth) blas_depth = c->blas[b].inner_depth;
-    const int need = rtxnp::stack_need(c->tlas_inner_depth, blas_depth), have = c->cfg.stack_size < RTX_MAX_STACK ? c->cfg.stack_size : RTX_MAX_STACK;
-    if (need > have) {
-        c->err = "rtx_query_sweep: the ordered descent needs " + std::to_string(need) + " stack entries (TLAS inner depth " + std::to_string(c->tlas_inner_depth) +
-                 " + 1, BLAS inner depth " + std::to_string(blas_depth) + " + 1), rtx_config.stack_size allows " + std::to_string(have);
-        return RTX_ERR_LIMIT;
-    }
-    if (int bad = filter_checks(c, filter, "rtx_query_sweep")) return bad;
-    hipSetDevice(c->cfg.device);
-    const bool sorted = (flags & RTX_QUERY_SORT) != 0;
-    QuerySort S = {};
-    DevQueues unused;
-    if (sorted) if (int rc = query_queues(c, n, unused, &S, false)) return rc;
-    if (int rc = ensure(c, c->d_nearest_head, sizeof(uint32_t))) return rc;      // the first call only
-    uint32_t * const head = (uint32_t *)c->d_nearest_head.p;
-    const DevScene sc = c->scene;
-    const int max_blocks = query_max_blocks(c);
-    for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
-        const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
-        const float * const rows = (const float *)sweeps_dev + 8 * first;
-        DevQuery t;
-        auto on = [&](uint32_t bit) { return (channels & bit) != 0; };
-        t.distance = on(RTX_QUERY_DISTANCE) && out->distance ? out->distance + first : nullptr;
-        t.position = on(RTX_QUERY_POSITION) && out->position ? out->position + 3 * first : nullptr;
-        t.normal = on(RTX_QUERY_NORMAL) && out->normal ? out->normal + 3 * first : nullptr;
-        t.uv = on(RTX_QUERY_UV) && out->uv ? out->uv + 2 * first : nullptr;
-        t.material_id = on(RTX_QUERY_MATERIAL_ID) && out->material_id ? out->material_id + first : nullptr;
-        t.object_id = on(RTX_QUERY_OBJECT_ID) && out->object_id ? out->object_id + first : nullptr;
-        t.triangle_id = on(RTX_QUERY_TRIANGLE_ID) && out->triangle_id ? out->triangle_id + first : nullptr;
-        if (sorted) if (int rc = query_sort_round<8, 7>(c, S, rows, m)) return rc;
-        const int tiles = (m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK, blocks = tiles < max_blocks ? tiles : max_blocks;
-        const uint64_t * const order = sorted ? S.keys : nullptr;
-        HIP_OK(c, hipMemsetAsync(head, 0, sizeof(uint32_t), c->stream));
-        if (filter) {
-            const QueryMasks<true> km = filter_masks(c, filter, first);
-            launch_timed(c, "k_query_sweep", c->stream, [&] { hipLaunchKernelGGL(k_query_sweep<true>, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, km); });
-        } else launch_timed(c, "k_query_sweep", c->stream, [&] { hipLaunchKernelGGL(k_query_sweep<false>, dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, t, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, QueryMasks<false>()); });
-    }
-    HIP_OK(c, hipGetLastError());
-    return RTX_OK;
+    WalkCall k;
+    if (int rc = walk_setup(c, "rtx_query_sweep", "ordered descent", n, flags, filter, k)) return rc;
+    return walk_rounds<8, 7>(c, k, sweeps_dev, n, [&](int64_t first, const float * rows, int m, int blocks) {
+        const DevQuery t = query_targets(channels, out, first);
+        walk_launch(c, k, "k_query_sweep", first, [&](auto km) {
+            hipLaunchKernelGGL((k_query_sweep<decltype(km)::filtered>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream,
+                               k.sc, rows, m, t, k.order, k.spill, k.spill_threads, k.head, km);
+        });
+    });
 }
 extern "C" int rtx_query_sweep(rtx_ctx * c, const void * sweeps_dev, int64_t n, uint32_t channels, const rtx_query_buffers * out, uint32_t flags) {
     return query_sweep_impl(c, sweeps_dev, n, channels, out, flags, nullptr);
@@ -2687,19 +2652,9 @@ extern "C" int rtx_query_sweep_filtered(rtx_ctx * c, const void * sweeps_dev, in
 }
 
 // ---- box-overlap queries (include/rtx.h: rtx_query_overlap; kernel in rtx_overlap.h, arithmetic and walk in rtx_overlap_math.h) ---------
-// n boxes in device memory against the frame the context holds: per round of at most RTX_QUERY_CHUNK_RAYS rows ONE launch of k_query_overlap,
-// which reads the rows and writes the ids of the max_hits smallest overlaps of every row and the row's count; with RTX_QUERY_SORT the bounds,
-// key and sort launches of the ray queries run first over the first four floats of the 10-float rows — the position key of rtx_query_nearest;
-// its fourth float is h.x here, so a box with h.x == 0 sorts with the dead rows, last, and is walked all the same — in the same sort block.
-// No queue set, no counters; the stack as for rtx_query_nearest (region 0 of the spill buffer only), its stack rule, and its tile counter
-// (the calls are ordered by the stream).
-template <int FORM> static void query_overlap_launch(rtx_ctx * c, const rtx_query_filter * filter, int64_t first, int blocks, const DevScene & sc, const float * rows, int m, int K,
-                                                     int32_t * object_id, int32_t * triangle_id, int32_t * count, const uint64_t * order, uint32_t * head) {
-    if (filter) {
-        const QueryMasks<true> km = filter_masks(c, filter, first);
-        launch_timed(c, "k_query_overlap", c->stream, [&] { hipLaunchKernelGGL((k_query_overlap<FORM, true>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, K, object_id, triangle_id, count, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, km); });
-    } else launch_timed(c, "k_query_overlap", c->stream, [&] { hipLaunchKernelGGL((k_query_overlap<FORM, false>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream, sc, rows, m, K, object_id, triangle_id, count, order, (int32_t *)c->d_spill.p, c->q.spill_threads, head, QueryMasks<false>()); });
-}
+// The walk queries' frame over n boxes: k_query_overlap writes the ids of the max_hits smallest overlaps of every row and the row's count.
+// The sort key is the first four floats of the 10-float rows — the position key of rtx_query_nearest; its fourth float is h.x here, so a box
+// with h.x == 0 sorts with the dead rows, last, and is walked all the same.  The stack uses region 0 of the spill buffer only.
 static int query_overlap_impl(rtx_ctx * c, const void * boxes_dev, int64_t n, int32_t max_hits, int32_t * object_id_dev, int32_t * triangle_id_dev, int32_t * count_dev,
                               uint32_t flags, const rtx_query_filter * filter) {
     const bool any = (flags & RTX_OVERLAP_ANY) != 0, objects = (flags & RTX_OVERLAP_OBJECTS) != 0;
@@ -2714,43 +2669,26 @@ static int query_overlap_impl(rtx_ctx * c, const void * boxes_dev, int64_t n, in
     }
     const void * const some_out = object_id_dev ? (const void *)object_id_dev : triangle_id_dev ? (const void *)triangle_id_dev : (const void *)count_dev;
     if (int bad = query_checks(c, boxes_dev, n, some_out, flags, "rtx_query_overlap", (uint32_t)RTX_QUERY_SORT | (uint32_t)RTX_OVERLAP_OBJECTS | (uint32_t)RTX_OVERLAP_ANY)) return bad;
-    int blas_depth = -1;
-    for (size_t b = 0; b < c->blas.size(); b++) if (c->h_blas[b].nodes && c->blas[b].inner_depth > blas_depth) blas_depth = c->blas[b].inner_depth;
-    const int need = rtxnp::stack_need(c->tlas_inner_depth, blas_depth), have = c->cfg.stack_size < RTX_MAX_STACK ? c->cfg.stack_size : RTX_MAX_STACK;
-    if (need > have) {
-        c->err = "rtx_query_overlap: the descent needs " + std::to_string(need) + " stack entries (TLAS inner depth " + std::to_string(c->tlas_inner_depth) +
-                 " + 1, BLAS inner depth " + std::to_string(blas_depth) + " + 1), rtx_config.stack_size allows " + std::to_string(have);
-        return RTX_ERR_LIMIT;
-    }
-    if (int bad = filter_checks(c, filter, "rtx_query_overlap")) return bad;
-    hipSetDevice(c->cfg.device);
-    const bool sorted = (flags & RTX_QUERY_SORT) != 0;
-    QuerySort S = {};
-    DevQueues unused;
-    if (sorted) if (int rc = query_queues(c, n, unused, &S, false)) return rc;
-    if (int rc = ensure(c, c->d_nearest_head, sizeof(uint32_t))) return rc;      // the first call only
-    uint32_t * const head = (uint32_t *)c->d_nearest_head.p;
-    const DevScene sc = c->scene;
-    const int max_blocks = query_max_blocks(c);
+    WalkCall k;
+    if (int rc = walk_setup(c, "rtx_query_overlap", "descent", n, flags, filter, k)) return rc;
     const int64_t K = max_hits;
-    for (int64_t first = 0; first < n; first += RTX_QUERY_CHUNK_RAYS) {
-        const int m = (int)(n - first < (int64_t)RTX_QUERY_CHUNK_RAYS ? n - first : (int64_t)RTX_QUERY_CHUNK_RAYS);
-        const float * const rows = (const float *)boxes_dev + rtxop::ROW_FLOATS * first;
-        int32_t * const object_id = K > 0 && object_id_dev ? object_id_dev + K * first : nullptr;
-        int32_t * const triangle_id = K > 0 && triangle_id_dev ? triangle_id_dev + K * first : nullptr;
+    return walk_rounds<rtxop::ROW_FLOATS, 4>(c, k, boxes_dev, n, [&](int64_t first, const float * rows, int m, int blocks) {
         int32_t * const count = count_dev ? count_dev + first : nullptr;
-        if (sorted) if (int rc = query_sort_round<rtxop::ROW_FLOATS, 4>(c, S, rows, m)) return rc;
-        const int tiles = (m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK, blocks = tiles < max_blocks ? tiles : max_blocks;
-        const uint64_t * const order = sorted ? S.keys : nullptr;
-        HIP_OK(c, hipMemsetAsync(head, 0, sizeof(uint32_t), c->stream));
-        if (any) query_overlap_launch<rtxop::FORM_ANY>(c, filter, first, blocks, sc, rows, m, 0, nullptr, nullptr, count, order, head);
-        else if (objects && K > 0) query_overlap_launch<rtxop::FORM_OBJECTS>(c, filter, first, blocks, sc, rows, m, (int)K, object_id, nullptr, count, order, head);
-        else if (objects) query_overlap_launch<rtxop::FORM_OBJECTS | OVERLAP_COUNT_ONLY>(c, filter, first, blocks, sc, rows, m, 0, nullptr, nullptr, count, order, head);
-        else if (K > 0) query_overlap_launch<rtxop::FORM_TRIANGLES>(c, filter, first, blocks, sc, rows, m, (int)K, object_id, triangle_id, count, order, head);
-        else query_overlap_launch<rtxop::FORM_TRIANGLES | OVERLAP_COUNT_ONLY>(c, filter, first, blocks, sc, rows, m, 0, nullptr, nullptr, count, order, head);
-    }
-    HIP_OK(c, hipGetLastError());
-    return RTX_OK;
+        // the kernel of form `form` with list length `held` (0: no list, and no ids); triangle ids only where the form reports them
+        auto go = [&](auto form, int held, bool triangles) {
+            int32_t * const object_id = held && object_id_dev ? object_id_dev + K * first : nullptr;
+            int32_t * const triangle_id = held && triangles && triangle_id_dev ? triangle_id_dev + K * first : nullptr;
+            walk_launch(c, k, "k_query_overlap", first, [&](auto km) {
+                hipLaunchKernelGGL((k_query_overlap<decltype(form)::value, decltype(km)::filtered>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream,
+                                   k.sc, rows, m, held, object_id, triangle_id, count, k.order, k.spill, k.spill_threads, k.head, km);
+            });
+        };
+        if (any) go(std::integral_constant<int, rtxop::FORM_ANY>(), 0, false);
+        else if (objects && K > 0) go(std::integral_constant<int, rtxop::FORM_OBJECTS>(), (int)K, false);
+        else if (objects) go(std::integral_constant<int, rtxop::FORM_OBJECTS | OVERLAP_COUNT_ONLY>(), 0, false);
+        else if (K > 0) go(std::integral_constant<int, rtxop::FORM_TRIANGLES>(), (int)K, true);
+        else go(std::integral_constant<int, rtxop::FORM_TRIANGLES | OVERLAP_COUNT_ONLY>(), 0, false);
+    });
 }
 extern "C" int rtx_query_overlap(rtx_ctx * c, const void * boxes_dev, int64_t n, int32_t max_hits, int32_t * object_id_dev, int32_t * triangle_id_dev, int32_t * count_dev, uint32_t flags) {
     return query_overlap_impl(c, boxes_dev, n, max_hits, object_id_dev, triangle_id_dev, count_dev, flags, nullptr);
@@ -2769,8 +2707,8 @@ extern "C" int rtx_debug_query_order(rtx_ctx * c, const void * rows_dev, int32_t
     hipSetDevice(c->cfg.device);
     DevQueues q;
     QuerySort S;
-    if (int rc = query_queues(c, n, q, &S)) return rc;
-    return query_rounds(c, q, n, [&](int64_t first, int m) -> int {
+    if (int rc = query_queues(c, n, &q, &S)) return rc;
+    return query_rounds(c, &q, n, [&](int64_t first, int m) -> int {
         const float * const rows = (const float *)rows_dev + (size_t)row_floats * first;
         if (int rc = row_floats == 4 ? query_sort_round<4>(c, S, rows, m) : row_floats == 6 ? query_sort_round<6>(c, S, rows, m) : query_sort_round<7>(c, S, rows, m)) return rc;
         launch_timed(c, "k_query_sort_order", c->stream, [&] { hipLaunchKernelGGL(k_query_sort_order, dim3((m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK), dim3(RTX_QUERY_BLOCK), 0, c->stream, (const uint64_t *)S.keys, m, (int32_t)first, order_out_dev + first); });
@@ -2821,7 +2759,7 @@ extern "C" int rtx_debug_trace_rays(rtx_ctx * c, const float * rays18, int32_t n
     int rc = upload(c, din, rays18, (size_t)n * 72);
     if (!rc) rc = upload(c, din6, rays6.data(), (size_t)n * 24);
     if (!rc) rc = ensure(c, dout, (size_t)n * 108);
-    if (!rc) rc = query_rounds(c, k.q, n, [&](int64_t first, int m) -> int {
+    if (!rc) rc = query_rounds(c, &k.q, n, [&](int64_t first, int m) -> int {
         if (int bad = query_closest_round(c, k, (const float *)din6.p + 6 * first, m)) return bad;
         hipLaunchKernelGGL(k_debug_rebuild, dim3((m + 255) / 256), dim3(256), 0, c->stream, k.sc, k.q, (const float *)din.p + 18 * first, (float *)dout.p + 27 * first, m);
         return RTX_OK;
@@ -2841,7 +2779,7 @@ extern "C" int rtx_debug_occluded(rtx_ctx * c, const float * origin_direction_ma
     DevBuf din, dout;
     int rc = upload(c, din, origin_direction_maxdist7, (size_t)n * 28);
     if (!rc) rc = ensure(c, dout, (size_t)n * 4);
-    if (!rc) rc = query_rounds(c, k.q, n, [&](int64_t first, int m) { return query_occluded_round(c, k, (const float *)din.p + 7 * first, m, (int32_t *)dout.p + first); });
+    if (!rc) rc = query_rounds(c, &k.q, n, [&](int64_t first, int m) { return query_occluded_round(c, k, (const float *)din.p + 7 * first, m, (int32_t *)dout.p + first); });
     HIP_OK(c, hipStreamSynchronize(c->stream));
     if (rc) return rc;
     HIP_OK(c, hipMemcpy(occluded, dout.p, (size_t)n * 4, hipMemcpyDeviceToHost));

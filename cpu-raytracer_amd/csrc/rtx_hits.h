@@ -1,13 +1,9 @@
 // rtx_hits.h — all-hits segment queries (include/rtx.h: rtx_query_hits): k_query_hits, one kernel per round.
 //
-// The frame of k_query_nearest (rtx_nearest.h): one row (origin, direction, max distance) per lane, RTX_QUERY_BLOCK lanes per workgroup, a
-// workgroup walks one tile of RTX_QUERY_BLOCK rows to the end and fetches the next from the round's counter, so the grid never exceeds the
-// threads the context's spill region was sized for.  The kernel reads the rows and writes the channels and the count itself: no queue set, no
-// resolve launch.  With an order (RTX_QUERY_SORT) slot i walks row key_row(order[i]) and scatters its answers there.
-//
-// The walk is rtxhp::walk (rtx_hits_math.h), the same function the host twin runs, over the per-lane node layout and the hot triangles as
-// k_query_nearest reads them.  Stack: entries (node, key), the first RTX_LDS_STACK per lane in LDS at [e][lane], deeper ones in regions 0 and 1
-// of the context's spill buffer; at most rtxnp::stack_need() entries, checked on the host: no overflow path.
+// The frame of the walk queries (rtx_nearest.h): tiles from the round's counter, the row of a slot, its caller row, the Scene (FILTERED: the
+// masks of rtx_query_hits_filtered), the stack of nearest_stack, the channel stores.  What differs:
+// The row: (origin, direction, max distance), seven floats.  The walk: rtxhp::walk (rtx_hits_math.h), the function the host twin runs.
+// The kernel writes the channels of the first K hits of every row, in order, and the row's count.
 // The list: (t, object, triangle) per held hit, three dwords, in LDS at [entry][field][lane] — one dword per lane and instruction, conflict
 // free like the stack, and addressed by a runtime entry without a private array (which would live in scratch).  u and v are not kept: after
 // the walk tri_test runs again on the at most K listed triangles, then the requested channels are rebuilt; the cold record is read only if
@@ -82,26 +78,15 @@ RTX_D void hit_write(const DevScene & sc, const DevQuery & out, const bool cold,
             material = pl.material_id;
         }
     }
-    if (out.distance) out.distance[e] = t;
-    if (out.position) { out.position[3 * e + 0] = point.x; out.position[3 * e + 1] = point.y; out.position[3 * e + 2] = point.z; }
-    if (out.normal) { out.normal[3 * e + 0] = normal.x; out.normal[3 * e + 1] = normal.y; out.normal[3 * e + 2] = normal.z; }
-    if (out.uv) { out.uv[2 * e + 0] = tu; out.uv[2 * e + 1] = tv; }
-    if (out.material_id) out.material_id[e] = material;
-    if (out.object_id) out.object_id[e] = object;
-    if (out.triangle_id) out.triangle_id[e] = triangle;
+    query_store_channels(out, e, t, point, normal, tu, tv, material, object, triangle);
 }
+// entry e of a row that holds fewer hits: the values of a miss
 RTX_D void hit_write_miss(const DevQuery & out, const size_t e) {
-    if (out.distance) out.distance[e] = INFINITY;
-    if (out.position) { out.position[3 * e + 0] = 0.0f; out.position[3 * e + 1] = 0.0f; out.position[3 * e + 2] = 0.0f; }
-    if (out.normal) { out.normal[3 * e + 0] = 0.0f; out.normal[3 * e + 1] = 0.0f; out.normal[3 * e + 2] = 0.0f; }
-    if (out.uv) { out.uv[2 * e + 0] = 0.0f; out.uv[2 * e + 1] = 0.0f; }
-    if (out.material_id) out.material_id[e] = -1;
-    if (out.object_id) out.object_id[e] = -1;
-    if (out.triangle_id) out.triangle_id[e] = -1;
+    const rtxnp::P3 zero = rtxnp::mk(0.0f, 0.0f, 0.0f);
+    query_store_channels(out, e, INFINITY, zero, zero, 0.0f, 0.0f, -1, -1, -1);
 }
 
 // rows7: the m segments of the round; out: the channel arrays advanced to the round's first row (K entries per row); count: likewise, or null
-// FILTERED: the masks of rtx_query_hits_filtered (rtx_nearest.h); the list, the stack and the tile counter are the same
 template <bool LIST, bool FILTERED>
 __global__ __launch_bounds__(RTX_QUERY_BLOCK)
 void k_query_hits(const DevScene sc, const float * __restrict__ rows7, const int m, const int K, const DevQuery out, int32_t * __restrict__ count,
@@ -111,37 +96,21 @@ void k_query_hits(const DevScene sc, const float * __restrict__ rows7, const int
     __shared__ float lds_key[RTX_QUERY_BLOCK / RTX_WAVE][RTX_LDS_STACK][RTX_WAVE];
     __shared__ float lds_list[LIST ? 3 * rtxhp::MAX_HITS * RTX_QUERY_BLOCK : 1];
     __shared__ int lds_tile;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int gtid = blockIdx.x * RTX_QUERY_BLOCK + threadIdx.x;                  // < spill_threads: the host sizes the grid
-    const size_t spill_region = (size_t)spill_threads * (RTX_MAX_STACK - RTX_LDS_STACK);
-    NearestStack st = { &lds_stack[wave][0][lane], &lds_key[wave][0][lane], spill_base + gtid, (float *)(spill_base + spill_region) + gtid, spill_threads };
+    NearestStack st = nearest_stack(lds_stack, lds_key, spill_base, spill_threads);
     const bool cold = out.normal || out.uv || out.material_id;                    // kernel arguments: the same for every lane
     const int tiles = (m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK;
     for (;;) {
-        __syncthreads();                                                          // every lane has taken its row and the number of the previous tile
-        if (threadIdx.x == 0) lds_tile = (int)atomicAdd(head, 1u);
-        __syncthreads();
-        const int tile = lds_tile;
+        const int tile = query_next_tile(head, lds_tile);
         if (tile >= tiles) break;
-        const int i = tile * RTX_QUERY_BLOCK + threadIdx.x;
         float r[7];
-        if (order) query_gather_row<7>(order, rows7, m, i, r);
-        else query_load_row<7>(lds_rows, rows7, m, r, tile);
-        if (i >= m) continue;
+        query_slot_row<7>(order, lds_rows, rows7, m, tile, r);
+        size_t p;
+        if (!query_caller_row(order, m, tile * RTX_QUERY_BLOCK + threadIdx.x, p)) continue;
         rtxhp::Tally w;
         typename std::conditional<LIST, HitsList, HitsNoList>::type L;
         if constexpr (LIST) L.base = &lds_list[threadIdx.x];
-        if constexpr (FILTERED) {
-            const size_t pr = order ? (size_t)rtxq::key_row(order[i]) : (size_t)i;
-            Masked<HitsScene> S = { { { sc, RTX_GPTR(sc.tlas_nodes), nullptr, nullptr } }, masks.table, pr < (size_t)m ? query_row_mask(masks, pr) : 0u };
-            rtxhp::walk(S, st, L, r, LIST ? K : 0, count != nullptr, w);
-        } else {
-            HitsScene S = { { sc, RTX_GPTR(sc.tlas_nodes), nullptr, nullptr } };
-            rtxhp::walk(S, st, L, r, LIST ? K : 0, count != nullptr, w);
-        }
-
-        const size_t p = order ? (size_t)rtxq::key_row(order[i]) : (size_t)i;      // the caller's row of this slot
-        if (p >= (size_t)m) continue;                                              // never: a sorted key holds a row of the round
+        auto S = query_scene<HitsScene>(sc, masks, p);
+        rtxhp::walk(S, st, L, r, LIST ? K : 0, count != nullptr, w);
         if (count) count[p] = w.count;
         if constexpr (LIST) {
             const rtxnp::P3 o = rtxnp::mk(r[0], r[1], r[2]), d = rtxnp::mk(r[3], r[4], r[5]);

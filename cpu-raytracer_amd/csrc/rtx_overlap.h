@@ -1,14 +1,12 @@
 // rtx_overlap.h — box-overlap queries (include/rtx.h: rtx_query_overlap): k_query_overlap, one kernel per round.
 //
-// The frame of k_query_hits (rtx_hits.h): one row (centre, half extents, quaternion) per lane, RTX_QUERY_BLOCK lanes per workgroup, a
-// workgroup walks one tile of RTX_QUERY_BLOCK rows to the end and fetches the next from the round's counter, so the grid never exceeds the
-// threads the context's spill region was sized for.  The kernel reads the rows and writes the ids and the count itself: no queue set, no
-// resolve launch.  With an order (RTX_QUERY_SORT) slot i walks row key_row(order[i]) and scatters its answers there.
-//
-// The walk is rtxop::walk (rtx_overlap_math.h), the same function the host twin runs, over the per-lane node layout and the hot triangles as
-// k_query_nearest reads them.  Stack: node ids only (the walk has no key: nothing is tested again when popped), the first RTX_LDS_STACK per
-// lane in LDS at [e][lane], deeper ones in region 0 of the context's spill buffer; at most rtxnp::stack_need() entries, checked on the host:
-// no overflow path.  The list: (object, triangle) per held overlap, two dwords, in LDS at [entry][field][lane] — one dword per lane and
+// The frame of the walk queries (rtx_nearest.h): tiles from the round's counter (query_next_tile); the row of a slot, its caller row and the
+// Scene (FILTERED: the masks of rtx_query_overlap_filtered) are spelled out in the kernel and must match the frame's functions.  What differs:
+// The row: (centre, half extents, quaternion), ten floats.  The walk: rtxop::walk (rtx_overlap_math.h), the function the host twin runs.
+// The kernel writes the ids of the K smallest overlaps of every row and the row's count.
+// Stack: node ids only (the walk has no key: nothing is tested again when popped), the first RTX_LDS_STACK per lane in LDS at [e][lane],
+// deeper ones in region 0 of the context's spill buffer; the host's stack rule is the same.
+// The list: (object, triangle) per held overlap, two dwords, in LDS at [entry][field][lane] — one dword per lane and
 // instruction, conflict free like the stack, and addressed by a runtime entry without a private array (which would live in scratch).
 // The lane's row stays in LDS during the walk (a sorted round writes the gathered row there too): the walk holds ONE frame and makes the
 // world frame again from the row when an instance is done (holding both frames in registers measured no better: DESIGN.md 3).
@@ -61,7 +59,7 @@ struct OverlapNoList {            // ANY and the count-only forms: offer() retur
 };
 
 // rows10: the m boxes of the round; object_id, triangle_id: the caller's arrays advanced to the round's first row (K entries per row), or
-// null; count: likewise ([m]; 0 / 1 in the ANY form), or null.  FILTERED: the masks of rtx_query_overlap_filtered (rtx_nearest.h)
+// null; count: likewise ([m]; 0 / 1 in the ANY form), or null
 template <int FORM, bool FILTERED>
 __global__ __launch_bounds__(RTX_QUERY_BLOCK)
 void k_query_overlap(const DevScene sc, const float * __restrict__ rows10, const int m, const int K, int32_t * __restrict__ object_id, int32_t * __restrict__ triangle_id,
@@ -78,14 +76,13 @@ void k_query_overlap(const DevScene sc, const float * __restrict__ rows10, const
     OverlapStack st = { &lds_stack[wave][0][lane], spill_base + gtid, spill_threads };
     const int tiles = (m + RTX_QUERY_BLOCK - 1) / RTX_QUERY_BLOCK;
     for (;;) {
-        __syncthreads();                                                          // every lane has taken its row and the number of the previous tile
-        if (threadIdx.x == 0) lds_tile = (int)atomicAdd(head, 1u);
-        __syncthreads();
-        const int tile = lds_tile;
+        const int tile = query_next_tile(head, lds_tile);
         if (tile >= tiles) break;
         const int i = tile * RTX_QUERY_BLOCK + threadIdx.x;
         float r[rtxop::ROW_FLOATS];
         float * const row = &lds_rows[threadIdx.x * rtxop::ROW_FLOATS];          // the lane's row stays in LDS for the walk, which reads it again
+        // From here to the caller row: query_slot_row, query_caller_row and query_scene spelled out; they must match those functions
+        // (rtx_nearest.h's header comment says why)
         if (order) { query_gather_row<rtxop::ROW_FLOATS>(order, rows10, m, i, r); for (int k = 0; k < rtxop::ROW_FLOATS; k++) row[k] = r[k]; }
         else query_load_row<rtxop::ROW_FLOATS>(lds_rows, rows10, m, r, tile);
         if (i >= m) continue;
@@ -100,7 +97,6 @@ void k_query_overlap(const DevScene sc, const float * __restrict__ rows10, const
             OverlapScene S = { { sc, RTX_GPTR(sc.tlas_nodes), nullptr, nullptr } };
             rtxop::walk<WALK>(S, st, L, row, LIST ? K : 0, w);
         }
-
         const size_t p = order ? (size_t)rtxq::key_row(order[i]) : (size_t)i;      // the caller's row of this slot
         if (p >= (size_t)m) continue;                                              // never: a sorted key holds a row of the round
         if (count) count[p] = w.count;

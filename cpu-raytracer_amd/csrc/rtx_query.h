@@ -31,6 +31,23 @@ struct DevQuery {
     float * distance; float * position; float * normal; float * uv;
     int32_t * material_id; int32_t * object_id; int32_t * triangle_id;
 };
+// element e of every requested channel (V: v3 or rtxnp::P3); every kernel that answers into a DevQuery stores through here
+template <typename V>
+RTX_D void query_store_channels(const DevQuery & out, const size_t e, const float distance, const V & point, const V & normal, const float tu, const float tv,
+                                const int material, const int object, const int triangle) {
+    if (out.distance) out.distance[e] = distance;
+    if (out.position) { out.position[3 * e + 0] = point.x; out.position[3 * e + 1] = point.y; out.position[3 * e + 2] = point.z; }
+    if (out.normal) { out.normal[3 * e + 0] = normal.x; out.normal[3 * e + 1] = normal.y; out.normal[3 * e + 2] = normal.z; }
+    if (out.uv) { out.uv[2 * e + 0] = tu; out.uv[2 * e + 1] = tv; }
+    if (out.material_id) out.material_id[e] = material;
+    if (out.object_id) out.object_id[e] = object;
+    if (out.triangle_id) out.triangle_id[e] = triangle;
+}
+// the object_id channel of instance / sphere / plane `index`: instances, then spheres, then planes, the numbering of RTX_AOV_OBJECT_ID (k_shade).
+// At most one of triangle, sphere is set; neither: a plane
+RTX_D int query_object_id(const DevScene & sc, const bool triangle, const bool sphere, const int index) {
+    return triangle ? index : sphere ? sc.instance_count + index : sc.instance_count + sc.sphere_count + index;
+}
 
 // Rows of ROW floats are 24 / 28 bytes: lane-per-row loads would be ROW loads of stride ROW * 4 B per lane.  The workgroup reads its
 // RTX_QUERY_BLOCK rows as one contiguous run of floats instead (consecutive lanes, consecutive dwords; any 4-byte aligned address) into LDS,
@@ -60,6 +77,13 @@ RTX_D void query_gather_row(const uint64_t * __restrict__ order, const float * _
         const float * const src = rows + (size_t)at * ROW;
         for (int k = 0; k < ROW; k++) row[k] = src[k];
     } else for (int k = 0; k < ROW; k++) row[k] = 0.0f;
+}
+// The caller's row p of slot i of a round of m rows: where the slot's answer goes, and where a filtered walk query reads its row mask.
+// false: the slot carries no row — i >= m, or (never: a sorted key holds a row of the round) a key whose row is none of the round's
+RTX_D bool query_caller_row(const uint64_t * order, const int m, const int i, size_t & p) {
+    if (i >= m) return false;
+    p = order ? (size_t)rtxq::key_row(order[i]) : (size_t)i;
+    return p < (size_t)m;
 }
 
 // The twelve bounds of a round's live rows, bounds[0..5] the minima as ordered keys, bounds[6..11] the maxima as complemented ordered keys:
@@ -177,16 +201,10 @@ __global__ __launch_bounds__(RTX_QUERY_BLOCK) void k_query_resolve(const DevScen
             h.material_id = B.material_offset + B.tri_cold[tri].material_id;
         } else h.material_id = kind == PRIM_SPHERE ? sc.spheres[pi].material_id : sc.planes[pi].material_id;
     }
-    const size_t p = order ? (size_t)rtxq::key_row(order[i]) : (size_t)i;      // the caller's row of this slot
-    if (p >= (size_t)m) return;                                                // never: a sorted key holds a row of the round
-    if (out.distance) out.distance[p] = is_hit ? h0.x : INFINITY;
-    if (out.position) { out.position[3 * p + 0] = h.point.x; out.position[3 * p + 1] = h.point.y; out.position[3 * p + 2] = h.point.z; }
-    if (out.normal) { out.normal[3 * p + 0] = h.normal.x; out.normal[3 * p + 1] = h.normal.y; out.normal[3 * p + 2] = h.normal.z; }
-    if (out.uv) { out.uv[2 * p + 0] = h.u; out.uv[2 * p + 1] = h.v; }
-    if (out.material_id) out.material_id[p] = is_hit ? h.material_id : -1;
-    if (out.object_id)                                            // instances, then spheres, then planes: the numbering of RTX_AOV_OBJECT_ID (k_shade)
-        out.object_id[p] = !is_hit ? -1 : kind == PRIM_TRI ? pi : kind == PRIM_SPHERE ? sc.instance_count + pi : sc.instance_count + sc.sphere_count + pi;
-    if (out.triangle_id) out.triangle_id[p] = (is_hit && kind == PRIM_TRI) ? tri : -1;
+    size_t p;
+    if (!query_caller_row(order, m, i, p)) return;
+    query_store_channels(out, p, is_hit ? h0.x : INFINITY, h.point, h.normal, h.u, h.v, is_hit ? h.material_id : -1,
+                         is_hit ? query_object_id(sc, kind == PRIM_TRI, kind == PRIM_SPHERE, pi) : -1, (is_hit && kind == PRIM_TRI) ? tri : -1);
 }
 
 // slots [0, m rounded up to a packet) of level 0 and of its one shadow segment (the caller's DevScene copy says light_count = 1, whatever
