@@ -250,6 +250,69 @@ static void stack_limits() {
     }
 }
 
+// Both trees deep: n instances under a chain-shaped TLAS (dt = n - 1 levels), each a mesh of m triangles under a chain-shaped BVH (inner depth
+// m - 2).  blas_any is m for the binary shadow-ray walk and at most RTX_PK4_MAX_NEED - 4 = 32 where the mesh has 4-wide records; blas_shared =
+// 2 m.  The combinations are those of tests/stackset.py's grid (c = dt + 1 + blas_any of the binary walk = n + m), whose routing
+// tests/test_gpu_packet_stack.py asserts on the device.  The shared closest-hit walk can have (n - 1) + 3 + 1 + (m - 1) + 3 = c + 5 entries
+// pending (far siblings of dt = n - 1 and m - 1 inner ancestors, three parks per tree, the iterator entry), so for two chains the third bound
+// is the one that binds: c <= 59 packets, beyond it the per-lane kernels.
+static void two_deep_trees() {
+    CASE("two deep trees");
+    const int S = RTX_PK_STACK;
+    struct Out { bool lane, pkc; };
+    auto rule = [](int n, int m, int blas_any) { Out o = { false, true }; plan_stack_limits(StackFigures{ false, n - 1, blas_any, 2 * m }, o.lane, o.pkc); return o; };
+    const struct { int c, n; } grid[] = { { 58, 31 }, { 58, 21 }, { 58, 8 }, { 61, 31 }, { 61, 22 }, { 61, 8 }, { 63, 31 }, { 63, 23 }, { 63, 8 }, { 64, 31 }, { 64, 24 }, { 64, 8 },
+                                          { 65, 31 }, { 65, 24 }, { 65, 8 }, { 66, 31 }, { 66, 25 }, { 66, 9 } };
+    for (const auto & g : grid) {
+        const int n = g.n, m = g.c - g.n;
+        CHECK(plan_shared_walk_need(StackFigures{ false, n - 1, m, 2 * m }) == g.c + 5);
+        const Out binary = rule(n, m, m), wide = rule(n, m, m < 32 ? m : 32);      // RTX_PK_WIDE=0, and 4-wide records: the shadow-ray walk needs less
+        CHECK(binary.lane == (g.c + 5 > S) && wide.lane == binary.lane);     // the shared walk is over the binary nodes whatever the records
+        CHECK(!binary.pkc && !wide.pkc);                                    // 2 dt + 1 + 2 m is far beyond the stack everywhere on the grid
+    }
+    CHECK(!rule(31, 28, 28).lane && rule(31, 29, 29).lane);               // c + 5 = 64 / 65, TLAS-heavy
+    CHECK(!rule(8, 51, 32).lane && rule(8, 52, 32).lane);                 // the same, mesh-heavy
+    {   // the deepest TLAS leaf holds two instances: the iterator entry then really lies below the BLAS part.  31 instances under a chain of
+        // dt = 29 levels over a 29- / 30-triangle chain: 29 + 3 + 1 + 28 + 3 = 64 (packets), 29 + 3 + 1 + 29 + 3 = 65 (per lane); the rule counts
+        // the entry whatever the leaves hold, so 30 single-instance leaves (dt = 29) route the same way
+        bool lane = false, pkc = true;
+        CHECK(plan_shared_walk_need(StackFigures{ false, 29, 29, 58 }) == 64 && plan_shared_walk_need(StackFigures{ false, 29, 30, 60 }) == 65);
+        plan_stack_limits(StackFigures{ false, 29, 29, 58 }, lane, pkc); CHECK(!lane);
+        plan_stack_limits(StackFigures{ false, 29, 30, 60 }, lane, pkc); CHECK(lane);
+        CHECK(plan_shared_walk_need(StackFigures{ false, 2, 4, 8 }) == 2 + 2 + 1 + 3 + 3);      // small trees: parks are bounded by the siblings
+        CHECK(plan_shared_walk_need(StackFigures{ false, 0, 2, 4 }) == 0 + 0 + 1 + 1 + 1);
+    }
+    CHECK(!rule(32, 4, 3).lane && rule(33, 4, 3).lane);                   // 2 dt + 1 = 63 / 65 over a shallow mesh: the older bound still decides there
+    CHECK(!rule(1, 60, 59).lane && !rule(1, 61, 32).lane && rule(1, 62, 32).lane);      // one instance: 1 + (m - 1) + 3; the 60-triangle chain of the unit tests stays with the packets
+    CHECK(!rule(1, 1, 1).lane && !rule(2, 2, 2).lane);                    // trees of one leaf
+    {   // the shadow-ray bound alone (dt + 1 + blas_any = 64 / 65): a mesh whose 4-wide records need more than its binary depth
+        bool lane = false, pkc = true;
+        plan_stack_limits(StackFigures{ false, 31, 32, 2 * 22 }, lane, pkc); CHECK(!lane);      // shared walk: 31 + 3 + 1 + 21 + 3 = 59
+        lane = false; plan_stack_limits(StackFigures{ false, 31, 33, 2 * 22 }, lane, pkc); CHECK(lane);
+    }
+    {   // the deepest trees among the golden scenes and the benchmark's (TLAS inner depth, deepest mesh's inner depth): cube (-1, 4), monkey (-1, 11),
+        // materials / dynamic (1, 11), tori16 (3, 11), the atrium (-1, 24).  All far inside every bound: their plans are what they were
+        const struct { int dt, depth; } shipped[] = { { 0, 4 }, { 0, 11 }, { 2, 11 }, { 4, 11 }, { 0, 24 } };
+        for (const auto & t : shipped) {
+            bool lane = false, pkc = true;
+            const StackFigures f = { false, t.dt, t.depth + 2, 2 * (t.depth + 2) };
+            plan_stack_limits(f, lane, pkc);
+            CHECK(!lane && pkc && plan_shared_walk_need(f) <= 32);
+        }
+    }
+    {   // in a plan: a depth across the bound is a different plan (and a different graph key): lane, the kernels of every level, the shadow-ray schedule
+        PlanInputs a = frame(), b = frame();
+        a.instance_count = b.instance_count = 31;
+        a.stack = StackFigures{ false, 30, 28, 56 }; b.stack = StackFigures{ false, 30, 29, 58 };
+        RenderPlan pa = plan_render(a), pb = plan_render(b);
+        CHECK(!pa.lane && pb.lane && !same(pa, pb) && all_closest(pb, CLOSEST_LANE) && pa.closest[0] == CLOSEST_PACKET);
+        CHECK(schedule(pb, { { 0, 1, ANY_LANE, 0, 0, 0 }, { 3, 1, ANY_LANE, 1, 3, 0 } }));
+        a.flags = b.flags = PKC | PSTAT;                                  // the flag is dropped on both sides, silently; the statistics mode yields to the forced lane
+        pa = plan_render(a); pb = plan_render(b);
+        CHECK(!pa.pk_closest && !pb.pk_closest && pa.pstat && !pb.pstat);
+    }
+}
+
 static void lpt_items_graph() {
     CASE("LPT");
     {
@@ -455,6 +518,7 @@ int main() {
     modes_and_schedule();
     instrumented_modes();
     stack_limits();
+    two_deep_trees();
     lpt_items_graph();
     if (failures) { printf("plan_check: %d FAILED\n", failures); return 1; }
     printf("plan_check: ok\n");

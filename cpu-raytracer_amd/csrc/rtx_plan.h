@@ -73,18 +73,44 @@ struct RenderPlan {
     int32_t graph_eligible;
 };
 
+// Entries the shared closest-hit walk of a packet can have pending (see plan_stack_limits): one far sibling per inner ancestor in both
+// trees (dt in the TLAS, inner depth + 1 in the mesh), at most three parked sign-split entries per tree, the iterator entry
+static inline int plan_shared_walk_need(const StackFigures & s) {
+    const int tlas_sib = s.dt > 0 ? s.dt : 0, blas_sib = s.blas_shared > 2 ? s.blas_shared / 2 - 1 : 0;
+    return tlas_sib + (tlas_sib < 3 ? tlas_sib : 3) + 1 + blas_sib + (blas_sib < 3 ? blas_sib : 3);
+}
+
 // What the uploaded trees allow the packet kernels (render calls and ray queries): lane = the call takes the per-lane kernels,
 // pk_closest = closest-hit packets may walk shared subtrees together.  Only ever turns lane on and pk_closest off.
 static inline void plan_stack_limits(const StackFigures & s, bool & lane, bool & pk_closest) {
     if (s.unfit_mesh) lane = true;      // limits of the packet kernels' packed entries
     // The packet kernels keep ONE 64-entry stack per wave (RTX_PK_STACK) for the TLAS part and the BLAS part of a walk together, where the
-    // reference has a stack per BVH (BVH_TRAVERSAL_STACK_SIZE each).  Both depths are known on the host, so the choice is made here
-    // and pk_push's overflow path is never taken:  TLAS part = one pending far sibling per level + the iterator entry of the leaf being
-    // visited (closest-hit rays: + one parked sign-split entry per level); BLAS part = the 4-wide records' bound (pk4_need), or one far
-    // sibling per level of the binary walk; the shared closest-hit walk parks sign-split entries there too.  Scenes beyond the bound
-    // (e.g. a chain-shaped TLAS of 60 instances) are traced by the per-lane kernels, whose stacks are per BVH like the reference's.
+    // reference has a stack per BVH (BVH_TRAVERSAL_STACK_SIZE each).  Both depths are known on the host, so the choice is made here, and
+    // pk_push's overflow path is taken by no walk these rules let through.  What a walk can have pending, from pk_walk's own rules:
+    //   TLAS part   one far sibling per inner node on the path: a leaf of the deepest level (depth dt = inner depth + 1) has dt inner
+    //               ancestors, so dt of them; closest-hit rays: one parked sign-split entry per AXIS (the lanes that walk on agree on that
+    //               axis for the rest of the subtree, and the parked entry is popped only after it): at most min(3, dt), which the older,
+    //               coarser "one per level" of 2 dt + 1 also covers; the iterator entry of the leaf being visited: popped when an instance
+    //               is entered and pushed again only while the leaf has instances left, so it lies below the BLAS part exactly where a
+    //               leaf holds more than one instance.  The host does not look at the leaves: it always counts 1.
+    //   BLAS part   shadow rays: the 4-wide records' bound (pk4_need), or one far sibling per level of the binary walk (inner depth + 2);
+    //               closest-hit rays that share the walk (always over the BINARY nodes, whatever records the mesh has): one far sibling per
+    //               inner ancestor of a deepest leaf, inner depth + 1 = blas_shared / 2 - 1, and again at most min(3, that) parked entries
+    //               — the lanes enter the instance with the signs of their model-space directions, which the TLAS part did not sort.
+    // The shared closest-hit walk is not only the RTX_RENDER_PACKET_CLOSEST mode.  In the default mode the packets of level 0 share the top of
+    // a BLAS walk until few lanes want a node (pk_defer_t0_primary), and a packet with a lane whose inverse direction is not finite, and every
+    // packet of an RTX_RENDER_PACKET_STATS call, walks ALL of it together at every level (pk_walk<.., ASM = false>: no lane turns private).  So
+    // the third bound below is on the call, not on a threshold: measured on an MI355X before it existed, 31 instances in a chain over a
+    // 35-triangle chain (each tree legal for the reference, the rule of the shadow-ray walk satisfied; 67 entries in a replay of the walk, 71
+    // by this count) ended in RTX_ERR_LIMIT in the default mode, and 31 over 33 (65 in the replay) in the statistics mode.
+    // Scenes beyond a bound (e.g. a chain-shaped TLAS of 60 instances) are traced by the per-lane kernels: a lane of those keeps far
+    // siblings only, nothing parked and no iterator entry, but also on ONE stack (RTX_MAX_STACK = 64 entries, k_trace_fast) for both trees:
+    // dt + (a leaf's instances - 1) + (inner depth + 1) entries.  Two trees that each fit the reference's per-BVH stack can exceed
+    // that together (32 instances in a chain over a 41-triangle chain: 31 + 40); such a frame still ends in RTX_ERR_LIMIT from
+    // rtx_get_stats, from every kernel there is.
     if (s.dt + 1 + s.blas_any > RTX_PK_STACK || 2 * s.dt + 1 > RTX_PK_STACK) lane = true;
     if (2 * s.dt + 1 + s.blas_shared > RTX_PK_STACK) pk_closest = false;
+    if (plan_shared_walk_need(s) > RTX_PK_STACK) lane = true;
 }
 
 // Grids of the streaming kernels (k_shade, k_resolve: grid-stride loops, any grid is correct) follow the batch: level d of a batch of P
