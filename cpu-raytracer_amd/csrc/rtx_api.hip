@@ -37,6 +37,7 @@
 #include "rtx_hits.h"
 #include "rtx_sweep.h"
 #include "rtx_overlap.h"
+#include "rtx_boxsweep.h"
 #include "rtx_texmip.h"
 #include <rocprim/device/device_radix_sort.hpp>      // rtx_update_instances, scenes beyond one workgroup: header-only, part of ROCm
 #include "rtx_hostmem.h"                             // DevBuf, StageRing, grow_keep: every device and pinned allocation has one owner
@@ -140,7 +141,7 @@ struct rtx_ctx {
     DevBuf d_query_sort; int32_t query_sort_cap = 0; size_t query_sort_tmp = 0;
     // rtx_query_nearest: the tile counter of a round (4 bytes, made by the first call); RTX_NEAREST_FETCH=0: tiles by stride, no counter (A/B)
     DevBuf d_nearest_head; bool nearest_fetch = true;
-    // rtx_query_nearest / rtx_query_hits / rtx_query_sweep / rtx_query_overlap: RTX_QUERY_GRID=g caps their grids at g workgroups (0: the spill region's size alone decides)
+    // rtx_query_nearest / rtx_query_hits / rtx_query_sweep / rtx_query_overlap / rtx_query_sweep_box: RTX_QUERY_GRID=g caps their grids at g workgroups (0: the spill region's size alone decides)
     int query_grid = 0;
     // rtx_set_object_masks / rtx_update_object_masks: the table the filtered walk queries read (M uint32_t, grown only, filled through a staging
     // ring of its own like the cameras), whether there is one, and (I, S, P) of the frame it was set for
@@ -2696,6 +2697,33 @@ extern "C" int rtx_query_overlap(rtx_ctx * c, const void * boxes_dev, int64_t n,
 extern "C" int rtx_query_overlap_filtered(rtx_ctx * c, const void * boxes_dev, int64_t n, int32_t max_hits, int32_t * object_id_dev, int32_t * triangle_id_dev, int32_t * count_dev,
                                           uint32_t flags, const rtx_query_filter * filter) {
     return query_overlap_impl(c, boxes_dev, n, max_hits, object_id_dev, triangle_id_dev, count_dev, flags, filter);
+}
+
+// ---- swept-box queries (include/rtx.h: rtx_query_sweep_box; kernel in rtx_boxsweep.h, arithmetic and walk in rtx_boxsweep_math.h) -------
+// The walk queries' frame over n sweeps: k_query_sweep_box writes t, the normal, the ids and the axis code; the sort key is the first seven
+// floats of the 14-float rows, the ray key of rtx_query_sweep.
+static int query_sweep_box_impl(rtx_ctx * c, const void * sweeps_dev, int64_t n, float * t_dev, float * normal_dev, int32_t * object_id_dev, int32_t * triangle_id_dev, int32_t * axis_dev,
+                                uint32_t flags, const rtx_query_filter * filter) {
+    const void * const some_out = t_dev ? (const void *)t_dev : normal_dev ? (const void *)normal_dev : object_id_dev ? (const void *)object_id_dev :
+                                  triangle_id_dev ? (const void *)triangle_id_dev : (const void *)axis_dev;
+    if (int bad = query_checks(c, sweeps_dev, n, some_out, flags, "rtx_query_sweep_box", (uint32_t)RTX_QUERY_SORT)) return bad;
+    WalkCall k;
+    if (int rc = walk_setup(c, "rtx_query_sweep_box", "ordered descent", n, flags, filter, k)) return rc;
+    return walk_rounds<rtxbs::ROW_FLOATS, rtxbs::KEY_FLOATS>(c, k, sweeps_dev, n, [&](int64_t first, const float * rows, int m, int blocks) {
+        const DevBoxSweep t = { t_dev ? t_dev + first : nullptr, normal_dev ? normal_dev + 3 * first : nullptr, object_id_dev ? object_id_dev + first : nullptr,
+                                triangle_id_dev ? triangle_id_dev + first : nullptr, axis_dev ? axis_dev + first : nullptr };
+        walk_launch(c, k, "k_query_sweep_box", first, [&](auto km) {
+            hipLaunchKernelGGL((k_query_sweep_box<decltype(km)::filtered>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream,
+                               k.sc, rows, m, t, k.order, k.spill, k.spill_threads, k.head, km);
+        });
+    });
+}
+extern "C" int rtx_query_sweep_box(rtx_ctx * c, const void * sweeps_dev, int64_t n, float * t_dev, float * normal_dev, int32_t * object_id_dev, int32_t * triangle_id_dev, int32_t * axis_dev, uint32_t flags) {
+    return query_sweep_box_impl(c, sweeps_dev, n, t_dev, normal_dev, object_id_dev, triangle_id_dev, axis_dev, flags, nullptr);
+}
+extern "C" int rtx_query_sweep_box_filtered(rtx_ctx * c, const void * sweeps_dev, int64_t n, float * t_dev, float * normal_dev, int32_t * object_id_dev, int32_t * triangle_id_dev, int32_t * axis_dev,
+                                            uint32_t flags, const rtx_query_filter * filter) {
+    return query_sweep_box_impl(c, sweeps_dev, n, t_dev, normal_dev, object_id_dev, triangle_id_dev, axis_dev, flags, filter);
 }
 
 // the order RTX_QUERY_SORT traces n rows of row_floats (6: rays, 7: segments) floats in: the bounds, key and sort launches of every round and

@@ -16,6 +16,7 @@
 #include "../csrc/rtx_hits_math.h"
 #include "../csrc/rtx_overlap_math.h"
 #include "../csrc/rtx_sweep_math.h"
+#include "../csrc/rtx_boxsweep_math.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -1194,6 +1195,132 @@ extern "C" int rtxh_query_overlap_exhaustive_filtered(const rtxh_nearest_scene *
     return query_overlap_exhaustive_host(scene, boxes, n, max_hits, object_id_out, triangle_id_out, count_out, flags, km);
 }
 extern "C" float rtxh_overlap_margin(float local_scale, float world_scale, float kappa) { return rtxop::margin(local_scale, world_scale, kappa); }
+
+// =================================================================================================
+// rtx_query_sweep_box on the host: rtxbs::walk (csrc/rtx_boxsweep_math.h) over the arrays of rtxh_query_nearest, and the exhaustive search
+namespace {
+struct HostBoxSweepScene : HostNearestScene {
+    explicit HostBoxSweepScene(const rtxh_nearest_scene & sc) : HostNearestScene{ sc } {}
+    int instance_count() const { return s.instance_count; }
+    int enter(int slot, rtxop::Frame & F, rtxnp::P3 & cd) {
+        const int inst = s.tlas_indices[slot];
+        F = rtxop::local_frame(F, s.instances[inst].world_inv);
+        cd = rtxnp::xform_dir(s.instances[inst].world_inv, cd);
+        B = &s.blas[s.instances[inst].blas_id];
+        return inst;
+    }
+};
+struct HostBoxSweepOut { float * t; float * normal; int32_t * object_id; int32_t * triangle_id; int32_t * axis; };
+int sweep_box_args_check(const rtxh_nearest_scene * s, const float * sweeps, int64_t n, const HostBoxSweepOut & o, bool trees) {
+    if (!o.t && !o.normal && !o.object_id && !o.triangle_id && !o.axis) return RTX_ERR_INVALID_ARG;
+    const rtx_query_buffers none = {};
+    return nearest_scene_check(s, sweeps, n, (uint32_t)RTX_QUERY_DISTANCE, &none, trees);
+}
+// the outputs of row i from its answer: what k_query_sweep_box stores
+void sweep_box_store(const rtxh_nearest_scene & s, const float * row, const rtxbs::Answer & a, int64_t i, const HostBoxSweepOut & o) {
+    if (o.t) o.t[i] = a.t;
+    if (o.normal) {
+        rtxnp::P3 n = rtxnp::mk(0.0f, 0.0f, 0.0f);
+        if (a.object >= 0 && a.t != 0.0f) {
+            const rtxop::Frame W = rtxbs::world_frame(row);
+            const rtxnp::P3 d = rtxnp::mk(row[3], row[4], row[5]);
+            if (a.slot >= 0) {
+                const rtx_instance & I = s.instances[a.object];
+                const rtx_triangle_hot & h = s.blas[I.blas_id].hot[a.slot];
+                n = rtxbs::triangle_normal(W, I.world_inv, rtxnp::ptr3(h.position_edge_1), rtxnp::ptr3(h.position_edge_2), a.axis, d);
+            } else if (a.axis == rtxbs::AXIS_SPHERE) {
+                const rtx_sphere & sp = s.spheres[a.object - s.instance_count];
+                n = rtxbs::sphere_normal(W, d, rtxnp::ptr3(sp.center), sp.radius_squared, a.t);
+            } else {
+                const rtx_plane & pl = s.planes[a.object - s.instance_count - s.sphere_count];
+                n = rtxbs::plane_normal(W, rtxnp::ptr3(pl.normal), pl.distance);
+            }
+        }
+        o.normal[3 * i] = n.x; o.normal[3 * i + 1] = n.y; o.normal[3 * i + 2] = n.z;
+    }
+    if (o.object_id) o.object_id[i] = a.object;
+    if (o.triangle_id) o.triangle_id[i] = a.slot;
+    if (o.axis) o.axis[i] = a.axis;
+}
+}  // namespace
+
+static int query_sweep_box_host(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, const HostBoxSweepOut & o, int32_t * stack_max_out, const HostMasks * km) {
+    if (int rc = sweep_box_args_check(scene, sweeps, n, o, true)) return rc;
+    int high = 0;
+    for (int64_t i = 0; i < n; i++) {
+        HostNearestStack st;
+        rtxbs::Answer a;
+        const float * row = sweeps + rtxbs::ROW_FLOATS * i;
+        if (km) { HostMasked<HostBoxSweepScene> S(*scene, km->table, km->of_row(i)); rtxbs::walk(S, st, row, a); }
+        else { HostBoxSweepScene S(*scene); rtxbs::walk(S, st, row, a); }
+        if (st.high > high) high = st.high;
+        sweep_box_store(*scene, row, a, i, o);
+    }
+    if (stack_max_out) *stack_max_out = high;
+    return RTX_OK;
+}
+extern "C" int rtxh_query_sweep_box(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, float * t_out, float * normal_out, int32_t * object_id_out, int32_t * triangle_id_out,
+                                    int32_t * axis_out, int32_t * stack_max_out, const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask) {
+    const HostMasks km = { object_masks, row_masks, row_mask };
+    const HostBoxSweepOut o = { t_out, normal_out, object_id_out, triangle_id_out, axis_out };
+    return query_sweep_box_host(scene, sweeps, n, o, stack_max_out, &km);
+}
+extern "C" int rtxh_query_sweep_box_exhaustive(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, float * t_out, float * normal_out, int32_t * object_id_out,
+                                               int32_t * triangle_id_out, int32_t * axis_out, const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask) {
+    const HostMasks km = { object_masks, row_masks, row_mask };
+    const HostBoxSweepOut o = { t_out, normal_out, object_id_out, triangle_id_out, axis_out };
+    if (int rc = sweep_box_args_check(scene, sweeps, n, o, false)) return rc;
+    const rtxh_nearest_scene & s = *scene;
+    for (int64_t i = 0; i < n; i++) {
+        const float * row = sweeps + rtxbs::ROW_FLOATS * i;
+        HostMasked<HostBoxSweepScene> S(s, km.table, km.of_row(i));
+        rtxbs::Answer a; rtxbs::clear(a);
+        if (rtxbs::row_is_live(row) && S.row_visible()) {
+            const float D = row[6];
+            a.t = D;
+            const rtxop::Frame W = rtxbs::world_frame(row);
+            const rtxnp::P3 d = rtxnp::mk(row[3], row[4], row[5]);
+            rtxbs::world_primitives(S, a, W, d, rtxop::to_box(W, d), D);
+            for (int k = 0; k < s.instance_count; k++) {
+                if (!S.object_visible(k)) continue;
+                const rtxop::Frame F = rtxop::local_frame(W, s.instances[k].world_inv);
+                const rtxnp::P3 w = rtxop::to_box(F, rtxnp::xform_dir(s.instances[k].world_inv, d));
+                const rtxh_nearest_blas & B = s.blas[s.instances[k].blas_id];
+                for (int j = 0; j < B.triangle_count; j++) {
+                    float t; int axis;
+                    if (rtxbs::triangle_sweep(F, w, rtxnp::ptr3(B.hot[j].position_0), rtxnp::ptr3(B.hot[j].position_edge_1), rtxnp::ptr3(B.hot[j].position_edge_2), a.t, t, axis))
+                        rtxbs::offer(a, D, t, k, j, axis);
+                }
+            }
+            rtxbs::finish(a);
+        }
+        sweep_box_store(s, row, a, i, o);
+    }
+    return RTX_OK;
+}
+extern "C" float rtxh_sweep_box_bound(float local_scale, float world_scale, float travelled, float kappa) { return rtxbs::sweep_box_bound(local_scale, world_scale, travelled, kappa); }
+// the candidate functions at a row's WORLD frame (an identity instance): 1 and (t, axis) when the primitive yields a candidate, else 0
+extern "C" int rtxh_sweep_box_triangle(const float row[14], float bound, const rtx_triangle_hot * tri, float * t_out, int32_t * axis_out) {
+    const rtxop::Frame W = rtxbs::world_frame(row);
+    float t = 0.0f; int axis = -1;
+    const bool any = rtxbs::triangle_sweep(W, rtxop::to_box(W, rtxnp::ptr3(row + 3)), rtxnp::ptr3(tri->position_0), rtxnp::ptr3(tri->position_edge_1), rtxnp::ptr3(tri->position_edge_2), bound, t, axis);
+    if (any) { *t_out = t; *axis_out = axis; }
+    return any ? 1 : 0;
+}
+extern "C" int rtxh_sweep_box_sphere(const float row[14], float bound, const rtx_sphere * sphere, float * t_out) {
+    const rtxop::Frame W = rtxbs::world_frame(row);
+    float t = 0.0f;
+    const bool any = rtxbs::sphere_sweep(W, rtxop::to_box(W, rtxnp::ptr3(row + 3)), rtxnp::ptr3(sphere->center), sphere->radius_squared, bound, t);
+    if (any) *t_out = t;
+    return any ? 1 : 0;
+}
+extern "C" int rtxh_sweep_box_plane(const float row[14], const rtx_plane * plane, float * t_out) {
+    const rtxop::Frame W = rtxbs::world_frame(row);
+    float t = 0.0f;
+    const bool any = rtxbs::plane_sweep(W, rtxnp::ptr3(row + 3), rtxnp::ptr3(plane->normal), plane->distance, t);
+    if (any) *t_out = t;
+    return any ? 1 : 0;
+}
 
 // =================================================================================================
 // Procedural atrium: a seeded Sponza-class stand-in (the real sponza.obj is absent from the mount).

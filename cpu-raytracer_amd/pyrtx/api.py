@@ -32,7 +32,7 @@ EXPORTS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error", "rt
            "rtx_debug_grids", "rtx_set_object_masks", "rtx_update_object_masks", "rtx_read_object_masks",
            "rtx_query_nearest_filtered", "rtx_query_hits_filtered", "rtx_query_sweep_filtered",
            "rtx_blas_pseudonormals", "rtx_read_blas_pseudonormals", "rtx_query_signed_distance",
-           "rtx_query_overlap", "rtx_query_overlap_filtered"]
+           "rtx_query_overlap", "rtx_query_overlap_filtered", "rtx_query_sweep_box", "rtx_query_sweep_box_filtered"]
 # newer than the A/B variants tools/ab.py may load (RTX_HIP_LIB = a library built from an older commit): bound when the library has them,
 # otherwise a call raises AttributeError (undefined symbol)
 VIEW_EXPORTS = ("rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer")
@@ -54,7 +54,8 @@ GRID_EXPORTS = ("rtx_debug_grids",)
 MASK_EXPORTS = ("rtx_set_object_masks", "rtx_update_object_masks", "rtx_read_object_masks",
                 "rtx_query_nearest_filtered", "rtx_query_hits_filtered", "rtx_query_sweep_filtered")
 OVERLAP_EXPORTS = ("rtx_query_overlap", "rtx_query_overlap_filtered")
-OPTIONAL_EXPORTS = (OVERLAP_EXPORTS + VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + QUERY_SORT_EXPORTS + LAYOUT_EXPORTS
+SWEEP_BOX_EXPORTS = ("rtx_query_sweep_box", "rtx_query_sweep_box_filtered")
+OPTIONAL_EXPORTS = (SWEEP_BOX_EXPORTS + OVERLAP_EXPORTS + VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + QUERY_SORT_EXPORTS + LAYOUT_EXPORTS
                     + TEXTURE_EXPORTS + NORMALS_EXPORTS + NEAREST_EXPORTS + HITS_EXPORTS + SWEEP_EXPORTS + GRID_EXPORTS + MASK_EXPORTS + SIGNED_EXPORTS)
 RTX_QUERY_MAX_HITS = 8
 # texel formats of rtx_update_texture (include/rtx.h RTX_TEXELS_*)
@@ -215,6 +216,9 @@ def load_library(path: Optional[str] = None):
     if hasattr(lib, "rtx_query_overlap"):
         lib.rtx_query_overlap.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp, u32]
         lib.rtx_query_overlap_filtered.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp, u32, C.POINTER(RtxQueryFilter)]
+    if hasattr(lib, "rtx_query_sweep_box"):
+        lib.rtx_query_sweep_box.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, u32]
+        lib.rtx_query_sweep_box_filtered.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, u32, C.POINTER(RtxQueryFilter)]
     for name in EXPORTS:
         if name in OPTIONAL_EXPORTS and not hasattr(lib, name):
             continue
@@ -1564,6 +1568,66 @@ class Renderer:
         if out is None and isinstance(boxes, (int, np.integer)) and not isinstance(boxes, bool):
             raise ValueError("with raw device pointers out must be the address of the result")
         return self._query_overlap(boxes, 0, True, RTX_OVERLAP_ANY, None if out is None else {"count": out}, n, sort, mask, ("count",))["count"]
+
+    # the outputs of query_sweep_box, in the order of rtx_query_sweep_box's arguments: name -> (dtype, width)
+    SWEEP_BOX_OUTPUTS = {"distance": (np.float32, 1), "normal": (np.float32, 3), "object_id": (np.int32, 1), "triangle_id": (np.int32, 1), "axis": (np.int32, 1)}
+
+    def query_sweep_box(self, sweeps, channels=("distance",), out: Optional[Dict] = None, n: Optional[int] = None, sort: bool = False, mask=None) -> Dict:
+        """The first contact of n moving oriented boxes with the frame the context holds (rtx_query_sweep_box): sweeps = float32 torch tensor
+        (n, 14) of (centre, direction, max distance D, half extents, rotation quaternion x y z w — query_overlap's box) on this context's GPU;
+        channels = names out of distance, normal, object_id, triangle_id, axis.  The centre moves along centre + t * direction without
+        turning; "distance" is the smallest t in [0, D) at which the box touches a triangle, a sphere's shell or a plane (0 when it touches
+        where it starts), "normal" the unit contact normal opposing the motion (0 at t == 0), "axis" the contact's kind: 0..2 a box face,
+        3 the triangle's face, 4..12 edge against edge (box axis (k - 4) % 3, triangle edge (k - 4) // 3), 13 an overlap at t == 0,
+        14 a sphere, 15 a plane.  No answer (nothing touched before D, or a dead row: a zero direction, a non-finite float, D NaN or not
+        above 0, a negative half extent, a zero quaternion): distance inf, ids and axis -1, normal 0; +inf is a legal D, zero half extents
+        are fine.  Returns {name: tensor}: float32 / int32, (n,) or (n, 3), allocated on the device unless out = {name: tensor} supplies them.
+        Queued on torch's current stream, checked like query_nearest; sort=True (RTX_QUERY_SORT) walks the rows of every round in the ray
+        queries' order, same answers row for row.  Raw device pointers: sweeps = address, n, out = {name: address} for every channel wanted.
+        mask: as for query_nearest — hidden objects neither stop the box nor overlap it."""
+        if isinstance(channels, str):
+            channels = (channels,)
+        names = tuple(channels)
+        if not names:
+            raise ValueError("channels must name at least one of " + ", ".join(self.SWEEP_BOX_OUTPUTS))
+        for name in names:
+            if name not in self.SWEEP_BOX_OUTPUTS:
+                raise ValueError(f"unknown channel {name!r}: query_sweep_box has " + ", ".join(self.SWEEP_BOX_OUTPUTS))
+        if len(set(names)) != len(names):
+            raise ValueError("channels names a channel twice")
+        ptr, n, rows_t = self._query_rows("sweeps", sweeps, 14, n)
+        if out is not None and not isinstance(out, dict):
+            raise TypeError(f"out must be a dict {{channel name: tensor}}, not {type(out).__name__}")
+        out = dict(out or {})
+        extra = [k for k in out if k not in names]
+        if extra:
+            raise ValueError(f"out holds channels that were not requested: {', '.join(map(str, extra))}")
+        raw = rows_t is None
+        if raw and len(out) != len(names):
+            raise ValueError("with raw device pointers out must hold an address for every requested channel")
+        fl = RTX_QUERY_SORT if sort else 0
+        filt, mask_t = self._query_filter(mask, n)
+        ptrs = {name: self._query_out(name, t, self.SWEEP_BOX_OUTPUTS[name][0], n, self.SWEEP_BOX_OUTPUTS[name][1], raw) for name, t in out.items()}
+        self._query_on_device({k: t for k, t in [("sweeps", rows_t)] + [(f"out[{k!r}]", t) for k, t in out.items()] if hasattr(t, "device")})
+        for name in names:
+            if name not in out:
+                import torch
+                dt, k = self.SWEEP_BOX_OUTPUTS[name]
+                out[name] = torch.empty(self._query_shape(n, k), dtype=torch.float32 if dt == np.float32 else torch.int32, device=rows_t.device)
+                ptrs[name] = out[name].data_ptr()
+
+        def launch():
+            args = (self.ctx, ptr, n, ptrs.get("distance"), ptrs.get("normal"), ptrs.get("object_id"), ptrs.get("triangle_id"), ptrs.get("axis"), fl)
+            if filt is None:
+                self._chk(self.lib.rtx_query_sweep_box(*args), "rtx_query_sweep_box")
+            else:
+                self._chk(self.lib.rtx_query_sweep_box_filtered(*args, C.byref(filt)), "rtx_query_sweep_box_filtered")
+        tensors = [t for t in [rows_t, mask_t] + list(out.values()) if hasattr(t, "record_stream")]
+        if tensors:
+            self._on_torch_stream(launch, tensors)
+        else:
+            launch()
+        return {name: out[name] for name in names}
 
     def debug_query_order(self, rows, n: Optional[int] = None):
         """The order sort=True traces the rows in (rtx_debug_query_order): rows = float32 torch tensor (n, 6) of rays, (n, 7) of segments or (n, 4) of

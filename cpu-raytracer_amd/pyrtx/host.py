@@ -25,12 +25,12 @@ EXPORTS = ["rtxh_camera_basis", "rtxh_camera_update", "rtxh_quaternion_axis_angl
            "rtxh_blas_build_balanced", "rtxh_blas_balanced_node_count", "rtxh_blas_balanced_inner_depth", "rtxh_vertex_normals",
            "rtxh_query_nearest", "rtxh_query_nearest_exhaustive", "rtxh_nearest_distance_bound", "rtxh_nearest_box_d2", "rtxh_nearest_triangle_d2",
            "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2", "rtxh_query_hits", "rtxh_query_hits_exhaustive", "rtxh_hits_margin",
-           "rtxh_query_sweep", "rtxh_query_sweep_exhaustive", "rtxh_sweep_bound", "rtxh_sweep_triangle", "rtxh_sweep_sphere", "rtxh_sweep_plane",
+           "rtxh_query_sweep", "rtxh_query_sweep_exhaustive", "rtxh_sweep_bound", "rtxh_query_sweep_box", "rtxh_query_sweep_box_exhaustive", "rtxh_sweep_box_bound", "rtxh_sweep_box_triangle", "rtxh_sweep_box_sphere", "rtxh_sweep_box_plane", "rtxh_sweep_triangle", "rtxh_sweep_sphere", "rtxh_sweep_plane",
            "rtxh_query_nearest_filtered", "rtxh_query_nearest_exhaustive_filtered", "rtxh_query_hits_filtered", "rtxh_query_hits_exhaustive_filtered",
            "rtxh_query_sweep_filtered", "rtxh_query_sweep_exhaustive_filtered", "rtxh_blas_pseudonormals",
            "rtxh_query_signed_distance", "rtxh_query_signed_distance_filtered", "rtxh_query_signed_distance_exhaustive", "rtxh_query_signed_distance_exhaustive_filtered",
            "rtxh_query_overlap", "rtxh_query_overlap_exhaustive", "rtxh_query_overlap_filtered", "rtxh_query_overlap_exhaustive_filtered", "rtxh_overlap_margin"]
-FLOAT_EXPORTS = ("rtxh_nearest_distance_bound", "rtxh_nearest_box_d2", "rtxh_nearest_triangle_d2", "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2", "rtxh_hits_margin", "rtxh_sweep_bound", "rtxh_overlap_margin")      # return a float, not a status
+FLOAT_EXPORTS = ("rtxh_nearest_distance_bound", "rtxh_nearest_box_d2", "rtxh_nearest_triangle_d2", "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2", "rtxh_hits_margin", "rtxh_sweep_bound", "rtxh_overlap_margin", "rtxh_sweep_box_bound")      # return a float, not a status
 
 PI = np.float32(3.14159265359)          # Util.h:8
 
@@ -149,6 +149,12 @@ def lib():
         l.rtxh_sweep_triangle.argtypes = [vp, vp, C.c_float, C.c_float, vp, vp, vp, vp]
         l.rtxh_sweep_sphere.argtypes = [vp, vp, C.c_float, vp, vp, vp]
         l.rtxh_sweep_plane.argtypes = [vp, vp, C.c_float, vp, vp, vp]
+        l.rtxh_query_sweep_box.argtypes = [C.POINTER(RtxhNearestScene), vp, C.c_int64, vp, vp, vp, vp, vp, C.POINTER(i32)] + masks3
+        l.rtxh_query_sweep_box_exhaustive.argtypes = [C.POINTER(RtxhNearestScene), vp, C.c_int64, vp, vp, vp, vp, vp] + masks3
+        l.rtxh_sweep_box_bound.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float]
+        l.rtxh_sweep_box_triangle.argtypes = [vp, C.c_float, vp, vp, vp]
+        l.rtxh_sweep_box_sphere.argtypes = [vp, C.c_float, vp, vp]
+        l.rtxh_sweep_box_plane.argtypes = [vp, vp, vp]
         for n in EXPORTS:
             getattr(l, n).restype = C.c_float if n in FLOAT_EXPORTS else C.c_int
         _lib = l
@@ -759,6 +765,54 @@ def query_sweep(scene, sweeps, channels=("distance",), blas=None, mask=None, obj
 def query_sweep_exhaustive(scene, sweeps, channels=("distance",), blas=None, mask=None, object_masks=None) -> dict:
     """rtxh_query_sweep_exhaustive: the same candidate functions over every primitive with no box test, the same order rule."""
     return _query_nearest("rtxh_query_sweep_exhaustive", scene, sweeps, channels, blas, False, 8, "sweeps", mask, object_masks)
+
+
+# ---- swept-box queries on the host (include/rtx_host.h: rtxh_query_sweep_box / rtxh_query_sweep_box_exhaustive) ---------------------------
+SWEEP_BOX_CHANNELS = {"distance": (np.float32, 1), "normal": (np.float32, 3), "object_id": (np.int32, 1), "triangle_id": (np.int32, 1), "axis": (np.int32, 1)}
+
+
+def _query_sweep_box(scene, sweeps, channels, blas, exhaustive, mask, object_masks):
+    sw = np.asarray(sweeps)
+    if sw.ndim != 2 or sw.shape[1] != 14 or sw.shape[0] < 1:
+        raise ValueError(f"sweeps must have shape (n, 14) with n >= 1, not {sw.shape}")
+    if sw.dtype != np.float32:
+        raise TypeError(f"sweeps must be float32, not {sw.dtype}")
+    sw = np.ascontiguousarray(sw)
+    names = (channels,) if isinstance(channels, str) else tuple(channels)
+    if not names or any(name not in SWEEP_BOX_CHANNELS for name in names):
+        raise ValueError(f"channels must be a non-empty subset of {tuple(SWEEP_BOX_CHANNELS)}, not {channels!r}")
+    s, keep = nearest_scene(scene, blas)
+    n = sw.shape[0]
+    out = {name: np.zeros((n, SWEEP_BOX_CHANNELS[name][1]) if SWEEP_BOX_CHANNELS[name][1] > 1 else (n,), SWEEP_BOX_CHANNELS[name][0]) for name in names}
+    ptr = lambda name: out[name].ctypes.data if name in out else None
+    high = C.c_int32(0)
+    filt = _filter_args(s, n, mask, object_masks)
+    masks = filt[0] if filt else [None, None, 0xFFFFFFFF]
+    args = [C.byref(s), sw.ctypes.data, n, ptr("distance"), ptr("normal"), ptr("object_id"), ptr("triangle_id"), ptr("axis")] + ([] if exhaustive else [C.byref(high)]) + masks
+    fn_name = "rtxh_query_sweep_box_exhaustive" if exhaustive else "rtxh_query_sweep_box"
+    rc = getattr(lib(), fn_name)(*args)
+    if rc:
+        raise ValueError(f"{fn_name} failed with status {rc}")
+    if not exhaustive:
+        out["stack_max"] = int(high.value)
+    return out
+
+
+def query_sweep_box(scene, sweeps, channels=("distance",), blas=None, mask=None, object_masks=None) -> dict:
+    """rtxh_query_sweep_box: what Renderer.query_sweep_box writes on the device for sweeps float32 (n, 14) of (centre, direction, max distance,
+    half extents, quaternion x y z w), from the same code (csrc/rtx_boxsweep_math.h) -> {channel: array} over distance, normal, object_id,
+    triangle_id, axis, plus "stack_max".  scene and blas as for query_nearest, mask / object_masks as there."""
+    return _query_sweep_box(scene, sweeps, channels, blas, False, mask, object_masks)
+
+
+def query_sweep_box_exhaustive(scene, sweeps, channels=("distance",), blas=None, mask=None, object_masks=None) -> dict:
+    """rtxh_query_sweep_box_exhaustive: the same candidate functions over every primitive with no node test, the same order rule."""
+    return _query_sweep_box(scene, sweeps, channels, blas, True, mask, object_masks)
+
+
+def sweep_box_bound(local_scale, world_scale=0.0, travelled=0.0, kappa=1.0) -> float:
+    """rtxbs::sweep_box_bound of csrc/rtx_boxsweep_math.h: how far, as a normalised gap, a returned contact may lie from touching exactly."""
+    return float(lib().rtxh_sweep_box_bound(C.c_float(float(local_scale)), C.c_float(float(world_scale)), C.c_float(float(travelled)), C.c_float(float(kappa))))
 
 
 # ---- box-overlap queries on the host (include/rtx_host.h: rtxh_query_overlap / rtxh_query_overlap_exhaustive) -----------------------------

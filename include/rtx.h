@@ -839,8 +839,8 @@ int rtx_query_hits(rtx_ctx * ctx, const void * segments_dev /* [n][7] f32: origi
  * bit-identical, row for row.
  * Errors, in this order and with the codes of rtx_query_nearest, its stack rule included.  An error queues nothing.
  * Limits: r and the distances are measured in each instance's LOCAL space, as for rtx_query_nearest — the world metric for rigid poses, local
- * units under a scaled world matrix.  The answer may depend on the tree within the bound.  Out of scope: swept capsules, boxes or rotating
- * shapes, all contacts along the sweep, a contact-normal channel, the rtx_group_* path.                                                    */
+ * units under a scaled world matrix.  The answer may depend on the tree within the bound.  Out of scope: swept capsules or rotating shapes (a
+ * swept box is rtx_query_sweep_box), all contacts along the sweep, a contact-normal channel, the rtx_group_* path.                                                    */
 int rtx_query_sweep(rtx_ctx * ctx, const void * sweeps_dev /* [n][8] f32: origin, direction, max distance, radius */, int64_t n,
                     uint32_t channels, const rtx_query_buffers * out, uint32_t flags /* RTX_QUERY_SORT or 0 */);
 
@@ -949,7 +949,7 @@ int rtx_query_signed_distance(rtx_ctx * ctx, const void * points_dev /* [n][4] f
  * with RTX_OVERLAP_OBJECTS; RTX_OVERLAP_OBJECTS with a triangle_id_dev; max_hits == 0 without a count_dev; max_hits > 0 without an id array;
  * a NULL boxes_dev, n < 1; any flag but RTX_QUERY_SORT, RTX_OVERLAP_OBJECTS, RTX_OVERLAP_ANY.  Then RTX_ERR_STATE and RTX_ERR_LIMIT as for
  * rtx_query_nearest, its stack rule included, and the state rule of the filtered queries.  An error queues nothing.
- * Out of scope: capsules, spheres and convex hulls as query volumes, swept boxes, penetration depth or contact points, more than
+ * Out of scope: capsules, spheres and convex hulls as query volumes, penetration depth (a swept box is rtx_query_sweep_box), or contact points, more than
  * RTX_QUERY_MAX_HITS entries per row, the rtx_group_* path.                                                                              */
 enum { RTX_OVERLAP_OBJECTS = 512, RTX_OVERLAP_ANY = 1024 };      /* bits of rtx_query_overlap's flags, beside RTX_QUERY_SORT */
 int rtx_query_overlap(rtx_ctx * ctx, const void * boxes_dev /* [n][10] f32: centre, half extents, quaternion */, int64_t n, int32_t max_hits,
@@ -957,6 +957,48 @@ int rtx_query_overlap(rtx_ctx * ctx, const void * boxes_dev /* [n][10] f32: cent
                       int32_t * count_dev /* [n] or NULL */, uint32_t flags /* RTX_QUERY_SORT, RTX_OVERLAP_OBJECTS, RTX_OVERLAP_ANY or 0 */);
 int rtx_query_overlap_filtered(rtx_ctx * ctx, const void * boxes_dev, int64_t n, int32_t max_hits, int32_t * object_id_dev, int32_t * triangle_id_dev,
                                int32_t * count_dev, uint32_t flags, const rtx_query_filter * filter);
+
+/* ---- swept-box queries ------------------------------------------------------------------------------------------------------------------
+ * "How far can this oriented box travel along this direction before it touches something, what does it touch, and with which face or edge":
+ * a character controller, a vehicle footprint, a gripper finger, a robot link with a box proxy, a pallet on a conveyor.
+ * rtx_query_sweep_box: row i = sweeps_dev[14i .. 14i+13] = (centre c, direction d, max distance D, half extents h, rotation quaternion
+ * x, y, z, w — the box of rtx_query_overlap, moved without turning), fp32 at any 4-byte aligned address in DEVICE memory; the scene is the
+ * frame the context holds, device-side updates included.  Queued on the context's stream, returns at once, nothing is read back; a
+ * steady-state call allocates and frees nothing; frames, render calls and rtx_get_stats are unchanged.
+ * The box's centre moves along c(t) = c + t * d, d used as given, t in units of |d|.  The answer is the smallest t in [0, D) (D excluded) at
+ * which the box touches a surface of the query family: a two-sided triangle by the continuous form of rtx_query_overlap's 13-axis test, a
+ * sphere's shell (a box inside a large sphere travels until its farthest corner reaches the shell), a two-sided plane (approached only).  A box
+ * that touches something where it starts answers t = 0.  An exact tie in t goes to the lowest (object_id, triangle_id).
+ * A row is live when its first seven floats are a live row of rtx_query_sweep's (a direction that is not zero, finite centre and direction,
+ * D > 0, +INFINITY included) and (c, h, q) is a live box of rtx_query_overlap (finite, h >= 0 — zero allowed: a point box is a ray — and a
+ * quaternion that is not zero).  A dead row is not walked and gets the no-answer values.
+ * Outputs, each a caller-supplied device array or NULL, at least one not NULL; element i belongs to row i:
+ *   array                   answer                                                                       no answer
+ *   t_dev [n] f32           t                                                                            +INFINITY
+ *   normal_dev [n][3] f32   the unit contact normal, world space, opposing the motion; 0 where t == 0    0
+ *   object_id_dev [n] i32   the numbering of RTX_QUERY_OBJECT_ID                                         -1
+ *   triangle_id_dev [n] i32 the triangle's slot in its BLAS; -1 for a sphere or a plane                  -1
+ *   axis_dev [n] i32        0..2 a box face's axis, 3 the triangle's normal (a box corner or edge onto   -1
+ *                           its face), 4..12 box axis (k - 4) % 3 x triangle edge (k - 4) / 3 (edges: e1,
+ *                           e2 - e1, e2): edge against edge; 13 an overlap at t == 0; 14 a sphere; 15 a plane
+ * The candidate functions, the order rule, the walk, the slack of its node test and the accuracy bound (stated in distance: at the returned
+ * t the returned primitive's largest separating gap is within the bound of 0, and nothing penetrates deeper than the bound before t) are
+ * specified in the header comment of csrc/rtx_boxsweep_math.h; rtxh_query_sweep_box in rtx_host.h is the same code on the host and gives the
+ * same bits.  Like rtx_query_overlap the test runs in each instance's local frame: exact for rigid poses.
+ * Any n >= 1, in rounds of RTX_QUERY_CHUNK_RAYS rows, one kernel launch per round.  flags: RTX_QUERY_SORT or 0; with it the rows of a round are
+ * walked in the order of the ray queries' 7-float keys, taken over each row's first seven floats, and the answers scattered back:
+ * bit-identical, row for row.  rtx_query_sweep_box_filtered: the same with the object masks of the filtered queries above and their state
+ * rule — a hidden object neither stops the box nor overlaps it, a row whose mask is 0 gets the no-answer values without a walk; a NULL filter
+ * is the unfiltered call.
+ * Errors, in this order: RTX_ERR_INVALID_ARG: a NULL ctx; a NULL sweeps_dev, five NULL outputs, n < 1; any flag but RTX_QUERY_SORT.  Then
+ * RTX_ERR_STATE and RTX_ERR_LIMIT as for rtx_query_nearest, its stack rule included, and the state rule of the filtered queries.  An error
+ * queues nothing.
+ * Out of scope: contact points or manifolds, rotation during the sweep, capsules and hulls, all contacts along the path, the rtx_group_* path. */
+int rtx_query_sweep_box(rtx_ctx * ctx, const void * sweeps_dev /* [n][14] f32: centre, direction, max distance, half extents, quaternion */, int64_t n,
+                        float * t_dev /* [n] or NULL */, float * normal_dev /* [n][3] or NULL */, int32_t * object_id_dev /* [n] or NULL */,
+                        int32_t * triangle_id_dev /* [n] or NULL */, int32_t * axis_dev /* [n] or NULL */, uint32_t flags /* RTX_QUERY_SORT or 0 */);
+int rtx_query_sweep_box_filtered(rtx_ctx * ctx, const void * sweeps_dev, int64_t n, float * t_dev, float * normal_dev, int32_t * object_id_dev,
+                                 int32_t * triangle_id_dev, int32_t * axis_dev, uint32_t flags, const rtx_query_filter * filter);
 
 /* Timing of every kernel launched since rtx_enable_kernel_timing(ctx, 1),
  * measured with HIP events on the stream the kernels are launched on.

@@ -40,6 +40,8 @@
  *   rtxh_query_nearest       rtx_query_nearest on the host: the walk and the arithmetic of csrc/rtx_nearest_math.h over plain arrays;
  *                            rtxh_query_nearest_exhaustive the same candidate functions over every primitive, without a tree
  *   rtxh_query_sweep         rtx_query_sweep on the host: the walk and the arithmetic of csrc/rtx_sweep_math.h over the same arrays;
+ *   rtxh_query_sweep_box     rtx_query_sweep_box on the host: the walk and the arithmetic of csrc/rtx_boxsweep_math.h over the same arrays;
+ *                            rtxh_query_sweep_box_exhaustive the same candidate functions over every primitive, without a node test
  *   rtxh_query_*_filtered    the three walk queries under object masks (rtx_query_*_filtered), and their exhaustive searches over the visible primitives
  *   rtxh_blas_pseudonormals  rtx_blas_pseudonormals on the host: the angle-weighted pseudonormal tables of csrc/rtx_side_math.h as a plain loop;
  *   rtxh_query_signed_distance  rtx_query_signed_distance on the host (and its _exhaustive / _filtered forms): rtxh_query_nearest with the sign
@@ -288,6 +290,27 @@ int rtxh_query_overlap_filtered(const rtxh_nearest_scene * scene, const float * 
 int rtxh_query_overlap_exhaustive_filtered(const rtxh_nearest_scene * scene, const float * boxes, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
                                            int32_t * count_out, uint32_t flags, const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask);
 float rtxh_overlap_margin(float local_scale, float world_scale, float kappa);
+
+/* rtx_query_sweep_box (include/rtx.h) on the host, by the code the kernel runs (csrc/rtx_boxsweep_math.h, whose header comment is the
+ * specification: candidate functions, the order rule, the walk and its slack, the accuracy bound).  The scene is rtxh_nearest_scene; sweeps:
+ * n x 14 floats (centre, direction, max distance, half extents, quaternion); the five outputs as for rtx_query_sweep_box, with host pointers,
+ * at least one not NULL; the answers are the device's bit for bit.  Both take the masks of the filtered call: object_masks (M masks or NULL:
+ * all ones), row_masks (n masks or NULL: row_mask for every row); NULL, NULL, 0xFFFFFFFF is the unfiltered call.  stack_max_out (or NULL):
+ * the most stack entries any row held, never above rtxnp::stack_need().
+ * rtxh_query_sweep_box_exhaustive: the same candidate functions over every sphere, plane and (instance, slot) without a node test, the same
+ * order rule.  The walk's t is never below the exhaustive t, and where the two are equal the answers are identical.
+ * rtxh_sweep_box_bound(S, W, T, kappa): rtxbs::sweep_box_bound, the bound in distance of ACCURACY in that header.
+ * rtxh_sweep_box_triangle / _sphere / _plane: one candidate function at the row's world frame (an identity instance): 1 and t (axis) when
+ * the primitive yields a candidate, else 0; bound is the walk's current t.
+ * RTX_ERR_INVALID_ARG: five NULL outputs and the argument rules of rtxh_query_nearest; RTX_ERR_LIMIT: a tree deeper than RTX_MAX_STACK entries. */
+int rtxh_query_sweep_box(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, float * t_out, float * normal_out, int32_t * object_id_out, int32_t * triangle_id_out,
+                         int32_t * axis_out, int32_t * stack_max_out, const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask);
+int rtxh_query_sweep_box_exhaustive(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, float * t_out, float * normal_out, int32_t * object_id_out,
+                                    int32_t * triangle_id_out, int32_t * axis_out, const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask);
+float rtxh_sweep_box_bound(float local_scale, float world_scale, float travelled, float kappa);
+int rtxh_sweep_box_triangle(const float row[14], float bound, const rtx_triangle_hot * tri, float * t_out, int32_t * axis_out);
+int rtxh_sweep_box_sphere(const float row[14], float bound, const rtx_sphere * sphere, float * t_out);
+int rtxh_sweep_box_plane(const float row[14], const rtx_plane * plane, float * t_out);
 
 /* The filtered walk queries (include/rtx.h: filtered queries) on the host: the same walks with FILTER's predicates of csrc/rtx_nearest_math.h,
  * so they give the device's bits.  The arguments of the function without the suffix, then object_masks (M = instance_count + sphere_count +
