@@ -110,6 +110,9 @@ struct rtx_ctx {
     StageRing frame_ring;
     DevScene scene;
     bool frame_set = false;
+    // every instance of the frame is a rigid pose (rtxu::instance_rigid): judged from the matrices rtx_set_frame is handed, true after
+    // rtx_update_instances by its unit-quaternion contract; the length queries refuse a frame that is not (walk_setup)
+    bool frame_rigid = true;
     // rtx_update_instances: a device block of its own for the updated instances / TLAS (both node layouts) / indices and the builder's scratch
     // (AABBs, bounds, keys), grown only; the DevScene pointers are switched to it, the rest of the frame stays in d_frame.  d_upd_sort = rocPRIM's
     // temporary storage and the unsorted keys (multi-launch path), grown only
@@ -523,6 +526,15 @@ extern "C" int rtx_set_frame(rtx_ctx * c, const rtx_frame * f) {
         const int b = f->instances[i].blas_id;
         if (b < 0 || (size_t)b >= c->h_blas.size() || !c->h_blas[b].nodes) return RTX_ERR_STATE;
     }
+    // A NaN or infinite cell makes every local ray of that instance non-finite, which the packet walks do not survive (rtx_trace.h,
+    // ray_is_finite): refused here, before anything changes.  Finite cells can still overflow a far origin (an open limit).
+    bool rigid = true;
+    for (int i = 0; i < f->instance_count; i++) {
+        if (!rtxu::matrix_finite(f->instances[i].world) || !rtxu::matrix_finite(f->instances[i].world_inv)) {
+            c->err = "rtx_set_frame: instance " + std::to_string(i) + " has a NaN or infinite world / world_inv cell"; return RTX_ERR_INVALID_ARG;
+        }
+        rigid = rigid && rtxu::instance_rigid(f->instances[i].world, f->instances[i].world_inv);
+    }
     // Pack the frame into one block: [TLAS nodes, lane layout][TLAS nodes, packet layout][indices][instances][spheres][planes][lights],
     // every part 256-byte aligned.  The block is staged in pinned memory and copied by ONE hipMemcpyAsync on the context's stream: it is
     // ordered after the frames already queued there (which still read the previous contents) and before the next render call.
@@ -568,7 +580,7 @@ extern "C" int rtx_set_frame(rtx_ctx * c, const rtx_frame * f) {
     for (int i = 0; i < f->sphere_count; i++) c->frame_primitive_materials.push_back(f->spheres[i].material_id);
     for (int i = 0; i < f->plane_count; i++) c->frame_primitive_materials.push_back(f->planes[i].material_id);
     c->tlas_inner_depth = tlas_depth;
-    c->frame_set = true; c->refs_dirty = true;
+    c->frame_set = true; c->refs_dirty = true; c->frame_rigid = rigid;
     return RTX_OK;
 }
 
@@ -822,6 +834,7 @@ extern "C" int rtx_update_instances(rtx_ctx * c, const void * positions_dev, con
     s.tlas_indices = u.indices; s.tlas_index_count = n; s.instances = u.instances;
     c->tlas_inner_depth = rtxu::tree_inner_depth(n);
     c->refs_dirty = true;
+    c->frame_rigid = true;                                  // unit quaternions, by this call's contract: Mesh::update's poses
     return RTX_OK;
 }
 
@@ -2485,10 +2498,15 @@ static QueryMasks<true> filter_masks(const rtx_ctx * c, const rtx_query_filter *
 // What a call decides once for all its rounds: the sort block and the sorted keys of a round (order; null = the caller's order), the tile
 // counter (head; null only for rtx_query_nearest under RTX_NEAREST_FETCH=0), the scene by value, the spill buffer and the grid limit it sets, the filter (null: none).
 struct WalkCall { QuerySort S; const uint64_t * order; uint32_t * head; DevScene sc; int32_t * spill; int spill_threads, max_blocks; const rtx_query_filter * filter; };
-// after the call's own argument checks and query_checks, in this order: the stack rule, the filter's state rule, then what allocates
+// after the call's own argument checks and query_checks, in this order: the rigid rule of the length queries (lengths: every walk query
+// but rtx_query_hits, whose t is invariant under an affine map), the stack rule, the filter's state rule, then what allocates
 // (rtx_query_signed_distance brings its side tables up to date behind it: side_table_current, which allocates and queues a copy, now
 // follows the tile counter's allocation; before, it came between the sort block and the counter)
-static int walk_setup(rtx_ctx * c, const char * what, const char * descent_word, int64_t n, uint32_t flags, const rtx_query_filter * filter, WalkCall & k, bool counter = true) {
+static int walk_setup(rtx_ctx * c, const char * what, const char * descent_word, int64_t n, uint32_t flags, const rtx_query_filter * filter, WalkCall & k, bool lengths, bool counter = true) {
+    if (lengths && !c->frame_rigid) {
+        c->err = std::string(what) + ": the frame holds an instance whose world / world_inv is not a rigid pose (scaled, sheared or flattened); the walk prunes by world-space distances and would miss answers";
+        return RTX_ERR_STATE;
+    }
     int blas_depth = -1;
     for (size_t b = 0; b < c->blas.size(); b++) if (c->h_blas[b].nodes && c->blas[b].inner_depth > blas_depth) blas_depth = c->blas[b].inner_depth;
     const int need = rtxnp::stack_need(c->tlas_inner_depth, blas_depth), have = c->cfg.stack_size < RTX_MAX_STACK ? c->cfg.stack_size : RTX_MAX_STACK;
@@ -2566,7 +2584,7 @@ static int query_nearest_impl(rtx_ctx * c, const void * points_dev, int64_t n, u
     } else if (c && (channels == 0 || (channels & ~(uint32_t)RTX_QUERY_ALL))) { c->err = "rtx_query_nearest: channels must be a non-empty subset of RTX_QUERY_ALL"; return RTX_ERR_INVALID_ARG; }
     if (int bad = query_checks(c, points_dev, n, out, flags, what, (uint32_t)RTX_QUERY_SORT)) return bad;
     WalkCall k;
-    if (int rc = walk_setup(c, what, "ordered descent", n, flags, filter, k, c->nearest_fetch)) return rc;
+    if (int rc = walk_setup(c, what, "ordered descent", n, flags, filter, k, true, c->nearest_fetch)) return rc;
     if (sg) if (int rc = side_table_current(c)) return rc;
     return walk_rounds<4>(c, k, points_dev, n, [&](int64_t first, const float * rows, int m, int blocks) {
         const DevQuery t = query_targets(channels, out, first);
@@ -2607,7 +2625,7 @@ static int query_hits_impl(rtx_ctx * c, const void * segments_dev, int64_t n, in
     }
     if (int bad = query_checks(c, segments_dev, n, max_hits ? (const void *)out : (const void *)count_dev, flags, "rtx_query_hits", (uint32_t)RTX_QUERY_SORT)) return bad;
     WalkCall k;
-    if (int rc = walk_setup(c, "rtx_query_hits", "ordered descent", n, flags, filter, k)) return rc;
+    if (int rc = walk_setup(c, "rtx_query_hits", "ordered descent", n, flags, filter, k, false)) return rc;
     const int64_t K = max_hits;
     return walk_rounds<7>(c, k, segments_dev, n, [&](int64_t first, const float * rows, int m, int blocks) {
         const DevQuery t = query_targets(channels, out, first, K);
@@ -2636,7 +2654,7 @@ static int query_sweep_impl(rtx_ctx * c, const void * sweeps_dev, int64_t n, uin
     if (c && (channels == 0 || (channels & ~(uint32_t)RTX_QUERY_ALL))) { c->err = "rtx_query_sweep: channels must be a non-empty subset of RTX_QUERY_ALL"; return RTX_ERR_INVALID_ARG; }
     if (int bad = query_checks(c, sweeps_dev, n, out, flags, "rtx_query_sweep", (uint32_t)RTX_QUERY_SORT)) return bad;
     WalkCall k;
-    if (int rc = walk_setup(c, "rtx_query_sweep", "ordered descent", n, flags, filter, k)) return rc;
+    if (int rc = walk_setup(c, "rtx_query_sweep", "ordered descent", n, flags, filter, k, true)) return rc;
     return walk_rounds<8, 7>(c, k, sweeps_dev, n, [&](int64_t first, const float * rows, int m, int blocks) {
         const DevQuery t = query_targets(channels, out, first);
         walk_launch(c, k, "k_query_sweep", first, [&](auto km) {
@@ -2671,7 +2689,7 @@ static int query_overlap_impl(rtx_ctx * c, const void * boxes_dev, int64_t n, in
     const void * const some_out = object_id_dev ? (const void *)object_id_dev : triangle_id_dev ? (const void *)triangle_id_dev : (const void *)count_dev;
     if (int bad = query_checks(c, boxes_dev, n, some_out, flags, "rtx_query_overlap", (uint32_t)RTX_QUERY_SORT | (uint32_t)RTX_OVERLAP_OBJECTS | (uint32_t)RTX_OVERLAP_ANY)) return bad;
     WalkCall k;
-    if (int rc = walk_setup(c, "rtx_query_overlap", "descent", n, flags, filter, k)) return rc;
+    if (int rc = walk_setup(c, "rtx_query_overlap", "descent", n, flags, filter, k, true)) return rc;
     const int64_t K = max_hits;
     return walk_rounds<rtxop::ROW_FLOATS, 4>(c, k, boxes_dev, n, [&](int64_t first, const float * rows, int m, int blocks) {
         int32_t * const count = count_dev ? count_dev + first : nullptr;
@@ -2708,7 +2726,7 @@ static int query_sweep_box_impl(rtx_ctx * c, const void * sweeps_dev, int64_t n,
                                   triangle_id_dev ? (const void *)triangle_id_dev : (const void *)axis_dev;
     if (int bad = query_checks(c, sweeps_dev, n, some_out, flags, "rtx_query_sweep_box", (uint32_t)RTX_QUERY_SORT)) return bad;
     WalkCall k;
-    if (int rc = walk_setup(c, "rtx_query_sweep_box", "ordered descent", n, flags, filter, k)) return rc;
+    if (int rc = walk_setup(c, "rtx_query_sweep_box", "ordered descent", n, flags, filter, k, true)) return rc;
     return walk_rounds<rtxbs::ROW_FLOATS, rtxbs::KEY_FLOATS>(c, k, sweeps_dev, n, [&](int64_t first, const float * rows, int m, int blocks) {
         const DevBoxSweep t = { t_dev ? t_dev + first : nullptr, normal_dev ? normal_dev + 3 * first : nullptr, object_id_dev ? object_id_dev + first : nullptr,
                                 triangle_id_dev ? triangle_id_dev + first : nullptr, axis_dev ? axis_dev + first : nullptr };

@@ -38,7 +38,9 @@
 //   6. The other child is pushed WITH its d2 if that is < b2 ...
 //   7. ... and tested again against the then-current b2 when popped.
 //   8. A TLAS leaf takes its instances in tlas_indices order: p_l = xform_pos(world_inv, p), the BLAS from its root with p_l and the same b2.
-//      The instances of a leaf are stepped through in two registers, not on the stack.
+//      The instances of a leaf are stepped through in two registers, not on the stack.  The same b2: a world-space box distance (steps 4 .. 7
+//      over the TLAS) and local distances are compared with one bound, which is right for rigid poses only — the host refuses a frame
+//      with any other instance before this walk runs (rtxu::instance_rigid, rtx_update_math.h; include/rtx.h, rtx_query_nearest: Limits).
 //   9. A BLAS leaf tests its slots in order.
 //   FILTER (rtx_query_nearest_filtered; the same rule in rtx_hits_math.h and rtx_sweep_math.h).  Objects are numbered as RTX_AOV_OBJECT_ID
 //   numbers them: instance i -> i, sphere s -> I + s, plane p -> I + S + p.  An object EXISTS for a row iff (object_mask & row_mask) != 0;

@@ -14,10 +14,10 @@
 //          not walked.
 // FRAME    what the tests read: c, a_k, h, and E_j = g_0 |a_0.j| + (g_1 |a_1.j| + g_2 |a_2.j|) with g_k = h_k / (a_k . a_k), the box's own
 //          AABB c +- E.  In an instance's local frame c_l = xform_pos(world_inv, c), a_k = xform_dir(world_inv, a_k), h unchanged, E from the
-//          local axes.  Every test reads the box as the set |a_k . (p - c)| <= h_k: exact for a rigid pose; a uniformly scaled matrix scales
-//          the axes and so the box (the caveat rtx_query_nearest states for its distances), and the division by a_k . a_k keeps E the AABB of
+//          local axes.  Every test reads the box as the set |a_k . (p - c)| <= h_k: exact for a rigid pose, the only kind the host lets
+//          through (the rigid rule of rtx_query_nearest: its 2^-12 admits a uniform scale of a part in 10^4, which scales the axes and so the box), and the division by a_k . a_k keeps E the AABB of
 //          that same set, so NODE and TRIANGLE stay consistent under matrices that are a rotation only up to a part in 10^4, as stored poses
-//          are.  A sheared matrix (non-uniform scale under a rotation) is outside the specification.
+//          are.  A sheared or visibly scaled matrix is refused by the host.
 // TRIANGLE (p0, e1, e2 of the hot record, in the instance's local frame.)  In the box frame: d0 = p0 - c_l, v0 = (a_k . d0), f1 = (a_k . e1),
 //          f2 = (a_k . e2), v1 = v0 + f1, v2 = v0 + f2 — edges are projected, not end points, so roundings stay relative to the triangle's
 //          size.  Then the 13-axis separating-axis test of Akenine-Möller (Fast 3D triangle-box overlap testing), every axis in the one form

@@ -21,7 +21,7 @@
 //          is none); sq = sqrtf(w).  entry_time: t = tc - sq; a negative t becomes 0 when tc + sq >= 0 (the origin is inside by a rounding:
 //          the overlap test has looked already) and is no contact otherwise.
 // TRIANGLE (p0, e1, e2) of the hot record in the instance's local ray: co = xform_pos(world_inv, o), cd = xform_dir(world_inv, d) as in
-//          rtx_hits_math.h, r unchanged (so r is in local units under a scaled instance matrix).  m = co - p0, n = e1 x e2.  In this order:
+//          rtx_hits_math.h, r unchanged (local units: the host lets rigid poses through only).  m = co - p0, n = e1 x e2.  In this order:
 //   plane    h = n.m, g = n.cd, rn = r * sqrtf(n.n).  If |h| > rn the ball starts outside the plane's slab: s = h > 0 ? -g : g is its
 //            speed towards it; no candidate unless s > 0; tp = (|h| - rn) / s; no candidate unless tp <= bound (the walk's current best t:
 //            nothing of this triangle is reached earlier than its slab).  Otherwise tp = 0.  Most triangles of a leaf end here.

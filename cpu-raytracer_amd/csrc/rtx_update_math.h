@@ -73,6 +73,34 @@ RTX_HD void invert(const float * m, float * out) {
 }
 #undef RTXU_T
 
+// ---- rigid poses: what the length queries accept (include/rtx.h, rtx_query_nearest: Limits) --------------------------------------------------
+// A matrix is rigid when its linear part R (rows c[4a .. 4a+2]) is orthogonal within RTXU_RIGID_TAU: every |(R.R^T - I)ij| <= tau, in fp64
+// from the fp32 cells (a NaN or infinite cell fails every comparison: not rigid).  A reflection is orthogonal and passes.  An instance is
+// rigid when both its world and its world_inv are.  tau = 2^-12 is a measurement (Non-rigid matrices): the power of two at
+// least four times the largest deviation over 10^5 random fp32 unit quaternions through world_matrix / invert above (7.2e-7) and over every
+// scene the suite builds (3.9e-5: poses scripted with a five-decimal axis, which Quaternion::axis_angle does not normalise).  Host code
+// only: rtx_set_frame and rtxh_instances_rigid compile this one definition.
+#define RTXU_RIGID_TAU (1.0 / 4096.0)
+inline double rigid_deviation(const float * c) {
+    double worst = 0.0;
+    for (int i = 0; i < 3; i++)
+        for (int j = i; j < 3; j++) {
+            double s = i == j ? -1.0 : 0.0;
+            for (int k = 0; k < 3; k++) s += (double)c[4 * i + k] * (double)c[4 * j + k];
+            const double a = s < 0.0 ? -s : s;
+            if (a != a) return a;                           // a NaN cell: the deviation is a NaN, which no comparison accepts
+            if (a > worst) worst = a;
+        }
+    return worst;
+}
+inline bool matrix_rigid(const float * c) { return rigid_deviation(c) <= RTXU_RIGID_TAU; }
+inline bool instance_rigid(const float * world, const float * world_inv) { return matrix_rigid(world) && matrix_rigid(world_inv); }
+inline bool matrix_finite(const float * c) {
+    bool f = true;
+    for (int i = 0; i < 16; i++) { uint32_t u; __builtin_memcpy(&u, c + i, 4); f = f && (u & 0x7f800000u) != 0x7f800000u; }
+    return f;
+}
+
 // AABB::transform (AABB.cpp:55-73) of the BLAS root box by the world matrix w
 RTX_HD Box transform_box(const float * w, const float mn[3], const float mx[3]) {
     float ce[3], ex[3];

@@ -364,6 +364,19 @@ extern "C" int rtxh_tlas_build(rtxh_tlas * t, const float * positions, const flo
 }
 
 // ---- the balanced TLAS of rtx_update_instances: csrc/rtx_update_math.h, the code the kernels run, driven sequentially ----------------------
+// the rigid rule of the length queries (rtxu::instance_rigid, csrc/rtx_update_math.h: the definition rtx_set_frame compiles)
+extern "C" int rtxh_instances_rigid(const rtx_instance * instances, int32_t count, double * deviation_out) {
+    bool rigid = true; double worst = 0.0;
+    for (int32_t i = 0; instances && i < count; i++) {
+        rigid = rigid && rtxu::instance_rigid(instances[i].world, instances[i].world_inv);
+        const double a = rtxu::rigid_deviation(instances[i].world), b = rtxu::rigid_deviation(instances[i].world_inv);
+        if (!(worst != worst)) worst = a != a || a > worst ? a : worst;      // a NaN stays
+        if (!(worst != worst)) worst = b != b || b > worst ? b : worst;
+    }
+    if (deviation_out) *deviation_out = worst;
+    return rigid ? 1 : 0;
+}
+
 extern "C" int32_t rtxh_tlas_balanced_node_count(int32_t n) { return n < 1 || n > RTX_UPDATE_MAX_INSTANCES ? 0 : rtxu::tree_node_count(n); }
 extern "C" int32_t rtxh_tlas_balanced_inner_depth(int32_t n) { return rtxu::tree_inner_depth(n); }
 
@@ -733,12 +746,15 @@ void signed_store(const rtxh_nearest_scene & s, const float * row, const rtxnp::
     if (sg.feature_out) sg.feature_out[i] = feature;
 }
 const rtx_query_buffers kNoBuffers = {};
+// what the walk twins of the length queries refuse with RTX_ERR_STATE, as the device calls do (the exhaustive searches prune nothing and answer)
+bool scene_rigid(const rtxh_nearest_scene & s) { return rtxh_instances_rigid(s.instances, s.instance_count, nullptr) == 1; }
 }  // namespace
 
 static int query_nearest_host(const rtxh_nearest_scene * scene, const float * points, int64_t n, uint32_t channels, const rtx_query_buffers * out, int32_t * stack_max_out, const HostMasks * km,
                               const HostSigned * sg = nullptr) {
     if (sg && !sg->signed_out) return RTX_ERR_INVALID_ARG;
     if (int rc = nearest_scene_check(scene, points, n, channels, out, true, sg != nullptr)) return rc;
+    if (!scene_rigid(*scene)) return RTX_ERR_STATE;
     if (!out) out = &kNoBuffers;
     int high = 0;
     for (int64_t i = 0; i < n; i++) {
@@ -992,6 +1008,7 @@ void sweep_store(const rtxh_nearest_scene & s, const float * row, const rtxsp::A
 
 static int query_sweep_host(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, uint32_t channels, const rtx_query_buffers * out, int32_t * stack_max_out, const HostMasks * km) {
     if (int rc = nearest_scene_check(scene, sweeps, n, channels, out, true)) return rc;
+    if (!scene_rigid(*scene)) return RTX_ERR_STATE;
     int high = 0;
     for (int64_t i = 0; i < n; i++) {
         HostNearestStack st;
@@ -1139,6 +1156,7 @@ void overlap_exhaustive_row(const rtxh_nearest_scene & s, Scene & S, HostOverlap
 static int query_overlap_host(const rtxh_nearest_scene * scene, const float * boxes, int64_t n, int32_t max_hits, int32_t * object_out, int32_t * triangle_out, int32_t * count_out,
                               uint32_t flags, int32_t * stack_max_out, const HostMasks * km) {
     if (int rc = overlap_args_check(scene, boxes, n, max_hits, object_out, triangle_out, count_out, flags, true)) return rc;
+    if (!scene_rigid(*scene)) return RTX_ERR_STATE;
     const int form = (flags & RTX_OVERLAP_ANY) ? rtxop::FORM_ANY : (flags & RTX_OVERLAP_OBJECTS) ? rtxop::FORM_OBJECTS : rtxop::FORM_TRIANGLES;
     int high = 0;
     for (int64_t i = 0; i < n; i++) {
@@ -1246,6 +1264,7 @@ void sweep_box_store(const rtxh_nearest_scene & s, const float * row, const rtxb
 
 static int query_sweep_box_host(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, const HostBoxSweepOut & o, int32_t * stack_max_out, const HostMasks * km) {
     if (int rc = sweep_box_args_check(scene, sweeps, n, o, true)) return rc;
+    if (!scene_rigid(*scene)) return RTX_ERR_STATE;
     int high = 0;
     for (int64_t i = 0; i < n; i++) {
         HostNearestStack st;

@@ -1332,7 +1332,9 @@ class Renderer:
         (n, 4) of (x, y, z, maximum distance) on this context's GPU; channels as for query_closest.  Returns {name: tensor}: distance to the
         nearest surface point, that point, and what a hit there would report as normal, uv and ids.  No answer (nothing strictly nearer
         than the maximum distance, a non-finite coordinate, a maximum distance that is NaN or not above 0): distance inf, ids -1, the rest 0;
-        +inf is a legal maximum distance.  Distances are measured in each instance's local space.  Queued on torch's current stream, checked
+        +inf is a legal maximum distance.  Distances are measured in each instance's local space, so the frame's instances must be rigid poses
+        (a scaled, sheared or flattened matrix: RtxError, RTX_ERR_STATE — on every length query: this one, query_signed_distance, query_sweep,
+        query_overlap, query_overlapped, query_sweep_box; query_hits, query_closest and query_occluded take any finite matrix).  Queued on torch's current stream, checked
         and shaped like query_closest; sort=True (RTX_QUERY_SORT) walks the points of every round in Morton order, same answers row for row.
         Raw device pointers: points = address, n, out = {name: address} for every channel wanted.
         mask (here, on query_hits and on query_sweep): None = this call; an int = the row mask of every row; an int32 tensor (n,) on this
@@ -1422,7 +1424,7 @@ class Renderer:
         it touches at its origin), "position" the contact point on the surface, normal, uv and ids what query_nearest reports for that
         point; the geometric contact normal is (origin + t * direction - position) / r.  No answer (nothing touched before D, a zero
         direction, a non-finite component, D or r NaN or not above 0, r infinite): distance inf, ids -1, the rest 0; +inf is a legal D.
-        r and distances are measured in each instance's local space.  Queued on torch's current stream, checked and shaped like
+        r and distances are measured in each instance's local space (rigid poses only, as for query_nearest).  Queued on torch's current stream, checked and shaped like
         query_nearest; sort=True (RTX_QUERY_SORT) walks the rows of every round in the ray queries' order, same answers row for row.
         Raw device pointers: sweeps = address, n, out = {name: address} for every channel wanted.  mask: as for query_nearest — hidden
         objects neither stop the ball nor overlap it."""

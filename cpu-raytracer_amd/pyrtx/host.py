@@ -29,7 +29,7 @@ EXPORTS = ["rtxh_camera_basis", "rtxh_camera_update", "rtxh_quaternion_axis_angl
            "rtxh_query_nearest_filtered", "rtxh_query_nearest_exhaustive_filtered", "rtxh_query_hits_filtered", "rtxh_query_hits_exhaustive_filtered",
            "rtxh_query_sweep_filtered", "rtxh_query_sweep_exhaustive_filtered", "rtxh_blas_pseudonormals",
            "rtxh_query_signed_distance", "rtxh_query_signed_distance_filtered", "rtxh_query_signed_distance_exhaustive", "rtxh_query_signed_distance_exhaustive_filtered",
-           "rtxh_query_overlap", "rtxh_query_overlap_exhaustive", "rtxh_query_overlap_filtered", "rtxh_query_overlap_exhaustive_filtered", "rtxh_overlap_margin"]
+           "rtxh_query_overlap", "rtxh_query_overlap_exhaustive", "rtxh_query_overlap_filtered", "rtxh_query_overlap_exhaustive_filtered", "rtxh_overlap_margin", "rtxh_instances_rigid"]
 FLOAT_EXPORTS = ("rtxh_nearest_distance_bound", "rtxh_nearest_box_d2", "rtxh_nearest_triangle_d2", "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2", "rtxh_hits_margin", "rtxh_sweep_bound", "rtxh_overlap_margin", "rtxh_sweep_box_bound")      # return a float, not a status
 
 PI = np.float32(3.14159265359)          # Util.h:8
@@ -109,6 +109,7 @@ def lib():
         l.rtxh_tlas_build_balanced.argtypes = [i32, vp, vp, vp, vp, C.POINTER(i32)]
         l.rtxh_scene_update_balanced.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32)]
         l.rtxh_tlas_balanced_node_count.argtypes = [i32]
+        l.rtxh_instances_rigid.argtypes = [vp, i32, C.POINTER(C.c_double)]
         l.rtxh_tlas_balanced_inner_depth.argtypes = [i32]
         l.rtxh_blas_refit.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, vp]
         l.rtxh_blas_build_balanced.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, C.POINTER(i32), vp, vp, vp, vp]
@@ -234,6 +235,15 @@ class Tlas:
             lib().rtxh_tlas_destroy(self.h)
         except Exception:
             pass
+
+
+def instances_rigid(instances, deviation: bool = False):
+    """rtxh_instances_rigid: True when every instance's world and world_inv are rigid poses within tau = 2^-12 (csrc/rtx_update_math.h), the
+    rule by which rtx_set_frame decides whether the length queries answer.  deviation=True: (rigid, largest |(R.R^T - I)ij|)."""
+    inst = np.ascontiguousarray(instances, sio.INSTANCE)
+    dev = C.c_double(0.0)
+    rigid = lib().rtxh_instances_rigid(inst.ctypes.data if len(inst) else None, len(inst), C.byref(dev)) == 1
+    return (rigid, float(dev.value)) if deviation else rigid
 
 
 def tlas_balanced_node_count(n: int) -> int:

@@ -268,7 +268,16 @@ int rtx_upload_sky(rtx_ctx * ctx, const float * texels_rgb, int32_t size);
 
 /* The result of Scene::update(delta) (Scene.cpp:139-171): camera basis,
  * instance matrices, rebuilt TLAS, analytic primitives, lights.  Must be
- * called before rendering, never concurrently with it (Main.cpp:54-57).      */
+ * called before rendering, never concurrently with it (Main.cpp:54-57).
+ * The instances' world / world_inv are taken as given, 16 floats each: any
+ * finite matrix is rendered and traced in the instance's local ray (rigid,
+ * scaled, mirrored, sheared, singular).  A NaN or infinite cell is
+ * RTX_ERR_INVALID_ARG and nothing changes: the previous frame stays bound.
+ * Finite cells can still carry a far origin to a non-finite local origin
+ * (|cell| * |origin| beyond FLT_MAX), which the packet kernels do not
+ * survive: keep matrices and origins within what fp32 multiplies.  Whether
+ * every instance is a rigid pose is decided here, for the length queries
+ * (rtx_query_nearest: Limits).                                               */
 int rtx_set_frame(rtx_ctx * ctx, const rtx_frame * frame);
 
 enum {
@@ -760,11 +769,19 @@ int rtx_debug_query_order(rtx_ctx * ctx, const void * rows_dev, int32_t row_floa
  * back: bit-identical, row for row; the sort scratch and its growth rule are those of the ray queries.
  * Errors, in this order: RTX_ERR_INVALID_ARG: channels == 0 or with bits outside RTX_QUERY_ALL; a NULL ctx, points_dev or out, n < 1; any
  * flag but RTX_QUERY_SORT.  RTX_ERR_STATE: before rtx_set_frame, in heat-map mode, a scene a render call refuses.  RTX_ERR_LIMIT: a BVH
- * deeper than rtx_config.stack_size allows (the check of rtx_render_tiles); and the walk's own stack rule: it holds at most (TLAS inner
+ * deeper than rtx_config.stack_size allows (the check of rtx_render_tiles).  RTX_ERR_STATE: the rigid rule — a frame with an instance
+ * whose matrix is not a rigid pose (Limits, below).  RTX_ERR_LIMIT: the walk's own stack rule: it holds at most (TLAS inner
  * depth + 1) + (deepest BLAS inner depth + 1) entries (inner depth: that of the deepest inner node, root 0; -1 for a single leaf), and a
  * scene that needs more than rtx_config.stack_size is refused.  An error queues nothing.
- * Limits: distances are measured in each instance's LOCAL space — for the rigid poses Mesh::update and rtx_update_instances make from unit
- * quaternions that is the world metric up to rounding; a scaled world matrix handed to rtx_set_frame is measured in its local units.  The
+ * Limits: distances are measured in each instance's LOCAL space, and the walk prunes by WORLD-space box distances: the two agree only for
+ * rigid poses.  The rigid rule: rtx_set_frame judges every instance it is handed — rigid iff, for the linear parts R of both world and
+ * world_inv, every |(R.R^T - I)ij| <= 2^-12, in fp64 (a reflection passes; rtxh_instances_rigid in rtx_host.h is the same code) — and a frame
+ * with a scaled, sheared or flattened instance is refused by this call, by rtx_query_signed_distance, rtx_query_sweep, rtx_query_overlap and
+ * rtx_query_sweep_box and by their _filtered forms (before this rule such a frame lost answers: the walk pruned a scaled instance by a
+ * bound in its local units).  rtx_query_hits, rtx_query_closest, rtx_query_occluded and the render calls take any finite matrix: t does not
+ * change under an affine map.  After rtx_update_instances the frame counts as rigid, by that call's unit-quaternion contract.  For the
+ * poses Mesh::update makes from unit quaternions the local metric is the world metric up to rounding; a matrix within the 2^-12 but
+ * farther from orthogonal than those adds 2^-13 times the distance to the bounds stated for these queries.  The
  * answer may depend on the tree within the bound: a refit, or a rebuild of the same triangles, may return another triangle at an equal
  * or nearly equal distance.  The side of the surface: rtx_query_signed_distance, below.  Out of scope: k nearest, all within a radius,
  * barycentrics, the rtx_group_* path.                                                                                                    */
@@ -801,7 +818,8 @@ int rtx_query_nearest(rtx_ctx * ctx, const void * points_dev /* [n][4] f32: x, y
  * walked in the order of the ray queries' 7-float keys and the answers scattered back: bit-identical, row for row.
  * Errors, in this order: RTX_ERR_INVALID_ARG: a max_hits / channels / count_dev combination other than the two above, channels outside
  * RTX_QUERY_ALL; a NULL ctx or segments_dev, a NULL out (a NULL count_dev in the count-only form), n < 1; any flag but RTX_QUERY_SORT.
- * RTX_ERR_STATE and RTX_ERR_LIMIT: as for rtx_query_nearest, its stack rule included.  An error queues nothing.
+ * RTX_ERR_STATE and RTX_ERR_LIMIT: as for rtx_query_nearest, its stack rule included and its rigid rule left out (t does not change under an
+ * affine map: any finite matrix is served).  An error queues nothing.
  * Limits: a BLAS whose leaves share triangles (the reference's SBVH with spatial splits) holds such a triangle once per slot, and every slot
  * is a hit.  Out of scope: hits beyond RTX_QUERY_MAX_HITS per row, an any-hit callback or per-material filtering (whole objects are
  * hidden by mask: filtered queries, below), a per-ray tmin other than RAY_EPSILON, signed distance as a single call, barycentrics as a channel, the rtx_group_* path.                                   */
@@ -837,9 +855,9 @@ int rtx_query_hits(rtx_ctx * ctx, const void * segments_dev /* [n][7] f32: origi
  * Any n >= 1, in rounds of RTX_QUERY_CHUNK_RAYS rows, one kernel launch per round.  flags: RTX_QUERY_SORT or 0; with it the rows of a round are
  * walked in the order of the ray queries' 7-float keys, taken over each row's first seven floats, and the answers scattered back:
  * bit-identical, row for row.
- * Errors, in this order and with the codes of rtx_query_nearest, its stack rule included.  An error queues nothing.
- * Limits: r and the distances are measured in each instance's LOCAL space, as for rtx_query_nearest — the world metric for rigid poses, local
- * units under a scaled world matrix.  The answer may depend on the tree within the bound.  Out of scope: swept capsules or rotating shapes (a
+ * Errors, in this order and with the codes of rtx_query_nearest, its rigid rule and its stack rule included.  An error queues nothing.
+ * Limits: r and the distances are measured in each instance's LOCAL space, as for rtx_query_nearest — the world metric for rigid poses; a
+ * frame with a scaled, sheared or flattened instance is refused (the rigid rule of rtx_query_nearest).  The answer may depend on the tree within the bound.  Out of scope: swept capsules or rotating shapes (a
  * swept box is rtx_query_sweep_box), all contacts along the sweep, a contact-normal channel, the rtx_group_* path.                                                    */
 int rtx_query_sweep(rtx_ctx * ctx, const void * sweeps_dev /* [n][8] f32: origin, direction, max distance, radius */, int64_t n,
                     uint32_t channels, const rtx_query_buffers * out, uint32_t flags /* RTX_QUERY_SORT or 0 */);
@@ -903,8 +921,8 @@ int rtx_query_sweep_filtered(rtx_ctx * ctx, const void * sweeps_dev, int64_t n, 
  * may be 0, and then out may be NULL — plus signed_dev[i] (required): the distance of row i, NEGATIVE iff r . N < 0, where r is the vector
  * from the nearest surface point to the row's point and N the pseudonormal of the feature of the nearest triangle that holds that point: the
  * face normal e1 x e2 of the slot, the edge's or the vertex's record of the tables rtx_blas_pseudonormals made.  r . N == 0, a zero N and a
- * NaN are positive; a point on the surface gets +0.  Both vectors are in the instance's local space, so rigid, scaled and mirrored instances
- * need nothing more.  A sphere is negative inside (l < r with the two roots of its distance), a plane where n.p + distance < 0.  A row
+ * NaN are positive; a point on the surface gets +0.  Both vectors are in the instance's local space, so rigid and mirrored instances
+ * need nothing more (a scaled one is refused: the rigid rule of rtx_query_nearest).  A sphere is negative inside (l < r with the two roots of its distance), a plane where n.p + distance < 0.  A row
  * without an answer gets +INFINITY.  feature_dev[i] (or NULL): 0 none, 1 face, 2 edge, 3 vertex, 4 sphere, 5 plane; + 8 when the winning
  * mesh has no tables — then e1 x e2 is used in every region, the naive rule, which is wrong near convex and concave edges and vertices.
  * For a closed, consistently oriented mesh negative is inside; for an open one it is the side the orientation calls back.  The sign rule is
@@ -913,7 +931,7 @@ int rtx_query_sweep_filtered(rtx_ctx * ctx, const void * sweeps_dev, int64_t n, 
  * mesh's 32-byte table entry and, behind it, one record (an edge) or a slot vertex and its record (a vertex): up to three dependent loads.
  * Errors, in this order: RTX_ERR_INVALID_ARG: a NULL ctx; channels with bits outside RTX_QUERY_ALL; a NULL or misaligned signed_dev, a
  * misaligned feature_dev; a NULL points_dev, a NULL out with channels != 0, n < 1; any flag but RTX_QUERY_SORT.  Then RTX_ERR_STATE and
- * RTX_ERR_LIMIT as for rtx_query_nearest, its stack rule included, and the state rule of the filtered queries.  An error queues nothing.
+ * RTX_ERR_LIMIT as for rtx_query_nearest, its rigid rule and its stack rule included, and the state rule of the filtered queries.  An error queues nothing.
  * Limits: the sign is relative to the OBJECT that owns the nearest point — for overlapping solids it is not the sign of their union.  Within
  * the accuracy bound of rtx_query_nearest of a surface, and where r is within rounding of perpendicular to N, the sign is not determined.
  * Out of scope: signed sweeps, generalized winding numbers, the sign of a union, the rtx_group_* path.                                    */
@@ -931,7 +949,8 @@ int rtx_query_signed_distance(rtx_ctx * ctx, const void * points_dev /* [n][4] f
  * query family measures everywhere: a triangle overlaps by the 13-axis separating-axis test (touching is overlapping), a sphere when its
  * shell meets the box (a box strictly inside the ball does not overlap), a plane when the box reaches it.  Everything is specified in the
  * header comment of csrc/rtx_overlap_math.h (ROW, TRIANGLE, SPHERE, PLANE, NODE, ORDER, WALK, FORMS, MARGIN, PROMISED); rtxh_query_overlap in
- * rtx_host.h gives the same bits.  Like rtx_query_nearest the test runs in each instance's local frame: exact for rigid poses.
+ * rtx_host.h gives the same bits.  Like rtx_query_nearest the test runs in each instance's local frame: exact for rigid poses, and a frame
+ * with an instance that is not one is refused (the rigid rule of rtx_query_nearest).
  * Three forms, chosen by flags:
  *   0                      the (object, triangle slot) overlaps of every row, ordered by (object_id, triangle_id) ascending — object ids in
  *                          the numbering of RTX_QUERY_OBJECT_ID, triangle_id -1 for spheres and planes: object_id_dev / triangle_id_dev
@@ -948,7 +967,7 @@ int rtx_query_signed_distance(rtx_ctx * ctx, const void * points_dev /* [n][4] f
  * Errors, in this order: RTX_ERR_INVALID_ARG: a NULL ctx; max_hits outside [0, RTX_QUERY_MAX_HITS]; RTX_OVERLAP_ANY with max_hits != 0 or
  * with RTX_OVERLAP_OBJECTS; RTX_OVERLAP_OBJECTS with a triangle_id_dev; max_hits == 0 without a count_dev; max_hits > 0 without an id array;
  * a NULL boxes_dev, n < 1; any flag but RTX_QUERY_SORT, RTX_OVERLAP_OBJECTS, RTX_OVERLAP_ANY.  Then RTX_ERR_STATE and RTX_ERR_LIMIT as for
- * rtx_query_nearest, its stack rule included, and the state rule of the filtered queries.  An error queues nothing.
+ * rtx_query_nearest, its rigid rule and its stack rule included, and the state rule of the filtered queries.  An error queues nothing.
  * Out of scope: capsules, spheres and convex hulls as query volumes, penetration depth (a swept box is rtx_query_sweep_box), or contact points, more than
  * RTX_QUERY_MAX_HITS entries per row, the rtx_group_* path.                                                                              */
 enum { RTX_OVERLAP_OBJECTS = 512, RTX_OVERLAP_ANY = 1024 };      /* bits of rtx_query_overlap's flags, beside RTX_QUERY_SORT */
@@ -984,15 +1003,15 @@ int rtx_query_overlap_filtered(rtx_ctx * ctx, const void * boxes_dev, int64_t n,
  * The candidate functions, the order rule, the walk, the slack of its node test and the accuracy bound (stated in distance: at the returned
  * t the returned primitive's largest separating gap is within the bound of 0, and nothing penetrates deeper than the bound before t) are
  * specified in the header comment of csrc/rtx_boxsweep_math.h; rtxh_query_sweep_box in rtx_host.h is the same code on the host and gives the
- * same bits.  Like rtx_query_overlap the test runs in each instance's local frame: exact for rigid poses.
+ * same bits.  Like rtx_query_overlap the test runs in each instance's local frame: exact for rigid poses; other frames are refused.
  * Any n >= 1, in rounds of RTX_QUERY_CHUNK_RAYS rows, one kernel launch per round.  flags: RTX_QUERY_SORT or 0; with it the rows of a round are
  * walked in the order of the ray queries' 7-float keys, taken over each row's first seven floats, and the answers scattered back:
  * bit-identical, row for row.  rtx_query_sweep_box_filtered: the same with the object masks of the filtered queries above and their state
  * rule — a hidden object neither stops the box nor overlaps it, a row whose mask is 0 gets the no-answer values without a walk; a NULL filter
  * is the unfiltered call.
  * Errors, in this order: RTX_ERR_INVALID_ARG: a NULL ctx; a NULL sweeps_dev, five NULL outputs, n < 1; any flag but RTX_QUERY_SORT.  Then
- * RTX_ERR_STATE and RTX_ERR_LIMIT as for rtx_query_nearest, its stack rule included, and the state rule of the filtered queries.  An error
- * queues nothing.
+ * RTX_ERR_STATE and RTX_ERR_LIMIT as for rtx_query_nearest, its rigid rule and its stack rule included, and the state rule of the filtered
+ * queries.  An error queues nothing.
  * Out of scope: contact points or manifolds, rotation during the sweep, capsules and hulls, all contacts along the path, the rtx_group_* path. */
 int rtx_query_sweep_box(rtx_ctx * ctx, const void * sweeps_dev /* [n][14] f32: centre, direction, max distance, half extents, quaternion */, int64_t n,
                         float * t_dev /* [n] or NULL */, float * normal_dev /* [n][3] or NULL */, int32_t * object_id_dev /* [n] or NULL */,

@@ -93,6 +93,10 @@ int rtxh_tlas_build(rtxh_tlas * t, const float * positions, const float * aabbs,
  * alone; slots that are no node are zero.  Defined for every float input: the indices are always a permutation, every range lies inside the
  * arrays.  O(n log n).  positions n*3, aabbs n*6 (min, max); nodes_out holds rtxh_tlas_balanced_node_count(n) entries, indices_out n.
  * 1 <= n <= 65 536 (RTX_ERR_LIMIT above).                                                                                                  */
+/* The rigid rule of the length queries (include/rtx.h, rtx_query_nearest: Limits), the one definition rtx_set_frame compiles: 1 when for
+ * every instance the linear parts R of world and world_inv have every |(R.R^T - I)ij| <= 2^-12 in fp64, else 0 (a NaN cell: 0; no instances:
+ * 1).  deviation_out (may be NULL): the largest such entry over all instances.                                                             */
+int rtxh_instances_rigid(const rtx_instance * instances, int32_t instance_count, double * deviation_out);
 int32_t rtxh_tlas_balanced_node_count(int32_t instance_count);     /* 2 << ceil(log2 n); 0 for n outside the supported range */
 int32_t rtxh_tlas_balanced_inner_depth(int32_t instance_count);    /* depth of the deepest inner node (-1 for one instance): ceil(log2 n) - 1 */
 int rtxh_tlas_build_balanced(int32_t instance_count, const float * positions, const float * aabbs,
@@ -216,7 +220,10 @@ int rtxh_query_sort_order(const float * rows, int32_t row_floats, int64_t n, int
  * one and exceeds it by at most rtxh_nearest_distance_bound(S, W) of the exhaustive winner (S = |p_l - p0| + |e1| + |e2|; W = |p| + |p_l|
  * for an instance whose matrix is not the identity, else 0).
  * RTX_ERR_INVALID_ARG: a null scene / points / out, n < 1, channels 0 or outside RTX_QUERY_ALL, a negative count, a count without its
- * array, an instance whose blas_id is outside [0, blas_count); RTX_ERR_LIMIT: a tree deeper than RTX_MAX_STACK entries of the walk.     */
+ * array, an instance whose blas_id is outside [0, blas_count); RTX_ERR_LIMIT: a tree deeper than RTX_MAX_STACK entries of the walk; then
+ * RTX_ERR_STATE, from the walks of the length queries only (rtxh_query_nearest, _signed_distance, _sweep, _overlap, _sweep_box and their
+ * _filtered forms): an instance that rtxh_instances_rigid does not accept, as on the device (include/rtx.h, rtx_query_nearest: Limits).
+ * The exhaustive searches prune nothing and answer for any matrix, in local units; so does rtxh_query_hits.                               */
 typedef struct rtxh_nearest_blas {
     const rtx_bvh_node * nodes; const rtx_triangle_hot * hot; const rtx_triangle_cold * cold;
     int32_t node_count, triangle_count, material_offset, pad;
@@ -262,7 +269,7 @@ float rtxh_hits_margin(float kappa, float scale);
  * The candidate functions on their own, for tests that restate them: 1 and *t_out (a triangle's weights in uv_out, the squared distance from
  * the origin in d20_out) when the primitive yields a candidate, else 0.  rtxh_sweep_triangle takes the LOCAL ray and the walk's bound
  * (no answer's d20: the "settled" early-out of the header, which changes no answer, never applies).
- * RTX_ERR_INVALID_ARG and RTX_ERR_LIMIT: as for rtxh_query_nearest.                                                                     */
+ * RTX_ERR_INVALID_ARG, RTX_ERR_STATE and RTX_ERR_LIMIT: as for rtxh_query_nearest.                                                      */
 int rtxh_query_sweep(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, uint32_t channels, const rtx_query_buffers * out, int32_t * stack_max_out);
 int rtxh_query_sweep_exhaustive(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, uint32_t channels, const rtx_query_buffers * out);
 float rtxh_sweep_bound(float local_scale, float world_scale, float travelled, float radius);
@@ -280,7 +287,8 @@ int rtxh_sweep_plane(const float origin[3], const float direction[3], float radi
  * the exhaustive one.  The _filtered forms take object_masks, row_masks and row_mask as the filtered walk queries below.
  * rtxh_overlap_margin(S, W, kappa): rtxop::margin, how far as a distance the computed triangle test may be from the exact one on an axis of
  * conditioning kappa (MARGIN in that header).
- * RTX_ERR_INVALID_ARG: the argument rules of rtx_query_overlap and rtxh_query_nearest; RTX_ERR_LIMIT: a tree deeper than RTX_MAX_STACK entries. */
+ * RTX_ERR_INVALID_ARG: the argument rules of rtx_query_overlap and rtxh_query_nearest; RTX_ERR_LIMIT: a tree deeper than RTX_MAX_STACK entries;
+ * RTX_ERR_STATE: a non-rigid instance (the walk only), as for rtxh_query_nearest. */
 int rtxh_query_overlap(const rtxh_nearest_scene * scene, const float * boxes, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
                        int32_t * count_out, uint32_t flags, int32_t * stack_max_out);
 int rtxh_query_overlap_exhaustive(const rtxh_nearest_scene * scene, const float * boxes, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
@@ -302,7 +310,8 @@ float rtxh_overlap_margin(float local_scale, float world_scale, float kappa);
  * rtxh_sweep_box_bound(S, W, T, kappa): rtxbs::sweep_box_bound, the bound in distance of ACCURACY in that header.
  * rtxh_sweep_box_triangle / _sphere / _plane: one candidate function at the row's world frame (an identity instance): 1 and t (axis) when
  * the primitive yields a candidate, else 0; bound is the walk's current t.
- * RTX_ERR_INVALID_ARG: five NULL outputs and the argument rules of rtxh_query_nearest; RTX_ERR_LIMIT: a tree deeper than RTX_MAX_STACK entries. */
+ * RTX_ERR_INVALID_ARG: five NULL outputs and the argument rules of rtxh_query_nearest; RTX_ERR_LIMIT: a tree deeper than RTX_MAX_STACK entries;
+ * RTX_ERR_STATE: a non-rigid instance (the walk only), as for rtxh_query_nearest. */
 int rtxh_query_sweep_box(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, float * t_out, float * normal_out, int32_t * object_id_out, int32_t * triangle_id_out,
                          int32_t * axis_out, int32_t * stack_max_out, const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask);
 int rtxh_query_sweep_box_exhaustive(const rtxh_nearest_scene * scene, const float * sweeps, int64_t n, float * t_out, float * normal_out, int32_t * object_id_out,

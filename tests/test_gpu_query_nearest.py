@@ -335,6 +335,14 @@ def test_every_error_code_in_order_and_a_valid_query_after_it(api):
     rt = api.Renderer(three)
     rt.render()                                                                # rays are served: 22 + 2 entries
     assert lib.rtx_query_nearest(rt.ctx, pp, n, D, B, 0) == LIMIT, "(1 + 1) + (22 + 1) = 25 entries against a stack_size of 24"
+    # a frame with a scaled instance: RTX_ERR_STATE after the checks of a render call (a shallow stack stays RTX_ERR_LIMIT) and before the walk's
+    # own stack rule (the three chains, enlarged by 2, are no longer RTX_ERR_LIMIT); the argument checks still come first; nothing is queued
+    import affineset
+    rn = api.Renderer(affineset.with_linear(three, [affineset.LINEAR["uniform2"]]))
+    rsn = api.Renderer(affineset.with_linear(shallow, [affineset.LINEAR["uniform2"]]))
+    assert lib.rtx_query_nearest(rn.ctx, pp, n, D, B, 0) == STATE and "rigid" in lib.rtx_last_error(rn.ctx).decode()
+    assert lib.rtx_query_nearest(rn.ctx, pp, n, 0, B, 0) == INVALID and lib.rtx_query_nearest(rsn.ctx, pp, n, D, B, 0) == LIMIT
+    rn.synchronize(); rsn.synchronize()
     for other in (empty, rh, rs, rc, rt):
         other.synchronize()
     r.synchronize()

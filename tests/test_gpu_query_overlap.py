@@ -595,6 +595,15 @@ def test_every_error_code_in_order_and_a_valid_query_after_it(api):
     rt = api.Renderer(three)
     assert lib.rtx_query_overlap(rt.ctx, pp, n, 2, op, tp, cp, 0) == LIMIT, "(1 + 1) + (22 + 1) = 25 entries against a stack_size of 24"
     assert lib.rtx_query_overlap(rt.ctx, pp, n, 0, None, None, cp, ANY) == LIMIT
+    # a frame with a scaled instance: RTX_ERR_STATE after the checks of a render call (a shallow stack stays RTX_ERR_LIMIT) and before the walk's
+    # own stack rule (the three chains, enlarged by 2, are no longer RTX_ERR_LIMIT); the argument checks still come first; nothing is queued
+    import affineset
+    rn = api.Renderer(affineset.with_linear(three, [affineset.LINEAR["uniform2"]]))
+    rsn = api.Renderer(affineset.with_linear(shallow, [affineset.LINEAR["uniform2"]]))
+    assert lib.rtx_query_overlap(rn.ctx, pp, n, 2, op, tp, cp, 0) == STATE and "rigid" in lib.rtx_last_error(rn.ctx).decode()
+    assert lib.rtx_query_overlap(rn.ctx, pp, n, 0, None, None, cp, ANY) == STATE and lib.rtx_query_overlap_filtered(rn.ctx, pp, n, 2, op, tp, cp, 0, C.byref(filt)) == STATE
+    assert lib.rtx_query_overlap(rn.ctx, pp, n, 9, op, tp, cp, 0) == INVALID and lib.rtx_query_overlap(rsn.ctx, pp, n, 2, op, tp, cp, 0) == LIMIT
+    rn.synchronize(); rsn.synchronize()
     assert "stack" in lib.rtx_last_error(rt.ctx).decode()
     # the state rule of the filtered call comes last: a table set for other counts than the frame's
     r.set_object_masks(np.full(len(sc.instances) + len(sc.spheres) + len(sc.planes), 1, np.uint32))

@@ -476,6 +476,15 @@ def test_state_and_limit_errors_in_the_documented_order(api):
     assert q(rt.ctx) == LIMIT and q(rt.ctx, ch=0, out=None) == LIMIT, "(1 + 1) + (22 + 1) = 25 entries against a stack_size of 24"
     assert b"stack" in lib.rtx_last_error(rt.ctx)
     arguments_first(rt.ctx, "the walk's stack rule")
+    # a frame with a scaled instance: RTX_ERR_STATE after the checks of a render call (a shallow stack stays RTX_ERR_LIMIT) and before the walk's
+    # own stack rule (the three chains, enlarged by 2, are no longer RTX_ERR_LIMIT); the argument checks still come first; nothing is queued
+    import affineset
+    rn = api.Renderer(affineset.with_linear(three, [affineset.LINEAR["uniform2"]]))
+    rsn = api.Renderer(affineset.with_linear(shallow, [affineset.LINEAR["uniform2"]]))
+    assert q(rn.ctx) == STATE and q(rn.ctx, ch=0, out=None) == STATE and q(rn.ctx, flt=FL) == STATE, "a scaled instance, before the walk's stack rule"
+    assert b"rigid" in lib.rtx_last_error(rn.ctx) and q(rsn.ctx) == LIMIT
+    arguments_first(rn.ctx, "a scaled instance")
+    rn.synchronize(); rsn.synchronize()
     rc.synchronize()
     sd.view(torch.int32).fill_(PATTERN)                                # the valid call on the chain wrote it
     torch.cuda.synchronize()

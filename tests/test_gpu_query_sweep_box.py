@@ -442,6 +442,15 @@ def test_every_error_code_in_order_and_a_valid_query_after_it(api):
     three.tlas_nodes, three.tlas_indices = host.tlas_build_balanced(np.array(centres, f32), np.array(bxs, f32))
     rt = api.Renderer(three)
     assert lib.rtx_query_sweep_box(rt.ctx, pp, n, tp, np_, op, sp, ap, 0) == LIMIT, "(1 + 1) + (22 + 1) = 25 entries against a stack_size of 24"
+    # a frame with a scaled instance: RTX_ERR_STATE after the checks of a render call (a shallow stack stays RTX_ERR_LIMIT) and before the walk's
+    # own stack rule (the three chains, enlarged by 2, are no longer RTX_ERR_LIMIT); the argument checks still come first; nothing is queued
+    import affineset
+    rn = api.Renderer(affineset.with_linear(three, [affineset.LINEAR["uniform2"]]))
+    rsn = api.Renderer(affineset.with_linear(shallow, [affineset.LINEAR["uniform2"]]))
+    assert lib.rtx_query_sweep_box(rn.ctx, pp, n, tp, np_, op, sp, ap, 0) == STATE and "rigid" in lib.rtx_last_error(rn.ctx).decode()
+    assert lib.rtx_query_sweep_box_filtered(rn.ctx, pp, n, tp, np_, op, sp, ap, 0, C.byref(filt)) == STATE
+    assert lib.rtx_query_sweep_box(rn.ctx, pp, n, tp, np_, op, sp, ap, 1) == INVALID and lib.rtx_query_sweep_box(rsn.ctx, pp, n, tp, np_, op, sp, ap, 0) == LIMIT
+    rn.synchronize(); rsn.synchronize()
     assert "stack" in lib.rtx_last_error(rt.ctx).decode()
     r.set_object_masks(np.full(len(sc.instances) + len(sc.spheres) + len(sc.planes), 1, np.uint32))
     fewer = copy.deepcopy(sc); fewer.spheres = fewer.spheres[:-1]
