@@ -512,7 +512,30 @@ static void twelve_levels() {
     }
 }
 
+// RTX_PK_LONE_ENTRY: the plan carries the frame's two facts with the knob applied, copy_class never without lone, and either changes the plan's bytes
+static void lone_entry() {
+    CASE("lone entry");
+    PlanInputs in = frame(); in.knobs.lone_entry = true;
+    const RenderPlan none = plan_render(in);
+    CHECK(!none.lone && !none.copy_class);
+    in.lone = true;
+    const RenderPlan lone = plan_render(in);
+    CHECK(lone.lone == 1 && !lone.copy_class && memcmp(&lone, &none, sizeof(lone)) != 0);
+    in.copy_class = true;
+    const RenderPlan copy = plan_render(in);
+    CHECK(copy.lone == 1 && copy.copy_class == 1 && memcmp(&copy, &lone, sizeof(copy)) != 0);
+    in.lone = false;                                                     // a fact the host never states: still no copy_class without lone
+    CHECK(!plan_render(in).lone && !plan_render(in).copy_class);
+    in.lone = true; in.knobs.lone_entry = false;
+    const RenderPlan off = plan_render(in);
+    CHECK(!off.lone && !off.copy_class);
+    in.lone = false; in.copy_class = false;
+    const RenderPlan off_none = plan_render(in);
+    CHECK(memcmp(&off, &off_none, sizeof(off)) == 0);                    // nothing else of the plan depends on the facts
+}
+
 int main() {
+    lone_entry();
     small_grids();
     twelve_levels();
     modes_and_schedule();

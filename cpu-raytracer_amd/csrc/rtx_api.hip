@@ -113,6 +113,9 @@ struct rtx_ctx {
     // every instance of the frame is a rigid pose (rtxu::instance_rigid): judged from the matrices rtx_set_frame is handed, true after
     // rtx_update_instances by its unit-quaternion contract; the length queries refuse a frame that is not (walk_setup)
     bool frame_rigid = true;
+    // plan_lone_facts of the state rtx_set_frame was handed; rtx_update_instances clears both (poses and TLAS made on the device: the host has not
+    // seen the matrices).  DevScene::lone / copy_class are these with the knob applied
+    LoneFacts frame_lone = { false, false };
     // rtx_update_instances: a device block of its own for the updated instances / TLAS (both node layouts) / indices and the builder's scratch
     // (AABBs, bounds, keys), grown only; the DevScene pointers are switched to it, the rest of the frame stays in d_frame.  d_upd_sort = rocPRIM's
     // temporary storage and the unsorted keys (multi-launch path), grown only
@@ -258,6 +261,7 @@ extern "C" int rtx_create(const rtx_config * config, rtx_ctx ** out_ctx) {
     K.tex_pass_levels = (int)knob_int("RTX_TEX_PASS_LEVELS", rtxt::DEFAULT_PASS_LEVELS, 1, rtxt::MAX_PASS_LEVELS);      // DESIGN.md 9, Device-side texture update
     c->nearest_fetch = knob_int("RTX_NEAREST_FETCH", 1, 0, 1) != 0;     // rtx_query_nearest: workgroups fetch tiles from a counter (1) or take them by stride (0): DESIGN.md 9
     c->query_grid = (int)knob_int("RTX_QUERY_GRID", 0, 0, 1 << 20);    // the walk queries: at most this many workgroups, each takes tile after tile (0: no cap); tests/test_gpu_query_tiles.py
+    K.lone_entry = knob_int("RTX_PK_LONE_ENTRY", 1, 0, 1) != 0;         // 0: the packet kernels take the TLAS iterator path for every scene (A/B runs, tests/test_gpu_lone_entry.py)
     K.fail_item_alloc = knob_int("RTX_DEBUG_FAIL_ITEM_ALLOC", 0, 0, 1) != 0;      // tests: the item buffer's allocation fails (a size no device has), the fallback kernel must take over
     int bpc = 0;
     hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k_trace_fast<false>, RTX_TRACE_BLOCK, 0);
@@ -581,6 +585,8 @@ extern "C" int rtx_set_frame(rtx_ctx * c, const rtx_frame * f) {
     for (int i = 0; i < f->plane_count; i++) c->frame_primitive_materials.push_back(f->planes[i].material_id);
     c->tlas_inner_depth = tlas_depth;
     c->frame_set = true; c->refs_dirty = true; c->frame_rigid = rigid;
+    c->frame_lone = plan_lone_facts(f->instance_count, f->tlas_nodes, f->tlas_node_count, f->tlas_indices, f->tlas_index_count, f->instances);
+    s.lone = c->knobs.lone_entry && c->frame_lone.lone; s.copy_class = s.lone && c->frame_lone.copy_class;
     return RTX_OK;
 }
 
@@ -835,6 +841,7 @@ extern "C" int rtx_update_instances(rtx_ctx * c, const void * positions_dev, con
     c->tlas_inner_depth = rtxu::tree_inner_depth(n);
     c->refs_dirty = true;
     c->frame_rigid = true;                                  // unit quaternions, by this call's contract: Mesh::update's poses
+    c->frame_lone = LoneFacts{ false, false }; s.lone = 0; s.copy_class = 0;      // matrices the host has not seen: the general entry until the next rtx_set_frame
     return RTX_OK;
 }
 
@@ -1336,6 +1343,7 @@ static PlanInputs gather_plan_inputs(const rtx_ctx * c, uint32_t flags, int view
     in.all_wide = all_meshes_wide(c);
     in.stack = stack_figures(c);
     in.n_cu = c->n_cu; in.pk_blocks_closest = c->pk_blocks_closest; in.pk_blocks_any = c->pk_blocks_any;
+    in.lone = c->frame_lone.lone; in.copy_class = c->frame_lone.copy_class;
     return in;
 }
 

@@ -107,6 +107,10 @@ struct DevScene {
     const rtx_spot_light *        spot_lights;  int32_t spot_light_count;
     const rtx_directional_light * dir_lights;   int32_t dir_light_count;
     int32_t light_count;                // total lights = shadow rays per lit hit
+    // plan_lone_facts (rtx_plan.h) of the frame state, both 0 with RTX_PK_LONE_ENTRY=0 and after rtx_update_instances (the host has not seen those
+    // matrices).  lone: the TLAS is one leaf holding instance 0 alone; copy_class: and its world_inv copies every non-zero component bit for bit.
+    // Read by the packet kernels only (pk_enter, rtx_packet.h)
+    int32_t lone, copy_class;
 };
 
 // One render call (a batch of tiles) works on P = tile_count * 1024 primary slots.  Slots of level d

@@ -140,6 +140,7 @@ RTX_D Pk4Step pk4_step(rtx_gptr nodes4, const int first, const PkRay & ray) {
 #endif
 struct PkWalk {                      // everything a packet walk carries; wave-uniform unless noted
     rtx_cptr tlas, nodes, tris;
+    rtx_cptr nodes4;                                                   // shadow rays: the 4-wide records of the BLAS being walked, or null (DevBlas::pk4_nodes)
     rtx_gptr lane_nodes, lane_nodes4c, lane_tris;                      // the BLAS being walked in the per-lane kernels' layout (per-lane phases)
     int sp, floor_sp, cur_inst, depth;
     int cur_idx, cur_first, cur_cnt;
@@ -1545,11 +1546,94 @@ RTX_D void pk_blas_closest_asm(PkWalk & W, const int stack_size, const int order
     if (err) W.err = 1;
 }
 
+// The mesh of instance `inst` becomes the one being walked: the wave-uniform pointers and ids of a BLAS walk.  Once per instance entered; in a
+// lone scene (DevScene::lone) once per wave, before the packet loop — nothing in a walk of such a scene changes them again.
+template <bool ANY>
+RTX_D void pk_bind_mesh(const DevScene & sc, PkWalk & W, const int inst) {
+    W.cur_blas = rfl(sc.instances[inst].blas_id);
+    const DevBlas & B = sc.blas[W.cur_blas];
+    W.nodes = pk_cptr(B.pk_nodes); W.tris = pk_cptr(B.tri_hot); W.cur_inst = inst;
+    W.lane_nodes = RTX_GPTR(B.nodes); W.lane_tris = RTX_GPTR(B.tri_hot);
+    if (ANY) W.nodes4 = pk_cptr(B.pk4_nodes); else W.lane_nodes4c = RTX_GPTR(B.pk4c_nodes);
+}
+
+// Mesh::trace / Mesh::intersect (Mesh.cpp:17-40): the lanes `pm` of the packet enter instance `inst` with the world-space ray (o, d) — ray into
+// model space, BLAS root test, the NaN-risk check, then the hand-scheduled walk of the instance where there is one.  Written once: pk_walk's
+// iterator branch and the direct entry of a lone scene (k_packet) both come here, with W.sp where the BLAS part of the stack begins.
+//   bound  the instance's mesh is bound to W already (pk_bind_mesh, lone scenes);
+//   copy   W.ray holds (o, d, 1 / d) and the instance's world_inv copies them bit for bit (DevScene::copy_class and no valid lane with a zero
+//          component, rtx_plan.h plan_lone_facts): W.ray is left as it is.
+// Returns false (FAST only) when some lane's inverse direction is not finite and its origin lies on a box plane of the mesh: the caller continues
+// with the reference-form variant from the BLAS root, which W then describes.  Returns true with W.m == 0 after a hand-scheduled walk, or
+// with the root's lanes in W.m for the compiled walk.
+template <bool ANY, bool FAST, bool ASM, bool SPLIT>
+RTX_D bool pk_enter(const DevScene & sc, PkWalk & W, const int lane, const bool ordered, const PkHybrid & H, const int inst, const unsigned long long pm,
+                    const v3 o, const v3 d, const bool bound, const bool copy) {
+    if (!bound) pk_bind_mesh<ANY>(sc, W, inst);
+    v3 co = o, cinv = V3(W.ray.i_xy.x, W.ray.i_xy.y, W.ray.i_zz.x);
+    if (!copy) {
+        const rtx_instance & I = sc.instances[inst];
+        co = xform_pos(I.world_inv, o);
+        const v3 cd = xform_dir(I.world_inv, d);
+        cinv = vrcp(cd);
+        pk_set_ray(W.ray, co, cd, cinv);
+    }
+    const DevBlas & B = sc.blas[W.cur_blas];
+    W.floor_sp = W.sp; W.depth = 0;
+    const float4 na = sld(W.nodes, 0), nb = sld(W.nodes, 1);            // BLAS root (BottomLevelBVH.cpp:360-370)
+    const bool risky = FAST && __ballot(W.valid && !inv_is_finite(cinv) && pk_nan_possible(B, co, cinv)) != 0ull;
+    W.m = (risky ? __ballot(pk_slab<false>(na, nb, W.ray)) : __ballot(pk_slab<FAST>(na, nb, W.ray))) & pm;
+    W.cur_idx = 0; W.cur_first = as_i(nb.z); W.cur_cnt = as_i(nb.w);
+    if (risky) return false;
+    if (ASM && FAST && !ANY && H.closest_asm) {
+        // the shared part of the closest-hit walk of this instance, hand-scheduled; returns with the packet stack back at floor_sp and
+        // m == 0: pk_walk's pop runs the private lanes' phase and returns to world space
+#ifdef RTX_LANE_PROF
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long sw_t0 = __builtin_amdgcn_s_memtime(); const int sw_s0 = W.pk_steps;
+#endif
+#ifdef RTX_PK_SKIPWALK
+        W.m = 0ull;                                          // measurement only: everything but the BLAS walk
+#else
+        pk_blas_closest_asm(W, sc.stack_size, ordered ? 1 : 0, H, PRIM_TRI | inst, H.gthread);
+#endif
+#ifdef RTX_LANE_PROF
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        W.lp[13] = (uint32_t)rfl((int)(W.lp[13] + (uint32_t)(__builtin_amdgcn_s_memtime() - sw_t0))); W.lp[14] = (uint32_t)rfl((int)(W.lp[14] + (uint32_t)(W.pk_steps - sw_s0)));
+        W.lp[15] = (uint32_t)rfl((int)(W.lp[15] + 1u));
+#endif
+    }
+    if (ASM && FAST && ANY) {
+        // the whole BLAS walk, hand-scheduled (returns with m == 0), then the per-lane phase over what it deferred
+        PK_T0();
+        W.psp = 0;
+        if (SPLIT) {                                         // split walk (every mesh has 4-wide records): deferred nodes become items, no per-lane phase here
+#ifdef RTX_PK_SKIPWALK
+            W.m = 0ull;                                      // measurement only: everything but the BLAS walk
+#else
+            pk_blas_any_asm4(W, W.nodes4, H.lane_lds, H.t0, H.t_leaf, H.grow, H.item_cap, H.item_base, W.item_slot);
+#endif
+            PK_T1(1);
+        } else if (W.nodes4) {                               // nested boxes: the 4-wide records
+            pk_blas_any_asm4(W, W.nodes4, H.lane_lds, H.t0, H.t_leaf, H.grow, 0u, 0ull, 0u);
+            PK_T1(1);
+            if (W.alive != 0ull && __ballot(W.psp > 0) != 0ull) { PK_T0(); pk_lane_phase_any4(W, lane, H.lane_lds, H.spill, H.spill_stride, RTX_GPTR(W.nodes4), W.lane_tris); PK_T1(2); }
+        } else {
+            pk_blas_any_asm(W, sc.stack_size, H.lane_lds, H.t0, H.grow);
+            PK_T1(1);
+            if (W.alive != 0ull && __ballot(W.psp > 0) != 0ull) { PK_T0(); pk_lane_phase_any(W, lane, H.stk, H.spill, H.spill_stride, W.lane_nodes, W.lane_tris); PK_T1(2); }
+        }
+    }
+    return true;
+}
+
 // Walks until the packet is finished (returns true) or, FAST only, until an instance is entered in which some lane's inverse
 // direction is not finite (returns false: the caller continues with the reference-form variant; the state is consistent).
 // `world(o, d)` reloads a lane's world-space ray (kept in memory, not in registers).
+// Lone scenes (DevScene::lone): `enter_m` != 0 are the lanes that passed the TLAS root, W.m == 0 and W.ray is the world-space ray the set-up has
+// just made.  The first "pop" is then the entry of instance 0 with those lanes — the iterator entry the TLAS leaf would have pushed, never
+// written to the stack, with the ray taken from W.ray instead of world() — and with `copy` W.ray is not even transformed (pk_enter).
 template <bool ANY, bool PSTAT, bool FAST, bool ASM, bool SPLIT, typename WorldFn>
-RTX_D bool pk_walk(const DevScene & sc, PkWalk & W, const int lane, const bool ordered, const PkHybrid & H, WorldFn && world) {
+RTX_D bool pk_walk(const DevScene & sc, PkWalk & W, const int lane, const bool ordered, const PkHybrid & H, WorldFn && world, unsigned long long enter_m, const bool copy) {
     for (;;) {
         if (W.m != 0ull) {
             if (!ANY && ASM && FAST && W.floor_sp >= 0) {
@@ -1630,24 +1714,28 @@ RTX_D bool pk_walk(const DevScene & sc, PkWalk & W, const int lane, const bool o
         }
         // ---------------- pop ----------------
         PK_T0();
-        if (ANY && W.alive == 0ull) return true;
-        if (W.floor_sp >= 0 && W.sp == W.floor_sp) {            // BottomLevelBVH::trace / intersect returned: back to world space
-            if (!ANY && ASM && FAST && W.pub != W.alive) {       // closest-hit hybrid: the private lanes finish this instance on their own
-                if (W.lane_nodes4c) pk_lane_phase_closest<true>(W, lane, ordered, H, W.lane_nodes, W.lane_nodes4c, W.lane_tris);
-                else pk_lane_phase_closest<false>(W, lane, ordered, H, W.lane_nodes, nullptr, W.lane_tris);
-                W.pub = W.alive;
+        const bool direct = enter_m != 0ull;                    // lone scene, first time here: nothing to pop, the entry is (slot 0, one instance, enter_m)
+        if (!direct) {
+            if (ANY && W.alive == 0ull) return true;
+            if (W.floor_sp >= 0 && W.sp == W.floor_sp) {            // BottomLevelBVH::trace / intersect returned: back to world space
+                if (!ANY && ASM && FAST && W.pub != W.alive) {       // closest-hit hybrid: the private lanes finish this instance on their own
+                    if (W.lane_nodes4c) pk_lane_phase_closest<true>(W, lane, ordered, H, W.lane_nodes, W.lane_nodes4c, W.lane_tris);
+                    else pk_lane_phase_closest<false>(W, lane, ordered, H, W.lane_nodes, nullptr, W.lane_tris);
+                    W.pub = W.alive;
+                }
+                if (W.sp == 0) return true;                         // nothing left in the TLAS: the world-space ray is not needed again
+                W.floor_sp = -1; W.nodes = W.tlas;
+                v3 o, d; world(o, d);
+                pk_set_ray(W.ray, o, d, vrcp(d));                   // finite for every lane of a packet that started FAST
             }
-            if (W.sp == 0) return true;                         // nothing left in the TLAS: the world-space ray is not needed again
-            W.floor_sp = -1; W.nodes = W.tlas;
-            v3 o, d; world(o, d);
-            pk_set_ray(W.ray, o, d, vrcp(d));                   // finite for every lane of a packet that started FAST
+            if (W.sp == 0) return true;
+            W.sp--;
         }
-        if (W.sp == 0) return true;
-        W.sp--;
-        const int ea = __builtin_amdgcn_readlane(W.st_a, W.sp), eb = __builtin_amdgcn_readlane(W.st_b, W.sp);
-        const int edf = __builtin_amdgcn_readlane(W.st_df, W.sp);
-        const unsigned long long em = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane(W.st_mhi, W.sp) << 32) |
-                                      (unsigned long long)(uint32_t)__builtin_amdgcn_readlane(W.st_mlo, W.sp);
+        const int ea = direct ? 0 : __builtin_amdgcn_readlane(W.st_a, W.sp), eb = direct ? 1 : __builtin_amdgcn_readlane(W.st_b, W.sp);
+        const int edf = direct ? PK_FLAG_ITER : __builtin_amdgcn_readlane(W.st_df, W.sp);
+        const unsigned long long em = direct ? enter_m : ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane(W.st_mhi, W.sp) << 32) |
+                                                         (unsigned long long)(uint32_t)__builtin_amdgcn_readlane(W.st_mlo, W.sp);
+        enter_m = 0ull;
         unsigned long long pm = em & W.alive;
         if (!ANY && ASM && FAST && (pm & ~W.pub) != 0ull) {
             // private lanes: the entry goes to their work lists (to be re-tested at its turn unless it is a pretested split entry)
@@ -1659,60 +1747,11 @@ RTX_D bool pk_walk(const DevScene & sc, PkWalk & W, const int lane, const bool o
         if (pm == 0ull) continue;
         if (edf & PK_FLAG_ITER) {
             if (eb > 1) pk_push<ANY>(W, ea + 1, eb - 1, pm, 0, PK_FLAG_ITER);
-            // Mesh::trace / Mesh::intersect (Mesh.cpp:17-40): ray into model space
-            const int inst = rfl(sc.tlas_indices[ea]);
-            const rtx_instance & I = sc.instances[inst];
-            v3 o, d; world(o, d);
-            const v3 co = xform_pos(I.world_inv, o), cd = xform_dir(I.world_inv, d), cinv = vrcp(cd);
-            pk_set_ray(W.ray, co, cd, cinv);
-            W.cur_blas = rfl(I.blas_id);
-            const DevBlas & B = sc.blas[W.cur_blas];
-            W.nodes = pk_cptr(B.pk_nodes); W.tris = pk_cptr(B.tri_hot); W.cur_inst = inst;
-            W.lane_nodes = RTX_GPTR(B.nodes); W.lane_tris = RTX_GPTR(B.tri_hot); if (!ANY) W.lane_nodes4c = RTX_GPTR(B.pk4c_nodes);
-            W.floor_sp = W.sp; W.depth = 0;
-            const float4 na = sld(W.nodes, 0), nb = sld(W.nodes, 1);            // BLAS root (BottomLevelBVH.cpp:360-370)
-            const bool risky = FAST && __ballot(W.valid && !inv_is_finite(cinv) && pk_nan_possible(B, co, cinv)) != 0ull;
-            W.m = (risky ? __ballot(pk_slab<false>(na, nb, W.ray)) : __ballot(pk_slab<FAST>(na, nb, W.ray))) & pm;
-            W.cur_idx = 0; W.cur_first = as_i(nb.z); W.cur_cnt = as_i(nb.w);
-            if (risky) return false;
-            if (ASM && FAST && !ANY && H.closest_asm) {
-                // the shared part of the closest-hit walk of this instance, hand-scheduled; returns with the packet stack back at floor_sp and
-                // m == 0: the pop below runs the private lanes' phase and returns to world space
-#ifdef RTX_LANE_PROF
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long sw_t0 = __builtin_amdgcn_s_memtime(); const int sw_s0 = W.pk_steps;
-#endif
-#ifdef RTX_PK_SKIPWALK
-                W.m = 0ull;                                          // measurement only: everything but the BLAS walk
-#else
-                pk_blas_closest_asm(W, sc.stack_size, ordered ? 1 : 0, H, PRIM_TRI | inst, H.gthread);
-#endif
-#ifdef RTX_LANE_PROF
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                W.lp[13] = (uint32_t)rfl((int)(W.lp[13] + (uint32_t)(__builtin_amdgcn_s_memtime() - sw_t0))); W.lp[14] = (uint32_t)rfl((int)(W.lp[14] + (uint32_t)(W.pk_steps - sw_s0)));
-                W.lp[15] = (uint32_t)rfl((int)(W.lp[15] + 1u));
-#endif
-            }
-            if (ASM && FAST && ANY) {
-                // the whole BLAS walk, hand-scheduled (returns with m == 0), then the per-lane phase over what it deferred
-                PK_T0();
-                W.psp = 0;
-                if (SPLIT) {                                         // split walk (every mesh has 4-wide records): deferred nodes become items, no per-lane phase here
-#ifdef RTX_PK_SKIPWALK
-                    W.m = 0ull;                                      // measurement only: everything but the BLAS walk
-#else
-                    pk_blas_any_asm4(W, pk_cptr(B.pk4_nodes), H.lane_lds, H.t0, H.t_leaf, H.grow, H.item_cap, H.item_base, W.item_slot);
-#endif
-                    PK_T1(1);
-                } else if (B.pk4_nodes) {                            // nested boxes: the 4-wide records
-                    pk_blas_any_asm4(W, pk_cptr(B.pk4_nodes), H.lane_lds, H.t0, H.t_leaf, H.grow, 0u, 0ull, 0u);
-                    PK_T1(1);
-                    if (W.alive != 0ull && __ballot(W.psp > 0) != 0ull) { PK_T0(); pk_lane_phase_any4(W, lane, H.lane_lds, H.spill, H.spill_stride, RTX_GPTR(B.pk4_nodes), RTX_GPTR(B.tri_hot)); PK_T1(2); }
-                } else {
-                    pk_blas_any_asm(W, sc.stack_size, H.lane_lds, H.t0, H.grow);
-                    PK_T1(1);
-                    if (W.alive != 0ull && __ballot(W.psp > 0) != 0ull) { PK_T0(); pk_lane_phase_any(W, lane, H.stk, H.spill, H.spill_stride, RTX_GPTR(B.nodes), RTX_GPTR(B.tri_hot)); PK_T1(2); }
-                }
-            }
+            // a lone scene's direct entry: instance 0, its mesh bound once per wave (k_packet), the ray W.ray holds; else the leaf's slot and the reloaded ray
+            const int inst = direct ? 0 : rfl(sc.tlas_indices[ea]);
+            v3 o = V3(W.ray.o_xy.x, W.ray.o_xy.y, W.ray.o_zz.x), d = W.ray.d;
+            if (!direct) world(o, d);
+            if (!pk_enter<ANY, FAST, ASM, SPLIT>(sc, W, lane, ordered, H, inst, pm, o, d, direct, direct && copy)) return false;
         } else {
             W.m = pm;
             if (!ANY && !(edf & PK_FLAG_PRETESTED)) {
@@ -1781,6 +1820,10 @@ void k_packet(const DevScene sc, const DevQueues q, const int level, const int l
     W.tlas = pk_cptr(sc.pk_tlas_nodes);
     W.err = 0; W.st_pairs = W.st_tris = W.st_pair_lanes = W.st_tri_lanes = 0ull; W.item_n = 0; W.item_slot = 0; W.cur_blas = 0;
     W.st_a = W.st_b = W.st_mlo = W.st_mhi = W.st_idx = W.st_df = 0;
+    W.nodes4 = (rtx_cptr)0;
+    // a lone scene (plan_lone_facts, rtx_plan.h): whatever passes the TLAS root enters instance 0, so its mesh is bound once per wave, not per packet
+    const bool lone = sc.lone != 0;
+    if (lone) pk_bind_mesh<ANY>(sc, W, 0);
     unsigned long long st_packets = 0ull;
     ShadeTally tally = { 0, 0, 0, 0, 0, 0, 0, 0 };               // FUSE: this wave's ray tallies over all its packets
     // Child-ray slots come out of wave-private CHUNKS of the next level's queue: one atomic per RTX_PK_CHUNK slots instead of one per packet
@@ -1902,10 +1945,10 @@ void k_packet(const DevScene sc, const DevQueues q, const int level, const int l
             const v3 winv = vrcp(wd);
             pk_set_ray(W.ray, wo, wd, winv);
             const bool nanfree_world = __ballot(W.valid && !inv_is_finite(winv) && pk_nan_possible_tlas(sc, wo, winv)) == 0ull;
-            W.nodes = W.tlas; W.tris = W.tlas;
-            W.sp = 0; W.floor_sp = -1; W.cur_inst = 0; W.depth = 0; W.cur_idx = 0;
+            if (!lone) { W.nodes = W.tlas; W.tris = W.tlas; W.cur_inst = 0; }
+            W.sp = 0; W.floor_sp = -1; W.depth = 0; W.cur_idx = 0;
             {   // TLAS root: pushed, popped and tested by the reference (TopLevelBVH.cpp:58-67)
-                const float4 na = sld(W.nodes, 0), nb = sld(W.nodes, 1);
+                const float4 na = sld(W.tlas, 0), nb = sld(W.tlas, 1);
                 W.m = (nanfree_world ? __ballot(pk_slab<true>(na, nb, W.ray)) : __ballot(pk_slab<false>(na, nb, W.ray))) & W.alive;
                 W.cur_first = as_i(nb.z); W.cur_cnt = as_i(nb.w);
             }
@@ -1913,9 +1956,19 @@ void k_packet(const DevScene sc, const DevQueues q, const int level, const int l
 #ifdef RTX_PK_PROF
             const unsigned long long pk_w0_ = __builtin_amdgcn_s_memtime();
 #endif
+            // Lone scene: the root is a leaf that holds instance 0 alone, so the lanes that passed its box enter the instance as pk_walk's first
+            // step, with the ray the set-up has just made: no iterator entry pushed and popped, no second derivation of the ray.  With a
+            // world_inv of the copy class the model-space ray IS the world-space ray unless a component is +-0, whose sign the arithmetic
+            // may change and the slab test reads: a packet with such a lane among its valid ones takes the arithmetic (plan_lone_facts, rtx_plan.h).
+            unsigned long long enter_m = 0ull; bool copy = false;
+            if (lone) {
+                enter_m = W.m; W.m = 0ull;
+                const bool has_zero = wo.x == 0.0f || wo.y == 0.0f || wo.z == 0.0f || wd.x == 0.0f || wd.y == 0.0f || wd.z == 0.0f;
+                copy = sc.copy_class != 0 && __ballot(W.valid && has_zero) == 0ull;
+            }
             bool done = false;
-            if (nanfree_world && !done) done = pk_walk<ANY, PSTAT, true, !PSTAT, SPLIT>(sc, W, lane, ordered, H, world);
-            if (!done) pk_walk<ANY, PSTAT, false, false, SPLIT>(sc, W, lane, ordered, H, world);
+            if (nanfree_world && !done) { done = pk_walk<ANY, PSTAT, true, !PSTAT, SPLIT>(sc, W, lane, ordered, H, world, enter_m, copy); enter_m = 0ull; }      // false: entered, and risky
+            if (!done) pk_walk<ANY, PSTAT, false, false, SPLIT>(sc, W, lane, ordered, H, world, enter_m, copy);
 #ifdef RTX_PK_PROF
             {   // slot 4: the longest single packet walk (max), slot 9: walks longer than 2^18 ticks
                 const unsigned long long dt = __builtin_amdgcn_s_memtime() - pk_w0_;

@@ -26,7 +26,36 @@ struct Knobs {
     bool fuse_shade;             // RTX_FUSE_SHADE         the closest-hit packet kernel shades its own hits (0: a k_shade launch per level)
     int update_small_max;        // RTX_UPDATE_SMALL_MAX   rtx_update_instances: scenes up to this many instances take the one-workgroup kernel (0: always the multi-launch path)
     int tex_pass_levels;         // RTX_TEX_PASS_LEVELS    rtx_update_texture: mip levels one launch makes below the level it reads, 1 .. 5 (1: a launch per level)
+    bool lone_entry;             // RTX_PK_LONE_ENTRY      packet kernels enter a lone instance straight from the packet set-up (0: the iterator path for every scene)
 };
+
+// Two facts about a frame's instances and TLAS that let the packet kernels skip work (rtx_packet.h, pk_enter), decided wherever the host
+// writes either:
+//   lone        one instance, and the TLAS root is a leaf of count 1 whose slot names instance 0, so the root is the one node a walk can reach
+//               (reference-built arrays carry an unused slot at index 1, which no walk looks at: the node COUNT is not asked).  Every ray that
+//               passes the root's box enters instance 0 and nothing else, so a packet enters it straight from its set-up (no iterator entry,
+//               no tlas_indices / instances chase);
+//   copy_class  lone, and the top three rows of the instance's world_inv have the bits of 1.0f on the diagonal and +0.0f or -0.0f everywhere
+//               else, the translation column included.  Against xform_pos / xform_dir (rtx_math.h, nothing fused): every other term of a row is
+//               then +-0 for finite inputs, so x' = 1 * x + (+-0) is x bit for bit whenever x != 0; a component that is itself +-0 can come out
+//               with the other sign of zero, and 1 / +-0 = +-inf is a sign the slab test reads.  So a packet none of whose valid lanes has a zero
+//               in o.xyz, d.xyz keeps the world-space ray, and every other packet takes the arithmetic.  Not a memcmp against an identity matrix:
+//               the host inverts `world` by cofactors, and an identity input leaves -0.0f in off-diagonal cells.  lone_check.cpp pins both.
+struct LoneFacts { bool lone, copy_class; };
+static inline LoneFacts plan_lone_facts(int instance_count, const rtx_bvh_node * tlas_nodes, int tlas_node_count, const int32_t * tlas_indices, int tlas_index_count,
+                                        const rtx_instance * instances) {
+    LoneFacts f = { false, false };
+    if (instance_count != 1 || tlas_node_count < 1 || tlas_index_count < 1 || !tlas_nodes || !tlas_indices || !instances) return f;
+    if (tlas_nodes[0].count != 1 || tlas_nodes[0].left_or_first != 0 || tlas_indices[0] != 0) return f;      // count: no axis bits either, a leaf of one
+    f.lone = true;
+    uint32_t bits[12]; memcpy(bits, instances[0].world_inv, sizeof(bits));        // cells[i + 4j]: rows 0 .. 2 are the first twelve
+    f.copy_class = true;
+    for (int k = 0; k < 12; k++) {
+        const bool diagonal = k == 0 || k == 5 || k == 10;
+        if (diagonal ? bits[k] != 0x3f800000u : (bits[k] & 0x7fffffffu) != 0u) f.copy_class = false;
+    }
+    return f;
+}
 
 // What the uploaded trees ask of the packet kernels' one stack (plan_stack_limits): unfit_mesh = some mesh exceeds the packet kernels' packed
 // entries; dt = TLAS levels (inner depth + 1, 0 without a TLAS); blas_any = the deepest mesh's need in the shadow-ray walk (the 4-wide
@@ -49,6 +78,7 @@ struct PlanInputs {
     bool heatmap, can_spawn, all_wide;               // can_spawn: plan_can_spawn of the materials; all_wide: every mesh has 4-wide shadow-ray records
     StackFigures stack;
     int n_cu, pk_blocks_closest, pk_blocks_any;      // the grids
+    bool lone, copy_class;                           // plan_lone_facts of the frame state (false after a device-side update)
 };
 
 enum : int32_t { CLOSEST_PLAIN, CLOSEST_PLAIN_COUNT, CLOSEST_LANE, CLOSEST_PACKET_STATS, CLOSEST_PACKET, CLOSEST_PACKET_FUSED, CLOSEST_PACKET_FUSED_CULL };
@@ -71,6 +101,7 @@ struct RenderPlan {
     int32_t split, item_cap;                         // the split walk is on; the item chunk capacity the call wants (0: none)
     int32_t lpt; uint32_t lpt_n;
     int32_t graph_eligible;
+    int32_t lone, copy_class;                        // what the packet kernels are told of the frame's lone instance (both 0 with RTX_PK_LONE_ENTRY=0)
 };
 
 // Entries the shared closest-hit walk of a packet can have pending (see plan_stack_limits): one far sibling per inner ancestor in both
@@ -152,6 +183,7 @@ static inline RenderPlan plan_render(const PlanInputs & in) {
     RenderPlan p; memset(&p, 0, sizeof(p));
     const Knobs & K = in.knobs;
     p.flags = in.flags; p.views = in.views;
+    p.lone = K.lone_entry && in.lone; p.copy_class = p.lone && in.copy_class;
     const bool count_work = (in.flags & RTX_RENDER_COUNT_WORK) != 0;
     const bool simple = (in.flags & RTX_RENDER_SIMPLE_TRACE) != 0;
     p.cull = (in.flags & RTX_RENDER_CULL_DEAD_SHADOW_RAYS) != 0 && !simple && !count_work;
