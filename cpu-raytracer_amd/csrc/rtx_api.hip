@@ -37,6 +37,7 @@
 #include "rtx_hits.h"
 #include "rtx_sweep.h"
 #include "rtx_overlap.h"
+#include "rtx_capsule.h"
 #include "rtx_boxsweep.h"
 #include "rtx_texmip.h"
 #include <rocprim/device/device_radix_sort.hpp>      // rtx_update_instances, scenes beyond one workgroup: header-only, part of ROCm
@@ -2723,6 +2724,51 @@ extern "C" int rtx_query_overlap(rtx_ctx * c, const void * boxes_dev, int64_t n,
 extern "C" int rtx_query_overlap_filtered(rtx_ctx * c, const void * boxes_dev, int64_t n, int32_t max_hits, int32_t * object_id_dev, int32_t * triangle_id_dev, int32_t * count_dev,
                                           uint32_t flags, const rtx_query_filter * filter) {
     return query_overlap_impl(c, boxes_dev, n, max_hits, object_id_dev, triangle_id_dev, count_dev, flags, filter);
+}
+
+// ---- capsule-overlap queries (include/rtx.h: rtx_query_overlap_capsule; kernel in rtx_capsule.h, arithmetic and walk in rtx_capsule_math.h) --
+// rtx_query_overlap's call over n capsules of seven floats.  The sort key is the ray key over the first six floats (start point, axis), so a
+// ball row (axis 0) sorts with the dead rows, last, and is walked all the same.  The stack uses region 0 of the spill buffer only.
+static int query_overlap_capsule_impl(rtx_ctx * c, const void * capsules_dev, int64_t n, int32_t max_hits, int32_t * object_id_dev, int32_t * triangle_id_dev, int32_t * count_dev,
+                                      uint32_t flags, const rtx_query_filter * filter) {
+    const bool any = (flags & RTX_OVERLAP_ANY) != 0, objects = (flags & RTX_OVERLAP_OBJECTS) != 0;
+    if (c) {
+        const char * bad = nullptr;
+        if (max_hits < 0 || max_hits > (int32_t)RTX_QUERY_MAX_HITS) bad = "max_hits must be in [0, RTX_QUERY_MAX_HITS]";
+        else if (any && (max_hits != 0 || objects)) bad = "RTX_OVERLAP_ANY needs max_hits == 0 and excludes RTX_OVERLAP_OBJECTS";
+        else if (objects && triangle_id_dev) bad = "RTX_OVERLAP_OBJECTS reports no triangle ids: triangle_id_dev must be NULL";
+        else if (max_hits == 0 && !count_dev) bad = "max_hits == 0 is the count-only form (or RTX_OVERLAP_ANY) and needs a count_dev";
+        else if (max_hits > 0 && !object_id_dev && !triangle_id_dev) bad = "max_hits > 0 needs object_id_dev or triangle_id_dev";
+        if (bad) { c->err = std::string("rtx_query_overlap_capsule: ") + bad; return RTX_ERR_INVALID_ARG; }
+    }
+    const void * const some_out = object_id_dev ? (const void *)object_id_dev : triangle_id_dev ? (const void *)triangle_id_dev : (const void *)count_dev;
+    if (int bad = query_checks(c, capsules_dev, n, some_out, flags, "rtx_query_overlap_capsule", (uint32_t)RTX_QUERY_SORT | (uint32_t)RTX_OVERLAP_OBJECTS | (uint32_t)RTX_OVERLAP_ANY)) return bad;
+    WalkCall k;
+    if (int rc = walk_setup(c, "rtx_query_overlap_capsule", "descent", n, flags, filter, k, true)) return rc;
+    const int64_t K = max_hits;
+    return walk_rounds<rtxcp::ROW_FLOATS, rtxcp::KEY_FLOATS>(c, k, capsules_dev, n, [&](int64_t first, const float * rows, int m, int blocks) {
+        int32_t * const count = count_dev ? count_dev + first : nullptr;
+        auto go = [&](auto form, int held, bool triangles) {
+            int32_t * const object_id = held && object_id_dev ? object_id_dev + K * first : nullptr;
+            int32_t * const triangle_id = held && triangles && triangle_id_dev ? triangle_id_dev + K * first : nullptr;
+            walk_launch(c, k, "k_query_overlap_capsule", first, [&](auto km) {
+                hipLaunchKernelGGL((k_query_overlap_capsule<decltype(form)::value, decltype(km)::filtered>), dim3(blocks), dim3(RTX_QUERY_BLOCK), 0, c->stream,
+                                   k.sc, rows, m, held, object_id, triangle_id, count, k.order, k.spill, k.spill_threads, k.head, km);
+            });
+        };
+        if (any) go(std::integral_constant<int, rtxcp::FORM_ANY>(), 0, false);
+        else if (objects && K > 0) go(std::integral_constant<int, rtxcp::FORM_OBJECTS>(), (int)K, false);
+        else if (objects) go(std::integral_constant<int, rtxcp::FORM_OBJECTS | OVERLAP_COUNT_ONLY>(), 0, false);
+        else if (K > 0) go(std::integral_constant<int, rtxcp::FORM_TRIANGLES>(), (int)K, true);
+        else go(std::integral_constant<int, rtxcp::FORM_TRIANGLES | OVERLAP_COUNT_ONLY>(), 0, false);
+    });
+}
+extern "C" int rtx_query_overlap_capsule(rtx_ctx * c, const void * capsules_dev, int64_t n, int32_t max_hits, int32_t * object_id_dev, int32_t * triangle_id_dev, int32_t * count_dev, uint32_t flags) {
+    return query_overlap_capsule_impl(c, capsules_dev, n, max_hits, object_id_dev, triangle_id_dev, count_dev, flags, nullptr);
+}
+extern "C" int rtx_query_overlap_capsule_filtered(rtx_ctx * c, const void * capsules_dev, int64_t n, int32_t max_hits, int32_t * object_id_dev, int32_t * triangle_id_dev, int32_t * count_dev,
+                                                  uint32_t flags, const rtx_query_filter * filter) {
+    return query_overlap_capsule_impl(c, capsules_dev, n, max_hits, object_id_dev, triangle_id_dev, count_dev, flags, filter);
 }
 
 // ---- swept-box queries (include/rtx.h: rtx_query_sweep_box; kernel in rtx_boxsweep.h, arithmetic and walk in rtx_boxsweep_math.h) -------

@@ -93,7 +93,7 @@
 //            at least one of its slots (SPLIT LEAVES above); the count of the exhaustive search, which tests every slot, is then larger.
 // NOT PROMISED  equality with the exhaustive list for a primitive within MARGIN of touching: NODE's comparisons and TRIANGLE's are different
 //            roundings of the same geometry, and a node test may reject a box whose triangle the triangle test accepts at a gap of 0.
-// OUT OF SCOPE  capsules, spheres and convex hulls as query volumes, penetration depth (swept boxes: rtx_boxsweep_math.h), or contact points, more than
+// OUT OF SCOPE  convex hulls as query volumes (capsules and balls: rtx_capsule_math.h), penetration depth (swept boxes: rtx_boxsweep_math.h), or contact points, more than
 //            RTX_QUERY_MAX_HITS entries per row, the rtx_group_* path.
 #pragma once
 #include <stdint.h>

@@ -15,6 +15,7 @@
 #include "../csrc/rtx_side_math.h"
 #include "../csrc/rtx_hits_math.h"
 #include "../csrc/rtx_overlap_math.h"
+#include "../csrc/rtx_capsule_math.h"
 #include "../csrc/rtx_sweep_math.h"
 #include "../csrc/rtx_boxsweep_math.h"
 
@@ -1213,6 +1214,102 @@ extern "C" int rtxh_query_overlap_exhaustive_filtered(const rtxh_nearest_scene *
     return query_overlap_exhaustive_host(scene, boxes, n, max_hits, object_id_out, triangle_id_out, count_out, flags, km);
 }
 extern "C" float rtxh_overlap_margin(float local_scale, float world_scale, float kappa) { return rtxop::margin(local_scale, world_scale, kappa); }
+
+// =================================================================================================
+// rtx_query_overlap_capsule on the host: rtxcp::walk (csrc/rtx_capsule_math.h) over the arrays of rtxh_query_nearest, and the exhaustive
+// search; the stack, the list, the argument rules and the stores are rtx_query_overlap's above
+namespace {
+struct HostCapsuleScene : HostNearestScene {
+    explicit HostCapsuleScene(const rtxh_nearest_scene & sc) : HostNearestScene{ sc } {}
+    int instance_count() const { return s.instance_count; }
+    int enter(int slot, rtxcp::Frame & F) {
+        const int inst = s.tlas_indices[slot];
+        F = rtxcp::local_frame(F, s.instances[inst].world_inv);
+        B = &s.blas[s.instances[inst].blas_id];
+        return inst;
+    }
+};
+template <int FORM, typename Scene>
+void capsule_exhaustive_row(const rtxh_nearest_scene & s, Scene & S, HostOverlapList & L, const float * row, int K, rtxop::Tally & w) {
+    w.count = 0; w.held = 0;
+    if (!rtxcp::row_is_live(row) || !S.row_visible()) return;
+    const rtxcp::Frame W = rtxcp::world_frame(row);
+    if (rtxcp::world_primitives<FORM>(S, L, K, w, W)) return;
+    for (int k = 0; k < s.instance_count; k++) {
+        if (!S.object_visible(k)) continue;
+        const rtxcp::Frame F = rtxcp::local_frame(W, s.instances[k].world_inv);
+        const rtxh_nearest_blas & B = s.blas[s.instances[k].blas_id];
+        for (int t = 0; t < B.triangle_count; t++) {
+            if (!rtxcp::triangle_overlaps(F, rtxnp::ptr3(B.hot[t].position_0), rtxnp::ptr3(B.hot[t].position_edge_1), rtxnp::ptr3(B.hot[t].position_edge_2))) continue;
+            if (FORM == rtxcp::FORM_TRIANGLES) { rtxop::offer(L, K, w, k, t); continue; }
+            rtxop::offer(L, K, w, k, -1);
+            if (FORM == rtxcp::FORM_ANY) return;
+            break;
+        }
+    }
+}
+}  // namespace
+
+static int query_overlap_capsule_host(const rtxh_nearest_scene * scene, const float * capsules, int64_t n, int32_t max_hits, int32_t * object_out, int32_t * triangle_out, int32_t * count_out,
+                                      uint32_t flags, int32_t * stack_max_out, const HostMasks * km) {
+    if (int rc = overlap_args_check(scene, capsules, n, max_hits, object_out, triangle_out, count_out, flags, true)) return rc;
+    if (!scene_rigid(*scene)) return RTX_ERR_STATE;
+    const int form = (flags & RTX_OVERLAP_ANY) ? rtxcp::FORM_ANY : (flags & RTX_OVERLAP_OBJECTS) ? rtxcp::FORM_OBJECTS : rtxcp::FORM_TRIANGLES;
+    int high = 0;
+    for (int64_t i = 0; i < n; i++) {
+        HostOverlapStack st;
+        HostOverlapList L;
+        rtxop::Tally w;
+        const float * row = capsules + rtxcp::ROW_FLOATS * i;
+        auto run = [&](auto & S) {
+            if (form == rtxcp::FORM_ANY) rtxcp::walk<rtxcp::FORM_ANY>(S, st, L, row, 0, w);
+            else if (form == rtxcp::FORM_OBJECTS) rtxcp::walk<rtxcp::FORM_OBJECTS>(S, st, L, row, max_hits, w);
+            else rtxcp::walk<rtxcp::FORM_TRIANGLES>(S, st, L, row, max_hits, w);
+        };
+        if (km) { HostMasked<HostCapsuleScene> S(*scene, km->table, km->of_row(i)); run(S); }
+        else { HostCapsuleScene S(*scene); run(S); }
+        if (st.high > high) high = st.high;
+        overlap_write(L, w, max_hits, i, object_out, triangle_out, count_out);
+    }
+    if (stack_max_out) *stack_max_out = high;
+    return RTX_OK;
+}
+extern "C" int rtxh_query_overlap_capsule(const rtxh_nearest_scene * scene, const float * capsules, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
+                                          int32_t * count_out, uint32_t flags, int32_t * stack_max_out) {
+    return query_overlap_capsule_host(scene, capsules, n, max_hits, object_id_out, triangle_id_out, count_out, flags, stack_max_out, nullptr);
+}
+extern "C" int rtxh_query_overlap_capsule_filtered(const rtxh_nearest_scene * scene, const float * capsules, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
+                                                   int32_t * count_out, uint32_t flags, int32_t * stack_max_out, const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask) {
+    const HostMasks km = { object_masks, row_masks, row_mask };
+    return query_overlap_capsule_host(scene, capsules, n, max_hits, object_id_out, triangle_id_out, count_out, flags, stack_max_out, &km);
+}
+
+static int query_overlap_capsule_exhaustive_host(const rtxh_nearest_scene * scene, const float * capsules, int64_t n, int32_t max_hits, int32_t * object_out, int32_t * triangle_out,
+                                                 int32_t * count_out, uint32_t flags, const HostMasks km) {
+    if (int rc = overlap_args_check(scene, capsules, n, max_hits, object_out, triangle_out, count_out, flags, false)) return rc;
+    const rtxh_nearest_scene & s = *scene;
+    for (int64_t i = 0; i < n; i++) {
+        const float * row = capsules + rtxcp::ROW_FLOATS * i;
+        HostMasked<HostCapsuleScene> S(s, km.table, km.of_row(i));
+        HostOverlapList L;
+        rtxop::Tally w;
+        if (flags & RTX_OVERLAP_ANY) capsule_exhaustive_row<rtxcp::FORM_ANY>(s, S, L, row, 0, w);
+        else if (flags & RTX_OVERLAP_OBJECTS) capsule_exhaustive_row<rtxcp::FORM_OBJECTS>(s, S, L, row, max_hits, w);
+        else capsule_exhaustive_row<rtxcp::FORM_TRIANGLES>(s, S, L, row, max_hits, w);
+        overlap_write(L, w, max_hits, i, object_out, triangle_out, count_out);
+    }
+    return RTX_OK;
+}
+extern "C" int rtxh_query_overlap_capsule_exhaustive(const rtxh_nearest_scene * scene, const float * capsules, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
+                                                     int32_t * count_out, uint32_t flags) {
+    return query_overlap_capsule_exhaustive_host(scene, capsules, n, max_hits, object_id_out, triangle_id_out, count_out, flags, kNoMasks);
+}
+extern "C" int rtxh_query_overlap_capsule_exhaustive_filtered(const rtxh_nearest_scene * scene, const float * capsules, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
+                                                              int32_t * count_out, uint32_t flags, const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask) {
+    const HostMasks km = { object_masks, row_masks, row_mask };
+    return query_overlap_capsule_exhaustive_host(scene, capsules, n, max_hits, object_id_out, triangle_id_out, count_out, flags, km);
+}
+extern "C" float rtxh_capsule_margin(float local_scale, float world_scale, float kappa) { return rtxcp::margin(local_scale, world_scale, kappa); }
 
 // =================================================================================================
 // rtx_query_sweep_box on the host: rtxbs::walk (csrc/rtx_boxsweep_math.h) over the arrays of rtxh_query_nearest, and the exhaustive search

@@ -32,7 +32,8 @@ EXPORTS = ["rtx_abi_version", "rtx_create", "rtx_destroy", "rtx_last_error", "rt
            "rtx_debug_grids", "rtx_set_object_masks", "rtx_update_object_masks", "rtx_read_object_masks",
            "rtx_query_nearest_filtered", "rtx_query_hits_filtered", "rtx_query_sweep_filtered",
            "rtx_blas_pseudonormals", "rtx_read_blas_pseudonormals", "rtx_query_signed_distance",
-           "rtx_query_overlap", "rtx_query_overlap_filtered", "rtx_query_sweep_box", "rtx_query_sweep_box_filtered"]
+           "rtx_query_overlap", "rtx_query_overlap_filtered", "rtx_query_sweep_box", "rtx_query_sweep_box_filtered",
+           "rtx_query_overlap_capsule", "rtx_query_overlap_capsule_filtered"]
 # newer than the A/B variants tools/ab.py may load (RTX_HIP_LIB = a library built from an older commit): bound when the library has them,
 # otherwise a call raises AttributeError (undefined symbol)
 VIEW_EXPORTS = ("rtx_set_views", "rtx_render_views", "rtx_read_views", "rtx_bind_view_framebuffer")
@@ -55,7 +56,8 @@ MASK_EXPORTS = ("rtx_set_object_masks", "rtx_update_object_masks", "rtx_read_obj
                 "rtx_query_nearest_filtered", "rtx_query_hits_filtered", "rtx_query_sweep_filtered")
 OVERLAP_EXPORTS = ("rtx_query_overlap", "rtx_query_overlap_filtered")
 SWEEP_BOX_EXPORTS = ("rtx_query_sweep_box", "rtx_query_sweep_box_filtered")
-OPTIONAL_EXPORTS = (SWEEP_BOX_EXPORTS + OVERLAP_EXPORTS + VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + QUERY_SORT_EXPORTS + LAYOUT_EXPORTS
+OVERLAP_CAPSULE_EXPORTS = ("rtx_query_overlap_capsule", "rtx_query_overlap_capsule_filtered")
+OPTIONAL_EXPORTS = (OVERLAP_CAPSULE_EXPORTS + SWEEP_BOX_EXPORTS + OVERLAP_EXPORTS + VIEW_EXPORTS + AOV_EXPORTS + RAY_EXPORTS + UPDATE_EXPORTS + REFIT_EXPORTS + QUERY_EXPORTS + QUERY_SORT_EXPORTS + LAYOUT_EXPORTS
                     + TEXTURE_EXPORTS + NORMALS_EXPORTS + NEAREST_EXPORTS + HITS_EXPORTS + SWEEP_EXPORTS + GRID_EXPORTS + MASK_EXPORTS + SIGNED_EXPORTS)
 RTX_QUERY_MAX_HITS = 8
 # texel formats of rtx_update_texture (include/rtx.h RTX_TEXELS_*)
@@ -216,6 +218,9 @@ def load_library(path: Optional[str] = None):
     if hasattr(lib, "rtx_query_overlap"):
         lib.rtx_query_overlap.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp, u32]
         lib.rtx_query_overlap_filtered.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp, u32, C.POINTER(RtxQueryFilter)]
+    if hasattr(lib, "rtx_query_overlap_capsule"):
+        lib.rtx_query_overlap_capsule.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp, u32]
+        lib.rtx_query_overlap_capsule_filtered.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp, u32, C.POINTER(RtxQueryFilter)]
     if hasattr(lib, "rtx_query_sweep_box"):
         lib.rtx_query_sweep_box.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, u32]
         lib.rtx_query_sweep_box_filtered.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, u32, C.POINTER(RtxQueryFilter)]
@@ -408,6 +413,27 @@ def grid_boxes(origin, cell, shape, device=None):
     rows[..., 3:6] = (0.5 * c).astype(np.float32)
     rows[..., 9] = 1.0
     rows = rows.reshape(-1, 10)
+    if device is None:
+        return rows
+    import torch
+    return torch.from_numpy(rows).to(device)
+
+
+def capsule_rows(a, b, radius, device=None):
+    """The query_overlap_capsule rows of capsules given by their end points: float32 (n, 7) of (p = a, d = b - a, r = radius).  a, b = (n, 3)
+    (or (3,)), radius = a number or (n,); b == a makes a ball.  d is rounded once, from the float32 end points.  device=None: a numpy array;
+    otherwise a torch tensor on that device."""
+    pa = np.atleast_2d(np.asarray(a, np.float32))
+    pb = np.atleast_2d(np.asarray(b, np.float32))
+    if pa.ndim != 2 or pa.shape[1] != 3 or pa.shape != pb.shape:
+        raise ValueError(f"a and b must both have shape (n, 3), not {pa.shape} and {pb.shape}")
+    r = np.asarray(radius, np.float32).reshape(-1)
+    if r.size not in (1, pa.shape[0]):
+        raise ValueError(f"radius must be one number or have shape ({pa.shape[0]},), not {np.shape(radius)}")
+    rows = np.zeros((pa.shape[0], 7), np.float32)
+    rows[:, 0:3] = pa
+    rows[:, 3:6] = pb - pa
+    rows[:, 6] = r
     if device is None:
         return rows
     import torch
@@ -1334,7 +1360,7 @@ class Renderer:
         than the maximum distance, a non-finite coordinate, a maximum distance that is NaN or not above 0): distance inf, ids -1, the rest 0;
         +inf is a legal maximum distance.  Distances are measured in each instance's local space, so the frame's instances must be rigid poses
         (a scaled, sheared or flattened matrix: RtxError, RTX_ERR_STATE — on every length query: this one, query_signed_distance, query_sweep,
-        query_overlap, query_overlapped, query_sweep_box; query_hits, query_closest and query_occluded take any finite matrix).  Queued on torch's current stream, checked
+        query_overlap, query_overlapped, query_overlap_capsule, query_overlapped_capsule, query_sweep_box; query_hits, query_closest and query_occluded take any finite matrix).  Queued on torch's current stream, checked
         and shaped like query_closest; sort=True (RTX_QUERY_SORT) walks the points of every round in Morton order, same answers row for row.
         Raw device pointers: points = address, n, out = {name: address} for every channel wanted.
         mask (here, on query_hits and on query_sweep): None = this call; an int = the row mask of every row; an int32 tensor (n,) on this
@@ -1505,9 +1531,11 @@ class Renderer:
             launch()
         return {name: out[name] for name in wanted}
 
-    def _query_overlap(self, boxes, K: int, count: bool, flags: int, out: Optional[Dict], n: Optional[int], sort: bool, mask, wanted: tuple) -> Dict:
-        """query_overlap and query_overlapped: rows of 10 floats in, the int32 tensors named in `wanted` out."""
-        ptr, n, box_t = self._query_rows("boxes", boxes, 10, n)
+    def _query_overlap(self, boxes, K: int, count: bool, flags: int, out: Optional[Dict], n: Optional[int], sort: bool, mask, wanted: tuple,
+                       rows: str = "boxes", width: int = 10, call: str = "rtx_query_overlap") -> Dict:
+        """query_overlap and query_overlapped (and their capsule forms: rows, width, call): rows of `width` floats in, the int32 tensors named
+        in `wanted` out."""
+        ptr, n, box_t = self._query_rows(rows, boxes, width, n)
         if out is not None and not isinstance(out, dict):
             raise TypeError(f"out must be a dict {{name: tensor}}, not {type(out).__name__}")
         out = dict(out or {})
@@ -1520,7 +1548,7 @@ class Renderer:
         fl = flags | (RTX_QUERY_SORT if sort else 0)
         filt, mask_t = self._query_filter(mask, n)
         ptrs = {name: self._query_out(name, t, np.int32, n, 1, raw, 0 if name == "count" else K) for name, t in out.items()}
-        self._query_on_device({k: t for k, t in [("boxes", box_t)] + [(f"out[{k!r}]", t) for k, t in out.items()] if hasattr(t, "device")})
+        self._query_on_device({k: t for k, t in [(rows, box_t)] + [(f"out[{k!r}]", t) for k, t in out.items()] if hasattr(t, "device")})
         for name in wanted:
             if name not in out:
                 import torch
@@ -1530,9 +1558,9 @@ class Renderer:
         def launch():
             args = (self.ctx, ptr, n, K, ptrs.get("object_id"), ptrs.get("triangle_id"), ptrs.get("count"), fl)
             if filt is None:
-                self._chk(self.lib.rtx_query_overlap(*args), "rtx_query_overlap")
+                self._chk(getattr(self.lib, call)(*args), call)
             else:
-                self._chk(self.lib.rtx_query_overlap_filtered(*args, C.byref(filt)), "rtx_query_overlap_filtered")
+                self._chk(getattr(self.lib, call + "_filtered")(*args, C.byref(filt)), call + "_filtered")
         tensors = [t for t in [box_t, mask_t] + list(out.values()) if hasattr(t, "record_stream")]
         if tensors:
             self._on_torch_stream(launch, tensors)
@@ -1570,6 +1598,34 @@ class Renderer:
         if out is None and isinstance(boxes, (int, np.integer)) and not isinstance(boxes, bool):
             raise ValueError("with raw device pointers out must be the address of the result")
         return self._query_overlap(boxes, 0, True, RTX_OVERLAP_ANY, None if out is None else {"count": out}, n, sort, mask, ("count",))["count"]
+
+    def query_overlap_capsule(self, capsules, max_hits: int = 4, count: bool = True, objects: bool = False, out: Optional[Dict] = None, n: Optional[int] = None,
+                              sort: bool = False, mask=None) -> Dict:
+        """What n capsules touch in the frame the context holds (rtx_query_overlap_capsule): capsules = float32 torch tensor (n, 7) of (start
+        point p, axis vector d, radius r) on this context's GPU — every point within r of the segment p + s d, s in [0, 1]; d = 0 is a ball
+        (every primitive within r of p), r = 0 a segment; capsule_rows() makes the rows from end points.  The outputs, max_hits, count,
+        objects, out, raw pointers, mask and checks are query_overlap's.  A triangle overlaps when its distance to the segment is <= r
+        (touching counts), a sphere when its shell meets the capsule, a plane when the capsule reaches it; a dead row (a non-finite float, a
+        negative radius) overlaps nothing.  sort=True (RTX_QUERY_SORT): the rows are walked in the order of the ray key over (p, d), same
+        answers row for row; ball rows have no ray key and are walked last."""
+        if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)):
+            raise TypeError(f"max_hits must be an int, not {type(max_hits).__name__}")
+        K = int(max_hits)
+        if not 0 <= K <= RTX_QUERY_MAX_HITS:
+            raise ValueError(f"max_hits must be in [0, {RTX_QUERY_MAX_HITS}], not {K}")
+        if K == 0 and not count:
+            raise ValueError("max_hits=0 is the count-only form: count must be True")
+        wanted = (("object_id",) + (() if objects else ("triangle_id",)) if K else ()) + (("count",) if count else ())
+        return self._query_overlap(capsules, K, bool(count), RTX_OVERLAP_OBJECTS if objects else 0, out, n, sort, mask, wanted,
+                                   "capsules", 7, "rtx_query_overlap_capsule")
+
+    def query_overlapped_capsule(self, capsules, out=None, n: Optional[int] = None, sort: bool = False, mask=None):
+        """Whether each of n capsules touches anything (rtx_query_overlap_capsule with RTX_OVERLAP_ANY): the int32 tensor (n,) of 1 / 0 (out,
+        or a new one); a row's walk ends at its first overlap.  capsules, sort, mask, raw pointers and checks as for query_overlap_capsule."""
+        if out is None and isinstance(capsules, (int, np.integer)) and not isinstance(capsules, bool):
+            raise ValueError("with raw device pointers out must be the address of the result")
+        return self._query_overlap(capsules, 0, True, RTX_OVERLAP_ANY, None if out is None else {"count": out}, n, sort, mask, ("count",),
+                                   "capsules", 7, "rtx_query_overlap_capsule")["count"]
 
     # the outputs of query_sweep_box, in the order of rtx_query_sweep_box's arguments: name -> (dtype, width)
     SWEEP_BOX_OUTPUTS = {"distance": (np.float32, 1), "normal": (np.float32, 3), "object_id": (np.int32, 1), "triangle_id": (np.int32, 1), "axis": (np.int32, 1)}

@@ -29,8 +29,9 @@ EXPORTS = ["rtxh_camera_basis", "rtxh_camera_update", "rtxh_quaternion_axis_angl
            "rtxh_query_nearest_filtered", "rtxh_query_nearest_exhaustive_filtered", "rtxh_query_hits_filtered", "rtxh_query_hits_exhaustive_filtered",
            "rtxh_query_sweep_filtered", "rtxh_query_sweep_exhaustive_filtered", "rtxh_blas_pseudonormals",
            "rtxh_query_signed_distance", "rtxh_query_signed_distance_filtered", "rtxh_query_signed_distance_exhaustive", "rtxh_query_signed_distance_exhaustive_filtered",
-           "rtxh_query_overlap", "rtxh_query_overlap_exhaustive", "rtxh_query_overlap_filtered", "rtxh_query_overlap_exhaustive_filtered", "rtxh_overlap_margin", "rtxh_instances_rigid"]
-FLOAT_EXPORTS = ("rtxh_nearest_distance_bound", "rtxh_nearest_box_d2", "rtxh_nearest_triangle_d2", "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2", "rtxh_hits_margin", "rtxh_sweep_bound", "rtxh_overlap_margin", "rtxh_sweep_box_bound")      # return a float, not a status
+           "rtxh_query_overlap", "rtxh_query_overlap_exhaustive", "rtxh_query_overlap_filtered", "rtxh_query_overlap_exhaustive_filtered", "rtxh_overlap_margin", "rtxh_instances_rigid",
+           "rtxh_query_overlap_capsule", "rtxh_query_overlap_capsule_exhaustive", "rtxh_query_overlap_capsule_filtered", "rtxh_query_overlap_capsule_exhaustive_filtered", "rtxh_capsule_margin"]
+FLOAT_EXPORTS = ("rtxh_nearest_distance_bound", "rtxh_nearest_box_d2", "rtxh_nearest_triangle_d2", "rtxh_nearest_sphere_d2", "rtxh_nearest_plane_d2", "rtxh_hits_margin", "rtxh_sweep_bound", "rtxh_overlap_margin", "rtxh_sweep_box_bound", "rtxh_capsule_margin")      # return a float, not a status
 
 PI = np.float32(3.14159265359)          # Util.h:8
 
@@ -146,6 +147,11 @@ def lib():
         l.rtxh_query_overlap_filtered.argtypes = l.rtxh_query_overlap.argtypes + masks3
         l.rtxh_query_overlap_exhaustive_filtered.argtypes = l.rtxh_query_overlap_exhaustive.argtypes + masks3
         l.rtxh_overlap_margin.argtypes = [C.c_float, C.c_float, C.c_float]
+        l.rtxh_query_overlap_capsule.argtypes = l.rtxh_query_overlap.argtypes
+        l.rtxh_query_overlap_capsule_exhaustive.argtypes = l.rtxh_query_overlap_exhaustive.argtypes
+        l.rtxh_query_overlap_capsule_filtered.argtypes = l.rtxh_query_overlap_filtered.argtypes
+        l.rtxh_query_overlap_capsule_exhaustive_filtered.argtypes = l.rtxh_query_overlap_exhaustive_filtered.argtypes
+        l.rtxh_capsule_margin.argtypes = [C.c_float, C.c_float, C.c_float]
         l.rtxh_sweep_bound.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float]
         l.rtxh_sweep_triangle.argtypes = [vp, vp, C.c_float, C.c_float, vp, vp, vp, vp]
         l.rtxh_sweep_sphere.argtypes = [vp, vp, C.c_float, vp, vp, vp]
@@ -830,12 +836,12 @@ RTX_OVERLAP_OBJECTS = 512
 RTX_OVERLAP_ANY = 1024
 
 
-def _query_overlap(scene, boxes, max_hits, count, objects, any_form, blas, exhaustive, mask, object_masks):
+def _query_overlap(scene, boxes, max_hits, count, objects, any_form, blas, exhaustive, mask, object_masks, rows="boxes", width=10, call="rtxh_query_overlap"):
     bx = np.asarray(boxes)
-    if bx.ndim != 2 or bx.shape[1] != 10 or bx.shape[0] < 1:
-        raise ValueError(f"boxes must have shape (n, 10) with n >= 1, not {bx.shape}")
+    if bx.ndim != 2 or bx.shape[1] != width or bx.shape[0] < 1:
+        raise ValueError(f"{rows} must have shape (n, {width}) with n >= 1, not {bx.shape}")
     if bx.dtype != np.float32:
-        raise TypeError(f"boxes must be float32, not {bx.dtype}")
+        raise TypeError(f"{rows} must be float32, not {bx.dtype}")
     bx = np.ascontiguousarray(bx)
     if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)):
         raise TypeError(f"max_hits must be an int, not {type(max_hits).__name__}")
@@ -857,7 +863,7 @@ def _query_overlap(scene, boxes, max_hits, count, objects, any_form, blas, exhau
     filt = _filter_args(s, n, mask, object_masks)
     ptr = lambda name: out[name].ctypes.data if name in out else None
     args = [C.byref(s), bx.ctypes.data, n, K, ptr("object_id"), ptr("triangle_id"), cnt.ctypes.data if count else None, flags] + ([] if exhaustive else [C.byref(high)])
-    fn_name = "rtxh_query_overlap_exhaustive" if exhaustive else "rtxh_query_overlap"
+    fn_name = call + "_exhaustive" if exhaustive else call
     if filt:
         fn_name += "_filtered"
         args += filt[0]
@@ -888,6 +894,24 @@ def overlap_margin(local_scale, world_scale=0.0, kappa=1.0) -> float:
     """rtxop::margin of csrc/rtx_overlap_math.h: how far, as a distance, the computed triangle test may be from the exact one on an axis of
     conditioning kappa."""
     return float(lib().rtxh_overlap_margin(C.c_float(float(local_scale)), C.c_float(float(world_scale)), C.c_float(float(kappa))))
+
+
+# ---- capsule-overlap queries on the host (include/rtx_host.h: rtxh_query_overlap_capsule / rtxh_query_overlap_capsule_exhaustive) ---------
+def query_overlap_capsule(scene, capsules, max_hits=4, count=True, objects=False, blas=None, exhaustive=False, mask=None, object_masks=None) -> dict:
+    """rtxh_query_overlap_capsule: what Renderer.query_overlap_capsule writes on the device for capsules float32 (n, 7) of (start point, axis
+    vector, radius), from the same code (csrc/rtx_capsule_math.h); the result and the arguments are query_overlap's."""
+    return _query_overlap(scene, capsules, max_hits, count, bool(objects), False, blas, bool(exhaustive), mask, object_masks, "capsules", 7, "rtxh_query_overlap_capsule")
+
+
+def query_overlapped_capsule(scene, capsules, blas=None, exhaustive=False, mask=None, object_masks=None) -> np.ndarray:
+    """The ANY form (RTX_OVERLAP_ANY): int32 (n,) of 0 / 1, what Renderer.query_overlapped_capsule writes."""
+    return _query_overlap(scene, capsules, 0, True, False, True, blas, bool(exhaustive), mask, object_masks, "capsules", 7, "rtxh_query_overlap_capsule")["count"]
+
+
+def capsule_margin(local_scale, world_scale=0.0, kappa=1.0) -> float:
+    """rtxcp::margin of csrc/rtx_capsule_math.h: how far, as a distance, the computed triangle test may be from the exact one for a sub-test
+    of conditioning kappa."""
+    return float(lib().rtxh_capsule_margin(C.c_float(float(local_scale)), C.c_float(float(world_scale)), C.c_float(float(kappa))))
 
 
 def sweep_bound(local_scale, world_scale=0.0, travelled=0.0, radius=0.0) -> float:

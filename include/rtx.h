@@ -776,7 +776,7 @@ int rtx_debug_query_order(rtx_ctx * ctx, const void * rows_dev, int32_t row_floa
  * Limits: distances are measured in each instance's LOCAL space, and the walk prunes by WORLD-space box distances: the two agree only for
  * rigid poses.  The rigid rule: rtx_set_frame judges every instance it is handed — rigid iff, for the linear parts R of both world and
  * world_inv, every |(R.R^T - I)ij| <= 2^-12, in fp64 (a reflection passes; rtxh_instances_rigid in rtx_host.h is the same code) — and a frame
- * with a scaled, sheared or flattened instance is refused by this call, by rtx_query_signed_distance, rtx_query_sweep, rtx_query_overlap and
+ * with a scaled, sheared or flattened instance is refused by this call, by rtx_query_signed_distance, rtx_query_sweep, rtx_query_overlap, rtx_query_overlap_capsule and
  * rtx_query_sweep_box and by their _filtered forms (before this rule such a frame lost answers: the walk pruned a scaled instance by a
  * bound in its local units).  rtx_query_hits, rtx_query_closest, rtx_query_occluded and the render calls take any finite matrix: t does not
  * change under an affine map.  After rtx_update_instances the frame counts as rigid, by that call's unit-quaternion contract.  For the
@@ -968,7 +968,7 @@ int rtx_query_signed_distance(rtx_ctx * ctx, const void * points_dev /* [n][4] f
  * with RTX_OVERLAP_OBJECTS; RTX_OVERLAP_OBJECTS with a triangle_id_dev; max_hits == 0 without a count_dev; max_hits > 0 without an id array;
  * a NULL boxes_dev, n < 1; any flag but RTX_QUERY_SORT, RTX_OVERLAP_OBJECTS, RTX_OVERLAP_ANY.  Then RTX_ERR_STATE and RTX_ERR_LIMIT as for
  * rtx_query_nearest, its rigid rule and its stack rule included, and the state rule of the filtered queries.  An error queues nothing.
- * Out of scope: capsules, spheres and convex hulls as query volumes, penetration depth (a swept box is rtx_query_sweep_box), or contact points, more than
+ * Out of scope: convex hulls as query volumes (capsules and balls: rtx_query_overlap_capsule), penetration depth (a swept box is rtx_query_sweep_box), or contact points, more than
  * RTX_QUERY_MAX_HITS entries per row, the rtx_group_* path.                                                                              */
 enum { RTX_OVERLAP_OBJECTS = 512, RTX_OVERLAP_ANY = 1024 };      /* bits of rtx_query_overlap's flags, beside RTX_QUERY_SORT */
 int rtx_query_overlap(rtx_ctx * ctx, const void * boxes_dev /* [n][10] f32: centre, half extents, quaternion */, int64_t n, int32_t max_hits,
@@ -976,6 +976,29 @@ int rtx_query_overlap(rtx_ctx * ctx, const void * boxes_dev /* [n][10] f32: cent
                       int32_t * count_dev /* [n] or NULL */, uint32_t flags /* RTX_QUERY_SORT, RTX_OVERLAP_OBJECTS, RTX_OVERLAP_ANY or 0 */);
 int rtx_query_overlap_filtered(rtx_ctx * ctx, const void * boxes_dev, int64_t n, int32_t max_hits, int32_t * object_id_dev, int32_t * triangle_id_dev,
                                int32_t * count_dev, uint32_t flags, const rtx_query_filter * filter);
+
+/* ---- capsule-overlap queries ------------------------------------------------------------------------------------------------------------
+ * "What does this capsule or ball touch": a character, a robot link or a finger with a capsule proxy, a cable or cloth edge with a
+ * thickness, a particle with a radius (every primitive within r of a point: the within-radius gather).
+ * rtx_query_overlap_capsule: row i = capsules_dev[7i .. 7i+6] = (start point p, axis vector d, radius r), fp32 at any 4-byte aligned
+ * address in DEVICE memory: the capsule is every point within r of the segment p + s d, s in [0, 1] — the first seven floats of a
+ * rtx_query_sweep row with d = direction * D.  A row is live when all seven floats are finite and r >= 0; d == 0 is a ball, r == 0 a
+ * segment, both a point; a dead row overlaps nothing.  A triangle overlaps iff its distance to the segment is <= r (touching is
+ * overlapping), a sphere when its shell meets the capsule (a capsule strictly inside the ball does not overlap), a plane when the capsule
+ * reaches it.  Everything is specified in the header comment of csrc/rtx_capsule_math.h (ROW, FRAME, TRIANGLE, SPHERE, PLANE, NODE, ORDER,
+ * WALK, FORMS, FILTER, MARGIN, PROMISED); rtxh_query_overlap_capsule in rtx_host.h gives the same bits.
+ * The forms, flags, outputs, max_hits rules and rounds are those of rtx_query_overlap.  RTX_QUERY_SORT: the rows of a round are walked in
+ * the order of the ray key of rtx_query_closest over (p, d); a ball row (d == 0) has no ray key: it sorts with the dead rows, last, and is
+ * walked all the same.  The call runs on the context's stream; nothing is read back, frames, render calls and rtx_get_stats are unchanged.
+ * rtx_query_overlap_capsule_filtered: the same with the object masks of the filtered queries above; a NULL filter is the unfiltered call.
+ * Errors: those of rtx_query_overlap in its order (capsules_dev for boxes_dev), its rigid rule and its stack rule included.
+ * Out of scope: swept capsules, a contact point or penetration depth, a position sort key for ball-only batches, more than
+ * RTX_QUERY_MAX_HITS entries per row, the rtx_group_* path.                                                                              */
+int rtx_query_overlap_capsule(rtx_ctx * ctx, const void * capsules_dev /* [n][7] f32: p, d, r */, int64_t n, int32_t max_hits,
+                              int32_t * object_id_dev /* [n][max_hits] or NULL */, int32_t * triangle_id_dev /* [n][max_hits] or NULL */,
+                              int32_t * count_dev /* [n] or NULL */, uint32_t flags /* RTX_QUERY_SORT, RTX_OVERLAP_OBJECTS, RTX_OVERLAP_ANY or 0 */);
+int rtx_query_overlap_capsule_filtered(rtx_ctx * ctx, const void * capsules_dev, int64_t n, int32_t max_hits, int32_t * object_id_dev, int32_t * triangle_id_dev,
+                                       int32_t * count_dev, uint32_t flags, const rtx_query_filter * filter);
 
 /* ---- swept-box queries ------------------------------------------------------------------------------------------------------------------
  * "How far can this oriented box travel along this direction before it touches something, what does it touch, and with which face or edge":

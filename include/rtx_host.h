@@ -221,7 +221,7 @@ int rtxh_query_sort_order(const float * rows, int32_t row_floats, int64_t n, int
  * for an instance whose matrix is not the identity, else 0).
  * RTX_ERR_INVALID_ARG: a null scene / points / out, n < 1, channels 0 or outside RTX_QUERY_ALL, a negative count, a count without its
  * array, an instance whose blas_id is outside [0, blas_count); RTX_ERR_LIMIT: a tree deeper than RTX_MAX_STACK entries of the walk; then
- * RTX_ERR_STATE, from the walks of the length queries only (rtxh_query_nearest, _signed_distance, _sweep, _overlap, _sweep_box and their
+ * RTX_ERR_STATE, from the walks of the length queries only (rtxh_query_nearest, _signed_distance, _sweep, _overlap, _overlap_capsule, _sweep_box and their
  * _filtered forms): an instance that rtxh_instances_rigid does not accept, as on the device (include/rtx.h, rtx_query_nearest: Limits).
  * The exhaustive searches prune nothing and answer for any matrix, in local units; so does rtxh_query_hits.                               */
 typedef struct rtxh_nearest_blas {
@@ -298,6 +298,20 @@ int rtxh_query_overlap_filtered(const rtxh_nearest_scene * scene, const float * 
 int rtxh_query_overlap_exhaustive_filtered(const rtxh_nearest_scene * scene, const float * boxes, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
                                            int32_t * count_out, uint32_t flags, const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask);
 float rtxh_overlap_margin(float local_scale, float world_scale, float kappa);
+
+/* rtx_query_overlap_capsule (include/rtx.h) on the host, by the code the kernel runs (csrc/rtx_capsule_math.h, whose header comment is the
+ * specification).  As rtxh_query_overlap and its three siblings above, over capsules: n x 7 floats (start point, axis vector, radius); the
+ * answers are the device's bit for bit.  rtxh_capsule_margin(S, W, kappa): rtxcp::margin, how far as a distance the computed triangle test
+ * may be from the exact one for a sub-test of conditioning kappa (MARGIN in that header).  The error codes are rtxh_query_overlap's. */
+int rtxh_query_overlap_capsule(const rtxh_nearest_scene * scene, const float * capsules, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
+                               int32_t * count_out, uint32_t flags, int32_t * stack_max_out);
+int rtxh_query_overlap_capsule_exhaustive(const rtxh_nearest_scene * scene, const float * capsules, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
+                                          int32_t * count_out, uint32_t flags);
+int rtxh_query_overlap_capsule_filtered(const rtxh_nearest_scene * scene, const float * capsules, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
+                                        int32_t * count_out, uint32_t flags, int32_t * stack_max_out, const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask);
+int rtxh_query_overlap_capsule_exhaustive_filtered(const rtxh_nearest_scene * scene, const float * capsules, int64_t n, int32_t max_hits, int32_t * object_id_out, int32_t * triangle_id_out,
+                                                   int32_t * count_out, uint32_t flags, const uint32_t * object_masks, const uint32_t * row_masks, uint32_t row_mask);
+float rtxh_capsule_margin(float local_scale, float world_scale, float kappa);
 
 /* rtx_query_sweep_box (include/rtx.h) on the host, by the code the kernel runs (csrc/rtx_boxsweep_math.h, whose header comment is the
  * specification: candidate functions, the order rule, the walk and its slack, the accuracy bound).  The scene is rtxh_nearest_scene; sweeps:
